@@ -148,6 +148,18 @@ def verify_sample(wl, rec_raw, scans_per_step, n_distinct, n_check):
     return compared
 
 
+def dump_records(out_dir, rec_raw):
+    """--dump-outputs: the csm_result records one step returned, one float64 array
+    per field, one entry per scan, as out_dir/<field>.npy. Every field converts
+    exactly (key = 32268 K + 499 S stays far below 2^53)."""
+    import numpy as np
+    from csm_hip import _lib as L
+    rec = np.frombuffer(rec_raw, dtype=np.dtype(L.Result))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in rec.dtype.names:
+        np.save(os.path.join(out_dir, name + ".npy"), rec[name].astype(np.float64))
+
+
 def cpu_baseline(wl, budget_s=10.0, max_scans=2000):
     """The CPU oracle (literal ScanMatcherCorrelative sweep with pruning) on the
     first scans of the same workload: one core (the reference is
@@ -882,6 +894,8 @@ def run_csm_workload(args, rank, world, dev, dev_index, rehearse, stream):
             step()
         fence()
         dt = time.perf_counter() - t0
+        # the timing pass and the exact-only run below write into `results` again
+        last_step = results.cpu().numpy().tobytes() if args.dump_outputs else None
         ctx.enable_kernel_timing(False)
         fine_ms, fine_n = ctx.kernel_time("score_fine")
         bound_ms, bound_n = ctx.kernel_time("score_bound")      # the packed-fp32 bound pass of the fine level
@@ -896,6 +910,8 @@ def run_csm_workload(args, rank, world, dev, dev_index, rehearse, stream):
     for name in ("score_coarse", "bin", "finalize"):
         ms, n = ctx.kernel_time(name)
         others[name] = ms / max(1, n) * 1e3
+    if last_step is not None and rank == 0:
+        dump_records(args.dump_outputs, last_step)
 
     # the same workload through the exact integer kernel alone (no bound pass): reported beside the headline
     exact_only = None
@@ -1079,6 +1095,19 @@ def run_side_workload(args, dev_index, which):
         "roofline": roof}), flush=True)
 
 
+def build_or_load():
+    """build() where this user may write the build directory (file-locked: ranks take turns, later
+    ones find it built). A tree built beforehand and read-only to this user cannot take the lock:
+    the library built there is loaded as it is, and a missing one is an error."""
+    import __graft_entry__ as ge
+    lock = os.path.join(ge.CSRC, ".build.lock")
+    if os.access(ge.CSRC, os.W_OK) and (not os.path.exists(lock) or os.access(lock, os.W_OK)):
+        ge.build()
+    else:
+        from csm_hip import _lib
+        _lib.load()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1098,7 +1127,16 @@ def main():
                          "(replicas). loop: configs[2], 256 candidate submaps per GPU. loop4: configs[3], 2048 "
                          "submaps sharded over the ranks (strong scaling) + all-gather. map: the frontend "
                          "cycle (latest-map build from 10 scans + match), not the BASELINE metric")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="csm workload: write the records of the last timed step (rank 0) as DIR/<field>.npy, "
+                         "float64, one entry per scan; the inputs are seeded, so runs with the same arguments "
+                         "can be compared output for output")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    runs_csm = args.workload == "csm" or (args.workload == "auto" and args.gpus == 1)
+    if args.dump_outputs and not runs_csm:
+        ap.error("--dump-outputs is implemented for the csm workload (the default at --gpus 1)")
 
     import torch
     import torch.distributed as dist
@@ -1121,8 +1159,7 @@ def main():
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
-    import __graft_entry__ as ge
-    ge.build()          # file-locked: ranks take turns, later ones find it built
+    build_or_load()
 
     workload = args.workload
     if workload == "auto":

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -36,10 +37,17 @@ def _check_roofline(r):
     assert abs(r["logical_hbm_frac"] - r["logical_hbm_gbs"] / 8000.0) < 1e-9
 
 
-def test_default_line():
-    d = _run("--steps", "2", "--warmup", "1",
+def test_default_line(tmp_path):
+    dump = tmp_path / "dump"
+    d = _run("--steps", "2", "--warmup", "1", "--dump-outputs", str(dump),
              env={"CSM_BENCH_SCANS": "256", "CSM_BENCH_DISTINCT": "128", "CSM_BENCH_WINDOWS": "64",
                   "CSM_BENCH_CONFIGS": "config2_single_query,config3,config5"})
+    fields = {"found", "best_x", "best_y", "best_theta", "key", "sum_values", "known", "tie_count", "flags", "score"}
+    assert {p.name for p in dump.iterdir()} == {f + ".npy" for f in fields}
+    rec = {f: np.load(dump / (f + ".npy")) for f in fields}
+    for a in rec.values():
+        assert a.dtype == np.float64 and a.shape == (256,)
+    assert rec["found"].sum() == d["config"]["poses_found"] and (rec["score"] > 0).all()
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
