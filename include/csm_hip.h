@@ -446,6 +446,91 @@ int  csm_cost_covariance_batch(csm_ctx* ctx, const csm_loop_query* queries, int3
 int  csm_linear_solver_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
                              const csm_refine_params* params, csm_refine_result* out);
 
+/* ---- the other cost type and the hill-climbing matcher ----
+ * CostGreedyEndpoint (inc/mapping/cost_function_greedy_endpoint.hpp;
+ * src/mapping/cost_function_greedy_endpoint.cpp: Cost, ComputeGradient,
+ * ComputeCovariance) and ScanMatcherHillClimbing::OptimizePose
+ * (src/mapping/scan_matcher_hill_climbing.cpp:72-180), the "GreedyEndpoint" /
+ * "HillClimbing" keys of src/cost_function_factory.cpp:11-30 and
+ * src/scan_matcher_factory.cpp:103-130.
+ *
+ * EXACT (bit-identical, unlike the square-error tolerance above): per beam the
+ * cost depends only on the integer cells of the hit and missed points
+ * (ScanData::HitAndMissedPoint, inc/sensor/sensor_data.hpp:252-273) and on a
+ * table lookup; map reads are ProbabilityOr(row, col, 0.0), so "outside the
+ * map", "unallocated block" and "unknown cell" all read 0 and are skipped (no
+ * allocation bitmap is needed). Every result equals the reference's
+ * arithmetic bit for bit: the sums are the literal beam-order double sums
+ * whenever a comparison is not decided with margin by a bounded approximation
+ * (DESIGN.md 4d), and a query any of whose hit or missed coordinates lies too
+ * close to a cell edge for the device's sin / cos to be trusted is finished by
+ * the host restatement below (result.host_path = 1). */
+#define CSM_TUNE_GREEDY_LITERAL_SUMS 4096u  /* every hill-climbing decision from the literal sums */
+
+#define CSM_GREEDY_KERNEL_SIZE_MAX 8     /* KernelSize 0..8 */
+
+/* CostGreedyEndpoint constructor arguments (cost_function_factory.cpp:17-22) */
+typedef struct {
+    double  map_resolution;       /* "MapResolution": the cost table's cell size (not the grid's) */
+    double  hit_and_missed_dist;  /* "HitAndMissedDist" */
+    double  occupancy_threshold;  /* "OccupancyThreshold" */
+    int32_t kernel_size;          /* "KernelSize", 0..CSM_GREEDY_KERNEL_SIZE_MAX */
+    int32_t reserved;
+    double  standard_deviation;   /* "StandardDeviation" (> 0) */
+    double  scaling_factor;       /* "ScalingFactor" */
+} csm_greedy_params;
+
+/* ScanMatcherHillClimbing constructor arguments (scan_matcher_factory.cpp:113-116) */
+typedef struct {
+    double            linear_step;      /* "LinearStep" (> 0) */
+    double            angular_step;     /* "AngularStep" (> 0) */
+    int32_t           max_iterations;   /* "MaxIterations" (>= 1) */
+    int32_t           max_refinements;  /* "MaxNumOfRefinements" */
+    csm_greedy_params cost;             /* "CostConfigGroup" */
+} csm_hill_climbing_params;
+
+typedef struct {
+    double  normalized_initial_cost;   /* Cost(start) / n_points: the InitialCost metric */
+    double  normalized_cost;           /* Cost(best) / n_points: ScanMatchingSummary::mNormalizedCost */
+    double  sensor_pose[3];            /* Compound(initial, relative sensor pose) */
+    double  best_sensor_pose[3];
+    double  estimated_pose[3];         /* MoveBackward(best sensor pose, relative sensor pose) */
+    double  covariance[9];             /* row-major, map-local: mEstimatedCovariance */
+    double  diff_translation;          /* metrics: Distance(initial, estimated) */
+    double  diff_rotation;             /*          |initial.theta - estimated.theta| */
+    int32_t iterations;                /* NumOfIterations */
+    int32_t refinements;               /* NumOfRefinements */
+    int32_t replays;                   /* passes whose decisions took the literal sums */
+    int32_t host_path;                 /* 1: finished by the host restatement */
+    int64_t cost_evaluations;          /* Cost() calls, covariance included */
+} csm_hill_climbing_result;
+
+/* CostGreedyEndpoint::Cost / n and ComputeCovariance at sensor_poses[i] (3
+ * doubles per query: the search's best sensor pose), scan and map of
+ * queries[i] (initial_pose is not read): the GreedyEndpoint counterpart of
+ * csm_cost_covariance_batch. out[i]: normalized_initial_cost ==
+ * normalized_cost, sensor_pose == best_sensor_pose == sensor_poses[i],
+ * estimated_pose, covariance; iterations = refinements = 0. */
+int  csm_greedy_cost_covariance_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
+                                      const double* sensor_poses, const csm_greedy_params* params,
+                                      csm_hill_climbing_result* out);
+/* ScanMatcherHillClimbing::OptimizePose for every query: queries[i].initial_pose
+ * is the map-local ROBOT pose (as in csm_linear_solver_batch). One launch chain
+ * for the whole batch; n_queries = 1 is the frontend's call. */
+int  csm_hill_climbing_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
+                             const csm_hill_climbing_params* params, csm_hill_climbing_result* out);
+/* Host restatements (pure CPU, glibc): the fallback of the two entries above and
+ * the CPU-testable reference for the device. grid: dense rows x cols raw cells
+ * (row-major, as csm_upload_grid takes them). csm_host_greedy_cost: *cost =
+ * Cost() (ScalingFactor applied, not normalized); covariance (may be NULL) =
+ * ComputeCovariance() at the same pose. */
+int  csm_host_greedy_cost(const uint16_t* grid, int32_t rows, int32_t cols, const csm_geometry* geom,
+                          const csm_scan* scan, const double sensor_pose[3],
+                          const csm_greedy_params* params, double* cost, double* covariance);
+int  csm_host_hill_climbing(const uint16_t* grid, int32_t rows, int32_t cols, const csm_geometry* geom,
+                            const csm_scan* scan, const double initial_pose[3],
+                            const csm_hill_climbing_params* params, csm_hill_climbing_result* out);
+
 /* ---- several GPUs behind one detector object, in one process ----
  * The reference's precedent is LoopDetectorFPGAParallel
  * (src/mapping/loop_detector_fpga_parallel.cpp:42-56): Detect() cuts the query

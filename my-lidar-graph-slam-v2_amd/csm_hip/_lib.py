@@ -38,6 +38,8 @@ TUNE_NO_LANE_MAP, TUNE_NO_XCD_MAP, TUNE_NO_PAIR_TAIL, TUNE_NO_TWO_SLICES = 1, 2,
 TUNE_NO_THETA_MAJOR, TUNE_NO_TILE_SPLIT, TUNE_MAP_HOST_PROJECTION, TUNE_NO_JOINT = 16, 32, 64, 128
 TUNE_NO_BOUND_PASS = 256
 TUNE_NO_TWO_PHASE, TUNE_FORCE_TWO_PHASE, TUNE_NO_GRAPHS = 512, 1024, 2048
+TUNE_GREEDY_LITERAL_SUMS = 4096
+GREEDY_KERNEL_SIZE_MAX = 8
 GROUP_FORCE_RCCL = 1
 
 
@@ -133,6 +135,26 @@ class RefineResult(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class GreedyParams(C.Structure):
+    _fields_ = [("map_resolution", C.c_double), ("hit_and_missed_dist", C.c_double),
+                ("occupancy_threshold", C.c_double), ("kernel_size", C.c_int32), ("reserved", C.c_int32),
+                ("standard_deviation", C.c_double), ("scaling_factor", C.c_double)]
+
+
+class HillClimbingParams(C.Structure):
+    _fields_ = [("linear_step", C.c_double), ("angular_step", C.c_double),
+                ("max_iterations", C.c_int32), ("max_refinements", C.c_int32), ("cost", GreedyParams)]
+
+
+class HillClimbingResult(C.Structure):
+    _fields_ = [("normalized_initial_cost", C.c_double), ("normalized_cost", C.c_double),
+                ("sensor_pose", C.c_double * 3), ("best_sensor_pose", C.c_double * 3),
+                ("estimated_pose", C.c_double * 3), ("covariance", C.c_double * 9),
+                ("diff_translation", C.c_double), ("diff_rotation", C.c_double),
+                ("iterations", C.c_int32), ("refinements", C.c_int32), ("replays", C.c_int32),
+                ("host_path", C.c_int32), ("cost_evaluations", C.c_int64)]
+
+
 class LoopQuery(C.Structure):
     _fields_ = [("map_id", C.c_uint64), ("geometry", Geometry), ("scan", Scan),
                 ("initial_pose", C.c_double * 3)]
@@ -209,6 +231,14 @@ SIGNATURES = {
     "csm_cost_covariance_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, C.c_void_p, C.c_double,
                                             _P(RefineResult)]),
     "csm_linear_solver_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(RefineParams), _P(RefineResult)]),
+    "csm_greedy_cost_covariance_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, C.c_void_p, _P(GreedyParams),
+                                                   _P(HillClimbingResult)]),
+    "csm_hill_climbing_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(HillClimbingParams),
+                                          _P(HillClimbingResult)]),
+    "csm_host_greedy_cost": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(Geometry), _P(Scan), C.c_void_p,
+                                       _P(GreedyParams), _P(C.c_double), C.c_void_p]),
+    "csm_host_hill_climbing": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(Geometry), _P(Scan), C.c_void_p,
+                                         _P(HillClimbingParams), _P(HillClimbingResult)]),
     "csm_shard_bounds": (None, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "csm_group_create": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
     "csm_group_create_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, _P(C.c_void_p)]),

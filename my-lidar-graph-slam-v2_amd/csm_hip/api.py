@@ -149,6 +149,58 @@ def host_project(geom, sensor_pose, step_theta, win_theta, angles, ranges, want_
     return (col, row, rc_, rs_) if want_products else (col, row)
 
 
+def greedy_params(map_resolution=0.05, hit_and_missed_dist=0.075, occupancy_threshold=0.1, kernel_size=1,
+                  standard_deviation=0.05, scaling_factor=1.0):
+    """csm_greedy_params; defaults as launcher_settings_default.json "CostGreedyEndpoint"."""
+    return L.GreedyParams(map_resolution, hit_and_missed_dist, occupancy_threshold, kernel_size, 0,
+                          standard_deviation, scaling_factor)
+
+
+def hill_climbing_params(linear_step=0.1, angular_step=0.1, max_iterations=100, max_refinements=5, greedy=None):
+    g = greedy if isinstance(greedy, L.GreedyParams) else greedy_params(**(greedy or {}))
+    return L.HillClimbingParams(linear_step, angular_step, max_iterations, max_refinements, g)
+
+
+def _scan_struct(angles, ranges, rel_pose):
+    a, r = _f64(angles), _f64(ranges)
+    sc = L.Scan()
+    sc.angles = a.ctypes.data_as(C.POINTER(C.c_double))
+    sc.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
+    sc.n_points = a.size
+    sc.relative_sensor_pose[:] = list(rel_pose)
+    return sc, (a, r)
+
+
+def host_greedy_cost(grid, geom, angles, ranges, sensor_pose, greedy=None, covariance=False):
+    """csm_host_greedy_cost: Cost() (ScalingFactor applied, not normalized), and
+    ComputeCovariance() if asked."""
+    g = np.ascontiguousarray(grid, dtype=np.uint16)
+    sc, keep = _scan_struct(angles, ranges, (0.0, 0.0, 0.0))
+    p = greedy if isinstance(greedy, L.GreedyParams) else greedy_params(**(greedy or {}))
+    cost = C.c_double()
+    cov = np.zeros(9)
+    rc = L.load().csm_host_greedy_cost(_ptr(g), g.shape[0], g.shape[1], C.byref(L.Geometry(*geom)),
+                                       C.byref(sc), _ptr(_f64(sensor_pose)), C.byref(p), C.byref(cost),
+                                       _ptr(cov) if covariance else None)
+    if rc:
+        raise CsmError(rc, "csm_host_greedy_cost")
+    return (cost.value, cov.reshape(3, 3)) if covariance else cost.value
+
+
+def host_hill_climbing(grid, geom, angles, ranges, rel_pose, init_pose, linear_step=0.1, angular_step=0.1,
+                       max_iterations=100, max_refinements=5, greedy=None):
+    """csm_host_hill_climbing: the library's host restatement of OptimizePose."""
+    g = np.ascontiguousarray(grid, dtype=np.uint16)
+    sc, keep = _scan_struct(angles, ranges, rel_pose)
+    p = hill_climbing_params(linear_step, angular_step, max_iterations, max_refinements, greedy)
+    out = L.HillClimbingResult()
+    rc = L.load().csm_host_hill_climbing(_ptr(g), g.shape[0], g.shape[1], C.byref(L.Geometry(*geom)),
+                                         C.byref(sc), _ptr(_f64(init_pose)), C.byref(p), C.byref(out))
+    if rc:
+        raise CsmError(rc, "csm_host_hill_climbing")
+    return Context._hill_to_dict(out)
+
+
 def host_probability_lut():
     lut = np.zeros(65536)
     L.load().csm_host_probability_lut(_ptr(lut))
@@ -496,6 +548,36 @@ class Context:
         self._check(self.lib.csm_linear_solver_batch(self._ctx, prep.arr, prep.n, C.byref(p), out))
         return [self._refine_to_dict(o) for o in out]
 
+    @staticmethod
+    def _hill_to_dict(r):
+        return dict(normalized_initial_cost=r.normalized_initial_cost, normalized_cost=r.normalized_cost,
+                    sensor_pose=list(r.sensor_pose), best_sensor_pose=list(r.best_sensor_pose),
+                    estimated_pose=list(r.estimated_pose), covariance=np.array(r.covariance).reshape(3, 3),
+                    diff_translation=r.diff_translation, diff_rotation=r.diff_rotation,
+                    iterations=r.iterations, refinements=r.refinements, replays=r.replays,
+                    host_path=r.host_path, cost_evaluations=int(r.cost_evaluations))
+
+    def greedy_cost_covariance_batch(self, queries, sensor_poses, greedy=None, as_records=False):
+        """CostGreedyEndpoint::Cost / n and ComputeCovariance at the given sensor poses.
+        greedy: greedy_params(...) or a dict of its keyword arguments (default settings if None)."""
+        prep = self.prepare_queries(queries)
+        sp = _f64(sensor_poses).reshape(prep.n, 3)
+        p = greedy_params(**(greedy or {})) if not isinstance(greedy, L.GreedyParams) else greedy
+        out = (L.HillClimbingResult * prep.n)()
+        self._check(self.lib.csm_greedy_cost_covariance_batch(self._ctx, prep.arr, prep.n, _ptr(sp),
+                                                              C.byref(p), out))
+        return out if as_records else [self._hill_to_dict(o) for o in out]
+
+    def hill_climbing_batch(self, queries, linear_step=0.1, angular_step=0.1, max_iterations=100,
+                            max_refinements=5, greedy=None, as_records=False):
+        """ScanMatcherHillClimbing::OptimizePose per query (init_pose = map-local robot pose);
+        defaults as launcher_settings_default.json "ScanMatcherHillClimbing" / "CostGreedyEndpoint"."""
+        prep = self.prepare_queries(queries)
+        p = hill_climbing_params(linear_step, angular_step, max_iterations, max_refinements, greedy)
+        out = (L.HillClimbingResult * prep.n)()
+        self._check(self.lib.csm_hill_climbing_batch(self._ctx, prep.arr, prep.n, C.byref(p), out))
+        return out if as_records else [self._hill_to_dict(o) for o in out]
+
     def enable_kernel_timing(self, on=True):
         self._check(self.lib.csm_enable_kernel_timing(self._ctx, 1 if on else 0))
 
@@ -651,4 +733,31 @@ class ScanMatcherGridSearchHIP:
                                          known_rate_threshold)
         if map_id is None:
             self.ctx.release_grid(mid)
+        return out
+
+
+class ScanMatcherHillClimbingHIP:
+    """Drop-in for ScanMatcherHillClimbing with the GreedyEndpoint cost (constructor
+    arguments as in src/my_lidar_graph_slam/scan_matcher_factory.cpp:103-130; `greedy`
+    holds the CostConfigGroup's keys as greedy_params() keyword arguments)."""
+
+    def __init__(self, name, linear_step, angular_step, max_iterations, max_refinements, greedy=None, ctx=None):
+        self.name = name
+        self.params = hill_climbing_params(linear_step, angular_step, max_iterations, max_refinements, greedy)
+        self.ctx = ctx or Context()
+        self._nonce = (1 << 62) + 2
+
+    def optimize_pose(self, grid, geom, angles, ranges, rel_pose, init_pose, map_id=None):
+        """ScanMatchingSummary fields plus the matcher's metrics; grid may be None when
+        map_id is resident; a throw-away latest map gets a nonce id."""
+        mid = self._nonce if map_id is None else map_id
+        if grid is not None and (map_id is None or not self.ctx.has_grid(mid)):
+            self.ctx.upload_grid(mid, grid)
+        q = dict(map_id=mid, geom=geom, angles=angles, ranges=ranges, rel_pose=rel_pose, init_pose=init_pose)
+        p = self.params
+        out = self.ctx.hill_climbing_batch([q], p.linear_step, p.angular_step, p.max_iterations,
+                                           p.max_refinements, p.cost)[0]
+        if map_id is None:
+            self.ctx.release_grid(mid)
+        out["pose_found"] = 1          # OptimizePose always finds a pose
         return out

@@ -80,6 +80,7 @@ int csm_create(const csm_config* cfg, csm_ctx** out)
         t.graphs = !(off & CSM_TUNE_NO_GRAPHS);
         t.tile_split = !(off & CSM_TUNE_NO_TILE_SPLIT);
         t.map_host_projection = (off & CSM_TUNE_MAP_HOST_PROJECTION) != 0;
+        t.greedy_literal = (off & CSM_TUNE_GREEDY_LITERAL_SUMS) != 0;
         if (off & CSM_TUNE_NO_THETA_MAJOR)
             t.theta_major = 0;
         t.map_unc_cap = cfg ? cfg->map_uncertain_cap : 0;
@@ -146,7 +147,8 @@ int csm_destroy(csm_ctx* ctx)
                        &ctx->b_ntiles, &ctx->b_lvl, &ctx->b_best, &ctx->b_jobs, &ctx->b_out, &ctx->b_abest, &ctx->bound_stats, &ctx->b_items, &ctx->tp_items, &ctx->ph_hits, &ctx->q_dev,
                        &ctx->fine_s, &ctx->fine_k, &ctx->tie, &ctx->ex_fine, &ctx->ex_fine_k, &ctx->ex_coarse, &ctx->ex_coarse_k,
                        &ctx->scan_dev, &ctx->unc, &ctx->sorted_rc, &ctx->b_sorted_rc, &ctx->rec_dev, &ctx->c_scans, &ctx->c_jobs, &ctx->box_jobs,
-                       &ctx->m_rays, &ctx->m_recs, &ctx->m_cell, &ctx->m_lists, &ctx->m_cnt, &ctx->m_lut };
+                       &ctx->m_rays, &ctx->m_recs, &ctx->m_cell, &ctx->m_lists, &ctx->m_cnt, &ctx->m_lut,
+                       &ctx->g_scans, &ctx->g_jobs, &ctx->g_scratch, &ctx->g_tab };
     for (DevBuf* b : bufs)
         if (b->p)
             (void)hipFree(b->p);

@@ -112,6 +112,7 @@ struct Tuning {
     bool graphs = true;        /* repeated single-query launch chains replayed as HIP graphs */
     bool tile_split = true;    /* small single windows: tile list split over blockIdx.z */
     bool map_host_projection = false;   /* map building: hit points on the host */
+    bool greedy_literal = false;        /* hill climbing: every decision from the literal sums */
     int  theta_major = -1;     /* -1: by launch size */
     int  fine_slices = 0, force_r = 0, pair_r = 0, pair_ncbx = 0, pair_groups = 0, pair_ls = 0,
          pair_tail_ls = 0, nbuf = 0, map_unc_cap = 0;
@@ -153,6 +154,9 @@ struct csm_ctx {
     std::vector<csm::BoxJob> box_stage;
     std::vector<double> c_stage;
     std::vector<csm::CostJob> c_job_stage;
+    /* greedy-endpoint / hill-climbing batches (csm_greedy_api.hip): scans, job table + outputs,
+     * rank scratch of scans too long for LDS, the cost tables */
+    DevBuf g_scans, g_jobs, g_scratch, g_tab;
     /* the final records of the last batch call in query order (csm_copy_last_batch_records) */
     DevBuf rec_dev;
     int rec_n = 0;

@@ -170,6 +170,22 @@ inline void FillSummary(const csm_summary& s, const RobotPose2D<double>& initial
     out->mNumOfCandidates = s.candidates;
     out->mFlags = s.raw.flags;
 }
+/* CostGreedyEndpoint::Cost / n and ComputeCovariance at the best sensor pose on the device
+ * (scan_matcher_correlative.cpp:209-219 with a "GreedyEndpoint" cost) */
+inline void DeviceGreedyCost(csm_ctx* ctx, std::uint64_t id, const csm_geometry& geom, const csm_scan& scan,
+                             const double bestSensorPose[3], const csm_greedy_params& prm,
+                             ScanMatchingSummary* out)
+{
+    csm_loop_query cq {};
+    cq.map_id = id;
+    cq.geometry = geom;
+    cq.scan = scan;
+    csm_hill_climbing_result r {};
+    CSM_ASSERT_OK(ctx, csm_greedy_cost_covariance_batch(ctx, &cq, 1, bestSensorPose, &prm, &r));
+    out->mNormalizedCost = r.normalized_cost;
+    for (int c = 0; c < 9; ++c)
+        out->mEstimatedCovariance[c] = r.covariance[c];
+}
 } /* namespace detail */
 
 /* The 15 value sequences a matcher registers with the MetricManager and observes
@@ -283,6 +299,8 @@ public:
             out.mNormalizedCost = rr.normalized_cost;
             for (int c = 0; c < 9; ++c)
                 out.mEstimatedCovariance[c] = rr.covariance[c];
+        } else if (this->mUseDeviceGreedy) {
+            detail::DeviceGreedyCost(ctx, id, geom, scan, s.best_sensor_pose, this->mGreedy, &out);
         }
         if (temporary && g.mValues)
             CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
@@ -292,6 +310,13 @@ public:
     /* Cost and covariance from the device's CostSquareError instead of a host callback
      * ("CovarianceScale", launcher_settings_default.json:11-13). */
     void UseDeviceCostFunction(double covarianceScale = 1e4) { this->mDeviceCovarianceScale = covarianceScale; }
+    /* ... or from the device's CostGreedyEndpoint (CostType "GreedyEndpoint", bit-exact) */
+    void UseDeviceGreedyCostFunction(const csm_greedy_params& params)
+    {
+        this->mGreedy = params;
+        this->mUseDeviceGreedy = true;
+        this->mDeviceCovarianceScale = 0.0;
+    }
 
 private:
     ScanMatcherCorrelativeHIP(const std::string& name, int lowResolution, double rangeX,
@@ -307,6 +332,8 @@ private:
     detail::CtxPtr mCtx;
     detail::RevisionMap mRevisions;
     double mDeviceCovarianceScale = 0.0;
+    bool mUseDeviceGreedy = false;
+    csm_greedy_params mGreedy {};
 };
 
 /* ScanMatcherGridSearch (inc/mapping/scan_matcher_grid_search.hpp,
@@ -366,13 +393,23 @@ public:
                                  q.mMapLocalInitialPose.mTheta };
         csm_summary s {};
         CSM_ASSERT_OK(ctx, csm_grid_search_match(ctx, id, &geom, &scan, init, &prm, &s));
-        if (temporary)
-            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
         ScanMatchingSummary out;
         detail::FillSummary(s, q.mMapLocalInitialPose, &out);
+        if (!this->mCostFunc && this->mUseDeviceGreedy)
+            detail::DeviceGreedyCost(ctx, id, geom, scan, s.best_sensor_pose, this->mGreedy, &out);
+        if (temporary)
+            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
         if (this->mCostFunc)
             this->mCostFunc(q, out.mBestSensorPose, &out.mNormalizedCost, out.mEstimatedCovariance);
         return out;
+    }
+
+    /* Cost and covariance from the device's CostGreedyEndpoint (the default cost of
+     * LoopDetectorGridSearch, launcher_settings_default.json:80) instead of a host callback */
+    void UseDeviceGreedyCostFunction(const csm_greedy_params& params)
+    {
+        this->mGreedy = params;
+        this->mUseDeviceGreedy = true;
     }
 
 private:
@@ -388,6 +425,92 @@ private:
     const CostCallback mCostFunc;
     detail::CtxPtr mCtx;
     detail::RevisionMap mRevisions;
+    bool mUseDeviceGreedy = false;
+    csm_greedy_params mGreedy {};
+};
+
+/* ScanMatcherHillClimbing with the GreedyEndpoint cost
+ * (inc/mapping/scan_matcher_hill_climbing.hpp, src/mapping/scan_matcher_hill_climbing.cpp:72-180;
+ * factory src/scan_matcher_factory.cpp:103-130): the whole search, the cost and the covariance on
+ * the device, bit-exact. LastResult() holds the metric inputs of the last call (NumOfIterations,
+ * NumOfRefinements, InitialCost, FinalCost, DiffTranslation, DiffRotation). */
+class ScanMatcherHillClimbingHIP final {
+public:
+    static std::unique_ptr<ScanMatcherHillClimbingHIP> Create(
+        const std::string& scanMatcherName, double linearStep, double angularStep, int maxIterations,
+        int maxNumOfRefinements, const csm_greedy_params& costParams, int deviceId = 0)
+    {
+        if (!(linearStep > 0.0) || !(angularStep > 0.0) || maxIterations < 1)
+            return nullptr;
+        detail::CtxPtr ctx = detail::MakeContext(deviceId);
+        if (!ctx)
+            return nullptr;
+        csm_hill_climbing_params prm {};
+        prm.linear_step = linearStep;
+        prm.angular_step = angularStep;
+        prm.max_iterations = maxIterations;
+        prm.max_refinements = maxNumOfRefinements;
+        prm.cost = costParams;
+        return std::unique_ptr<ScanMatcherHillClimbingHIP>(
+            new ScanMatcherHillClimbingHIP(scanMatcherName, prm, std::move(ctx)));
+    }
+
+    ScanMatcherHillClimbingHIP(const ScanMatcherHillClimbingHIP&) = delete;
+    ScanMatcherHillClimbingHIP& operator=(const ScanMatcherHillClimbingHIP&) = delete;
+
+    const std::string& Name() const { return this->mName; }
+    csm_ctx* Context() const { return this->mCtx.get(); }
+    const csm_hill_climbing_result& LastResult() const { return this->mLast; }
+
+    ScanMatchingSummary OptimizePose(const ScanMatchingQuery& q)
+    {
+        csm_ctx* ctx = this->mCtx.get();
+        const GridMapView& g = q.mGridMap;
+        const bool temporary = g.mId == GridMapView::kInvalidId;
+        if (!temporary && g.mId >= GridMapView::kReservedIds) {
+            std::fprintf(stderr, "Assertion failed: map id below 2^62 at %s:%d\n", __FILE__, __LINE__);
+            std::abort();
+        }
+        const std::uint64_t id = temporary ? GridMapView::kReservedIds + 2 : g.mId;
+        auto held = this->mRevisions.find(id);
+        if (g.mValues && (temporary || !csm_has_grid(ctx, id) || held == this->mRevisions.end() ||
+                          held->second != g.mRevision)) {
+            CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, id, g.mValues, g.mRows, g.mCols));
+            this->mRevisions[id] = g.mRevision;
+        }
+        csm_loop_query cq {};
+        cq.map_id = id;
+        cq.geometry = { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
+        cq.scan = detail::ToScan(q.mScanData);
+        cq.initial_pose[0] = q.mMapLocalInitialPose.mX;
+        cq.initial_pose[1] = q.mMapLocalInitialPose.mY;
+        cq.initial_pose[2] = q.mMapLocalInitialPose.mTheta;
+        CSM_ASSERT_OK(ctx, csm_hill_climbing_batch(ctx, &cq, 1, &this->mParams, &this->mLast));
+        if (temporary && g.mValues)
+            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
+        const csm_hill_climbing_result& r = this->mLast;
+        ScanMatchingSummary out;
+        out.mPoseFound = true;      /* scan_matcher_hill_climbing.cpp:176-179 */
+        out.mNormalizedCost = r.normalized_cost;
+        out.mMapLocalInitialPose = q.mMapLocalInitialPose;
+        out.mEstimatedPose = { r.estimated_pose[0], r.estimated_pose[1], r.estimated_pose[2] };
+        out.mBestSensorPose = { r.best_sensor_pose[0], r.best_sensor_pose[1], r.best_sensor_pose[2] };
+        for (int c = 0; c < 9; ++c)
+            out.mEstimatedCovariance[c] = r.covariance[c];
+        out.mNumOfCandidates = r.cost_evaluations;
+        return out;
+    }
+
+private:
+    ScanMatcherHillClimbingHIP(const std::string& name, const csm_hill_climbing_params& prm,
+                               detail::CtxPtr ctx) :
+        mName(name), mParams(prm), mCtx(std::move(ctx)) { }
+
+    const std::string mName;
+    const csm_hill_climbing_params mParams;
+    detail::CtxPtr mCtx;
+    detail::RevisionMap mRevisions;
+    csm_hill_climbing_result mLast {};
 };
 
 /* inc/mapping/loop_detector.hpp:27-55, flattened to what the search reads:
