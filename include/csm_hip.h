@@ -308,7 +308,8 @@ int  csm_score_windows_dump_dev(csm_ctx* ctx, int32_t n, const uint64_t* map_ids
                                 const int32_t* const* hit_row_dev, csm_result* out_dev,
                                 uint32_t* const* dump_s_dev, uint16_t* const* dump_k_dev,
                                 float* const* dump_f_dev);
-/* What the last single-window search (csm_correlative_match) evaluated. Large windows are searched
+/* What the last single-window search (csm_correlative_match) evaluated, and whether its launch chain
+ * was a replay of a recorded HIP graph (graph_replayed). Large windows are searched
  * coarse-first (scan_matcher_correlative.cpp:176-192 is the reference's pruning): every
  * coarse node is scored, then the fine level only on the candidate blocks that hold an eligible
  * coarse node reaching the best fine score found under the best coarse node. SURVEY 8(d) asks for
@@ -318,7 +319,7 @@ typedef struct {
     int64_t coarse_nodes_scored;       /* 0: exhaustive search, no coarse pass needed */
     int64_t fine_candidates_scored;    /* candidates of the fine blocks scored (whole blocks) */
     int32_t two_phase;                 /* 1: coarse-first */
-    int32_t reserved;
+    int32_t graph_replayed;            /* 1: csm_correlative_match replayed a recorded graph */
     int64_t blocks_scored, blocks_skipped;
 } csm_search_info;
 int  csm_last_search_info(csm_ctx* ctx, csm_search_info* out);

@@ -45,7 +45,7 @@ GROUP_FORCE_RCCL = 1
 
 class SearchInfo(C.Structure):
     _fields_ = [("nominal_candidates", C.c_int64), ("coarse_nodes_scored", C.c_int64),
-                ("fine_candidates_scored", C.c_int64), ("two_phase", C.c_int32), ("reserved", C.c_int32),
+                ("fine_candidates_scored", C.c_int64), ("two_phase", C.c_int32), ("graph_replayed", C.c_int32),
                 ("blocks_scored", C.c_int64), ("blocks_skipped", C.c_int64)]
 
 

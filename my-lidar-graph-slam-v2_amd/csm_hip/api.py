@@ -365,10 +365,11 @@ class Context:
                                                         arr(dump_s_ptrs), arr(dump_k_ptrs), arr(dump_f_ptrs)))
 
     def last_search_info(self):
-        """What the last correlative_match() evaluated (nominal / coarse nodes / fine candidates)."""
+        """What the last correlative_match() evaluated (nominal / coarse nodes / fine candidates,
+        two_phase, graph_replayed: 1 when its launch chain was a replayed HIP graph)."""
         info = L.SearchInfo()
         self._check(self.lib.csm_last_search_info(self._ctx, C.byref(info)))
-        return {k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"}
+        return {k: getattr(info, k) for k, _ in info._fields_}
 
     def bound_pass_stats(self):
         """(candidate blocks the exact kernel scored, blocks it skipped after the fp32 bound

@@ -14,13 +14,18 @@
 
 namespace csm_host {
 
-void free_levels(DeviceGrid& g, bool keep_base)
+void base_changed(DeviceGrid& g)
 {
     for (auto& kv : g.phase)
         if (kv.second.grid)
             free_levels(*kv.second.grid, false);
     g.phase.clear();
     ++g.base_epoch;
+}
+
+void free_levels(DeviceGrid& g, bool keep_base)
+{
+    base_changed(g);
     if (!keep_base) {
         if (g.xg)
             (void)hipFree(g.xg);
@@ -134,7 +139,7 @@ int csm_destroy(csm_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& kv : ctx->graphs)
-        (void)hipGraphExecDestroy(kv.second);
+        (void)hipGraphExecDestroy(kv.second.exec);
     ctx->graphs.clear();
     if (ctx->q_pin)
         (void)hipHostFree(ctx->q_pin);
@@ -545,6 +550,7 @@ int csm_last_search_info(csm_ctx* ctx, csm_search_info* out)
     out->nominal_candidates = ctx->last_nominal;
     out->coarse_nodes_scored = ctx->last_coarse_nodes;
     out->fine_candidates_scored = ctx->last_fine_candidates;
+    out->graph_replayed = ctx->last_graph_replayed ? 1 : 0;
     if (ctx->tp_count_dev) {
         uint32_t kept = 0;
         HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -55,7 +55,8 @@ struct DeviceGrid;
 struct PhaseMap {
     std::unique_ptr<DeviceGrid> grid;
     int hp = 0, wp = 0, pad = 0;
-    const uint16_t* built_from = nullptr;   /* the level's buffer and the base epoch it was built at */
+    const uint16_t* built_from = nullptr;   /* the level's buffer, its shape and the base epoch it was built at */
+    int from_rows = 0, from_cols = 0, from_pitch = 0;
     uint64_t epoch = 0;
 };
 
@@ -135,8 +136,13 @@ struct csm_ctx {
      * nodes point at may have moved */
     uint64_t alloc_epoch = 0;
     bool capturing = false;
-    std::map<std::vector<uint64_t>, hipGraphExec_t> graphs;
+    struct RecordedChain {
+        hipGraphExec_t exec = nullptr;
+        csm::ScoreJob fine;          /* the fine-level job baked into the chain: last_fine after a replay */
+    };
+    std::map<std::vector<uint64_t>, RecordedChain> graphs;
     std::map<std::vector<uint64_t>, int> graph_seen;
+    bool last_graph_replayed = false;            /* csm_last_search_info: the last match was a replay */
     void* q_pin = nullptr;           /* pinned: [ProjJob | angles | ranges] up, [record | uncertified count] back */
     size_t q_pin_cap = 0;
     DevBuf q_dev;
@@ -170,7 +176,9 @@ struct csm_ctx {
     /* job tables of csm_score_windows_dev calls (pageable sources of asynchronous
      * uploads), each kept until the event recorded behind its launch chain has fired */
     std::vector<std::pair<hipEvent_t, std::shared_ptr<void>>> resident_hold;
-    /* the fine-level job of the last csm window, for the tie collection pass */
+    /* the fine-level job of the last launch chain (run_window, or the recorded job of a replayed
+     * graph), for the tie collection pass: its flag word and two-phase eligibility levels are
+     * facts of that launch, not of the window alone */
     csm::ScoreJob last_fine;
     unsigned flag_toggle = 0;     /* two flag words, used alternately: k_finalize of query i
                                      clears the word of query i + 1 */
@@ -282,6 +290,9 @@ inline DeviceGrid* find_grid(csm_ctx* ctx, uint64_t id)
 
 /* defined in csm_api.hip */
 void free_levels(DeviceGrid& g, bool keep_base);
+/* level 0's cells changed: drop the phase-major copies and bump base_epoch (the caller has
+ * synchronised the stream that may still read them) */
+void base_changed(DeviceGrid& g);
 
 } /* namespace csm_host */
 using namespace csm_host;

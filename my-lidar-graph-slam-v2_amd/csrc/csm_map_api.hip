@@ -392,6 +392,11 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
         else
             g.levels[i].cells = g.levels[0].cells;     /* an alias of the base (window 1) */
     }
+    /* level 0 changes in place or moves: the phase-major copies of the box-max levels would
+     * otherwise be taken for current (same level buffer, same epoch) */
+    if (!g.phase.empty())
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    base_changed(g);
     g.xg_stale = true;         /* the pair-row copy follows the base */
     g.alloc_stale = true;      /* and so does the derived block-allocation bitmap */
     g.alloc_user = false;

@@ -473,7 +473,8 @@ int ensure_phase_map(csm_ctx* ctx, DeviceGrid& g, int level, int need, PhaseMap*
     const int L = g.levels[level].win;
     PhaseMap& pm = g.phase[L];
     const uint16_t* src = g.levels[level].cells;
-    if (pm.grid && pm.built_from == src && pm.epoch == g.base_epoch && pm.pad >= need + 2) {
+    if (pm.grid && pm.built_from == src && pm.from_rows == g.rows && pm.from_cols == g.cols &&
+        pm.from_pitch == g.pitch && pm.epoch == g.base_epoch && pm.pad >= need + 2) {
         *out = &pm;
         return CSM_OK;
     }
@@ -505,6 +506,9 @@ int ensure_phase_map(csm_ctx* ctx, DeviceGrid& g, int level, int need, PhaseMap*
     pm.wp = wp;
     pm.pad = pad;
     pm.built_from = src;
+    pm.from_rows = g.rows;
+    pm.from_cols = g.cols;
+    pm.from_pitch = g.pitch;
     pm.epoch = g.base_epoch;
     *out = &pm;
     return CSM_OK;
@@ -940,20 +944,25 @@ int csm_correlative_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
         (uint64_t)(uint32_t)w.min_known, (uint64_t)w.merge_mode, 0 };
     std::memcpy(&key.back(), &w.score_threshold, 8);
     bool launched = false;
+    ctx->last_graph_replayed = false;
     if (!two_phase && !ctx->timing && ctx->tune.graphs && !g->xg_stale) {
         auto it = ctx->graphs.find(key);
         if (it != ctx->graphs.end()) {
-            HIP_TRY(ctx, hipGraphLaunch(it->second, ctx->stream));
+            HIP_TRY(ctx, hipGraphLaunch(it->second.exec, ctx->stream));
             ctx->last_nominal = (int64_t)p.n_theta * p.nx * p.ny;
             ctx->last_coarse_nodes = 0;
             ctx->last_fine_candidates = ctx->last_nominal;
             ctx->tp_count_dev = nullptr;
+            /* run_window did not run: the tie pass must see the job this chain was recorded with
+             * (its map, plan and flag word), not that of the last plain launch */
+            ctx->last_fine = it->second.fine;
+            ctx->last_graph_replayed = true;
             launched = true;
         } else if (++ctx->graph_seen[key] >= 3) {
             /* third query of this shape: every workspace has its size; record the chain */
             if (ctx->graphs.size() >= 8) {
                 for (auto& kv : ctx->graphs)
-                    (void)hipGraphExecDestroy(kv.second);
+                    (void)hipGraphExecDestroy(kv.second.exec);
                 ctx->graphs.clear();
                 ctx->graph_seen.clear();
             }
@@ -966,7 +975,7 @@ int csm_correlative_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
                 const hipError_t e_end = hipStreamEndCapture(ctx->stream, &graph);
                 if (rc_cap == CSM_OK && e_end == hipSuccess && graph &&
                     hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    ctx->graphs[key] = exec;
+                    ctx->graphs[key] = { exec, ctx->last_fine };   /* last_fine: set while capturing */
                     HIP_TRY(ctx, hipGraphLaunch(exec, ctx->stream));
                     launched = true;
                 }

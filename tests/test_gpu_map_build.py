@@ -265,10 +265,23 @@ def test_map_many_scans_fine_resolution(gpu_ctx, oracle):
     gpu_ctx.release_grid(470)
 
 
-def test_frontend_loop_over_a_trajectory(gpu_ctx, oracle):
+@pytest.fixture(params=["default", "two_phase"])
+def frontend_ctx(request):
+    """The session context, and one that searches every window coarse-first (its phase-major
+    copies of the box-max level must follow each rebuild of the map)."""
+    if request.param == "default":
+        yield request.getfixturevalue("gpu_ctx")
+        return
+    ctx = api.Context(0, tuning_off=L.TUNE_FORCE_TWO_PHASE)
+    yield ctx
+    ctx.close()
+
+
+def test_frontend_loop_over_a_trajectory(frontend_ctx, oracle):
     """25 scans in a row, as the frontend runs them: rebuild the latest map from
     the last 10 scan nodes in the frame the previous build left, match the new
     scan against it, move on. Every step is compared with the CPU pipeline."""
+    gpu_ctx = frontend_ctx
     case = synth.map_case(77, n_scans=26, n_beams=360, step=0.15)
     nodes = case["nodes"]
     shape_dev = shape_cpu = case["shape"]
