@@ -687,6 +687,86 @@ int  csm_update_map_with_scan(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shap
                               const double global_map_pose[3], const csm_scan_node* node,
                               const csm_map_builder_params* params, csm_map_build_info* info);
 
+/* ---- pose-graph optimization: the backend's Optimize step ---- */
+
+/* LinearSolver / SolverType of PoseGraphOptimizerLM (inc/mapping/pose_graph_optimizer_lm.hpp) */
+#define CSM_PG_SOLVER_SPARSE_CHOLESKY     0   /* SimplicialLDLT: not provided (CSM_EINVAL) */
+#define CSM_PG_SOLVER_CONJUGATE_GRADIENT  1   /* Eigen ConjugateGradient<.., Lower>, Jacobi preconditioner */
+
+/* robust loss functions (src/mapping/robust_loss_function.cpp) */
+#define CSM_PG_LOSS_SQUARED         0
+#define CSM_PG_LOSS_HUBER           1
+#define CSM_PG_LOSS_CAUCHY          2
+#define CSM_PG_LOSS_FAIR            3
+#define CSM_PG_LOSS_GEMAN_MCCLURE   4
+#define CSM_PG_LOSS_WELSCH          5
+
+/* PoseGraph::Edge as the optimizer reads it (EdgePose, inc/mapping/pose_graph.hpp):
+ * start = local map node local_map_index, end = scan node scan_index */
+typedef struct {
+    int32_t local_map_index;     /* mLocalMapNodeIdx */
+    int32_t scan_index;          /* mScanNodeIdx */
+    int32_t is_loop;             /* mIsLoopConstraint: only these get the robust weight */
+    int32_t reserved;
+    double  relative_pose[3];    /* mRelativePose */
+    double  information[9];      /* mInformationMat, row-major */
+} csm_pose_graph_edge;
+
+/* PoseGraphOptimizerLM constructor arguments (defaults: launcher_settings_default.json
+ * "PoseGraphOptimizerLM": 10, 1e-4, ConjugateGradient, Huber 0.01) */
+typedef struct {
+    int32_t iterations_max;      /* NumOfIterationsMax, >= 1 */
+    int32_t solver_type;         /* CSM_PG_SOLVER_* */
+    int32_t loss_type;           /* CSM_PG_LOSS_* */
+    int32_t reserved;
+    double  error_tolerance;     /* ErrorTolerance */
+    double  loss_scale;          /* the loss function's Scale (unused by Squared), >= 0 */
+} csm_pose_graph_lm_params;
+
+typedef struct {
+    int32_t steps;               /* LM steps taken (the reference's NumOfIterations metric) */
+    int32_t reserved;
+    int64_t cg_iterations;       /* sum over the steps of the CG solver's iterations() */
+    double  initial_error;       /* ComputeTotalError before the first step */
+    double  final_error;         /* ... after the last step */
+    double  final_lambda;        /* mLambda when Optimize returns (also written to *lambda) */
+} csm_pose_graph_lm_info;
+
+/* one record per LM step */
+typedef struct {
+    double  total_error;         /* ComputeTotalError after the step */
+    double  lambda;              /* the damping factor the step's H was built with */
+    double  rhs_norm2;           /* |b|^2: the CG stops once |r|^2 < max(DBL_EPSILON^2 |b|^2, DBL_MIN) */
+    double  residual_norm2;      /* the CG's last recursively updated |r|^2 (0 when b = 0) */
+    int32_t cg_iterations;       /* ConjugateGradient::iterations(): at most 2 * 3 * (n_local + n_scan) */
+    int32_t reserved;
+} csm_pose_graph_lm_step;
+
+/* PoseGraphOptimizerLM::Optimize (src/mapping/pose_graph_optimizer_lm.cpp:38-106) with the
+ * ConjugateGradient solver, on the device: one launch, one workgroup, every LM step inside.
+ * local_poses [3 * n_local] and scan_poses [3 * n_scan] are updated in place; *lambda is the
+ * optimizer's mLambda, read at the start and written back at the end (it carries over between
+ * calls). info and trace may be null; a trace holds iterations_max records, of which
+ * info->steps are written. Runs on the ctx stream and returns when the results are on the host.
+ * Deterministic; agrees with csm_host_pose_graph_lm within rounding of the reduction order
+ * (DESIGN.md 4e). SparseCholesky, an index out of range, a non-finite pose, relative pose or
+ * information entry, n_local < 1 or iterations_max < 1: CSM_EINVAL. */
+int  csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double* scan_poses,
+                       int32_t n_scan, const csm_pose_graph_edge* edges, int32_t n_edges,
+                       const csm_pose_graph_lm_params* params, double* lambda,
+                       csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace);
+
+/* Host only: the same, as a sequential literal restatement in double with glibc's sin / cos /
+ * fmod (every sum in a fixed sequential order). The CPU reference of the above. */
+int  csm_host_pose_graph_lm(double* local_poses, int32_t n_local, double* scan_poses, int32_t n_scan,
+                            const csm_pose_graph_edge* edges, int32_t n_edges,
+                            const csm_pose_graph_lm_params* params, double* lambda,
+                            csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace);
+
+/* Host only: Loss(t) and Weight(t) of loss function loss_type with the given scale. */
+int  csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_error, double* loss,
+                              double* weight);
+
 /* ---- measurement hooks (bench.py) ---- */
 /* enable = 1: every kernel launch is bracketed by HIP events on the ctx
  * stream; enable = 2: only the dominant (fine-level) scoring kernel, to keep

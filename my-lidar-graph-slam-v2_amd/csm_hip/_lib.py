@@ -155,6 +155,32 @@ class HillClimbingResult(C.Structure):
                 ("host_path", C.c_int32), ("cost_evaluations", C.c_int64)]
 
 
+# pose-graph optimization (include/csm_hip.h)
+PG_SOLVER_SPARSE_CHOLESKY, PG_SOLVER_CONJUGATE_GRADIENT = 0, 1
+PG_LOSS_SQUARED, PG_LOSS_HUBER, PG_LOSS_CAUCHY, PG_LOSS_FAIR, PG_LOSS_GEMAN_MCCLURE, PG_LOSS_WELSCH = range(6)
+
+
+class PoseGraphEdge(C.Structure):
+    _fields_ = [("local_map_index", C.c_int32), ("scan_index", C.c_int32), ("is_loop", C.c_int32),
+                ("reserved", C.c_int32), ("relative_pose", C.c_double * 3), ("information", C.c_double * 9)]
+
+
+class PoseGraphLMParams(C.Structure):
+    _fields_ = [("iterations_max", C.c_int32), ("solver_type", C.c_int32), ("loss_type", C.c_int32),
+                ("reserved", C.c_int32), ("error_tolerance", C.c_double), ("loss_scale", C.c_double)]
+
+
+class PoseGraphLMInfo(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("reserved", C.c_int32), ("cg_iterations", C.c_int64),
+                ("initial_error", C.c_double), ("final_error", C.c_double), ("final_lambda", C.c_double)]
+
+
+class PoseGraphLMStep(C.Structure):
+    _fields_ = [("total_error", C.c_double), ("lambda_", C.c_double), ("rhs_norm2", C.c_double),
+                ("residual_norm2", C.c_double),
+                ("cg_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
 class LoopQuery(C.Structure):
     _fields_ = [("map_id", C.c_uint64), ("geometry", Geometry), ("scan", Scan),
                 ("initial_pose", C.c_double * 3)]
@@ -239,6 +265,13 @@ SIGNATURES = {
                                        _P(GreedyParams), _P(C.c_double), C.c_void_p]),
     "csm_host_hill_climbing": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(Geometry), _P(Scan), C.c_void_p,
                                          _P(HillClimbingParams), _P(HillClimbingResult)]),
+    "csm_pose_graph_lm": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(PoseGraphEdge), C.c_int32,
+                                    _P(PoseGraphLMParams), _P(C.c_double), _P(PoseGraphLMInfo),
+                                    _P(PoseGraphLMStep)]),
+    "csm_host_pose_graph_lm": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(PoseGraphEdge), C.c_int32,
+                                         _P(PoseGraphLMParams), _P(C.c_double), _P(PoseGraphLMInfo),
+                                         _P(PoseGraphLMStep)]),
+    "csm_host_pose_graph_loss": (C.c_int, [C.c_int32, C.c_double, C.c_double, _P(C.c_double), _P(C.c_double)]),
     "csm_shard_bounds": (None, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "csm_group_create": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
     "csm_group_create_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, _P(C.c_void_p)]),

@@ -207,6 +207,75 @@ def host_probability_lut():
     return lut
 
 
+PG_SOLVERS = {"SparseCholesky": L.PG_SOLVER_SPARSE_CHOLESKY, "ConjugateGradient": L.PG_SOLVER_CONJUGATE_GRADIENT}
+PG_LOSSES = {"Squared": L.PG_LOSS_SQUARED, "Huber": L.PG_LOSS_HUBER, "Cauchy": L.PG_LOSS_CAUCHY,
+             "Fair": L.PG_LOSS_FAIR, "GemanMcClure": L.PG_LOSS_GEMAN_MCCLURE, "Welsch": L.PG_LOSS_WELSCH}
+
+
+def pose_graph_params(iterations_max=10, error_tolerance=1e-4, solver="ConjugateGradient", loss="Huber",
+                      loss_scale=0.01):
+    """csm_pose_graph_lm_params; defaults as launcher_settings_default.json "PoseGraphOptimizerLM".
+    solver / loss: a name (SolverType, LossFunctionType) or the CSM_PG_* number."""
+    st = PG_SOLVERS[solver] if isinstance(solver, str) else int(solver)
+    lt = PG_LOSSES[loss] if isinstance(loss, str) else int(loss)
+    return L.PoseGraphLMParams(int(iterations_max), st, lt, 0, float(error_tolerance), float(loss_scale))
+
+
+def pose_graph_edges(edges):
+    """A csm_pose_graph_edge array from dicts {local, scan, rel (3), info (3x3 or 9), loop}
+    (EdgePose: mLocalMapNodeIdx, mScanNodeIdx, mRelativePose, mInformationMat, mIsLoopConstraint)."""
+    if isinstance(edges, C.Array):
+        return edges
+    arr = (L.PoseGraphEdge * max(len(edges), 1))()
+    for e, d in zip(arr, edges):
+        e.local_map_index = int(d["local"])
+        e.scan_index = int(d["scan"])
+        e.is_loop = 1 if d.get("loop") else 0
+        e.relative_pose[:] = [float(v) for v in d["rel"]]
+        e.information[:] = [float(v) for v in np.asarray(d["info"], dtype=np.float64).reshape(9)]
+    return arr
+
+
+def _pose_graph_run(fn, head, local_poses, scan_poses, edges, lambda_, params):
+    lp = np.array(local_poses, dtype=np.float64).reshape(-1, 3)
+    sp = np.array(scan_poses, dtype=np.float64).reshape(-1, 3)
+    ea = pose_graph_edges(edges)
+    n_edges = len(edges)
+    lam = C.c_double(lambda_)
+    info = L.PoseGraphLMInfo()
+    trace = (L.PoseGraphLMStep * max(params.iterations_max, 1))()
+    rc = fn(*head, _ptr(lp), lp.shape[0], _ptr(sp), sp.shape[0], ea, n_edges, C.byref(params), C.byref(lam),
+            C.byref(info), trace)
+    out = dict(steps=info.steps, cg_iterations=int(info.cg_iterations), initial_error=info.initial_error,
+               final_error=info.final_error, lambda_=lam.value,
+               trace=[dict(total_error=t.total_error, lambda_=t.lambda_, rhs_norm2=t.rhs_norm2,
+                           residual_norm2=t.residual_norm2,
+                           cg_iterations=t.cg_iterations) for t in trace[:info.steps]] if rc == 0 else [])
+    return rc, lp, sp, out
+
+
+def host_pose_graph_lm(local_poses, scan_poses, edges, lambda_=1e-4, params=None, **kw):
+    """csm_host_pose_graph_lm: the library's sequential restatement of PoseGraphOptimizerLM::Optimize.
+    Returns (local poses [n, 3], scan poses [m, 3], info dict with the per-step trace and the final
+    lambda_). params: pose_graph_params(...), or its keyword arguments."""
+    p = params if params is not None else pose_graph_params(**kw)
+    rc, lp, sp, out = _pose_graph_run(L.load().csm_host_pose_graph_lm, (), local_poses, scan_poses, edges,
+                                      lambda_, p)
+    if rc:
+        raise CsmError(rc, "csm_host_pose_graph_lm")
+    return lp, sp, out
+
+
+def host_pose_graph_loss(loss, scale, squared_error):
+    """(Loss(t), Weight(t)) of a robust loss function (csm_host_pose_graph_loss)."""
+    lo, w = C.c_double(), C.c_double()
+    lt = PG_LOSSES[loss] if isinstance(loss, str) else int(loss)
+    rc = L.load().csm_host_pose_graph_loss(lt, scale, squared_error, C.byref(lo), C.byref(w))
+    if rc:
+        raise CsmError(rc, "csm_host_pose_graph_loss")
+    return lo.value, w.value
+
+
 class Context:
     """One csm_ctx: owns the device grids, workspaces and a stream."""
 
@@ -579,6 +648,16 @@ class Context:
         self._check(self.lib.csm_hill_climbing_batch(self._ctx, prep.arr, prep.n, C.byref(p), out))
         return out if as_records else [self._hill_to_dict(o) for o in out]
 
+    def pose_graph_lm(self, local_poses, scan_poses, edges, lambda_, params=None, **kw):
+        """PoseGraphOptimizerLM::Optimize on the device (csm_pose_graph_lm). Returns new arrays
+        (local poses [n, 3], scan poses [m, 3]) and a dict: steps, cg_iterations, initial_error,
+        final_error, lambda_ (the final damping factor) and trace (one dict per LM step)."""
+        p = params if params is not None else pose_graph_params(**kw)
+        rc, lp, sp, out = _pose_graph_run(self.lib.csm_pose_graph_lm, (self._ctx,), local_poses, scan_poses,
+                                          edges, lambda_, p)
+        self._check(rc)
+        return lp, sp, out
+
     def enable_kernel_timing(self, on=True):
         self._check(self.lib.csm_enable_kernel_timing(self._ctx, 1 if on else 0))
 
@@ -762,3 +841,26 @@ class ScanMatcherHillClimbingHIP:
             self.ctx.release_grid(mid)
         out["pose_found"] = 1          # OptimizePose always finds a pose
         return out
+
+
+class PoseGraphOptimizerLMHIP:
+    """Drop-in for PoseGraphOptimizerLM with the ConjugateGradient solver (constructor arguments as
+    the optimizer's settings group, launcher_settings_default.json "PoseGraphOptimizerLM"). The damping
+    factor is kept between optimize() calls, as the reference's mLambda member is."""
+
+    def __init__(self, solver="ConjugateGradient", iterations_max=10, error_tolerance=1e-4, initial_lambda=1e-4,
+                 loss="Huber", loss_scale=0.01, ctx=None):
+        self.params = pose_graph_params(iterations_max, error_tolerance, solver, loss, loss_scale)
+        if self.params.solver_type != L.PG_SOLVER_CONJUGATE_GRADIENT:
+            raise CsmError(L.CSM_EINVAL, "PoseGraphOptimizerLMHIP: only the ConjugateGradient solver is provided")
+        self.lambda_ = float(initial_lambda)
+        self.ctx = ctx or Context()
+        self.last_info = None
+
+    def optimize(self, local_map_nodes, scan_nodes, edges):
+        """Optimize(localMapNodes, scanNodes, poseGraphEdges): returns the updated (local, scan)
+        pose arrays; the metrics of the call are in last_info."""
+        lp, sp, info = self.ctx.pose_graph_lm(local_map_nodes, scan_nodes, edges, self.lambda_, self.params)
+        self.lambda_ = info["lambda_"]
+        self.last_info = info
+        return lp, sp

@@ -146,3 +146,90 @@ def map_case(seed, n_scans=10, n_beams=1080, fov=1.5 * math.pi, max_range=8.0, r
     n = (n + block - 1) // block * block
     shape = dict(res=res, off_x=0.0, off_y=0.0, rows=n, cols=n, log2_block=4)
     return dict(nodes=nodes, map_pose=nodes[0]["pose"], shape=shape, segs=segs)
+
+
+def _inverse_compound(a, b):
+    c, s = math.cos(a[2]), math.sin(a[2])
+    dx, dy = b[0] - a[0], b[1] - a[1]
+    return (c * dx + s * dy, -s * dx + c * dy, math.atan2(math.sin(b[2] - a[2]), math.cos(b[2] - a[2])))
+
+
+def _compound(a, d):
+    c, s = math.cos(a[2]), math.sin(a[2])
+    return (a[0] + c * d[0] - s * d[1], a[1] + s * d[0] + c * d[1], a[2] + d[2])
+
+
+def pose_graph_case(seed, n_scans=100, scans_per_map=10, lap_scans=None, step=0.25, loop_every=3,
+                    loop_radius=1.0, wrong_fraction=0.0, sigma=(0.05, 0.05, 0.02), odom_noise=(0.02, 0.02, 0.008)):
+    """A pose graph as the backend hands it to PoseGraphOptimizer::Optimize: a robot drives laps
+    of a slightly widening circle (lap_scans scans per lap), a local map starts every scans_per_map
+    scans at the pose of its first scan, and the initial node poses come from integrated noisy
+    odometry (they drift). Edges, in the order a run appends them:
+      - local map -> each of its scans, and the previous local map -> a new map's first scan
+        (odometry edges, is_loop = 0);
+      - every loop_every-th scan from the second lap on: a loop edge to the nearest local map of an
+        earlier lap within loop_radius (is_loop = 1);
+      - of those, a fraction wrong_fraction are wrong: tied to a random older local map with a
+        small relative pose, as a false match would be.
+    Measurements are the true relative poses plus Gaussian noise of a random SPD covariance; the
+    edge's information matrix is that covariance's inverse. Returns dict(local, scan (initial poses,
+    [n, 3]), truth_local, truth_scan, edges (dicts for api.pose_graph_edges), wrong (edge indices))."""
+    rng = np.random.RandomState(seed)
+    lap = lap_scans or max(6, min(200, n_scans // 3))
+    radius = lap * step / (2 * math.pi)
+    truth = []
+    for k in range(n_scans):
+        phi = 2 * math.pi * k / lap
+        r = radius * (1.0 + 0.03 * (k // lap)) + 0.05 * math.sin(5 * phi)
+        truth.append((r * math.cos(phi), r * math.sin(phi), phi + 0.5 * math.pi))
+    est = [truth[0]]
+    for k in range(1, n_scans):
+        d = _inverse_compound(truth[k - 1], truth[k])
+        d = tuple(d[i] + odom_noise[i] * rng.randn() for i in range(3))
+        est.append(_compound(est[-1], d))
+    n_maps = (n_scans + scans_per_map - 1) // scans_per_map
+    map_of = [k // scans_per_map for k in range(n_scans)]
+
+    def measure(a, b, wrong=False):
+        m = rng.randn(3, 3) * 0.3 + np.eye(3)
+        sd = np.diag(sigma) * (0.5 + rng.rand())
+        cov = sd @ (m @ m.T + 0.1 * np.eye(3)) @ sd
+        info = np.linalg.inv(cov)
+        info = 0.5 * (info + info.T)
+        if wrong:
+            rel = (rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5), rng.uniform(-0.3, 0.3))
+        else:
+            rel = _inverse_compound(a, b)
+            rel = tuple(np.asarray(rel) + np.linalg.cholesky(cov) @ rng.randn(3))
+        return [float(v) for v in rel], info
+
+    edges, wrong = [], []
+    for k in range(n_scans):
+        m = map_of[k]
+        rel, info = measure(truth[m * scans_per_map], truth[k])
+        edges.append(dict(local=m, scan=k, rel=rel, info=info, loop=0))
+        if m >= 1 and k == m * scans_per_map:
+            rel, info = measure(truth[(m - 1) * scans_per_map], truth[k])
+            edges.append(dict(local=m - 1, scan=k, rel=rel, info=info, loop=0))
+        if k >= lap and loop_every and k % loop_every == 0:
+            best, best_d = None, loop_radius
+            for j in range(max(0, m - 1)):
+                if j * scans_per_map > k - lap // 2:
+                    break
+                t = truth[j * scans_per_map]
+                dd = math.hypot(t[0] - truth[k][0], t[1] - truth[k][1])
+                if dd < best_d:
+                    best, best_d = j, dd
+            if best is None:
+                continue
+            bad = rng.rand() < wrong_fraction
+            if bad:
+                best = int(rng.randint(0, max(1, m - 1)))
+            rel, info = measure(truth[best * scans_per_map], truth[k], wrong=bad)
+            if bad:
+                wrong.append(len(edges))
+            edges.append(dict(local=best, scan=k, rel=rel, info=info, loop=1))
+    local = np.array([est[j * scans_per_map] for j in range(n_maps)], dtype=np.float64)
+    truth_local = np.array([truth[j * scans_per_map] for j in range(n_maps)], dtype=np.float64)
+    return dict(local=local, scan=np.array(est, dtype=np.float64), truth_local=truth_local,
+                truth_scan=np.array(truth, dtype=np.float64), edges=edges, wrong=wrong)

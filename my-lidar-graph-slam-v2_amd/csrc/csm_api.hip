@@ -153,7 +153,7 @@ int csm_destroy(csm_ctx* ctx)
                        &ctx->fine_s, &ctx->fine_k, &ctx->tie, &ctx->ex_fine, &ctx->ex_fine_k, &ctx->ex_coarse, &ctx->ex_coarse_k,
                        &ctx->scan_dev, &ctx->unc, &ctx->sorted_rc, &ctx->b_sorted_rc, &ctx->rec_dev, &ctx->c_scans, &ctx->c_jobs, &ctx->box_jobs,
                        &ctx->m_rays, &ctx->m_recs, &ctx->m_cell, &ctx->m_lists, &ctx->m_cnt, &ctx->m_lut,
-                       &ctx->g_scans, &ctx->g_jobs, &ctx->g_scratch, &ctx->g_tab };
+                       &ctx->g_scans, &ctx->g_jobs, &ctx->g_scratch, &ctx->g_tab, &ctx->pg_buf };
     for (DevBuf* b : bufs)
         if (b->p)
             (void)hipFree(b->p);

@@ -163,6 +163,9 @@ struct csm_ctx {
     /* greedy-endpoint / hill-climbing batches (csm_greedy_api.hip): scans, job table + outputs,
      * rank scratch of scans too long for LDS, the cost tables */
     DevBuf g_scans, g_jobs, g_scratch, g_tab;
+    /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
+    DevBuf pg_buf;
+    std::vector<uint8_t> pg_stage;
     /* the final records of the last batch call in query order (csm_copy_last_batch_records) */
     DevBuf rec_dev;
     int rec_n = 0;

@@ -1,0 +1,424 @@
+/* csm_posegraph_api.hip -- host side of the pose-graph optimizer (PoseGraphOptimizerLM with the
+ * ConjugateGradient solver): validation, the block structure of H with the ordered contribution list
+ * of every stored block, the host restatement csm_host_pose_graph_lm (the CPU reference) and the
+ * device entry csm_pose_graph_lm, whose kernel is in csm_posegraph_kernels.hip. A translation unit of
+ * libcsm_hip.so of its own. DESIGN.md 4e. */
+#include "csm_internal.hpp"
+
+#include "csm_posegraph_kernels.hip"
+
+#include <unordered_map>
+
+namespace {
+
+constexpr int kPgMaxNodes = 1 << 24;     /* 2 * 3 * nodes stays an int (the CG's iteration cap) */
+
+/* the graph as both solvers read it: inputs in node indices, the incidence lists, the distinct
+ * cross blocks and the rows of H */
+struct PgGraph {
+    int n_local = 0, n_nodes = 0, n_vars = 0, n_edges = 0, n_cross = 0;
+    std::vector<double> rel, info;
+    std::vector<int32_t> enode, is_loop, node_ptr, node_edges, cross_ptr, cross_edges, row_ptr, row_col, row_ent;
+};
+
+const char* pg_check(const double* local_poses, int n_local, const double* scan_poses, int n_scan,
+                     const csm_pose_graph_edge* edges, int n_edges, const csm_pose_graph_lm_params* p,
+                     const double* lambda)
+{
+    if (!p || !lambda || !local_poses || n_local < 1 || n_scan < 0 || (n_scan > 0 && !scan_poses) || n_edges < 0 ||
+        (n_edges > 0 && !edges) || (int64_t)n_local + n_scan > kPgMaxNodes)
+        return "bad arguments";
+    if (p->solver_type == CSM_PG_SOLVER_SPARSE_CHOLESKY)
+        return "SolverType SparseCholesky (SimplicialLDLT) is not provided; use ConjugateGradient";
+    if (p->solver_type != CSM_PG_SOLVER_CONJUGATE_GRADIENT)
+        return "unknown solver type";
+    if (p->loss_type < CSM_PG_LOSS_SQUARED || p->loss_type > CSM_PG_LOSS_WELSCH)
+        return "unknown loss type";
+    if (p->iterations_max < 1)
+        return "iterations_max < 1";
+    if (std::isnan(p->error_tolerance) || !std::isfinite(p->loss_scale) || p->loss_scale < 0.0 ||
+        !std::isfinite(*lambda))
+        return "non-finite or negative parameter";
+    for (int i = 0; i < 3 * n_local; ++i)
+        if (!std::isfinite(local_poses[i]))
+            return "non-finite local map node pose";
+    for (int i = 0; i < 3 * n_scan; ++i)
+        if (!std::isfinite(scan_poses[i]))
+            return "non-finite scan node pose";
+    for (int e = 0; e < n_edges; ++e) {
+        const csm_pose_graph_edge& E = edges[e];
+        if (E.local_map_index < 0 || E.local_map_index >= n_local || E.scan_index < 0 || E.scan_index >= n_scan)
+            return "edge node index out of range";
+        for (int j = 0; j < 3; ++j)
+            if (!std::isfinite(E.relative_pose[j]))
+                return "non-finite edge relative pose";
+        for (int j = 0; j < 9; ++j)
+            if (!std::isfinite(E.information[j]))
+                return "non-finite edge information matrix";
+    }
+    return nullptr;
+}
+
+void pg_build(int n_local, int n_scan, const csm_pose_graph_edge* edges, int n_edges, PgGraph& G)
+{
+    const int N = n_local + n_scan;
+    G.n_local = n_local;
+    G.n_nodes = N;
+    G.n_vars = 3 * N;
+    G.n_edges = n_edges;
+    G.rel.resize(3 * (size_t)n_edges);
+    G.info.resize(9 * (size_t)n_edges);
+    G.enode.resize(2 * (size_t)n_edges);
+    G.is_loop.resize(n_edges);
+    std::vector<int32_t> cross_of(n_edges);
+    std::unordered_map<int64_t, int32_t> pair_id;
+    std::vector<std::pair<int32_t, int32_t>> pairs;       /* (end node, start node) of cross block u */
+    G.node_ptr.assign(N + 1, 0);
+    for (int e = 0; e < n_edges; ++e) {
+        const csm_pose_graph_edge& E = edges[e];
+        const int s = E.local_map_index, t = n_local + E.scan_index;
+        std::memcpy(&G.rel[3 * (size_t)e], E.relative_pose, 3 * sizeof(double));
+        std::memcpy(&G.info[9 * (size_t)e], E.information, 9 * sizeof(double));
+        G.enode[2 * e] = s;
+        G.enode[2 * e + 1] = t;
+        G.is_loop[e] = E.is_loop ? 1 : 0;
+        ++G.node_ptr[s + 1];
+        ++G.node_ptr[t + 1];
+        const int64_t key = (int64_t)t * N + s;
+        auto it = pair_id.find(key);
+        if (it == pair_id.end()) {
+            it = pair_id.emplace(key, (int32_t)pairs.size()).first;
+            pairs.emplace_back(t, s);
+        }
+        cross_of[e] = it->second;
+    }
+    const int U = (int)pairs.size();
+    G.n_cross = U;
+    for (int k = 0; k < N; ++k)
+        G.node_ptr[k + 1] += G.node_ptr[k];
+    G.node_edges.resize(2 * (size_t)n_edges);
+    G.cross_ptr.assign(U + 1, 0);
+    for (int e = 0; e < n_edges; ++e)
+        ++G.cross_ptr[cross_of[e] + 1];
+    for (int u = 0; u < U; ++u)
+        G.cross_ptr[u + 1] += G.cross_ptr[u];
+    G.cross_edges.resize(n_edges);
+    {
+        std::vector<int32_t> fill(G.node_ptr.begin(), G.node_ptr.end() - 1);
+        std::vector<int32_t> cfill(G.cross_ptr.begin(), G.cross_ptr.end() - 1);
+        for (int e = 0; e < n_edges; ++e) {          /* edge order within every list */
+            G.node_edges[fill[G.enode[2 * e]]++] = e;
+            G.node_edges[fill[G.enode[2 * e + 1]]++] = e;
+            G.cross_edges[cfill[cross_of[e]]++] = e;
+        }
+    }
+    /* rows: per node its diagonal block and one block per distinct neighbour, ascending column */
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> rows(N);
+    for (int k = 0; k < N; ++k)
+        rows[k].emplace_back(k, (k << 2) | (G.node_ptr[k] == G.node_ptr[k + 1] ? kPgDiagOnly : 0));
+    for (int u = 0; u < U; ++u) {
+        const int t = pairs[u].first, s = pairs[u].second, slot = N + u;
+        rows[t].emplace_back(s, slot << 2);
+        rows[s].emplace_back(t, (slot << 2) | kPgTransposed);
+    }
+    G.row_ptr.assign(N + 1, 0);
+    G.row_col.clear();
+    G.row_ent.clear();
+    G.row_col.reserve(N + 2 * (size_t)U);
+    G.row_ent.reserve(N + 2 * (size_t)U);
+    for (int k = 0; k < N; ++k) {
+        std::sort(rows[k].begin(), rows[k].end());
+        for (const auto& ce : rows[k]) {
+            G.row_col.push_back(ce.first);
+            G.row_ent.push_back(ce.second);
+        }
+        G.row_ptr[k + 1] = (int32_t)G.row_col.size();
+    }
+}
+
+void pg_job_structure(const PgGraph& G, const csm_pose_graph_lm_params& p, double lambda, PgJob& J)
+{
+    J.n_local = G.n_local;
+    J.n_nodes = G.n_nodes;
+    J.n_vars = G.n_vars;
+    J.n_edges = G.n_edges;
+    J.n_cross = G.n_cross;
+    J.iterations_max = p.iterations_max;
+    J.loss_type = p.loss_type;
+    J.cg_max = 2 * G.n_vars;              /* IterativeSolverBase::maxIterations(): 2 * cols */
+    J.error_tolerance = p.error_tolerance;
+    J.loss_scale = p.loss_scale;
+    J.lambda = lambda;
+}
+
+/* Optimize, statement by statement and in sequence: the reference the device is held to */
+void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vector<double>& pose, double& lambda,
+                 csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
+{
+    const int n = G.n_vars;
+    std::vector<double> ev((size_t)kPgEdgeVals * G.n_edges), bv(9 * ((size_t)G.n_nodes + G.n_cross));
+    std::vector<double> b(n), invd(n), x(n), r(n), z(n), pv(n), ap(n);
+    PgJob J {};
+    pg_job_structure(G, p, lambda, J);
+    J.pose = pose.data();
+    J.rel = G.rel.data();
+    J.info = G.info.data();
+    J.enode = G.enode.data();
+    J.is_loop = G.is_loop.data();
+    J.node_ptr = G.node_ptr.data();
+    J.node_edges = G.node_edges.data();
+    J.cross_ptr = G.cross_ptr.data();
+    J.cross_edges = G.cross_edges.data();
+    J.row_ptr = G.row_ptr.data();
+    J.row_col = G.row_col.data();
+    J.row_ent = G.row_ent.data();
+    J.ev = ev.data();
+    J.bv = bv.data();
+    auto total_error = [&]() {
+        double t = 0.0;
+        for (int e = 0; e < G.n_edges; ++e)
+            t += pg_edge_loss(&pose[3 * (size_t)G.enode[2 * e]], &pose[3 * (size_t)G.enode[2 * e + 1]],
+                              &G.rel[3 * (size_t)e], &G.info[9 * (size_t)e], p.loss_type, p.loss_scale);
+        return t;
+    };
+    auto dot = [n](const std::vector<double>& a, const std::vector<double>& c) {
+        double s = 0.0;
+        for (int i = 0; i < n; ++i)
+            s += a[i] * c[i];
+        return s;
+    };
+    J.b = b.data();
+    J.invd = invd.data();
+    double prev = DBL_MAX, total = DBL_MAX;
+    const double initial = total_error();
+    int steps = 0;
+    int64_t cg_total = 0;
+    for (;;) {
+        for (int e = 0; e < G.n_edges; ++e)
+            pg_edge_values(&pose[3 * (size_t)G.enode[2 * e]], &pose[3 * (size_t)G.enode[2 * e + 1]],
+                           &G.rel[3 * (size_t)e], &G.info[9 * (size_t)e], G.is_loop[e], p.loss_type, p.loss_scale,
+                           &ev[(size_t)kPgEdgeVals * e]);
+        for (int k = 0; k < G.n_nodes; ++k)
+            pg_assemble_node(J, k, lambda);
+        for (int u = 0; u < G.n_cross; ++u)
+            pg_assemble_cross(J, u);
+        /* conjugate_gradient with x0 = 0: residual = b */
+        std::fill(x.begin(), x.end(), 0.0);
+        r = b;
+        const double rhs2 = dot(b, b);
+        double r2 = rhs2;
+        int cg = 0;
+        if (rhs2 != 0.0) {
+            const double a = DBL_EPSILON * DBL_EPSILON * rhs2;
+            const double thr = (a < DBL_MIN) ? DBL_MIN : a;
+            if (!(r2 < thr)) {
+                for (int i = 0; i < n; ++i)
+                    pv[i] = invd[i] * r[i];
+                double abs_new = dot(r, pv);
+                for (; cg < J.cg_max; ++cg) {
+                    for (int i = 0; i < n; ++i)
+                        ap[i] = pg_row_times(J, i, pv.data());
+                    const double alpha = abs_new / dot(pv, ap);
+                    for (int i = 0; i < n; ++i)
+                        x[i] += alpha * pv[i];
+                    for (int i = 0; i < n; ++i)
+                        r[i] -= alpha * ap[i];
+                    r2 = dot(r, r);
+                    if (r2 < thr)
+                        break;
+                    for (int i = 0; i < n; ++i)
+                        z[i] = invd[i] * r[i];
+                    const double abs_old = abs_new;
+                    abs_new = dot(r, z);
+                    const double beta = abs_new / abs_old;
+                    for (int i = 0; i < n; ++i)
+                        pv[i] = z[i] + beta * pv[i];
+                }
+            }
+        }
+        for (int i = 0; i < n; ++i)
+            pose[i] += x[i];
+        total = total_error();
+        if (trace) {
+            csm_pose_graph_lm_step& s = trace[steps];
+            std::memset(&s, 0, sizeof(s));
+            s.total_error = total;
+            s.lambda = lambda;
+            s.rhs_norm2 = rhs2;
+            s.residual_norm2 = r2;
+            s.cg_iterations = cg;
+        }
+        cg_total += cg;
+        if (++steps >= p.iterations_max || std::fabs(prev - total) < p.error_tolerance)
+            break;
+        lambda = (total < prev) ? lambda * 0.5 : lambda * 2.0;
+        prev = total;
+    }
+    if (info) {
+        std::memset(info, 0, sizeof(*info));
+        info->steps = steps;
+        info->cg_iterations = cg_total;
+        info->initial_error = initial;
+        info->final_error = total;
+        info->final_lambda = lambda;
+    }
+}
+
+/* one device allocation carved into 256-byte aligned pieces */
+struct Carve {
+    size_t off = 0;
+    size_t take(size_t bytes)
+    {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+
+} /* namespace */
+
+extern "C" {
+
+int csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_error, double* loss, double* weight)
+{
+    if (loss_type < CSM_PG_LOSS_SQUARED || loss_type > CSM_PG_LOSS_WELSCH || !loss || !weight)
+        return CSM_EINVAL;
+    *loss = pg_loss(loss_type, scale, squared_error);
+    *weight = pg_weight(loss_type, scale, squared_error);
+    return CSM_OK;
+}
+
+int csm_host_pose_graph_lm(double* local_poses, int32_t n_local, double* scan_poses, int32_t n_scan,
+                           const csm_pose_graph_edge* edges, int32_t n_edges, const csm_pose_graph_lm_params* params,
+                           double* lambda, csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
+{
+    if (pg_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, params, lambda))
+        return CSM_EINVAL;
+    PgGraph G;
+    pg_build(n_local, n_scan, edges, n_edges, G);
+    std::vector<double> pose(G.n_vars);
+    std::memcpy(pose.data(), local_poses, 3 * (size_t)n_local * sizeof(double));
+    if (n_scan)
+        std::memcpy(pose.data() + 3 * (size_t)n_local, scan_poses, 3 * (size_t)n_scan * sizeof(double));
+    pg_host_run(G, *params, pose, *lambda, info, trace);
+    std::memcpy(local_poses, pose.data(), 3 * (size_t)n_local * sizeof(double));
+    if (n_scan)
+        std::memcpy(scan_poses, pose.data() + 3 * (size_t)n_local, 3 * (size_t)n_scan * sizeof(double));
+    return CSM_OK;
+}
+
+int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double* scan_poses, int32_t n_scan,
+                      const csm_pose_graph_edge* edges, int32_t n_edges, const csm_pose_graph_lm_params* params,
+                      double* lambda, csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
+{
+    if (!ctx)
+        return CSM_EINVAL;
+    if (const char* why = pg_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, params, lambda))
+        return fail(ctx, CSM_EINVAL, "csm_pose_graph_lm: %s", why);
+    PgGraph G;
+    pg_build(n_local, n_scan, edges, n_edges, G);
+    const int n = G.n_vars, E = G.n_edges, NB = G.n_nodes + G.n_cross, R = (int)G.row_col.size();
+    const int n_out = 4 + 5 * params->iterations_max;
+    /* inputs (uploaded): pose, rel, info, then the int lists; work and output after them */
+    Carve c;
+    const size_t o_pose = c.take(8 * (size_t)n), o_rel = c.take(24 * (size_t)E), o_info = c.take(72 * (size_t)E);
+    const size_t o_enode = c.take(8 * (size_t)E), o_loop = c.take(4 * (size_t)E);
+    const size_t o_nptr = c.take(4 * ((size_t)G.n_nodes + 1)), o_nedge = c.take(8 * (size_t)E);
+    const size_t o_cptr = c.take(4 * ((size_t)G.n_cross + 1)), o_cedge = c.take(4 * (size_t)E);
+    const size_t o_rptr = c.take(4 * ((size_t)G.n_nodes + 1)), o_rcol = c.take(4 * (size_t)R),
+                 o_rent = c.take(4 * (size_t)R);
+    const size_t up_bytes = c.off;
+    const size_t o_ev = c.take(8 * (size_t)kPgEdgeVals * E), o_bv = c.take(72 * (size_t)NB);
+    size_t o_vec[7];
+    for (size_t& o : o_vec)
+        o = c.take(8 * (size_t)n);
+    const size_t o_out = c.take(8 * (size_t)n_out);
+    int rc;
+    if ((rc = ensure(ctx, ctx->pg_buf, c.off)))
+        return rc;
+    std::vector<uint8_t>& st = ctx->pg_stage;
+    st.assign(up_bytes, 0);
+    auto put = [&](size_t off, const void* src, size_t bytes) {
+        if (bytes)
+            std::memcpy(st.data() + off, src, bytes);
+    };
+    put(o_pose, local_poses, 24 * (size_t)n_local);
+    put(o_pose + 24 * (size_t)n_local, scan_poses, 24 * (size_t)n_scan);
+    put(o_rel, G.rel.data(), 24 * (size_t)E);
+    put(o_info, G.info.data(), 72 * (size_t)E);
+    put(o_enode, G.enode.data(), 8 * (size_t)E);
+    put(o_loop, G.is_loop.data(), 4 * (size_t)E);
+    put(o_nptr, G.node_ptr.data(), 4 * ((size_t)G.n_nodes + 1));
+    put(o_nedge, G.node_edges.data(), 8 * (size_t)E);
+    put(o_cptr, G.cross_ptr.data(), 4 * ((size_t)G.n_cross + 1));
+    put(o_cedge, G.cross_edges.data(), 4 * (size_t)E);
+    put(o_rptr, G.row_ptr.data(), 4 * ((size_t)G.n_nodes + 1));
+    put(o_rcol, G.row_col.data(), 4 * (size_t)R);
+    put(o_rent, G.row_ent.data(), 4 * (size_t)R);
+
+    uint8_t* d = reinterpret_cast<uint8_t*>(ctx->pg_buf.p);
+    PgJob J {};
+    pg_job_structure(G, *params, *lambda, J);
+    J.pose = reinterpret_cast<double*>(d + o_pose);
+    J.rel = reinterpret_cast<const double*>(d + o_rel);
+    J.info = reinterpret_cast<const double*>(d + o_info);
+    J.enode = reinterpret_cast<const int32_t*>(d + o_enode);
+    J.is_loop = reinterpret_cast<const int32_t*>(d + o_loop);
+    J.node_ptr = reinterpret_cast<const int32_t*>(d + o_nptr);
+    J.node_edges = reinterpret_cast<const int32_t*>(d + o_nedge);
+    J.cross_ptr = reinterpret_cast<const int32_t*>(d + o_cptr);
+    J.cross_edges = reinterpret_cast<const int32_t*>(d + o_cedge);
+    J.row_ptr = reinterpret_cast<const int32_t*>(d + o_rptr);
+    J.row_col = reinterpret_cast<const int32_t*>(d + o_rcol);
+    J.row_ent = reinterpret_cast<const int32_t*>(d + o_rent);
+    J.ev = reinterpret_cast<double*>(d + o_ev);
+    J.bv = reinterpret_cast<double*>(d + o_bv);
+    double** vecs[7] = { &J.b, &J.invd, &J.x, &J.r, &J.z, &J.p, &J.ap };
+    for (int v = 0; v < 7; ++v)
+        *vecs[v] = reinterpret_cast<double*>(d + o_vec[v]);
+    J.out = reinterpret_cast<double*>(d + o_out);
+
+    HIP_TRY(ctx, hipMemcpyAsync(d, st.data(), up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    {
+        ScopedTimer tm(ctx, "pose_graph");
+        hipLaunchKernelGGL(k_pose_graph_lm, dim3(1), dim3(kPgBlock), 0, ctx->stream, J);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    std::vector<double> res(n + (size_t)n_out);
+    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d + o_pose, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(res.data() + n, d + o_out, 8 * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+    std::memcpy(local_poses, res.data(), 24 * (size_t)n_local);
+    if (n_scan)
+        std::memcpy(scan_poses, res.data() + 3 * (size_t)n_local, 24 * (size_t)n_scan);
+    const double* o = res.data() + n;
+    const int steps = (int)o[0];
+    if (steps < 1 || steps > params->iterations_max)
+        return fail(ctx, CSM_EIO, "csm_pose_graph_lm: the kernel reported %d steps", steps);
+    *lambda = o[3];
+    int64_t cg_total = 0;
+    for (int s = 0; s < steps; ++s) {
+        const double* t = o + 4 + 5 * s;
+        cg_total += (int64_t)t[4];
+        if (trace) {
+            std::memset(&trace[s], 0, sizeof(trace[s]));
+            trace[s].total_error = t[0];
+            trace[s].lambda = t[1];
+            trace[s].rhs_norm2 = t[2];
+            trace[s].residual_norm2 = t[3];
+            trace[s].cg_iterations = (int32_t)t[4];
+        }
+    }
+    if (info) {
+        std::memset(info, 0, sizeof(*info));
+        info->steps = steps;
+        info->cg_iterations = cg_total;
+        info->initial_error = o[1];
+        info->final_error = o[2];
+        info->final_lambda = o[3];
+    }
+    return CSM_OK;
+}
+
+} /* extern "C" */

@@ -10,6 +10,7 @@
  *   double res, offX, offY, rangeX, rangeY, rangeT, scoreThr, knownThr
  *   double rel[3]; double init[3 * n_queries]; double angles[n]; double ranges[n]
  *   uint16 grid[rows * cols]
+ * mode 5 (pose-graph optimizer) has a layout of its own: see run_pose_graph.
  */
 #include <cinttypes>
 #include <cstdio>
@@ -92,6 +93,53 @@ static int run_builder(FILE* f, const int32_t* hdr)
     return 0;
 }
 
+/* mode 5: PoseGraphOptimizerLMHIP. File: int32 5, n_local, n_scan, n_edges, iterations_max, loss_type;
+ * double error_tolerance, loss_scale, initial_lambda; double local[3 n_local], scan[3 n_scan];
+ * n_edges csm_pose_graph_edge records. Optimizes twice on one optimizer (the second call starts from
+ * the first's poses and lambda) and prints the poses and lambda after each call. */
+static int run_pose_graph(FILE* f, const int32_t* hdr)
+{
+    const int nl = hdr[1], ns = hdr[2], ne = hdr[3];
+    double prm[3];
+    std::vector<std::array<double, 3>> local(nl), scan(ns);
+    std::vector<csm_pose_graph_edge> raw(ne);
+    if (!rd(f, prm, 3) || !rd(f, local.data(), local.size()) || !rd(f, scan.data(), scan.size()) ||
+        !rd(f, raw.data(), raw.size()))
+        return 2;
+    std::vector<EdgePose> edges;
+    for (const csm_pose_graph_edge& r : raw) {
+        EdgePose e {};
+        e.mIsLoopConstraint = r.is_loop != 0;
+        e.mLocalMapNodeIdx = r.local_map_index;
+        e.mScanNodeIdx = r.scan_index;
+        for (int j = 0; j < 3; ++j)
+            e.mRelativePose[j] = r.relative_pose[j];
+        for (int j = 0; j < 9; ++j)
+            e.mInformationMat[j] = r.information[j];
+        edges.push_back(e);
+    }
+    using Opt = PoseGraphOptimizerLMHIP;
+    const bool cholRejected = !Opt::Create(Opt::SolverType::SparseCholesky, hdr[4], prm[0], prm[2], hdr[5], prm[1]);
+    auto opt = Opt::Create(Opt::SolverType::ConjugateGradient, hdr[4], prm[0], prm[2], hdr[5], prm[1]);
+    if (!opt) {
+        std::printf("{\"error\": \"no device\"}\n");
+        return 3;
+    }
+    std::printf("{\"cholesky_rejected\": %d, \"calls\": [", cholRejected ? 1 : 0);
+    for (int call = 0; call < 2; ++call) {
+        opt->Optimize(local, scan, edges);
+        std::printf("%s{\"lambda\": \"%a\", \"steps\": %d, \"poses\": [", call ? ", " : "", opt->Lambda(),
+                    opt->LastInfo().steps);
+        int k = 0;
+        for (const auto* v : { &local, &scan })
+            for (const auto& p : *v)
+                std::printf("%s\"%a\", \"%a\", \"%a\"", k++ ? ", " : "", p[0], p[1], p[2]);
+        std::printf("]}");
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 2)
@@ -104,8 +152,8 @@ int main(int argc, char** argv)
     double step[3] = { 0.0, 0.0, 0.0 };
     if (!rd(f, hdr, 6))
         return 2;
-    if (hdr[0] == 4) {
-        const int rc = run_builder(f, hdr);
+    if (hdr[0] == 4 || hdr[0] == 5) {
+        const int rc = hdr[0] == 4 ? run_builder(f, hdr) : run_pose_graph(f, hdr);
         std::fclose(f);
         return rc;
     }

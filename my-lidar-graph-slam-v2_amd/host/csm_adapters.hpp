@@ -28,6 +28,7 @@
 #define CSM_ADAPTERS_HPP
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -959,6 +960,90 @@ private:
     GridMapView mLatestMap;
     int mInitialCells = 0;
     std::map<std::uint64_t, csm_map_shape> mLocalShapes;
+};
+
+/* EdgePose (inc/mapping/pose_graph_edge.hpp:131-157) with the Eigen members restated as arrays:
+ * mRelativePose = { x, y, theta }, mInformationMat row-major */
+struct EdgePose {
+    bool mIsLoopConstraint;
+    int mLocalMapNodeIdx;
+    int mScanNodeIdx;
+    std::array<double, 3> mRelativePose;
+    std::array<double, 9> mInformationMat;
+};
+
+/* PoseGraphOptimizerLM (inc/mapping/pose_graph_optimizer_lm.hpp:84-160) on the device. Create()
+ * takes the constructor's arguments with the loss function as (CSM_PG_LOSS_*, scale); it returns null
+ * for SolverType SparseCholesky (not provided), NumOfIterationsMax < 1 or no device. mLambda is kept
+ * between Optimize calls, as the reference's member is. Node poses are { x, y, theta } in place of
+ * Eigen::Vector3d. */
+class PoseGraphOptimizerLMHIP final {
+public:
+    enum class SolverType { SparseCholesky, ConjugateGradient };
+
+    static std::unique_ptr<PoseGraphOptimizerLMHIP> Create(SolverType solverType, int numOfIterationsMax,
+                                                           double errorTolerance, double initialLambda,
+                                                           int lossType, double lossScale, int deviceId = 0)
+    {
+        if (solverType != SolverType::ConjugateGradient || numOfIterationsMax < 1)
+            return nullptr;
+        detail::CtxPtr ctx = detail::MakeContext(deviceId);
+        if (!ctx)
+            return nullptr;
+        csm_pose_graph_lm_params prm {};
+        prm.iterations_max = numOfIterationsMax;
+        prm.solver_type = CSM_PG_SOLVER_CONJUGATE_GRADIENT;
+        prm.loss_type = lossType;
+        prm.error_tolerance = errorTolerance;
+        prm.loss_scale = lossScale;
+        return std::unique_ptr<PoseGraphOptimizerLMHIP>(
+            new PoseGraphOptimizerLMHIP(prm, initialLambda, std::move(ctx)));
+    }
+
+    PoseGraphOptimizerLMHIP(const PoseGraphOptimizerLMHIP&) = delete;
+    PoseGraphOptimizerLMHIP& operator=(const PoseGraphOptimizerLMHIP&) = delete;
+
+    csm_ctx* Context() const { return this->mCtx.get(); }
+    double Lambda() const { return this->mLambda; }
+    /* the metrics of the last call (PoseGraphOptimizerLMMetrics: NumOfIterations, InitialError, FinalError) */
+    const csm_pose_graph_lm_info& LastInfo() const { return this->mLast; }
+
+    void Optimize(std::vector<std::array<double, 3>>& localMapNodes, std::vector<std::array<double, 3>>& scanNodes,
+                  const std::vector<EdgePose>& poseGraphEdges)
+    {
+        this->mEdges.resize(poseGraphEdges.size());
+        for (std::size_t i = 0; i < poseGraphEdges.size(); ++i) {
+            const EdgePose& e = poseGraphEdges[i];
+            csm_pose_graph_edge& d = this->mEdges[i];
+            d = csm_pose_graph_edge {};
+            d.local_map_index = e.mLocalMapNodeIdx;
+            d.scan_index = e.mScanNodeIdx;
+            d.is_loop = e.mIsLoopConstraint ? 1 : 0;
+            for (int j = 0; j < 3; ++j)
+                d.relative_pose[j] = e.mRelativePose[j];
+            for (int j = 0; j < 9; ++j)
+                d.information[j] = e.mInformationMat[j];
+        }
+        /* std::array<double, 3> is three contiguous doubles: the vectors are the flat pose arrays */
+        static_assert(sizeof(std::array<double, 3>) == 3 * sizeof(double), "pose layout");
+        CSM_ASSERT_OK(this->mCtx.get(),
+                      csm_pose_graph_lm(this->mCtx.get(), localMapNodes.empty() ? nullptr : localMapNodes.front().data(),
+                                        static_cast<std::int32_t>(localMapNodes.size()),
+                                        scanNodes.empty() ? nullptr : scanNodes.front().data(),
+                                        static_cast<std::int32_t>(scanNodes.size()), this->mEdges.data(),
+                                        static_cast<std::int32_t>(this->mEdges.size()), &this->mParams,
+                                        &this->mLambda, &this->mLast, nullptr));
+    }
+
+private:
+    PoseGraphOptimizerLMHIP(const csm_pose_graph_lm_params& prm, double lambda, detail::CtxPtr ctx) :
+        mParams(prm), mLambda(lambda), mCtx(std::move(ctx)) { }
+
+    const csm_pose_graph_lm_params mParams;
+    double mLambda;
+    detail::CtxPtr mCtx;
+    std::vector<csm_pose_graph_edge> mEdges;
+    csm_pose_graph_lm_info mLast {};
 };
 
 } /* namespace CsmHip */
