@@ -781,6 +781,10 @@ int  csm_reset_kernel_timing(csm_ctx* ctx);
 /* Library / build identification */
 const char* csm_version(void);
 
+/* Test hook: bytes of device / pinned host memory the library holds right now, over
+ * every context and group of the process. */
+int  csm_debug_live_bytes(int64_t* device, int64_t* pinned);
+
 #ifdef __cplusplus
 }
 #endif

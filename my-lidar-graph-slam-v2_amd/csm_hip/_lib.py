@@ -289,6 +289,7 @@ SIGNATURES = {
     "csm_kernel_time": (C.c_int, [_ctx, C.c_char_p, _P(C.c_double), _P(C.c_int64)]),
     "csm_reset_kernel_timing": (C.c_int, [_ctx]),
     "csm_version": (C.c_char_p, []),
+    "csm_debug_live_bytes": (C.c_int, [_P(C.c_int64), _P(C.c_int64)]),
 }
 
 _lib = None

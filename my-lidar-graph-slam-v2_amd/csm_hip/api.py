@@ -104,6 +104,13 @@ def host_map_resize(shape, box, expand=False):
                  log2_block=sh.log2_block_size), (int(shift[0]), int(shift[1])))
 
 
+def debug_live_bytes():
+    """csm_debug_live_bytes: (device, pinned) bytes the library holds, over the whole process."""
+    dev, pin = C.c_int64(0), C.c_int64(0)
+    L.load().csm_debug_live_bytes(C.byref(dev), C.byref(pin))
+    return dev.value, pin.value
+
+
 def host_window(rng, step):
     return L.load().csm_host_window(rng, step)
 
@@ -323,6 +330,9 @@ class Context:
         """Block-sparse upload (the reference's own storage): blocks[br * block_cols + bc] is a
         (2^k, 2^k) uint16 array or None for an unallocated block."""
         keep = [None if b is None else np.ascontiguousarray(b, dtype=np.uint16) for b in blocks]
+        side = 1 << log2_block
+        if any(b is not None and b.shape != (side, side) for b in keep):
+            raise ValueError("upload_grid_blocks: every block must be (%d, %d)" % (side, side))
         ptrs = (C.c_void_p * len(keep))(*[None if b is None else b.ctypes.data for b in keep])
         self._check(self.lib.csm_upload_grid_blocks(self._ctx, map_id, ptrs, block_rows, block_cols, log2_block))
         self.shapes[map_id] = (block_rows << log2_block, block_cols << log2_block)

@@ -16,9 +16,6 @@ namespace csm_host {
 
 void base_changed(DeviceGrid& g)
 {
-    for (auto& kv : g.phase)
-        if (kv.second.grid)
-            free_levels(*kv.second.grid, false);
     g.phase.clear();
     ++g.base_epoch;
 }
@@ -27,27 +24,27 @@ void free_levels(DeviceGrid& g, bool keep_base)
 {
     base_changed(g);
     if (!keep_base) {
-        if (g.xg)
-            (void)hipFree(g.xg);
-        g.xg = nullptr;
-        g.xg_cap = 0;
+        g.xg.reset();
+        g.xgf.reset();
+        g.alloc.reset();
         g.xg_stale = true;
-        if (g.xgf)
-            (void)hipFree(g.xgf);
-        g.xgf = nullptr;
-        g.xgf_cap = 0;
         g.xgf_valid = false;
-        if (g.alloc)
-            (void)hipFree(g.alloc);
-        g.alloc = nullptr;
-        g.alloc_cap = 0;
         g.alloc_user = false;
         g.alloc_stale = true;
     }
-    for (size_t i = keep_base ? 1 : 0; i < g.levels.size(); ++i)
-        if (g.levels[i].owned && g.levels[i].cells)
-            (void)hipFree(g.levels[i].cells);
     g.levels.resize(keep_base && !g.levels.empty() ? 1 : 0);
+}
+
+DeviceGrid take_grid(csm_ctx* ctx, uint64_t map_id)
+{
+    DeviceGrid g;
+    auto it = ctx->grids.find(map_id);
+    if (it != ctx->grids.end()) {
+        g = std::move(it->second);
+        ctx->grids.erase(it);
+        free_levels(g, false);
+    }
+    return g;
 }
 
 } /* namespace csm_host */
@@ -58,6 +55,15 @@ extern "C" {
 
 
 const char* csm_version(void) { return "csm_hip 0.1 (gfx950)"; }
+
+int csm_debug_live_bytes(int64_t* device, int64_t* pinned)
+{
+    if (!device || !pinned)
+        return CSM_EINVAL;
+    *device = g_live_bytes[0];
+    *pinned = g_live_bytes[1];
+    return CSM_OK;
+}
 
 int csm_create(const csm_config* cfg, csm_ctx** out)
 {
@@ -123,8 +129,8 @@ int csm_create(const csm_config* cfg, csm_ctx** out)
     ctx->stream = ctx->own_stream;
     std::vector<double> lut(65536);
     csm_host_probability_lut(lut.data());
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->lut_dev), 65536 * 8) != hipSuccess ||
-        hipMemcpy(ctx->lut_dev, lut.data(), 65536 * 8, hipMemcpyHostToDevice) != hipSuccess) {
+    if (grow(ctx, ctx->lut_dev, 65536 * 8, 65536 * 8, false) ||
+        hipMemcpy(ctx->lut_dev.p, lut.data(), 65536 * 8, hipMemcpyHostToDevice) != hipSuccess) {
         delete ctx;
         return CSM_ENOMEM;
     }
@@ -141,31 +147,6 @@ int csm_destroy(csm_ctx* ctx)
     for (auto& kv : ctx->graphs)
         (void)hipGraphExecDestroy(kv.second.exec);
     ctx->graphs.clear();
-    if (ctx->q_pin)
-        (void)hipHostFree(ctx->q_pin);
-    ctx->q_pin = nullptr;
-    for (auto& kv : ctx->grids)
-        free_levels(kv.second, false);
-    DevBuf* bufs[] = { &ctx->hits, &ctx->sorted, &ctx->tiles, &ctx->ntiles, &ctx->misc,
-                       &ctx->coarse_s, &ctx->coarse_k, &ctx->best, &ctx->dump_s, &ctx->dump_k,
-                       &ctx->scratch, &ctx->b_prod, &ctx->b_hits, &ctx->b_sorted, &ctx->b_tiles,
-                       &ctx->b_ntiles, &ctx->b_lvl, &ctx->b_best, &ctx->b_jobs, &ctx->b_out, &ctx->b_abest, &ctx->bound_stats, &ctx->b_items, &ctx->tp_items, &ctx->ph_hits, &ctx->q_dev,
-                       &ctx->fine_s, &ctx->fine_k, &ctx->tie, &ctx->ex_fine, &ctx->ex_fine_k, &ctx->ex_coarse, &ctx->ex_coarse_k,
-                       &ctx->scan_dev, &ctx->unc, &ctx->sorted_rc, &ctx->b_sorted_rc, &ctx->rec_dev, &ctx->c_scans, &ctx->c_jobs, &ctx->box_jobs,
-                       &ctx->m_rays, &ctx->m_recs, &ctx->m_cell, &ctx->m_lists, &ctx->m_cnt, &ctx->m_lut,
-                       &ctx->g_scans, &ctx->g_jobs, &ctx->g_scratch, &ctx->g_tab, &ctx->pg_buf };
-    for (DevBuf* b : bufs)
-        if (b->p)
-            (void)hipFree(b->p);
-    if (ctx->lut_dev)
-        (void)hipFree(ctx->lut_dev);
-    for (auto& kv : ctx->lane_maps)
-        if (kv.second)
-            (void)hipFree(kv.second);
-    if (ctx->pin)
-        (void)hipHostFree(ctx->pin);
-    if (ctx->pin_scans)
-        (void)hipHostFree(ctx->pin_scans);
     for (auto& kv : ctx->timers)
         for (auto& s : kv.second.spans) {
             (void)hipEventDestroy(s.a);
@@ -183,7 +164,7 @@ int csm_destroy(csm_ctx* ctx)
             (void)hipEventDestroy(e);
     if (ctx->own_stream)
         (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;                           /* the grids and buffers free themselves */
     return CSM_OK;
 }
 
@@ -211,9 +192,8 @@ int csm_upload_grid(csm_ctx* ctx, uint64_t map_id, const uint16_t* dense, int32_
     if (!ctx || !dense || rows < 1 || cols < 1)
         return fail(ctx, CSM_EINVAL, "csm_upload_grid: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DeviceGrid& g = ctx->grids[map_id];
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    free_levels(g, false);
+    DeviceGrid g = take_grid(ctx, map_id);      /* registered once it is complete */
     g.rows = rows;
     g.cols = cols;
     g.pitch = (cols + 7) & ~7;
@@ -233,27 +213,15 @@ int csm_upload_grid(csm_ctx* ctx, uint64_t map_id, const uint16_t* dense, int32_
     }
     Level base;
     const size_t bytes = (size_t)rows * g.pitch * 2;
-    if (hipMalloc(reinterpret_cast<void**>(&base.cells), bytes) != hipSuccess) {
-        ctx->grids.erase(map_id);
-        return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", bytes);
-    }
-    base.win = 1;
-    base.owned = true;
-    base.cap = bytes;
-    g.levels.push_back(base);
+    if (int rc = grow(ctx, base.own, bytes, bytes, false))
+        return rc;
+    base.cells = base.own.as<uint16_t>();
     /* GridMap::CopyValues' output goes through a pinned staging buffer of the context,
      * already in the device layout (pitched rows, pad cells 0): one contiguous DMA, no
      * device-side clearing, and the caller's buffer is free again when the call returns */
-    if (bytes > ctx->pin_cap) {
-        if (ctx->pin)
-            (void)hipHostFree(ctx->pin);
-        ctx->pin = nullptr;
-        ctx->pin_cap = 0;
-        if (hipHostMalloc(&ctx->pin, bytes + bytes / 4, hipHostMallocDefault) != hipSuccess)
-            return fail(ctx, CSM_ENOMEM, "hipHostMalloc(%zu) failed", bytes);
-        ctx->pin_cap = bytes + bytes / 4;
-    }
-    uint16_t* stage = reinterpret_cast<uint16_t*>(ctx->pin);
+    if (int rc = grow(ctx, ctx->pin, bytes, bytes + bytes / 4, false))
+        return rc;
+    uint16_t* stage = ctx->pin.as<uint16_t>();
     for (int r = 0; r < rows; ++r) {
         std::memcpy(stage + (size_t)r * g.pitch, dense + (size_t)r * cols, (size_t)cols * 2);
         if (g.pitch > cols)
@@ -261,6 +229,8 @@ int csm_upload_grid(csm_ctx* ctx, uint64_t map_id, const uint16_t* dense, int32_
     }
     HIP_TRY(ctx, hipMemcpyAsync(base.cells, stage, bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      /* the staging buffer is reused by the next upload */
+    g.levels.push_back(std::move(base));
+    ctx->grids[map_id] = std::move(g);
     return CSM_OK;
 }
 
@@ -277,41 +247,27 @@ int csm_upload_grid_blocks(csm_ctx* ctx, uint64_t map_id, const uint16_t* const*
     int n_alloc = 0;
     for (int b = 0; b < n_blocks; ++b)
         n_alloc += blocks[b] != nullptr;
-    DeviceGrid& g = ctx->grids[map_id];
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    free_levels(g, false);
+    DeviceGrid g = take_grid(ctx, map_id);      /* registered once it is complete */
     g.rows = rows;
     g.cols = cols;
     g.pitch = (cols + 7) & ~7;
     Level base;
     const size_t bytes = (size_t)rows * g.pitch * 2;
-    if (hipMalloc(reinterpret_cast<void**>(&base.cells), bytes) != hipSuccess) {
-        ctx->grids.erase(map_id);
-        return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", bytes);
-    }
-    base.win = 1;
-    base.owned = true;
-    base.cap = bytes;
-    g.levels.push_back(base);
-    if (hipMalloc(reinterpret_cast<void**>(&g.alloc), (size_t)n_blocks + 64) != hipSuccess)
-        return fail(ctx, CSM_ENOMEM, "hipMalloc(%d) failed", n_blocks + 64);
-    g.alloc_cap = (size_t)n_blocks + 64;
+    if (int rc = grow(ctx, base.own, bytes, bytes, false))
+        return rc;
+    base.cells = base.own.as<uint16_t>();
+    if (int rc = grow(ctx, g.alloc, (size_t)n_blocks + 64, (size_t)n_blocks + 64, false))
+        return rc;
     /* pinned staging: [first known row, column][slot of every block][the allocated blocks]; one DMA */
     const size_t head = (((size_t)(2 + n_blocks) * 4) + 255) & ~(size_t)255;
     const size_t stage_bytes = head + (size_t)n_alloc * block_cells * 2;
-    if (stage_bytes > ctx->pin_cap) {
-        if (ctx->pin)
-            (void)hipHostFree(ctx->pin);
-        ctx->pin = nullptr;
-        ctx->pin_cap = 0;
-        if (hipHostMalloc(&ctx->pin, stage_bytes + stage_bytes / 4, hipHostMallocDefault) != hipSuccess)
-            return fail(ctx, CSM_ENOMEM, "hipHostMalloc(%zu) failed", stage_bytes);
-        ctx->pin_cap = stage_bytes + stage_bytes / 4;
-    }
-    int32_t* h_head = reinterpret_cast<int32_t*>(ctx->pin);
+    if (int rc = grow(ctx, ctx->pin, stage_bytes, stage_bytes + stage_bytes / 4, false))
+        return rc;
+    int32_t* h_head = ctx->pin.as<int32_t>();
     h_head[0] = rows;                       /* "no known cell": what csm_upload_grid reports */
     h_head[1] = cols;
-    uint16_t* h_packed = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(ctx->pin) + head);
+    uint16_t* h_packed = reinterpret_cast<uint16_t*>(ctx->pin.as<char>() + head);
     int next = 0;
     for (int b = 0; b < n_blocks; ++b) {
         h_head[2 + b] = blocks[b] ? next : -1;
@@ -321,12 +277,13 @@ int csm_upload_grid_blocks(csm_ctx* ctx, uint64_t map_id, const uint16_t* const*
     int rc = ensure(ctx, ctx->scratch, stage_bytes);
     if (rc)
         return rc;
-    char* d_stage = reinterpret_cast<char*>(ctx->scratch.p);
-    HIP_TRY(ctx, hipMemcpyAsync(d_stage, ctx->pin, stage_bytes, hipMemcpyHostToDevice, ctx->stream));
+    char* d_stage = ctx->scratch.as<char>();
+    HIP_TRY(ctx, hipMemcpyAsync(d_stage, ctx->pin.p, stage_bytes, hipMemcpyHostToDevice, ctx->stream));
     const int grid_blocks = (int)std::min<size_t>(4096, ((size_t)rows * g.pitch + 255) / 256);
     if (int e = csm_launch::deblock(ctx->stream, grid_blocks, reinterpret_cast<const uint16_t*>(d_stage + head),
                                     reinterpret_cast<const int32_t*>(d_stage) + 2, log2_block, block_cols, rows, cols,
-                                    g.pitch, base.cells, g.alloc, n_blocks, reinterpret_cast<int32_t*>(d_stage)))
+                                    g.pitch, base.cells, g.alloc.as<uint8_t>(), n_blocks,
+                                    reinterpret_cast<int32_t*>(d_stage)))
         return launched_ok(ctx, e, "block upload");
     int32_t known[2] = { rows, cols };
     HIP_TRY(ctx, hipMemcpyAsync(known, d_stage, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -337,6 +294,8 @@ int csm_upload_grid_blocks(csm_ctx* ctx, uint64_t map_id, const uint16_t* const*
     g.alloc_bcols = block_cols;
     g.alloc_user = true;
     g.alloc_stale = false;
+    g.levels.push_back(std::move(base));
+    ctx->grids[map_id] = std::move(g);
     return CSM_OK;
 }
 
@@ -349,11 +308,9 @@ int csm_release_grid(csm_ctx* ctx, uint64_t map_id)
 {
     if (!ctx)
         return CSM_EINVAL;
-    DeviceGrid* g = find_grid(ctx, map_id);
-    if (!g)
+    if (!find_grid(ctx, map_id))
         return fail(ctx, CSM_ENOENT, "map %llu not resident", (unsigned long long)map_id);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    free_levels(*g, false);
     ctx->grids.erase(map_id);
     return CSM_OK;
 }
@@ -370,28 +327,19 @@ int csm_build_pyramid(csm_ctx* ctx, uint64_t map_id, const int32_t* win_sizes, i
     if (win_sizes[0] != 1)
         return fail(ctx, CSM_EINVAL, "win_sizes[0] must be 1 (level 0 is the grid itself)");
     free_levels(*g, true);
-    std::vector<Level> lv;
-    lv.push_back(g->levels[0]);
     for (int i = 1; i < n_levels; ++i) {
         Level l;
         if (win_sizes[i] == 1) {
-            l = g->levels[0];
-            l.owned = false;
-        } else {
-            int rc = build_level(ctx, *g, win_sizes[i], &l);
-            if (rc) {
-                for (size_t j = 1; j < lv.size(); ++j)
-                    if (lv[j].owned)
-                        (void)hipFree(lv[j].cells);
-                return rc;
-            }
+            l.cells = g->levels[0].cells;
+        } else if (int rc = build_level(ctx, *g, win_sizes[i], &l)) {
+            g->levels.resize(1);
+            return rc;
         }
-        lv.push_back(l);
+        g->levels.push_back(std::move(l));
     }
-    g->levels = lv;
     std::vector<PendingBox> pending;
     for (int i = 1; i < n_levels; ++i)
-        if (g->levels[i].owned)
+        if (g->levels[i].owned())
             pending.push_back({ g, i });
     int rc = launch_box_jobs(ctx, pending);
     if (rc)

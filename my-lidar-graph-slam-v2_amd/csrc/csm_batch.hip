@@ -96,7 +96,7 @@ int bnb_literal(csm_ctx* ctx, const csm_loop_query& q, const BatchPrep& p, const
         ej.nx = nxh;
         ej.ny = nyh;
         ej.stride = 1 << h;
-        ej.lut = ctx->lut_dev;
+        ej.lut = ctx->lut_dev.as<double>();
         ej.out_score = reinterpret_cast<double*>(ctx->ex_fine.p);
         ej.out_k = reinterpret_cast<uint32_t*>(ctx->ex_fine_k.p);
         if (int e = csm_launch::exact_scores(ctx->stream, (unsigned)((n + kBlock - 1) / kBlock), ej))
@@ -352,16 +352,9 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
     double* scans = nullptr;
     if (!resident) {
         const size_t need = scan_total * 8;
-        if (need > ctx->pin_scans_cap) {
-            if (ctx->pin_scans)
-                (void)hipHostFree(ctx->pin_scans);
-            ctx->pin_scans = nullptr;
-            ctx->pin_scans_cap = 0;
-            if (hipHostMalloc(&ctx->pin_scans, need + need / 4 + 64, hipHostMallocDefault) != hipSuccess)
-                return fail(ctx, CSM_ENOMEM, "hipHostMalloc(%zu) failed", need);
-            ctx->pin_scans_cap = need + need / 4 + 64;
-        }
-        scans = reinterpret_cast<double*>(ctx->pin_scans);
+        if (int rc = grow(ctx, ctx->pin_scans, need, need + need / 4 + 64, false))
+            return rc;
+        scans = ctx->pin_scans.as<double>();
         size_t filled = 0;                  /* scans are laid out in first-use order */
         std::vector<int> first_use;
         for (int k = 0; k < nq; ++k) {
@@ -567,7 +560,7 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
         ScoreJob& F = sj[0][k];
         F = base;
         F.cells = g.levels[p.level[0]].cells;
-        F.xg = g.xg;
+        F.xg = g.xg.as<uint32_t>();
         F.xg_pitch = g.xg_pitch;
         F.xg_pad = g.xg_pad;
         F.nx = nx;
@@ -575,7 +568,7 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
         F.stride = 1;
         F.block_best = d_best + p.best_off;
         if (bound_pass) {
-            F.xgf = g.xgf;
+            F.xgf = g.xgf.as<float>();
             F.approx_best = reinterpret_cast<float*>(ctx->b_abest.p) + p.best_off;
             /* |fp32 key - key| <= (n + 2) 2^-24 * key for a sum of n non-negative terms (one rounding
              * per fused multiply-add, one for each cell's float, one for joining the two accumulator
@@ -633,7 +626,7 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
         Z.hit_row = I.hit_row;
         Z.n_points = p.n;
         Z.score_thr = resident ? resident->windows[idx[k]].score_threshold : spec.score_thr;
-        Z.lut = ctx->lut_dev;
+        Z.lut = ctx->lut_dev.as<double>();
         Z.flags_in = d_flags + k;
         Z.out = resident ? resident->out_dev + idx[k] : d_out + k;
     }

@@ -13,24 +13,16 @@ const int kDefaultLog2Block = 4;    /* "PatchSize": 16, launcher_settings_defaul
 /* the allocation bitmap the cost function's ProbabilityOr(.., 0.5) needs */
 int ensure_allocation(csm_ctx* ctx, DeviceGrid& g)
 {
-    if (g.alloc && (g.alloc_user || !g.alloc_stale))
+    if (g.alloc.p && (g.alloc_user || !g.alloc_stale))
         return CSM_OK;
     const int log2b = g.alloc_log2 > 0 ? g.alloc_log2 : kDefaultLog2Block;
     const int brows = (g.rows + (1 << log2b) - 1) >> log2b, bcols = (g.cols + (1 << log2b) - 1) >> log2b;
     const size_t bytes = (size_t)brows * bcols;
-    if (bytes > g.alloc_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (g.alloc)
-            (void)hipFree(g.alloc);
-        g.alloc = nullptr;
-        g.alloc_cap = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&g.alloc), bytes + 64) != hipSuccess)
-            return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", bytes);
-        g.alloc_cap = bytes + 64;
-    }
-    HIP_TRY(ctx, hipMemsetAsync(g.alloc, 0, bytes, ctx->stream));
+    if (int rc = grow(ctx, g.alloc, bytes, bytes + 64, false))
+        return rc;
+    HIP_TRY(ctx, hipMemsetAsync(g.alloc.p, 0, bytes, ctx->stream));
     hipLaunchKernelGGL(k_block_allocation, dim3((unsigned)bytes), dim3(256), 0, ctx->stream,
-                       g.levels[0].cells, g.rows, g.cols, g.pitch, log2b, bcols, g.alloc);
+                       g.levels[0].cells, g.rows, g.cols, g.pitch, log2b, bcols, g.alloc.as<uint8_t>());
     HIP_TRY(ctx, hipGetLastError());
     g.alloc_log2 = log2b;
     g.alloc_bcols = bcols;
@@ -82,7 +74,7 @@ int run_cost_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n, const
         J.rows = g.rows;
         J.cols = g.cols;
         J.pitch = g.pitch;
-        J.alloc = g.alloc;
+        J.alloc = g.alloc.as<uint8_t>();
         J.log2_block = g.alloc_log2;
         J.block_cols = g.alloc_bcols;
         J.res = q.geometry.resolution;
@@ -102,7 +94,7 @@ int run_cost_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n, const
         J.convergence_threshold = prm->convergence_threshold;
         J.lambda = prm->lambda;
         J.covariance_scale = prm->covariance_scale;
-        J.lut = ctx->lut_dev;
+        J.lut = ctx->lut_dev.as<double>();
         J.out = d_out + i;
     }
     HIP_TRY(ctx, hipMemcpyAsync(d_scans, ctx->c_stage.data(), scan_total * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -160,17 +152,9 @@ int csm_set_block_allocation(csm_ctx* ctx, uint64_t map_id, int32_t log2_block_s
     const int bs = 1 << log2_block_size;
     const int brows = (g->rows + bs - 1) >> log2_block_size, bcols = (g->cols + bs - 1) >> log2_block_size;
     const size_t bytes = (size_t)brows * bcols;
-    if (bytes > g->alloc_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (g->alloc)
-            (void)hipFree(g->alloc);
-        g->alloc = nullptr;
-        g->alloc_cap = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&g->alloc), bytes + 64) != hipSuccess)
-            return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", bytes);
-        g->alloc_cap = bytes + 64;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(g->alloc, allocated, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = grow(ctx, g->alloc, bytes, bytes + 64, false))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(g->alloc.p, allocated, bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     g->alloc_bcols = bcols;
     g->alloc_user = true;

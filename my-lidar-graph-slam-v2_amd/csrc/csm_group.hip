@@ -227,10 +227,8 @@ int csm_group_destroy(csm_group* g)
         (void)hipStreamSynchronize(g->members[k]->stream);
         if (k < g->comms.size() && g->comms[k] && g->p_comm_destroy)
             (void)g->p_comm_destroy(g->comms[k]);
-        if (g->send[k].p)
-            (void)hipFree(g->send[k].p);
-        if (g->recv[k].p)
-            (void)hipFree(g->recv[k].p);
+        g->send[k].reset();
+        g->recv[k].reset();
     }
     for (csm_ctx* c : g->members)
         csm_destroy(c);

@@ -1,5 +1,6 @@
 /* csm_internal.hpp -- what the translation units of libcsm_hip.so share on the host side: the
- * context (device grids, workspaces, tuning switches, graphs), error / allocation / timing helpers.
+ * context (device grids, workspaces, tuning switches, graphs), error / timing helpers and the owners
+ * of device and pinned memory (DevBuf, PinBuf: move-only, freed by their destructors, grown by grow()).
  * csm_api.hip (matchers), csm_map_api.hip (map updates), csm_cost_api.hip (cost / covariance /
  * refinement) and csm_group.hip (several GPUs in one process) are compiled on their own. */
 #ifndef CSM_INTERNAL_HPP
@@ -24,6 +25,7 @@
 #include <thread>
 #include <tuple>
 #include <atomic>
+#include <utility>
 #include <vector>
 
 #include "csm_device.hpp"
@@ -35,17 +37,64 @@ using namespace csm;
 
 namespace csm_host {
 
-struct DevBuf {
+/* bytes held by all live owners of the process: [0] device, [1] pinned (csm_debug_live_bytes) */
+inline std::atomic<int64_t> g_live_bytes[2];
+
+/* The owner of one hipMalloc (DevBuf) or hipHostMalloc (PinBuf) block: move-only, freed by its
+ * destructor. Whoever drops a buffer that a queued kernel or copy may still read synchronises
+ * first. Grown by grow() (below), never by hand. */
+template <bool Pinned>
+struct HipBuf {
     void*  p = nullptr;
     size_t cap = 0;
-};
 
+    HipBuf() = default;
+    HipBuf(const HipBuf&) = delete;
+    HipBuf& operator=(const HipBuf&) = delete;
+    HipBuf(HipBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    HipBuf& operator=(HipBuf&& o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p = std::exchange(o.p, nullptr);
+            cap = std::exchange(o.cap, 0);
+        }
+        return *this;
+    }
+    ~HipBuf() { reset(); }
+
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    void reset()
+    {
+        if (p) {
+            (void)(Pinned ? hipHostFree(p) : hipFree(p));
+            g_live_bytes[Pinned] -= (int64_t)cap;
+        }
+        p = nullptr;
+        cap = 0;
+    }
+    bool alloc(size_t bytes)       /* into an empty owner */
+    {
+        if ((Pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes)) != hipSuccess) {
+            p = nullptr;
+            return false;
+        }
+        cap = bytes;
+        g_live_bytes[Pinned] += (int64_t)bytes;
+        return true;
+    }
+};
+using DevBuf = HipBuf<false>;
+using PinBuf = HipBuf<true>;
+
+/* A level of a map: `cells` points into its own buffer, or (a window-1 level above level 0) at the
+ * base's cells. Move-only, through `own`. */
 struct Level {
     int       win = 1;
     uint16_t* cells = nullptr;   /* pitched rows*pitch */
-    bool      owned = false;
+    DevBuf    own;               /* empty for an alias of the base */
     bool      stale = false;     /* derived from a base that was rebuilt since */
-    size_t    cap = 0;           /* bytes allocated (owned levels) */
+    bool owned() const { return own.p != nullptr; }
 };
 
 struct DeviceGrid;
@@ -60,6 +109,7 @@ struct PhaseMap {
     uint64_t epoch = 0;
 };
 
+/* Move-only (its buffers are owners): a copy does not compile. */
 struct DeviceGrid {
     int rows = 0, cols = 0, pitch = 0;
     uint64_t base_epoch = 0;          /* bumped whenever level 0's cells change */
@@ -68,19 +118,16 @@ struct DeviceGrid {
     std::vector<Level> levels;   /* levels[0] is the uploaded grid */
     /* expanded, zero-padded pair-row copy of level 0 for the fine kernel's LDS-DMA
      * staging (k_expand_pairs); rebuilt when the base changes or a window needs more padding */
-    uint32_t* xg = nullptr;
-    size_t xg_cap = 0;
+    DevBuf xg;                   /* uint32_t */
     int xg_pad = 0, xg_pitch = 0;
     bool xg_stale = true;
     /* the same layout holding float(499 v + 32268 (v != 0)) per cell: source of the fp32 bound
      * pass of the joint fine level (k_expand_pairs_f); follows xg */
-    float* xgf = nullptr;
-    size_t xgf_cap = 0;
+    DevBuf xgf;                  /* float */
     bool xgf_valid = false;
     /* block-allocation bitmap for the cost function's ProbabilityOr(.., 0.5): one byte per
      * block; the caller's (csm_set_block_allocation) or derived from the cells */
-    uint8_t* alloc = nullptr;
-    size_t alloc_cap = 0;
+    DevBuf alloc;                /* uint8_t */
     int alloc_log2 = 0, alloc_bcols = 0;
     bool alloc_user = false, alloc_stale = true;
 };
@@ -127,7 +174,7 @@ struct csm_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     std::map<uint64_t, DeviceGrid> grids;
-    double* lut_dev = nullptr;
+    DevBuf lut_dev;                  /* double[65536]: csm_host_probability_lut */
     /* workspaces */
     DevBuf hits, sorted, tiles, ntiles, misc, coarse_s, coarse_k, best, dump_s, dump_k, scratch;
     DevBuf b_prod, b_hits, b_sorted, b_tiles, b_ntiles, b_lvl, b_best, b_jobs, b_out, b_abest, bound_stats, b_items, tp_items, ph_hits;
@@ -143,18 +190,15 @@ struct csm_ctx {
     std::map<std::vector<uint64_t>, RecordedChain> graphs;
     std::map<std::vector<uint64_t>, int> graph_seen;
     bool last_graph_replayed = false;            /* csm_last_search_info: the last match was a replay */
-    void* q_pin = nullptr;           /* pinned: [ProjJob | angles | ranges] up, [record | uncertified count] back */
-    size_t q_pin_cap = 0;
+    PinBuf q_pin;                    /* [ProjJob | angles | ranges] up, [record | uncertified count] back */
     DevBuf q_dev;
     const uint32_t* tp_count_dev = nullptr;      /* blocks kept (= items of the work list) by the last two-phase search */
     int64_t tp_blocks_total = 0;                 /* ... of this many */
     int64_t last_coarse_nodes = 0, last_fine_candidates = 0, last_nominal = 0, last_block_candidates = 0;   /* csm_last_search_info */
     DevBuf fine_s, fine_k, tie, ex_fine, ex_fine_k, ex_coarse, ex_coarse_k, scan_dev, unc, sorted_rc, b_sorted_rc;
-    std::map<std::array<int, 4>, uint16_t*> lane_maps;   /* lane_map_for(): (cbx, groups, R, LS) -> device table */
-    void* pin = nullptr;          /* pinned staging of csm_upload_grid */
-    size_t pin_cap = 0;
-    void* pin_scans = nullptr;    /* pinned staging of a batch's scans */
-    size_t pin_scans_cap = 0;
+    std::map<std::array<int, 4>, DevBuf> lane_maps;   /* lane_map_for(): (cbx, groups, R, LS) -> uint16_t table */
+    PinBuf pin;                   /* staging of csm_upload_grid */
+    PinBuf pin_scans;             /* staging of a batch's scans */
     /* cost / refinement batches: device scans + job table, host staging */
     DevBuf c_scans, c_jobs, box_jobs;
     std::vector<csm::BoxJob> box_stage;
@@ -220,23 +264,30 @@ inline int fail(csm_ctx* ctx, int code, const char* fmt, ...)
                         hipGetErrorString(e_), __FILE__, __LINE__);               \
     } while (0)
 
-inline int ensure(csm_ctx* ctx, DevBuf& b, size_t bytes)
+/* The one way an owner grows: when `bytes` exceed b's capacity, free it (after the stream has
+ * drained, if it held a buffer) and allocate `want` >= bytes, the site's growth policy; the old
+ * contents are not kept. `moves_graph_inputs`: recorded graphs may point at b (alloc_epoch). */
+template <bool Pinned>
+int grow(csm_ctx* ctx, HipBuf<Pinned>& b, size_t bytes, size_t want, bool moves_graph_inputs)
 {
     if (bytes <= b.cap)
         return CSM_OK;
-    if (ctx->capturing)
-        return fail(ctx, CSM_EIO, "internal: a workspace would grow during graph capture");
-    ++ctx->alloc_epoch;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (moves_graph_inputs)
+        ++ctx->alloc_epoch;
     if (b.p)
-        HIP_TRY(ctx, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    if (hipMalloc(&b.p, want) != hipSuccess)
-        return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", want);
-    b.cap = want;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    b.reset();
+    if (!b.alloc(want))
+        return fail(ctx, CSM_ENOMEM, "%s(%zu) failed", Pinned ? "hipHostMalloc" : "hipMalloc", want);
     return CSM_OK;
+}
+
+/* a workspace of the context: 25 % + 256 bytes of slack; never grows during graph capture */
+inline int ensure(csm_ctx* ctx, DevBuf& b, size_t bytes)
+{
+    if (bytes > b.cap && ctx->capturing)
+        return fail(ctx, CSM_EIO, "internal: a workspace would grow during graph capture");
+    return grow(ctx, b, bytes, bytes + bytes / 4 + 256, true);
 }
 
 struct ScopedTimer {
@@ -292,7 +343,12 @@ inline DeviceGrid* find_grid(csm_ctx* ctx, uint64_t id)
 }
 
 /* defined in csm_api.hip */
+/* drops g's levels above the base (keep_base) or all its memory; the scalars that steer the next
+ * build (xg_pad, alloc_log2) stay. The caller has synchronised the stream. */
 void free_levels(DeviceGrid& g, bool keep_base);
+/* map_id's grid taken out of the context with its memory released (the caller has synchronised):
+ * a rebuild starts from it and is registered again only once it has succeeded */
+DeviceGrid take_grid(csm_ctx* ctx, uint64_t map_id);
 /* level 0's cells changed: drop the phase-major copies and bump base_epoch (the caller has
  * synchronised the stream that may still read them) */
 void base_changed(DeviceGrid& g);

@@ -350,44 +350,37 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
         ctx->m_lut_miss = prm->prob_miss;
     }
 
-    /* the destination grid: keep the old allocation when it is large enough */
-    DeviceGrid& g = ctx->grids[map_id];
+    /* the destination grid: keep the old allocation when it is large enough; a new one is
+     * built here and registered once the build has succeeded */
     const int pitch = (cols + 7) & ~7;
     const size_t bytes = (size_t)rows * pitch * 2;
+    DeviceGrid* dst = find_grid(ctx, map_id);
+    DeviceGrid fresh;
+    if (!keep_cells && (!dst || dst->levels.empty() || !dst->levels[0].owned() || dst->levels[0].own.cap < bytes)) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        fresh = take_grid(ctx, map_id);
+        dst = &fresh;
+        Level base;
+        if ((rc = grow(ctx, base.own, bytes + bytes / 2, bytes + bytes / 2, false))) return rc;
+        base.cells = base.own.as<uint16_t>();
+        fresh.levels.push_back(std::move(base));
+    }
+    DeviceGrid& g = *dst;
     if (keep_cells && resized) {
         /* GridMap::Resize moves the blocks (grid_map.cpp:866-879): the old cells, shifted */
         Level base;
-        const size_t want = bytes + bytes / 2;
-        if (hipMalloc(reinterpret_cast<void**>(&base.cells), want) != hipSuccess)
-            return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", want);
-        base.win = 1;
-        base.owned = true;
-        base.cap = want;
+        if ((rc = grow(ctx, base.own, bytes + bytes / 2, bytes + bytes / 2, false))) return rc;
+        base.cells = base.own.as<uint16_t>();
         const int shift_r = -shift[0], shift_c = -shift[1];
         HIP_TRY(ctx, hipMemsetAsync(base.cells, 0, bytes, ctx->stream));
         HIP_TRY(ctx, hipMemcpy2DAsync(base.cells + (size_t)shift_r * pitch + shift_c, (size_t)pitch * 2,
                                       g.levels[0].cells, (size_t)g.pitch * 2, (size_t)g.cols * 2, g.rows,
                                       hipMemcpyDeviceToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (g.levels[0].owned)
-            (void)hipFree(g.levels[0].cells);
-        g.levels[0] = base;
-    } else if (!keep_cells && (g.levels.empty() || !g.levels[0].owned || g.levels[0].cap < bytes)) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        free_levels(g, false);
-        Level base;
-        const size_t want = bytes + bytes / 2;
-        if (hipMalloc(reinterpret_cast<void**>(&base.cells), want) != hipSuccess) {
-            ctx->grids.erase(map_id);
-            return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", want);
-        }
-        base.win = 1;
-        base.owned = true;
-        base.cap = want;
-        g.levels.push_back(base);
+        g.levels[0] = std::move(base);
     }
     for (size_t i = 1; i < g.levels.size(); ++i) {
-        if (g.levels[i].owned)
+        if (g.levels[i].owned())
             g.levels[i].stale = true;
         else
             g.levels[i].cells = g.levels[0].cells;     /* an alias of the base (window 1) */
@@ -475,8 +468,7 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
     if (info)
         (void)hipEventElapsedTime(&dev_ms, ev_a, ev_b);
     if (counters[kMapError]) {
-        free_levels(g, false);          /* the cells may be half updated: drop the map */
-        ctx->grids.erase(map_id);
+        ctx->grids.erase(map_id);       /* the cells may be half updated: drop the map */
         return fail(ctx, CSM_EINVAL, "a ray leaves the resized map (flags %llu): the reference asserts",
                     counters[kMapError]);
     }
@@ -499,6 +491,8 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
         info->host_us = std::chrono::duration<double, std::micro>(t1 - t0).count();
         info->device_us = dev_ms * 1e3;
     }
+    if (dst == &fresh)
+        ctx->grids[map_id] = std::move(fresh);
     return CSM_OK;
 }
 

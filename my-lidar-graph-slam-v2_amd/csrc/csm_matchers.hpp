@@ -119,8 +119,7 @@ int launch_pairs_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, const PassPlan& p
 int launch_score_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, int n_jobs, const PassPlan& pp,
                        int n_theta_max, int n_slices, int theta_groups = 0, const JointList* list = nullptr);
 int launch_box_jobs(csm_ctx* ctx, const std::vector<PendingBox>& pending);
-int build_level(csm_ctx* ctx, DeviceGrid& g, int win, Level* out, uint16_t* reuse = nullptr,
-                size_t reuse_cap = 0);
+int build_level(csm_ctx* ctx, DeviceGrid& g, int win, Level* out);
 int level_for_window(csm_ctx* ctx, DeviceGrid& g, int win, int* index,
                      std::vector<PendingBox>* pending = nullptr);
 int ensure_xgrid(csm_ctx* ctx, DeviceGrid& g, int need_pad);

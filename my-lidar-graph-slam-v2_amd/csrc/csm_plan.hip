@@ -446,11 +446,10 @@ int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out)
     const std::array<int, 4> key = { pp.cbx, pp.groups, pp.R, pp.lstride };
     auto it = ctx->lane_maps.find(key);
     if (it != ctx->lane_maps.end()) {
-        *out = it->second;
+        *out = it->second.as<uint16_t>();
         return CSM_OK;
     }
-    uint16_t*& slot = ctx->lane_maps[key];
-    slot = nullptr;
+    DevBuf& slot = ctx->lane_maps[key];
     const int nhw = kBlock / 32, nfull = pp.cbx / 32;
     auto pos = [&](int g, int c) { return (c + (pp.R / 2) * pp.lstride * g) % 32; };
     auto passes_of = [&](const std::vector<uint16_t>& t) {
@@ -516,9 +515,10 @@ int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out)
     }
     if (passes_of(table) >= passes_of(linear))
         return CSM_OK;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot), kBlock * sizeof(uint16_t)));
-    HIP_TRY(ctx, hipMemcpy(slot, table.data(), kBlock * sizeof(uint16_t), hipMemcpyHostToDevice));
-    *out = slot;
+    if (int rc = grow(ctx, slot, kBlock * sizeof(uint16_t), kBlock * sizeof(uint16_t), false))
+        return rc;
+    HIP_TRY(ctx, hipMemcpy(slot.p, table.data(), kBlock * sizeof(uint16_t), hipMemcpyHostToDevice));
+    *out = slot.as<uint16_t>();
     return CSM_OK;
 }
 
@@ -702,30 +702,20 @@ int launch_box_jobs(csm_ctx* ctx, const std::vector<PendingBox>& pending)
     return CSM_OK;
 }
 
-/* Prepares level `win` of g for building: allocates (or reuses) its buffer and
- * records it in `pending`; the caller launches. `reuse`: a buffer of at least
- * rows * pitch * 2 bytes to build into, or null to allocate one. */
-int build_level(csm_ctx* ctx, DeviceGrid& g, int win, Level* out, uint16_t* reuse,
-                size_t reuse_cap)
+/* Prepares level `win` of g for building: into its own buffer when that is large enough, else
+ * into a new one, and records it in `pending`; the caller launches. */
+int build_level(csm_ctx* ctx, DeviceGrid& g, int win, Level* out)
 {
     if (win < 1 || win > g.rows || win > g.cols)
         return fail(ctx, CSM_EINVAL, "box-max window %d does not fit %dx%d", win, g.rows, g.cols);
     if (win > kBoxMaxWin)
         return fail(ctx, CSM_EINVAL, "box-max window %d exceeds %d", win, kBoxMaxWin);
     const size_t bytes = (size_t)g.rows * g.pitch * 2;
-    uint16_t* dst = reuse;
-    size_t cap = reuse_cap;
-    if (!dst) {
-        ++ctx->alloc_epoch;
-        if (hipMalloc(reinterpret_cast<void**>(&dst), bytes) != hipSuccess)
-            return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", bytes);
-        cap = bytes;
-    }
+    if (int rc = grow(ctx, out->own, bytes, bytes, true))
+        return rc;
     out->win = win;
-    out->cells = dst;
-    out->owned = true;
+    out->cells = out->own.as<uint16_t>();
     out->stale = false;
-    out->cap = cap;
     return CSM_OK;
 }
 
@@ -740,23 +730,11 @@ int level_for_window(csm_ctx* ctx, DeviceGrid& g, int win, int* index,
     auto finish = [&]() { return pending ? CSM_OK : launch_box_jobs(ctx, local); };
     for (size_t i = 0; i < g.levels.size(); ++i)
         if (g.levels[i].win == win) {
-            Level& have = g.levels[i];
-            if (have.stale) {
+            if (g.levels[i].stale) {
                 /* the base was rebuilt (csm_construct_map_from_scans): redo the box
                  * maximum, into the old buffer when it is large enough */
-                const size_t bytes = (size_t)g.rows * g.pitch * 2;
-                const bool fits = have.owned && have.cap >= bytes;
-                if (have.owned && !fits) {
-                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                    (void)hipFree(have.cells);
-                    have.cells = nullptr;
-                    have.cap = 0;
-                }
-                Level fresh;
-                int rc = build_level(ctx, g, win, &fresh, fits ? have.cells : nullptr, have.cap);
-                if (rc)
+                if (int rc = build_level(ctx, g, win, &g.levels[i]))
                     return rc;
-                have = fresh;
                 todo.push_back({ &g, (int)i });
             }
             *index = (int)i;
@@ -766,7 +744,7 @@ int level_for_window(csm_ctx* ctx, DeviceGrid& g, int win, int* index,
     int rc = build_level(ctx, g, win, &lv);
     if (rc)
         return rc;
-    g.levels.push_back(lv);
+    g.levels.push_back(std::move(lv));
     *index = (int)g.levels.size() - 1;
     todo.push_back({ &g, *index });
     return finish();
@@ -775,28 +753,19 @@ int level_for_window(csm_ctx* ctx, DeviceGrid& g, int win, int* index,
 /* The pair-row copy of level 0 with at least `need_pad` cells of zero padding. */
 int ensure_xgrid(csm_ctx* ctx, DeviceGrid& g, int need_pad)
 {
-    if (g.xg && !g.xg_stale && g.xg_pad >= need_pad)
+    if (g.xg.p && !g.xg_stale && g.xg_pad >= need_pad)
         return CSM_OK;
     const int pad = std::max(need_pad, g.xg_pad);
     const int prows = (g.rows + 2 * pad + 1) / 2 + 1;
     const int xp = (g.cols + 2 * pad + 1) & ~1;
     const size_t bytes = (size_t)prows * xp * 8;
-    if (bytes > g.xg_cap) {
-        ++ctx->alloc_epoch;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (g.xg)
-            (void)hipFree(g.xg);
-        g.xg = nullptr;
-        g.xg_cap = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&g.xg), bytes) != hipSuccess)
-            return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", bytes);
-        g.xg_cap = bytes;
-    }
+    if (int rc = grow(ctx, g.xg, bytes, bytes, true))
+        return rc;
     const size_t total = (size_t)prows * xp;
     const int blocks = (int)std::min<size_t>(4096, (total + 255) / 256);
     ScopedTimer tm(ctx, "expand");
     if (int rc = launched_ok(ctx, csm_launch::expand_pairs(ctx->stream, blocks, g.levels[0].cells, g.rows, g.cols, g.pitch,
-                                                            g.xg, prows, xp, pad), "pair-row copy"))
+                                                            g.xg.as<uint32_t>(), prows, xp, pad), "pair-row copy"))
         return rc;
     g.xg_pad = pad;
     g.xg_pitch = xp;
@@ -808,24 +777,16 @@ int ensure_xgrid(csm_ctx* ctx, DeviceGrid& g, int need_pad)
 /* The fp32 key copy in the layout of the (up-to-date) pair-row copy. */
 int ensure_xgrid_f(csm_ctx* ctx, DeviceGrid& g)
 {
-    if (g.xgf && g.xgf_valid)
+    if (g.xgf.p && g.xgf_valid)
         return CSM_OK;
-    if (!g.xg || g.xg_stale)
+    if (!g.xg.p || g.xg_stale)
         return fail(ctx, CSM_EINVAL, "internal: pair-row copy missing");
     const int prows = (g.rows + 2 * g.xg_pad + 1) / 2 + 1;
     const size_t bytes = (size_t)prows * g.xg_pitch * 8;
-    if (bytes > g.xgf_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (g.xgf)
-            (void)hipFree(g.xgf);
-        g.xgf = nullptr;
-        g.xgf_cap = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&g.xgf), bytes) != hipSuccess)
-            return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", bytes);
-        g.xgf_cap = bytes;
-    }
+    if (int rc = grow(ctx, g.xgf, bytes, bytes, false))
+        return rc;
     ScopedTimer tm(ctx, "expand");
-    const int e = csm::launch_expand_pairs_f(ctx->stream, g.levels[0].cells, g.rows, g.cols, g.pitch, g.xgf, prows,
+    const int e = csm::launch_expand_pairs_f(ctx->stream, g.levels[0].cells, g.rows, g.cols, g.pitch, g.xgf.as<float>(), prows,
                                              g.xg_pitch, g.xg_pad);
     if (e != 0)
         return fail(ctx, CSM_EIO, "k_expand_pairs_f launch failed: %s", hipGetErrorString((hipError_t)e));

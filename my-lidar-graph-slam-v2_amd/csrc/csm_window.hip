@@ -80,7 +80,7 @@ int run_level_pass_joint(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const
     fj.flags = flags;
     fj.min_known = w->min_known;
     fj.cells = g.levels[0].cells;
-    fj.xg = g.xg;
+    fj.xg = g.xg.as<uint32_t>();
     fj.xg_pitch = g.xg_pitch;
     fj.xg_pad = g.xg_pad;
     fj.nx = p.nx;
@@ -284,7 +284,7 @@ int run_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
     const BlockBest* tp_reduced = nullptr;
     ScoreJob fj = base;
     fj.cells = g.levels[0].cells;
-    fj.xg = g.xg;
+    fj.xg = g.xg.as<uint32_t>();
     fj.xg_pitch = g.xg_pitch;
     fj.xg_pad = g.xg_pad;
     fj.nx = p.nx;
@@ -453,7 +453,7 @@ int run_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
     fin.hit_row = hit_row_dev;
     fin.n_points = p.n;
     fin.score_thr = w->score_threshold;
-    fin.lut = ctx->lut_dev;
+    fin.lut = ctx->lut_dev.as<double>();
     fin.flags_in = flags;
     fin.flags_clear = flags_next;
     fin.out = out_dev;
@@ -493,13 +493,12 @@ int ensure_phase_map(csm_ctx* ctx, DeviceGrid& g, int level, int need, PhaseMap*
     pg.known_c0 = 0;
     Level base;
     const size_t bytes = (size_t)pg.rows * pg.pitch * 2;
-    if (hipMalloc(reinterpret_cast<void**>(&base.cells), bytes) != hipSuccess)
-        return fail(ctx, CSM_ENOMEM, "hipMalloc(%zu) failed", bytes);
-    base.win = 1;
-    base.owned = true;
-    base.cap = bytes;
-    pg.levels.push_back(base);
-    const int e = csm::launch_phase_map(ctx->stream, src, g.rows, g.cols, g.pitch, L, hp, wp, pad, base.cells, pg.pitch);
+    if (int rc = grow(ctx, base.own, bytes, bytes, false))
+        return rc;
+    base.cells = base.own.as<uint16_t>();
+    pg.levels.push_back(std::move(base));
+    const int e = csm::launch_phase_map(ctx->stream, src, g.rows, g.cols, g.pitch, L, hp, wp, pad, pg.levels[0].cells,
+                                        pg.pitch);
     if (e)
         return fail(ctx, CSM_EIO, "k_phase_map launch failed: %s", hipGetErrorString((hipError_t)e));
     pm.hp = hp;
@@ -615,7 +614,7 @@ int resolve_ties(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p
     tj.hit_row = row_dev;
     tj.n_points = p.n;
     tj.score_thr = w->score_threshold;
-    tj.lut = ctx->lut_dev;
+    tj.lut = ctx->lut_dev.as<double>();
     tj.out = out_dev;
     uint32_t n = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&n, count, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -651,7 +650,7 @@ int resolve_literal(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan
     ej.n_points = p.n;
     ej.x_lo = p.x_lo;
     ej.y_lo = p.y_lo;
-    ej.lut = ctx->lut_dev;
+    ej.lut = ctx->lut_dev.as<double>();
     ExactJob cj = ej;
     cj.cells = g.levels[w->coarse_level].cells;
     cj.nx = p.nxc;
@@ -879,19 +878,9 @@ int csm_correlative_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
     const size_t job_bytes = (sizeof(ProjJob) + 255) & ~(size_t)255;
     const size_t up_bytes = job_bytes + (size_t)n * 16;
     const size_t pin_bytes = up_bytes + 256;
-    if (pin_bytes > ctx->q_pin_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->q_pin)
-            (void)hipHostFree(ctx->q_pin);
-        ctx->q_pin = nullptr;
-        ctx->q_pin_cap = 0;
-        ++ctx->alloc_epoch;
-        if (hipHostMalloc(&ctx->q_pin, pin_bytes + pin_bytes / 4, hipHostMallocDefault) != hipSuccess)
-            return fail(ctx, CSM_ENOMEM, "hipHostMalloc(%zu) failed", pin_bytes);
-        ctx->q_pin_cap = pin_bytes + pin_bytes / 4;
-    }
+    if ((rc = grow(ctx, ctx->q_pin, pin_bytes, pin_bytes + pin_bytes / 4, true))) return rc;
     if ((rc = ensure(ctx, ctx->q_dev, up_bytes))) return rc;
-    char* pin = reinterpret_cast<char*>(ctx->q_pin);
+    char* pin = ctx->q_pin.as<char>();
     char* qd = reinterpret_cast<char*>(ctx->q_dev.p);
     double* ang_dev = reinterpret_cast<double*>(qd + job_bytes);
     double* rng_dev = ang_dev + n;
@@ -938,7 +927,7 @@ int csm_correlative_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
     /* what a graph of this chain has baked in */
     std::vector<uint64_t> key = {
         ctx->alloc_epoch, (uint64_t)(uintptr_t)ctx->stream, (uint64_t)(uintptr_t)g->levels[0].cells,
-        (uint64_t)(uintptr_t)g->levels[level].cells, (uint64_t)(uintptr_t)g->xg, (uint64_t)g->xg_pad,
+        (uint64_t)(uintptr_t)g->levels[level].cells, (uint64_t)(uintptr_t)g->xg.p, (uint64_t)g->xg_pad,
         (uint64_t)g->rows, (uint64_t)g->cols, (uint64_t)g->known_r0, (uint64_t)g->known_c0,
         (uint64_t)w.n_theta, (uint64_t)n, (uint64_t)w.win_x, (uint64_t)w.win_y, (uint64_t)w.low_resolution,
         (uint64_t)(uint32_t)w.min_known, (uint64_t)w.merge_mode, 0 };
@@ -1140,7 +1129,7 @@ int csm_grid_search_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
         gj.n_points = n;
         gj.min_known = csm_host_min_known(n, prm->known_rate_threshold);
         gj.score_thr = prm->score_threshold;
-        gj.lut = ctx->lut_dev;
+        gj.lut = ctx->lut_dev.as<double>();
         gj.out_score = reinterpret_cast<double*>(ctx->ex_fine.p);
         gj.out_k = reinterpret_cast<uint32_t*>(ctx->ex_fine_k.p);
         gj.best_bits = d_best;

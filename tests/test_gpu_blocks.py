@@ -84,3 +84,13 @@ def test_block_upload_matches_dense_upload_in_search_and_cost(gpu_ctx, oracle):
         assert np.array_equal(np.asarray(ra[key]), np.asarray(rb[key])), key
     gpu_ctx.release_grid(811)
     gpu_ctx.release_grid(812)
+
+
+def test_misshaped_block_is_refused_before_upload(gpu_ctx):
+    """A block that is not (2^k, 2^k) raises before the library reads it; the id is not resident."""
+    k, br, bc = 4, 3, 2
+    blocks = [np.ones((16, 16), np.uint16) for _ in range(br * bc)]
+    blocks[4] = np.ones((16, 8), np.uint16)
+    with pytest.raises(ValueError):
+        gpu_ctx.upload_grid_blocks(821, blocks, br, bc, k)
+    assert not gpu_ctx.has_grid(821)
