@@ -401,11 +401,8 @@ int  csm_copy_last_batch_records(csm_ctx* ctx, csm_result* dst_dev);
  * Map reads are GridMap::ProbabilityOr(row, col, 0.5)
  * (src/grid_map_new/grid_map.cpp:423-436): 0.5 outside the map or in a block
  * that was never allocated, the cell's probability (0 for unknown) otherwise.
- * Allocation is not part of the dense export: pass it with
- * csm_set_block_allocation. Without it a block counts as allocated iff it
- * holds a known cell -- exact for maps that were only ever updated (finished
- * local maps: every update leaves a value >= 1, grid_map.cpp:514-535), not for
- * a map that was cleared with ResetValues() (the frontend's latest map). */
+ * Allocation is not part of the dense export; the library keeps it per map
+ * (rules beside csm_set_block_allocation). */
 typedef struct {
     double  covariance_scale;       /* CostSquareError: "CovarianceScale" */
     int32_t iterations_max;         /* "NumOfIterationsMax" */
@@ -432,8 +429,23 @@ typedef struct {
 
 /* allocated: one byte per block (non-zero = allocated), row-major
  * [ceil(rows / 2^log2)][ceil(cols / 2^log2)]: GridMap::IsAllocated of any cell
- * of the block. Null: back to the rule above with this block size. Must be
- * repeated after the map is uploaded again. */
+ * of the block. Null: the rule "a block is allocated iff it holds a known
+ * cell" on blocks of 2^log2 cells (log2 0: every cell its own block).
+ *
+ * Each map carries the reference's allocation state:
+ *  - csm_upload_grid: the rule, on 16-cell blocks ("PatchSize" 16). Exact for
+ *    maps that were only ever updated (every update leaves a value >= 1 and
+ *    allocates its block, grid_map.cpp:514-535, 645-700).
+ *  - csm_upload_grid_blocks: its blocks; a NULL block is unallocated.
+ *  - csm_set_block_allocation: as given, until the map changes.
+ *  - csm_construct_map_from_scans, csm_update_map_with_scan: the old map's
+ *    blocks moved by the block shift of Resize / Expand (the ones outside the
+ *    new map dropped; ResetValues keeps them allocated, grid_map.cpp:278-287,
+ *    841-936), plus every block a cell update touched, on blocks of
+ *    shape->log2_block_size. The old map is the resident map_id if its rows
+ *    and cols are shape's: its bitmap if that is on shape's blocks, else the
+ *    rule on them. If map_id is not resident or its rows or cols differ,
+ *    nothing was allocated (a fresh GridMap). */
 int  csm_set_block_allocation(csm_ctx* ctx, uint64_t map_id, int32_t log2_block_size,
                               const uint8_t* allocated);
 /* Cost / n and ComputeCovariance at sensor_poses[i] (3 doubles per query: the

@@ -29,7 +29,8 @@ void free_levels(DeviceGrid& g, bool keep_base)
         g.alloc.reset();
         g.xg_stale = true;
         g.xgf_valid = false;
-        g.alloc_user = false;
+        g.alloc_log2 = kDefaultLog2Block;     /* back to the rule of a dense upload */
+        g.alloc_derived = true;
         g.alloc_stale = true;
     }
     g.levels.resize(keep_base && !g.levels.empty() ? 1 : 0);
@@ -292,7 +293,7 @@ int csm_upload_grid_blocks(csm_ctx* ctx, uint64_t map_id, const uint16_t* const*
     g.known_c0 = known[1];
     g.alloc_log2 = log2_block;
     g.alloc_bcols = block_cols;
-    g.alloc_user = true;
+    g.alloc_derived = false;
     g.alloc_stale = false;
     g.levels.push_back(std::move(base));
     ctx->grids[map_id] = std::move(g);

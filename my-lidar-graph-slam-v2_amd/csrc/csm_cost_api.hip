@@ -6,30 +6,48 @@
 #include "csm_cost_kernels.hip"
 
 
+namespace csm_host {
+
 namespace {
 
-const int kDefaultLog2Block = 4;    /* "PatchSize": 16, launcher_settings_default.json:178 */
-
-/* the allocation bitmap the cost function's ProbabilityOr(.., 0.5) needs */
-int ensure_allocation(csm_ctx* ctx, DeviceGrid& g)
+int launch_block_allocation(csm_ctx* ctx, DeviceGrid& g, int log2b, const uint8_t* carried, int carried_brows,
+                            int carried_bcols, int carried_br0, int carried_bc0)
 {
-    if (g.alloc.p && (g.alloc_user || !g.alloc_stale))
-        return CSM_OK;
-    const int log2b = g.alloc_log2 > 0 ? g.alloc_log2 : kDefaultLog2Block;
     const int brows = (g.rows + (1 << log2b) - 1) >> log2b, bcols = (g.cols + (1 << log2b) - 1) >> log2b;
     const size_t bytes = (size_t)brows * bcols;
+    if (bytes > 0x7fffffff)
+        return fail(ctx, CSM_EINVAL, "block allocation: %zu blocks", bytes);
     if (int rc = grow(ctx, g.alloc, bytes, bytes + 64, false))
         return rc;
-    HIP_TRY(ctx, hipMemsetAsync(g.alloc.p, 0, bytes, ctx->stream));
     hipLaunchKernelGGL(k_block_allocation, dim3((unsigned)bytes), dim3(256), 0, ctx->stream,
-                       g.levels[0].cells, g.rows, g.cols, g.pitch, log2b, bcols, g.alloc.as<uint8_t>());
+                       g.levels[0].cells, g.rows, g.cols, g.pitch, log2b, bcols, carried, carried_brows,
+                       carried_bcols, carried_br0, carried_bc0, g.alloc.as<uint8_t>());
     HIP_TRY(ctx, hipGetLastError());
     g.alloc_log2 = log2b;
     g.alloc_bcols = bcols;
-    g.alloc_user = false;
     g.alloc_stale = false;
     return CSM_OK;
 }
+
+} /* namespace */
+
+int ensure_allocation(csm_ctx* ctx, DeviceGrid& g)
+{
+    if (!g.alloc_stale)
+        return CSM_OK;          /* current, or a bitmap as given / carried (never stale) */
+    return launch_block_allocation(ctx, g, g.alloc_log2, nullptr, 0, 0, 0, 0);
+}
+
+int build_allocation(csm_ctx* ctx, DeviceGrid& g, int log2b, const uint8_t* carried, int carried_brows,
+                     int carried_bcols, int carried_br0, int carried_bc0)
+{
+    g.alloc_derived = false;
+    return launch_block_allocation(ctx, g, log2b, carried, carried_brows, carried_bcols, carried_br0, carried_bc0);
+}
+
+} /* namespace csm_host */
+
+namespace {
 
 /* poses: n x 3 sensor poses (sensor_given) or null = Compound(query initial pose, relative sensor pose) */
 int run_cost_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n, const double* sensor_poses,
@@ -145,7 +163,7 @@ int csm_set_block_allocation(csm_ctx* ctx, uint64_t map_id, int32_t log2_block_s
         return fail(ctx, CSM_ENOENT, "map %llu not resident", (unsigned long long)map_id);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     g->alloc_log2 = log2_block_size;
-    g->alloc_user = false;
+    g->alloc_derived = true;
     g->alloc_stale = true;
     if (!allocated)
         return CSM_OK;              /* back to the rule "a block with a known cell is allocated" */
@@ -157,7 +175,7 @@ int csm_set_block_allocation(csm_ctx* ctx, uint64_t map_id, int32_t log2_block_s
     HIP_TRY(ctx, hipMemcpyAsync(g->alloc.p, allocated, bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     g->alloc_bcols = bcols;
-    g->alloc_user = true;
+    g->alloc_derived = false;
     g->alloc_stale = false;
     return CSM_OK;
 }

@@ -19,25 +19,35 @@ namespace csm {
 
 constexpr int kCostBlock = 256;
 
-/* allocated[b] = 1 iff block b holds a known (non-zero) cell: exactly the
- * reference's allocation state for a map that was only ever updated (every
- * update leaves a value >= 1 and allocates the block on the way,
- * src/grid_map_new/grid_map.cpp:514-535). */
+/* allocated[b] = 1 iff block b holds a known (non-zero) cell or its block
+ * (br + carried_br0, bc + carried_bc0) of `carried` (null: none) is allocated,
+ * else 0. Every update leaves a value >= 1 and allocates its block
+ * (src/grid_map_new/grid_map.cpp:514-535, 645-700); Resize and Expand move the
+ * blocks of the old map that overlap the new one (:841-889, 915-936) and
+ * ResetValues keeps them allocated (:278-287). One workgroup per block. */
 __global__ __launch_bounds__(256) void k_block_allocation(const uint16_t* __restrict__ cells, int rows, int cols,
                                                          int pitch, int log2_block, int block_cols,
+                                                         const uint8_t* __restrict__ carried, int carried_brows,
+                                                         int carried_bcols, int carried_br0, int carried_bc0,
                                                          uint8_t* __restrict__ allocated)
 {
     const int b = blockIdx.x;
     const int br = b / block_cols, bc = b % block_cols;
     const int bs = 1 << log2_block;
     bool any = false;
+    if (carried && threadIdx.x == 0) {
+        const int orow = br + carried_br0, ocol = bc + carried_bc0;
+        any = orow >= 0 && orow < carried_brows && ocol >= 0 && ocol < carried_bcols &&
+              carried[(size_t)orow * carried_bcols + ocol] != 0;
+    }
     for (int i = threadIdx.x; i < bs * bs; i += 256) {
         const int r = (br << log2_block) + (i >> log2_block), c = (bc << log2_block) + (i & (bs - 1));
         if (r < rows && c < cols && cells[(size_t)r * pitch + c] != 0)
             any = true;
     }
-    if (__syncthreads_or(any) && threadIdx.x == 0)
-        allocated[b] = 1;
+    const bool set = __syncthreads_or(any);
+    if (threadIdx.x == 0)
+        allocated[b] = set ? 1 : 0;
 }
 
 struct CostTerms {

@@ -109,6 +109,9 @@ struct PhaseMap {
     uint64_t epoch = 0;
 };
 
+/* "PatchSize": 16 (launcher_settings_default.json:178): the block size of maps uploaded dense */
+constexpr int kDefaultLog2Block = 4;
+
 /* Move-only (its buffers are owners): a copy does not compile. */
 struct DeviceGrid {
     int rows = 0, cols = 0, pitch = 0;
@@ -125,11 +128,14 @@ struct DeviceGrid {
      * pass of the joint fine level (k_expand_pairs_f); follows xg */
     DevBuf xgf;                  /* float */
     bool xgf_valid = false;
-    /* block-allocation bitmap for the cost function's ProbabilityOr(.., 0.5): one byte per
-     * block; the caller's (csm_set_block_allocation) or derived from the cells */
+    /* block-allocation bitmap for the cost function's ProbabilityOr(.., 0.5): one byte per block
+     * of 2^alloc_log2 x 2^alloc_log2 cells. alloc_derived: it follows the cells (a block is
+     * allocated iff it holds a known cell) and is rebuilt when alloc_stale. Otherwise it is the
+     * reference's state as given (csm_set_block_allocation, csm_upload_grid_blocks) or carried
+     * through the map builds, and never stale (include/csm_hip.h, csm_set_block_allocation). */
     DevBuf alloc;                /* uint8_t */
-    int alloc_log2 = 0, alloc_bcols = 0;
-    bool alloc_user = false, alloc_stale = true;
+    int alloc_log2 = kDefaultLog2Block, alloc_bcols = 0;
+    bool alloc_derived = true, alloc_stale = true;
 };
 
 struct TimedSpan {
@@ -216,6 +222,7 @@ struct csm_ctx {
     std::vector<csm_result> rec_patch;            /* host copies of records fixed up after the device pass */
     /* map building */
     DevBuf m_rays, m_recs, m_cell, m_lists, m_cnt, m_lut;
+    DevBuf m_alloc;                               /* the old map's allocation bitmap during a build */
     double m_lut_hit = -1.0, m_lut_miss = -1.0;   /* probabilities the update tables were built for */
     bool m_apply_attr = false;
     hipEvent_t m_ev[2] = { nullptr, nullptr };    /* device_us of csm_map_build_info */
@@ -344,7 +351,7 @@ inline DeviceGrid* find_grid(csm_ctx* ctx, uint64_t id)
 
 /* defined in csm_api.hip */
 /* drops g's levels above the base (keep_base) or all its memory; the scalars that steer the next
- * build (xg_pad, alloc_log2) stay. The caller has synchronised the stream. */
+ * build (xg_pad) stay. The caller has synchronised the stream. */
 void free_levels(DeviceGrid& g, bool keep_base);
 /* map_id's grid taken out of the context with its memory released (the caller has synchronised):
  * a rebuild starts from it and is registered again only once it has succeeded */
@@ -352,6 +359,16 @@ DeviceGrid take_grid(csm_ctx* ctx, uint64_t map_id);
 /* level 0's cells changed: drop the phase-major copies and bump base_epoch (the caller has
  * synchronised the stream that may still read them) */
 void base_changed(DeviceGrid& g);
+
+/* defined in csm_cost_api.hip */
+/* g.alloc made current: a derived bitmap that is stale is rebuilt from the cells */
+int ensure_allocation(csm_ctx* ctx, DeviceGrid& g);
+/* g.alloc after a map build (g's rows, cols and cells are the new map's), on blocks of 2^log2b:
+ * block (br, bc) is allocated iff block (br + carried_br0, bc + carried_bc0) of `carried`
+ * (carried_brows x carried_bcols, null = nothing) is, or it holds a known cell. Queued on
+ * ctx->stream; `carried` must stay alive until the stream has drained. */
+int build_allocation(csm_ctx* ctx, DeviceGrid& g, int log2b, const uint8_t* carried, int carried_brows,
+                     int carried_bcols, int carried_br0, int carried_bc0);
 
 } /* namespace csm_host */
 using namespace csm_host;

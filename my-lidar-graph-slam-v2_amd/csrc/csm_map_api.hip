@@ -350,6 +350,31 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
         ctx->m_lut_miss = prm->prob_miss;
     }
 
+    /* The old map's block allocation, which Resize / Expand move and ResetValues keeps
+     * (grid_map.cpp:278-287, 841-889, 915-936): the resident map_id's, if its rows and cols
+     * are the shape's; its bitmap if that is on the shape's blocks, else the rule "a block with a
+     * known cell is allocated" on them. Otherwise nothing was allocated. It moves to
+     * ctx->m_alloc (the grid's bitmap buffer takes m_alloc's place) until the new bitmap is built. */
+    const int lb = shape->log2_block_size;
+    int carried_brows = 0, carried_bcols = 0;
+    bool carried = false;
+    if (DeviceGrid* old = find_grid(ctx, map_id)) {
+        if (!old->levels.empty() && old->rows == shape->rows && old->cols == shape->cols) {
+            if (old->alloc_derived || old->alloc_log2 != lb) {
+                old->alloc_stale |= old->alloc_log2 != lb || !old->alloc_derived;
+                old->alloc_derived = true;
+                old->alloc_log2 = lb;
+            }
+            if ((rc = ensure_allocation(ctx, *old))) return rc;
+            carried = true;
+            carried_brows = (old->rows + (1 << lb) - 1) >> lb;
+            carried_bcols = old->alloc_bcols;
+        }
+        std::swap(ctx->m_alloc, old->alloc);
+        old->alloc_derived = true;          /* until the build below has finished */
+        old->alloc_stale = true;
+    }
+
     /* the destination grid: keep the old allocation when it is large enough; a new one is
      * built here and registered once the build has succeeded */
     const int pitch = (cols + 7) & ~7;
@@ -391,8 +416,6 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     base_changed(g);
     g.xg_stale = true;         /* the pair-row copy follows the base */
-    g.alloc_stale = true;      /* and so does the derived block-allocation bitmap */
-    g.alloc_user = false;
     g.rows = rows;
     g.cols = cols;
     g.pitch = pitch;
@@ -458,6 +481,12 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
                 256, ceil_div((int)std::min<long long>(usable, (long long)n_cells), 4));
             hipLaunchKernelGGL(k_map_apply_hits, dim3(wgs), dim3(256), 65536 * sizeof(uint16_t), ctx->stream, mj);
         }
+        HIP_TRY(ctx, hipGetLastError());
+        /* the old allocation moved by the block shift, and every block a cell update touched
+         * (each leaves a known cell) */
+        if ((rc = build_allocation(ctx, g, lb, carried ? ctx->m_alloc.as<uint8_t>() : nullptr, carried_brows,
+                                   carried_bcols, shift[0] / (1 << lb), shift[1] / (1 << lb))))
+            return rc;
     }
     HIP_TRY(ctx, hipGetLastError());
     if (info)

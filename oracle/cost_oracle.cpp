@@ -246,11 +246,14 @@ struct OrcRefineResult {
 
 /* ScanMatcherLinearSolver::OptimizePose + OptimizeStep:
  * scan_matcher_linear_solver.cpp:66-169. lambda: the object's damping factor
- * when the call starts (InitialLambda on the first call). */
-void orc_linear_solver(const OrcCostGrid* g, const double* angles, const double* ranges, int n,
-                       const double rel[3], const double initialPose[3], int iterationsMax,
-                       double convergenceThreshold, double lambda, double covarianceScale,
-                       OrcRefineResult* out)
+ * when the call starts (InitialLambda on the first call). trace (null: none):
+ * per iteration k < traceCap, (cost before the step, cost after it, the damping
+ * factor the step used) at trace[3k .. 3k + 2] -- what the stop test and the
+ * damping update of that iteration decided on. */
+void orc_linear_solver_trace(const OrcCostGrid* g, const double* angles, const double* ranges, int n,
+                             const double rel[3], const double initialPose[3], int iterationsMax,
+                             double convergenceThreshold, double lambda, double covarianceScale,
+                             OrcRefineResult* out, double* trace, int traceCap)
 {
     orc_compound(initialPose, rel, out->sensorPose);
     const double initialCost = orc_cost(g, angles, ranges, n, out->sensorPose);
@@ -270,6 +273,11 @@ void orc_linear_solver(const OrcCostGrid* g, const double* angles, const double*
         best[1] += delta[1];
         best[2] += delta[2];
         cost = orc_cost(g, angles, ranges, n, best);
+        if (trace && iterations < traceCap) {
+            trace[3 * iterations] = prevCost;
+            trace[3 * iterations + 1] = cost;
+            trace[3 * iterations + 2] = lambda;
+        }
         if (++iterations >= iterationsMax || std::fabs(prevCost - cost) < convergenceThreshold)
             break;
         if (cost < prevCost)
@@ -284,6 +292,16 @@ void orc_linear_solver(const OrcCostGrid* g, const double* angles, const double*
     orc_covariance(g, angles, ranges, n, best, covarianceScale, out->covariance);
     out->lambda = lambda;
     out->iterations = iterations;
+}
+
+/* the same without the trace (the entry point's original signature) */
+void orc_linear_solver(const OrcCostGrid* g, const double* angles, const double* ranges, int n,
+                       const double rel[3], const double initialPose[3], int iterationsMax,
+                       double convergenceThreshold, double lambda, double covarianceScale,
+                       OrcRefineResult* out)
+{
+    orc_linear_solver_trace(g, angles, ranges, n, rel, initialPose, iterationsMax, convergenceThreshold, lambda,
+                            covarianceScale, out, nullptr, 0);
 }
 
 } /* extern "C" */

@@ -26,8 +26,12 @@
  * cross-check it against an independent closed form.
  *
  * The dense array stands for GridMap<GridBinaryBayes>: unallocated blocks read
- * as 0 (unknown) and ConstructMapFromScans resets every kept block, so the
- * block structure only matters for the geometry, which is restated exactly.
+ * as 0 (unknown) and ConstructMapFromScans resets every kept block. Which
+ * blocks are allocated (what the cost function's ProbabilityOr(.., 0.5) sees)
+ * is tracked beside it in a bitmap of one byte per block: Resize and Expand
+ * move the old blocks that overlap the new map and drop the rest
+ * (grid_map.cpp:841-889, 915-936), ResetValues keeps them allocated
+ * (:278-287), and every cell update allocates its block (:645-700).
  * Build with -ffp-contract=off (the reference is plain x86-64, no FMA).
  */
 #include <algorithm>
@@ -215,8 +219,8 @@ struct OrcBuilderParams {
 /* Steps 1-2 of ConstructMapFromScans (grid_map_builder.cpp:583-645): the
  * bounding box of the sensor positions and the usable hit points, then
  * GridMap::Resize on the map's CURRENT geometry. `shape` is updated in place. */
-int orc_map_resize(OrcMapShape* shape, const double mapPose[3], const OrcScanNode* nodes,
-                   int nNodes, const OrcBuilderParams* prm)
+int orc_map_resize_shift(OrcMapShape* shape, const double mapPose[3], const OrcScanNode* nodes,
+                         int nNodes, const OrcBuilderParams* prm, int* rowMinOut, int* colMinOut)
 {
     if (nNodes < 1)
         return 1;
@@ -264,7 +268,35 @@ int orc_map_resize(OrcMapShape* shape, const double mapPose[3], const OrcScanNod
     shape->cols = (bMaxX - bMinX) << shape->log2Block;
     shape->offX += shape->res * colMin;            /* grid_map_geometry.cpp:61-72 */
     shape->offY += shape->res * rowMin;
+    if (rowMinOut)
+        *rowMinOut = rowMin;                       /* the new map's first cell in the old frame */
+    if (colMinOut)
+        *colMinOut = colMin;
     return 0;
+}
+
+/* the same without the shift (the entry point's original signature) */
+int orc_map_resize(OrcMapShape* shape, const double mapPose[3], const OrcScanNode* nodes,
+                   int nNodes, const OrcBuilderParams* prm)
+{
+    return orc_map_resize_shift(shape, mapPose, nodes, nNodes, prm, nullptr, nullptr);
+}
+
+/* The block move of GridMap::Resize (grid_map.cpp:857-879) on the allocation
+ * bitmaps: new block (row - bMinY, col - bMinX) takes old block (row, col) for
+ * every old block inside the new map, the others start unallocated. old: oldRows
+ * x oldCols blocks or null (nothing allocated). */
+void orc_map_move_blocks(const uint8_t* old, int oldRows, int oldCols, int bMinY, int bMinX,
+                         uint8_t* out, int newRows, int newCols)
+{
+    std::memset(out, 0, static_cast<size_t>(newRows) * newCols);
+    if (!old)
+        return;
+    const int r0 = std::max(0, bMinY), r1 = std::min(oldRows, bMinY + newRows);
+    const int c0 = std::max(0, bMinX), c1 = std::min(oldCols, bMinX + newCols);
+    for (int row = r0; row < r1; ++row)
+        for (int col = c0; col < c1; ++col)
+            out[static_cast<size_t>(row - bMinY) * newCols + (col - bMinX)] = old[static_cast<size_t>(row) * oldCols + col];
 }
 
 /* Step 3 (grid_map_builder.cpp:647-692) on a zeroed dense array of the resized
@@ -273,12 +305,22 @@ int orc_map_resize(OrcMapShape* shape, const double mapPose[3], const OrcScanNod
  * walk (the reference asserts). Returns nonzero if an update leaves the map. */
 static int map_integrate(const OrcMapShape* shape, const double mapPose[3], const OrcScanNode* nodes,
                          int nNodes, const OrcBuilderParams* prm, uint16_t* grid, long long* stats,
-                         bool reset);
+                         bool reset, uint8_t* alloc);
 
 int orc_map_integrate(const OrcMapShape* shape, const double mapPose[3], const OrcScanNode* nodes,
                       int nNodes, const OrcBuilderParams* prm, uint16_t* grid, long long* stats)
 {
-    return map_integrate(shape, mapPose, nodes, nNodes, prm, grid, stats, true);
+    return map_integrate(shape, mapPose, nodes, nNodes, prm, grid, stats, true, nullptr);
+}
+
+/* The same, tracking allocation: alloc = the allocation bitmap of the resized
+ * map, one byte per block, row-major [rows >> log2Block][cols >> log2Block];
+ * every updated cell's block is marked. */
+int orc_map_integrate_alloc(const OrcMapShape* shape, const double mapPose[3], const OrcScanNode* nodes,
+                            int nNodes, const OrcBuilderParams* prm, uint16_t* grid, long long* stats,
+                            uint8_t* alloc)
+{
+    return map_integrate(shape, mapPose, nodes, nNodes, prm, grid, stats, true, alloc);
 }
 
 /* The update loop of GridMapBuilder::UpdateGridMap (grid_map_builder.cpp:446-477):
@@ -286,7 +328,14 @@ int orc_map_integrate(const OrcMapShape* shape, const double mapPose[3], const O
 int orc_map_integrate_keep(const OrcMapShape* shape, const double mapPose[3], const OrcScanNode* node,
                            const OrcBuilderParams* prm, uint16_t* grid, long long* stats)
 {
-    return map_integrate(shape, mapPose, node, 1, prm, grid, stats, false);
+    return map_integrate(shape, mapPose, node, 1, prm, grid, stats, false, nullptr);
+}
+
+/* the same, tracking allocation as orc_map_integrate_alloc */
+int orc_map_integrate_keep_alloc(const OrcMapShape* shape, const double mapPose[3], const OrcScanNode* node,
+                                 const OrcBuilderParams* prm, uint16_t* grid, long long* stats, uint8_t* alloc)
+{
+    return map_integrate(shape, mapPose, node, 1, prm, grid, stats, false, alloc);
 }
 
 /* UpdateGridMap's bounding box + GridMap::Expand (grid_map_builder.cpp:425-434,
@@ -343,8 +392,14 @@ int orc_map_expand(OrcMapShape* shape, const double mapPose[3], const OrcScanNod
 
 static int map_integrate(const OrcMapShape* shape, const double mapPose[3], const OrcScanNode* nodes,
                          int nNodes, const OrcBuilderParams* prm, uint16_t* grid, long long* stats,
-                         bool reset)
+                         bool reset, uint8_t* alloc)
 {
+    const int blockCols = shape->cols >> shape->log2Block;
+    auto update = [&](int x, int y, double odds, long long* oob) {
+        if (alloc)                                                 /* grid_map.cpp:656-657 */
+            alloc[static_cast<size_t>(y >> shape->log2Block) * blockCols + (x >> shape->log2Block)] = 1;
+        bb_update(&grid[static_cast<size_t>(y) * shape->cols + x], odds, oob);
+    };
     const double oddsHit = bb_probability_to_odds(prm->probHit);     /* grid_map_builder.cpp:95-96 */
     const double oddsMiss = bb_probability_to_odds(prm->probMiss);
     const int scale = prm->subpixel;
@@ -388,12 +443,12 @@ static int map_integrate(const OrcMapShape* shape, const double mapPose[3], cons
             for (const Cell& c : walk) {
                 if (!inside(c.first, c.second))
                     return 4;
-                bb_update(&grid[static_cast<size_t>(c.second) * shape->cols + c.first], oddsMiss, &oob);
+                update(c.first, c.second, oddsMiss, &oob);
                 ++updates;
             }
             if (!inside(hitX, hitY))
                 return 4;
-            bb_update(&grid[static_cast<size_t>(hitY) * shape->cols + hitX], oddsHit, &oob);
+            update(hitX, hitY, oddsHit, &oob);
             ++updates;
             ++rays;
         }

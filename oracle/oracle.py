@@ -311,35 +311,68 @@ def _nodes(nodes):
     return arr, keep
 
 
+def _block_dims(shape):
+    bs = 1 << shape["log2_block"]
+    return -(-shape["rows"] // bs), -(-shape["cols"] // bs)
+
+
+def move_blocks(alloc, old_shape, new_shape, row_min, col_min):
+    """The block move of GridMap::Resize on an allocation bitmap: the blocks of the
+    old map (alloc, None = nothing allocated) that overlap the new map keep their
+    state, the others start unallocated. row_min / col_min: the new map's first
+    cell in the old frame (multiples of the block size)."""
+    bs = 1 << new_shape["log2_block"]
+    assert row_min % bs == 0 and col_min % bs == 0
+    nbr, nbc = _block_dims(new_shape)
+    out = np.zeros((nbr, nbc), np.uint8)
+    old = None
+    obr = obc = 0
+    if alloc is not None:
+        old = np.ascontiguousarray(alloc, dtype=np.uint8)
+        obr, obc = _block_dims(old_shape)
+        assert old.shape == (obr, obc), (old.shape, (obr, obc))
+    lib().orc_map_move_blocks(None if old is None else _p(old), obr, obc, row_min // bs, col_min // bs,
+                              _p(out), nbr, nbc)
+    return out
+
+
 def construct_map(shape, map_pose, nodes, usable_min=0.01, usable_max=20.0, prob_hit=0.62,
-                  prob_miss=0.46, subpixel=100):
+                  prob_miss=0.46, subpixel=100, alloc=None):
     """Literal GridMapBuilder::ConstructMapFromScans on a dense array. shape =
-    dict(res, off_x, off_y, rows, cols, log2_block) of the map BEFORE the call.
-    Returns (new shape dict, grid, stats dict)."""
+    dict(res, off_x, off_y, rows, cols, log2_block) of the map BEFORE the call;
+    alloc = its block-allocation bitmap (uint8 [block rows, block cols]; None: a
+    fresh map, nothing allocated). Returns (new shape dict, grid, stats dict);
+    stats["alloc"] is the new map's bitmap (Resize moves the old blocks,
+    ResetValues keeps them, every cell update allocates its block)."""
     sh = MapShape(shape["res"], shape["off_x"], shape["off_y"], shape["rows"], shape["cols"],
                   shape["log2_block"])
     arr, keep = _nodes(nodes)
     prm = BuilderParams(usable_min, usable_max, prob_hit, prob_miss, subpixel)
     mp = _f64(map_pose)
-    rc = lib().orc_map_resize(C.byref(sh), _p(mp), arr, len(nodes), C.byref(prm))
+    r0, c0 = C.c_int(0), C.c_int(0)
+    rc = lib().orc_map_resize_shift(C.byref(sh), _p(mp), arr, len(nodes), C.byref(prm), C.byref(r0),
+                                    C.byref(c0))
     if rc:
         raise ValueError("orc_map_resize failed: %d" % rc)
-    grid = np.zeros((sh.rows, sh.cols), np.uint16)
-    stats = (C.c_longlong * 4)()
-    rc = lib().orc_map_integrate(C.byref(sh), _p(mp), arr, len(nodes), C.byref(prm), _p(grid), stats)
-    if rc:
-        raise ValueError("orc_map_integrate failed: %d" % rc)
     new_shape = dict(res=sh.res, off_x=sh.offX, off_y=sh.offY, rows=sh.rows, cols=sh.cols,
                      log2_block=sh.log2Block)
+    new_alloc = move_blocks(alloc, shape, new_shape, r0.value, c0.value)
+    grid = np.zeros((sh.rows, sh.cols), np.uint16)
+    stats = (C.c_longlong * 4)()
+    rc = lib().orc_map_integrate_alloc(C.byref(sh), _p(mp), arr, len(nodes), C.byref(prm), _p(grid), stats,
+                                       _p(new_alloc))
+    if rc:
+        raise ValueError("orc_map_integrate failed: %d" % rc)
     return new_shape, grid, dict(rays=stats[0], updates=stats[1], oob_reads=stats[2],
-                                 end_missing=stats[3])
+                                 end_missing=stats[3], row_min=r0.value, col_min=c0.value, alloc=new_alloc)
 
 
 def update_map(shape, grid, map_pose, node, usable_min=0.01, usable_max=20.0, prob_hit=0.62,
-               prob_miss=0.46, subpixel=100):
+               prob_miss=0.46, subpixel=100, alloc=None):
     """Literal GridMapBuilder::UpdateGridMap for one scan node on a dense array:
-    Expand (keeping the cells), then the ray casts. Returns (new shape, new
-    grid, stats)."""
+    Expand (keeping the cells), then the ray casts. alloc: the map's
+    block-allocation bitmap before the call (None: nothing allocated). Returns
+    (new shape, new grid, stats); stats["alloc"] is the new bitmap."""
     sh = MapShape(shape["res"], shape["off_x"], shape["off_y"], shape["rows"], shape["cols"],
                   shape["log2_block"])
     arr, keep = _nodes([node])
@@ -349,17 +382,31 @@ def update_map(shape, grid, map_pose, node, usable_min=0.01, usable_max=20.0, pr
     rc = lib().orc_map_expand(C.byref(sh), _p(mp), arr, C.byref(prm), C.byref(r0), C.byref(c0))
     if rc:
         raise ValueError("orc_map_expand failed: %d" % rc)
+    new_shape = dict(res=sh.res, off_x=sh.offX, off_y=sh.offY, rows=sh.rows, cols=sh.cols,
+                     log2_block=sh.log2Block)
+    new_alloc = move_blocks(alloc, shape, new_shape, r0.value, c0.value)
     old = np.ascontiguousarray(grid, dtype=np.uint16)
     new = np.zeros((sh.rows, sh.cols), np.uint16)
     new[-r0.value:-r0.value + old.shape[0], -c0.value:-c0.value + old.shape[1]] = old
     stats = (C.c_longlong * 4)()
-    rc = lib().orc_map_integrate_keep(C.byref(sh), _p(mp), arr, C.byref(prm), _p(new), stats)
+    rc = lib().orc_map_integrate_keep_alloc(C.byref(sh), _p(mp), arr, C.byref(prm), _p(new), stats,
+                                            _p(new_alloc))
     if rc:
         raise ValueError("orc_map_integrate_keep failed: %d" % rc)
-    new_shape = dict(res=sh.res, off_x=sh.offX, off_y=sh.offY, rows=sh.rows, cols=sh.cols,
-                     log2_block=sh.log2Block)
     return new_shape, new, dict(rays=stats[0], updates=stats[1], oob_reads=stats[2],
-                                end_missing=stats[3], row_min=r0.value, col_min=c0.value)
+                                end_missing=stats[3], row_min=r0.value, col_min=c0.value, alloc=new_alloc)
+
+
+def derived_alloc(grid, log2_block=4):
+    """The rule "a block is allocated iff it holds a known cell" on 2^log2_block blocks
+    (ragged edge blocks included): the reference's state for a map that was only
+    ever updated."""
+    bs = 1 << log2_block
+    g = np.asarray(grid)
+    rows, cols = -(-g.shape[0] // bs) * bs, -(-g.shape[1] // bs) * bs
+    pad = np.zeros((rows, cols), g.dtype)
+    pad[:g.shape[0], :g.shape[1]] = g
+    return (pad.reshape(rows // bs, bs, cols // bs, bs).max(axis=(1, 3)) > 0).astype(np.uint8)
 
 
 def ray_cells(sx, sy, ex, ey, scale=100, cap=1 << 16):
@@ -435,16 +482,22 @@ def solve3(m, b):
 
 def linear_solver(grid, geom, angles, ranges, rel_pose, init_pose, iterations_max=10,
                   convergence_threshold=1e-4, lambda_=1e-4, covariance_scale=1e4, alloc=None,
-                  log2_block=4):
-    """ScanMatcherLinearSolver::OptimizePose; defaults as launcher_settings_default.json:28-35, 11-13."""
+                  log2_block=4, trace=False):
+    """ScanMatcherLinearSolver::OptimizePose; defaults as launcher_settings_default.json:28-35, 11-13.
+    trace: also return "trace" = [(cost before, cost after, lambda used)] per iteration."""
     cg, keep = _cost_grid(grid, geom, alloc, log2_block)
     a, r = _f64(angles), _f64(ranges)
     out = RefineResult()
-    lib().orc_linear_solver(C.byref(cg), _p(a), _p(r), a.size, _p(_f64(rel_pose)), _p(_f64(init_pose)),
-                            iterations_max, C.c_double(convergence_threshold), C.c_double(lambda_),
-                            C.c_double(covariance_scale), C.byref(out))
-    return dict(normalized_initial_cost=out.normalizedInitialCost, normalized_cost=out.normalizedCost,
-                sensor_pose=list(out.sensorPose), best_sensor_pose=list(out.bestSensorPose),
-                estimated_pose=list(out.estimatedPose),
-                covariance=np.array(out.covariance).reshape(3, 3), lambda_=out.lambda_,
-                iterations=out.iterations)
+    cap = max(iterations_max, 1) if trace else 0
+    tr = np.zeros(3 * cap)
+    lib().orc_linear_solver_trace(C.byref(cg), _p(a), _p(r), a.size, _p(_f64(rel_pose)), _p(_f64(init_pose)),
+                                  iterations_max, C.c_double(convergence_threshold), C.c_double(lambda_),
+                                  C.c_double(covariance_scale), C.byref(out), _p(tr) if trace else None, cap)
+    d = dict(normalized_initial_cost=out.normalizedInitialCost, normalized_cost=out.normalizedCost,
+             sensor_pose=list(out.sensorPose), best_sensor_pose=list(out.bestSensorPose),
+             estimated_pose=list(out.estimatedPose),
+             covariance=np.array(out.covariance).reshape(3, 3), lambda_=out.lambda_,
+             iterations=out.iterations)
+    if trace:
+        d["trace"] = [tuple(tr[3 * k:3 * k + 3]) for k in range(min(out.iterations, cap))]
+    return d

@@ -190,3 +190,134 @@ def test_map_golden(oracle, rec):
     assert (shape["rows"], shape["cols"], stats["rays"], stats["updates"], stats["oob_reads"]) == \
         (want["rows"], want["cols"], want["rays"], want["updates"], want["saturated"])
     assert [shape["off_x"], shape["off_y"]] == [unhex(v) for v in want["off"]]
+
+
+# ---------------------------------------------------------------- block allocation
+
+
+def test_block_move_by_hand(oracle):
+    """GridMap::Resize's block move on the bitmap: shifts in both directions, and a shrink that
+    drops the blocks outside the new map."""
+    old = np.arange(1, 13, dtype=np.uint8).reshape(3, 4)
+    shape = dict(res=0.05, off_x=0.0, off_y=0.0, rows=48, cols=64, log2_block=4)
+    grown = dict(shape, rows=80, cols=96)
+    # the new map starts one block row below and two block columns left of the old one
+    got = oracle.move_blocks(old, shape, grown, -16, -32)
+    want = np.zeros((5, 6), np.uint8)
+    want[1:4, 2:6] = old
+    assert np.array_equal(got, want)
+    # ... and one block row above / one block column right of it: a shift the other way
+    moved = dict(shape, rows=32, cols=64)
+    got = oracle.move_blocks(old, shape, moved, 16, 16)
+    want = np.zeros((2, 4), np.uint8)
+    want[:, :3] = old[1:, 1:]
+    assert np.array_equal(got, want)
+    # a shrink to the middle block: everything else is dropped
+    small = dict(shape, rows=16, cols=16)
+    assert np.array_equal(oracle.move_blocks(old, shape, small, 16, 16), old[1:2, 1:2])
+    # nothing allocated before: nothing after
+    assert not oracle.move_blocks(None, shape, grown, -16, -32).any()
+
+
+@pytest.mark.parametrize("log2_block", [2, 3, 4, 5])
+def test_construct_map_tracks_allocation(oracle, log2_block):
+    """A fresh construct allocates exactly the blocks holding a known cell; a rebuild from other
+    scans moves the old blocks (shift in either direction), keeps the overlapping ones allocated
+    with their cells reset, and every known cell lies in an allocated block."""
+    from cost_edge_cases import initial_shape
+    case = synth.map_case(5, n_scans=16, n_beams=360, step=0.2)
+    nodes = case["nodes"]
+    shape0 = initial_shape(0.05, log2_block)
+    shape1, grid1, st1 = oracle.construct_map(shape0, nodes[0]["pose"], nodes[:6])
+    assert np.array_equal(st1["alloc"], oracle.derived_alloc(grid1, log2_block))
+    assert st1["alloc"].shape == (shape1["rows"] >> log2_block, shape1["cols"] >> log2_block)
+    reset_but_allocated = 0
+    shape, grid, alloc = shape1, grid1, st1["alloc"]
+    for lo, hi in ((8, 16), (0, 3), (4, 12)):
+        nshape, ngrid, st = oracle.construct_map(shape, nodes[0]["pose"], nodes[lo:hi], alloc=alloc)
+        bs = 1 << log2_block
+        r0, c0 = st["row_min"], st["col_min"]
+        want = oracle.derived_alloc(ngrid, log2_block)
+        for br in range(want.shape[0]):
+            for bc in range(want.shape[1]):
+                obr, obc = br + r0 // bs, bc + c0 // bs
+                if 0 <= obr < alloc.shape[0] and 0 <= obc < alloc.shape[1] and alloc[obr, obc]:
+                    want[br, bc] = 1
+        assert np.array_equal(st["alloc"], want)
+        known = oracle.derived_alloc(ngrid, log2_block)
+        assert not (known & ~st["alloc"]).any()                 # every known cell is allocated
+        reset_but_allocated += int((st["alloc"] & ~known).sum())
+        shape, grid, alloc = nshape, ngrid, st["alloc"]
+    assert reset_but_allocated > 0
+
+
+@pytest.mark.parametrize("log2_block", [3, 4, 5])
+def test_update_only_allocation_equals_derived_rule(oracle, log2_block):
+    """A map that was only ever updated (a local map grown scan by scan, resizes included): the
+    tracked bitmap is the rule "a block is allocated iff it holds a known cell"."""
+    from cost_edge_cases import local_map_steps
+    grew = 0
+    for step in local_map_steps(oracle, log2_block):
+        assert np.array_equal(step["alloc"], oracle.derived_alloc(step["grid"], log2_block)), step["k"]
+        grew += step["grew"]
+    assert grew >= 1
+
+
+@pytest.mark.parametrize("log2_block", [3, 4])
+def test_frontend_rebuilds_keep_reset_blocks(oracle, log2_block):
+    """The latest-map cycle: rebuilt maps keep blocks that hold no known cell any more, and the
+    cost the library used to compute (16-cell blocks derived from the cells) differs from the
+    reference's by far more than the tolerance in many frames (test_gpu_cost_edges.py's
+    precondition)."""
+    from cost_edge_cases import MARGIN, divergence, frontend_frames
+    kept, diverging = 0, 0
+    for fr in frontend_frames(oracle, log2_block):
+        known = oracle.derived_alloc(fr["grid"], log2_block)
+        assert not (known & ~fr["alloc"]).any()
+        kept += int((fr["alloc"] & ~known).sum())
+        diverging += divergence(oracle, fr["grid"], fr["query"], fr["alloc"], log2_block) > MARGIN
+    assert kept > 0
+    assert diverging >= 5, diverging
+
+
+@pytest.mark.parametrize("log2_block", [2, 3, 4, 5])
+def test_fresh_construct_divergence(oracle, log2_block):
+    """Fresh constructs: the tracked bitmap is the derived rule on the map's own blocks; on
+    blocks other than 16 cells the cost differs from the 16-cell rule (the B.3(a) precondition),
+    on 16-cell blocks it is the same bitmap (the control)."""
+    from cost_edge_cases import MARGIN, divergence, fresh_construct
+    w = fresh_construct(oracle, log2_block)
+    assert np.array_equal(w["alloc"], oracle.derived_alloc(w["grid"], log2_block))
+    if log2_block == 4:
+        assert np.array_equal(w["alloc"], oracle.derived_alloc(w["grid"], 4))
+        return
+    n = sum(divergence(oracle, w["grid"], q, w["alloc"], log2_block) > MARGIN for q in w["queries"])
+    assert n >= 2, n
+
+
+def test_local_map_divergence_off_16_cell_blocks(oracle):
+    """A local map on 8-cell blocks grown by updates: the 16-cell rule reads it differently (the
+    B.3(c) precondition)."""
+    from cost_edge_cases import MARGIN, divergence, local_map_steps
+    n = sum(divergence(oracle, s["grid"], s["query"], s["alloc"], 3) > MARGIN
+            for s in local_map_steps(oracle, 3) if s["query"] is not None)
+    assert n >= 2, n
+
+
+def test_linear_solver_trace(oracle):
+    """The oracle's per-iteration trace: one entry per iteration, each step starts from the cost
+    the previous one ended with, and the damping factor follows the halving / doubling rule."""
+    c = synth.csm_case(3100, n_beams=1080, fov=1.5 * math.pi)
+    init = tuple(np.asarray(c["truth"]) + (0.3, -0.25, 0.05))
+    w = oracle.linear_solver(c["grid"], c["geom"], c["angles"], c["ranges"], c["rel_pose"], init, 10, 1e-4,
+                             1e-4, 1e4, trace=True)
+    tr = w["trace"]
+    assert len(tr) == w["iterations"] >= 2
+    assert tr[0][0] == w["normalized_initial_cost"] * len(c["angles"])
+    assert tr[-1][1] == w["normalized_cost"] * len(c["angles"])
+    for (p0, c0, l0), (p1, c1, l1) in zip(tr, tr[1:]):
+        assert p1 == c0
+        assert l1 == (max(1e-8, l0 * 0.5) if c0 < p0 else min(1e-4, l0 * 2.0))
+    plain = oracle.linear_solver(c["grid"], c["geom"], c["angles"], c["ranges"], c["rel_pose"], init, 10, 1e-4,
+                                 1e-4, 1e4)
+    assert plain["best_sensor_pose"] == w["best_sensor_pose"] and "trace" not in plain

@@ -7,11 +7,12 @@ every output with `==` against a fresh map id holding the final cells, uploaded 
 against the oracle's matcher where one exists. The final cells themselves are first checked
 against the oracle's map (construct_map / update_map).
 
-A caller's block-allocation bitmap (csm_set_block_allocation) does not survive a change of the
-map: map_build (update_map_with_scan, construct_map_from_scans) clears alloc_user, and
-upload_grid / upload_grid_blocks start the map afresh, so afterwards the bitmap is derived from
-the cells again (a block is allocated iff it holds a known cell). The cost cells set an
-all-allocated bitmap before the change and check exactly that."""
+The block-allocation bitmap follows the reference's GridMap: the cost cells mark every block of
+the map allocated (csm_set_block_allocation) before the change. upload_grid starts the map afresh
+(a block is allocated iff it holds a known cell); construct_map_from_scans and
+update_map_with_scan carry the old bitmap through Resize / Expand, and ResetValues keeps it, so the
+blocks of the old map that overlap the new one stay allocated. Their fresh-id reference holds the
+final cells plus the oracle's tracked bitmap (construct_map / update_map with alloc=)."""
 import itertools
 import math
 
@@ -68,7 +69,7 @@ def _upload(kind):
 
     queries = _room_queries(segs_b, geom_b, seed)
     warm = [dict(q, geom=geom_a) for q in queries]
-    return dict(setup=setup, mutate=mutate, grid=gb, queries=queries, warm=warm)
+    return dict(setup=setup, mutate=mutate, grid=gb, queries=queries, warm=warm, cost_alloc=_derived_alloc(gb))
 
 
 def _map_local(map_pose, pose, err):
@@ -91,10 +92,12 @@ def _built(kind, oracle):
     first, second = {"construct_reuse": (nodes[0:8], nodes[2:9]), "construct_grow": ([near], nodes[0:14]),
                      "update_in_place": (nodes[0:10], nodes[5]), "update_grow": (nodes[0:3], nodes[13])}[kind]
     shape1, grid1, _ = oracle.construct_map(shape0, map_pose, first)
+    # the cost cells mark every block of the first map allocated before the change
+    ones = np.ones((shape1["rows"] >> 4, shape1["cols"] >> 4), np.uint8)
     if kind.startswith("construct"):
-        shape2, grid2, _ = oracle.construct_map(shape1, map_pose, second)
+        shape2, grid2, st2 = oracle.construct_map(shape1, map_pose, second, alloc=ones)
     else:
-        shape2, grid2, _ = oracle.update_map(shape1, grid1, map_pose, second)
+        shape2, grid2, st2 = oracle.update_map(shape1, grid1, map_pose, second, alloc=ones)
     if kind == "construct_reuse":
         assert _pitch_bytes(shape2) <= 1.5 * _pitch_bytes(shape1), (shape1, shape2)
     elif kind == "construct_grow":
@@ -122,7 +125,7 @@ def _built(kind, oracle):
                  init_pose=_map_local(map_pose, nd["pose"], err))
         queries.append(dict(q, geom=(shape2["res"], shape2["off_x"], shape2["off_y"])))
         warm.append(dict(q, geom=(shape1["res"], shape1["off_x"], shape1["off_y"])))
-    return dict(setup=setup, mutate=mutate, grid=grid2, queries=queries, warm=warm)
+    return dict(setup=setup, mutate=mutate, grid=grid2, queries=queries, warm=warm, cost_alloc=st2["alloc"])
 
 
 MUTATIONS = ["upload_same_shape", "upload_other_shape", "blocks_then_dense", "construct_reuse",
@@ -218,8 +221,7 @@ def _derived_alloc(grid):
     return (g.reshape(rows // 16, 16, cols // 16, 16).max(axis=(1, 3)) > 0).astype(np.uint8)
 
 
-def _cost_oracle(oracle, grid, qs, got):
-    alloc = _derived_alloc(grid)
+def _cost_oracle(oracle, grid, qs, got, alloc):
     for q, p, o in zip(qs, _poses(qs), got[:len(qs)]):
         want = oracle.cost(grid, q["geom"], q["angles"], q["ranges"], p, alloc=alloc)
         assert abs(o["normalized_cost"] * len(q["angles"]) - want) <= 1e-10 * want, (o["normalized_cost"], want)
@@ -296,9 +298,14 @@ def test_derived_state_follows_the_map(oracle, refs, mutation, consumer):
     rid = next(_ids)
     ref.upload_grid(rid, world["grid"])
     try:
+        if consumer == "cost_linear":
+            ref.set_block_allocation(rid, 4, world["cost_alloc"])
         want = run(ref, _with_id(world["queries"], rid))
     finally:
         ref.release_grid(rid)
     assert got[0] == want
     assert got[1] == want
-    check(oracle, world["grid"], qs, want)
+    if consumer == "cost_linear":
+        check(oracle, world["grid"], qs, want, world["cost_alloc"])
+    else:
+        check(oracle, world["grid"], qs, want)
