@@ -155,9 +155,7 @@ int csm_destroy(csm_ctx* ctx)
         }
     for (auto& h : ctx->resident_hold)
         (void)hipEventDestroy(h.first);
-    ctx->resident_hold.clear();           /* returns the blocks they hold to pin_free */
-    for (auto& b : ctx->pin_free)
-        (void)hipHostFree(b.first);
+    ctx->resident_hold.clear();
     for (hipEvent_t e : ctx->event_pool)
         (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->m_ev)

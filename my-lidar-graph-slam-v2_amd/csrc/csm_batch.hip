@@ -1,6 +1,8 @@
 /* csm_batch.hip -- many windows in one launch chain (host code only): branch-and-bound and correlative
- * loop-detection batches (run_batch_group: staging, joint binning, bound pass + exact rounds), device-resident
- * window batches (csm_score_windows_dev), their entry points of the C ABI. */
+ * loop-detection batches (one driver, loop_batch), device-resident window batches (csm_score_windows_dev),
+ * their entry points of the C ABI. run_batch_group takes one group of queries through its stages: plan,
+ * scan staging, workspaces, job tables, upload, launch chain (joint binning, bound pass + exact rounds),
+ * host finish with the exact fall-backs. */
 #include "csm_matchers.hpp"
 
 #ifdef CSM_BIN_TIMING
@@ -18,13 +20,13 @@ static uint32_t* bin_debug_buffer()
 namespace csm_host {
 
 
-struct BatchPrep {
+/* One query of a group: its window, frame and places in the group's workspaces. */
+struct BatchPrep : WindowFrame {
     DeviceGrid* grid = nullptr;
     int level[kMaxElig] = { 0 };   /* index into grid->levels of box-max(2^h) */
     int n_theta = 0, n = 0;
     int win_x = 0, win_y = 0, win_t = 0;
-    int nx = 0, ny = 0;
-    int tiles_x = 0, tiles_y = 0, max_tiles = 0;
+    int max_tiles = 0;
     size_t hit_off = 0, tile_off = 0, theta_off = 0, best_off = 0;
     size_t lvl_off[kMaxElig] = { 0 };
 };
@@ -44,8 +46,8 @@ struct HeapNode {
  * discipline (std::priority_queue, same push / pop order as
  * src/mapping/scan_matcher_branch_bound.cpp:156-231) reading those scores
  * instead of calling Score(). No score is computed on the CPU. */
-int bnb_literal(csm_ctx* ctx, const csm_loop_query& q, const BatchPrep& p, const csm_summary& o,
-                const csm_bnb_params* prm, csm_result* res)
+static int bnb_literal(csm_ctx* ctx, const csm_loop_query& q, const BatchPrep& p, const csm_summary& o,
+                       const csm_bnb_params* prm, csm_result* res)
 {
     const int H = prm->node_height_max;
     const int nx = p.nx, ny = p.ny;
@@ -158,7 +160,7 @@ int bnb_literal(csm_ctx* ctx, const csm_loop_query& q, const BatchPrep& p, const
 
 /* The device copy of a batch's final records: sized here, filled by
  * run_batch_group, handed out by csm_copy_last_batch_records. */
-int begin_batch_records(csm_ctx* ctx, int n_queries)
+static int begin_batch_records(csm_ctx* ctx, int n_queries)
 {
     ctx->rec_n = 0;
     int rc = ensure(ctx, ctx->rec_dev, (size_t)n_queries * sizeof(csm_result));
@@ -176,7 +178,7 @@ struct BatchSpec {
     bool bnb = true;          /* branch and bound (leaf + 2^h levels) or correlative (fine + one
                                  box-max(L) level) */
     int H = 0;                /* number of coarser levels */
-    int stride[kMaxElig] = { 1 };   /* stride[j] of level j (stride[0] = 1) */
+    int stride[kMaxElig] = { 1 };   /* stride[j] of level j (stride[0] = 1): its box-max window */
     int unit = 1;             /* candidate domain is padded to a multiple of this */
     double range_x = 0, range_y = 0, range_theta = 0;
     double score_thr = 0, known_thr = 0;
@@ -197,35 +199,85 @@ struct ResidentBatch {
     float* const* dump_f = nullptr;       /* optional: every candidate's fp32 key of the bound pass */
 };
 
-/* One group of queries that share (nx, ny): the whole device pipeline. */
-int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vector<int>& idx,
-                    const std::vector<std::vector<int>>& levels, const BatchSpec& spec,
-                    csm_summary* out, const ResidentBatch* resident = nullptr)
-{
-    const int H = spec.H;
-    const int nq = (int)idx.size();
-    const bool host_timing = ctx->tune.host_timing;
-    auto tick = [&](const char* what) {
+/* One group of queries that share (nx, ny) on its way through run_batch_group's stages: what each
+ * stage decides or places, read by the stages after it. */
+struct BatchGroup {
+    csm_ctx* ctx;
+    const csm_loop_query* queries;
+    const std::vector<int>& idx;                  /* the group's queries */
+    const std::vector<std::vector<int>>& levels;  /* [query][h] index into its grid's levels */
+    const BatchSpec& spec;
+    csm_summary* out;
+    const ResidentBatch* resident;
+    const int H, nq;
+
+    /* host set-up and plan */
+    std::vector<BatchPrep> pp;
+    std::vector<csm_summary> scratch_out;         /* resident mode: no host summaries */
+    int nx = 0, ny = 0, n_theta_max = 0, n_points_max = 0;
+    std::vector<PassPlan> lp;                     /* [H + 1] launch geometry shared by the group */
+    size_t bin_lds = 0, binj_lds = 0;
+    bool joint = false, bound_pass = false, two_rounds = false;
+    size_t hit_total = 0, tile_total = 0, theta_total = 0;
+    /* scans */
+    std::vector<size_t> scan_off;
+    size_t scan_total = 0;
+    double* scans = nullptr;                      /* pinned staging */
+    /* workspaces */
+    size_t lvl_total = 0, best_total = 0, blocks_total = 0, jobs_bytes = 0;
+    double* d_scans = nullptr;
+    csm_result* d_out = nullptr;
+    uint32_t* d_flags = nullptr;                  /* [nq], behind the records */
+    /* job tables, and where they were uploaded */
+    std::vector<ProjJob> ij;
+    std::vector<BinJob> bj;
+    std::vector<FinalJob> fj;
+    std::vector<std::vector<ScoreJob>> sj;        /* [h][query] */
+    std::vector<ZeroJob> zj;                      /* [query][h - 1] */
+    size_t zero_words_max = 0;
+    PinBuf tables;                                /* from ctx->pin_free, back there after the chain */
+    char *d_ij = nullptr, *d_bj = nullptr, *d_fj = nullptr, *d_idx = nullptr, *d_zj = nullptr;
+    std::vector<char*> d_sj;
+
+    BatchGroup(csm_ctx* c, const csm_loop_query* q, const std::vector<int>& i, const std::vector<std::vector<int>>& l,
+               const BatchSpec& s, csm_summary* o, const ResidentBatch* r)
+        : ctx(c), queries(q), idx(i), levels(l), spec(s), out(o), resident(r), H(s.H), nq((int)i.size())
+    {
+    }
+    int plan();                                   /* the stages, in order */
+    int stage_scans();
+    int size_workspaces();
+    int fill_job_tables();
+    void build_jobs(int k);
+    int upload_tables();
+    int launch_chain();
+    int finish();
+    int min_known_of(int k) const
+    {
+        return resident ? resident->windows[idx[k]].min_known : csm_host_min_known(pp[k].n, spec.known_thr);
+    }
+    double score_thr(int k) const { return resident ? resident->windows[idx[k]].score_threshold : spec.score_thr; }
+    /* CSM_TUNING host timing: time since the previous tick */
+    void tick(const char* what) const
+    {
         static thread_local std::chrono::steady_clock::time_point last;
         const auto now = std::chrono::steady_clock::now();
-        if (host_timing && what)
+        if (ctx->tune.host_timing && what)
             fprintf(stderr, "[run_batch_group nq=%d] %-10s %8.3f ms\n", nq, what,
                     std::chrono::duration<double, std::milli>(now - last).count());
         last = now;
-    };
-    tick(nullptr);
-    std::vector<BatchPrep> pp(nq);
-    std::vector<csm_summary> scratch_out;
-    if (resident) {                       /* no host summaries in this mode */
+    }
+};
+
+/* Stage 1, host set-up and plan: each query's window and frame, the launch geometry shared by the
+ * group, the joint / bound-pass / two-round decisions, the sizes of the per-query lists. */
+int BatchGroup::plan()
+{
+    pp.resize(nq);
+    if (resident) {
         scratch_out.assign((size_t)*std::max_element(idx.begin(), idx.end()) + 1, csm_summary {});
         out = scratch_out.data();
     }
-    int rc;
-
-    /* ---- host set-up: window, projection products (threaded over queries) ---- */
-    size_t hit_total = 0, tile_total = 0, theta_total = 0;
-    int n_theta_max = 0, n_points_max = 0;
-    size_t bin_lds = 0;
     for (int k = 0; k < nq; ++k) {
         const csm_loop_query& q = queries[idx[k]];
         csm_summary& o = out[idx[k]];
@@ -250,67 +302,54 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
             p.n_theta = 2 * p.win_t + 1;
             p.n = q.scan.n_points;
         }
-        const int big = spec.unit;
-        p.nx = ceil_div(2 * p.win_x + 1, big) * big;
-        p.ny = ceil_div(2 * p.win_y + 1, big) * big;
-        p.tiles_x = ceil_div(p.grid->cols + p.win_x + (-p.win_x + p.nx - 1), kTile);
-        p.tiles_y = ceil_div(p.grid->rows + p.win_y + (-p.win_y + p.ny - 1) + 1, kTile);
+        static_cast<WindowFrame&>(p) = window_frame(*p.grid, p.win_x, p.win_y, spec.unit);
         if (p.n > kMaxPoints)
             return fail(ctx, CSM_EINVAL, "query %d: more than %d beams per scan", idx[k], kMaxPoints);
         n_theta_max = std::max(n_theta_max, p.n_theta);
         n_points_max = std::max(n_points_max, p.n);
     }
-    const int nx = pp[0].nx, ny = pp[0].ny;
+    nx = pp[0].nx;
+    ny = pp[0].ny;
 
-    /* ---- launch geometry shared by the group ---- */
-    std::vector<PassPlan> lp(H + 1);
-    for (int h = 0; h <= H; ++h) {
-        if (h == 0) {
-            if (!plan_pass_pairs(ctx->tune, nx, ny, &lp[0], true))
-                return fail(ctx, CSM_EINVAL, "no launch geometry for the fine level");
-            continue;
-        }
+    lp.resize(H + 1);
+    if (!plan_pass_pairs(ctx->tune, nx, ny, &lp[0], true))
+        return fail(ctx, CSM_EINVAL, "no launch geometry for the fine level");
+    for (int h = 1; h <= H; ++h)
         if (!plan_pass(ctx->tune, nx / spec.stride[h], ny / spec.stride[h], spec.stride[h], &lp[h]))
-            return fail(ctx, CSM_EINVAL, "no launch geometry for level %d (stride %d)", h,
-                        spec.stride[h]);
-    }
+            return fail(ctx, CSM_EINVAL, "no launch geometry for level %d (stride %d)", h, spec.stride[h]);
+    PassPlan& fine = lp[0];
     if (resident) {
-        lp[0].weighted = resident->windows[idx[0]].merge_mode == 0;
+        fine.weighted = resident->windows[idx[0]].merge_mode == 0;
     } else {
         const csm_loop_query& q0 = queries[idx[0]];
-        lp[0].weighted = merging_pays(q0.scan.angles, q0.scan.ranges, q0.scan.n_points,
-                                      q0.geometry.resolution);
+        fine.weighted = merging_pays(q0.scan.angles, q0.scan.ranges, q0.scan.n_points, q0.geometry.resolution);
     }
     /* Joint entry lists of slice pairs (k_binj + k_score_joint_batch, csm_joint_kernels.hip): the
      * two-slice plan with merged (weighted) entries, when the joint hash table of every query
      * fits a CU's LDS. Otherwise round 2's per-slice lists. */
-    size_t binj_lds = 0;
-    for (int k = 0; k < nq; ++k)
-        binj_lds = std::max(binj_lds, csm::binj_lds_bytes(pp[k].tiles_x * pp[k].tiles_y, pp[k].n,
-                                                          csm::binj_hash_size(pp[k].n)));
-    const bool joint = ctx->tune.joint && lp[0].pairs && lp[0].lists == 2 && lp[0].weighted &&
-                       binj_lds <= 150 * 1024;     /* up to ~1,100 beams four binning workgroups share a CU, two up
-                                                      to ~2,200; one (the fine level's gain outweighs the slower
-                                                      binning) up to ~4,200 beams per scan */
-    lp[0].joint = joint;
+    for (const BatchPrep& p : pp)
+        binj_lds = std::max(binj_lds, csm::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, csm::binj_hash_size(p.n)));
+    joint = ctx->tune.joint && fine.pairs && fine.lists == 2 && fine.weighted &&
+              binj_lds <= 150 * 1024;     /* up to ~1,100 beams four binning workgroups share a CU, two up
+                                               to ~2,200; one (the fine level's gain outweighs the slower
+                                               binning) up to ~4,200 beams per scan */
+    fine.joint = joint;
     /* The packed-fp32 bound pass in front of the exact kernel: only where the arg-max is over ALL
      * candidates of the window -- the correlative sweep with a known-rate threshold that the coarse
      * level passes whenever a fine candidate scores at all (min_known <= 1; a touched edge band
      * switches the skipping off per query on the device). Branch and bound tests every leaf's own
      * known count: exact kernel only. */
-    bool bound_pass = joint && ctx->tune.bound_pass && nq < (1 << 14) && lp[0].ncb() <= 256 &&
-                      (n_theta_max + 1) / 2 <= 1024;       /* the work list's item format */
+    bound_pass = joint && ctx->tune.bound_pass && nq < (1 << 14) && fine.ncb() <= 256 &&
+                   (n_theta_max + 1) / 2 <= 1024;       /* the work list's item format */
     /* Where the winner must pass a known-count test the bound pass does not see -- branch and bound:
      * every leaf's own count; the correlative sweep with a known-rate threshold above one beam: the
      * coarse node's count (the reference's loop detectors run with 0.6) -- the window's greatest
      * fp32 key may belong to a candidate that does not count, and the exact pass runs in two rounds
      * (k_bound_select). */
-    bool two_rounds = spec.bnb;
+    two_rounds = spec.bnb;
     for (int k = 0; k < nq; ++k)
-        two_rounds = two_rounds || (resident ? resident->windows[idx[k]].min_known
-                                             : csm_host_min_known(pp[k].n, spec.known_thr)) > 1;
-    for (int k = 0; k < nq; ++k) {
-        BatchPrep& p = pp[k];
+        two_rounds = two_rounds || min_known_of(k) > 1;
+    for (BatchPrep& p : pp) {
         /* lists and records per slice, or per pair of slices (2 n entries each) */
         const int units = joint ? (p.n_theta + 1) / 2 : p.n_theta;
         const int per_unit = joint ? 2 * p.n : p.n;
@@ -325,44 +364,38 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
     }
     if (bin_lds > 160 * 1024 - 64)
         return fail(ctx, CSM_EINVAL, "grid + window too large for the binning kernel (its per-tile words, hash table and cell list exceed the LDS)");
+    return CSM_OK;
+}
 
-    /* scans go to the device as they are (angles, ranges); the projection runs
-     * there with a per-entry certificate (k_project) */
-    /* Queries that share a scan (one query scan node against many local maps: the
-     * usual shape of a Detect() call) share its device copy. The staging buffer is
-     * pinned and owned by the context: no clearing, one DMA. */
-    std::vector<size_t> scan_off(nq);
-    size_t scan_total = 0;
-    {
-        std::map<std::tuple<const double*, const double*, int>, size_t> seen;
-        for (int k = 0; k < nq; ++k) {
-            const csm_scan& sc = queries[idx[k]].scan;
-            auto key = std::make_tuple(sc.angles, sc.ranges, pp[k].n);
-            auto it = resident ? seen.end() : seen.find(key);
-            if (it != seen.end()) {
-                scan_off[k] = it->second;
-                continue;
-            }
-            scan_off[k] = scan_total;
-            if (!resident)
-                seen.emplace(key, scan_total);
-            scan_total += 2 * (size_t)pp[k].n;
+/* Stage 2: scans go to the device as they are (angles, ranges); the projection runs there with a
+ * per-entry certificate (k_project). Queries that share a scan (one query scan node against many
+ * local maps: the usual shape of a Detect() call) share its device copy. The staging buffer is
+ * pinned and owned by the context: no clearing, one DMA. */
+int BatchGroup::stage_scans()
+{
+    scan_off.resize(nq);
+    std::vector<int> first_use;             /* scans are laid out in first-use order */
+    std::map<std::tuple<const double*, const double*, int>, size_t> seen;
+    for (int k = 0; k < nq; ++k) {
+        const csm_scan& sc = queries[idx[k]].scan;
+        auto key = std::make_tuple(sc.angles, sc.ranges, pp[k].n);
+        auto it = resident ? seen.end() : seen.find(key);
+        if (it != seen.end()) {
+            scan_off[k] = it->second;       /* a duplicate of an earlier query's scan */
+            continue;
         }
+        scan_off[k] = scan_total;
+        if (!resident) {
+            seen.emplace(key, scan_total);
+            first_use.push_back(k);
+        }
+        scan_total += 2 * (size_t)pp[k].n;
     }
-    double* scans = nullptr;
     if (!resident) {
         const size_t need = scan_total * 8;
         if (int rc = grow(ctx, ctx->pin_scans, need, need + need / 4 + 64, false))
             return rc;
         scans = ctx->pin_scans.as<double>();
-        size_t filled = 0;                  /* scans are laid out in first-use order */
-        std::vector<int> first_use;
-        for (int k = 0; k < nq; ++k) {
-            if (scan_off[k] != filled)
-                continue;                   /* a duplicate of an earlier query's scan */
-            first_use.push_back(k);
-            filled += 2 * (size_t)pp[k].n;
-        }
         host_parallel_for((int)first_use.size(), 128, [&](int lo, int hi) {
             for (int j = lo; j < hi; ++j) {
                 const int k = first_use[j];
@@ -372,28 +405,31 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
             }
         });
     }
-
     tick("setup");
-    const int lstride = lp[0].lstride;
-    const int ncb = lp[0].ncb();
+    return CSM_OK;
+}
 
-    /* ---- workspaces ---- */
-    size_t lvl_total = 0, best_total = 0;
-    for (int k = 0; k < nq; ++k) {
-        BatchPrep& p = pp[k];
+/* Stage 3: the context's workspaces sized for the group and carved up; the scans go up, the
+ * per-query flag words are cleared. */
+int BatchGroup::size_workspaces()
+{
+    const int ncb = lp[0].ncb();
+    for (BatchPrep& p : pp) {
         for (int h = 1; h <= H; ++h) {
             p.lvl_off[h] = lvl_total;
             lvl_total += (size_t)p.n_theta * (nx / spec.stride[h]) * (ny / spec.stride[h]);
         }
         p.best_off = best_total;
         best_total += (size_t)p.n_theta * ncb;
+        blocks_total += (size_t)((p.n_theta + 1) / 2) * ncb;
     }
+    int rc;
     if ((rc = ensure(ctx, ctx->b_prod, (resident ? 0 : scan_total * 8) + 64))) return rc;
     if ((rc = ensure(ctx, ctx->b_hits, (resident ? 0 : hit_total * 8) + 64))) return rc;
     if ((rc = ensure(ctx, ctx->b_sorted, hit_total * 4 + 256))) return rc;
     if (lp[0].pairs)
-        for (int k = 0; k < nq; ++k)
-            if ((rc = ensure_xgrid(ctx, *pp[k].grid, xgrid_pad_for(nx, ny)))) return rc;
+        for (BatchPrep& p : pp)
+            if ((rc = ensure_xgrid(ctx, *p.grid, xgrid_pad_for(nx, ny)))) return rc;
     if ((rc = ensure(ctx, ctx->b_sorted_rc, hit_total * 4))) return rc;
     if ((rc = ensure(ctx, ctx->b_tiles, tile_total * sizeof(TileRec)))) return rc;
     if ((rc = ensure(ctx, ctx->b_ntiles, theta_total * 4))) return rc;
@@ -406,259 +442,173 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
         }
         if ((rc = ensure(ctx, ctx->b_abest, best_total * sizeof(float)))) return rc;
         /* work lists of the exact kernel: [2 counts, pad][items 0][items 1], one item per (pair, block) */
-        size_t blocks_total = 0;
-        for (int k = 0; k < nq; ++k)
-            blocks_total += (size_t)((pp[k].n_theta + 1) / 2) * ncb;
         if ((rc = ensure(ctx, ctx->b_items, 64 + 2 * blocks_total * 4))) return rc;
-        for (int k = 0; k < nq; ++k)
-            if ((rc = ensure_xgrid_f(ctx, *pp[k].grid))) return rc;
+        for (BatchPrep& p : pp)
+            if ((rc = ensure_xgrid_f(ctx, *p.grid))) return rc;
     }
     if ((rc = ensure(ctx, ctx->b_out, (size_t)nq * (sizeof(csm_result) + 4)))) return rc;
-    const size_t jobs_bytes = (size_t)nq * (sizeof(ProjJob) + sizeof(BinJob) + sizeof(FinalJob) +
-                                            (size_t)(H + 1) * sizeof(ScoreJob) + (size_t)H * sizeof(ZeroJob));
+    jobs_bytes = (size_t)nq * (sizeof(ProjJob) + sizeof(BinJob) + sizeof(FinalJob) +
+                                 (size_t)(H + 1) * sizeof(ScoreJob) + (size_t)H * sizeof(ZeroJob));
     if ((rc = ensure(ctx, ctx->b_jobs, jobs_bytes + 1024))) return rc;
 
-    double* d_scans = reinterpret_cast<double*>(ctx->b_prod.p);
-    int32_t* d_col = reinterpret_cast<int32_t*>(ctx->b_hits.p);
-    int32_t* d_row = d_col + hit_total;
-    uint32_t* d_sorted = reinterpret_cast<uint32_t*>(ctx->b_sorted.p);
-    uint32_t* d_sorted_rc = reinterpret_cast<uint32_t*>(ctx->b_sorted_rc.p);
-    TileRec* d_tiles = reinterpret_cast<TileRec*>(ctx->b_tiles.p);
-    int32_t* d_ntiles = reinterpret_cast<int32_t*>(ctx->b_ntiles.p);
-    uint32_t* d_lvl_s = reinterpret_cast<uint32_t*>(ctx->b_lvl.p);
-    uint32_t* d_lvl_k = d_lvl_s + lvl_total;
-    BlockBest* d_best = reinterpret_cast<BlockBest*>(ctx->b_best.p);
-    csm_result* d_out = reinterpret_cast<csm_result*>(ctx->b_out.p);
-    uint32_t* d_flags = reinterpret_cast<uint32_t*>(d_out + nq);
+    d_scans = ctx->b_prod.as<double>();
+    d_out = ctx->b_out.as<csm_result>();
+    d_flags = reinterpret_cast<uint32_t*>(d_out + nq);
 
     if (!resident)
         HIP_TRY(ctx, hipMemcpyAsync(d_scans, scans, scan_total * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, (size_t)nq * 4, ctx->stream));
-
     tick("workspace");
-    /* ---- job tables ---- */
-    std::vector<ProjJob> ij(nq);
-    std::vector<BinJob> bj(nq);
-    std::vector<FinalJob> fj(nq);
-    std::vector<std::vector<ScoreJob>> sj(H + 1, std::vector<ScoreJob>(nq));
-    std::vector<ZeroJob> zj((size_t)nq * H);
-    size_t zero_words_max = 0;
-    for (int k = 0; k < nq; ++k) {
-        const csm_loop_query& q = queries[idx[k]];
-        const csm_summary& o = out[idx[k]];
-        const BatchPrep& p = pp[k];
-        const DeviceGrid& g = *p.grid;
-        const int x_lo = -p.win_x, y_lo = -p.win_y;
-        const int min_known = resident ? resident->windows[idx[k]].min_known
-                                       : csm_host_min_known(p.n, spec.known_thr);
+    return CSM_OK;
+}
 
-        ProjJob& I = ij[k];
-        std::memset(&I, 0, sizeof(I));
-        I.angles = d_scans + scan_off[k];
-        I.ranges = d_scans + scan_off[k] + p.n;
-        I.hit_col = resident ? const_cast<int32_t*>(resident->hit_col[idx[k]]) : d_col + p.hit_off;
-        I.hit_row = resident ? const_cast<int32_t*>(resident->hit_row[idx[k]]) : d_row + p.hit_off;
-        I.flags = d_flags + k;
-        I.n_theta = p.n_theta;
-        I.n_points = p.n;
-        I.win_theta = p.win_t;
-        I.sensor_x = o.sensor_pose[0];
-        I.sensor_y = o.sensor_pose[1];
-        I.sensor_theta = o.sensor_pose[2];
-        I.step_theta = o.step_theta;
-        I.off_x = q.geometry.offset_x;
-        I.off_y = q.geometry.offset_y;
-        I.res = q.geometry.resolution;
-        I.check_nodes = spec.bnb ? 1 : 0;
-        I.flag_uncertain = 1;
-        I.x_lo = x_lo;
-        I.y_lo = y_lo;
-        I.nx = nx;
-        I.ny = ny;
-        I.step_x = o.step_x;
-        I.step_y = o.step_y;
+/* Stage 4, for query k: its projection, binning, level, fine and final records. */
+void BatchGroup::build_jobs(int k)
+{
+    const int i = idx[k];
+    const csm_loop_query& q = queries[i];
+    const csm_summary& o = out[i];
+    const BatchPrep& p = pp[k];
+    const DeviceGrid& gr = *p.grid;
+    const int min_known = min_known_of(k);
+    uint32_t* const flags = d_flags + k;
+    int32_t* const hits = ctx->b_hits.as<int32_t>() + p.hit_off;     /* [col | row] */
+    uint32_t* const lvl_s = ctx->b_lvl.as<uint32_t>();
+    uint32_t* const lvl_k = lvl_s + lvl_total;
 
-        BinJob& B = bj[k];
-        std::memset(&B, 0, sizeof(B));
-        B.hit_col = I.hit_col;
-        B.hit_row = I.hit_row;
-        B.sorted_pb = d_sorted + p.hit_off;
-        B.sorted_rc = H > 0 ? d_sorted_rc + p.hit_off : nullptr;
-        B.tiles = d_tiles + p.tile_off;
-        B.n_tiles = d_ntiles + p.theta_off;
-        B.flags = d_flags + k;
-        B.n_theta = p.n_theta;
-        B.n_points = p.n;
-        B.max_tiles = p.max_tiles;
-        B.rows = g.rows;
-        B.cols = g.cols;
-        B.x_lo = x_lo;
-        B.y_lo = y_lo;
-        B.x_hi = x_lo + nx - 1;
-        B.y_hi = y_lo + ny - 1;
-        B.tiles_x = p.tiles_x;
-        B.tiles_y = p.tiles_y;
-        B.known_r0 = g.known_r0;
-        B.known_c0 = g.known_c0;
-        B.hash_size = joint ? csm::binj_hash_size(p.n) : bin_hash_size(p.n);
-        B.max_mult = lp[0].weighted ? kMaxMult : 1;
-        B.lstride = lstride;
-        B.pair_mode = joint ? 2 : lp[0].pairs ? 1 : 0;
+    ProjJob& I = ij[k];
+    I = proj_job(q.geometry, o.sensor_pose, o.step_theta, p.win_t, p.n, d_scans + scan_off[k],
+                 d_scans + scan_off[k] + p.n, resident ? const_cast<int32_t*>(resident->hit_col[i]) : hits,
+                 resident ? const_cast<int32_t*>(resident->hit_row[i]) : hits + hit_total);
+    I.flags = flags;
+    I.check_nodes = spec.bnb ? 1 : 0;
+    I.flag_uncertain = 1;
+    I.x_lo = p.x_lo;
+    I.y_lo = p.y_lo;
+    I.nx = p.nx;
+    I.ny = p.ny;
+    I.step_x = o.step_x;
+    I.step_y = o.step_y;
+
+    BinJob& B = bj[k];
+    B = bin_job(gr, p, p.n_theta, p.n, p.max_tiles, I.hit_col, I.hit_row, ctx->b_sorted.as<uint32_t>() + p.hit_off,
+                ctx->b_tiles.as<TileRec>() + p.tile_off, ctx->b_ntiles.as<int32_t>() + p.theta_off, flags,
+                joint ? 2 : lp[0].pairs ? 1 : 0);
+    B.sorted_rc = H > 0 ? ctx->b_sorted_rc.as<uint32_t>() + p.hit_off : nullptr;
+    B.hash_size = joint ? csm::binj_hash_size(p.n) : bin_hash_size(p.n);
+    B.max_mult = lp[0].weighted ? kMaxMult : 1;
+    B.lstride = lp[0].lstride;
 #ifdef CSM_BIN_TIMING
-        B.tuning_counters = bin_debug_buffer();
+    B.tuning_counters = bin_debug_buffer();
 #endif
-        B.frame_shift = lp[0].pairs ? ((ny - 1) & 1) : 0;
-        B.n_band = H;
-        for (int h = 1; h <= H; ++h) {
-            B.band_win[h - 1] = spec.stride[h];
-            B.band_nx[h - 1] = nx / spec.stride[h];
-            B.band_ny[h - 1] = ny / spec.stride[h];
-        }
+    B.n_band = H;
 
-        ScoreJob base;
-        std::memset(&base, 0, sizeof(base));
-        base.rows = g.rows;
-        base.cols = g.cols;
-        base.pitch = g.pitch;
-        base.sorted_pb = B.sorted_pb;
-        base.tiles = B.tiles;
-        base.n_tiles = B.n_tiles;
-        base.n_theta = p.n_theta;
-        base.n_points = p.n;
-        base.max_tiles = p.max_tiles;
-        base.x_lo = x_lo;
-        base.y_lo = y_lo;
-        base.flags = d_flags + k;
-        base.min_known = min_known;
-        base.joint = joint ? 1 : 0;
-        base.rank_l = spec.bnb ? 1 : spec.unit;
-        for (int h = 1; h <= H; ++h) {
-            ScoreJob& S = sj[h][k];
-            S = base;
-            S.cells = g.levels[p.level[h]].cells;
-            S.nx = nx / spec.stride[h];
-            S.ny = ny / spec.stride[h];
-            S.stride = spec.stride[h];
-            S.log2_stride = ilog2_exact(spec.stride[h]);
-            /* a leaf's own known count bounds every ancestor's from below when
-             * no read can fall in the edge band: the level passes are only
-             * needed to detect (and then handle) that case */
-            S.skip_unless_band = spec.bnb ? 1 : (min_known <= 1);
-            S.sorted_pb = B.sorted_rc;
-            S.acc_s = d_lvl_s + p.lvl_off[h];
-            S.acc_k = d_lvl_k + p.lvl_off[h];
-            /* the level's atomic accumulators: cleared only when the pass will run */
-            ZeroJob& Z0 = zj[(size_t)k * H + (h - 1)];
-            Z0.a = S.acc_s;
-            Z0.b = S.acc_k;
-            Z0.words = (size_t)p.n_theta * S.nx * S.ny;
-            Z0.flags = d_flags + k;
-            Z0.always = S.skip_unless_band ? 0 : 1;
-            Z0.pad = 0;
-            zero_words_max = std::max(zero_words_max, Z0.words);
-        }
-        ScoreJob& F = sj[0][k];
-        F = base;
-        F.cells = g.levels[p.level[0]].cells;
-        F.xg = g.xg.as<uint32_t>();
-        F.xg_pitch = g.xg_pitch;
-        F.xg_pad = g.xg_pad;
-        F.nx = nx;
-        F.ny = ny;
-        F.stride = 1;
-        F.block_best = d_best + p.best_off;
-        if (bound_pass) {
-            F.xgf = g.xgf.as<float>();
-            F.approx_best = reinterpret_cast<float*>(ctx->b_abest.p) + p.best_off;
-            /* |fp32 key - key| <= (n + 2) 2^-24 * key for a sum of n non-negative terms (one rounding
-             * per fused multiply-add, one for each cell's float, one for joining the two accumulator
-             * sets), n <= beams. A candidate that reaches the winner's exact key has an fp32 key of at
-             * least max_fp32 * (1 - 3 (n + 3) 2^-24); the kernel compares with 4 (n + 3) 2^-24. */
-            F.approx_slack = 4.0f * (float)(p.n + 3) * 5.9604645e-08f;
-            F.bound_stats = reinterpret_cast<uint32_t*>(ctx->bound_stats.p);
-            /* found <=> sum of probabilities / n > threshold, and that sum is (0.998 / 65534 / 499) * key
-             * up to the f64 rounding of the beam-order summation (1e-12 relative): a candidate below
-             * this key cannot be reported */
-            const double thr = resident ? resident->windows[idx[k]].score_threshold : spec.score_thr;
-            F.key_floor = thr > 0.0 ? (float)(thr * p.n * (65534.0 * 499.0 / 0.998) * (1.0 - 1e-9)) *
-                                          (1.0f - F.approx_slack)
-                                    : 0.0f;
-            F.round1_record = resident ? (const void*)(resident->out_dev + idx[k]) : (const void*)(d_out + k);
-            if (resident && resident->dump_f)
-                F.dump_f = resident->dump_f[idx[k]];
-        }
-        if (resident && resident->dump_s)
-            F.dump_s = resident->dump_s[idx[k]];
-        if (resident && resident->dump_k)
-            F.dump_k = resident->dump_k[idx[k]];
-        /* branch and bound tests every popped node, leaf included; the
-         * correlative sweep tests the coarse node only */
-        F.check_own_known = spec.bnb || H == 0;
-        F.elig_only_if_band = spec.bnb ? 1 : (min_known <= 1);
-        F.n_elig = H;
-        for (int h = 1; h <= H; ++h) {
-            F.elig[h - 1].k = d_lvl_k + p.lvl_off[h];
-            F.elig[h - 1].s = d_lvl_s + p.lvl_off[h];
-            F.elig[h - 1].div = spec.stride[h];
-            F.elig[h - 1].nxc = nx / spec.stride[h];
-            F.elig[h - 1].nyc = ny / spec.stride[h];
-        }
-
-        FinalJob& Z = fj[k];
-        std::memset(&Z, 0, sizeof(Z));
-        Z.block_best = F.block_best;
-        Z.n_entries = p.n_theta * ncb;
-        Z.nx = nx;
-        Z.ny = ny;
-        Z.rank_l = spec.bnb ? 1 : spec.unit;
-        Z.x_lo = x_lo;
-        Z.y_lo = y_lo;
-        Z.win_theta = p.win_t;
-        /* scan_matcher_branch_bound.cpp:144-146 / scan_matcher_correlative.cpp:149-152 */
-        Z.init_x = spec.bnb ? 0 : -p.win_x;
-        Z.init_y = spec.bnb ? 0 : -p.win_y;
-        Z.init_theta = spec.bnb ? 0 : -p.win_t;
-        Z.cells = F.cells;
-        Z.rows = g.rows;
-        Z.cols = g.cols;
-        Z.pitch = g.pitch;
-        Z.hit_col = I.hit_col;
-        Z.hit_row = I.hit_row;
-        Z.n_points = p.n;
-        Z.score_thr = resident ? resident->windows[idx[k]].score_threshold : spec.score_thr;
-        Z.lut = ctx->lut_dev.as<double>();
-        Z.flags_in = d_flags + k;
-        Z.out = resident ? resident->out_dev + idx[k] : d_out + k;
+    ScoreJob& F = sj[0][k];
+    F = score_job(gr, gr.levels[p.level[0]].cells, 1, B, min_known);
+    F.joint = joint ? 1 : 0;
+    F.rank_l = spec.bnb ? 1 : spec.unit;
+    for (int h = 1; h <= H; ++h) {
+        B.band_win[h - 1] = spec.stride[h];
+        B.band_nx[h - 1] = p.nx / spec.stride[h];
+        B.band_ny[h - 1] = p.ny / spec.stride[h];
+        ScoreJob& S = sj[h][k];
+        S = score_job(gr, gr.levels[p.level[h]].cells, spec.stride[h], B, min_known);
+        S.joint = F.joint;
+        S.rank_l = F.rank_l;
+        /* a leaf's own known count bounds every ancestor's from below when
+         * no read can fall in the edge band: the level passes are only
+         * needed to detect (and then handle) that case */
+        S.skip_unless_band = spec.bnb ? 1 : (min_known <= 1);
+        S.sorted_pb = B.sorted_rc;
+        S.acc_s = lvl_s + p.lvl_off[h];
+        S.acc_k = lvl_k + p.lvl_off[h];
+        F.elig[h - 1] = EligLevel { S.acc_k, S.acc_s, S.stride, S.nx, S.ny };
+        /* the level's atomic accumulators: cleared only when the pass will run */
+        ZeroJob& Z0 = zj[(size_t)k * H + (h - 1)];
+        Z0 = ZeroJob { S.acc_s, S.acc_k, (size_t)p.n_theta * S.nx * S.ny, flags, S.skip_unless_band ? 0 : 1, 0 };
+        zero_words_max = std::max(zero_words_max, Z0.words);
     }
-    /* upload the job tables: one device buffer with 256-byte aligned sections, filled
-     * from one pinned block by ONE copy (five copies from pageable vectors cost 18 us per
-     * 64-window chain and a staging pass each) */
+    F.xg = gr.xg.as<uint32_t>();
+    F.xg_pitch = gr.xg_pitch;
+    F.xg_pad = gr.xg_pad;
+    F.block_best = ctx->b_best.as<BlockBest>() + p.best_off;
+    if (bound_pass) {
+        F.xgf = gr.xgf.as<float>();
+        F.approx_best = ctx->b_abest.as<float>() + p.best_off;
+        /* |fp32 key - key| <= (n + 2) 2^-24 * key for a sum of n non-negative terms (one rounding
+         * per fused multiply-add, one for each cell's float, one for joining the two accumulator
+         * sets), n <= beams. A candidate that reaches the winner's exact key has an fp32 key of at
+         * least max_fp32 * (1 - 3 (n + 3) 2^-24); the kernel compares with 4 (n + 3) 2^-24. */
+        F.approx_slack = 4.0f * (float)(p.n + 3) * 5.9604645e-08f;
+        F.bound_stats = ctx->bound_stats.as<uint32_t>();
+        /* found <=> sum of probabilities / n > threshold, and that sum is (0.998 / 65534 / 499) * key
+         * up to the f64 rounding of the beam-order summation (1e-12 relative): a candidate below
+         * this key cannot be reported */
+        const double thr = score_thr(k);
+        F.key_floor = thr > 0.0 ? (float)(thr * p.n * (65534.0 * 499.0 / 0.998) * (1.0 - 1e-9)) *
+                                      (1.0f - F.approx_slack)
+                                : 0.0f;
+        F.round1_record = resident ? (const void*)(resident->out_dev + i) : (const void*)(d_out + k);
+        if (resident && resident->dump_f)
+            F.dump_f = resident->dump_f[i];
+    }
+    if (resident && resident->dump_s)
+        F.dump_s = resident->dump_s[i];
+    if (resident && resident->dump_k)
+        F.dump_k = resident->dump_k[i];
+    /* branch and bound tests every popped node, leaf included; the
+     * correlative sweep tests the coarse node only */
+    F.check_own_known = spec.bnb || H == 0;
+    F.elig_only_if_band = spec.bnb ? 1 : (min_known <= 1);
+    F.n_elig = H;
+
+    FinalJob& Z = fj[k];
+    Z = final_job(F, p.n_theta * lp[0].ncb(), I.hit_col, I.hit_row, score_thr(k), ctx->lut_dev.as<double>(),
+                  resident ? resident->out_dev + i : d_out + k);
+    if (spec.bnb) {
+        /* scan_matcher_branch_bound.cpp:144-146 (scan_matcher_correlative.cpp:149-152: the first candidate) */
+        Z.init_x = Z.init_y = Z.init_theta = 0;
+    }
+}
+
+/* Stage 4: every query's job records. */
+int BatchGroup::fill_job_tables()
+{
+    ij.resize(nq);
+    bj.resize(nq);
+    fj.resize(nq);
+    sj.assign(H + 1, std::vector<ScoreJob>(nq));
+    zj.resize((size_t)nq * H);
+    for (int k = 0; k < nq; ++k)
+        build_jobs(k);
+    return CSM_OK;
+}
+
+
+/* A pinned block of at least `bytes` for a batch's job tables: the first in the pool that is large
+ * enough, else a new one with room to grow. */
+static int take_pinned(csm_ctx* ctx, size_t bytes, PinBuf* out)
+{
+    for (size_t b = 0; b < ctx->pin_free.size(); ++b)
+        if (ctx->pin_free[b].cap >= bytes) {
+            *out = std::move(ctx->pin_free[b]);
+            ctx->pin_free.erase(ctx->pin_free.begin() + b);
+            return CSM_OK;
+        }
+    return grow(ctx, *out, bytes, bytes + bytes / 4 + 4096, false);
+}
+
+/* Stage 5: upload the job tables: one device buffer with 256-byte aligned sections, filled from
+ * one pinned block by ONE copy (five copies from pageable vectors cost 18 us per 64-window chain
+ * and a staging pass each). */
+int BatchGroup::upload_tables()
+{
     const size_t tables_cap = jobs_bytes + (size_t)nq * 4 + 256 * (size_t)(H + 10);
+    int rc;
     if ((rc = ensure(ctx, ctx->b_jobs, tables_cap))) return rc;
-    std::shared_ptr<std::pair<void*, size_t>> pin_block;
-    {
-        std::pair<void*, size_t> blk(nullptr, 0);
-        for (size_t b = 0; b < ctx->pin_free.size(); ++b)
-            if (ctx->pin_free[b].second >= tables_cap) {
-                blk = ctx->pin_free[b];
-                ctx->pin_free.erase(ctx->pin_free.begin() + b);
-                break;
-            }
-        if (!blk.first) {
-            const size_t cap = tables_cap + tables_cap / 4 + 4096;
-            if (hipHostMalloc(&blk.first, cap, hipHostMallocDefault) != hipSuccess)
-                return fail(ctx, CSM_ENOMEM, "hipHostMalloc(%zu) failed", cap);
-            blk.second = cap;
-        }
-        csm_ctx* owner = ctx;
-        pin_block = std::shared_ptr<std::pair<void*, size_t>>(
-            new std::pair<void*, size_t>(blk), [owner](std::pair<void*, size_t>* b) {
-                owner->pin_free.push_back(*b);
-                delete b;
-            });
-    }
+    if ((rc = take_pinned(ctx, tables_cap, &tables))) return rc;
     char* const jb0 = reinterpret_cast<char*>(ctx->b_jobs.p);
-    char* const hb0 = reinterpret_cast<char*>(pin_block->first);
+    char* const hb0 = tables.as<char>();
     size_t tables_off = 0;
     auto put = [&](const void* src, size_t bytes, char** dev) -> hipError_t {
         *dev = jb0 + tables_off;
@@ -666,21 +616,27 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
         tables_off += (bytes + 255) & ~(size_t)255;
         return tables_off <= tables_cap ? hipSuccess : hipErrorInvalidValue;
     };
-    char *d_ij, *d_bj, *d_fj, *d_idx = nullptr, *d_zj = nullptr;
     if (H > 0)
         HIP_TRY(ctx, put(zj.data(), zj.size() * sizeof(ZeroJob), &d_zj));
     if (!resident)
         HIP_TRY(ctx, put(idx.data(), (size_t)nq * sizeof(int), &d_idx));
-    std::vector<char*> d_sj(H + 1);
+    d_sj.resize(H + 1);
     HIP_TRY(ctx, put(ij.data(), nq * sizeof(ProjJob), &d_ij));
     HIP_TRY(ctx, put(bj.data(), nq * sizeof(BinJob), &d_bj));
     HIP_TRY(ctx, put(fj.data(), nq * sizeof(FinalJob), &d_fj));
     for (int h = 0; h <= H; ++h)
         HIP_TRY(ctx, put(sj[h].data(), nq * sizeof(ScoreJob), &d_sj[h]));
     HIP_TRY(ctx, hipMemcpyAsync(jb0, hb0, tables_off, hipMemcpyHostToDevice, ctx->stream));
-
     tick("jobs");
-    /* ---- launches ---- */
+    return CSM_OK;
+}
+
+/* Stage 6: projection, binning, edge-band clears, coarser levels, bound pass, exact fine level and
+ * finalize, in one chain on the context's stream. */
+int BatchGroup::launch_chain()
+{
+    const ScoreJob* fine_jobs = reinterpret_cast<const ScoreJob*>(d_sj[0]);
+    int rc;
     if (!resident) {
         ScopedTimer tm(ctx, "project");
         const int pb = ceil_div(n_points_max, kBlock);
@@ -726,7 +682,7 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
         PassPlan fp = lp[0];
         fp.fp32 = true;
         ScopedTimer tm(ctx, "score_bound");
-        if ((rc = launch_score_batch(ctx, reinterpret_cast<const ScoreJob*>(d_sj[0]), nq, fp, n_theta_max, 1)))
+        if ((rc = launch_score_batch(ctx, fine_jobs, nq, fp, n_theta_max, 1)))
             return rc;
     }
     auto finalize = [&]() -> int {
@@ -735,46 +691,49 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
         return launched_ok(ctx, csm_launch::finalize_batch(ctx->stream, ctx->device, nq, lds,
                                                            reinterpret_cast<const FinalJob*>(d_fj)), "finalize");
     };
-    if (bound_pass) {
-        size_t blocks_total = 0;
-        for (int k = 0; k < nq; ++k)
-            blocks_total += (size_t)((pp[k].n_theta + 1) / 2) * ncb;
-        uint32_t* counts = reinterpret_cast<uint32_t*>(ctx->b_items.p);
-        uint32_t* items0 = counts + 16;
-        uint32_t* items1 = items0 + blocks_total;
-        JointList list;
-        list.items[0] = items0;
-        list.items[1] = items1;
-        list.counts = counts;
-        list.blocks = (int)std::min<size_t>(blocks_total, 2048);
-        const int split_cb = tail_split(ctx, lp[0]) ? lp[0].ncbx * (lp[0].ncby - 1) : ncb;
-        for (int round = 1; round <= (two_rounds ? 2 : 1); ++round) {
-            {
-                ScopedTimer tm(ctx, "score_fine");
-                HIP_TRY(ctx, hipMemsetAsync(counts, 0, 8, ctx->stream));
-                const int e = csm::launch_bound_select(ctx->stream, reinterpret_cast<const ScoreJob*>(d_sj[0]), nq, ncb,
-                                                       split_cb, items0, items1, counts, (uint32_t)blocks_total, round);
-                if (e != 0)
-                    return fail(ctx, CSM_EIO, "k_bound_select launch failed: %s", hipGetErrorString((hipError_t)e));
-                if ((rc = launch_score_batch(ctx, reinterpret_cast<const ScoreJob*>(d_sj[0]), nq, lp[0], n_theta_max, 1,
-                                             0, &list)))
-                    return rc;
-            }
-            if ((rc = finalize()))
-                return rc;
-        }
-    } else {
+    if (!bound_pass) {
         {
             ScopedTimer tm(ctx, "score_fine");
-            if ((rc = launch_score_batch(ctx, reinterpret_cast<const ScoreJob*>(d_sj[0]), nq, lp[0], n_theta_max, 1)))
+            if ((rc = launch_score_batch(ctx, fine_jobs, nq, lp[0], n_theta_max, 1)))
+                return rc;
+        }
+        return finalize();
+    }
+    const int ncb = lp[0].ncb();
+    uint32_t* counts = reinterpret_cast<uint32_t*>(ctx->b_items.p);
+    uint32_t* items0 = counts + 16;
+    uint32_t* items1 = items0 + blocks_total;
+    JointList list;
+    list.items[0] = items0;
+    list.items[1] = items1;
+    list.counts = counts;
+    list.blocks = (int)std::min<size_t>(blocks_total, 2048);
+    const int split_cb = tail_split(ctx, lp[0]) ? lp[0].ncbx * (lp[0].ncby - 1) : ncb;
+    for (int round = 1; round <= (two_rounds ? 2 : 1); ++round) {
+        {
+            ScopedTimer tm(ctx, "score_fine");
+            HIP_TRY(ctx, hipMemsetAsync(counts, 0, 8, ctx->stream));
+            const int e = csm::launch_bound_select(ctx->stream, fine_jobs, nq, ncb, split_cb, items0, items1, counts,
+                                                   (uint32_t)blocks_total, round);
+            if (e != 0)
+                return fail(ctx, CSM_EIO, "k_bound_select launch failed: %s", hipGetErrorString((hipError_t)e));
+            if ((rc = launch_score_batch(ctx, fine_jobs, nq, lp[0], n_theta_max, 1, 0, &list)))
                 return rc;
         }
         if ((rc = finalize()))
             return rc;
     }
+    return CSM_OK;
+}
+
+/* Stage 7. Resident mode: asynchronous, the records stay on the device and the pinned block of the
+ * job tables is held until the chain has run. Otherwise the records in query order go to the
+ * device copy (csm_copy_last_batch_records) and to the host, where flagged queries take the exact
+ * path and the summaries are completed. */
+int BatchGroup::finish()
+{
+    int rc;
     if (resident) {
-        /* asynchronous: the records stay on the device. The pinned block the job tables
-         * are copied from goes back to the pool when this chain has run. */
         hipEvent_t done = nullptr;
         if (!ctx->event_pool.empty()) {
             done = ctx->event_pool.back();
@@ -783,10 +742,9 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
             HIP_TRY(ctx, hipEventCreate(&done));
         }
         HIP_TRY(ctx, hipEventRecord(done, ctx->stream));
-        ctx->resident_hold.emplace_back(done, std::shared_ptr<void>(pin_block));
+        ctx->resident_hold.emplace_back(done, std::move(tables));
         return CSM_OK;
     }
-    /* device copy of the records in query order (csm_copy_last_batch_records) */
     csm_result* rec_dev = reinterpret_cast<csm_result*>(ctx->rec_dev.p);
     if (rec_dev) {
         if ((rc = launched_ok(ctx, csm_launch::scatter_records(ctx->stream, d_out, reinterpret_cast<const int32_t*>(d_idx),
@@ -838,31 +796,38 @@ int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vect
     return CSM_OK;
 }
 
-} /* namespace csm_host */
-
-extern "C" {
-
-
-int csm_bnb_match_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
-                        const csm_bnb_params* prm, csm_summary* out)
+/* One group of queries that share (nx, ny): the whole device pipeline. */
+static int run_batch_group(csm_ctx* ctx, const csm_loop_query* queries, const std::vector<int>& idx,
+                           const std::vector<std::vector<int>>& levels, const BatchSpec& spec, csm_summary* out, const ResidentBatch* resident = nullptr)
 {
-    if (!ctx || !queries || n_queries < 1 || !prm || !out || prm->node_height_max < 0 ||
-        prm->node_height_max >= kMaxElig)
-        return fail(ctx, CSM_EINVAL, "csm_bnb_match_batch: bad arguments");
+    BatchGroup g(ctx, queries, idx, levels, spec, out, resident);
+    g.tick(nullptr);
+    int rc = g.plan();
+    if (!rc) rc = g.stage_scans();
+    if (!rc) rc = g.size_workspaces();
+    if (!rc) rc = g.fill_job_tables();
+    if (!rc) rc = g.upload_tables();
+    if (!rc) rc = g.launch_chain();
+    if (!rc) rc = g.finish();
+    if (g.tables.p)                       /* not held by a resident chain: the copy has run (or failed) */
+        ctx->pin_free.push_back(std::move(g.tables));
+    return rc;
+}
+
+/* The loop-detection batches once their arguments are checked: pyramid levels built and cached
+ * per map id, as mPrecompMaps does (loop_detector_branch_bound.cpp:83-89), all missing ones in
+ * one launch; then one run_batch_group per leaf-window shape. */
+static int loop_batch(csm_ctx* ctx, const csm_loop_query* queries, int n_queries, BatchSpec spec, csm_summary* out)
+{
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int H = prm->node_height_max;
-    const bool host_timing = ctx->tune.host_timing;
+    const int H = spec.H;
+    const bool host_timing = ctx->tune.host_timing && spec.bnb;   /* the branch-and-bound batch's ticks */
     const auto tb0 = std::chrono::steady_clock::now();
-    {
-        int rc = begin_batch_records(ctx, n_queries);
-        if (rc)
-            return rc;
-    }
+    if (int rc = begin_batch_records(ctx, n_queries))
+        return rc;
     const auto t0 = std::chrono::steady_clock::now();
     if (host_timing)
         fprintf(stderr, "[bnb batch] begin_records %8.3f ms\n", std::chrono::duration<double, std::milli>(t0 - tb0).count());
-    /* pyramids: build and cache per map id, as mPrecompMaps does
-     * (loop_detector_branch_bound.cpp:83-89) */
     std::vector<std::vector<int>> levels(n_queries, std::vector<int>(H + 1, 0));
     std::vector<PendingBox> pending_levels;
     std::vector<double> max_range(n_queries, 0.0);
@@ -878,52 +843,31 @@ int csm_bnb_match_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_q
         if (!g)
             return fail(ctx, CSM_ENOENT, "query %d: map %llu not resident", i,
                         (unsigned long long)queries[i].map_id);
-        for (int h = 0; h <= H; ++h) {
-            int rc = level_for_window(ctx, *g, 1 << h, &levels[i][h], &pending_levels);
-            if (rc)
+        for (int h = 0; h <= H; ++h)      /* h = 0: the map itself */
+            if (int rc = level_for_window(ctx, *g, spec.stride[h], &levels[i][h], &pending_levels))
                 return rc;
-        }
     }
-    {
-        /* all missing levels of all maps: one launch */
-        int rc = launch_box_jobs(ctx, pending_levels);
-        if (rc)
-            return rc;
-    }
+    if (int rc = launch_box_jobs(ctx, pending_levels))
+        return rc;
     const auto t1 = std::chrono::steady_clock::now();
-
     if (host_timing)
         fprintf(stderr, "[bnb batch] levels        %8.3f ms\n", std::chrono::duration<double, std::milli>(t1 - t0).count());
+
     /* group queries by leaf-window shape */
     std::memset(out, 0, sizeof(csm_summary) * (size_t)n_queries);
     std::map<std::pair<int, int>, std::vector<int>> groups;
     for (int i = 0; i < n_queries; ++i) {
         double sx, sy, st;
         search_step_from_max(queries[i].geometry.resolution, max_range[i], &sx, &sy, &st);
-        const int big = 1 << H;
-        const int nx = ceil_div(2 * csm_host_window(prm->range_x, sx) + 1, big) * big;
-        const int ny = ceil_div(2 * csm_host_window(prm->range_y, sy) + 1, big) * big;
-        groups[{ nx, ny }].push_back(i);
+        groups[{ padded_extent(csm_host_window(spec.range_x, sx), spec.unit),
+                 padded_extent(csm_host_window(spec.range_y, sy), spec.unit) }].push_back(i);
     }
+    spec.max_range = max_range.data();
     for (auto& kv : groups) {
-        BatchSpec spec;
-        spec.bnb = true;
-        spec.max_range = max_range.data();
-        spec.H = H;
-        for (int h = 0; h <= H; ++h)
-            spec.stride[h] = 1 << h;
-        spec.unit = 1 << H;
-        spec.range_x = prm->range_x;
-        spec.range_y = prm->range_y;
-        spec.range_theta = prm->range_theta;
-        spec.score_thr = prm->score_threshold;
-        spec.known_thr = prm->known_rate_threshold;
-        spec.bnb_params = prm;
         if (host_timing)
             fprintf(stderr, "[bnb batch] grouping      %8.3f ms\n",
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
-        int rc = run_batch_group(ctx, queries, kv.second, levels, spec, out);
-        if (rc)
+        if (int rc = run_batch_group(ctx, queries, kv.second, levels, spec, out))
             return rc;
     }
     const auto t2 = std::chrono::steady_clock::now();
@@ -936,6 +880,32 @@ int csm_bnb_match_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_q
     return CSM_OK;
 }
 
+} /* namespace csm_host */
+
+extern "C" {
+
+
+int csm_bnb_match_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
+                        const csm_bnb_params* prm, csm_summary* out)
+{
+    if (!ctx || !queries || n_queries < 1 || !prm || !out || prm->node_height_max < 0 ||
+        prm->node_height_max >= kMaxElig)
+        return fail(ctx, CSM_EINVAL, "csm_bnb_match_batch: bad arguments");
+    BatchSpec spec;
+    spec.bnb = true;
+    spec.H = prm->node_height_max;
+    for (int h = 0; h <= spec.H; ++h)
+        spec.stride[h] = 1 << h;
+    spec.unit = 1 << spec.H;
+    spec.range_x = prm->range_x;
+    spec.range_y = prm->range_y;
+    spec.range_theta = prm->range_theta;
+    spec.score_thr = prm->score_threshold;
+    spec.known_thr = prm->known_rate_threshold;
+    spec.bnb_params = prm;
+    return loop_batch(ctx, queries, n_queries, spec, out);
+}
+
 /* LoopDetectorCorrelative::Detect's search part for a batch of queries
  * (src/mapping/loop_detector_correlative.cpp:59-156 lines 68-108): one coarse
  * map per local map id, cached on the device like mPrecompMaps. */
@@ -944,75 +914,19 @@ int csm_correlative_match_batch(csm_ctx* ctx, const csm_loop_query* queries, int
 {
     if (!ctx || !queries || n_queries < 1 || !prm || !out || prm->low_resolution < 1)
         return fail(ctx, CSM_EINVAL, "csm_correlative_match_batch: bad arguments");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int L = prm->low_resolution;
-    const int H = L > 1 ? 1 : 0;
-    {
-        int rc = begin_batch_records(ctx, n_queries);
-        if (rc)
-            return rc;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<PendingBox> pending_levels;
-    std::vector<std::vector<int>> levels(n_queries, std::vector<int>(H + 1, 0));
-    std::vector<double> max_range(n_queries, 0.0);
-    {
-        const int i = scans_finite_max(queries, n_queries, max_range.data());
-        if (i >= 0 && (!queries[i].scan.angles || !queries[i].scan.ranges || queries[i].scan.n_points < 1))
-            return fail(ctx, CSM_EINVAL, "query %d: empty scan", i);
-        if (i >= 0)
-            return fail(ctx, CSM_EINVAL, "query %d: scan holds a non-finite range or angle", i);
-    }
-    for (int i = 0; i < n_queries; ++i) {
-        DeviceGrid* g = find_grid(ctx, queries[i].map_id);
-        if (!g)
-            return fail(ctx, CSM_ENOENT, "query %d: map %llu not resident", i,
-                        (unsigned long long)queries[i].map_id);
-        if (H) {
-            int rc = level_for_window(ctx, *g, L, &levels[i][1], &pending_levels);
-            if (rc)
-                return rc;
-        }
-    }
-    {
-        int rc = launch_box_jobs(ctx, pending_levels);
-        if (rc)
-            return rc;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    std::memset(out, 0, sizeof(csm_summary) * (size_t)n_queries);
-    std::map<std::pair<int, int>, std::vector<int>> groups;
-    for (int i = 0; i < n_queries; ++i) {
-        double sx, sy, st;
-        search_step_from_max(queries[i].geometry.resolution, max_range[i], &sx, &sy, &st);
-        const int nx = ceil_div(2 * csm_host_window(prm->range_x, sx) + 1, L) * L;
-        const int ny = ceil_div(2 * csm_host_window(prm->range_y, sy) + 1, L) * L;
-        groups[{ nx, ny }].push_back(i);
-    }
-    for (auto& kv : groups) {
-        BatchSpec spec;
-        spec.bnb = false;
-        spec.max_range = max_range.data();
-        spec.H = H;
-        spec.stride[0] = 1;
-        spec.stride[1] = L;
-        spec.unit = L;
-        spec.range_x = prm->range_x;
-        spec.range_y = prm->range_y;
-        spec.range_theta = prm->range_theta;
-        spec.score_thr = prm->score_threshold;
-        spec.known_thr = prm->known_rate_threshold;
-        spec.csm_params = prm;
-        int rc = run_batch_group(ctx, queries, kv.second, levels, spec, out);
-        if (rc)
-            return rc;
-    }
-    const auto t2 = std::chrono::steady_clock::now();
-    for (int i = 0; i < n_queries; ++i) {
-        out[i].input_setup_us = std::chrono::duration<double, std::micro>(t1 - t0).count() / n_queries;
-        out[i].optimization_us = std::chrono::duration<double, std::micro>(t2 - t1).count() / n_queries;
-    }
-    return CSM_OK;
+    BatchSpec spec;
+    spec.bnb = false;
+    spec.H = L > 1 ? 1 : 0;
+    spec.stride[1] = L;
+    spec.unit = L;
+    spec.range_x = prm->range_x;
+    spec.range_y = prm->range_y;
+    spec.range_theta = prm->range_theta;
+    spec.score_thr = prm->score_threshold;
+    spec.known_thr = prm->known_rate_threshold;
+    spec.csm_params = prm;
+    return loop_batch(ctx, queries, n_queries, spec, out);
 }
 
 /* csm_score_window_dev for many windows at once: one launch chain (k_bin_batch,
@@ -1056,8 +970,7 @@ int csm_score_windows_dump_dev(csm_ctx* ctx, int32_t n, const uint64_t* map_ids,
         }
         std::memset(&queries[i], 0, sizeof(csm_loop_query));
         queries[i].map_id = map_ids[i];
-        const int nx = ceil_div(2 * w.win_x + 1, L) * L, ny = ceil_div(2 * w.win_y + 1, L) * L;
-        groups[{ nx, ny, L, w.merge_mode }].push_back(i);
+        groups[{ padded_extent(w.win_x, L), padded_extent(w.win_y, L), L, w.merge_mode }].push_back(i);
     }
     ResidentBatch resident { windows, hit_col_dev, hit_row_dev, out_dev, dump_s_dev, dump_k_dev, dump_f_dev };
     /* drop the tables of earlier calls whose launch chains have completed */
@@ -1069,6 +982,7 @@ int csm_score_windows_dump_dev(csm_ctx* ctx, int32_t n, const uint64_t* map_ids,
         else if (hipEventQuery(ev) != hipSuccess)
             break;
         ctx->event_pool.push_back(ev);
+        ctx->pin_free.push_back(std::move(ctx->resident_hold.front().second));
         ctx->resident_hold.erase(ctx->resident_hold.begin());
     }
     for (auto& kv : groups) {
@@ -1076,7 +990,6 @@ int csm_score_windows_dump_dev(csm_ctx* ctx, int32_t n, const uint64_t* map_ids,
         BatchSpec spec;
         spec.bnb = false;
         spec.H = L > 1 ? 1 : 0;
-        spec.stride[0] = 1;
         spec.stride[1] = L;
         spec.unit = L;
         int rc = run_batch_group(ctx, queries.data(), kv.second, levels, spec, nullptr, &resident);

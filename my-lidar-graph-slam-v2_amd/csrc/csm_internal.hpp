@@ -227,9 +227,10 @@ struct csm_ctx {
     bool m_apply_attr = false;
     hipEvent_t m_ev[2] = { nullptr, nullptr };    /* device_us of csm_map_build_info */
     std::vector<double> stage;                    /* host staging of one scan (angles, ranges) */
-    /* job tables of csm_score_windows_dev calls (pageable sources of asynchronous
-     * uploads), each kept until the event recorded behind its launch chain has fired */
-    std::vector<std::pair<hipEvent_t, std::shared_ptr<void>>> resident_hold;
+    /* pinned job-table blocks of csm_score_windows_dev calls (sources of asynchronous
+     * uploads), each kept until the event recorded behind its launch chain has fired; an entry
+     * taken out must move its block back to pin_free (dropping it frees the block) */
+    std::vector<std::pair<hipEvent_t, PinBuf>> resident_hold;
     /* the fine-level job of the last launch chain (run_window, or the recorded job of a replayed
      * graph), for the tie collection pass: its flag word and two-phase eligibility levels are
      * facts of that launch, not of the window alone */
@@ -243,8 +244,8 @@ struct csm_ctx {
     std::map<std::string, KernelTimer> timers;
     std::vector<hipEvent_t> event_pool;
     /* pinned staging blocks of the batch entries' job tables, reused once the copy
-     * that reads them has run */
-    std::vector<std::pair<void*, size_t>> pin_free;
+     * that reads them has run (first fit) */
+    std::vector<PinBuf> pin_free;
 };
 
 namespace csm_host {

@@ -1,6 +1,7 @@
-/* csm_matchers.hpp -- what the matchers' host translation units share (csm_plan.hip: planner, launch
- * helpers, levels; csm_window.hip: one window at a time; csm_batch.hip: batches; csm_api.hip: context,
- * grids, pyramids, host restatements, timing). All of it lives in namespace csm_host. */
+/* csm_matchers.hpp -- what the matchers' host translation units share (csm_plan.hip: planner, window
+ * frame, job-record builders, launch helpers, levels; csm_window.hip: one window at a time; csm_batch.hip:
+ * batches; csm_api.hip: context, grids, pyramids, host restatements, timing). All of it lives in namespace
+ * csm_host. */
 #ifndef CSM_MATCHERS_HPP
 #define CSM_MATCHERS_HPP
 
@@ -27,14 +28,21 @@ struct PassPlan {
     int ncb() const { return ncbx * ncby; }
 };
 
+/* Candidate domain and tile frame of a window (window_frame): nx x ny candidates at cell offsets
+ * [x_lo, x_hi] x [y_lo, y_hi], binned over tiles_x x tiles_y tiles of the grid. */
+struct WindowFrame {
+    int nx = 0, ny = 0;
+    int x_lo = 0, y_lo = 0, x_hi = 0, y_hi = 0;
+    int tiles_x = 0, tiles_y = 0;
+};
+
 /* Launch geometry of one search window. */
-struct Plan {
+struct Plan : WindowFrame {
     int n_theta = 0, n = 0;
     int win_x = 0, win_y = 0, L = 1;
-    int nxc = 0, nyc = 0, nx = 0, ny = 0;
-    int x_lo = 0, y_lo = 0, x_hi = 0, y_hi = 0;
+    int nxc = 0, nyc = 0;
     PassPlan fine, coarse;
-    int tiles_x = 0, tiles_y = 0, max_tiles = 0;
+    int max_tiles = 0;
 };
 
 /* Work list of the exact joint kernel after the bound pass (k_bound_select): items of the main
@@ -105,9 +113,22 @@ bool plan_pass_pairs(const Tuning& tune, int nx, int ny, PassPlan* out, bool two
 int xgrid_pad_for(int nx, int ny);
 int pick_buffers(const Tuning& tune, size_t lds_one, long blocks);
 size_t pass_lds_bytes(const PassPlan& p);
+int padded_extent(int win, int unit);
+WindowFrame window_frame(const DeviceGrid& g, int win_x, int win_y, int unit);
 int make_plan(csm_ctx* ctx, const DeviceGrid& g, const csm_window* w, Plan* p);
+/* Job records: each starts zero-filled, with the fields every site sets the same way; the caller
+ * sets the rest. */
+ProjJob proj_job(const csm_geometry& geom, const double sensor_pose[3], double step_theta, int win_theta,
+                 int n_points, const double* angles, const double* ranges, int32_t* hit_col, int32_t* hit_row);
+BinJob bin_job(const DeviceGrid& g, const WindowFrame& f, int n_theta, int n_points, int max_tiles,
+               const int32_t* hit_col, const int32_t* hit_row, uint32_t* sorted_pb, TileRec* tiles,
+               int32_t* n_tiles, uint32_t* flags, int pair_mode);
+ScoreJob score_job(const DeviceGrid& g, const uint16_t* cells, int stride, const BinJob& entries, int min_known);
+FinalJob final_job(const ScoreJob& fine, int n_blocks, const int32_t* hit_col, const int32_t* hit_row,
+                   double score_thr, const double* lut, void* out);
 int launched_ok(csm_ctx* ctx, int e, const char* what);
 csm_launch::ScoreLaunch score_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, size_t lds);
+csm::JointLaunch joint_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, const uint16_t* lane_map);
 int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out);
 int launch_score(csm_ctx* ctx, const ScoreJob& job, const PassPlan& pp, int n_theta, int n_slices);
 int launch_score_list(csm_ctx* ctx, const ScoreJob& job, const PassPlan& pp, const uint32_t* items,

@@ -1,7 +1,8 @@
 /* csm_plan.hip -- the matchers' launch planning and level bookkeeping (host code only): bit-exact host
  * restatements (search step, probability table), the candidate-block planner of the scoring passes
  * (plan_pass, plan_pass_pairs, make_plan), the lane table, the launch helpers on top of csm_launch.hpp /
- * csm_joint.hpp, box-maximum levels and the pair-row copies of a grid. Declared in csm_matchers.hpp. */
+ * csm_joint.hpp, the window frame and the builders of the job records, box-maximum levels and the pair-row
+ * copies of a grid. Declared in csm_matchers.hpp. */
 #include "csm_matchers.hpp"
 
 namespace csm_host {
@@ -363,6 +364,27 @@ size_t pass_lds_bytes(const PassPlan& p)
     return (size_t)rows * p.lstride * 4 + kPbMax * 4;
 }
 
+/* Candidates per axis of a window of offsets [-win, win]: padded to a multiple of `unit` (L, or 2^H
+ * for branch and bound) so that every coarser level's nodes cover whole blocks. */
+int padded_extent(int win, int unit)
+{
+    return ceil_div(2 * win + 1, unit) * unit;
+}
+
+WindowFrame window_frame(const DeviceGrid& g, int win_x, int win_y, int unit)
+{
+    WindowFrame f;
+    f.nx = padded_extent(win_x, unit);
+    f.ny = padded_extent(win_y, unit);
+    f.x_lo = -win_x;
+    f.y_lo = -win_y;
+    f.x_hi = f.x_lo + f.nx - 1;
+    f.y_hi = f.y_lo + f.ny - 1;
+    f.tiles_x = ceil_div(g.cols - f.x_lo + f.x_hi, kTile);
+    f.tiles_y = ceil_div(g.rows - f.y_lo + f.y_hi + 1, kTile);    /* + 1: k_bin's frame shift */
+    return f;
+}
+
 int make_plan(csm_ctx* ctx, const DeviceGrid& g, const csm_window* w, Plan* p)
 {
     if (w->n_theta < 1 || w->n_points < 1 || w->win_x < 0 || w->win_y < 0 ||
@@ -373,21 +395,14 @@ int make_plan(csm_ctx* ctx, const DeviceGrid& g, const csm_window* w, Plan* p)
     p->win_x = w->win_x;
     p->win_y = w->win_y;
     p->L = w->low_resolution;
-    p->nxc = ceil_div(2 * w->win_x + 1, p->L);
-    p->nyc = ceil_div(2 * w->win_y + 1, p->L);
-    p->nx = p->nxc * p->L;
-    p->ny = p->nyc * p->L;
-    p->x_lo = -w->win_x;
-    p->y_lo = -w->win_y;
-    p->x_hi = p->x_lo + p->nx - 1;
-    p->y_hi = p->y_lo + p->ny - 1;
+    static_cast<WindowFrame&>(*p) = window_frame(g, w->win_x, w->win_y, p->L);
+    p->nxc = p->nx / p->L;
+    p->nyc = p->ny / p->L;
     if (!plan_pass_pairs(ctx->tune, p->nx, p->ny, &p->fine))
         return fail(ctx, CSM_EINVAL, "internal: no launch geometry for the fine level");
     p->fine.weighted = w->merge_mode == 0;
     if (p->L > 1 && !plan_pass(ctx->tune, p->nxc, p->nyc, p->L, &p->coarse))
         return fail(ctx, CSM_EINVAL, "LowResolution %d too large for the coarse kernel", p->L);
-    p->tiles_x = ceil_div(g.cols - p->x_lo + p->x_hi, kTile);
-    p->tiles_y = ceil_div(g.rows - p->y_lo + p->y_hi + 1, kTile);    /* + 1: k_bin's frame shift */
     p->max_tiles = std::min(p->n, p->tiles_x * p->tiles_y) + p->n / kPbMax + 1;
     if (p->n > kMaxPoints)
         return fail(ctx, CSM_EINVAL, "more than %d beams per scan", kMaxPoints);
@@ -395,6 +410,120 @@ int make_plan(csm_ctx* ctx, const DeviceGrid& g, const csm_window* w, Plan* p)
     if (bin_lds > 160 * 1024 - 64)
         return fail(ctx, CSM_EINVAL, "grid + window too large for the binning kernel (its per-tile words, hash table and cell list exceed the LDS)");
     return CSM_OK;
+}
+
+/* ---- job records ---- */
+
+ProjJob proj_job(const csm_geometry& geom, const double sensor_pose[3], double step_theta, int win_theta,
+                 int n_points, const double* angles, const double* ranges, int32_t* hit_col, int32_t* hit_row)
+{
+    ProjJob j;
+    std::memset(&j, 0, sizeof(j));
+    j.angles = angles;
+    j.ranges = ranges;
+    j.hit_col = hit_col;
+    j.hit_row = hit_row;
+    j.n_theta = 2 * win_theta + 1;
+    j.n_points = n_points;
+    j.win_theta = win_theta;
+    j.sensor_x = sensor_pose[0];
+    j.sensor_y = sensor_pose[1];
+    j.sensor_theta = sensor_pose[2];
+    j.step_theta = step_theta;
+    j.off_x = geom.offset_x;
+    j.off_y = geom.offset_y;
+    j.res = geom.resolution;
+    return j;
+}
+
+/* pair_mode: 0 per-slice lists, 1 aligned row pairs (pair-row fine kernel), 2 joint entries of slice pairs */
+BinJob bin_job(const DeviceGrid& g, const WindowFrame& f, int n_theta, int n_points, int max_tiles,
+               const int32_t* hit_col, const int32_t* hit_row, uint32_t* sorted_pb, TileRec* tiles,
+               int32_t* n_tiles, uint32_t* flags, int pair_mode)
+{
+    BinJob j;
+    std::memset(&j, 0, sizeof(j));
+    j.hit_col = hit_col;
+    j.hit_row = hit_row;
+    j.sorted_pb = sorted_pb;
+    j.tiles = tiles;
+    j.n_tiles = n_tiles;
+    j.flags = flags;
+    j.n_theta = n_theta;
+    j.n_points = n_points;
+    j.max_tiles = max_tiles;
+    j.rows = g.rows;
+    j.cols = g.cols;
+    j.x_lo = f.x_lo;
+    j.y_lo = f.y_lo;
+    j.x_hi = f.x_hi;
+    j.y_hi = f.y_hi;
+    j.tiles_x = f.tiles_x;
+    j.tiles_y = f.tiles_y;
+    j.known_r0 = g.known_r0;
+    j.known_c0 = g.known_c0;
+    j.pair_mode = pair_mode;
+    j.frame_shift = pair_mode ? ((f.ny - 1) & 1) : 0;
+    return j;
+}
+
+/* A scoring pass over the entry lists `entries` binned: one level (`cells`) of g, every stride-th
+ * candidate of the entries' frame; outputs and eligibility set by the caller. */
+ScoreJob score_job(const DeviceGrid& g, const uint16_t* cells, int stride, const BinJob& entries, int min_known)
+{
+    ScoreJob j;
+    std::memset(&j, 0, sizeof(j));
+    j.cells = cells;
+    j.rows = g.rows;
+    j.cols = g.cols;
+    j.pitch = g.pitch;
+    j.sorted_pb = entries.sorted_pb;
+    j.tiles = entries.tiles;
+    j.n_tiles = entries.n_tiles;
+    j.n_theta = entries.n_theta;
+    j.n_points = entries.n_points;
+    j.max_tiles = entries.max_tiles;
+    j.x_lo = entries.x_lo;
+    j.y_lo = entries.y_lo;
+    j.nx = (entries.x_hi - entries.x_lo + 1) / stride;
+    j.ny = (entries.y_hi - entries.y_lo + 1) / stride;
+    j.stride = stride;
+    j.log2_stride = ilog2_exact(stride);
+    j.flags = entries.flags;
+    j.min_known = min_known;
+    return j;
+}
+
+/* The record of the window the fine job scores: its n_blocks block results reduced, the winner
+ * replayed in f64; nothing found reports the window's first candidate. */
+FinalJob final_job(const ScoreJob& fine, int n_blocks, const int32_t* hit_col, const int32_t* hit_row,
+                   double score_thr, const double* lut, void* out)
+{
+    FinalJob j;
+    std::memset(&j, 0, sizeof(j));
+    j.block_best = fine.block_best;
+    j.n_entries = n_blocks;
+    j.nx = fine.nx;
+    j.ny = fine.ny;
+    j.rank_l = fine.rank_l;
+    j.x_lo = fine.x_lo;
+    j.y_lo = fine.y_lo;
+    j.win_theta = (fine.n_theta - 1) / 2;
+    j.init_x = fine.x_lo;
+    j.init_y = fine.y_lo;
+    j.init_theta = -j.win_theta;
+    j.cells = fine.cells;
+    j.rows = fine.rows;
+    j.cols = fine.cols;
+    j.pitch = fine.pitch;
+    j.hit_col = hit_col;
+    j.hit_row = hit_row;
+    j.n_points = fine.n_points;
+    j.score_thr = score_thr;
+    j.lut = lut;
+    j.flags_in = fine.flags;
+    j.out = out;
+    return j;
 }
 
 /* What the wrappers of csm_launch.hip return: a HIP error code, or -1 for "no kernel instantiated". */
@@ -424,6 +553,22 @@ csm_launch::ScoreLaunch score_launch(const csm_ctx* ctx, const PassPlan& pp, dim
     a.lds = lds;
     a.ncb = pp.ncb();
     return a;
+}
+
+/* the fields of a csm::JointLaunch a pass plan decides */
+csm::JointLaunch joint_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, const uint16_t* lane_map)
+{
+    csm::JointLaunch L{};
+    L.stream = ctx->stream;
+    L.device = ctx->device;
+    L.grid = grid;
+    L.lds_bytes = pass_lds_bytes(pp);
+    L.ls = pp.lstride;
+    L.R = pp.R;
+    L.cbx = pp.cbx;
+    L.groups = pp.groups;
+    L.lane_map = lane_map;
+    return L;
 }
 
 /* Which candidate (lane group g, column dxi) a thread of a pair kernel owns. A ds_read_b64
@@ -584,24 +729,14 @@ bool tail_split(const csm_ctx* ctx, const PassPlan& pp)
 int launch_pairs_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, const PassPlan& pp, dim3 grid, BlockBase bb,
                        const JointList* list, int which)
 {
-    const size_t lds = pass_lds_bytes(pp);
     const uint16_t* lane_map = nullptr;
     if (int rc = lane_map_for(ctx, pp, &lane_map))
         return rc;
     /* one job's workgroups on one XCD (k_score_pairs*_batch, xcd_block); CSM_TUNE_NO_XCD_MAP: identity */
     const int xcd_map = ctx->tune.xcd_map ? 1 : 0;
     if (pp.joint) {
-        csm::JointLaunch L;
-        L.stream = ctx->stream;
-        L.device = ctx->device;
+        csm::JointLaunch L = joint_launch(ctx, pp, dim3(grid.x, (grid.y + 1) / 2, grid.z), lane_map);
         L.jobs_dev = jobs_dev;
-        L.grid = dim3(grid.x, (grid.y + 1) / 2, grid.z);
-        L.lds_bytes = lds;
-        L.ls = pp.lstride;
-        L.R = pp.R;
-        L.cbx = pp.cbx;
-        L.groups = pp.groups;
-        L.lane_map = lane_map;
         L.xcd_map = xcd_map;
         L.row_base = bb.row_base;
         L.cb_base = bb.cb_base;
@@ -619,7 +754,7 @@ int launch_pairs_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, const PassPlan& p
             return fail(ctx, CSM_EIO, "joint fine kernel launch failed: %s", hipGetErrorString((hipError_t)e));
         return CSM_OK;
     }
-    csm_launch::ScoreLaunch a = score_launch(ctx, pp, grid, lds);
+    csm_launch::ScoreLaunch a = score_launch(ctx, pp, grid, pass_lds_bytes(pp));
     a.lane_map = lane_map;
     a.xcd_map = xcd_map;
     a.bb = bb;

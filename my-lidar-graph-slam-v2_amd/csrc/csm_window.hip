@@ -33,59 +33,21 @@ int run_level_pass_joint(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const
     if ((rc = ensure(ctx, ctx->sorted, (size_t)n_pairs * 2 * p.n * 4 + 256))) return rc;
     if ((rc = ensure(ctx, ctx->tiles, (size_t)n_pairs * max_tiles * sizeof(TileRec)))) return rc;
     if ((rc = ensure(ctx, ctx->ntiles, (size_t)n_pairs * 8))) return rc;
-    BinJob bj;
-    std::memset(&bj, 0, sizeof(bj));
-    bj.hit_col = hit_col_dev;
-    bj.hit_row = hit_row_dev;
-    bj.sorted_pb = reinterpret_cast<uint32_t*>(ctx->sorted.p);
-    bj.tiles = reinterpret_cast<TileRec*>(ctx->tiles.p);
-    bj.n_tiles = reinterpret_cast<int32_t*>(ctx->ntiles.p);
-    bj.flags = flags;
-    bj.n_theta = p.n_theta;
-    bj.n_points = p.n;
-    bj.max_tiles = max_tiles;
-    bj.rows = g.rows;
-    bj.cols = g.cols;
-    bj.x_lo = p.x_lo;
-    bj.y_lo = p.y_lo;
-    bj.x_hi = p.x_hi;
-    bj.y_hi = p.y_hi;
-    bj.tiles_x = p.tiles_x;
-    bj.tiles_y = p.tiles_y;
-    bj.known_r0 = g.known_r0;
-    bj.known_c0 = g.known_c0;
+    BinJob bj = bin_job(g, p, p.n_theta, p.n, max_tiles, hit_col_dev, hit_row_dev,
+                        reinterpret_cast<uint32_t*>(ctx->sorted.p), reinterpret_cast<TileRec*>(ctx->tiles.p),
+                        reinterpret_cast<int32_t*>(ctx->ntiles.p), flags, 2);
     bj.hash_size = hash_size;
     bj.max_mult = kMaxMult;
     bj.lstride = jp.lstride;
-    bj.pair_mode = 2;
-    bj.frame_shift = (p.ny - 1) & 1;
     {
         ScopedTimer tm(ctx, "bin");
         if ((rc = launched_ok(ctx, csm::launch_binj_one(ctx->stream, ctx->device, bj, n_pairs, binj_lds), "joint binning")))
             return rc;
     }
-    ScoreJob fj;
-    std::memset(&fj, 0, sizeof(fj));
-    fj.rows = g.rows;
-    fj.cols = g.cols;
-    fj.pitch = g.pitch;
-    fj.sorted_pb = bj.sorted_pb;
-    fj.tiles = bj.tiles;
-    fj.n_tiles = bj.n_tiles;
-    fj.n_theta = p.n_theta;
-    fj.n_points = p.n;
-    fj.max_tiles = max_tiles;
-    fj.x_lo = p.x_lo;
-    fj.y_lo = p.y_lo;
-    fj.flags = flags;
-    fj.min_known = w->min_known;
-    fj.cells = g.levels[0].cells;
+    ScoreJob fj = score_job(g, g.levels[0].cells, 1, bj, w->min_known);
     fj.xg = g.xg.as<uint32_t>();
     fj.xg_pitch = g.xg_pitch;
     fj.xg_pad = g.xg_pad;
-    fj.nx = p.nx;
-    fj.ny = p.ny;
-    fj.stride = 1;
     fj.rank_l = p.L;
     fj.joint = 1;
     /* every candidate's sums, stored; no arg-max, no record */
@@ -99,16 +61,7 @@ int run_level_pass_joint(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const
     const uint16_t* lane_map = nullptr;
     if ((rc = lane_map_for(ctx, jp, &lane_map)))
         return rc;
-    csm::JointLaunch L{};
-    L.stream = ctx->stream;
-    L.device = ctx->device;
-    L.grid = dim3(jp.ncb(), 1, 1);
-    L.lds_bytes = pass_lds_bytes(jp);
-    L.ls = jp.lstride;
-    L.R = jp.R;
-    L.cbx = jp.cbx;
-    L.groups = jp.groups;
-    L.lane_map = lane_map;
+    csm::JointLaunch L = joint_launch(ctx, jp, dim3(jp.ncb(), 1, 1), lane_map);
     L.ncb = jp.ncb();
     ScopedTimer tm(ctx, "score_coarse");
     return launched_ok(ctx, csm::launch_joint_one(L, fj, n_pairs), "joint level pass");
@@ -189,32 +142,12 @@ int run_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
             return rcj;
     }
 
-    BinJob bj;
-    std::memset(&bj, 0, sizeof(bj));
-    bj.hit_col = hit_col_dev;
-    bj.hit_row = hit_row_dev;
-    bj.sorted_pb = reinterpret_cast<uint32_t*>(ctx->sorted.p);
-    bj.tiles = reinterpret_cast<TileRec*>(ctx->tiles.p);
-    bj.n_tiles = reinterpret_cast<int32_t*>(ctx->ntiles.p);
-    bj.flags = flags;
-    bj.n_theta = p.n_theta;
-    bj.n_points = p.n;
-    bj.max_tiles = p.max_tiles;
-    bj.rows = g.rows;
-    bj.cols = g.cols;
-    bj.x_lo = p.x_lo;
-    bj.y_lo = p.y_lo;
-    bj.x_hi = p.x_hi;
-    bj.y_hi = p.y_hi;
-    bj.tiles_x = p.tiles_x;
-    bj.tiles_y = p.tiles_y;
-    bj.known_r0 = g.known_r0;
-    bj.known_c0 = g.known_c0;
+    BinJob bj = bin_job(g, p, p.n_theta, p.n, p.max_tiles, hit_col_dev, hit_row_dev,
+                        reinterpret_cast<uint32_t*>(ctx->sorted.p), reinterpret_cast<TileRec*>(ctx->tiles.p),
+                        reinterpret_cast<int32_t*>(ctx->ntiles.p), flags, p.fine.pairs ? 1 : 0);
     bj.hash_size = bin_hash_size(p.n);
     bj.max_mult = p.fine.weighted ? kMaxMult : 1;
     bj.lstride = p.fine.lstride;
-    bj.pair_mode = p.fine.pairs ? 1 : 0;
-    bj.frame_shift = p.fine.pairs ? ((p.ny - 1) & 1) : 0;
     bj.sorted_rc = p.L > 1 ? reinterpret_cast<uint32_t*>(ctx->sorted_rc.p) : nullptr;
     const bool coarse_exits = w->min_known <= 1 && !force_coarse && tp_mode != 2;   /* unless a beam reaches the band */
     if (p.L > 1) {
@@ -231,40 +164,14 @@ int run_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
     if (p.L > 1 && tp_mode != 2) {
         /* the coarse pass accumulates with atomics: its sums are cleared first, but
          * only when it is going to run (k_zero_if_band reads the band flag k_bin set) */
-        ZeroJob zj;
-        zj.a = reinterpret_cast<uint32_t*>(ctx->coarse_s.p);
-        zj.b = reinterpret_cast<uint32_t*>(ctx->coarse_k.p);
-        zj.words = nt * p.nxc * p.nyc;
-        zj.flags = flags;
-        zj.always = coarse_exits ? 0 : 1;
-        zj.pad = 0;
+        const ZeroJob zj = { ctx->coarse_s.as<uint32_t>(), ctx->coarse_k.as<uint32_t>(), nt * p.nxc * p.nyc, flags,
+                             coarse_exits ? 0 : 1, 0 };
         const int zb = (int)std::min<size_t>(256, (zj.words + 255) / 256);
         if ((rc = launched_ok(ctx, csm_launch::zero_if_band(ctx->stream, std::max(1, zb), zj), "edge-band clear"))) return rc;
     }
 
-    ScoreJob base;
-    std::memset(&base, 0, sizeof(base));
-    base.rows = g.rows;
-    base.cols = g.cols;
-    base.pitch = g.pitch;
-    base.sorted_pb = bj.sorted_pb;
-    base.tiles = bj.tiles;
-    base.n_tiles = bj.n_tiles;
-    base.n_theta = p.n_theta;
-    base.n_points = p.n;
-    base.max_tiles = p.max_tiles;
-    base.x_lo = p.x_lo;
-    base.y_lo = p.y_lo;
-    base.flags = flags;
-    base.min_known = w->min_known;
-
     if (p.L > 1 && tp_mode != 2) {
-        ScoreJob cj = base;
-        cj.cells = g.levels[w->coarse_level].cells;
-        cj.nx = p.nxc;
-        cj.ny = p.nyc;
-        cj.stride = p.L;
-        cj.log2_stride = p.coarse.log2s;
+        ScoreJob cj = score_job(g, g.levels[w->coarse_level].cells, p.L, bj, w->min_known);
         cj.sorted_pb = bj.sorted_rc;
         cj.acc_s = reinterpret_cast<uint32_t*>(ctx->coarse_s.p);
         cj.acc_k = reinterpret_cast<uint32_t*>(ctx->coarse_k.p);
@@ -282,14 +189,10 @@ int run_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
     }
 
     const BlockBest* tp_reduced = nullptr;
-    ScoreJob fj = base;
-    fj.cells = g.levels[0].cells;
+    ScoreJob fj = score_job(g, g.levels[0].cells, 1, bj, w->min_known);
     fj.xg = g.xg.as<uint32_t>();
     fj.xg_pitch = g.xg_pitch;
     fj.xg_pad = g.xg_pad;
-    fj.nx = p.nx;
-    fj.ny = p.ny;
-    fj.stride = 1;
     fj.block_best = reinterpret_cast<BlockBest*>(ctx->best.p);
     (void)fine_slices;
     fj.rank_l = p.L;
@@ -428,35 +331,13 @@ int run_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
     }
     ctx->last_fine = fj;
 
-    FinalJob fin;
-    std::memset(&fin, 0, sizeof(fin));
-    fin.block_best = fj.block_best;
-    fin.n_entries = p.n_theta * ncb;
+    FinalJob fin = final_job(fj, p.n_theta * ncb, hit_col_dev, hit_row_dev, w->score_threshold,
+                             ctx->lut_dev.as<double>(), out_dev);
     if (tp_reduced) {
         fin.block_best = tp_reduced;
         fin.n_entries = csm::kReducedBest;
     }
-    fin.nx = p.nx;
-    fin.ny = p.ny;
-    fin.rank_l = p.L;
-    fin.x_lo = p.x_lo;
-    fin.y_lo = p.y_lo;
-    fin.win_theta = (p.n_theta - 1) / 2;
-    fin.init_x = -p.win_x;
-    fin.init_y = -p.win_y;
-    fin.init_theta = -fin.win_theta;
-    fin.cells = g.levels[0].cells;
-    fin.rows = g.rows;
-    fin.cols = g.cols;
-    fin.pitch = g.pitch;
-    fin.hit_col = hit_col_dev;
-    fin.hit_row = hit_row_dev;
-    fin.n_points = p.n;
-    fin.score_thr = w->score_threshold;
-    fin.lut = ctx->lut_dev.as<double>();
-    fin.flags_in = flags;
     fin.flags_clear = flags_next;
-    fin.out = out_dev;
     {
         const size_t lds = (size_t)p.n * 8;
         ScopedTimer tm(ctx, "finalize");
@@ -885,25 +766,11 @@ int csm_correlative_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
     double* ang_dev = reinterpret_cast<double*>(qd + job_bytes);
     double* rng_dev = ang_dev + n;
     Tail* tail_pin = reinterpret_cast<Tail*>(pin + ((up_bytes + 63) & ~(size_t)63));
-    ProjJob pj;
-    std::memset(&pj, 0, sizeof(pj));
-    pj.angles = ang_dev;
-    pj.ranges = rng_dev;
-    pj.hit_col = col_dev;
-    pj.hit_row = row_dev;
+    ProjJob pj = proj_job(*geom, out->sensor_pose, out->step_theta, out->win_theta, n, ang_dev, rng_dev, col_dev,
+                          row_dev);
     pj.unc_count = unc_count;
     pj.unc_list = unc_list;
     pj.unc_cap = kUncCap;
-    pj.n_theta = w.n_theta;
-    pj.n_points = n;
-    pj.win_theta = out->win_theta;
-    pj.sensor_x = out->sensor_pose[0];
-    pj.sensor_y = out->sensor_pose[1];
-    pj.sensor_theta = out->sensor_pose[2];
-    pj.step_theta = out->step_theta;
-    pj.off_x = geom->offset_x;
-    pj.off_y = geom->offset_y;
-    pj.res = geom->resolution;
     std::memcpy(pin, &pj, sizeof(pj));
     std::memcpy(pin + job_bytes, scan->angles, (size_t)n * 8);
     std::memcpy(pin + job_bytes + (size_t)n * 8, scan->ranges, (size_t)n * 8);
@@ -1035,9 +902,7 @@ int csm_correlative_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
     out->best_sensor_pose[1] = out->sensor_pose[1] + out->raw.best_y * out->step_y;
     out->best_sensor_pose[2] = out->sensor_pose[2] + out->raw.best_theta * out->step_theta;
     csm_host_move_backward(out->best_sensor_pose, scan->relative_sensor_pose, out->estimated_pose);
-    const int nx = ceil_div(2 * w.win_x + 1, w.low_resolution) * w.low_resolution;
-    const int ny = ceil_div(2 * w.win_y + 1, w.low_resolution) * w.low_resolution;
-    out->candidates = (int64_t)w.n_theta * nx * ny;
+    out->candidates = (int64_t)w.n_theta * p.nx * p.ny;
     out->input_setup_us = std::chrono::duration<double, std::micro>(t1 - t0).count();
     out->optimization_us = std::chrono::duration<double, std::micro>(t2 - t1).count();
     return CSM_OK;
@@ -1194,25 +1059,10 @@ int csm_project_scan(csm_ctx* ctx, const csm_geometry* geom, const double sensor
     HIP_TRY(ctx, hipMemcpyAsync(ang_dev, angles, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(rng_dev, ranges, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(unc_count, 0, 16, ctx->stream));
-    ProjJob pj;
-    std::memset(&pj, 0, sizeof(pj));
-    pj.angles = ang_dev;
-    pj.ranges = rng_dev;
-    pj.hit_col = col_dev;
-    pj.hit_row = row_dev;
+    ProjJob pj = proj_job(*geom, sensor_pose, step_theta, win_theta, n, ang_dev, rng_dev, col_dev, row_dev);
     pj.unc_count = unc_count;
     pj.unc_list = unc_list;
     pj.unc_cap = (uint32_t)uncertified_cap;
-    pj.n_theta = n_theta;
-    pj.n_points = n;
-    pj.win_theta = win_theta;
-    pj.sensor_x = sensor_pose[0];
-    pj.sensor_y = sensor_pose[1];
-    pj.sensor_theta = sensor_pose[2];
-    pj.step_theta = step_theta;
-    pj.off_x = geom->offset_x;
-    pj.off_y = geom->offset_y;
-    pj.res = geom->resolution;
     if (int e = csm_launch::project(ctx->stream, dim3(ceil_div(n, kBlock), proj_theta_groups(n_theta, ceil_div(n, kBlock))), pj))
         return launched_ok(ctx, e, "projection");
     uint32_t count = 0;
