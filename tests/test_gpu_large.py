@@ -149,6 +149,7 @@ def test_config4_batch_of_2048_submaps_world_size_1(oracle):
     assert len(records) == n and len(found) > 0
     _check_loop_records(records, found, cases, oracle, 64)
     dev = torch.zeros(n * parallel.RECORD_BYTES, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()            # the fill runs on torch's stream, the copy on the context's
     ctx.copy_last_batch_records(dev.data_ptr())
     ctx.synchronize()
     assert parallel.bytes_to_records(dev.cpu().numpy()) == records
