@@ -7,11 +7,11 @@ N = 1 (default): BASELINE.json configs[1] -- frontend CSM, 1080-beam scan over
 each). One step = SCANS_PER_STEP (3072) scans, hit indices and grid already
 resident in HBM, scored 256 windows per batched launch chain
 (csm_score_windows_dev), so that the K timed steps last seconds, not
-milliseconds. The same line carries, under "configs", short driver-timed runs
-of configs[2] (256 submaps, pyramid build reported separately), configs[3] at
-N = 1 (2048 submaps on one GPU: the strong-scaling base), configs[4]
-(exhaustive 2000x2000) and the host-inclusive single-query latency of
-configs[1].
+milliseconds. With --full the same line carries, under "config.side_runs",
+short driver-timed runs of configs[2] (256 submaps, pyramid build reported
+separately), configs[3] at N = 1 (2048 submaps on one GPU: the strong-scaling
+base), configs[4] (exhaustive 2000x2000) and the host-inclusive single-query
+latency of configs[1].
 
 N > 1 (default): BASELINE.json configs[3] -- branch-and-bound loop detection,
 2048 candidate submaps sharded in contiguous blocks of 2048 / N queries per
@@ -20,10 +20,13 @@ best records over RCCL per step (":53-56"). Total work is fixed: strong
 scaling. `--workload csm` keeps configs[1] per GPU instead (independent
 replicas, weak scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-"roofline" (dominant kernel = fine / leaf scoring kernel, HIP events inside the
-library on its launch stream) and, at N = 1, "cpu_baseline" (CPU oracle on one
-core and on all cores, bounded samples).
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times its
+steps, writes --dump-outputs and prints the line, nothing more. --full adds what
+the headline does not need: "roofline" (dominant kernel = fine / leaf scoring
+kernel, HIP events inside the library on its launch stream) and per-kernel
+times, records checked against the CPU oracle, the exact-only rate, the side
+runs and, at N = 1, "cpu_baseline" (CPU oracle on one core and on all cores,
+bounded samples).
 
 Roofline: the fine kernel gathers from LDS, not from HBM (a 400x400 grid is
 320 KB; measured HBM traffic is < 0.1 % of the algorithmic bytes), so the bound
@@ -369,8 +372,7 @@ def run_loop_workload(args, rank, world, dev, dev_index, rehearse, stream, n_tot
         leaves = leaves_local
         found = sum(o["pose_found"] for o in outs)
     if rank == 0:
-        rl = loop_roofline(leaves_local, fine_ms, fine_n, loop_gathers(queries, LOOP_PARAMS), len(queries))
-        print(json.dumps({
+        line = {
             "metric": METRIC, "value": leaves * args.steps / dt, "unit": "candidate poses/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -395,8 +397,11 @@ def run_loop_workload(args, rank, world, dev, dev_index, rehearse, stream, n_tot
                                     "all_gather_ms_max_rank0": max(gather_ms) if gather_ms else None,
                                     "note": "HIP events on the scoring stream around the collective, rank 0"}
                        if world > 1 else None},
-            "roofline": rl,
-        }), flush=True)
+        }
+        if args.full:
+            line["roofline"] = loop_roofline(leaves_local, fine_ms, fine_n, loop_gathers(queries, LOOP_PARAMS),
+                                             len(queries))
+        print(json.dumps(line), flush=True)
     ctx.close()
 
 
@@ -455,12 +460,13 @@ def measure_loop_config(dev_index, n_sub, steps=5):
             "roofline": rl}
 
 
-def measure_config5(dev_index, runs=2, warmup=1):
+def measure_config5(dev_index, runs=2, warmup=1, kernels=True):
     """configs[4]: global CSM, 2000x2000 @ 2.5 cm, +-10 m / +-180 deg at 2.5 cm / 0.25 deg, 1080
     beams, L = 4: 9.3e8 candidate poses in the window. Searched coarse-first: every
     coarse node scored, the fine level only on the candidate blocks that can still win; value =
     NOMINAL window poses / s (what the reference's pruned sweep is quoted in), with the poses
-    actually evaluated beside it."""
+    actually evaluated beside it. kernels: per-kernel times and the roofline from a short
+    extra pass."""
     import torch
     from csm_hip import api, synth
     case = synth.csm_case(7, rows=2000, cols=2000, res=0.025, n_beams=N_BEAMS, fov=1.5 * math.pi,
@@ -480,6 +486,20 @@ def measure_config5(dev_index, runs=2, warmup=1):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / runs
     info = ctx.last_search_info()
+    d = {"workload": "configs[4]: global CSM, 2000x2000@2.5cm, +-10 m/+-180 deg at 2.5 cm/0.25 deg, "
+                     "1080 beams, L=4; host-inclusive csm_correlative_match (projection on device), "
+                     "searched coarse-first" + ("" if info["two_phase"] == 1 else " -- NOT taken: exhaustive"),
+         "value": out["candidates"] / dt, "unit": "candidate poses/s (nominal window)", "ms_per_query": dt * 1e3,
+         "runs": runs, "candidates": out["candidates"], "found": out["pose_found"], "upload_ms": t_up * 1e3,
+         "evaluated": {"coarse_nodes": info["coarse_nodes_scored"], "fine_candidates": info["fine_candidates_scored"],
+                       "fine_blocks_scored": info["blocks_scored"], "fine_blocks_skipped": info["blocks_skipped"],
+                       "evaluated_poses_per_s": (info["coarse_nodes_scored"] + info["fine_candidates_scored"]) / dt,
+                       "note": "fully evaluated N-beam scores: every coarse node + every candidate of the fine "
+                               "blocks scored; the rest of the nominal window is excluded by the box-max bound "
+                               "exactly as scan_matcher_correlative.cpp:181-182 excludes it"}}
+    if not kernels:
+        ctx.close()
+        return d
     # per-kernel times from a short extra pass (HIP events around every launch cost host time)
     ctx.lib.csm_enable_kernel_timing(ctx._ctx, 1)
     ctx.reset_kernel_timing()
@@ -491,7 +511,6 @@ def measure_config5(dev_index, runs=2, warmup=1):
         ms, n = ctx.kernel_time(name)
         if n:
             kern[name] = ms / 3.0 * 1e3          # us per query (a name may cover two launches)
-    cands = out["candidates"]
     wt = out["win_theta"]
     col, row = api.host_project(case["geom"], out["sensor_pose"], out["step_theta"], wt, case["angles"],
                                 case["ranges"])
@@ -511,30 +530,21 @@ def measure_config5(dev_index, runs=2, warmup=1):
         lds = 4.0 * per_slice * info["fine_candidates_scored"]
     ctx.close()
     ach = lds / (dom_us * 1e-6) / 1e9 if dom_us > 0 else None
-    return {"workload": "configs[4]: global CSM, 2000x2000@2.5cm, +-10 m/+-180 deg at 2.5 cm/0.25 deg, "
-                        "1080 beams, L=4; host-inclusive csm_correlative_match (projection on device), "
-                        "searched coarse-first" + ("" if two_phase else " -- NOT taken: exhaustive"),
-            "value": cands / dt, "unit": "candidate poses/s (nominal window)", "ms_per_query": dt * 1e3, "runs": runs,
-            "candidates": cands, "found": out["pose_found"], "upload_ms": t_up * 1e3,
-            "evaluated": {"coarse_nodes": info["coarse_nodes_scored"], "fine_candidates": info["fine_candidates_scored"],
-                          "fine_blocks_scored": info["blocks_scored"], "fine_blocks_skipped": info["blocks_skipped"],
-                          "evaluated_poses_per_s": (info["coarse_nodes_scored"] + info["fine_candidates_scored"]) / dt,
-                          "note": "fully evaluated N-beam scores: every coarse node + every candidate of the fine "
-                                  "blocks scored; the rest of the nominal window is excluded by the box-max bound "
-                                  "exactly as scan_matcher_correlative.cpp:181-182 excludes it"},
-            "kernel_us_per_query": kern,
-            "roofline": {"bound": "lds", "kernel": dom, "unit": "GB/s", "peak": LDS_PEAK_GBS,
-                         "achieved": ach, "frac": ach / LDS_PEAK_GBS if ach else None,
-                         "avg_launch_us": dom_us,
-                         "traffic": pmc_traffic(os.path.join(ROOT, "profiles", "r03_config5_pmc_traffic.json"))[0],
-                         "traffic_source": pmc_traffic(os.path.join(ROOT, "profiles", "r03_config5_pmc_traffic.json"))[1],
-                         "note": "LDS gather bytes (4 B x cell entries x candidates the kernel scores) / its time; "
-                                 "HBM-side traffic of this workload: profiles/ (PMC passes)"}}
+    d["kernel_us_per_query"] = kern
+    d["roofline"] = {"bound": "lds", "kernel": dom, "unit": "GB/s", "peak": LDS_PEAK_GBS,
+                     "achieved": ach, "frac": ach / LDS_PEAK_GBS if ach else None,
+                     "avg_launch_us": dom_us,
+                     "traffic": pmc_traffic(os.path.join(ROOT, "profiles", "r03_config5_pmc_traffic.json"))[0],
+                     "traffic_source": pmc_traffic(os.path.join(ROOT, "profiles", "r03_config5_pmc_traffic.json"))[1],
+                     "note": "LDS gather bytes (4 B x cell entries x candidates the kernel scores) / its time; "
+                             "HBM-side traffic of this workload: profiles/ (PMC passes)"}
+    return d
 
 
-def measure_config2_latency(dev_index, wl, reps=30, warmup=3):
+def measure_config2_latency(dev_index, wl, reps=30, warmup=3, kernels=True):
     """What one frontend caller sees: csm_correlative_match per scan, scan in host
-    memory, projection on the device, summary back on the host."""
+    memory, projection on the device, summary back on the host. kernels: per-kernel
+    times from a short extra pass."""
     from csm_hip import api
     rx, ry, rt, L = wl["params"]
     ctx = api.Context(dev_index)
@@ -555,19 +565,21 @@ def measure_config2_latency(dev_index, wl, reps=30, warmup=3):
     t_all = time.perf_counter() - t_all
     # per-kernel times from a short extra pass: HIP events around every launch cost host time and
     # switch the graph replay off, so they are not collected inside the timed loop
-    ctx.lib.csm_enable_kernel_timing(ctx._ctx, 1)
-    ctx.reset_kernel_timing()
-    n_k = min(200, reps)
-    for i in range(n_k):
-        sc = wl["scans"][i % len(wl["scans"])]
-        ctx.correlative_match(1, wl["geom"], sc["angles"], sc["ranges"], sc["rel_pose"], sc["init_pose"],
-                              rx, ry, rt, L, 0.0, 0.0)
-    ctx.enable_kernel_timing(False)
-    kernels = {}
-    for name in ("project", "bin", "score_coarse", "score_fine", "argmax", "finalize"):
-        ms, n = ctx.kernel_time(name)
-        if n:
-            kernels[name] = ms / n_k * 1e3
+    kern = None
+    if kernels:
+        ctx.lib.csm_enable_kernel_timing(ctx._ctx, 1)
+        ctx.reset_kernel_timing()
+        n_k = min(200, reps)
+        for i in range(n_k):
+            sc = wl["scans"][i % len(wl["scans"])]
+            ctx.correlative_match(1, wl["geom"], sc["angles"], sc["ranges"], sc["rel_pose"], sc["init_pose"],
+                                  rx, ry, rt, L, 0.0, 0.0)
+        ctx.enable_kernel_timing(False)
+        kern = {}
+        for name in ("project", "bin", "score_coarse", "score_fine", "argmax", "finalize"):
+            ms, n = ctx.kernel_time(name)
+            if n:
+                kern[name] = ms / n_k * 1e3
     ctx.close()
     samples = sorted(samples[warmup:])
     med = samples[len(samples) // 2]
@@ -576,7 +588,7 @@ def measure_config2_latency(dev_index, wl, reps=30, warmup=3):
             "latency_ms_median": med * 1e3, "latency_ms_min": samples[0] * 1e3,
             "latency_ms_p90": samples[int(0.9 * (len(samples) - 1))] * 1e3,
             "value": out["candidates"] / med, "unit": "candidate poses/s", "reps": reps,
-            "total_s": t_all, "candidates_total": cands, "kernel_us_per_query": kernels,
+            "total_s": t_all, "candidates_total": cands, "kernel_us_per_query": kern,
             "note": "the timed loop replays each launch shape's chain as a HIP graph (from the third query of a "
                     "shape on); kernel_us_per_query comes from a separate pass with HIP events around every launch"}
 
@@ -636,17 +648,17 @@ def run_map_workload(args, rank, world, dev, dev_index, rehearse):
     dt = time.perf_counter() - t0
     gc.enable()
     split_timed = [split[0] / args.steps * 1e3, split[1] / args.steps * 1e3]
-    # kernel breakdown from a few extra steps with the event timers on (they
-    # allocate events per launch, so they stay out of the timed region)
+    # --full: kernel breakdown from a few extra steps with the event timers on
+    # (they allocate events per launch, so they stay out of the timed region)
     k_steps = 10
-    ctx.enable_kernel_timing(True)
-    step()
-    ctx.reset_kernel_timing()
-    for _ in range(k_steps):
+    if args.full:
+        ctx.enable_kernel_timing(True)
         step()
-    fence()
-    ctx.enable_kernel_timing(False)
-    build_ms, build_n = ctx.kernel_time("map_build")
+        ctx.reset_kernel_timing()
+        for _ in range(k_steps):
+            step()
+        fence()
+        ctx.enable_kernel_timing(False)
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=None if rehearse else dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -662,18 +674,20 @@ def run_map_workload(args, rank, world, dev, dev_index, rehearse):
                                    "%d rays, %d cell updates) + ScanMatcherCorrelative on the resident map; "
                                    "host-inclusive calls" % (shape["rows"], shape["cols"], info["rays"],
                                                              info["cell_updates"]),
-                       "map_kernels_us_per_step": build_ms / max(1, build_n) * 1e3,
                        "build_ms_per_step": split_timed[0],
                        "match_ms_per_step": split_timed[1],
-                       "match_kernels_us": {k: ctx.kernel_time(k)[0] / k_steps * 1e3 for k in
-                                            ("boxmax", "project", "bin", "score_coarse", "score_fine",
-                                             "finalize")},
                        "match_found": out["pose_found"], "match_flags": out["raw"]["flags"],
                        "match_tie_count": out["raw"]["tie_count"],
                        "match_setup_us": out["input_setup_us"], "match_optimization_us": out["optimization_us"],
                        "parallelism": "independent replicas" if world > 1 else "single GPU"},
         }
-        if not args.no_cpu_baseline:
+        if args.full:
+            build_ms, build_n = ctx.kernel_time("map_build")
+            line["config"]["map_kernels_us_per_step"] = build_ms / max(1, build_n) * 1e3
+            line["config"]["match_kernels_us"] = {k: ctx.kernel_time(k)[0] / k_steps * 1e3 for k in
+                                                  ("boxmax", "project", "bin", "score_coarse", "score_fine",
+                                                   "finalize")}
+        if args.full and not args.no_cpu_baseline:
             from oracle import oracle
             t0 = time.perf_counter()
             reps = 0
@@ -754,139 +768,8 @@ def run_csm_workload(args, rank, world, dev, dev_index, rehearse, stream):
         for _ in range(args.warmup):
             step()
         fence()
-        # events around the dominant kernel only inside the timed region; the
-        # other kernels are timed in a short extra pass afterwards
-        ctx.lib.csm_enable_kernel_timing(ctx._ctx, 2)
-        ctx.reset_kernel_timing()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        dt = time.perf_counter() - t0
-        ctx.enable_kernel_timing(False)
-        fine_ms, fine_n = ctx.kernel_time("score_fine")
-        bound_ms, bound_n = ctx.kernel_time("score_bound")      # the packed-fp32 bound pass of the fine level
-        fine_ms += bound_ms
-        blocks_scored, blocks_skipped = ctx.bound_pass_stats()
-        ctx.lib.csm_enable_kernel_timing(ctx._ctx, 1)
-        ctx.reset_kernel_timing()
-        step()
-        fence()
-        ctx.enable_kernel_timing(False)
-    others = {}
-    for name in ("score_coarse", "bin", "finalize"):
-        ms, n = ctx.kernel_time(name)
-        others[name] = ms / max(1, n) * 1e3
-
-    if world > 1:
-        tmax = torch.tensor([dt], dtype=torch.float64, device=None if rehearse else dev)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        dt = float(tmax.item())
-    if rank == 0:
-        line = {
-            "metric": "map cell updates/sec (latest-map build + match per step)",
-            "value": info["cell_updates"] * args.steps * world / dt, "unit": "cell updates/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u16", "data": "synthetic",
-            "config": {"workload": "frontend cycle: ConstructMapFromScans of 10 x 1080 beams (%d x %d cells, "
-                                   "%d rays, %d cell updates) + ScanMatcherCorrelative on the resident map; "
-                                   "host-inclusive calls" % (shape["rows"], shape["cols"], info["rays"],
-                                                             info["cell_updates"]),
-                       "map_kernels_us_per_step": build_ms / max(1, build_n) * 1e3,
-                       "build_ms_per_step": split_timed[0],
-                       "match_ms_per_step": split_timed[1],
-                       "match_kernels_us": {k: ctx.kernel_time(k)[0] / k_steps * 1e3 for k in
-                                            ("boxmax", "project", "bin", "score_coarse", "score_fine",
-                                             "finalize")},
-                       "match_found": out["pose_found"], "match_flags": out["raw"]["flags"],
-                       "match_tie_count": out["raw"]["tie_count"],
-                       "match_setup_us": out["input_setup_us"], "match_optimization_us": out["optimization_us"],
-                       "parallelism": "independent replicas" if world > 1 else "single GPU"},
-        }
-        if not args.no_cpu_baseline:
-            from oracle import oracle
-            t0 = time.perf_counter()
-            reps = 0
-            while time.perf_counter() - t0 < 5.0:
-                oracle.construct_map(mc["shape"], mc["map_pose"], mc["nodes"])
-                reps += 1
-            cdt = (time.perf_counter() - t0) / reps
-            line["cpu_baseline"] = dict(value=info["cell_updates"] / cdt, unit="cell updates/s", cores=1,
-                                        kind="port", sample="%d builds of the same 10 scans, map build only, "
-                                        "%.2f ms each" % (reps, cdt * 1e3))
-        print(json.dumps(line), flush=True)
-    ctx.close()
-
-
-# ------------------------------------------------------------------ frontend CSM (configs[1])
-
-def run_csm_workload(args, rank, world, dev, dev_index, rehearse, stream):
-    import numpy as np
-    import torch
-    import torch.distributed as dist
-    from csm_hip import api
-
-    n_chunks = max(1, SCANS_PER_STEP // WINDOWS_PER_LAUNCH)
-    n_distinct = max(WINDOWS_PER_LAUNCH, min(DISTINCT_SCANS, n_chunks * WINDOWS_PER_LAUNCH))
-    n_distinct -= n_distinct % WINDOWS_PER_LAUNCH
-    scans_per_step = n_chunks * WINDOWS_PER_LAUNCH
-    wl = make_workload(rank, n_distinct)
-    rx, ry, rt, L = wl["params"]
-    ctx = api.Context(dev_index, tuning_off=args.tuning_off)
-    # a non-default torch stream: csm_set_stream(NULL) would mean "the context's
-    # own stream", and the collectives below must be ordered against the scoring
-    ctx.set_stream(stream.cuda_stream)
-    ctx.upload_grid(1, wl["grid"])
-    ctx.build_pyramid(1, [1, L])
-
-    windows, cols, rows_, cands = [], [], [], []
-    for sc in wl["scans"]:
-        wx, wy, wt = sc["win"]
-        windows.append(ctx.make_window(2 * wt + 1, N_BEAMS, wx, wy, L, 1, api.host_min_known(N_BEAMS, 0.0), 0.0))
-        cols.append(torch.from_numpy(sc["col"]).to(dev))
-        rows_.append(torch.from_numpy(sc["row"]).to(dev))
-        nx = -(-(2 * wx + 1) // L) * L
-        ny = -(-(2 * wy + 1) // L) * L
-        cands.append((2 * wt + 1) * nx * ny)
-    rec_bytes = 48
-    results = torch.zeros(scans_per_step * rec_bytes, dtype=torch.uint8, device=dev)
-    gathered = torch.zeros(world * scans_per_step * rec_bytes, dtype=torch.uint8, device=dev)
-    n_batches = n_distinct // WINDOWS_PER_LAUNCH
-    prepared = []
-    for b in range(n_batches):
-        sl = slice(b * WINDOWS_PER_LAUNCH, (b + 1) * WINDOWS_PER_LAUNCH)
-        prepared.append(ctx.prepare_windows([1] * WINDOWS_PER_LAUNCH, windows[sl],
-                                            [c.data_ptr() for c in cols[sl]],
-                                            [r.data_ptr() for r in rows_[sl]]))
-    cands_per_batch = [sum(cands[b * WINDOWS_PER_LAUNCH:(b + 1) * WINDOWS_PER_LAUNCH]) for b in range(n_batches)]
-    cands_per_step = sum(cands_per_batch[k % n_batches] for k in range(n_chunks))
-
-    def step():
-        for k in range(n_chunks):
-            ctx.score_windows_dev(prepared[k % n_batches],
-                                  results.data_ptr() + k * WINDOWS_PER_LAUNCH * rec_bytes)
-        if world > 1:
-            if rehearse:
-                host = results.cpu()
-                out = torch.zeros(world * host.numel(), dtype=torch.uint8)
-                dist.all_gather_into_tensor(out, host)
-                gathered.copy_(out)
-            else:
-                dist.all_gather_into_tensor(gathered, results)
-
-    def fence():
-        torch.cuda.synchronize(dev)
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize(dev)
-
-    with torch.cuda.stream(stream):
-        for _ in range(args.warmup):
-            step()
-        fence()
-        # events around the dominant kernel only inside the timed region; the
-        # other kernels are timed in a short extra pass afterwards
+        # events around the dominant kernel only inside the timed region; with
+        # --full the other kernels are timed in a short extra pass afterwards
         ctx.lib.csm_enable_kernel_timing(ctx._ctx, 2)
         ctx.reset_kernel_timing()
         t0 = time.perf_counter()
@@ -901,21 +784,18 @@ def run_csm_workload(args, rank, world, dev, dev_index, rehearse, stream):
         bound_ms, bound_n = ctx.kernel_time("score_bound")      # the packed-fp32 bound pass of the fine level
         fine_ms += bound_ms
         blocks_scored, blocks_skipped = ctx.bound_pass_stats()
-        ctx.lib.csm_enable_kernel_timing(ctx._ctx, 1)
-        ctx.reset_kernel_timing()
-        step()
-        fence()
-        ctx.enable_kernel_timing(False)
-    others = {}
-    for name in ("score_coarse", "bin", "finalize"):
-        ms, n = ctx.kernel_time(name)
-        others[name] = ms / max(1, n) * 1e3
+        if args.full:
+            ctx.lib.csm_enable_kernel_timing(ctx._ctx, 1)
+            ctx.reset_kernel_timing()
+            step()
+            fence()
+            ctx.enable_kernel_timing(False)
     if last_step is not None and rank == 0:
         dump_records(args.dump_outputs, last_step)
 
     # the same workload through the exact integer kernel alone (no bound pass): reported beside the headline
     exact_only = None
-    if world == 1 and not args.no_configs and not (args.tuning_off & 256) and blocks_skipped:
+    if world == 1 and args.full and not args.no_configs and not (args.tuning_off & 256) and blocks_skipped:
         ctx2 = api.Context(dev_index, tuning_off=args.tuning_off | 256)
         ctx2.set_stream(stream.cuda_stream)
         ctx2.upload_grid(1, wl["grid"])
@@ -947,27 +827,10 @@ def run_csm_workload(args, rank, world, dev, dev_index, rehearse, stream):
     rec_raw = results.cpu().numpy().tobytes()
     rec = np.frombuffer(rec_raw, dtype=np.int32).reshape(scans_per_step, 12)
     n_found = int(rec[:, 0].sum())
-    verified = verify_sample(wl, rec_raw, scans_per_step, n_distinct, args.verify) if rank == 0 else 0
-
 
     if rank == 0:
         total = cands_per_step * args.steps * world
         value = total / dt
-        cands_per_launch = cands_per_step / n_chunks
-        alg_bytes = 2.0 * N_BEAMS * cands_per_launch
-        avg_fine_s = (fine_ms / max(1, fine_n)) * 1e-3
-        # LDS gathers one launch needs: cell entries x candidates, summed over its windows
-        gathers = 0
-        for i in range(WINDOWS_PER_LAUNCH):
-            sc = wl["scans"][i]
-            wx, wy, wt = sc["win"]
-            nx = -(-(2 * wx + 1) // L) * L
-            ny = -(-(2 * wy + 1) // L) * L
-            gathers += cell_entries(sc["col"], sc["row"], 400, 400, -wx, -wy, -wx + nx - 1, -wy + ny - 1) * nx * ny
-        lds_bytes = 4.0 * gathers
-        achieved = lds_bytes / avg_fine_s / 1e9 if avg_fine_s > 0 else 0.0
-        logical = alg_bytes / avg_fine_s / 1e9 if avg_fine_s > 0 else 0.0
-        traffic, traffic_src = pmc_traffic()
         out = {
             "metric": METRIC,
             "value": value,
@@ -999,41 +862,19 @@ def run_csm_workload(args, rank, world, dev, dev_index, rehearse, stream):
                                "proven) + exact integer kernel on the %.2f %% of candidate blocks within that bound of "
                                "the window's maximum" % (100.0 * blocks_scored / max(1, blocks_scored + blocks_skipped)))
                               if blocks_skipped else "exact integer kernel on every candidate block",
-                "bound_pass_us_per_launch": bound_ms / max(1, bound_n) * 1e3,
-                "exact_integer_kernel_only_poses_per_s": exact_only,
-                "verified": verified,
-                "verified_note": "records of the last timed step compared, after the timed region, with the CPU "
-                                 "oracle's literal sweep (best x, y, theta and the f64 score at tolerance 0)",
-            },
-            "roofline": {
-                "bound": "lds",
-                "kernel": ("fine level of %d windows: k_score_jointf_batch<156, 8> + <156, 6> (packed-fp32 bound pass: the "
-                           "48-row blocks, then the 36-row blocks) + k_bound_select + k_score_joint_list<156, 8> / <156, 6> "
-                           "(exact kernel on the blocks kept); avg_launch_us spans all of them"
-                           if blocks_skipped else
-                           "fine level of %d windows: the exact kernel's launches (48-row blocks, then the 36-row blocks); "
-                           "avg_launch_us spans them") % WINDOWS_PER_LAUNCH,
-                "achieved": achieved,
-                "peak": LDS_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / LDS_PEAK_GBS,
-                "note": "LDS gather bytes (4 B x cell entries x candidates) per launch / launch time vs "
-                        "256 B/clk/CU x 256 CUs x 2.4 GHz; the grid window lives in LDS, HBM is not the bound",
-                "lds_gathers_per_launch": gathers,
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "hbm_frac_measured": (traffic / avg_fine_s / 1e9 / HBM_PEAK_GBS)
-                                     if traffic is not None and avg_fine_s > 0 else None,
-                "logical_hbm_gbs": logical,
-                "logical_hbm_frac": logical / HBM_PEAK_GBS,
-                "avg_launch_us": avg_fine_s * 1e6,
-                "launches": fine_n,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "other_kernels_avg_us": others,
             },
         }
+        if args.full:
+            out["config"].update({
+                "bound_pass_us_per_launch": bound_ms / max(1, bound_n) * 1e3,
+                "exact_integer_kernel_only_poses_per_s": exact_only,
+                "verified": verify_sample(wl, rec_raw, scans_per_step, n_distinct, args.verify),
+                "verified_note": "records of the last timed step compared, after the timed region, with the CPU "
+                                 "oracle's literal sweep (best x, y, theta and the f64 score at tolerance 0)",
+            })
+            out["roofline"] = csm_roofline(ctx, wl, cands_per_step / n_chunks, fine_ms, fine_n, blocks_skipped)
         ctx.close()
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             cfgs = {}
             wanted = os.environ.get("CSM_BENCH_CONFIGS",
                                     "config2_single_query,config3,config4_one_gpu,config5").split(",")
@@ -1052,47 +893,101 @@ def run_csm_workload(args, rank, world, dev, dev_index, rehearse, stream):
             out["config"]["side_runs_summary"] = {
                 k: {kk: v[kk] for kk in ("value", "unit", "ms_per_step", "ms_per_query", "latency_ms_median") if kk in v}
                 for k, v in cfgs.items() if isinstance(v, dict)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl)
         print(json.dumps(out), flush=True)
     else:
         ctx.close()
 
 
+def csm_roofline(ctx, wl, cands_per_launch, fine_ms, fine_n, blocks_skipped):
+    """--full: the fine level of the timed steps against the LDS read rate, and the
+    other kernels of one more step (the pass timed right after the timed region)."""
+    L = wl["params"][3]
+    alg_bytes = 2.0 * N_BEAMS * cands_per_launch
+    avg_fine_s = (fine_ms / max(1, fine_n)) * 1e-3
+    # LDS gathers one launch needs: cell entries x candidates, summed over its windows
+    gathers = 0
+    for i in range(WINDOWS_PER_LAUNCH):
+        sc = wl["scans"][i]
+        wx, wy, wt = sc["win"]
+        nx = -(-(2 * wx + 1) // L) * L
+        ny = -(-(2 * wy + 1) // L) * L
+        gathers += cell_entries(sc["col"], sc["row"], 400, 400, -wx, -wy, -wx + nx - 1, -wy + ny - 1) * nx * ny
+    lds_bytes = 4.0 * gathers
+    achieved = lds_bytes / avg_fine_s / 1e9 if avg_fine_s > 0 else 0.0
+    logical = alg_bytes / avg_fine_s / 1e9 if avg_fine_s > 0 else 0.0
+    traffic, traffic_src = pmc_traffic()
+    others = {}
+    for name in ("score_coarse", "bin", "finalize"):
+        ms, n = ctx.kernel_time(name)
+        others[name] = ms / max(1, n) * 1e3
+    return {
+        "bound": "lds",
+        "kernel": ("fine level of %d windows: k_score_jointf_batch<156, 8> + <156, 6> (packed-fp32 bound pass: the "
+                   "48-row blocks, then the 36-row blocks) + k_bound_select + k_score_joint_list<156, 8> / <156, 6> "
+                   "(exact kernel on the blocks kept); avg_launch_us spans all of them"
+                   if blocks_skipped else
+                   "fine level of %d windows: the exact kernel's launches (48-row blocks, then the 36-row blocks); "
+                   "avg_launch_us spans them") % WINDOWS_PER_LAUNCH,
+        "achieved": achieved,
+        "peak": LDS_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": achieved / LDS_PEAK_GBS,
+        "note": "LDS gather bytes (4 B x cell entries x candidates) per launch / launch time vs "
+                "256 B/clk/CU x 256 CUs x 2.4 GHz; the grid window lives in LDS, HBM is not the bound",
+        "lds_gathers_per_launch": gathers,
+        "traffic": traffic,
+        "traffic_source": traffic_src,
+        "hbm_frac_measured": (traffic / avg_fine_s / 1e9 / HBM_PEAK_GBS)
+                             if traffic is not None and avg_fine_s > 0 else None,
+        "logical_hbm_gbs": logical,
+        "logical_hbm_frac": logical / HBM_PEAK_GBS,
+        "avg_launch_us": avg_fine_s * 1e6,
+        "launches": fine_n,
+        "algorithmic_bytes_per_launch": alg_bytes,
+        "other_kernels_avg_us": others,
+    }
+
+
 def run_side_workload(args, dev_index, which):
     """`--workload config5` / `--workload latency` as lines of their own (the same contract):
     a step is one query (one csm_correlative_match call, host-inclusive)."""
     if which == "config5":
-        d = measure_config5(dev_index, runs=args.steps, warmup=max(1, args.warmup))
+        d = measure_config5(dev_index, runs=args.steps, warmup=max(1, args.warmup), kernels=args.full)
         total_s = d["ms_per_query"] * 1e-3 * args.steps
         ms_step = d["ms_per_query"]
         value = d["value"]
-        roof = d["roofline"]
+        roof = d.get("roofline")
     else:
         wl = make_workload(0, 64)
-        d = measure_config2_latency(dev_index, wl, reps=args.steps, warmup=max(3, args.warmup))
+        d = measure_config2_latency(dev_index, wl, reps=args.steps, warmup=max(3, args.warmup), kernels=args.full)
         total_s = d["total_s"]
         ms_step = d["total_s"] / args.steps * 1e3
         value = d["candidates_total"] / d["total_s"]
-        fine_us = d["kernel_us_per_query"].get("score_fine", 0.0)
-        sc = wl["scans"][0]
-        wx, wy, wt = sc["win"]
-        L = wl["params"][3]
-        nx, ny = -(-(2 * wx + 1) // L) * L, -(-(2 * wy + 1) // L) * L
-        gathers = cell_entries(sc["col"], sc["row"], 400, 400, -wx, -wy, -wx + nx - 1, -wy + ny - 1) * nx * ny
-        ach = 4.0 * gathers / (fine_us * 1e-6) / 1e9 if fine_us else None
-        roof = {"bound": "lds", "kernel": "k_score_pairs (fine level of one window, tile-split)", "unit": "GB/s",
-                "peak": LDS_PEAK_GBS, "achieved": ach, "frac": ach / LDS_PEAK_GBS if ach else None,
-                "avg_launch_us": fine_us, "traffic": None,
-                "note": "a single 0.87-M-pose window is latency-bound: six launches and two copies around "
-                        "~50 us of scoring; frac is the fine launch's share of the LDS read peak"}
-    print(json.dumps({
+        roof = None
+        if args.full:
+            fine_us = d["kernel_us_per_query"].get("score_fine", 0.0)
+            sc = wl["scans"][0]
+            wx, wy, wt = sc["win"]
+            L = wl["params"][3]
+            nx, ny = -(-(2 * wx + 1) // L) * L, -(-(2 * wy + 1) // L) * L
+            gathers = cell_entries(sc["col"], sc["row"], 400, 400, -wx, -wy, -wx + nx - 1, -wy + ny - 1) * nx * ny
+            ach = 4.0 * gathers / (fine_us * 1e-6) / 1e9 if fine_us else None
+            roof = {"bound": "lds", "kernel": "k_score_pairs (fine level of one window, tile-split)", "unit": "GB/s",
+                    "peak": LDS_PEAK_GBS, "achieved": ach, "frac": ach / LDS_PEAK_GBS if ach else None,
+                    "avg_launch_us": fine_us, "traffic": None,
+                    "note": "a single 0.87-M-pose window is latency-bound: six launches and two copies around "
+                            "~50 us of scoring; frac is the fine launch's share of the LDS read peak"}
+    line = {
         "metric": METRIC, "value": value, "unit": "candidate poses/s", "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "u32", "data": "synthetic",
         "config": {"workload": d["workload"], "step": "one csm_correlative_match call (host-inclusive)",
-                   "timed_s": total_s, "detail": {k: v for k, v in d.items() if k not in ("roofline", "workload")}},
-        "roofline": roof}), flush=True)
+                   "timed_s": total_s, "detail": {k: v for k, v in d.items() if k not in ("roofline", "workload")}}}
+    if roof is not None:
+        line["roofline"] = roof
+    print(json.dumps(line), flush=True)
 
 
 def build_or_load():
@@ -1114,14 +1009,20 @@ def main():
     ap.add_argument("--steps", type=int, default=None,
                     help="default: 20 (csm, loop workloads), 40 queries (config5), 12000 queries (latency)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: "
+                         "roofline and per-kernel times (extra timed passes), records against the CPU oracle, "
+                         "the exact-only rate, the side runs of the other configs and the CPU baselines. "
+                         "Without it a run sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--tuning-off", type=int, default=0,
                     help="csm_config.tuning_off bits (CSM_TUNE_*: A/B runs of single launch optimisations)")
     ap.add_argument("--verify", type=int, default=24,
-                    help="records of the last timed step compared with the CPU oracle after the timed region "
-                         "(configs[1] workload; 0 = none)")
+                    help="with --full: records of the last timed step compared with the CPU oracle after the "
+                         "timed region (configs[1] workload; 0 = none)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the short side runs of configs[2], [3] at N = 1, [4] and the single-query latency")
+                    help="with --full: skip the exact-only rate and the short side runs of configs[2], [3] at "
+                         "N = 1, [4] and the single-query latency")
     ap.add_argument("--workload", choices=["auto", "csm", "loop", "loop4", "map", "config5", "latency"], default="auto",
                     help="auto (default): csm at N = 1, loop4 at N > 1. csm: BASELINE configs[1] per GPU "
                          "(replicas). loop: configs[2], 256 candidate submaps per GPU. loop4: configs[3], 2048 "

@@ -1,7 +1,7 @@
 """bench.py's output contract on a real GPU: one JSON line with the fields the
-driver reads, for the default workload, the side configs and the extra
-workloads (short runs), plus the N > 1 control flow with two ranks sharing
-this box's one GPU over gloo."""
+driver reads, for the default workload (plain and --full), the side configs and
+the extra workloads (short runs), plus the N > 1 control flow with two ranks
+sharing this box's one GPU over gloo."""
 import json
 import os
 import subprocess
@@ -37,9 +37,32 @@ def _check_roofline(r):
     assert abs(r["logical_hbm_frac"] - r["logical_hbm_gbs"] / 8000.0) < 1e-9
 
 
+_SMALL = {"CSM_BENCH_SCANS": "256", "CSM_BENCH_DISTINCT": "128", "CSM_BENCH_WINDOWS": "64"}
+_FIELDS = {"found", "best_x", "best_y", "best_theta", "key", "sum_values", "known", "tie_count", "flags", "score"}
+
+
+def test_plain_line_is_the_headline_alone(tmp_path):
+    """Without --full the line carries the contract fields and nothing measured
+    after the timed steps; its dumped records are those of a --full run."""
+    d = _run("--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "plain"), env=_SMALL)
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["value"] > 1e8 and d["higher_is_better"] is True and d["dtype"] == "f32+u32"
+    assert d["config"]["poses_found"] == d["config"]["scans_per_step"] == 256
+    assert "roofline" not in d and "cpu_baseline" not in d
+    for k in ("verified", "side_runs", "exact_integer_kernel_only_poses_per_s", "bound_pass_us_per_launch"):
+        assert k not in d["config"], k
+    _run("--full", "--no-configs", "--no-cpu-baseline", "--steps", "2", "--warmup", "1",
+         "--dump-outputs", str(tmp_path / "full"), env=_SMALL)
+    for f in _FIELDS:
+        a, b = np.load(tmp_path / "plain" / (f + ".npy")), np.load(tmp_path / "full" / (f + ".npy"))
+        assert a.shape == (256,) and np.array_equal(a, b), f
+
+
 def test_default_line(tmp_path):
     dump = tmp_path / "dump"
-    d = _run("--steps", "2", "--warmup", "1", "--dump-outputs", str(dump),
+    d = _run("--full", "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump),
              env={"CSM_BENCH_SCANS": "256", "CSM_BENCH_DISTINCT": "128", "CSM_BENCH_WINDOWS": "64",
                   "CSM_BENCH_CONFIGS": "config2_single_query,config3,config5"})
     fields = {"found", "best_x", "best_y", "best_theta", "key", "sum_values", "known", "tie_count", "flags", "score"}
@@ -83,7 +106,7 @@ def test_default_line(tmp_path):
 
 @pytest.mark.parametrize("workload,steps", [("config5", "3"), ("latency", "200")])
 def test_side_workloads_as_lines_of_their_own(workload, steps):
-    d = _run("--workload", workload, "--steps", steps, "--warmup", "1")
+    d = _run("--full", "--workload", workload, "--steps", steps, "--warmup", "1")
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == int(steps) and d["value"] > 1e8
@@ -93,7 +116,7 @@ def test_side_workloads_as_lines_of_their_own(workload, steps):
 
 @pytest.mark.parametrize("workload", ["loop", "map"])
 def test_extra_workloads(workload):
-    d = _run("--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+    d = _run("--full", "--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
     for k in REQUIRED:
         assert k in d, k
     assert d["value"] > 0 and "workload" in d["config"]

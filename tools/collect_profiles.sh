@@ -23,17 +23,17 @@ run_pmc() {     # name, counter, bench args...
 }
 
 # configs[1], the default line
-run_stats csm --no-configs --no-cpu-baseline || exit 1
+run_stats csm --full --no-configs --no-cpu-baseline || exit 1
 export CSM_BENCH_SCANS=512 CSM_BENCH_DISTINCT=256
 run_pmc csm FETCH_SIZE --steps 3 --warmup 1 --no-configs --no-cpu-baseline || exit 1
 run_pmc csm WRITE_SIZE --steps 3 --warmup 1 --no-configs --no-cpu-baseline || exit 1
 # configs[4]: the one workload whose maps leave L2 (56 MB pair-row copy, 8 MB grid)
-run_stats cfg5 --workload config5 --steps 5 --warmup 1 || exit 1
+run_stats cfg5 --full --workload config5 --steps 5 --warmup 1 || exit 1
 run_pmc cfg5 FETCH_SIZE --workload config5 --steps 2 --warmup 1 || exit 1
 run_pmc cfg5 WRITE_SIZE --workload config5 --steps 2 --warmup 1 || exit 1
 unset CSM_BENCH_SCANS CSM_BENCH_DISTINCT CSM_BENCH_CONFIGS CSM_BENCH_WINDOWS
 # configs[2]: the branch-and-bound batch
-run_stats loop --workload loop --steps 10 --no-cpu-baseline || exit 1
+run_stats loop --full --workload loop --steps 10 --no-cpu-baseline || exit 1
 run_pmc loop FETCH_SIZE --workload loop --steps 3 --warmup 1 --no-cpu-baseline || exit 1
 run_pmc loop WRITE_SIZE --workload loop --steps 3 --warmup 1 --no-cpu-baseline || exit 1
 
