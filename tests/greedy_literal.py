@@ -72,8 +72,10 @@ class Greedy:
         max_sq = max_dx * max_dx + max_dy * max_dy
         self.default = -math.exp(-0.5 * max_sq / self.var)
 
-    def beam_values(self, grid, geom, angles, ranges, pose):
-        """minCostValue of every beam (Cost's loop body), as a float64 array."""
+    def beam_values(self, grid, geom, angles, ranges, pose, alloc=None):
+        """minCostValue of every beam (Cost's loop body), as a float64 array. alloc: None (every
+        cell readable) or (bitmap, log2_block), the map's block allocation; a read in an
+        unallocated block returns ProbabilityOr's default 0.0."""
         res, off_x, off_y = geom
         n = len(angles)
         cs = np.empty(n)
@@ -98,6 +100,11 @@ class Greedy:
 
         def prob_or(row, col):
             inside = (row >= 0) & (row < rows) & (col >= 0) & (col < cols)
+            if alloc is not None:
+                bitmap, log2_block = alloc
+                blk = np.zeros(row.shape, bool)
+                blk[inside] = bitmap[row[inside] >> log2_block, col[inside] >> log2_block] != 0
+                inside &= blk
             v = np.zeros(row.shape, np.uint16)
             v[inside] = grid[row[inside], col[inside]]
             return np.where(inside, pl[v], 0.0)
@@ -113,26 +120,26 @@ class Greedy:
                 best = np.where(keep, np.minimum(best, cost), best)
         return best
 
-    def cost(self, grid, geom, angles, ranges, pose):
-        vals = self.beam_values(grid, geom, angles, ranges, pose)
+    def cost(self, grid, geom, angles, ranges, pose, alloc=None):
+        vals = self.beam_values(grid, geom, angles, ranges, pose, alloc)
         s = float(np.cumsum(vals)[-1])      # sumCostValue += minCostValue, in beam order
         s *= self.scale
         return s
 
-    def gradient(self, grid, geom, angles, ranges, pose):
+    def gradient(self, grid, geom, angles, ranges, pose, alloc=None):
         diff_linear = geom[0]
         diff_angular = 1e-2
 
         def c(p):
-            return self.cost(grid, geom, angles, ranges, p)
+            return self.cost(grid, geom, angles, ranges, p, alloc)
         x, y, t = pose
         dx = c((x + diff_linear, y + 0.0, t + 0.0)) - c((x - diff_linear, y - 0.0, t - 0.0))
         dy = c((x + 0.0, y + diff_linear, t + 0.0)) - c((x - 0.0, y - diff_linear, t - 0.0))
         dt = c((x + 0.0, y + 0.0, t + diff_angular)) - c((x - 0.0, y - 0.0, t - diff_angular))
         return (0.5 * dx / diff_linear, 0.5 * dy / diff_linear, 0.5 * dt / diff_angular)
 
-    def covariance(self, grid, geom, angles, ranges, pose):
-        g = self.gradient(grid, geom, angles, ranges, pose)
+    def covariance(self, grid, geom, angles, ranges, pose, alloc=None):
+        g = self.gradient(grid, geom, angles, ranges, pose, alloc)
         cov = [[g[i] * g[j] for j in range(3)] for i in range(3)]
         cov[0][0] += 0.1
         cov[1][1] += 0.1
@@ -141,15 +148,16 @@ class Greedy:
 
 
 def optimize_pose(grid, geom, angles, ranges, rel_pose, init_pose, linear_step, angular_step,
-                  max_iterations, max_refinements, greedy):
-    """ScanMatcherHillClimbing::OptimizePose; returns the summary fields and metrics."""
+                  max_iterations, max_refinements, greedy, alloc=None):
+    """ScanMatcherHillClimbing::OptimizePose; returns the summary fields and metrics.
+    alloc: the map's block allocation, as in Greedy.beam_values."""
     move_x = (1.0, -1.0, 0.0, 0.0, 0.0, 0.0)
     move_y = (0.0, 0.0, 1.0, -1.0, 0.0, 0.0)
     move_t = (0.0, 0.0, 0.0, 0.0, 1.0, -1.0)
     cf = greedy if isinstance(greedy, Greedy) else Greedy(**{**DEFAULT_GREEDY, **(greedy or {})})
     n = len(angles)
     sensor = tuple(api.host_compound(init_pose, rel_pose))
-    initial_cost = cf.cost(grid, geom, angles, ranges, sensor)
+    initial_cost = cf.cost(grid, geom, angles, ranges, sensor, alloc)
     normalized_initial = initial_cost / n
     min_cost = initial_cost
     best = sensor
@@ -162,7 +170,7 @@ def optimize_pose(grid, geom, angles, ranges, rel_pose, init_pose, linear_step, 
         updated = False
         for i in range(6):
             pose = (best[0] + move_x[i] * lin, best[1] + move_y[i] * lin, best[2] + move_t[i] * ang)
-            c = cf.cost(grid, geom, angles, ranges, pose)
+            c = cf.cost(grid, geom, angles, ranges, pose, alloc)
             if c < min_local:
                 min_local = c
                 best_local = pose
@@ -181,7 +189,7 @@ def optimize_pose(grid, geom, angles, ranges, rel_pose, init_pose, linear_step, 
         if not iterations < max_iterations:
             break
     estimated = tuple(api.host_move_backward(best, rel_pose))
-    cov = cf.covariance(grid, geom, angles, ranges, best)
+    cov = cf.covariance(grid, geom, angles, ranges, best, alloc)
     return dict(normalized_initial_cost=normalized_initial, normalized_cost=min_cost / n,
                 sensor_pose=list(sensor), best_sensor_pose=list(best), estimated_pose=list(estimated),
                 covariance=cov, iterations=iterations, refinements=refinements,
