@@ -494,19 +494,20 @@ int csm_last_search_info(csm_ctx* ctx, csm_search_info* out)
     if (!ctx || !out)
         return CSM_EINVAL;
     std::memset(out, 0, sizeof(*out));
-    out->nominal_candidates = ctx->last_nominal;
-    out->coarse_nodes_scored = ctx->last_coarse_nodes;
-    out->fine_candidates_scored = ctx->last_fine_candidates;
+    const csm_ctx::LastRun& run = ctx->last_run;
+    out->nominal_candidates = run.nominal;
+    out->coarse_nodes_scored = run.coarse_nodes;
+    out->fine_candidates_scored = run.fine_candidates;
     out->graph_replayed = ctx->last_graph_replayed ? 1 : 0;
-    if (ctx->tp_count_dev) {
+    if (run.kept_dev) {
         uint32_t kept = 0;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipMemcpyAsync(&kept, ctx->tp_count_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&kept, run.kept_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         out->two_phase = 1;
         out->blocks_scored = kept;
-        out->blocks_skipped = ctx->tp_blocks_total - (int64_t)kept;
-        out->fine_candidates_scored = (int64_t)kept * ctx->last_block_candidates;
+        out->blocks_skipped = run.blocks_total - (int64_t)kept;
+        out->fine_candidates_scored = (int64_t)kept * run.block_candidates;
     }
     return CSM_OK;
 }

@@ -76,12 +76,8 @@ static int bnb_literal(csm_ctx* ctx, const csm_loop_query& q, const BatchPrep& p
         const size_t n = (size_t)p.n_theta * nxh * nyh;
         if ((rc = ensure(ctx, ctx->ex_fine, n * 8))) return rc;
         if ((rc = ensure(ctx, ctx->ex_fine_k, n * 4))) return rc;
-        ExactJob ej;
-        std::memset(&ej, 0, sizeof(ej));
-        ej.cells = p.grid->levels[p.level[h]].cells;
-        ej.rows = p.grid->rows;
-        ej.cols = p.grid->cols;
-        ej.pitch = p.grid->pitch;
+        ExactJob ej = exact_job(*p.grid, p.grid->levels[p.level[h]].cells, p.n_theta, p.n, -p.win_x, -p.win_y, nxh, nyh,
+                                1 << h, ctx->lut_dev.as<double>(), ctx->ex_fine.as<double>(), ctx->ex_fine_k.as<uint32_t>());
         ej.r_cos = d_rc;
         ej.r_sin = d_rs;
         ej.sensor_x = o.sensor_pose[0];
@@ -91,16 +87,6 @@ static int bnb_literal(csm_ctx* ctx, const csm_loop_query& q, const BatchPrep& p
         ej.off_x = q.geometry.offset_x;
         ej.off_y = q.geometry.offset_y;
         ej.res = q.geometry.resolution;
-        ej.n_theta = p.n_theta;
-        ej.n_points = p.n;
-        ej.x_lo = -p.win_x;
-        ej.y_lo = -p.win_y;
-        ej.nx = nxh;
-        ej.ny = nyh;
-        ej.stride = 1 << h;
-        ej.lut = ctx->lut_dev.as<double>();
-        ej.out_score = reinterpret_cast<double*>(ctx->ex_fine.p);
-        ej.out_k = reinterpret_cast<uint32_t*>(ctx->ex_fine_k.p);
         if (int e = csm_launch::exact_scores(ctx->stream, (unsigned)((n + kBlock - 1) / kBlock), ej))
             return launched_ok(ctx, e, "exact score");
         sc[h].resize(n);

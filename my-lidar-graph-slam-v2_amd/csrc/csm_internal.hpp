@@ -191,16 +191,25 @@ struct csm_ctx {
     bool capturing = false;
     struct RecordedChain {
         hipGraphExec_t exec = nullptr;
-        csm::ScoreJob fine;          /* the fine-level job baked into the chain: last_fine after a replay */
+        csm::ScoreJob fine;          /* the fine-level job baked into the chain: last_run.fine after a replay */
     };
     std::map<std::vector<uint64_t>, RecordedChain> graphs;
     std::map<std::vector<uint64_t>, int> graph_seen;
     bool last_graph_replayed = false;            /* csm_last_search_info: the last match was a replay */
     PinBuf q_pin;                    /* [ProjJob | angles | ranges] up, [record | uncertified count] back */
     DevBuf q_dev;
-    const uint32_t* tp_count_dev = nullptr;      /* blocks kept (= items of the work list) by the last two-phase search */
-    int64_t tp_blocks_total = 0;                 /* ... of this many */
-    int64_t last_coarse_nodes = 0, last_fine_candidates = 0, last_nominal = 0, last_block_candidates = 0;   /* csm_last_search_info */
+    /* What the last single-window launch chain (csm_window.hip: a driver, or the replay of a recorded
+     * graph) left behind, for resolve_ties and csm_last_search_info, which may run in a later call. */
+    struct LastRun {
+        /* the chain's fine-level job, for the tie collection pass: its flag word and two-phase
+         * eligibility levels are facts of that launch, not of the window alone */
+        csm::ScoreJob fine = {};
+        int64_t nominal = 0, coarse_nodes = 0, fine_candidates = 0;
+        /* coarse-first searches: blocks kept (= items of the work list, a device counter) of
+         * blocks_total, each of block_candidates candidates */
+        const uint32_t* kept_dev = nullptr;
+        int64_t blocks_total = 0, block_candidates = 0;
+    } last_run;
     DevBuf fine_s, fine_k, tie, ex_fine, ex_fine_k, ex_coarse, ex_coarse_k, scan_dev, unc, sorted_rc, b_sorted_rc;
     std::map<std::array<int, 4>, DevBuf> lane_maps;   /* lane_map_for(): (cbx, groups, R, LS) -> uint16_t table */
     PinBuf pin;                   /* staging of csm_upload_grid */
@@ -231,10 +240,6 @@ struct csm_ctx {
      * uploads), each kept until the event recorded behind its launch chain has fired; an entry
      * taken out must move its block back to pin_free (dropping it frees the block) */
     std::vector<std::pair<hipEvent_t, PinBuf>> resident_hold;
-    /* the fine-level job of the last launch chain (run_window, or the recorded job of a replayed
-     * graph), for the tie collection pass: its flag word and two-phase eligibility levels are
-     * facts of that launch, not of the window alone */
-    csm::ScoreJob last_fine;
     unsigned flag_toggle = 0;     /* two flag words, used alternately: k_finalize of query i
                                      clears the word of query i + 1 */
     bool flags_ready = false;

@@ -1,7 +1,7 @@
 /* csm_matchers.hpp -- what the matchers' host translation units share (csm_plan.hip: planner, window
- * frame, job-record builders, launch helpers, levels; csm_window.hip: one window at a time; csm_batch.hip:
- * batches; csm_api.hip: context, grids, pyramids, host restatements, timing). All of it lives in namespace
- * csm_host. */
+ * frame, job-record builders, launch helpers, levels; csm_batch.hip: batches; csm_api.hip: context, grids,
+ * pyramids, host restatements, timing). csm_window.hip (one window at a time) keeps its launch chains to
+ * itself: it shares nothing but its entry points of the C ABI. All of it lives in namespace csm_host. */
 #ifndef CSM_MATCHERS_HPP
 #define CSM_MATCHERS_HPP
 
@@ -59,24 +59,6 @@ struct PendingBox {
     int level;          /* index into grid->levels: its cells are the destination */
 };
 
-struct WindowOutputs {
-    uint32_t* dump_s = nullptr;     /* device */
-    uint16_t* dump_k = nullptr;
-};
-
-/* The CSM pipeline on device-resident inputs; asynchronous. */
-/* Two-phase search (csm_phase_kernels.hip). mode 1: score the window and STORE every candidate's
- * sums [n_theta][nx][ny] (the coarse pass, run on the level's phase-major copy), nothing else;
- * mode 2: the fine level, its eligibility from such sums (level_s / level_k with strides nxs, nys),
- * over the work list of the blocks that can still win. */
-struct TwoPhaseCtl {
-    int mode = 0;
-    uint32_t* level_s = nullptr;
-    uint32_t* level_k = nullptr;
-    int nxs = 0, nys = 0;
-    uint32_t stats[4] = { 0, 0, 0, 0 };      /* mode 2, filled on request: items, kept, dropped */
-};
-
 /* Splits [0, n) over up to four host threads (the batch entries touch tens of
  * megabytes of scan data before anything can be launched); fn(lo, hi) must not
  * touch the context. */
@@ -126,6 +108,8 @@ BinJob bin_job(const DeviceGrid& g, const WindowFrame& f, int n_theta, int n_poi
 ScoreJob score_job(const DeviceGrid& g, const uint16_t* cells, int stride, const BinJob& entries, int min_known);
 FinalJob final_job(const ScoreJob& fine, int n_blocks, const int32_t* hit_col, const int32_t* hit_row,
                    double score_thr, const double* lut, void* out);
+ExactJob exact_job(const DeviceGrid& g, const uint16_t* cells, int n_theta, int n_points, int x_lo, int y_lo,
+                   int nx, int ny, int stride, const double* lut, double* out_score, uint32_t* out_k);
 int launched_ok(csm_ctx* ctx, int e, const char* what);
 csm_launch::ScoreLaunch score_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, size_t lds);
 csm::JointLaunch joint_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, const uint16_t* lane_map);
@@ -145,23 +129,6 @@ int level_for_window(csm_ctx* ctx, DeviceGrid& g, int win, int* index,
                      std::vector<PendingBox>* pending = nullptr);
 int ensure_xgrid(csm_ctx* ctx, DeviceGrid& g, int need_pad);
 int ensure_xgrid_f(csm_ctx* ctx, DeviceGrid& g);
-int run_level_pass_joint(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
-                         const int32_t* hit_col_dev, const int32_t* hit_row_dev, uint32_t* flags, TwoPhaseCtl* tp);
-int run_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
-               const int32_t* hit_col_dev, const int32_t* hit_row_dev,
-               csm_result* out_dev, const WindowOutputs* dumps, bool force_coarse = false,
-               TwoPhaseCtl* tp = nullptr);
-int ensure_phase_map(csm_ctx* ctx, DeviceGrid& g, int level, int need, PhaseMap** out);
-bool wants_two_phase(const csm_ctx* ctx, const Plan& p);
-int search_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p, const int32_t* col_dev,
-                  const int32_t* row_dev, csm_result* out_dev);
-int resolve_ties(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
-                 const int32_t* col_dev, const int32_t* row_dev, csm_result* out_dev);
-int resolve_literal(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
-                    const int32_t* col_dev, const int32_t* row_dev, csm_result* out_dev);
-int resolve_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
-                   const int32_t* col_dev, const int32_t* row_dev, csm_result* out_dev,
-                   const csm_result* have = nullptr, bool* changed = nullptr);
 
 } /* namespace csm_host */
 #endif

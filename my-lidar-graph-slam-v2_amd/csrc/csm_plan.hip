@@ -526,6 +526,30 @@ FinalJob final_job(const ScoreJob& fine, int n_blocks, const int32_t* hit_col, c
     return j;
 }
 
+/* Exhaustive f64 scores of every stride-th candidate of a window on one level (`cells`) of g; the
+ * caller sets the projection: hit indices, or per-node products with the pose and geometry. */
+ExactJob exact_job(const DeviceGrid& g, const uint16_t* cells, int n_theta, int n_points, int x_lo, int y_lo,
+                   int nx, int ny, int stride, const double* lut, double* out_score, uint32_t* out_k)
+{
+    ExactJob j;
+    std::memset(&j, 0, sizeof(j));
+    j.cells = cells;
+    j.rows = g.rows;
+    j.cols = g.cols;
+    j.pitch = g.pitch;
+    j.n_theta = n_theta;
+    j.n_points = n_points;
+    j.x_lo = x_lo;
+    j.y_lo = y_lo;
+    j.nx = nx;
+    j.ny = ny;
+    j.stride = stride;
+    j.lut = lut;
+    j.out_score = out_score;
+    j.out_k = out_k;
+    return j;
+}
+
 /* What the wrappers of csm_launch.hip return: a HIP error code, or -1 for "no kernel instantiated". */
 int launched_ok(csm_ctx* ctx, int e, const char* what)
 {

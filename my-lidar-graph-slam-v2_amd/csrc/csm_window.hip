@@ -1,315 +1,219 @@
-/* csm_window.hip -- one search window at a time (host code only): the CSM launch chain (run_window), the
- * coarse-first search of large windows (search_window, csm_phase_kernels.hip), tie / literal resolution,
- * and the single-query entry points of the C ABI (csm_score_window*, csm_correlative_match with its graph
- * replay, csm_grid_search_match, csm_project_scan). */
+/* csm_window.hip -- one search window at a time (host code only): three launch chains over the stages of
+ * WindowRun (run_exhaustive; the coarse-first search_window of large windows = run_level_pass, then
+ * run_fine_under_level), tie / literal resolution, and the single-query entry points of the C ABI, the
+ * only names visible outside: csm_score_window*, csm_correlative_match (query block, graph cache,
+ * uncertified projection entries), csm_grid_search_match, csm_project_scan. */
 #include "csm_matchers.hpp"
 
-namespace csm_host {
+namespace {
 
+/* Every candidate's sums of a scored level, [n_theta][nxs][nys]: the eligibility of the level below. */
+struct StoredLevel {
+    uint32_t *s = nullptr, *k = nullptr;
+    int nxs = 0, nys = 0;
+};
 
-/* Mode 1 on JOINT entries of slice pairs (csm_joint_kernels.hip: k_binj_one + k_score_joint_one), jobs
- * by value. On the phase-major copy a tile holds the beams of one phase only (configs[4]: ~6 entries per
- * staged window against ~53 at the fine level), so the pass is bound by staging; a pair of neighbouring
- * slices shares every staged window. Returns kNotJoint where the joint tables do not fit (the caller
- * then takes the per-slice pair kernel). */
-const int kNotJoint = -1000;
-
-int run_level_pass_joint(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
-                         const int32_t* hit_col_dev, const int32_t* hit_row_dev, uint32_t* flags, TwoPhaseCtl* tp)
+/* Can the level pass run on JOINT entries of slice pairs (k_binj_one + k_score_joint_one)? On the
+ * phase-major copy a tile holds the beams of one phase only (configs[4]: ~6 entries per staged window
+ * against ~53 at the fine level), so the pass is bound by staging, and a pair of neighbouring slices
+ * shares every staged window. Not where the joint tables do not fit (then: the per-slice pair kernel). */
+bool joint_level_plan(const csm_ctx* ctx, const Plan& p, PassPlan* jp)
 {
     if (!ctx->tune.joint || !ctx->tune.two_slices || !p.fine.pairs || p.L != 1)
-        return kNotJoint;
-    PassPlan jp;
-    const int hash_size = csm::binj_hash_size(p.n);
-    const size_t binj_lds = csm::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, hash_size);
+        return false;
+    const size_t binj_lds = csm::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, csm::binj_hash_size(p.n));
     /* the exact joint kernel keeps kJRec entry words next to the window copy (not two kPbMax lists) */
-    if (binj_lds > 150 * 1024 || !plan_pass_pairs(ctx->tune, p.nx, p.ny, &jp, true, kJRec * 4) || jp.lists != 2)
-        return kNotJoint;
-    jp.joint = true;
-    jp.weighted = true;
-    int rc;
-    const int n_pairs = (p.n_theta + 1) / 2;
-    const int max_tiles = std::min(2 * p.n, p.tiles_x * p.tiles_y) + 2 * p.n / kJRec + 1;
-    if ((rc = ensure(ctx, ctx->sorted, (size_t)n_pairs * 2 * p.n * 4 + 256))) return rc;
-    if ((rc = ensure(ctx, ctx->tiles, (size_t)n_pairs * max_tiles * sizeof(TileRec)))) return rc;
-    if ((rc = ensure(ctx, ctx->ntiles, (size_t)n_pairs * 8))) return rc;
-    BinJob bj = bin_job(g, p, p.n_theta, p.n, max_tiles, hit_col_dev, hit_row_dev,
-                        reinterpret_cast<uint32_t*>(ctx->sorted.p), reinterpret_cast<TileRec*>(ctx->tiles.p),
-                        reinterpret_cast<int32_t*>(ctx->ntiles.p), flags, 2);
-    bj.hash_size = hash_size;
-    bj.max_mult = kMaxMult;
-    bj.lstride = jp.lstride;
-    {
-        ScopedTimer tm(ctx, "bin");
-        if ((rc = launched_ok(ctx, csm::launch_binj_one(ctx->stream, ctx->device, bj, n_pairs, binj_lds), "joint binning")))
-            return rc;
-    }
-    ScoreJob fj = score_job(g, g.levels[0].cells, 1, bj, w->min_known);
-    fj.xg = g.xg.as<uint32_t>();
-    fj.xg_pitch = g.xg_pitch;
-    fj.xg_pad = g.xg_pad;
-    fj.rank_l = p.L;
-    fj.joint = 1;
-    /* every candidate's sums, stored; no arg-max, no record */
-    fj.acc_s = reinterpret_cast<uint32_t*>(ctx->coarse_s.p);
-    fj.acc_k = reinterpret_cast<uint32_t*>(ctx->coarse_k.p);
-    fj.acc_x_major = 2;
-    tp->level_s = fj.acc_s;
-    tp->level_k = fj.acc_k;
-    tp->nxs = p.nx;
-    tp->nys = p.ny;
-    const uint16_t* lane_map = nullptr;
-    if ((rc = lane_map_for(ctx, jp, &lane_map)))
-        return rc;
-    csm::JointLaunch L = joint_launch(ctx, jp, dim3(jp.ncb(), 1, 1), lane_map);
-    L.ncb = jp.ncb();
-    ScopedTimer tm(ctx, "score_coarse");
-    return launched_ok(ctx, csm::launch_joint_one(L, fj, n_pairs), "joint level pass");
+    if (binj_lds > 150 * 1024 || !plan_pass_pairs(ctx->tune, p.nx, p.ny, jp, true, kJRec * 4) || jp->lists != 2)
+        return false;
+    jp->joint = true;
+    jp->weighted = true;
+    return true;
 }
 
-int run_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
-               const int32_t* hit_col_dev, const int32_t* hit_row_dev,
-               csm_result* out_dev, const WindowOutputs* dumps, bool force_coarse,
-               TwoPhaseCtl* tp)
+/* Tile-split fine launch when the window gives fewer than ~1.5 workgroups per CU (config 2: 246);
+ * CSM_TUNE_NO_TILE_SPLIT: never. *fine_slices > 1: the accumulators are sized and zero. */
+int tile_split_slices(csm_ctx* ctx, const Plan& p, int* fine_slices)
 {
-    const int tp_mode = tp ? tp->mode : 0;
-    if (w->coarse_level < 0 || w->coarse_level >= (int)g.levels.size())
-        return fail(ctx, CSM_ENOENT, "coarse level %d not built", w->coarse_level);
-    if (g.levels[w->coarse_level].stale)
-        return fail(ctx, CSM_ENOENT, "coarse level %d is stale: the map was rebuilt", w->coarse_level);
-    if (g.levels[w->coarse_level].win != p.L)
-        return fail(ctx, CSM_EINVAL, "level %d holds box-max(%d), window asks L=%d",
-                    w->coarse_level, g.levels[w->coarse_level].win, p.L);
     int rc;
-    const size_t nt = p.n_theta;
-    if ((rc = ensure(ctx, ctx->sorted, nt * p.n * 4 + 256))) return rc;   /* + 64 entries: the LDS-DMA of a
-                                                                             tile's list reads whole 64-entry pieces */
-    if (p.fine.pairs && (rc = ensure_xgrid(ctx, g, xgrid_pad_for(p.nx, p.ny)))) return rc;
-    if ((rc = ensure(ctx, ctx->tiles, nt * p.max_tiles * sizeof(TileRec)))) return rc;
-    if ((rc = ensure(ctx, ctx->ntiles, nt * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->misc, 256))) return rc;
-    if ((rc = ensure(ctx, ctx->coarse_s, nt * p.nxc * p.nyc * 4))) return rc;
-    if ((rc = ensure(ctx, ctx->coarse_k, nt * p.nxc * p.nyc * 4))) return rc;
-    const int ncb = p.fine.ncb();
-    if ((rc = ensure(ctx, ctx->best, nt * ncb * sizeof(BlockBest)))) return rc;
-    if ((rc = ensure(ctx, ctx->sorted_rc, nt * p.n * 4))) return rc;
+    const long blocks = (long)p.fine.ncb() * p.n_theta;
+    *fine_slices = 1;
+    if (blocks < 384)
+        *fine_slices = (int)std::min<long>(4, std::max<long>(1, 492 / std::max<long>(1, blocks)));
+    if (!ctx->tune.tile_split)
+        *fine_slices = 1;
+    else if (ctx->tune.fine_slices)
+        *fine_slices = std::max(1, std::min(8, ctx->tune.fine_slices));
+    if (*fine_slices <= 1)
+        return CSM_OK;
+    /* the accumulators are zero between queries: cleared once when
+     * (re)allocated, then by the arg-max pass as it reads them */
+    const size_t words = (size_t)p.n_theta * p.nx * p.ny;
+    const void *old_s = ctx->fine_s.p, *old_k = ctx->fine_k.p;
+    if ((rc = ensure(ctx, ctx->fine_s, words * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->fine_k, words * 4))) return rc;
+    if (ctx->fine_s.p != old_s || ctx->fine_acc_dirty)
+        HIP_TRY(ctx, hipMemsetAsync(ctx->fine_s.p, 0, ctx->fine_s.cap, ctx->stream));
+    if (ctx->fine_k.p != old_k || ctx->fine_acc_dirty)
+        HIP_TRY(ctx, hipMemsetAsync(ctx->fine_k.p, 0, ctx->fine_k.cap, ctx->stream));
+    ctx->fine_acc_dirty = false;
+    return CSM_OK;
+}
 
-    /* tile-split fine launch when the window gives fewer than ~1.5 workgroups
-     * per CU (config 2: 246); CSM_TUNE_NO_TILE_SPLIT: never */
-    int fine_slices = 1;
+/* One window's launch chain in the making: what its stages share. A driver calls the stages it
+ * needs top to bottom; each stage queues its work on ctx->stream and returns a CSM_* code. */
+struct WindowRun {
+    csm_ctx* ctx;
+    DeviceGrid& g;
+    const csm_window* w;
+    const Plan& p;
+    const int32_t *hit_col, *hit_row;   /* device */
+    uint32_t *flags = nullptr, *flags_next = nullptr;   /* this chain's flag word; the word its finalize clears for the next */
+    BinJob bj;                          /* the entry lists the scoring stages read (bin, bin_joint) */
+
+    /* The window's level checked, then the workspaces every chain sizes for its window (a graph is
+     * recorded on a shape's third query: by then none may grow). */
+    int workspaces()
     {
-        const long blocks = (long)ncb * p.n_theta;
-        if (blocks < 384)
-            fine_slices = (int)std::min<long>(4, std::max<long>(1, 492 / std::max<long>(1, blocks)));
-        if (!ctx->tune.tile_split || tp_mode)
-            fine_slices = 1;
-        else if (ctx->tune.fine_slices)
-            fine_slices = std::max(1, std::min(8, ctx->tune.fine_slices));
-        if (fine_slices > 1) {
-            /* the accumulators are zero between queries: cleared once when
-             * (re)allocated, then by the arg-max pass as it reads them */
-            const size_t words = nt * (size_t)p.nx * p.ny;
-            const void* old_s = ctx->fine_s.p;
-            const void* old_k = ctx->fine_k.p;
-            if ((rc = ensure(ctx, ctx->fine_s, words * 4))) return rc;
-            if ((rc = ensure(ctx, ctx->fine_k, words * 4))) return rc;
-            if (ctx->fine_s.p != old_s || ctx->fine_acc_dirty)
-                HIP_TRY(ctx, hipMemsetAsync(ctx->fine_s.p, 0, ctx->fine_s.cap, ctx->stream));
-            if (ctx->fine_k.p != old_k || ctx->fine_acc_dirty)
-                HIP_TRY(ctx, hipMemsetAsync(ctx->fine_k.p, 0, ctx->fine_k.cap, ctx->stream));
-            ctx->fine_acc_dirty = false;
+        if (w->coarse_level < 0 || w->coarse_level >= (int)g.levels.size())
+            return fail(ctx, CSM_ENOENT, "coarse level %d not built", w->coarse_level);
+        if (g.levels[w->coarse_level].stale)
+            return fail(ctx, CSM_ENOENT, "coarse level %d is stale: the map was rebuilt", w->coarse_level);
+        if (g.levels[w->coarse_level].win != p.L)
+            return fail(ctx, CSM_EINVAL, "level %d holds box-max(%d), window asks L=%d",
+                        w->coarse_level, g.levels[w->coarse_level].win, p.L);
+        int rc;
+        const size_t nt = p.n_theta;
+        if ((rc = ensure(ctx, ctx->sorted, nt * p.n * 4 + 256))) return rc;   /* + 64 entries: the LDS-DMA of a
+                                                                                 tile's list reads whole 64-entry pieces */
+        if (p.fine.pairs && (rc = ensure_xgrid(ctx, g, xgrid_pad_for(p.nx, p.ny)))) return rc;
+        if ((rc = ensure(ctx, ctx->tiles, nt * p.max_tiles * sizeof(TileRec)))) return rc;
+        if ((rc = ensure(ctx, ctx->ntiles, nt * 8))) return rc;
+        if ((rc = ensure(ctx, ctx->misc, 256))) return rc;
+        if ((rc = ensure(ctx, ctx->coarse_s, nt * p.nxc * p.nyc * 4))) return rc;
+        if ((rc = ensure(ctx, ctx->coarse_k, nt * p.nxc * p.nyc * 4))) return rc;
+        if ((rc = ensure(ctx, ctx->best, nt * p.fine.ncb() * sizeof(BlockBest)))) return rc;
+        return ensure(ctx, ctx->sorted_rc, nt * p.n * 4);
+    }
+
+    /* Two flag words of ctx->misc used alternately: k_finalize of query i clears the word of query
+     * i + 1, so only a chain that ends in a finalize moves on to the next word. */
+    int take_flags(bool finalize_follows)
+    {
+        uint32_t* flag_words = reinterpret_cast<uint32_t*>(ctx->misc.p);
+        if (!ctx->flags_ready && !ctx->capturing) {
+            HIP_TRY(ctx, hipMemsetAsync(flag_words, 0, 16, ctx->stream));
+            ctx->flags_ready = true;
         }
-    }
-    uint32_t* flag_words = reinterpret_cast<uint32_t*>(ctx->misc.p);
-    if (!ctx->flags_ready && !ctx->capturing) {
-        HIP_TRY(ctx, hipMemsetAsync(flag_words, 0, 16, ctx->stream));
-        ctx->flags_ready = true;
-    }
-    uint32_t* flags = flag_words + (ctx->flag_toggle & 1u);
-    uint32_t* flags_next = flag_words + ((ctx->flag_toggle + 1u) & 1u);
-    if (ctx->capturing) {
-        /* a graph bakes its pointers: a flag word of its own, cleared by a node of the graph */
-        flags = flag_words + 2;
-        flags_next = nullptr;
-        HIP_TRY(ctx, hipMemsetAsync(flags, 0, 4, ctx->stream));
-    } else if (tp_mode != 1) {  /* the level pass sets no flag and has no finalize to clear one */
-        ctx->flag_toggle++;
+        flags = flag_words + (ctx->flag_toggle & 1u);
+        flags_next = flag_words + ((ctx->flag_toggle + 1u) & 1u);
+        if (ctx->capturing) {
+            /* a graph bakes its pointers: a flag word of its own, cleared by a node of the graph */
+            flags = flag_words + 2;
+            flags_next = nullptr;
+            HIP_TRY(ctx, hipMemsetAsync(flags, 0, 4, ctx->stream));
+        } else if (finalize_follows) {
+            ctx->flag_toggle++;
+        }
+        return CSM_OK;
     }
 
-    if (tp_mode == 1) {
-        const int rcj = run_level_pass_joint(ctx, g, w, p, hit_col_dev, hit_row_dev, flags, tp);
-        if (rcj != kNotJoint)
-            return rcj;
-    }
-
-    BinJob bj = bin_job(g, p, p.n_theta, p.n, p.max_tiles, hit_col_dev, hit_row_dev,
-                        reinterpret_cast<uint32_t*>(ctx->sorted.p), reinterpret_cast<TileRec*>(ctx->tiles.p),
-                        reinterpret_cast<int32_t*>(ctx->ntiles.p), flags, p.fine.pairs ? 1 : 0);
-    bj.hash_size = bin_hash_size(p.n);
-    bj.max_mult = p.fine.weighted ? kMaxMult : 1;
-    bj.lstride = p.fine.lstride;
-    bj.sorted_rc = p.L > 1 ? reinterpret_cast<uint32_t*>(ctx->sorted_rc.p) : nullptr;
-    const bool coarse_exits = w->min_known <= 1 && !force_coarse && tp_mode != 2;   /* unless a beam reaches the band */
-    if (p.L > 1) {
-        bj.n_band = 1;
-        bj.band_win[0] = p.L;
-        bj.band_nx[0] = p.nxc;
-        bj.band_ny[0] = p.nyc;
-    }
+    /* Per-slice entry lists (row pairs for the pair-row fine kernel); L > 1: also the coarse level's
+     * lists and the edge-band flag. */
+    int bin()
     {
-        const size_t lds = bin_lds_bytes(p.tiles_x * p.tiles_y, p.n);
+        bj = bin_job(g, p, p.n_theta, p.n, p.max_tiles, hit_col, hit_row, ctx->sorted.as<uint32_t>(),
+                     ctx->tiles.as<TileRec>(), ctx->ntiles.as<int32_t>(), flags, p.fine.pairs ? 1 : 0);
+        bj.hash_size = bin_hash_size(p.n);
+        bj.max_mult = p.fine.weighted ? kMaxMult : 1;
+        bj.lstride = p.fine.lstride;
+        bj.sorted_rc = p.L > 1 ? ctx->sorted_rc.as<uint32_t>() : nullptr;
+        if (p.L > 1) {
+            bj.n_band = 1;
+            bj.band_win[0] = p.L;
+            bj.band_nx[0] = p.nxc;
+            bj.band_ny[0] = p.nyc;
+        }
         ScopedTimer tm(ctx, "bin");
-        if ((rc = launched_ok(ctx, csm_launch::bin(ctx->stream, ctx->device, p.n_theta, lds, bj), "binning"))) return rc;
+        return launched_ok(ctx, csm_launch::bin(ctx->stream, ctx->device, p.n_theta,
+                                                bin_lds_bytes(p.tiles_x * p.tiles_y, p.n), bj), "binning");
     }
-    if (p.L > 1 && tp_mode != 2) {
+
+    /* Joint entry lists of slice pairs, for score_joint. */
+    int bin_joint(const PassPlan& jp)
+    {
+        int rc;
+        const int n_pairs = (p.n_theta + 1) / 2;
+        const int max_tiles = std::min(2 * p.n, p.tiles_x * p.tiles_y) + 2 * p.n / kJRec + 1;
+        if ((rc = ensure(ctx, ctx->sorted, (size_t)n_pairs * 2 * p.n * 4 + 256))) return rc;
+        if ((rc = ensure(ctx, ctx->tiles, (size_t)n_pairs * max_tiles * sizeof(TileRec)))) return rc;
+        if ((rc = ensure(ctx, ctx->ntiles, (size_t)n_pairs * 8))) return rc;
+        bj = bin_job(g, p, p.n_theta, p.n, max_tiles, hit_col, hit_row, ctx->sorted.as<uint32_t>(),
+                     ctx->tiles.as<TileRec>(), ctx->ntiles.as<int32_t>(), flags, 2);
+        bj.hash_size = csm::binj_hash_size(p.n);
+        bj.max_mult = kMaxMult;
+        bj.lstride = jp.lstride;
+        const size_t lds = csm::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, bj.hash_size);
+        ScopedTimer tm(ctx, "bin");
+        return launched_ok(ctx, csm::launch_binj_one(ctx->stream, ctx->device, bj, n_pairs, lds), "joint binning");
+    }
+
+    /* The coarse level of an exhaustive window (L > 1), its sums into ctx->coarse_s / coarse_k. With
+     * `exits` it only runs when a beam reaches the edge band (rare). */
+    int coarse(bool exits)
+    {
         /* the coarse pass accumulates with atomics: its sums are cleared first, but
          * only when it is going to run (k_zero_if_band reads the band flag k_bin set) */
-        const ZeroJob zj = { ctx->coarse_s.as<uint32_t>(), ctx->coarse_k.as<uint32_t>(), nt * p.nxc * p.nyc, flags,
-                             coarse_exits ? 0 : 1, 0 };
+        const ZeroJob zj = { ctx->coarse_s.as<uint32_t>(), ctx->coarse_k.as<uint32_t>(),
+                             (size_t)p.n_theta * p.nxc * p.nyc, flags, exits ? 0 : 1, 0 };
         const int zb = (int)std::min<size_t>(256, (zj.words + 255) / 256);
-        if ((rc = launched_ok(ctx, csm_launch::zero_if_band(ctx->stream, std::max(1, zb), zj), "edge-band clear"))) return rc;
-    }
-
-    if (p.L > 1 && tp_mode != 2) {
+        if (int rc = launched_ok(ctx, csm_launch::zero_if_band(ctx->stream, std::max(1, zb), zj), "edge-band clear")) return rc;
         ScoreJob cj = score_job(g, g.levels[w->coarse_level].cells, p.L, bj, w->min_known);
         cj.sorted_pb = bj.sorted_rc;
-        cj.acc_s = reinterpret_cast<uint32_t*>(ctx->coarse_s.p);
-        cj.acc_k = reinterpret_cast<uint32_t*>(ctx->coarse_k.p);
+        cj.acc_s = ctx->coarse_s.as<uint32_t>();
+        cj.acc_k = ctx->coarse_k.as<uint32_t>();
         cj.rank_l = 1;
-        cj.skip_unless_band = coarse_exits;
-        const size_t nodes = nt * p.nxc * p.nyc;
-        (void)nodes;
+        cj.skip_unless_band = exits;
         ScopedTimer tm(ctx, "score_coarse");
-        /* few candidates per slice: split the tile list over blockIdx.z so
-         * enough workgroups are in flight to hide the staging latency -- unless
-         * the pass only runs when a beam reaches the edge band (rare): then one
-         * slice, so that the launch that normally exits at once stays small */
-        if ((rc = launch_score(ctx, cj, p.coarse, p.n_theta, coarse_exits ? 1 : kCoarseSlices)))
-            return rc;
+        /* few candidates per slice: split the tile list over blockIdx.z so enough workgroups are in flight
+         * to hide the staging latency -- unless the pass only runs when a beam reaches the edge band
+         * (rare): then one slice, so that the launch that normally exits at once stays small */
+        return launch_score(ctx, cj, p.coarse, p.n_theta, exits ? 1 : kCoarseSlices);
     }
 
-    const BlockBest* tp_reduced = nullptr;
-    ScoreJob fj = score_job(g, g.levels[0].cells, 1, bj, w->min_known);
-    fj.xg = g.xg.as<uint32_t>();
-    fj.xg_pitch = g.xg_pitch;
-    fj.xg_pad = g.xg_pad;
-    fj.block_best = reinterpret_cast<BlockBest*>(ctx->best.p);
-    (void)fine_slices;
-    fj.rank_l = p.L;
-    if (dumps) {
-        fj.dump_s = dumps->dump_s;
-        fj.dump_k = dumps->dump_k;
-    }
-    if (p.L > 1) {
-        fj.n_elig = 1;
-        fj.elig[0].k = reinterpret_cast<const uint32_t*>(ctx->coarse_k.p);
-        fj.elig[0].s = reinterpret_cast<const uint32_t*>(ctx->coarse_s.p);
-        fj.elig[0].div = p.L;
-        fj.elig[0].nxc = p.nxc;
-        fj.elig[0].nyc = p.nyc;
-        fj.elig_only_if_band = coarse_exits;
-        if (tp_mode == 2) {
-            fj.elig[0].k = tp->level_k;
-            fj.elig[0].s = tp->level_s;
-            fj.elig[0].nxc = tp->nxs;
-            fj.elig[0].nyc = tp->nys;
+    /* THE fine-level job over the entry lists of bj; the caller sets where its results go. L > 1: only
+     * candidates under an eligible node of `elig` (only_if_band: consulted only when a beam reaches the band). */
+    ScoreJob fine_job(const StoredLevel& elig, bool only_if_band) const
+    {
+        ScoreJob fj = score_job(g, g.levels[0].cells, 1, bj, w->min_known);
+        fj.xg = g.xg.as<uint32_t>();
+        fj.xg_pitch = g.xg_pitch;
+        fj.xg_pad = g.xg_pad;
+        fj.rank_l = p.L;
+        if (p.L > 1) {
+            fj.n_elig = 1;
+            fj.elig[0].k = elig.k;
+            fj.elig[0].s = elig.s;
+            fj.elig[0].div = p.L;
+            fj.elig[0].nxc = elig.nxs;
+            fj.elig[0].nyc = elig.nys;
+            fj.elig_only_if_band = only_if_band;
+        } else {
+            fj.check_own_known = 1;
         }
-    } else {
-        fj.check_own_known = 1;
+        return fj;
     }
-    if (tp_mode == 1) {
-        /* every candidate's sums, stored; no arg-max, no record */
-        fj.block_best = nullptr;
-        fj.check_own_known = 0;
-        fj.acc_s = reinterpret_cast<uint32_t*>(ctx->coarse_s.p);
-        fj.acc_k = reinterpret_cast<uint32_t*>(ctx->coarse_k.p);
-        fj.acc_x_major = 2;
-        tp->level_s = fj.acc_s;
-        tp->level_k = fj.acc_k;
-        tp->nxs = p.nx;
-        tp->nys = p.ny;
-        ScopedTimer tm(ctx, "score_coarse");
-        return launch_score(ctx, fj, p.fine, p.n_theta, 1);
-    }
-    if (tp_mode == 2) {
-        /* the blocks whose coarse bound reaches the best fine key under the best coarse node */
-        if (p.fine.ncb() > 4096 || (size_t)p.n_theta * tp->nxs * tp->nys >= (1u << 26) || p.n > 4096)
-            return fail(ctx, CSM_EINVAL, "internal: window too large for the two-phase work list");
-        const size_t n_blocks = nt * ncb;
-        if ((rc = ensure(ctx, ctx->tp_items, 64 + csm::kReducedBest * sizeof(BlockBest) + n_blocks * 5))) return rc;
-        unsigned long long* best2 = reinterpret_cast<unsigned long long*>(ctx->tp_items.p);
-        uint32_t* count = reinterpret_cast<uint32_t*>(best2 + 2);
-        BlockBest* reduced = reinterpret_cast<BlockBest*>(reinterpret_cast<char*>(ctx->tp_items.p) + 64);
-        uint32_t* items = reinterpret_cast<uint32_t*>(reduced + csm::kReducedBest);
-        unsigned char* keep = reinterpret_cast<unsigned char*>(items + n_blocks);
-        HIP_TRY(ctx, hipMemsetAsync(ctx->tp_items.p, 0, 64, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(keep, 0, n_blocks, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->best.p, 0, n_blocks * sizeof(BlockBest), ctx->stream));
-        csm::TwoPhaseJob J;
-        std::memset(&J, 0, sizeof(J));
-        J.coarse_s = tp->level_s;
-        J.coarse_k = tp->level_k;
-        J.n_theta = p.n_theta;
-        J.nxc = p.nxc;
-        J.nyc = p.nyc;
-        J.nxs = tp->nxs;
-        J.nys = tp->nys;
-        J.L = p.L;
-        J.min_known = w->min_known;
-        J.cells = g.levels[0].cells;
-        J.rows = g.rows;
-        J.cols = g.cols;
-        J.pitch = g.pitch;
-        J.hit_col = hit_col_dev;
-        J.hit_row = hit_row_dev;
-        J.n_points = p.n;
-        J.x_lo = p.x_lo;
-        J.y_lo = p.y_lo;
-        J.nx = p.nx;
-        J.ny = p.ny;
-        J.cbx = p.fine.cbx;
-        J.cby = p.fine.groups * p.fine.R;
-        J.ncbx = p.fine.ncbx;
-        J.ncb = ncb;
-        J.flags = flags;
-        J.best = best2;
-        J.items = items;
-        J.count = count;
-        J.keep = keep;
-        J.cap = (uint32_t)n_blocks;
-        {
-            ScopedTimer tm(ctx, "select");
-            int e = csm::launch_coarse_best(ctx->stream, J);
-            if (!e) e = csm::launch_fine_under_best(ctx->stream, J);
-            if (!e) e = csm::launch_mark_blocks(ctx->stream, J);
-            if (e)
-                return fail(ctx, CSM_EIO, "two-phase select launch failed: %s", hipGetErrorString((hipError_t)e));
-        }
-        {
-            ScopedTimer tm(ctx, "score_fine");
-            if ((rc = launch_score_list(ctx, fj, p.fine, items, count, (int)std::min<size_t>(n_blocks, 2048))))
-                return rc;
-        }
-        /* k_finalize reads kReducedBest records instead of one per block of the window */
-        if ((rc = launched_ok(ctx, csm::launch_reduce_items(ctx->stream, fj.block_best, items, count, (uint32_t)n_blocks,
-                                                            ncb, reduced), "record reduction")))
-            return rc;
-        tp_reduced = reduced;
-        ctx->tp_count_dev = count;
-        ctx->tp_blocks_total = (int64_t)n_blocks;
-    }
-    if (tp_mode == 2) {
-        /* launched above */
-    } else if (fine_slices > 1) {
-        /* small windows: too few workgroups to fill the chip, so the tile list
-         * is split over blockIdx.z, the slices add their exact integer sums
-         * with atomics, and a second pass does the arg-max */
+
+    /* Small windows: too few workgroups to fill the chip, so the tile list is split over blockIdx.z,
+     * the slices add their exact integer sums with atomics, and a second pass does the arg-max. */
+    int score_tile_split(const ScoreJob& fj, int fine_slices)
+    {
+        int rc;
         ScoreJob sj = fj;
         sj.block_best = nullptr;
         sj.dump_s = nullptr;
         sj.dump_k = nullptr;
-        sj.acc_s = reinterpret_cast<uint32_t*>(ctx->fine_s.p);
-        sj.acc_k = reinterpret_cast<uint32_t*>(ctx->fine_k.p);
+        sj.acc_s = ctx->fine_s.as<uint32_t>();
+        sj.acc_k = ctx->fine_k.as<uint32_t>();
         sj.acc_x_major = 1;
         ctx->fine_acc_dirty = true;
         {
@@ -324,28 +228,163 @@ int run_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
         if ((rc = launch_argmax(ctx, aj, p.fine, p.n_theta)))
             return rc;
         ctx->fine_acc_dirty = false;
+        return CSM_OK;
+    }
+
+    /* The work list (J.items, J.count of J.cap): the blocks whose coarse bound reaches the best fine key under
+     * the best coarse node. ctx->tp_items = [best pair | count | pad to 64][*reduced records][items][keep bytes]. */
+    int select_blocks(const StoredLevel& level, csm::TwoPhaseJob& J, BlockBest** reduced)
+    {
+        const size_t n_blocks = (size_t)p.n_theta * p.fine.ncb();
+        if (int rc = ensure(ctx, ctx->tp_items, 64 + csm::kReducedBest * sizeof(BlockBest) + n_blocks * 5))
+            return rc;
+        std::memset(&J, 0, sizeof(J));
+        J.best = ctx->tp_items.as<unsigned long long>();
+        J.count = reinterpret_cast<uint32_t*>(J.best + 2);
+        *reduced = reinterpret_cast<BlockBest*>(ctx->tp_items.as<char>() + 64);
+        J.items = reinterpret_cast<uint32_t*>(*reduced + csm::kReducedBest);
+        J.keep = reinterpret_cast<unsigned char*>(J.items + n_blocks);
+        J.cap = (uint32_t)n_blocks;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->tp_items.p, 0, 64, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(J.keep, 0, n_blocks, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->best.p, 0, n_blocks * sizeof(BlockBest), ctx->stream));
+        J.coarse_s = level.s;
+        J.coarse_k = level.k;
+        J.n_theta = p.n_theta;
+        J.nxc = p.nxc;
+        J.nyc = p.nyc;
+        J.nxs = level.nxs;
+        J.nys = level.nys;
+        J.L = p.L;
+        J.min_known = w->min_known;
+        J.cells = g.levels[0].cells;
+        J.rows = g.rows;
+        J.cols = g.cols;
+        J.pitch = g.pitch;
+        J.hit_col = hit_col;
+        J.hit_row = hit_row;
+        J.n_points = p.n;
+        J.x_lo = p.x_lo;
+        J.y_lo = p.y_lo;
+        J.nx = p.nx;
+        J.ny = p.ny;
+        J.cbx = p.fine.cbx;
+        J.cby = p.fine.groups * p.fine.R;
+        J.ncbx = p.fine.ncbx;
+        J.ncb = p.fine.ncb();
+        J.flags = flags;
+        ScopedTimer tm(ctx, "select");
+        int e = csm::launch_coarse_best(ctx->stream, J);
+        if (!e) e = csm::launch_fine_under_best(ctx->stream, J);
+        if (!e) e = csm::launch_mark_blocks(ctx->stream, J);
+        if (e)
+            return fail(ctx, CSM_EIO, "two-phase select launch failed: %s", hipGetErrorString((hipError_t)e));
+        return CSM_OK;
+    }
+
+    /* The window's record from n_records block records of the fine job; clears the next chain's flag word. */
+    int finalize(const ScoreJob& fj, const BlockBest* records, int n_records, csm_result* out_dev)
+    {
+        FinalJob fin = final_job(fj, n_records, hit_col, hit_row, w->score_threshold, ctx->lut_dev.as<double>(), out_dev);
+        fin.block_best = records;
+        fin.flags_clear = flags_next;
+        ScopedTimer tm(ctx, "finalize");
+        return launched_ok(ctx, csm_launch::finalize(ctx->stream, ctx->device, (size_t)p.n * 8, fin), "finalize");
+    }
+};
+
+/* The exhaustive chain: every candidate at the fine level (L > 1: under an eligible node of the coarse
+ * level, scored first). force_coarse: the coarse level always runs (csm_score_window_dump reads its sums). */
+int run_exhaustive(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p, const int32_t* hit_col,
+                   const int32_t* hit_row, csm_result* out_dev, uint32_t* dump_s = nullptr,
+                   uint16_t* dump_k = nullptr, bool force_coarse = false)
+{
+    WindowRun r = { ctx, g, w, p, hit_col, hit_row };
+    int rc, fine_slices = 1;
+    if ((rc = r.workspaces())) return rc;
+    if ((rc = tile_split_slices(ctx, p, &fine_slices))) return rc;
+    if ((rc = r.take_flags(true))) return rc;
+    if ((rc = r.bin())) return rc;
+    const bool coarse_exits = w->min_known <= 1 && !force_coarse;   /* unless a beam reaches the band */
+    if (p.L > 1 && (rc = r.coarse(coarse_exits))) return rc;
+    ScoreJob fj = r.fine_job({ ctx->coarse_s.as<uint32_t>(), ctx->coarse_k.as<uint32_t>(), p.nxc, p.nyc }, coarse_exits);
+    fj.block_best = ctx->best.as<BlockBest>();
+    fj.dump_s = dump_s;
+    fj.dump_k = dump_k;
+    if (fine_slices > 1) {
+        if ((rc = r.score_tile_split(fj, fine_slices))) return rc;
     } else {
         ScopedTimer tm(ctx, "score_fine");
-        if ((rc = launch_score(ctx, fj, p.fine, p.n_theta, 1)))
-            return rc;
+        if ((rc = launch_score(ctx, fj, p.fine, p.n_theta, 1))) return rc;
     }
-    ctx->last_fine = fj;
-
-    FinalJob fin = final_job(fj, p.n_theta * ncb, hit_col_dev, hit_row_dev, w->score_threshold,
-                             ctx->lut_dev.as<double>(), out_dev);
-    if (tp_reduced) {
-        fin.block_best = tp_reduced;
-        fin.n_entries = csm::kReducedBest;
-    }
-    fin.flags_clear = flags_next;
-    {
-        const size_t lds = (size_t)p.n * 8;
-        ScopedTimer tm(ctx, "finalize");
-        if ((rc = launched_ok(ctx, csm_launch::finalize(ctx->stream, ctx->device, lds, fin), "finalize"))) return rc;
-    }
-    return CSM_OK;
+    ctx->last_run.fine = fj;
+    return r.finalize(fj, fj.block_best, p.n_theta * p.fine.ncb(), out_dev);
 }
 
+/* The level pass: the window (one of L = 1, on a phase-major copy) scored and every candidate's
+ * sums STORED as *level in ctx->coarse_s / coarse_k; no arg-max, no record, so no flag to pass on. */
+int run_level_pass(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p, const int32_t* hit_col,
+                   const int32_t* hit_row, StoredLevel* level)
+{
+    WindowRun r = { ctx, g, w, p, hit_col, hit_row };
+    int rc;
+    PassPlan jp;
+    if ((rc = r.workspaces())) return rc;
+    if ((rc = r.take_flags(false))) return rc;
+    const bool joint = joint_level_plan(ctx, p, &jp);
+    if ((rc = joint ? r.bin_joint(jp) : r.bin())) return rc;
+    *level = { ctx->coarse_s.as<uint32_t>(), ctx->coarse_k.as<uint32_t>(), p.nx, p.ny };
+    ScoreJob fj = r.fine_job(StoredLevel(), false);
+    fj.joint = joint;
+    fj.check_own_known = 0;
+    fj.acc_s = level->s;
+    fj.acc_k = level->k;
+    fj.acc_x_major = 2;
+    const uint16_t* lane_map = nullptr;
+    if (joint && (rc = lane_map_for(ctx, jp, &lane_map))) return rc;
+    ScopedTimer tm(ctx, "score_coarse");
+    if (!joint)
+        return launch_score(ctx, fj, p.fine, p.n_theta, 1);
+    csm::JointLaunch L = joint_launch(ctx, jp, dim3(jp.ncb(), 1, 1), lane_map);
+    L.ncb = jp.ncb();
+    return launched_ok(ctx, csm::launch_joint_one(L, fj, (p.n_theta + 1) / 2), "joint level pass");
+}
+
+/* The fine level of a large window (L > 1) under a stored level: eligibility from the level's
+ * sums, only the blocks of the work list scored, the record from kReducedBest reduced records. */
+int run_fine_under_level(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p, const int32_t* hit_col,
+                         const int32_t* hit_row, const StoredLevel& level, csm_result* out_dev)
+{
+    WindowRun r = { ctx, g, w, p, hit_col, hit_row };
+    int rc;
+    csm::TwoPhaseJob list;
+    BlockBest* reduced = nullptr;
+    if ((rc = r.workspaces())) return rc;
+    if ((rc = r.take_flags(true))) return rc;
+    if ((rc = r.bin())) return rc;
+    ScoreJob fj = r.fine_job(level, false);
+    fj.block_best = ctx->best.as<BlockBest>();
+    if (p.fine.ncb() > 4096 || (size_t)p.n_theta * level.nxs * level.nys >= (1u << 26) || p.n > 4096)
+        return fail(ctx, CSM_EINVAL, "internal: window too large for the two-phase work list");
+    if ((rc = r.select_blocks(level, list, &reduced))) return rc;
+    {
+        ScopedTimer tm(ctx, "score_fine");
+        if ((rc = launch_score_list(ctx, fj, p.fine, list.items, list.count, (int)std::min<uint32_t>(list.cap, 2048))))
+            return rc;
+    }
+    /* k_finalize reads kReducedBest records instead of one per block of the window */
+    if ((rc = launched_ok(ctx, csm::launch_reduce_items(ctx->stream, fj.block_best, list.items, list.count,
+                                                        list.cap, p.fine.ncb(), reduced),
+                          "record reduction")))
+        return rc;
+    ctx->last_run.fine = fj;
+    ctx->last_run.coarse_nodes = (int64_t)p.n_theta * p.nxc * p.nyc;
+    ctx->last_run.fine_candidates = -1;           /* from the device counters, on request (csm_last_search_info) */
+    ctx->last_run.kept_dev = list.count;
+    ctx->last_run.blocks_total = (int64_t)list.cap;
+    ctx->last_run.block_candidates = (int64_t)p.fine.cbx * p.fine.groups * p.fine.R;
+    return r.finalize(fj, reduced, csm::kReducedBest, out_dev);
+}
 
 /* The phase-major copy of box-max level `level` of g for coarse windows of up to `need` candidates
  * per axis (its zero padding), built on first use and whenever the level changed. */
@@ -406,16 +445,24 @@ bool wants_two_phase(const csm_ctx* ctx, const Plan& p)
     return ctx->tune.two_phase > 0 || (double)p.n_theta * p.nx * p.ny >= 3.0e7;
 }
 
-/* One window, device-resident hit indices: exhaustive (run_window) or coarse-first. */
+/* ctx->last_run of an exhaustive search of the window (its fine job: set by the chain, or restored
+ * from the recorded graph). */
+void note_exhaustive_search(csm_ctx* ctx, const Plan& p)
+{
+    ctx->last_run.nominal = (int64_t)p.n_theta * p.nx * p.ny;
+    ctx->last_run.coarse_nodes = 0;
+    ctx->last_run.fine_candidates = ctx->last_run.nominal;
+    ctx->last_run.kept_dev = nullptr;
+}
+
+/* One window, device-resident hit indices: exhaustive, or coarse-first (the level pass on the
+ * phase-major copy of the coarse level, then the fine level under what it stored). */
 int search_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p, const int32_t* col_dev,
                   const int32_t* row_dev, csm_result* out_dev)
 {
-    ctx->last_nominal = (int64_t)p.n_theta * p.nx * p.ny;
-    ctx->last_coarse_nodes = 0;
-    ctx->last_fine_candidates = ctx->last_nominal;
-    ctx->tp_count_dev = nullptr;
+    note_exhaustive_search(ctx, p);
     if (!wants_two_phase(ctx, p))
-        return run_window(ctx, g, w, p, col_dev, row_dev, out_dev, nullptr);
+        return run_exhaustive(ctx, g, w, p, col_dev, row_dev, out_dev);
     int rc;
     PhaseMap* pm = nullptr;
     if ((rc = ensure_phase_map(ctx, g, w->coarse_level, std::max(p.nxc, p.nyc) + 1, &pm))) return rc;
@@ -439,15 +486,9 @@ int search_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& 
         if (e)
             return fail(ctx, CSM_EIO, "k_phase_hits launch failed: %s", hipGetErrorString((hipError_t)e));
     }
-    TwoPhaseCtl tp;
-    tp.mode = 1;
-    if ((rc = run_window(ctx, *pm->grid, &wc, pc, pcol, prow, nullptr, nullptr, false, &tp))) return rc;
-    tp.mode = 2;
-    if ((rc = run_window(ctx, g, w, p, col_dev, row_dev, out_dev, nullptr, false, &tp))) return rc;
-    ctx->last_coarse_nodes = (int64_t)p.n_theta * p.nxc * p.nyc;
-    ctx->last_fine_candidates = -1;         /* from the device counters, on request (csm_last_search_info) */
-    ctx->last_block_candidates = (int64_t)p.fine.cbx * p.fine.groups * p.fine.R;
-    return CSM_OK;
+    StoredLevel level;
+    if ((rc = run_level_pass(ctx, *pm->grid, &wc, pc, pcol, prow, &level))) return rc;
+    return run_fine_under_level(ctx, g, w, p, col_dev, row_dev, level, out_dev);
 }
 
 const uint32_t kTieCap = 1u << 16;
@@ -464,7 +505,7 @@ int resolve_ties(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p
     double* score = reinterpret_cast<double*>(list + kTieCap);
     uint32_t* count = reinterpret_cast<uint32_t*>(score + kTieCap);
     HIP_TRY(ctx, hipMemsetAsync(count, 0, 4, ctx->stream));
-    ScoreJob cj = ctx->last_fine;
+    ScoreJob cj = ctx->last_run.fine;
     cj.block_best = nullptr;
     cj.dump_s = nullptr;
     cj.dump_k = nullptr;
@@ -520,41 +561,20 @@ int resolve_literal(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan
     if ((rc = ensure(ctx, ctx->ex_fine_k, nf * 4))) return rc;
     if ((rc = ensure(ctx, ctx->ex_coarse, nc * 8))) return rc;
     if ((rc = ensure(ctx, ctx->ex_coarse_k, nc * 4))) return rc;
-    ExactJob ej;
-    std::memset(&ej, 0, sizeof(ej));
-    ej.rows = g.rows;
-    ej.cols = g.cols;
-    ej.pitch = g.pitch;
-    ej.hit_col = col_dev;
-    ej.hit_row = row_dev;
-    ej.n_theta = p.n_theta;
-    ej.n_points = p.n;
-    ej.x_lo = p.x_lo;
-    ej.y_lo = p.y_lo;
-    ej.lut = ctx->lut_dev.as<double>();
-    ExactJob cj = ej;
-    cj.cells = g.levels[w->coarse_level].cells;
-    cj.nx = p.nxc;
-    cj.ny = p.nyc;
-    cj.stride = p.L;
-    cj.out_score = reinterpret_cast<double*>(ctx->ex_coarse.p);
-    cj.out_k = reinterpret_cast<uint32_t*>(ctx->ex_coarse_k.p);
-    if (int e = csm_launch::exact_scores(ctx->stream, (unsigned)((nc + kBlock - 1) / kBlock), cj))
-        return launched_ok(ctx, e, "exact score");
-    ExactJob fj = ej;
-    fj.cells = g.levels[0].cells;
-    fj.nx = p.nx;
-    fj.ny = p.ny;
-    fj.stride = 1;
-    fj.out_score = reinterpret_cast<double*>(ctx->ex_fine.p);
-    fj.out_k = reinterpret_cast<uint32_t*>(ctx->ex_fine_k.p);
-    if (int e = csm_launch::exact_scores(ctx->stream, (unsigned)((nf + kBlock - 1) / kBlock), fj))
-        return launched_ok(ctx, e, "exact score");
+    auto exact = [&](const uint16_t* cells, int nx, int ny, int stride, size_t n, DevBuf& score, DevBuf& known) {
+        ExactJob j = exact_job(g, cells, p.n_theta, p.n, p.x_lo, p.y_lo, nx, ny, stride, ctx->lut_dev.as<double>(),
+                               score.as<double>(), known.as<uint32_t>());
+        j.hit_col = col_dev;
+        j.hit_row = row_dev;
+        return launched_ok(ctx, csm_launch::exact_scores(ctx->stream, (unsigned)((n + kBlock - 1) / kBlock), j), "exact score");
+    };
+    if ((rc = exact(g.levels[w->coarse_level].cells, p.nxc, p.nyc, p.L, nc, ctx->ex_coarse, ctx->ex_coarse_k))) return rc;
+    if ((rc = exact(g.levels[0].cells, p.nx, p.ny, 1, nf, ctx->ex_fine, ctx->ex_fine_k))) return rc;
     LiteralJob lj;
     std::memset(&lj, 0, sizeof(lj));
-    lj.coarse_score = cj.out_score;
-    lj.coarse_k = cj.out_k;
-    lj.fine_score = fj.out_score;
+    lj.coarse_score = ctx->ex_coarse.as<double>();
+    lj.coarse_k = ctx->ex_coarse_k.as<uint32_t>();
+    lj.fine_score = ctx->ex_fine.as<double>();
     lj.n_theta = p.n_theta;
     lj.nxc = p.nxc;
     lj.nyc = p.nyc;
@@ -571,7 +591,7 @@ int resolve_literal(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan
 /* Finish a window whose fast-path record carries a tie or an edge-band flag. */
 int resolve_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& p,
                    const int32_t* col_dev, const int32_t* row_dev, csm_result* out_dev,
-                   const csm_result* have, bool* changed)
+                   const csm_result* have = nullptr, bool* changed = nullptr)
 {   /* have: the record as already read back by the caller (saves a copy and a wait per query) */
     csm_result r;
     if (have) {
@@ -593,7 +613,176 @@ int resolve_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan&
     return CSM_OK;
 }
 
-} /* namespace csm_host */
+/* result record and the uncertified-entry count sit side by side: one read-back */
+struct Tail {
+    csm_result res;
+    uint32_t n_unc, pad[3];
+};
+
+/* Where one query's data lives. Up from `pin` to `dev` in one copy of up_bytes: [projection job, padded to
+ * job_bytes | angles | ranges]; back into the pinned block: the Tail behind the hit indices of ctx->hits. */
+struct QueryBlock {
+    int n = 0;                  /* beams */
+    size_t hn = 0;              /* hit indices per axis: n_theta * n */
+    size_t job_bytes = 0, up_bytes = 0;
+    char *pin = nullptr, *dev = nullptr;
+    double *ang_dev = nullptr, *rng_dev = nullptr;
+    int32_t *col_dev = nullptr, *row_dev = nullptr;     /* ctx->hits */
+    Tail *tail_dev = nullptr, *tail_pin = nullptr;
+    uint32_t* unc_list = nullptr;       /* device: indices of the entries the projection could not certify */
+};
+
+int query_block(csm_ctx* ctx, int n_theta, int n, QueryBlock* q)
+{
+    int rc;
+    q->n = n;
+    q->hn = (size_t)n_theta * n;
+    if ((rc = ensure(ctx, ctx->hits, q->hn * 8 + 256))) return rc;
+    if ((rc = ensure(ctx, ctx->unc, 16 + (size_t)kUncCap * 4))) return rc;
+    q->job_bytes = (sizeof(ProjJob) + 255) & ~(size_t)255;
+    q->up_bytes = q->job_bytes + (size_t)n * 16;
+    const size_t pin_bytes = q->up_bytes + 256;
+    if ((rc = grow(ctx, ctx->q_pin, pin_bytes, pin_bytes + pin_bytes / 4, true))) return rc;
+    if ((rc = ensure(ctx, ctx->q_dev, q->up_bytes))) return rc;
+    q->pin = ctx->q_pin.as<char>();
+    q->dev = ctx->q_dev.as<char>();
+    q->ang_dev = reinterpret_cast<double*>(q->dev + q->job_bytes);
+    q->rng_dev = q->ang_dev + n;
+    q->col_dev = ctx->hits.as<int32_t>();
+    q->row_dev = q->col_dev + q->hn;
+    q->tail_dev = reinterpret_cast<Tail*>(q->row_dev + q->hn);
+    q->tail_pin = reinterpret_cast<Tail*>(q->pin + ((q->up_bytes + 63) & ~(size_t)63));
+    q->unc_list = ctx->unc.as<uint32_t>() + 4;
+    return CSM_OK;
+}
+
+/* One query's stream work: [projection job | angles | ranges] up from the pinned block, the
+ * projection, the search, [record | uncertified count] back into the pinned block. The same
+ * sequence for every query of one launch shape, so from the third query of a shape on it is
+ * replayed as a HIP graph (one launch instead of nine; every varying input lives in the pinned
+ * block or in device memory the nodes point at). */
+int enqueue_query(csm_ctx* ctx, DeviceGrid& g, const csm_window& w, const Plan& p, const QueryBlock& q)
+{
+    HIP_TRY(ctx, hipMemcpyAsync(q.dev, q.pin, q.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(&q.tail_dev->n_unc, 0, 16, ctx->stream));
+    {
+        ScopedTimer tm(ctx, "project");
+        const int pb = ceil_div(q.n, kBlock);
+        if (int e = csm_launch::project_batch(ctx->stream, dim3(pb, proj_theta_groups(w.n_theta, pb), 1),
+                                              reinterpret_cast<const ProjJob*>(q.dev)))
+            return launched_ok(ctx, e, "projection");
+    }
+    if (int rc = search_window(ctx, g, &w, p, q.col_dev, q.row_dev, &q.tail_dev->res))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(q.tail_pin, q.tail_dev, sizeof(Tail), hipMemcpyDeviceToHost, ctx->stream));
+    return CSM_OK;
+}
+
+/* What a graph of the query's chain has baked in. */
+std::vector<uint64_t> graph_key(const csm_ctx* ctx, const DeviceGrid& g, int level, const csm_window& w, int n)
+{
+    std::vector<uint64_t> key = {
+        ctx->alloc_epoch, (uint64_t)(uintptr_t)ctx->stream, (uint64_t)(uintptr_t)g.levels[0].cells,
+        (uint64_t)(uintptr_t)g.levels[level].cells, (uint64_t)(uintptr_t)g.xg.p, (uint64_t)g.xg_pad,
+        (uint64_t)g.rows, (uint64_t)g.cols, (uint64_t)g.known_r0, (uint64_t)g.known_c0,
+        (uint64_t)w.n_theta, (uint64_t)n, (uint64_t)w.win_x, (uint64_t)w.win_y, (uint64_t)w.low_resolution,
+        (uint64_t)(uint32_t)w.min_known, (uint64_t)w.merge_mode, 0 };
+    std::memcpy(&key.back(), &w.score_threshold, 8);
+    return key;
+}
+
+/* Launches the recorded chain of `key`, if there is one (*launched). */
+int replay_graph(csm_ctx* ctx, const std::vector<uint64_t>& key, const Plan& p, bool* launched)
+{
+    auto it = ctx->graphs.find(key);
+    if (it == ctx->graphs.end())
+        return CSM_OK;
+    HIP_TRY(ctx, hipGraphLaunch(it->second.exec, ctx->stream));
+    note_exhaustive_search(ctx, p);
+    /* no driver ran: the tie pass must see the job this chain was recorded with (its map, plan and
+     * flag word), not that of the last plain launch */
+    ctx->last_run.fine = it->second.fine;
+    ctx->last_graph_replayed = true;
+    *launched = true;
+    return CSM_OK;
+}
+
+/* A sighting of a shape without a graph. The third: every workspace has its size, so the chain is captured,
+ * kept and launched (a failed capture leaves the plain launch to the caller); at eight graphs all are dropped first. */
+int record_graph(csm_ctx* ctx, const std::vector<uint64_t>& key, DeviceGrid& g, const csm_window& w, const Plan& p,
+                 const QueryBlock& q, bool* launched)
+{
+    if (++ctx->graph_seen[key] < 3)
+        return CSM_OK;
+    if (ctx->graphs.size() >= 8) {
+        for (auto& kv : ctx->graphs)
+            (void)hipGraphExecDestroy(kv.second.exec);
+        ctx->graphs.clear();
+        ctx->graph_seen.clear();
+    }
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed) != hipSuccess)
+        return CSM_OK;
+    ctx->capturing = true;
+    const int rc_cap = enqueue_query(ctx, g, w, p, q);
+    ctx->capturing = false;
+    const hipError_t e_end = hipStreamEndCapture(ctx->stream, &graph);
+    if (rc_cap == CSM_OK && e_end == hipSuccess && graph &&
+        hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+        ctx->graphs[key] = { exec, ctx->last_run.fine };   /* last_run.fine: set while capturing */
+        HIP_TRY(ctx, hipGraphLaunch(exec, ctx->stream));
+        *launched = true;
+    }
+    if (graph)
+        (void)hipGraphDestroy(graph);
+    (void)hipGetLastError();
+    return CSM_OK;
+}
+
+/* The n_unc hit indices the device projection could not certify (listed up to kUncCap) recomputed exactly as
+ * the reference does, with glibc. *patched: some entry differed and the corrected indices are on the device. */
+int patch_uncertified(csm_ctx* ctx, const csm_geometry* geom, const csm_scan* scan, const csm_summary* out,
+                      const QueryBlock& q, uint32_t n_unc, bool* patched)
+{
+    const size_t hn = q.hn;
+    std::vector<int32_t> col(hn), row(hn);
+    HIP_TRY(ctx, hipMemcpy(col.data(), q.col_dev, hn * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(row.data(), q.row_dev, hn * 4, hipMemcpyDeviceToHost));
+    *patched = false;
+    if (n_unc > kUncCap) {
+        std::vector<int32_t> c2(hn), r2(hn);
+        csm_host_project(geom, out->sensor_pose, out->step_theta, out->win_theta, scan->angles,
+                         scan->ranges, q.n, c2.data(), r2.data(), nullptr, nullptr);
+        *patched = c2 != col || r2 != row;
+        col.swap(c2);
+        row.swap(r2);
+    } else {
+        std::vector<uint32_t> list(n_unc);
+        HIP_TRY(ctx, hipMemcpy(list.data(), q.unc_list, (size_t)n_unc * 4, hipMemcpyDeviceToHost));
+        for (uint32_t idx : list) {
+            const int t = (int)(idx / (uint32_t)q.n) - out->win_theta;
+            const int i = (int)(idx % (uint32_t)q.n);
+            const double theta = out->sensor_pose[2] + out->step_theta * t;
+            const double hx = out->sensor_pose[0] + scan->ranges[i] * std::cos(theta + scan->angles[i]);
+            const double hy = out->sensor_pose[1] + scan->ranges[i] * std::sin(theta + scan->angles[i]);
+            const int32_t c = static_cast<int>(std::floor((hx - geom->offset_x) / geom->resolution));
+            const int32_t r = static_cast<int>(std::floor((hy - geom->offset_y) / geom->resolution));
+            if (c != col[idx] || r != row[idx]) {
+                col[idx] = c;
+                row[idx] = r;
+                *patched = true;
+            }
+        }
+    }
+    if (*patched) {
+        HIP_TRY(ctx, hipMemcpy(q.col_dev, col.data(), hn * 4, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(q.row_dev, row.data(), hn * 4, hipMemcpyHostToDevice));
+    }
+    return CSM_OK;
+}
+
+} /* namespace */
 
 extern "C" {
 
@@ -610,7 +799,7 @@ int csm_score_window_dev(csm_ctx* ctx, uint64_t map_id, const csm_window* w,
     int rc = make_plan(ctx, *g, w, &p);
     if (rc)
         return rc;
-    return run_window(ctx, *g, w, p, hit_col_dev, hit_row_dev, out_dev, nullptr);
+    return run_exhaustive(ctx, *g, w, p, hit_col_dev, hit_row_dev, out_dev);
 }
 
 int csm_resolve_window_dev(csm_ctx* ctx, uint64_t map_id, const csm_window* w,
@@ -650,27 +839,20 @@ int csm_score_window_dump(csm_ctx* ctx, uint64_t map_id, const csm_window* w, co
     csm_result* res_dev = reinterpret_cast<csm_result*>(row_dev + hn);
     HIP_TRY(ctx, hipMemcpyAsync(col_dev, hit_col, hn * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(row_dev, hit_row, hn * 4, hipMemcpyHostToDevice, ctx->stream));
-    WindowOutputs dumps;
     const size_t nc = (size_t)p.n_theta * p.nx * p.ny;
-    if (dump_s) {
-        if ((rc = ensure(ctx, ctx->dump_s, nc * 4))) return rc;
-        dumps.dump_s = reinterpret_cast<uint32_t*>(ctx->dump_s.p);
-    }
-    if (dump_k) {
-        if ((rc = ensure(ctx, ctx->dump_k, nc * 2))) return rc;
-        dumps.dump_k = reinterpret_cast<uint16_t*>(ctx->dump_k.p);
-    }
-    rc = run_window(ctx, *g, w, p, col_dev, row_dev, res_dev, (dump_s || dump_k) ? &dumps : nullptr,
-                    dump_coarse_k != nullptr);
-    if (rc)
+    if (dump_s && (rc = ensure(ctx, ctx->dump_s, nc * 4))) return rc;
+    if (dump_k && (rc = ensure(ctx, ctx->dump_k, nc * 2))) return rc;
+    uint32_t* dump_s_dev = dump_s ? ctx->dump_s.as<uint32_t>() : nullptr;
+    uint16_t* dump_k_dev = dump_k ? ctx->dump_k.as<uint16_t>() : nullptr;
+    if ((rc = run_exhaustive(ctx, *g, w, p, col_dev, row_dev, res_dev, dump_s_dev, dump_k_dev, dump_coarse_k != nullptr)))
         return rc;
     if ((rc = resolve_window(ctx, *g, w, p, col_dev, row_dev, res_dev)))
         return rc;
     HIP_TRY(ctx, hipMemcpyAsync(out, res_dev, sizeof(csm_result), hipMemcpyDeviceToHost, ctx->stream));
     if (dump_s)
-        HIP_TRY(ctx, hipMemcpyAsync(dump_s, dumps.dump_s, nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(dump_s, dump_s_dev, nc * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (dump_k)
-        HIP_TRY(ctx, hipMemcpyAsync(dump_k, dumps.dump_k, nc * 2, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(dump_k, dump_k_dev, nc * 2, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<uint32_t> ck32;
     if (dump_coarse_k && p.L > 1) {
         ck32.resize((size_t)p.n_theta * p.nxc * p.nyc);
@@ -712,14 +894,12 @@ int csm_correlative_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
      * input_setup_us is the host side of the set-up */
     const auto t1 = std::chrono::steady_clock::now();
 
-    /* scan_matcher_correlative.cpp:130-146 */
     csm_host_compound(initial_pose, scan->relative_sensor_pose, out->sensor_pose);
     csm_host_search_step(geom->resolution, scan->ranges, scan->n_points, &out->step_x,
                          &out->step_y, &out->step_theta);
     out->win_x = csm_host_window(prm->range_x, out->step_x);
     out->win_y = csm_host_window(prm->range_y, out->step_y);
     out->win_theta = csm_host_window(prm->range_theta, out->step_theta);
-
     csm_window w;
     std::memset(&w, 0, sizeof(w));
     w.n_theta = 2 * out->win_theta + 1;
@@ -731,168 +911,46 @@ int csm_correlative_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
     w.min_known = csm_host_min_known(scan->n_points, prm->known_rate_threshold);
     w.score_threshold = prm->score_threshold;
     w.merge_mode = merging_pays(scan->angles, scan->ranges, scan->n_points, geom->resolution) ? 0 : 1;
-
     /* Projection on the device with a per-entry certificate; the host
      * recomputes (glibc) only the entries that could not be certified. */
-    const size_t hn = (size_t)w.n_theta * w.n_points;
     const int n = scan->n_points;
     Plan p;
+    QueryBlock q;
     if ((rc = make_plan(ctx, *g, &w, &p))) return rc;
-    if ((rc = ensure(ctx, ctx->hits, hn * 8 + 256))) return rc;
-    if ((rc = ensure(ctx, ctx->unc, 16 + (size_t)kUncCap * 4))) return rc;
-    int32_t* col_dev = reinterpret_cast<int32_t*>(ctx->hits.p);
-    int32_t* row_dev = col_dev + hn;
-    /* result record and the uncertified-entry count sit side by side: one read-back */
-    struct Tail {
-        csm_result res;
-        uint32_t n_unc, pad[3];
-    };
-    Tail* tail_dev = reinterpret_cast<Tail*>(row_dev + hn);
-    csm_result* res_dev = &tail_dev->res;
-    uint32_t* unc_count = &tail_dev->n_unc;
-    uint32_t* unc_list = reinterpret_cast<uint32_t*>(ctx->unc.p) + 4;
-    /* One query's stream work: [projection job | angles | ranges] up from a pinned block, the
-     * projection, the search, [record | uncertified count] back into the pinned block. The same
-     * sequence for every query of one launch shape, so from the third query of a shape on it is
-     * replayed as a HIP graph (one launch instead of nine; every varying input lives in the pinned
-     * block or in device memory the nodes point at). */
-    const size_t job_bytes = (sizeof(ProjJob) + 255) & ~(size_t)255;
-    const size_t up_bytes = job_bytes + (size_t)n * 16;
-    const size_t pin_bytes = up_bytes + 256;
-    if ((rc = grow(ctx, ctx->q_pin, pin_bytes, pin_bytes + pin_bytes / 4, true))) return rc;
-    if ((rc = ensure(ctx, ctx->q_dev, up_bytes))) return rc;
-    char* pin = ctx->q_pin.as<char>();
-    char* qd = reinterpret_cast<char*>(ctx->q_dev.p);
-    double* ang_dev = reinterpret_cast<double*>(qd + job_bytes);
-    double* rng_dev = ang_dev + n;
-    Tail* tail_pin = reinterpret_cast<Tail*>(pin + ((up_bytes + 63) & ~(size_t)63));
-    ProjJob pj = proj_job(*geom, out->sensor_pose, out->step_theta, out->win_theta, n, ang_dev, rng_dev, col_dev,
-                          row_dev);
-    pj.unc_count = unc_count;
-    pj.unc_list = unc_list;
+    if ((rc = query_block(ctx, w.n_theta, n, &q))) return rc;
+    ProjJob pj = proj_job(*geom, out->sensor_pose, out->step_theta, out->win_theta, n, q.ang_dev, q.rng_dev, q.col_dev,
+                          q.row_dev);
+    pj.unc_count = &q.tail_dev->n_unc;
+    pj.unc_list = q.unc_list;
     pj.unc_cap = kUncCap;
-    std::memcpy(pin, &pj, sizeof(pj));
-    std::memcpy(pin + job_bytes, scan->angles, (size_t)n * 8);
-    std::memcpy(pin + job_bytes + (size_t)n * 8, scan->ranges, (size_t)n * 8);
-    const bool two_phase = wants_two_phase(ctx, p);
-    auto enqueue = [&]() -> int {
-        HIP_TRY(ctx, hipMemcpyAsync(qd, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(unc_count, 0, 16, ctx->stream));
-        {
-            ScopedTimer tm(ctx, "project");
-            const int pb = ceil_div(n, kBlock);
-            if (int e = csm_launch::project_batch(ctx->stream, dim3(pb, proj_theta_groups(w.n_theta, pb), 1),
-                                                  reinterpret_cast<const ProjJob*>(qd)))
-                return launched_ok(ctx, e, "projection");
-        }
-        int rc2 = search_window(ctx, *g, &w, p, col_dev, row_dev, res_dev);
-        if (rc2)
-            return rc2;
-        HIP_TRY(ctx, hipMemcpyAsync(tail_pin, tail_dev, sizeof(Tail), hipMemcpyDeviceToHost, ctx->stream));
-        return CSM_OK;
-    };
-    /* what a graph of this chain has baked in */
-    std::vector<uint64_t> key = {
-        ctx->alloc_epoch, (uint64_t)(uintptr_t)ctx->stream, (uint64_t)(uintptr_t)g->levels[0].cells,
-        (uint64_t)(uintptr_t)g->levels[level].cells, (uint64_t)(uintptr_t)g->xg.p, (uint64_t)g->xg_pad,
-        (uint64_t)g->rows, (uint64_t)g->cols, (uint64_t)g->known_r0, (uint64_t)g->known_c0,
-        (uint64_t)w.n_theta, (uint64_t)n, (uint64_t)w.win_x, (uint64_t)w.win_y, (uint64_t)w.low_resolution,
-        (uint64_t)(uint32_t)w.min_known, (uint64_t)w.merge_mode, 0 };
-    std::memcpy(&key.back(), &w.score_threshold, 8);
+    std::memcpy(q.pin, &pj, sizeof(pj));
+    std::memcpy(q.pin + q.job_bytes, scan->angles, (size_t)n * 8);
+    std::memcpy(q.pin + q.job_bytes + (size_t)n * 8, scan->ranges, (size_t)n * 8);
+
     bool launched = false;
     ctx->last_graph_replayed = false;
-    if (!two_phase && !ctx->timing && ctx->tune.graphs && !g->xg_stale) {
-        auto it = ctx->graphs.find(key);
-        if (it != ctx->graphs.end()) {
-            HIP_TRY(ctx, hipGraphLaunch(it->second.exec, ctx->stream));
-            ctx->last_nominal = (int64_t)p.n_theta * p.nx * p.ny;
-            ctx->last_coarse_nodes = 0;
-            ctx->last_fine_candidates = ctx->last_nominal;
-            ctx->tp_count_dev = nullptr;
-            /* run_window did not run: the tie pass must see the job this chain was recorded with
-             * (its map, plan and flag word), not that of the last plain launch */
-            ctx->last_fine = it->second.fine;
-            ctx->last_graph_replayed = true;
-            launched = true;
-        } else if (++ctx->graph_seen[key] >= 3) {
-            /* third query of this shape: every workspace has its size; record the chain */
-            if (ctx->graphs.size() >= 8) {
-                for (auto& kv : ctx->graphs)
-                    (void)hipGraphExecDestroy(kv.second.exec);
-                ctx->graphs.clear();
-                ctx->graph_seen.clear();
-            }
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
-                ctx->capturing = true;
-                const int rc_cap = enqueue();
-                ctx->capturing = false;
-                const hipError_t e_end = hipStreamEndCapture(ctx->stream, &graph);
-                if (rc_cap == CSM_OK && e_end == hipSuccess && graph &&
-                    hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    ctx->graphs[key] = { exec, ctx->last_fine };   /* last_fine: set while capturing */
-                    HIP_TRY(ctx, hipGraphLaunch(exec, ctx->stream));
-                    launched = true;
-                }
-                if (graph)
-                    (void)hipGraphDestroy(graph);
-                (void)hipGetLastError();
-            }
-        }
+    if (!wants_two_phase(ctx, p) && !ctx->timing && ctx->tune.graphs && !g->xg_stale) {
+        const std::vector<uint64_t> key = graph_key(ctx, *g, level, w, n);
+        if ((rc = replay_graph(ctx, key, p, &launched))) return rc;
+        if (!launched && (rc = record_graph(ctx, key, *g, w, p, q, &launched))) return rc;
     }
-    if (!launched && (rc = enqueue()))
+    if (!launched && (rc = enqueue_query(ctx, *g, w, p, q)))
         return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    Tail tail = *tail_pin;
-    {
-        bool changed = false;
-        if ((rc = resolve_window(ctx, *g, &w, p, col_dev, row_dev, res_dev, &tail.res, &changed))) return rc;
-        if (changed) {
-            HIP_TRY(ctx, hipMemcpyAsync(&tail.res, res_dev, sizeof(csm_result), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        }
+    Tail tail = *q.tail_pin;
+    csm_result* res_dev = &q.tail_dev->res;
+    bool changed = false, patched = false;
+    if ((rc = resolve_window(ctx, *g, &w, p, q.col_dev, q.row_dev, res_dev, &tail.res, &changed))) return rc;
+    if (changed) {
+        HIP_TRY(ctx, hipMemcpyAsync(&tail.res, res_dev, sizeof(csm_result), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     out->raw = tail.res;
-    const uint32_t n_unc = tail.n_unc;
-    if (n_unc > 0) {
-        /* recompute the uncertified entries exactly as the reference does */
-        std::vector<int32_t> col(hn), row(hn);
-        HIP_TRY(ctx, hipMemcpy(col.data(), col_dev, hn * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(row.data(), row_dev, hn * 4, hipMemcpyDeviceToHost));
-        bool patched = false;
-        if (n_unc > kUncCap) {
-            std::vector<int32_t> c2(hn), r2(hn);
-            csm_host_project(geom, out->sensor_pose, out->step_theta, out->win_theta, scan->angles,
-                             scan->ranges, n, c2.data(), r2.data(), nullptr, nullptr);
-            patched = c2 != col || r2 != row;
-            col.swap(c2);
-            row.swap(r2);
-        } else {
-            std::vector<uint32_t> list(n_unc);
-            HIP_TRY(ctx, hipMemcpy(list.data(), unc_list, (size_t)n_unc * 4, hipMemcpyDeviceToHost));
-            for (uint32_t idx : list) {
-                const int t = (int)(idx / (uint32_t)n) - out->win_theta;
-                const int i = (int)(idx % (uint32_t)n);
-                const double theta = out->sensor_pose[2] + out->step_theta * t;
-                const double hx = out->sensor_pose[0] + scan->ranges[i] * std::cos(theta + scan->angles[i]);
-                const double hy = out->sensor_pose[1] + scan->ranges[i] * std::sin(theta + scan->angles[i]);
-                const int32_t c = static_cast<int>(std::floor((hx - geom->offset_x) / geom->resolution));
-                const int32_t r = static_cast<int>(std::floor((hy - geom->offset_y) / geom->resolution));
-                if (c != col[idx] || r != row[idx]) {
-                    col[idx] = c;
-                    row[idx] = r;
-                    patched = true;
-                }
-            }
-        }
-        if (patched) {
-            HIP_TRY(ctx, hipMemcpy(col_dev, col.data(), hn * 4, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipMemcpy(row_dev, row.data(), hn * 4, hipMemcpyHostToDevice));
-            if ((rc = search_window(ctx, *g, &w, p, col_dev, row_dev, res_dev))) return rc;
-            if ((rc = resolve_window(ctx, *g, &w, p, col_dev, row_dev, res_dev))) return rc;
-            HIP_TRY(ctx, hipMemcpy(&out->raw, res_dev, sizeof(csm_result), hipMemcpyDeviceToHost));
-        }
+    if (tail.n_unc > 0 && (rc = patch_uncertified(ctx, geom, scan, out, q, tail.n_unc, &patched))) return rc;
+    if (patched) {
+        if ((rc = search_window(ctx, *g, &w, p, q.col_dev, q.row_dev, res_dev))) return rc;
+        if ((rc = resolve_window(ctx, *g, &w, p, q.col_dev, q.row_dev, res_dev))) return rc;
+        HIP_TRY(ctx, hipMemcpy(&out->raw, res_dev, sizeof(csm_result), hipMemcpyDeviceToHost));
     }
     const auto t2 = std::chrono::steady_clock::now();
 
@@ -907,8 +965,6 @@ int csm_correlative_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
     out->optimization_us = std::chrono::duration<double, std::micro>(t2 - t1).count();
     return CSM_OK;
 }
-
-
 
 /* ScanMatcherGridSearch::OptimizePose (scan_matcher_grid_search.cpp:69-190) */
 int csm_grid_search_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geom,
