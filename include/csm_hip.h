@@ -702,8 +702,23 @@ int  csm_update_map_with_scan(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shap
 /* ---- pose-graph optimization: the backend's Optimize step ---- */
 
 /* LinearSolver / SolverType of PoseGraphOptimizerLM (inc/mapping/pose_graph_optimizer_lm.hpp) */
-#define CSM_PG_SOLVER_SPARSE_CHOLESKY     0   /* SimplicialLDLT: not provided (CSM_EINVAL) */
+#define CSM_PG_SOLVER_SPARSE_CHOLESKY     0   /* SimplicialLDLT: not provided (CSM_EINVAL); the direct solver
+                                                 that is provided is CSM_PG_SOLVER_SCHUR_CHOLESKY */
 #define CSM_PG_SOLVER_CONJUGATE_GRADIENT  1   /* Eigen ConjugateGradient<.., Lower>, Jacobi preconditioner */
+#define CSM_PG_SOLVER_SCHUR_CHOLESKY      2   /* direct: the scan nodes eliminated block by block (every edge joins
+                                                 a local map node to a scan node, so their 3x3 blocks are
+                                                 independent), then a dense unpivoted LDL^T of the Schur
+                                                 complement on the local map nodes. Not SimplicialLDLT: no
+                                                 fill-reducing ordering, another elimination order, other
+                                                 rounding. Trace: cg_iterations = 0, residual_norm2 = the true
+                                                 |b - H delta|^2 computed after the solve. A zero or non-finite
+                                                 pivot (possible only with an information matrix that is not
+                                                 positive semi-definite) does not stop the call: as in the
+                                                 reference, which never reads the solver's info(), the step goes
+                                                 on with what the arithmetic gives. */
+/* the Schur complement is stored dense ((3 n_local)^2 doubles, 1.2 GB at the cap): more local map
+ * nodes than this are CSM_EINVAL under CSM_PG_SOLVER_SCHUR_CHOLESKY, on the device and on the host */
+#define CSM_PG_SCHUR_MAX_LOCAL            4096
 
 /* robust loss functions (src/mapping/robust_loss_function.cpp) */
 #define CSM_PG_LOSS_SQUARED         0
@@ -749,20 +764,25 @@ typedef struct {
     double  total_error;         /* ComputeTotalError after the step */
     double  lambda;              /* the damping factor the step's H was built with */
     double  rhs_norm2;           /* |b|^2: the CG stops once |r|^2 < max(DBL_EPSILON^2 |b|^2, DBL_MIN) */
-    double  residual_norm2;      /* the CG's last recursively updated |r|^2 (0 when b = 0) */
-    int32_t cg_iterations;       /* ConjugateGradient::iterations(): at most 2 * 3 * (n_local + n_scan) */
+    double  residual_norm2;      /* the CG's last recursively updated |r|^2 (0 when b = 0); SCHUR_CHOLESKY:
+                                    the true |b - H delta|^2 */
+    int32_t cg_iterations;       /* ConjugateGradient::iterations(): at most 2 * 3 * (n_local + n_scan);
+                                    SCHUR_CHOLESKY: 0 */
     int32_t reserved;
 } csm_pose_graph_lm_step;
 
 /* PoseGraphOptimizerLM::Optimize (src/mapping/pose_graph_optimizer_lm.cpp:38-106) with the
- * ConjugateGradient solver, on the device: one launch, one workgroup, every LM step inside.
+ * ConjugateGradient solver (one launch, one workgroup, every LM step inside) or the direct
+ * SchurCholesky solver (a chain of grid-wide launches per LM step, the LM state kept on the device),
+ * on the device.
  * local_poses [3 * n_local] and scan_poses [3 * n_scan] are updated in place; *lambda is the
  * optimizer's mLambda, read at the start and written back at the end (it carries over between
  * calls). info and trace may be null; a trace holds iterations_max records, of which
  * info->steps are written. Runs on the ctx stream and returns when the results are on the host.
  * Deterministic; agrees with csm_host_pose_graph_lm within rounding of the reduction order
  * (DESIGN.md 4e). SparseCholesky, an index out of range, a non-finite pose, relative pose or
- * information entry, n_local < 1 or iterations_max < 1: CSM_EINVAL. */
+ * information entry, n_local < 1, iterations_max < 1, or n_local > CSM_PG_SCHUR_MAX_LOCAL under
+ * SchurCholesky: CSM_EINVAL. */
 int  csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double* scan_poses,
                        int32_t n_scan, const csm_pose_graph_edge* edges, int32_t n_edges,
                        const csm_pose_graph_lm_params* params, double* lambda,

@@ -156,7 +156,8 @@ class HillClimbingResult(C.Structure):
 
 
 # pose-graph optimization (include/csm_hip.h)
-PG_SOLVER_SPARSE_CHOLESKY, PG_SOLVER_CONJUGATE_GRADIENT = 0, 1
+PG_SOLVER_SPARSE_CHOLESKY, PG_SOLVER_CONJUGATE_GRADIENT, PG_SOLVER_SCHUR_CHOLESKY = 0, 1, 2
+PG_SCHUR_MAX_LOCAL = 4096
 PG_LOSS_SQUARED, PG_LOSS_HUBER, PG_LOSS_CAUCHY, PG_LOSS_FAIR, PG_LOSS_GEMAN_MCCLURE, PG_LOSS_WELSCH = range(6)
 
 

@@ -214,7 +214,8 @@ def host_probability_lut():
     return lut
 
 
-PG_SOLVERS = {"SparseCholesky": L.PG_SOLVER_SPARSE_CHOLESKY, "ConjugateGradient": L.PG_SOLVER_CONJUGATE_GRADIENT}
+PG_SOLVERS = {"SparseCholesky": L.PG_SOLVER_SPARSE_CHOLESKY, "ConjugateGradient": L.PG_SOLVER_CONJUGATE_GRADIENT,
+              "SchurCholesky": L.PG_SOLVER_SCHUR_CHOLESKY}
 PG_LOSSES = {"Squared": L.PG_LOSS_SQUARED, "Huber": L.PG_LOSS_HUBER, "Cauchy": L.PG_LOSS_CAUCHY,
              "Fair": L.PG_LOSS_FAIR, "GemanMcClure": L.PG_LOSS_GEMAN_MCCLURE, "Welsch": L.PG_LOSS_WELSCH}
 
@@ -854,15 +855,17 @@ class ScanMatcherHillClimbingHIP:
 
 
 class PoseGraphOptimizerLMHIP:
-    """Drop-in for PoseGraphOptimizerLM with the ConjugateGradient solver (constructor arguments as
+    """Drop-in for PoseGraphOptimizerLM with the ConjugateGradient solver, or with the direct
+    "SchurCholesky" solver in place of SparseCholesky, which is not provided (constructor arguments as
     the optimizer's settings group, launcher_settings_default.json "PoseGraphOptimizerLM"). The damping
     factor is kept between optimize() calls, as the reference's mLambda member is."""
 
     def __init__(self, solver="ConjugateGradient", iterations_max=10, error_tolerance=1e-4, initial_lambda=1e-4,
                  loss="Huber", loss_scale=0.01, ctx=None):
         self.params = pose_graph_params(iterations_max, error_tolerance, solver, loss, loss_scale)
-        if self.params.solver_type != L.PG_SOLVER_CONJUGATE_GRADIENT:
-            raise CsmError(L.CSM_EINVAL, "PoseGraphOptimizerLMHIP: only the ConjugateGradient solver is provided")
+        if self.params.solver_type not in (L.PG_SOLVER_CONJUGATE_GRADIENT, L.PG_SOLVER_SCHUR_CHOLESKY):
+            raise CsmError(L.CSM_EINVAL, "PoseGraphOptimizerLMHIP: only the ConjugateGradient and SchurCholesky "
+                                         "solvers are provided")
         self.lambda_ = float(initial_lambda)
         self.ctx = ctx or Context()
         self.last_info = None

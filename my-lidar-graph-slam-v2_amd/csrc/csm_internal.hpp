@@ -224,6 +224,7 @@ struct csm_ctx {
     DevBuf g_scans, g_jobs, g_scratch, g_tab;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
+    DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */
     std::vector<uint8_t> pg_stage;
     /* the final records of the last batch call in query order (csm_copy_last_batch_records) */
     DevBuf rec_dev;

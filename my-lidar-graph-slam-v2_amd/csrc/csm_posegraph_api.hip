@@ -1,7 +1,8 @@
 /* csm_posegraph_api.hip -- host side of the pose-graph optimizer (PoseGraphOptimizerLM with the
- * ConjugateGradient solver): validation, the block structure of H with the ordered contribution list
- * of every stored block, the host restatement csm_host_pose_graph_lm (the CPU reference) and the
- * device entry csm_pose_graph_lm, whose kernel is in csm_posegraph_kernels.hip. A translation unit of
+ * ConjugateGradient solver or the direct Schur-complement Cholesky solver): validation, the block
+ * structure of H with the ordered contribution list of every stored block (and of every block of the
+ * Schur complement), the host restatement csm_host_pose_graph_lm (the CPU reference) and the device
+ * entry csm_pose_graph_lm, whose kernels are in csm_posegraph_kernels.hip. A translation unit of
  * libcsm_hip.so of its own. DESIGN.md 4e. */
 #include "csm_internal.hpp"
 
@@ -19,6 +20,11 @@ struct PgGraph {
     int n_local = 0, n_nodes = 0, n_vars = 0, n_edges = 0, n_cross = 0;
     std::vector<double> rel, info;
     std::vector<int32_t> enode, is_loop, node_ptr, node_edges, cross_ptr, cross_edges, row_ptr, row_col, row_ent;
+    /* the Schur complement on the local map nodes (pg_build_schur): its stored 3x3 blocks (s1 >= s2,
+     * the n_local diagonal ones first) and, per block, the cross-block pairs of the scan nodes adjacent
+     * to both, in ascending scan node order */
+    int n_sblk = 0;
+    std::vector<int32_t> sb_rc, sb_ptr, sb_pair;
 };
 
 const char* pg_check(const double* local_poses, int n_local, const double* scan_poses, int n_scan,
@@ -30,8 +36,10 @@ const char* pg_check(const double* local_poses, int n_local, const double* scan_
         return "bad arguments";
     if (p->solver_type == CSM_PG_SOLVER_SPARSE_CHOLESKY)
         return "SolverType SparseCholesky (SimplicialLDLT) is not provided; use ConjugateGradient";
-    if (p->solver_type != CSM_PG_SOLVER_CONJUGATE_GRADIENT)
+    if (p->solver_type != CSM_PG_SOLVER_CONJUGATE_GRADIENT && p->solver_type != CSM_PG_SOLVER_SCHUR_CHOLESKY)
         return "unknown solver type";
+    if (p->solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY && n_local > CSM_PG_SCHUR_MAX_LOCAL)
+        return "n_local exceeds CSM_PG_SCHUR_MAX_LOCAL (the Schur complement is stored dense)";
     if (p->loss_type < CSM_PG_LOSS_SQUARED || p->loss_type > CSM_PG_LOSS_WELSCH)
         return "unknown loss type";
     if (p->iterations_max < 1)
@@ -136,6 +144,59 @@ void pg_build(int n_local, int n_scan, const csm_pose_graph_edge* edges, int n_e
     }
 }
 
+/* which scan nodes contribute to which block of S = A - B^T D^-1 B: a scan node with d distinct
+ * neighbours contributes to d (d + 1) / 2 blocks. Returns false when the lists would not fit an int. */
+bool pg_build_schur(PgGraph& G)
+{
+    const int nl = G.n_local;
+    std::unordered_map<int64_t, int32_t> block_id;
+    std::vector<std::vector<int32_t>> lists(nl);
+    G.sb_rc.clear();
+    for (int s = 0; s < nl; ++s) {
+        G.sb_rc.push_back(s);
+        G.sb_rc.push_back(s);
+    }
+    int64_t total = 0;
+    for (int t = nl; t < G.n_nodes; ++t) {             /* ascending t: every list ends up in that order */
+        const int q0 = G.row_ptr[t], q1 = G.row_ptr[t + 1];
+        for (int a = q0; a < q1; ++a) {
+            if (G.row_col[a] == t)
+                continue;
+            for (int b = q0; b <= a; ++b) {            /* columns ascend, so s1 = col[a] >= s2 = col[b] */
+                const int s1 = G.row_col[a], s2 = G.row_col[b];
+                int32_t id = s1;
+                if (s1 != s2) {
+                    const int64_t key = (int64_t)s1 * nl + s2;
+                    auto it = block_id.find(key);
+                    if (it == block_id.end()) {
+                        it = block_id.emplace(key, (int32_t)lists.size()).first;
+                        lists.emplace_back();
+                        G.sb_rc.push_back(s1);
+                        G.sb_rc.push_back(s2);
+                    }
+                    id = it->second;
+                }
+                lists[id].push_back((G.row_ent[a] >> 2) - G.n_nodes);
+                lists[id].push_back((G.row_ent[b] >> 2) - G.n_nodes);
+                if (++total > (INT32_MAX / 4))
+                    return false;
+            }
+        }
+    }
+    G.n_sblk = (int)lists.size();
+    G.sb_ptr.assign(G.n_sblk + 1, 0);
+    G.sb_pair.clear();
+    G.sb_pair.reserve(2 * (size_t)total);
+    for (int q = 0; q < G.n_sblk; ++q) {
+        G.sb_pair.insert(G.sb_pair.end(), lists[q].begin(), lists[q].end());
+        G.sb_ptr[q + 1] = (int32_t)(G.sb_pair.size() / 2);
+    }
+    return true;
+}
+
+/* the n_s = 3 n_local rounded up to whole tiles of the blocked factorization */
+int pg_schur_padded(int n_local) { return ceil_div(3 * n_local, kPgsTile) * kPgsTile; }
+
 void pg_job_structure(const PgGraph& G, const csm_pose_graph_lm_params& p, double lambda, PgJob& J)
 {
     J.n_local = G.n_local;
@@ -156,6 +217,7 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
                  csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
 {
     const int n = G.n_vars;
+    const bool schur = p.solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY;
     std::vector<double> ev((size_t)kPgEdgeVals * G.n_edges), bv(9 * ((size_t)G.n_nodes + G.n_cross));
     std::vector<double> b(n), invd(n), x(n), r(n), z(n), pv(n), ap(n);
     PgJob J {};
@@ -189,25 +251,12 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
     };
     J.b = b.data();
     J.invd = invd.data();
-    double prev = DBL_MAX, total = DBL_MAX;
-    const double initial = total_error();
-    int steps = 0;
-    int64_t cg_total = 0;
-    for (;;) {
-        for (int e = 0; e < G.n_edges; ++e)
-            pg_edge_values(&pose[3 * (size_t)G.enode[2 * e]], &pose[3 * (size_t)G.enode[2 * e + 1]],
-                           &G.rel[3 * (size_t)e], &G.info[9 * (size_t)e], G.is_loop[e], p.loss_type, p.loss_scale,
-                           &ev[(size_t)kPgEdgeVals * e]);
-        for (int k = 0; k < G.n_nodes; ++k)
-            pg_assemble_node(J, k, lambda);
-        for (int u = 0; u < G.n_cross; ++u)
-            pg_assemble_cross(J, u);
-        /* conjugate_gradient with x0 = 0: residual = b */
+    /* conjugate_gradient with x0 = 0: residual = b. Returns |r|^2 and the iteration count. */
+    auto solve_cg = [&](double rhs2, int& cg) {
         std::fill(x.begin(), x.end(), 0.0);
         r = b;
-        const double rhs2 = dot(b, b);
         double r2 = rhs2;
-        int cg = 0;
+        cg = 0;
         if (rhs2 != 0.0) {
             const double a = DBL_EPSILON * DBL_EPSILON * rhs2;
             const double thr = (a < DBL_MIN) ? DBL_MIN : a;
@@ -236,6 +285,84 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
                 }
             }
         }
+        return r2;
+    };
+    /* block elimination of the scan nodes, dense LDL^T of the Schur complement (steps 1 - 5 of
+     * DESIGN.md 4e, "direct solver"). Returns the true |b - H x|^2. */
+    const int ns = 3 * G.n_local;
+    std::vector<double> S, g, w, wrow;
+    if (schur) {
+        S.resize((size_t)ns * ns);
+        g.resize(3 * (size_t)(G.n_nodes - G.n_local));
+        w.resize(9 * (size_t)G.n_cross);
+        wrow.resize(ns);
+    }
+    auto solve_schur = [&]() {
+        for (int t = G.n_local; t < G.n_nodes; ++t)
+            pg_eliminate_scan(J, g.data(), w.data(), t);
+        std::fill(S.begin(), S.end(), 0.0);
+        for (int q = 0; q < G.n_sblk; ++q)
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j)
+                    S[(3 * (size_t)G.sb_rc[2 * q] + i) * ns + 3 * (size_t)G.sb_rc[2 * q + 1] + j] =
+                        pg_schur_entry(J, G.sb_rc.data(), G.sb_ptr.data(), G.sb_pair.data(), w.data(), q, i, j);
+        for (int a = 0; a < ns; ++a)
+            x[a] = pg_schur_rhs(J, g.data(), a / 3, a % 3);
+        for (int i = 0; i < ns; ++i) {               /* L below the diagonal, d on it */
+            double* ri = &S[(size_t)i * ns];
+            for (int j = 0; j <= i; ++j) {
+                const double* rj = &S[(size_t)j * ns];
+                double v = ri[j];
+                for (int k = 0; k < j; ++k)
+                    v -= wrow[k] * rj[k];
+                if (j < i) {
+                    const double l = v / rj[j];
+                    ri[j] = l;
+                    wrow[j] = l * rj[j];
+                } else {
+                    ri[i] = v;
+                }
+            }
+        }
+        for (int i = 0; i < ns; ++i) {
+            double v = x[i];
+            for (int k = 0; k < i; ++k)
+                v -= S[(size_t)i * ns + k] * x[k];
+            x[i] = v;
+        }
+        for (int i = 0; i < ns; ++i)
+            x[i] = x[i] / S[(size_t)i * ns + i];
+        for (int i = ns - 1; i >= 0; --i) {
+            double v = x[i];
+            for (int k = ns - 1; k > i; --k)
+                v -= S[(size_t)k * ns + i] * x[k];
+            x[i] = v;
+        }
+        for (int t = G.n_local; t < G.n_nodes; ++t)
+            pg_back_scan(J, g.data(), w.data(), x.data(), t);
+        double r2 = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double ri = b[i] - pg_row_times(J, i, x.data());
+            r2 += ri * ri;
+        }
+        return r2;
+    };
+    double prev = DBL_MAX, total = DBL_MAX;
+    const double initial = total_error();
+    int steps = 0;
+    int64_t cg_total = 0;
+    for (;;) {
+        for (int e = 0; e < G.n_edges; ++e)
+            pg_edge_values(&pose[3 * (size_t)G.enode[2 * e]], &pose[3 * (size_t)G.enode[2 * e + 1]],
+                           &G.rel[3 * (size_t)e], &G.info[9 * (size_t)e], G.is_loop[e], p.loss_type, p.loss_scale,
+                           &ev[(size_t)kPgEdgeVals * e]);
+        for (int k = 0; k < G.n_nodes; ++k)
+            pg_assemble_node(J, k, lambda);
+        for (int u = 0; u < G.n_cross; ++u)
+            pg_assemble_cross(J, u);
+        const double rhs2 = dot(b, b);
+        int cg = 0;
+        const double r2 = schur ? solve_schur() : solve_cg(rhs2, cg);
         for (int i = 0; i < n; ++i)
             pose[i] += x[i];
         total = total_error();
@@ -275,6 +402,52 @@ struct Carve {
     }
 };
 
+/* the direct solver's launches for one Optimize call: the initial total error, then the chain of one
+ * LM step iterations_max times (a step's kernels return at once after the step that stopped) */
+int pg_schur_chain(csm_ctx* ctx, const PgSchurJob& Q, bool small)
+{
+    const PgJob& J = Q.J;
+    hipStream_t s = ctx->stream;
+    const dim3 blk(kPgsBlock);
+    const int n_scan = J.n_nodes - J.n_local, nt = Q.np / kPgsTile;
+    auto over = [](int64_t count) { return dim3((unsigned)((count + kPgsBlock - 1) / kPgsBlock)); };
+    if (J.n_edges)
+        hipLaunchKernelGGL(k_pgs_error, over(J.n_edges), blk, 0, s, Q);
+    hipLaunchKernelGGL(k_pgs_decide, dim3(1), blk, 0, s, Q, 1);
+    for (int it = 0; it < J.iterations_max; ++it) {
+        if (J.n_edges)
+            hipLaunchKernelGGL(k_pgs_edges, over(J.n_edges), blk, 0, s, Q);
+        hipLaunchKernelGGL(k_pgs_assemble, over((int64_t)J.n_nodes + J.n_cross), blk, 0, s, Q);
+        if (n_scan)
+            hipLaunchKernelGGL(k_pgs_eliminate, over(n_scan), blk, 0, s, Q);
+        if (small) {
+            hipLaunchKernelGGL(k_pgs_small, dim3(1), blk, 0, s, Q);
+        } else {
+            const int64_t cells = (int64_t)Q.np * Q.np;
+            hipLaunchKernelGGL(k_pgs_clear, dim3((unsigned)std::min<int64_t>((cells + kPgsBlock - 1) / kPgsBlock, 16384)),
+                               blk, 0, s, Q);
+            hipLaunchKernelGGL(k_pgs_schur, over(9 * (int64_t)Q.n_sblk + Q.np), blk, 0, s, Q);
+            for (int p = 0; p < nt; ++p) {
+                hipLaunchKernelGGL(k_pgs_ldl_diag, dim3(1), blk, 0, s, Q, p);
+                const int below = nt - p - 1;
+                if (below) {
+                    hipLaunchKernelGGL(k_pgs_ldl_panel, dim3(ceil_div(below * kPgsTile, 64)), dim3(64), 0, s, Q, p);
+                    hipLaunchKernelGGL(k_pgs_ldl_update, dim3(below, below), blk, 0, s, Q, p);
+                }
+            }
+            hipLaunchKernelGGL(k_pgs_solve, dim3(1), dim3(kPgsSolveBlock), 0, s, Q);
+        }
+        if (n_scan)
+            hipLaunchKernelGGL(k_pgs_back, over(n_scan), blk, 0, s, Q);
+        hipLaunchKernelGGL(k_pgs_update, dim3(Q.nb_vars), blk, 0, s, Q);
+        if (J.n_edges)
+            hipLaunchKernelGGL(k_pgs_error, over(J.n_edges), blk, 0, s, Q);
+        hipLaunchKernelGGL(k_pgs_decide, dim3(1), blk, 0, s, Q, 0);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return CSM_OK;
+}
+
 } /* namespace */
 
 extern "C" {
@@ -296,6 +469,8 @@ int csm_host_pose_graph_lm(double* local_poses, int32_t n_local, double* scan_po
         return CSM_EINVAL;
     PgGraph G;
     pg_build(n_local, n_scan, edges, n_edges, G);
+    if (params->solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY && !pg_build_schur(G))
+        return CSM_EINVAL;
     std::vector<double> pose(G.n_vars);
     std::memcpy(pose.data(), local_poses, 3 * (size_t)n_local * sizeof(double));
     if (n_scan)
@@ -315,8 +490,11 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
         return CSM_EINVAL;
     if (const char* why = pg_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, params, lambda))
         return fail(ctx, CSM_EINVAL, "csm_pose_graph_lm: %s", why);
+    const bool schur = params->solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY;
     PgGraph G;
     pg_build(n_local, n_scan, edges, n_edges, G);
+    if (schur && !pg_build_schur(G))
+        return fail(ctx, CSM_EINVAL, "csm_pose_graph_lm: the Schur complement's contribution lists are too long");
     const int n = G.n_vars, E = G.n_edges, NB = G.n_nodes + G.n_cross, R = (int)G.row_col.size();
     const int n_out = 4 + 5 * params->iterations_max;
     /* inputs (uploaded): pose, rel, info, then the int lists; work and output after them */
@@ -327,14 +505,24 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
     const size_t o_cptr = c.take(4 * ((size_t)G.n_cross + 1)), o_cedge = c.take(4 * (size_t)E);
     const size_t o_rptr = c.take(4 * ((size_t)G.n_nodes + 1)), o_rcol = c.take(4 * (size_t)R),
                  o_rent = c.take(4 * (size_t)R);
+    /* the direct solver's lists and the LM state it keeps on the device */
+    const size_t o_sbrc = c.take(schur ? 8 * (size_t)G.n_sblk : 0), o_sbptr = c.take(schur ? 4 * ((size_t)G.n_sblk + 1) : 0),
+                 o_sbpair = c.take(schur ? 4 * G.sb_pair.size() : 0), o_state = c.take(schur ? sizeof(PgState) : 0);
     const size_t up_bytes = c.off;
     const size_t o_ev = c.take(8 * (size_t)kPgEdgeVals * E), o_bv = c.take(72 * (size_t)NB);
     size_t o_vec[7];
     for (size_t& o : o_vec)
         o = c.take(8 * (size_t)n);
     const size_t o_out = c.take(8 * (size_t)n_out);
+    const int np = pg_schur_padded(n_local), nb_vars = ceil_div(n, kPgsBlock), nb_edges = ceil_div(E, kPgsBlock);
+    const bool small = 3 * n_local <= kPgsSmall;
+    const size_t o_g = c.take(schur ? 24 * (size_t)n_scan : 0), o_w = c.take(schur ? 72 * (size_t)G.n_cross : 0),
+                 o_y = c.take(schur ? 8 * (size_t)np : 0), o_wp = c.take(schur && !small ? 8 * (size_t)np * kPgsTile : 0),
+                 o_part = c.take(schur ? 8 * (2 * (size_t)nb_vars + nb_edges) : 0);
     int rc;
     if ((rc = ensure(ctx, ctx->pg_buf, c.off)))
+        return rc;
+    if (schur && !small && (rc = grow(ctx, ctx->pg_s, 8 * (size_t)np * np, 8 * (size_t)np * np, false)))
         return rc;
     std::vector<uint8_t>& st = ctx->pg_stage;
     st.assign(up_bytes, 0);
@@ -355,6 +543,13 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
     put(o_rptr, G.row_ptr.data(), 4 * ((size_t)G.n_nodes + 1));
     put(o_rcol, G.row_col.data(), 4 * (size_t)R);
     put(o_rent, G.row_ent.data(), 4 * (size_t)R);
+    if (schur) {
+        const PgState st0 = { *lambda, DBL_MAX, DBL_MAX, 0.0, 0, 0 };
+        put(o_sbrc, G.sb_rc.data(), 8 * (size_t)G.n_sblk);
+        put(o_sbptr, G.sb_ptr.data(), 4 * ((size_t)G.n_sblk + 1));
+        put(o_sbpair, G.sb_pair.data(), 4 * G.sb_pair.size());
+        put(o_state, &st0, sizeof(st0));
+    }
 
     uint8_t* d = reinterpret_cast<uint8_t*>(ctx->pg_buf.p);
     PgJob J {};
@@ -379,10 +574,31 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
     J.out = reinterpret_cast<double*>(d + o_out);
 
     HIP_TRY(ctx, hipMemcpyAsync(d, st.data(), up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    {
+    if (!schur) {
         ScopedTimer tm(ctx, "pose_graph");
         hipLaunchKernelGGL(k_pose_graph_lm, dim3(1), dim3(kPgBlock), 0, ctx->stream, J);
         HIP_TRY(ctx, hipGetLastError());
+    } else {
+        PgSchurJob Q {};
+        Q.J = J;
+        Q.n_s = 3 * n_local;
+        Q.np = np;
+        Q.n_sblk = G.n_sblk;
+        Q.nb_vars = nb_vars;
+        Q.nb_edges = nb_edges;
+        Q.sb_rc = reinterpret_cast<const int32_t*>(d + o_sbrc);
+        Q.sb_ptr = reinterpret_cast<const int32_t*>(d + o_sbptr);
+        Q.sb_pair = reinterpret_cast<const int32_t*>(d + o_sbpair);
+        Q.g = reinterpret_cast<double*>(d + o_g);
+        Q.w = reinterpret_cast<double*>(d + o_w);
+        Q.S = small ? nullptr : ctx->pg_s.as<double>();
+        Q.wp = reinterpret_cast<double*>(d + o_wp);
+        Q.y = reinterpret_cast<double*>(d + o_y);
+        Q.part = reinterpret_cast<double*>(d + o_part);
+        Q.st = reinterpret_cast<PgState*>(d + o_state);
+        ScopedTimer tm(ctx, "pose_graph");
+        if ((rc = pg_schur_chain(ctx, Q, small)))
+            return rc;
     }
     std::vector<double> res(n + (size_t)n_out);
     HIP_TRY(ctx, hipMemcpyAsync(res.data(), d + o_pose, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));

@@ -387,5 +387,532 @@ __global__ __launch_bounds__(kPgBlock) void k_pose_graph_lm(PgJob J)
     }
 }
 
+/* ================================================================== Schur-complement Cholesky solver
+ * CSM_PG_SOLVER_SCHUR_CHOLESKY: every edge joins a local map node to a scan node, so
+ * D (the scan nodes' diagonal blocks) is block diagonal. Per LM step: D_t = L D L^T (3x3, unpivoted),
+ * g_t = D_t^-1 b_t and W_ts = D_t^-1 B_ts per scan node; S = A - B^T W and c = b_local - B^T g from
+ * host-built ordered lists; a dense unpivoted scalar LDL^T of S (lower triangle, row-major, each
+ * entry's inner product over k ascending); substitutions; x_t = g_t - sum_s W_ts x_s. The per-entry
+ * arithmetic below is shared by the host restatement and the kernels; the device's blocked
+ * factorization subtracts every entry's terms in the same ascending k order, one after the other. */
+
+constexpr int kPgsTile = 48;      /* panel width = tile edge of the blocked LDL^T: a multiple of 3 */
+constexpr int kPgsSmall = 96;     /* 3 n_local up to here: S lives in the LDS of one workgroup */
+constexpr int kPgsBlock = 256;    /* threads of the grid-wide kernels and of the reductions */
+constexpr int kPgsSolveBlock = 1024;
+
+/* what the LM loop carries from step to step on the device */
+struct PgState {
+    double lambda, prev, total, initial;
+    int32_t steps, done;
+};
+
+struct PgSchurJob {
+    PgJob J;                      /* J.x is delta; J.r, J.z, J.p, J.ap are unused */
+    int n_s, np;                  /* 3 n_local; n_s rounded up to whole tiles (= the row stride of S) */
+    int n_sblk;                   /* stored 3x3 blocks of S: the n_local diagonal ones, then the others */
+    int nb_vars, nb_edges;        /* workgroups (= partial sums) of k_pgs_update / k_pgs_error */
+    const int32_t* sb_rc;         /* [2 n_sblk]: s1 >= s2 */
+    const int32_t* sb_ptr;        /* [n_sblk + 1] into sb_pair */
+    const int32_t* sb_pair;       /* cross blocks (t, s1), (t, s2) of every common scan node t, ascending t */
+    double* g;                    /* [3 n_scan] */
+    double* w;                    /* [9 n_cross] */
+    double* S;                    /* [np * np] (blocked path) */
+    double* wp;                   /* [np * kPgsTile]: (L d) of the current panel */
+    double* y;                    /* [np]: c, then the substitutions in place */
+    double* part;                 /* [2 nb_vars + nb_edges]: |r|^2, |b|^2, total-error partial sums */
+    PgState* st;
+};
+
+/* unpivoted LDL^T of a self-adjoint 3x3 block read from its lower triangle (row-major, 9 entries):
+ * f = d0 d1 d2 l10 l20 l21; the same formulas as the dense factorization of S */
+__host__ __device__ inline void pg_ldl3(const double* D, double f[6])
+{
+    f[0] = D[0];
+    f[3] = D[3] / f[0];
+    f[4] = D[6] / f[0];
+    f[1] = D[4] - (f[3] * f[0]) * f[3];
+    f[5] = (D[7] - (f[4] * f[0]) * f[3]) / f[1];
+    f[2] = D[8] - (f[4] * f[0]) * f[4] - (f[5] * f[1]) * f[5];
+}
+
+/* forward (k ascending), diagonal, backward (k descending) */
+__host__ __device__ inline void pg_ldl3_solve(const double f[6], double v0, double v1, double v2, double x[3])
+{
+    const double y1 = v1 - f[3] * v0;
+    const double y2 = v2 - f[4] * v0 - f[5] * y1;
+    const double z0 = v0 / f[0], z1 = y1 / f[1], z2 = y2 / f[2];
+    x[2] = z2;
+    x[1] = z1 - f[5] * x[2];
+    x[0] = z0 - f[4] * x[2] - f[3] * x[1];
+}
+
+/* step 1 for scan node t (a node index >= n_local): g_t and W of each of its cross blocks */
+__host__ __device__ inline void pg_eliminate_scan(const PgJob& J, double* g, double* w, int t)
+{
+    double f[6];
+    pg_ldl3(J.bv + 9 * (size_t)t, f);
+    const double* bt = J.b + 3 * (size_t)t;
+    pg_ldl3_solve(f, bt[0], bt[1], bt[2], g + 3 * (size_t)(t - J.n_local));
+    for (int q = J.row_ptr[t]; q < J.row_ptr[t + 1]; ++q) {
+        if (J.row_col[q] == t)
+            continue;
+        const int slot = J.row_ent[q] >> 2;
+        const double* B = J.bv + 9 * (size_t)slot;
+        double* W = w + 9 * (size_t)(slot - J.n_nodes);
+        for (int j = 0; j < 3; ++j) {
+            double x[3];
+            pg_ldl3_solve(f, B[j], B[3 + j], B[6 + j], x);
+            W[j] = x[0];
+            W[3 + j] = x[1];
+            W[6 + j] = x[2];
+        }
+    }
+}
+
+/* step 2: entry (i, j) of stored S block q */
+__host__ __device__ inline double pg_schur_entry(const PgJob& J, const int32_t* sb_rc, const int32_t* sb_ptr,
+                                                 const int32_t* sb_pair, const double* w, int q, int i, int j)
+{
+    const int s1 = sb_rc[2 * q], s2 = sb_rc[2 * q + 1];
+    double acc = (s1 == s2) ? J.bv[9 * (size_t)s1 + 3 * i + j] : 0.0;
+    for (int m = sb_ptr[q]; m < sb_ptr[q + 1]; ++m) {
+        const double* B = J.bv + 9 * ((size_t)J.n_nodes + sb_pair[2 * m]);
+        const double* W = w + 9 * (size_t)sb_pair[2 * m + 1];
+        acc -= B[i] * W[j] + B[3 + i] * W[3 + j] + B[6 + i] * W[6 + j];
+    }
+    return acc;
+}
+
+/* step 2: entry a of the reduced right-hand side of local map node s */
+__host__ __device__ inline double pg_schur_rhs(const PgJob& J, const double* g, int s, int a)
+{
+    double acc = J.b[3 * (size_t)s + a];
+    for (int q = J.row_ptr[s]; q < J.row_ptr[s + 1]; ++q) {
+        if (!(J.row_ent[q] & kPgTransposed))
+            continue;
+        const double* B = J.bv + 9 * (size_t)(J.row_ent[q] >> 2);
+        const double* gt = g + 3 * (size_t)(J.row_col[q] - J.n_local);
+        acc -= B[a] * gt[0] + B[3 + a] * gt[1] + B[6 + a] * gt[2];
+    }
+    return acc;
+}
+
+/* step 4 for scan node t: its three entries of delta (x holds the local map nodes' already) */
+__host__ __device__ inline void pg_back_scan(const PgJob& J, const double* g, const double* w, double* x, int t)
+{
+    double acc[3];
+    for (int i = 0; i < 3; ++i)
+        acc[i] = g[3 * (size_t)(t - J.n_local) + i];
+    for (int q = J.row_ptr[t]; q < J.row_ptr[t + 1]; ++q) {
+        if (J.row_col[q] == t)
+            continue;
+        const double* W = w + 9 * (size_t)((J.row_ent[q] >> 2) - J.n_nodes);
+        const double* xs = x + 3 * (size_t)J.row_col[q];
+        for (int i = 0; i < 3; ++i)
+            acc[i] -= W[3 * i] * xs[0] + W[3 * i + 1] * xs[1] + W[3 * i + 2] * xs[2];
+    }
+    for (int i = 0; i < 3; ++i)
+        x[3 * (size_t)t + i] = acc[i];
+}
+
+/* ------------------------------------------------------------------ device: the launch chain of one LM step.
+ * Every kernel returns at once when the state's done flag is set; none waits on another workgroup. */
+
+/* sum of N values per thread over a kPgsBlock workgroup, the same bits on every thread */
+template <int N>
+__device__ inline void pgs_block_sum(double (&v)[N], double (*buf)[N])
+{
+    for (int m = 32; m >= 1; m >>= 1)
+        for (int q = 0; q < N; ++q)
+            v[q] += __shfl_xor(v[q], m, 64);
+    if ((threadIdx.x & 63) == 0)
+        for (int q = 0; q < N; ++q)
+            buf[threadIdx.x >> 6][q] = v[q];
+    __syncthreads();
+    for (int q = 0; q < N; ++q) {
+        double s = buf[0][q];
+        for (int w = 1; w < kPgsBlock / 64; ++w)
+            s += buf[w][q];
+        v[q] = s;
+    }
+}
+
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_edges(PgSchurJob Q)
+{
+    const PgJob& J = Q.J;
+    const int e = blockIdx.x * kPgsBlock + threadIdx.x;
+    if (Q.st->done || e >= J.n_edges)
+        return;
+    pg_edge_values(J.pose + 3 * (size_t)J.enode[2 * e], J.pose + 3 * (size_t)J.enode[2 * e + 1],
+                   J.rel + 3 * (size_t)e, J.info + 9 * (size_t)e, J.is_loop[e], J.loss_type, J.loss_scale,
+                   J.ev + (size_t)kPgEdgeVals * e);
+}
+
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_assemble(PgSchurJob Q)
+{
+    const PgJob& J = Q.J;
+    const int k = blockIdx.x * kPgsBlock + threadIdx.x;
+    if (Q.st->done)
+        return;
+    if (k < J.n_nodes)
+        pg_assemble_node(J, k, Q.st->lambda);
+    else if (k - J.n_nodes < J.n_cross)
+        pg_assemble_cross(J, k - J.n_nodes);
+}
+
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_eliminate(PgSchurJob Q)
+{
+    const int t = Q.J.n_local + blockIdx.x * kPgsBlock + threadIdx.x;
+    if (Q.st->done || t >= Q.J.n_nodes)
+        return;
+    pg_eliminate_scan(Q.J, Q.g, Q.w, t);
+}
+
+/* S = 0 with a unit diagonal in the padding rows (they factor to L = 0, d = 1) */
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_clear(PgSchurJob Q)
+{
+    if (Q.st->done)
+        return;
+    const size_t total = (size_t)Q.np * Q.np;
+    for (size_t i = (size_t)blockIdx.x * kPgsBlock + threadIdx.x; i < total; i += (size_t)gridDim.x * kPgsBlock) {
+        const int r = (int)(i / Q.np), c = (int)(i - (size_t)r * Q.np);
+        Q.S[i] = (r == c && r >= Q.n_s) ? 1.0 : 0.0;
+    }
+}
+
+/* a thread per scalar of a stored S block, then a thread per entry of c */
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_schur(PgSchurJob Q)
+{
+    if (Q.st->done)
+        return;
+    const int id = blockIdx.x * kPgsBlock + threadIdx.x;
+    if (id < 9 * Q.n_sblk) {
+        const int q = id / 9, ij = id - 9 * q, i = ij / 3, j = ij - 3 * i;
+        const size_t r = 3 * (size_t)Q.sb_rc[2 * q] + i, c = 3 * (size_t)Q.sb_rc[2 * q + 1] + j;
+        Q.S[r * Q.np + c] = pg_schur_entry(Q.J, Q.sb_rc, Q.sb_ptr, Q.sb_pair, Q.w, q, i, j);
+    } else if (id - 9 * Q.n_sblk < Q.np) {
+        const int a = id - 9 * Q.n_sblk;
+        Q.y[a] = (a < Q.n_s) ? pg_schur_rhs(Q.J, Q.g, a / 3, a % 3) : 0.0;
+    }
+}
+
+/* blocked right-looking LDL^T, panel p: the diagonal tile by one workgroup in LDS */
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_ldl_diag(PgSchurJob Q, int p)
+{
+    __shared__ double A[kPgsTile][kPgsTile + 1];
+    __shared__ double Lk[kPgsTile], Wk[kPgsTile];
+    if (Q.st->done)
+        return;
+    const int tid = threadIdx.x;
+    double* T = Q.S + ((size_t)p * kPgsTile) * Q.np + (size_t)p * kPgsTile;
+    for (int q = tid; q < kPgsTile * kPgsTile; q += kPgsBlock)
+        A[q / kPgsTile][q % kPgsTile] = T[(size_t)(q / kPgsTile) * Q.np + q % kPgsTile];
+    for (int k = 0; k < kPgsTile; ++k) {
+        __syncthreads();
+        if (tid > k && tid < kPgsTile) {
+            const double d = A[k][k], l = A[tid][k] / d;
+            A[tid][k] = l;
+            Lk[tid] = l;
+            Wk[tid] = l * d;
+        }
+        __syncthreads();
+        for (int q = tid; q < kPgsTile * kPgsTile; q += kPgsBlock) {
+            const int i = q / kPgsTile, j = q % kPgsTile;
+            if (j > k && j <= i)
+                A[i][j] -= Wk[i] * Lk[j];
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < kPgsTile * kPgsTile; q += kPgsBlock)
+        if (q % kPgsTile <= q / kPgsTile)
+            T[(size_t)(q / kPgsTile) * Q.np + q % kPgsTile] = A[q / kPgsTile][q % kPgsTile];
+}
+
+/* panel p: a thread per row below the diagonal tile; its (L d) values stay in registers */
+__global__ __launch_bounds__(64) void k_pgs_ldl_panel(PgSchurJob Q, int p)
+{
+    __shared__ double Ld[kPgsTile][kPgsTile];
+    __shared__ double dd[kPgsTile];
+    if (Q.st->done)
+        return;
+    const int j0 = p * kPgsTile;
+    for (int q = threadIdx.x; q < kPgsTile * kPgsTile; q += 64)
+        Ld[q / kPgsTile][q % kPgsTile] = Q.S[(size_t)(j0 + q / kPgsTile) * Q.np + j0 + q % kPgsTile];
+    __syncthreads();
+    if (threadIdx.x < kPgsTile)
+        dd[threadIdx.x] = Ld[threadIdx.x][threadIdx.x];
+    __syncthreads();
+    const int r = j0 + kPgsTile + blockIdx.x * 64 + threadIdx.x;
+    if (r >= Q.np)
+        return;
+    double* row = Q.S + (size_t)r * Q.np + j0;
+    double* wrow = Q.wp + (size_t)r * kPgsTile;
+    double w[kPgsTile];
+#pragma unroll
+    for (int j = 0; j < kPgsTile; ++j) {
+        double v = row[j];
+#pragma unroll
+        for (int k = 0; k < j; ++k)
+            v -= w[k] * Ld[j][k];
+        const double l = v / dd[j];
+        w[j] = l * dd[j];
+        row[j] = l;
+        wrow[j] = w[j];
+    }
+}
+
+/* trailing update behind panel p: tile (ti, tj), ti >= tj > p, S_ij -= sum_k (L d)_ik L_jk with k
+ * ascending, a 3x3 register tile per thread, both operand tiles staged k-major in LDS */
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_ldl_update(PgSchurJob Q, int p)
+{
+    __shared__ double Wt[kPgsTile][kPgsTile + 1];
+    __shared__ double Lt[kPgsTile][kPgsTile + 1];
+    if (Q.st->done || blockIdx.x > blockIdx.y)
+        return;
+    const int ti = p + 1 + blockIdx.y, tj = p + 1 + blockIdx.x;
+    const int i0 = ti * kPgsTile, c0 = tj * kPgsTile, j0 = p * kPgsTile;
+    for (int q = threadIdx.x; q < kPgsTile * kPgsTile; q += kPgsBlock) {
+        const int r = q / kPgsTile, k = q % kPgsTile;
+        Wt[k][r] = Q.wp[(size_t)(i0 + r) * kPgsTile + k];
+        Lt[k][r] = Q.S[(size_t)(c0 + r) * Q.np + j0 + k];
+    }
+    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+    double acc[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            acc[a][b] = Q.S[(size_t)(i0 + ty + 16 * a) * Q.np + c0 + tx + 16 * b];
+    __syncthreads();
+#pragma unroll 4
+    for (int k = 0; k < kPgsTile; ++k) {
+        double wv[3], lv[3];
+        for (int a = 0; a < 3; ++a) {
+            wv[a] = Wt[k][ty + 16 * a];
+            lv[a] = Lt[k][tx + 16 * a];
+        }
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b)
+                acc[a][b] -= wv[a] * lv[b];
+    }
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            Q.S[(size_t)(i0 + ty + 16 * a) * Q.np + c0 + tx + 16 * b] = acc[a][b];
+}
+
+/* forward, diagonal and backward substitution on the factored S by one workgroup: per panel the
+ * diagonal tile on one wave (row i on lane i), then a thread per remaining row (forward) or
+ * column (backward). Forward subtracts in ascending k, backward in descending k. */
+__global__ __launch_bounds__(kPgsSolveBlock) void k_pgs_solve(PgSchurJob Q)
+{
+    __shared__ double blk[kPgsTile][kPgsTile + 1];
+    __shared__ double pan[kPgsTile];
+    if (Q.st->done)
+        return;
+    const int tid = threadIdx.x, nt = Q.np / kPgsTile, n = Q.n_s;
+    double* y = Q.y;
+    for (int p = 0; p < nt; ++p) {
+        const int j0 = p * kPgsTile;
+        for (int q = tid; q < kPgsTile * kPgsTile; q += kPgsSolveBlock)
+            blk[q / kPgsTile][q % kPgsTile] = Q.S[(size_t)(j0 + q / kPgsTile) * Q.np + j0 + q % kPgsTile];
+        __syncthreads();
+        if (tid < 64) {
+            double yi = (tid < kPgsTile) ? y[j0 + tid] : 0.0;
+            for (int j = 0; j < kPgsTile; ++j) {
+                const double yj = __shfl(yi, j, 64);
+                if (tid > j && tid < kPgsTile)
+                    yi -= blk[tid][j] * yj;
+            }
+            if (tid < kPgsTile) {
+                pan[tid] = yi;
+                y[j0 + tid] = yi;
+            }
+        }
+        __syncthreads();
+        for (int r = j0 + kPgsTile + tid; r < n; r += kPgsSolveBlock) {
+            const double* row = Q.S + (size_t)r * Q.np + j0;
+            double v = y[r];
+            for (int k = 0; k < kPgsTile; ++k)
+                v -= row[k] * pan[k];
+            y[r] = v;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < n; i += kPgsSolveBlock)
+        y[i] = y[i] / Q.S[(size_t)i * Q.np + i];
+    __syncthreads();
+    for (int p = nt - 1; p >= 0; --p) {
+        const int j0 = p * kPgsTile;
+        for (int q = tid; q < kPgsTile * kPgsTile; q += kPgsSolveBlock)
+            blk[q / kPgsTile][q % kPgsTile] = Q.S[(size_t)(j0 + q / kPgsTile) * Q.np + j0 + q % kPgsTile];
+        __syncthreads();
+        if (tid < 64) {
+            double xi = (tid < kPgsTile) ? y[j0 + tid] : 0.0;
+            for (int j = kPgsTile - 1; j >= 0; --j) {
+                const double xj = __shfl(xi, j, 64);
+                if (tid < j && j0 + j < n)
+                    xi -= blk[j][tid] * xj;
+            }
+            if (tid < kPgsTile) {
+                pan[tid] = xi;
+                y[j0 + tid] = xi;
+            }
+        }
+        __syncthreads();
+        const int kmax = (n - j0 < kPgsTile) ? n - j0 : kPgsTile;
+        for (int i = tid; i < j0; i += kPgsSolveBlock) {
+            double v = y[i];
+            for (int k = kmax - 1; k >= 0; --k)
+                v -= Q.S[(size_t)(j0 + k) * Q.np + i] * pan[k];
+            y[i] = v;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < n; i += kPgsSolveBlock)
+        Q.J.x[i] = y[i];
+}
+
+/* 3 n_local <= kPgsSmall: steps 2 and 3 in one workgroup, S in LDS */
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_small(PgSchurJob Q)
+{
+    __shared__ double A[kPgsSmall][kPgsSmall + 1];
+    __shared__ double y[kPgsSmall], Lk[kPgsSmall], Wk[kPgsSmall];
+    if (Q.st->done)
+        return;
+    const int tid = threadIdx.x, n = Q.n_s;
+    for (int q = tid; q < n * n; q += kPgsBlock)
+        A[q / n][q % n] = 0.0;
+    __syncthreads();
+    for (int id = tid; id < 9 * Q.n_sblk; id += kPgsBlock) {
+        const int q = id / 9, ij = id - 9 * q, i = ij / 3, j = ij - 3 * i;
+        A[3 * Q.sb_rc[2 * q] + i][3 * Q.sb_rc[2 * q + 1] + j] =
+            pg_schur_entry(Q.J, Q.sb_rc, Q.sb_ptr, Q.sb_pair, Q.w, q, i, j);
+    }
+    if (tid < n)
+        y[tid] = pg_schur_rhs(Q.J, Q.g, tid / 3, tid % 3);
+    for (int k = 0; k < n; ++k) {
+        __syncthreads();
+        if (tid > k && tid < n) {
+            const double d = A[k][k], l = A[tid][k] / d;
+            A[tid][k] = l;
+            Lk[tid] = l;
+            Wk[tid] = l * d;
+        }
+        __syncthreads();
+        const int m = n - k - 1;              /* rows and columns k + 1 .. n - 1 */
+        for (int q = tid; q < m * m; q += kPgsBlock) {
+            const int i = k + 1 + q / m, j = k + 1 + q % m;
+            if (j <= i)
+                A[i][j] -= Wk[i] * Lk[j];
+        }
+    }
+    for (int k = 0; k < n; ++k) {
+        __syncthreads();
+        if (tid > k && tid < n)
+            y[tid] -= A[tid][k] * y[k];
+    }
+    __syncthreads();
+    if (tid < n)
+        y[tid] = y[tid] / A[tid][tid];
+    for (int k = n - 1; k >= 0; --k) {
+        __syncthreads();
+        if (tid < k)
+            y[tid] -= A[k][tid] * y[k];
+    }
+    __syncthreads();
+    if (tid < n)
+        Q.J.x[tid] = y[tid];
+}
+
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_back(PgSchurJob Q)
+{
+    const int t = Q.J.n_local + blockIdx.x * kPgsBlock + threadIdx.x;
+    if (Q.st->done || t >= Q.J.n_nodes)
+        return;
+    pg_back_scan(Q.J, Q.g, Q.w, Q.J.x, t);
+}
+
+/* the true residual b - H delta and |b|^2 as per-workgroup partial sums; node += delta */
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_update(PgSchurJob Q)
+{
+    __shared__ double red[kPgsBlock / 64][2];
+    if (Q.st->done)
+        return;
+    const PgJob& J = Q.J;
+    const int i = blockIdx.x * kPgsBlock + threadIdx.x;
+    double v[2] = { 0.0, 0.0 };
+    if (i < J.n_vars) {
+        const double bi = J.b[i], r = bi - pg_row_times(J, i, J.x);
+        v[0] = r * r;
+        v[1] = bi * bi;
+        J.pose[i] += J.x[i];
+    }
+    pgs_block_sum<2>(v, red);
+    if (threadIdx.x == 0) {
+        Q.part[blockIdx.x] = v[0];
+        Q.part[Q.nb_vars + blockIdx.x] = v[1];
+    }
+}
+
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_error(PgSchurJob Q)
+{
+    __shared__ double red[kPgsBlock / 64][1];
+    if (Q.st->done)
+        return;
+    const PgJob& J = Q.J;
+    const int e = blockIdx.x * kPgsBlock + threadIdx.x;
+    double v[1] = { 0.0 };
+    if (e < J.n_edges)
+        v[0] = pg_edge_loss(J.pose + 3 * (size_t)J.enode[2 * e], J.pose + 3 * (size_t)J.enode[2 * e + 1],
+                            J.rel + 3 * (size_t)e, J.info + 9 * (size_t)e, J.loss_type, J.loss_scale);
+    pgs_block_sum<1>(v, red);
+    if (threadIdx.x == 0)
+        Q.part[2 * Q.nb_vars + blockIdx.x] = v[0];
+}
+
+/* one workgroup: the partial sums in a fixed shape, the step's trace record and the LM decision.
+ * first != 0: only the initial total error. */
+__global__ __launch_bounds__(kPgsBlock) void k_pgs_decide(PgSchurJob Q, int first)
+{
+    __shared__ double red[kPgsBlock / 64][3];
+    PgState& st = *Q.st;
+    if (st.done)
+        return;
+    double v[3] = { 0.0, 0.0, 0.0 };
+    if (!first)
+        for (int q = threadIdx.x; q < Q.nb_vars; q += kPgsBlock) {
+            v[0] += Q.part[q];
+            v[1] += Q.part[Q.nb_vars + q];
+        }
+    for (int q = threadIdx.x; q < Q.nb_edges; q += kPgsBlock)
+        v[2] += Q.part[2 * Q.nb_vars + q];
+    pgs_block_sum<3>(v, red);
+    if (threadIdx.x != 0)
+        return;
+    const double total = v[2];
+    if (first) {
+        st.initial = total;
+        Q.J.out[1] = total;
+        return;
+    }
+    double* o = Q.J.out + 4 + 5 * (size_t)st.steps;
+    o[0] = total;
+    o[1] = st.lambda;
+    o[2] = v[1];
+    o[3] = v[0];
+    o[4] = 0.0;
+    const int steps = st.steps + 1;
+    st.steps = steps;
+    st.total = total;
+    if (steps >= Q.J.iterations_max || fabs(st.prev - total) < Q.J.error_tolerance) {
+        st.done = 1;
+    } else {
+        st.lambda = (total < st.prev) ? st.lambda * 0.5 : st.lambda * 2.0;
+        st.prev = total;
+    }
+    Q.J.out[0] = (double)steps;
+    Q.J.out[2] = total;
+    Q.J.out[3] = st.lambda;
+}
+
 } /* namespace csm */
 #endif

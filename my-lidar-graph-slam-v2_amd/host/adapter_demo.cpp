@@ -93,7 +93,7 @@ static int run_builder(FILE* f, const int32_t* hdr)
     return 0;
 }
 
-/* mode 5: PoseGraphOptimizerLMHIP. File: int32 5, n_local, n_scan, n_edges, iterations_max, loss_type;
+/* mode 5 (ConjugateGradient) or 6 (SchurCholesky): PoseGraphOptimizerLMHIP. File: int32 mode, n_local, n_scan, n_edges, iterations_max, loss_type;
  * double error_tolerance, loss_scale, initial_lambda; double local[3 n_local], scan[3 n_scan];
  * n_edges csm_pose_graph_edge records. Optimizes twice on one optimizer (the second call starts from
  * the first's poses and lambda) and prints the poses and lambda after each call. */
@@ -120,7 +120,9 @@ static int run_pose_graph(FILE* f, const int32_t* hdr)
     }
     using Opt = PoseGraphOptimizerLMHIP;
     const bool cholRejected = !Opt::Create(Opt::SolverType::SparseCholesky, hdr[4], prm[0], prm[2], hdr[5], prm[1]);
-    auto opt = Opt::Create(Opt::SolverType::ConjugateGradient, hdr[4], prm[0], prm[2], hdr[5], prm[1]);
+    /* mode word 5: ConjugateGradient; 6: the same input and output with the direct SchurCholesky solver */
+    const Opt::SolverType solver = hdr[0] == 6 ? Opt::SolverType::SchurCholesky : Opt::SolverType::ConjugateGradient;
+    auto opt = Opt::Create(solver, hdr[4], prm[0], prm[2], hdr[5], prm[1]);
     if (!opt) {
         std::printf("{\"error\": \"no device\"}\n");
         return 3;
@@ -152,7 +154,7 @@ int main(int argc, char** argv)
     double step[3] = { 0.0, 0.0, 0.0 };
     if (!rd(f, hdr, 6))
         return 2;
-    if (hdr[0] == 4 || hdr[0] == 5) {
+    if (hdr[0] == 4 || hdr[0] == 5 || hdr[0] == 6) {
         const int rc = hdr[0] == 4 ? run_builder(f, hdr) : run_pose_graph(f, hdr);
         std::fclose(f);
         return rc;

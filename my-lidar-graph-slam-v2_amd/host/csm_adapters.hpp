@@ -974,25 +974,28 @@ struct EdgePose {
 
 /* PoseGraphOptimizerLM (inc/mapping/pose_graph_optimizer_lm.hpp:84-160) on the device. Create()
  * takes the constructor's arguments with the loss function as (CSM_PG_LOSS_*, scale); it returns null
- * for SolverType SparseCholesky (not provided), NumOfIterationsMax < 1 or no device. mLambda is kept
+ * for SolverType SparseCholesky (SimplicialLDLT: not provided; SchurCholesky is the direct solver that
+ * is), NumOfIterationsMax < 1 or no device. mLambda is kept
  * between Optimize calls, as the reference's member is. Node poses are { x, y, theta } in place of
  * Eigen::Vector3d. */
 class PoseGraphOptimizerLMHIP final {
 public:
-    enum class SolverType { SparseCholesky, ConjugateGradient };
+    enum class SolverType { SparseCholesky, ConjugateGradient, SchurCholesky };
 
     static std::unique_ptr<PoseGraphOptimizerLMHIP> Create(SolverType solverType, int numOfIterationsMax,
                                                            double errorTolerance, double initialLambda,
                                                            int lossType, double lossScale, int deviceId = 0)
     {
-        if (solverType != SolverType::ConjugateGradient || numOfIterationsMax < 1)
+        if ((solverType != SolverType::ConjugateGradient && solverType != SolverType::SchurCholesky) ||
+            numOfIterationsMax < 1)
             return nullptr;
         detail::CtxPtr ctx = detail::MakeContext(deviceId);
         if (!ctx)
             return nullptr;
         csm_pose_graph_lm_params prm {};
         prm.iterations_max = numOfIterationsMax;
-        prm.solver_type = CSM_PG_SOLVER_CONJUGATE_GRADIENT;
+        prm.solver_type = solverType == SolverType::SchurCholesky ? CSM_PG_SOLVER_SCHUR_CHOLESKY
+                                                                  : CSM_PG_SOLVER_CONJUGATE_GRADIENT;
         prm.loss_type = lossType;
         prm.error_tolerance = errorTolerance;
         prm.loss_scale = lossScale;
