@@ -314,7 +314,7 @@ int BatchGroup::plan()
      * two-slice plan with merged (weighted) entries, when the joint hash table of every query
      * fits a CU's LDS. Otherwise round 2's per-slice lists. */
     for (const BatchPrep& p : pp)
-        binj_lds = std::max(binj_lds, csm::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, csm::binj_hash_size(p.n)));
+        binj_lds = std::max(binj_lds, csm_launch::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, csm_launch::binj_hash_size(p.n)));
     joint = ctx->tune.joint && fine.pairs && fine.lists == 2 && fine.weighted &&
               binj_lds <= 150 * 1024;     /* up to ~1,100 beams four binning workgroups share a CU, two up
                                                to ~2,200; one (the fine level's gain outweighs the slower
@@ -481,7 +481,7 @@ void BatchGroup::build_jobs(int k)
                 ctx->b_tiles.as<TileRec>() + p.tile_off, ctx->b_ntiles.as<int32_t>() + p.theta_off, flags,
                 joint ? 2 : lp[0].pairs ? 1 : 0);
     B.sorted_rc = H > 0 ? ctx->b_sorted_rc.as<uint32_t>() + p.hit_off : nullptr;
-    B.hash_size = joint ? csm::binj_hash_size(p.n) : bin_hash_size(p.n);
+    B.hash_size = joint ? csm_launch::binj_hash_size(p.n) : bin_hash_size(p.n);
     B.max_mult = lp[0].weighted ? kMaxMult : 1;
     B.lstride = lp[0].lstride;
 #ifdef CSM_BIN_TIMING
@@ -632,10 +632,9 @@ int BatchGroup::launch_chain()
     }
     if (joint) {
         ScopedTimer tm(ctx, "bin");
-        const int e = csm::launch_binj_batch(ctx->stream, ctx->device, reinterpret_cast<const BinJob*>(d_bj),
-                                             (n_theta_max + 1) / 2, nq, binj_lds);
-        if (e != 0)
-            return fail(ctx, CSM_EIO, "joint binning launch failed: %s", hipGetErrorString((hipError_t)e));
+        if ((rc = launched_ok(ctx, csm_launch::binj_batch(ctx->stream, ctx->device, (n_theta_max + 1) / 2, nq, binj_lds,
+                                                          reinterpret_cast<const BinJob*>(d_bj)), "joint binning")))
+            return rc;
     } else {
         ScopedTimer tm(ctx, "bin");
         if ((rc = launched_ok(ctx, csm_launch::bin_batch(ctx->stream, ctx->device, n_theta_max, nq, bin_lds,
@@ -699,10 +698,9 @@ int BatchGroup::launch_chain()
         {
             ScopedTimer tm(ctx, "score_fine");
             HIP_TRY(ctx, hipMemsetAsync(counts, 0, 8, ctx->stream));
-            const int e = csm::launch_bound_select(ctx->stream, fine_jobs, nq, ncb, split_cb, items0, items1, counts,
-                                                   (uint32_t)blocks_total, round);
-            if (e != 0)
-                return fail(ctx, CSM_EIO, "k_bound_select launch failed: %s", hipGetErrorString((hipError_t)e));
+            if ((rc = launched_ok(ctx, csm_launch::bound_select(ctx->stream, fine_jobs, nq, ncb, split_cb, items0, items1,
+                                                                counts, (uint32_t)blocks_total, round), "bound selection")))
+                return rc;
             if ((rc = launch_score_batch(ctx, fine_jobs, nq, lp[0], n_theta_max, 1, 0, &list)))
                 return rc;
         }

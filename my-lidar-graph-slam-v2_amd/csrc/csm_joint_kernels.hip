@@ -23,10 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <utility>
 
 #include "csm_score_common.hpp"
 #include "csm_joint.hpp"
@@ -1197,63 +1194,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_score_joint_list(const ScoreJob* 
 
 /* ------------------------------------------------------------------ host launchers */
 
-namespace {
-
-/* Dynamic LDS above 64 KB needs the function attribute; process-wide, only ever raised. */
-hipError_t grant_lds(int device, const void* fn, size_t bytes)
-{
-    if (bytes <= 64 * 1024)
-        return hipSuccess;
-    static std::mutex guard;
-    static std::map<std::pair<int, const void*>, size_t> granted;
-    std::lock_guard<std::mutex> lock(guard);
-    size_t& have = granted[{ device, fn }];
-    if (bytes > have) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess)
-            return e;
-        have = bytes;
-    }
-    return hipSuccess;
-}
-
-template <int LS, int R>
-hipError_t launch_joint(const csm::JointLaunch& L)
-{
-    if (L.items) {
-        auto list_kernel = csm::k_score_joint_list<LS, R>;
-        const hipError_t e = grant_lds(L.device, reinterpret_cast<const void*>(list_kernel), L.lds_bytes);
-        if (e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(list_kernel, dim3(L.list_blocks), dim3(csm::kBlock), L.lds_bytes, L.stream, L.jobs_dev,
-                           L.cbx, L.groups, L.lane_map, csm::BlockBase{ L.row_base, L.cb_base, L.ncb }, L.items,
-                           L.item_count);
-        return hipGetLastError();
-    }
-    auto kernel = L.fp32 ? csm::k_score_jointf_batch<LS, R> : csm::k_score_joint_batch<LS, R>;
-    const hipError_t e = grant_lds(L.device, reinterpret_cast<const void*>(kernel), L.lds_bytes);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(kernel, L.grid, dim3(csm::kBlock), L.lds_bytes, L.stream, L.jobs_dev, L.cbx, L.groups,
-                       L.lane_map, L.xcd_map, csm::BlockBase{ L.row_base, L.cb_base, L.ncb });
-    return hipGetLastError();
-}
-
-template <int LS, int R>
-hipError_t launch_joint_one_t(const csm::JointLaunch& L, const csm::ScoreJob& job, int n_pairs)
-{
-    auto kernel = csm::k_score_joint_one<LS, R>;
-    const hipError_t e = grant_lds(L.device, reinterpret_cast<const void*>(kernel), L.lds_bytes);
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)n_pairs * L.grid.x), dim3(csm::kBlock), L.lds_bytes, L.stream, job, L.cbx,
-                       L.groups, L.lane_map, n_pairs, csm::BlockBase{ L.row_base, L.cb_base, L.ncb });
-    return hipGetLastError();
-}
-
-} /* namespace */
-
-namespace csm {
+namespace csm_launch {
 
 /* load factor <= 3/4 when every beam of the two slices lands on a cell of its own (in practice a quarter
  * of that: 533 cells of 2160 beams for configs[1]); < 2^16 slots: the list holds 16-bit slot numbers */
@@ -1269,74 +1210,49 @@ size_t binj_lds_bytes(int tiles, int n_points, int hash_size)
     return 20 * ntp + 12 * (size_t)hash_size + 2 * (size_t)(2 * n_points) + 16;
 }
 
-int launch_binj_batch(hipStream_t stream, int device, const BinJob* jobs_dev, int n_pairs_max, int n_jobs,
-                      size_t lds_bytes)
+int binj_batch(hipStream_t s, int device, int n_pairs_max, int n_jobs, size_t lds, const BinJob* jobs)
 {
-    const hipError_t e = grant_lds(device, reinterpret_cast<const void*>(k_binj_batch), lds_bytes);
-    if (e != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(k_binj_batch, dim3(n_pairs_max, n_jobs), dim3(kBinjBlock), lds_bytes, stream, jobs_dev);
-    return (int)hipGetLastError();
+    return launch_lds(device, k_binj_batch, dim3(n_pairs_max, n_jobs), dim3(kBinjBlock), lds, s, jobs);
 }
 
-int launch_binj_one(hipStream_t stream, int device, const BinJob& job, int n_pairs, size_t lds_bytes)
+int binj_one(hipStream_t s, int device, int n_pairs, size_t lds, const BinJob& job)
 {
-    const hipError_t e = grant_lds(device, reinterpret_cast<const void*>(k_binj_one), lds_bytes);
-    if (e != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(k_binj_one, dim3(n_pairs, 1), dim3(kBinjBlock), lds_bytes, stream, job);
-    return (int)hipGetLastError();
+    return launch_lds(device, k_binj_one, dim3(n_pairs, 1), dim3(kBinjBlock), lds, s, job);
 }
 
-#define JOINT_CASE(LS)                                                                 \
-    if (L.ls == LS && L.R == 8)                                                        \
-        return (int)launch_joint<LS, 8>(L);                                            \
-    if (L.ls == LS && L.R == 6)                                                        \
-        return (int)launch_joint<LS, 6>(L);
-#define JOINT_ONE_CASE(LS)                                                             \
-    if (L.ls == LS && L.R == 8)                                                        \
-        return (int)launch_joint_one_t<LS, 8>(L, job, n_pairs);                        \
-    if (L.ls == LS && L.R == 6)                                                        \
-        return (int)launch_joint_one_t<LS, 6>(L, job, n_pairs);
+int joint_batch(const ScoreLaunch& a, const ScoreJob* jobs)
+{
+    return match_pair_shape(a, [&](auto ls, auto r) {
+        if (a.items)
+            return launch_lds(a.device, k_score_joint_list<ls, r>, dim3(a.blocks), dim3(kBlock), a.lds, a.stream, jobs,
+                              a.cbx, a.groups, a.lane_map, a.bb, a.items, a.count);
+        return launch_lds(a.device, a.fp32 ? k_score_jointf_batch<ls, r> : k_score_joint_batch<ls, r>,
+                          dim3(a.grid.x, (a.grid.y + 1) / 2, a.grid.z), dim3(kBlock), a.lds, a.stream, jobs, a.cbx,
+                          a.groups, a.lane_map, a.xcd_map, a.bb);
+    });
+}
 
-int launch_expand_pairs_f(hipStream_t stream, const uint16_t* cells, int rows, int cols, int pitch, float* xgf,
-                          int xg_prows, int xg_pitch, int pad)
+int joint_one(const ScoreLaunch& a, const ScoreJob& job, int n_pairs)
+{
+    return match_pair_shape(a, [&](auto ls, auto r) {
+        return launch_lds(a.device, k_score_joint_one<ls, r>, dim3((unsigned)n_pairs * a.grid.x), dim3(kBlock), a.lds,
+                          a.stream, job, a.cbx, a.groups, a.lane_map, n_pairs, a.bb);
+    });
+}
+
+int bound_select(hipStream_t s, const ScoreJob* jobs, int n_jobs, int ncb, int split_cb, uint32_t* items0,
+                 uint32_t* items1, uint32_t* counts, uint32_t cap, int round)
+{
+    return launch(k_bound_select, dim3(n_jobs), dim3(256), s, jobs, ncb, split_cb, items0, items1, counts, cap, round);
+}
+
+int expand_pairs_f(hipStream_t s, const uint16_t* cells, int rows, int cols, int pitch, float* xgf, int xg_prows,
+                   int xg_pitch, int pad)
 {
     const size_t total = (size_t)xg_prows * xg_pitch;
     const int blocks = (int)(total + 255 < 4096 * 256 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_expand_pairs_f, dim3(blocks), dim3(256), 0, stream, cells, rows, cols, pitch,
-                       reinterpret_cast<float2*>(xgf), xg_prows, xg_pitch, pad);
-    return (int)hipGetLastError();
+    return launch(k_expand_pairs_f, dim3(blocks), dim3(256), s, cells, rows, cols, pitch,
+                  reinterpret_cast<float2*>(xgf), xg_prows, xg_pitch, pad);
 }
 
-int launch_bound_select(hipStream_t stream, const ScoreJob* jobs_dev, int n_jobs, int ncb, int split_cb,
-                        uint32_t* items0, uint32_t* items1, uint32_t* counts, uint32_t cap, int round)
-{
-    hipLaunchKernelGGL(k_bound_select, dim3(n_jobs), dim3(256), 0, stream, jobs_dev, ncb, split_cb, items0, items1,
-                       counts, cap, round);
-    return (int)hipGetLastError();
-}
-
-int launch_joint_batch(const JointLaunch& L)
-{
-#ifdef CSM_FAST_BUILD
-    JOINT_CASE(150) JOINT_CASE(156)
-#else
-    JOINT_CASE(86) JOINT_CASE(98) JOINT_CASE(118) JOINT_CASE(124) JOINT_CASE(130) JOINT_CASE(150)
-    JOINT_CASE(156) JOINT_CASE(162) JOINT_CASE(182)
-#endif
-    return -1;      /* no instantiation for this row pitch */
-}
-
-int launch_joint_one(const JointLaunch& L, const ScoreJob& job, int n_pairs)
-{
-#ifdef CSM_FAST_BUILD
-    JOINT_ONE_CASE(150) JOINT_ONE_CASE(156)
-#else
-    JOINT_ONE_CASE(86) JOINT_ONE_CASE(98) JOINT_ONE_CASE(118) JOINT_ONE_CASE(124) JOINT_ONE_CASE(130) JOINT_ONE_CASE(150)
-    JOINT_ONE_CASE(156) JOINT_ONE_CASE(162) JOINT_ONE_CASE(182)
-#endif
-    return -1;
-}
-
-} /* namespace csm */
+} /* namespace csm_launch */

@@ -1,311 +1,164 @@
 /* csm_launch.hip -- the translation unit of the per-slice kernels (csm_kernels.hip) and their launch
- * wrappers (csm_launch.hpp): template dispatch of the scoring kernels by (row pitch, rows per lane,
- * stride kind, weighted), the dynamic-LDS attribute, plain wrappers for everything else. */
+ * wrappers (csm_launch.hpp): dispatch of the scoring kernels over the shape tables (row pitch, rows per lane,
+ * stride kind) and the weighted flag, plain wrappers for everything else. */
 #include <hip/hip_runtime.h>
-
-#include <map>
-#include <mutex>
-#include <utility>
 
 #include "csm_kernels.hip"
 #include "csm_launch.hpp"
 
 namespace csm_launch {
 
-namespace {
-
-/* Dynamic LDS above 64 KB needs the function attribute. It is a driver call and
- * it belongs to the function on a device, not to a context: one process-wide
- * table, only ever raised (a smaller value set by another context would make
- * a larger launch of this one fail). */
-template <typename K>
-hipError_t set_lds(int device, K kernel, size_t bytes)
-{
-    if (bytes <= 64 * 1024)
-        return hipSuccess;
-    static std::mutex guard;
-    static std::map<std::pair<int, const void*>, size_t> granted;
-    const void* fn = reinterpret_cast<const void*>(kernel);
-    std::lock_guard<std::mutex> lock(guard);
-    size_t& have = granted[{ device, fn }];
-    if (bytes > have) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess)
-            return e;
-        have = bytes;
-    }
-    return hipSuccess;
-}
-
-} /* namespace */
-
-/* Template dispatch of the strided kernels (coarser levels): LSTRIDE in {128,192} x R in {1,2,4},
- * stride a power of two (MODE 1) or any (MODE 2). The stride-1 level is always a pair kernel
- * (PAIR_DISPATCH); round 1's stride-1 body survives only as the arg-max pass (k_argmax). */
-#define SCORE_CASE(LS, RR, ST, CALL)                                                   \
-    if (a.lstride == LS && a.R == RR && a.mode == ST) {                                \
-        CALL(LS, RR, ST, true);                                                        \
-    }
-#ifdef CSM_FAST_BUILD
-/* tuning builds (tools/build_variant.sh): only the instantiations bench.py's configs[1] uses */
-#define SCORE_DISPATCH(CALL)                                                           \
-    do {                                                                               \
-        SCORE_CASE(192, 1, 1, CALL)                                                    \
-    } while (0)
-#else
-#define SCORE_DISPATCH(CALL)                                                           \
-    do {                                                                               \
-        SCORE_CASE(128, 1, 1, CALL) SCORE_CASE(128, 2, 1, CALL)                        \
-        SCORE_CASE(128, 4, 1, CALL) SCORE_CASE(192, 1, 1, CALL)                        \
-        SCORE_CASE(192, 2, 1, CALL) SCORE_CASE(192, 4, 1, CALL)                        \
-        SCORE_CASE(128, 1, 2, CALL) SCORE_CASE(128, 2, 2, CALL)                        \
-        SCORE_CASE(128, 4, 2, CALL) SCORE_CASE(192, 1, 2, CALL)                        \
-        SCORE_CASE(192, 2, 2, CALL) SCORE_CASE(192, 4, 2, CALL)                        \
-    } while (0)
-#endif
-
-#define CALL_SINGLE(LS, RR, ST, WW)                                                    \
-    do {                                                                               \
-        const hipError_t e_ = set_lds(a.device, k_score<LS, RR, ST, WW>, a.lds);       \
-        if (e_ != hipSuccess)                                                          \
-            return (int)e_;                                                            \
-        hipLaunchKernelGGL((k_score<LS, RR, ST, WW>), a.grid, dim3(kBlock), a.lds, a.stream, job, a.cbx, \
-                           a.groups, a.n_buf);                                         \
-        return (int)hipGetLastError();                                                 \
-    } while (0)
-
-#define CALL_BATCH(LS, RR, ST, WW)                                                     \
-    do {                                                                               \
-        const hipError_t e_ = set_lds(a.device, k_score_batch<LS, RR, ST, WW>, a.lds); \
-        if (e_ != hipSuccess)                                                          \
-            return (int)e_;                                                            \
-        hipLaunchKernelGGL((k_score_batch<LS, RR, ST, WW>), a.grid, dim3(kBlock), a.lds, a.stream, jobs, a.cbx, \
-                           a.groups, a.n_slices, a.n_buf);                             \
-        return (int)hipGetLastError();                                                 \
-    } while (0)
-
+/* The strided kernels (coarser levels): kStridedLS x kStridedR, stride a power of two (MODE 1) or any
+ * (MODE 2), always on weighted entries. The stride-1 level is always a pair kernel; round 1's stride-1
+ * body survives only as the arg-max pass (k_argmax). */
 int score_strided(const ScoreLaunch& a, const ScoreJob& job)
 {
-    SCORE_DISPATCH(CALL_SINGLE);
-    return -1;
+    return match_strided_shape(a, [&](auto ls, auto r, auto mode) {
+        return launch_lds(a.device, k_score<ls, r, mode, true>, a.grid, dim3(kBlock), a.lds, a.stream, job, a.cbx,
+                          a.groups, a.n_buf);
+    });
 }
 
 int score_strided_batch(const ScoreLaunch& a, const ScoreJob* jobs)
 {
-    SCORE_DISPATCH(CALL_BATCH);
-    return -1;
+    return match_strided_shape(a, [&](auto ls, auto r, auto mode) {
+        return launch_lds(a.device, k_score_batch<ls, r, mode, true>, a.grid, dim3(kBlock), a.lds, a.stream, jobs,
+                          a.cbx, a.groups, a.n_slices, a.n_buf);
+    });
 }
 
-/* The pair-row fine kernels: row pitches (slots per pair row) x R in {8, 6} x weighted. */
-#define PAIR_CASE_R(LS, RR, CALL)                                                      \
-    if (a.lstride == LS && a.R == RR) {                                                \
-        if (a.weighted) {                                                              \
-            CALL(LS, RR, true);                                                        \
-        } else {                                                                       \
-            CALL(LS, RR, false);                                                       \
-        }                                                                              \
-    }
-#define PAIR_CASE(LS, CALL) PAIR_CASE_R(LS, 8, CALL) PAIR_CASE_R(LS, 6, CALL)
-#ifdef CSM_FAST_BUILD
-#define PAIR_DISPATCH(CALL)                                                            \
-    do {                                                                               \
-        PAIR_CASE(150, CALL) PAIR_CASE(156, CALL)                                      \
-    } while (0)
-#else
-#define PAIR_DISPATCH(CALL)                                                            \
-    do {                                                                               \
-        PAIR_CASE(86, CALL) PAIR_CASE(98, CALL) PAIR_CASE(118, CALL) PAIR_CASE(124, CALL) \
-        PAIR_CASE(130, CALL) PAIR_CASE(150, CALL) PAIR_CASE(156, CALL) PAIR_CASE(162, CALL) \
-        PAIR_CASE(182, CALL)                                                           \
-    } while (0)
-#endif
-
-#define CALL_PAIRS_SINGLE(LS, RR, WW)                                                  \
-    do {                                                                               \
-        const hipError_t e_ = set_lds(a.device, k_score_pairs<LS, RR, WW>, a.lds);     \
-        if (e_ != hipSuccess)                                                          \
-            return (int)e_;                                                            \
-        hipLaunchKernelGGL((k_score_pairs<LS, RR, WW>), a.theta_major ? dim3(a.grid.y, a.grid.x, 1) : a.grid, \
-                           dim3(kBlock), a.lds, a.stream, job, a.cbx, a.groups, a.theta_major, a.lane_map); \
-        return (int)hipGetLastError();                                                 \
-    } while (0)
-
-#define CALL_PAIRS_BATCH(LS, RR, WW)                                                   \
-    do {                                                                               \
-        if (a.lists == 2) {                                                            \
-            const hipError_t e_ = set_lds(a.device, k_score_pairs2_batch<LS, RR, WW>, a.lds); \
-            if (e_ != hipSuccess)                                                      \
-                return (int)e_;                                                        \
-            hipLaunchKernelGGL((k_score_pairs2_batch<LS, RR, WW>),                     \
-                               dim3(a.grid.x, (a.grid.y + 1) / 2, a.grid.z), dim3(kBlock), a.lds, \
-                               a.stream, jobs, a.cbx, a.groups, a.lane_map, a.xcd_map, a.bb); \
-        } else {                                                                       \
-            const hipError_t e_ = set_lds(a.device, k_score_pairs_batch<LS, RR, WW>, a.lds); \
-            if (e_ != hipSuccess)                                                      \
-                return (int)e_;                                                        \
-            hipLaunchKernelGGL((k_score_pairs_batch<LS, RR, WW>), a.grid, dim3(kBlock), a.lds, \
-                               a.stream, jobs, a.cbx, a.groups, a.lane_map, a.xcd_map, a.bb); \
-        }                                                                              \
-        return (int)hipGetLastError();                                                 \
-    } while (0)
-
-#define CALL_PAIRS_LIST(LS, RR, WW)                                                    \
-    do {                                                                               \
-        const hipError_t e_ = set_lds(a.device, k_score_pairs_list<LS, RR, WW>, a.lds); \
-        if (e_ != hipSuccess)                                                          \
-            return (int)e_;                                                            \
-        hipLaunchKernelGGL((k_score_pairs_list<LS, RR, WW>), dim3(a.blocks), dim3(kBlock), a.lds, a.stream, job, \
-                           a.cbx, a.groups, a.ncb, a.lane_map, a.items, a.count);      \
-        return (int)hipGetLastError();                                                 \
-    } while (0)
+/* The pair-row fine kernels: kPairLS (slots per pair row) x kPairR x weighted. */
+template <class F>
+int match_pairs(const ScoreLaunch& a, F f)
+{
+    return match_pair_shape(a, [&](auto ls, auto r) {
+        return a.weighted ? f(ls, r, std::true_type()) : f(ls, r, std::false_type());
+    });
+}
 
 int score_pairs(const ScoreLaunch& a, const ScoreJob& job)
 {
-    PAIR_DISPATCH(CALL_PAIRS_SINGLE);
-    return -1;
+    return match_pairs(a, [&](auto ls, auto r, auto w) {
+        return launch_lds(a.device, k_score_pairs<ls, r, w>, a.theta_major ? dim3(a.grid.y, a.grid.x, 1) : a.grid,
+                          dim3(kBlock), a.lds, a.stream, job, a.cbx, a.groups, a.theta_major, a.lane_map);
+    });
 }
 
 int score_pairs_batch(const ScoreLaunch& a, const ScoreJob* jobs)
 {
-    PAIR_DISPATCH(CALL_PAIRS_BATCH);
-    return -1;
+    return match_pairs(a, [&](auto ls, auto r, auto w) {
+        if (a.lists == 2)
+            return launch_lds(a.device, k_score_pairs2_batch<ls, r, w>, dim3(a.grid.x, (a.grid.y + 1) / 2, a.grid.z),
+                              dim3(kBlock), a.lds, a.stream, jobs, a.cbx, a.groups, a.lane_map, a.xcd_map, a.bb);
+        return launch_lds(a.device, k_score_pairs_batch<ls, r, w>, a.grid, dim3(kBlock), a.lds, a.stream, jobs, a.cbx,
+                          a.groups, a.lane_map, a.xcd_map, a.bb);
+    });
 }
 
 int score_pairs_list(const ScoreLaunch& a, const ScoreJob& job)
 {
-    PAIR_DISPATCH(CALL_PAIRS_LIST);
-    return -1;
+    return match_pairs(a, [&](auto ls, auto r, auto w) {
+        return launch_lds(a.device, k_score_pairs_list<ls, r, w>, dim3(a.blocks), dim3(kBlock), a.lds, a.stream, job,
+                          a.cbx, a.groups, a.ncb, a.lane_map, a.items, a.count);
+    });
 }
 
-/* only the lane <-> candidate mapping (cbx, groups, R) matters to the arg-max pass: k_argmax<128, 6 | 8> */
+/* only the lane <-> candidate mapping (cbx, groups, R) matters to the arg-max pass: k_argmax<128, R> */
 int argmax(const ScoreLaunch& a, const ScoreJob& job)
 {
-    if (a.R == 8)
-        hipLaunchKernelGGL((k_argmax<128, 8>), a.grid, dim3(kBlock), 0, a.stream, job, a.cbx, a.groups);
-    else if (a.R == 6)
-        hipLaunchKernelGGL((k_argmax<128, 6>), a.grid, dim3(kBlock), 0, a.stream, job, a.cbx, a.groups);
-    else
-        return -1;
-    return (int)hipGetLastError();
+    return match<kPairR>(a.R, [&](auto r) {
+        return launch(k_argmax<128, r>, a.grid, dim3(kBlock), a.stream, job, a.cbx, a.groups);
+    });
 }
 
 /* ---- the other kernels ---- */
 
 int bin(hipStream_t s, int device, int n_theta, size_t lds, const BinJob& job)
 {
-    const hipError_t e = set_lds(device, k_bin, lds);
-    if (e != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(k_bin, dim3(n_theta), dim3(kBinBlock), lds, s, job);
-    return (int)hipGetLastError();
+    return launch_lds(device, k_bin, dim3(n_theta), dim3(kBinBlock), lds, s, job);
 }
 
 int bin_batch(hipStream_t s, int device, int n_theta_max, int n_jobs, size_t lds, const BinJob* jobs)
 {
-    const hipError_t e = set_lds(device, k_bin_batch, lds);
-    if (e != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(k_bin_batch, dim3(n_theta_max, n_jobs), dim3(kBinBlock), lds, s, jobs);
-    return (int)hipGetLastError();
+    return launch_lds(device, k_bin_batch, dim3(n_theta_max, n_jobs), dim3(kBinBlock), lds, s, jobs);
 }
 
 int zero_if_band(hipStream_t s, int blocks, const ZeroJob& job)
 {
-    hipLaunchKernelGGL(k_zero_if_band, dim3(blocks, 1), dim3(256), 0, s, job);
-    return (int)hipGetLastError();
+    return launch(k_zero_if_band, dim3(blocks, 1), dim3(256), s, job);
 }
 
 int zero_if_band_batch(hipStream_t s, int blocks, int n_jobs, const ZeroJob* jobs)
 {
-    hipLaunchKernelGGL(k_zero_if_band_batch, dim3(blocks, n_jobs), dim3(256), 0, s, jobs);
-    return (int)hipGetLastError();
+    return launch(k_zero_if_band_batch, dim3(blocks, n_jobs), dim3(256), s, jobs);
 }
 
 int finalize(hipStream_t s, int device, size_t lds, const FinalJob& job)
 {
-    const hipError_t e = set_lds(device, k_finalize, lds);
-    if (e != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(kBlock), lds, s, job);
-    return (int)hipGetLastError();
+    return launch_lds(device, k_finalize, dim3(1), dim3(kBlock), lds, s, job);
 }
 
 int finalize_batch(hipStream_t s, int device, int n_jobs, size_t lds, const FinalJob* jobs)
 {
-    const hipError_t e = set_lds(device, k_finalize_batch, lds);
-    if (e != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(k_finalize_batch, dim3(n_jobs), dim3(kBlock), lds, s, jobs);
-    return (int)hipGetLastError();
+    return launch_lds(device, k_finalize_batch, dim3(n_jobs), dim3(kBlock), lds, s, jobs);
 }
 
 int tie_replay_pick(hipStream_t s, int device, unsigned n, size_t lds, const TieJob& job)
 {
-    const hipError_t e = set_lds(device, k_tie_replay, lds);
-    if (e != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(k_tie_replay, dim3(n), dim3(kBlock), lds, s, job);
-    hipLaunchKernelGGL(k_tie_pick, dim3(1), dim3(64), 0, s, job);
-    return (int)hipGetLastError();
+    if (int e = launch_lds(device, k_tie_replay, dim3(n), dim3(kBlock), lds, s, job))
+        return e;
+    return launch(k_tie_pick, dim3(1), dim3(64), s, job);
 }
 
 int exact_scores(hipStream_t s, unsigned blocks, const ExactJob& job)
 {
-    hipLaunchKernelGGL(k_exact_scores, dim3(blocks), dim3(kBlock), 0, s, job);
-    return (int)hipGetLastError();
+    return launch(k_exact_scores, dim3(blocks), dim3(kBlock), s, job);
 }
 
 int literal_scan(hipStream_t s, const LiteralJob& job)
 {
-    hipLaunchKernelGGL(k_csm_literal_scan, dim3(1), dim3(64), 0, s, job);
-    return (int)hipGetLastError();
+    return launch(k_csm_literal_scan, dim3(1), dim3(64), s, job);
 }
 
 int boxmax_batch(hipStream_t s, dim3 grid, const BoxJob* jobs)
 {
-    hipLaunchKernelGGL(k_boxmax_batch, grid, dim3(256), 0, s, jobs);
-    return (int)hipGetLastError();
+    return launch(k_boxmax_batch, grid, dim3(256), s, jobs);
 }
 
 int expand_pairs(hipStream_t s, int blocks, const uint16_t* cells, int rows, int cols, int pitch, uint32_t* xg,
                  int prows, int xp, int pad)
 {
-    hipLaunchKernelGGL(k_expand_pairs, dim3(blocks), dim3(256), 0, s, cells, rows, cols, pitch,
-                       reinterpret_cast<uint2*>(xg), prows, xp, pad);
-    return (int)hipGetLastError();
+    return launch(k_expand_pairs, dim3(blocks), dim3(256), s, cells, rows, cols, pitch, reinterpret_cast<uint2*>(xg),
+                  prows, xp, pad);
 }
 
 int deblock(hipStream_t s, int blocks, const uint16_t* packed, const int32_t* slot, int log2_block, int block_cols,
             int rows, int cols, int pitch, uint16_t* cells, uint8_t* alloc, int n_blocks, int32_t* known_first)
 {
-    hipLaunchKernelGGL(k_deblock, dim3(blocks), dim3(256), 0, s, packed, slot, log2_block, block_cols, rows, cols,
-                       pitch, cells, alloc, n_blocks, known_first);
-    return (int)hipGetLastError();
+    return launch(k_deblock, dim3(blocks), dim3(256), s, packed, slot, log2_block, block_cols, rows, cols, pitch, cells,
+                  alloc, n_blocks, known_first);
 }
 
 int project(hipStream_t s, dim3 grid, const ProjJob& job)
 {
-    hipLaunchKernelGGL(k_project, grid, dim3(kBlock), 0, s, job);
-    return (int)hipGetLastError();
+    return launch(k_project, grid, dim3(kBlock), s, job);
 }
 
 int project_batch(hipStream_t s, dim3 grid, const ProjJob* jobs)
 {
-    hipLaunchKernelGGL(k_project_batch, grid, dim3(kBlock), 0, s, jobs);
-    return (int)hipGetLastError();
+    return launch(k_project_batch, grid, dim3(kBlock), s, jobs);
 }
 
 int grid_scores_pick(hipStream_t s, int blocks, const GridSearchJob& job)
 {
-    hipLaunchKernelGGL(k_grid_scores, dim3(blocks), dim3(kBlock), 0, s, job);
-    hipLaunchKernelGGL(k_grid_pick, dim3(blocks), dim3(kBlock), 0, s, job);
-    return (int)hipGetLastError();
+    if (int e = launch(k_grid_scores, dim3(blocks), dim3(kBlock), s, job))
+        return e;
+    return launch(k_grid_pick, dim3(blocks), dim3(kBlock), s, job);
 }
 
 int scatter_records(hipStream_t s, const csm_result* src, const int32_t* idx, csm_result* dst, int n)
 {
-    hipLaunchKernelGGL(k_scatter_records, dim3((n + 255) / 256), dim3(256), 0, s, src, idx, dst, n);
-    return (int)hipGetLastError();
+    return launch(k_scatter_records, dim3((n + 255) / 256), dim3(256), s, src, idx, dst, n);
 }
 
 } /* namespace csm_launch */

@@ -112,7 +112,6 @@ ExactJob exact_job(const DeviceGrid& g, const uint16_t* cells, int n_theta, int 
                    int nx, int ny, int stride, const double* lut, double* out_score, uint32_t* out_k);
 int launched_ok(csm_ctx* ctx, int e, const char* what);
 csm_launch::ScoreLaunch score_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, size_t lds);
-csm::JointLaunch joint_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, const uint16_t* lane_map);
 int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out);
 int launch_score(csm_ctx* ctx, const ScoreJob& job, const PassPlan& pp, int n_theta, int n_slices);
 int launch_score_list(csm_ctx* ctx, const ScoreJob& job, const PassPlan& pp, const uint32_t* items,

@@ -242,55 +242,52 @@ __global__ __launch_bounds__(256) void k_reduce_items(const BlockBest* __restric
     }
 }
 
-int launch_phase_map(hipStream_t stream, const uint16_t* level, int rows, int cols, int level_pitch, int L,
-                     int hp, int wp, int pad, uint16_t* out, int pitch)
+} /* namespace csm */
+
+namespace csm_launch {
+
+int phase_map(hipStream_t s, const uint16_t* level, int rows, int cols, int level_pitch, int L, int hp, int wp,
+              int pad, uint16_t* out, int pitch)
 {
     const size_t total = (size_t)L * hp * pitch;
     const int blocks = (int)(total + 255 < (size_t)8192 * 256 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(k_phase_map, dim3(blocks), dim3(256), 0, stream, level, rows, cols, level_pitch, L, hp, wp,
-                       pad, out, pitch);
-    return (int)hipGetLastError();
+    return launch(k_phase_map, dim3(blocks), dim3(256), s, level, rows, cols, level_pitch, L, hp, wp, pad, out, pitch);
 }
 
-int launch_phase_hits(hipStream_t stream, const int32_t* col, const int32_t* row, size_t n, int x_lo, int y_lo,
-                      int L, int hp, int wp, int pad, int rows_c, int cols_c, int win_x, int win_y, int32_t* col_out,
-                      int32_t* row_out)
+int phase_hits(hipStream_t s, const int32_t* col, const int32_t* row, size_t n, int x_lo, int y_lo, int L, int hp,
+               int wp, int pad, int rows_c, int cols_c, int win_x, int win_y, int32_t* col_out, int32_t* row_out)
 {
     const int blocks = (int)(n + 255 < (size_t)4096 * 256 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_phase_hits, dim3(blocks), dim3(256), 0, stream, col, row, n, x_lo, y_lo, L, hp, wp, pad,
-                       rows_c, cols_c, win_x, win_y, col_out, row_out);
-    return (int)hipGetLastError();
+    return launch(k_phase_hits, dim3(blocks), dim3(256), s, col, row, n, x_lo, y_lo, L, hp, wp, pad, rows_c, cols_c,
+                  win_x, win_y, col_out, row_out);
 }
 
-int launch_coarse_best(hipStream_t stream, const TwoPhaseJob& job)
+int coarse_best(hipStream_t s, const TwoPhaseJob& job)
 {
     const size_t total = (size_t)job.n_theta * job.nxs * job.nys;
     const int blocks = (int)(total + 255 < (size_t)2048 * 256 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_coarse_best, dim3(blocks), dim3(256), 0, stream, job);
-    return (int)hipGetLastError();
+    return launch(k_coarse_best, dim3(blocks), dim3(256), s, job);
 }
 
-int launch_fine_under_best(hipStream_t stream, const TwoPhaseJob& job)
+int fine_under_best(hipStream_t s, const TwoPhaseJob& job)
 {
-    hipLaunchKernelGGL(k_fine_under_best, dim3(1), dim3(1024), 0, stream, job);
-    return (int)hipGetLastError();
+    return launch(k_fine_under_best, dim3(1), dim3(1024), s, job);
 }
 
-int launch_mark_blocks(hipStream_t stream, const TwoPhaseJob& job)
+int mark_blocks(hipStream_t s, const TwoPhaseJob& job)
 {
     const int total = job.n_theta * job.ncb;
     const size_t nodes = (size_t)job.n_theta * job.nxs * job.nys;
     const int blocks = (int)(nodes + 255 < (size_t)4096 * 256 ? (nodes + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_mark_nodes, dim3(blocks), dim3(256), 0, stream, job);
-    hipLaunchKernelGGL(k_compact_blocks, dim3((total + 255) / 256), dim3(256), 0, stream, job);
-    return (int)hipGetLastError();
+    if (int e = launch(k_mark_nodes, dim3(blocks), dim3(256), s, job))
+        return e;
+    return launch(k_compact_blocks, dim3((total + 255) / 256), dim3(256), s, job);
 }
 
-int launch_reduce_items(hipStream_t stream, const BlockBest* block_best, const uint32_t* items, const uint32_t* count,
-                        uint32_t cap, int ncb, BlockBest* out)
+int reduce_items(hipStream_t s, const BlockBest* block_best, const uint32_t* items, const uint32_t* count,
+                 uint32_t cap, int ncb, BlockBest* out)
 {
-    hipLaunchKernelGGL(k_reduce_items, dim3(kReducedBest), dim3(256), 0, stream, block_best, items, count, cap, ncb, out);
-    return (int)hipGetLastError();
+    return launch(k_reduce_items, dim3(kReducedBest), dim3(256), s, block_best, items, count, cap, ncb, out);
 }
 
-} /* namespace csm */
+} /* namespace csm_launch */

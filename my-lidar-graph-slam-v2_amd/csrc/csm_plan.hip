@@ -171,15 +171,15 @@ bool plan_pass(const Tuning& tune, int nx, int ny, int stride, PassPlan* out)
     p.cbx = ceil_div(nx, nb);
     p.ncbx = ceil_div(nx, p.cbx);
     const int need = kTile + 8 + (p.cbx - 1) * stride;
-    const int cand_ls[] = { 96, 128, 160, 192 };
-    for (int ls : cand_ls) {
-        /* phase-major layout: column phase p owns floor(ls / stride) cells */
-        const int need8 = (need + 7) & ~7;
-        if ((ls / stride) * stride < need8 || (strided && ls != 128 && ls != 192))
-            continue;
-        p.lstride = ls;
-        break;
-    }
+    /* phase-major layout: column phase p owns floor(ls / stride) cells; strided passes take the pitches
+     * (and below, the rows per lane) the strided kernels are built for (csm_launch.hpp) */
+    static const int ls_fine[] = { 96, 128, 160, 192 };
+    const int* lss = strided ? csm_launch::kStridedLS : ls_fine;
+    const int nls = strided ? (int)std::size(csm_launch::kStridedLS) : 4;
+    const int need8 = (need + 7) & ~7;
+    for (int k = 0; k < nls && !p.lstride; ++k)
+        if ((lss[k] / stride) * stride >= need8)
+            p.lstride = lss[k];
     if (!p.lstride)
         return false;
     /* rows: stride-1 regions hold kTile + cby - 1 rows, strided ones
@@ -190,9 +190,8 @@ bool plan_pass(const Tuning& tune, int nx, int ny, int stride, PassPlan* out)
         return false;
     int g = std::max(1, kBlock / p.cbx);
     static const int r_fine[] = { 4, 5, 6, 7, 8 };
-    static const int r_strided[] = { 1, 2, 4 };
-    const int* rs = strided ? r_strided : r_fine;
-    const int nrs = strided ? 3 : 5;
+    const int* rs = strided ? csm_launch::kStridedR : r_fine;
+    const int nrs = strided ? (int)std::size(csm_launch::kStridedR) : 5;
     long best_cost = -1;
     for (int k = 0; k < nrs; ++k) {
         const int r = rs[k];
@@ -221,13 +220,10 @@ bool plan_pass(const Tuning& tune, int nx, int ny, int stride, PassPlan* out)
     return true;
 }
 
-/* The pair-row fine kernel (k_score_pairs<LS, 8, W>): LS = slots per pair row of
- * the LDS region = alignment column + 64-cell tile + cbx - 1 candidates, even
- * (16-byte rows for the LDS-DMA pieces). Instantiated for these LS; a candidate
- * block may be any width cbx <= LS - 65 (124: the conflict-free pitch of R = 6, cbx = 52,
- * the branch-and-bound detector's default window; 156: that of R = 6, cbx = 84, the 36-row
- * tail block of the frontend window). */
-const int kPairLS[] = { 86, 98, 118, 124, 130, 150, 156, 162, 182 };
+/* The pair-row fine kernels: their row pitches (kPairLS) and rows per lane (kPairR) are the tables of
+ * csm_launch.hpp, what the kernels are instantiated for. */
+using csm_launch::kPairLS;
+using csm_launch::kPairR;
 
 size_t pair_lds_bytes(int ls, int cby, int lists)
 {
@@ -248,11 +244,11 @@ bool plan_pass_pairs(const Tuning& tune, int nx, int ny, PassPlan* out, bool two
         return list_lds >= 0 ? pair_lds_bytes(ls, cby, 0) + (size_t)list_lds : pair_lds_bytes(ls, cby, lists);
     };
     double best = -1.0;
-    const int max_cbx = kPairLS[sizeof(kPairLS) / sizeof(kPairLS[0]) - 1] - 65;
+    const int max_cbx = kPairLS[std::size(kPairLS) - 1] - 65;
     /* R = candidate rows per lane: 8, or 6 where that covers the rows with fewer
      * multiply-adds per wave (52 rows: 9 groups x 6 instead of 7 x 8) */
     const int force_r = tune.pair_r, force_ncbx = tune.pair_ncbx, force_g = tune.pair_groups;   /* tuning builds */
-    for (int R : { 8, 6 })
+    for (int R : kPairR)
     for (int ncbx = ceil_div(nx, max_cbx); ncbx <= ceil_div(nx, max_cbx) + 2; ++ncbx) {
         if ((force_r && R != force_r) || (force_ncbx && ncbx != force_ncbx))
             continue;
@@ -550,7 +546,7 @@ ExactJob exact_job(const DeviceGrid& g, const uint16_t* cells, int n_theta, int 
     return j;
 }
 
-/* What the wrappers of csm_launch.hip return: a HIP error code, or -1 for "no kernel instantiated". */
+/* What every wrapper of the launch layer returns: a HIP error code, or -1 for "no kernel instantiated". */
 int launched_ok(csm_ctx* ctx, int e, const char* what)
 {
     if (e < 0)
@@ -571,28 +567,13 @@ csm_launch::ScoreLaunch score_launch(const csm_ctx* ctx, const PassPlan& pp, dim
     a.mode = pp.stride == 1 ? 0 : pp.log2s >= 0 ? 1 : 2;
     a.weighted = pp.weighted;
     a.lists = pp.lists;
+    a.fp32 = pp.fp32;
     a.cbx = pp.cbx;
     a.groups = pp.groups;
     a.grid = grid;
     a.lds = lds;
     a.ncb = pp.ncb();
     return a;
-}
-
-/* the fields of a csm::JointLaunch a pass plan decides */
-csm::JointLaunch joint_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, const uint16_t* lane_map)
-{
-    csm::JointLaunch L{};
-    L.stream = ctx->stream;
-    L.device = ctx->device;
-    L.grid = grid;
-    L.lds_bytes = pass_lds_bytes(pp);
-    L.ls = pp.lstride;
-    L.R = pp.R;
-    L.cbx = pp.cbx;
-    L.groups = pp.groups;
-    L.lane_map = lane_map;
-    return L;
 }
 
 /* Which candidate (lane group g, column dxi) a thread of a pair kernel owns. A ds_read_b64
@@ -758,31 +739,18 @@ int launch_pairs_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, const PassPlan& p
         return rc;
     /* one job's workgroups on one XCD (k_score_pairs*_batch, xcd_block); CSM_TUNE_NO_XCD_MAP: identity */
     const int xcd_map = ctx->tune.xcd_map ? 1 : 0;
-    if (pp.joint) {
-        csm::JointLaunch L = joint_launch(ctx, pp, dim3(grid.x, (grid.y + 1) / 2, grid.z), lane_map);
-        L.jobs_dev = jobs_dev;
-        L.xcd_map = xcd_map;
-        L.row_base = bb.row_base;
-        L.cb_base = bb.cb_base;
-        L.ncb = bb.ncb;
-        L.fp32 = pp.fp32 ? 1 : 0;
-        if (list && !pp.fp32) {
-            L.items = list->items[which];
-            L.item_count = list->counts + which;
-            L.list_blocks = list->blocks;
-        }
-        const int e = csm::launch_joint_batch(L);
-        if (e < 0)
-            return fail(ctx, CSM_EINVAL, "internal: no joint kernel for LS %d R %d", pp.lstride, pp.R);
-        if (e != 0)
-            return fail(ctx, CSM_EIO, "joint fine kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        return CSM_OK;
-    }
     csm_launch::ScoreLaunch a = score_launch(ctx, pp, grid, pass_lds_bytes(pp));
     a.lane_map = lane_map;
     a.xcd_map = xcd_map;
     a.bb = bb;
-    return launched_ok(ctx, csm_launch::score_pairs_batch(a, jobs_dev), "pair-row batch");
+    if (!pp.joint)
+        return launched_ok(ctx, csm_launch::score_pairs_batch(a, jobs_dev), "pair-row batch");
+    if (list && !pp.fp32) {
+        a.items = list->items[which];
+        a.count = list->counts + which;
+        a.blocks = list->blocks;
+    }
+    return launched_ok(ctx, csm_launch::joint_batch(a, jobs_dev), "joint fine");
 }
 
 int launch_score_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, int n_jobs, const PassPlan& pp,
@@ -945,10 +913,9 @@ int ensure_xgrid_f(csm_ctx* ctx, DeviceGrid& g)
     if (int rc = grow(ctx, g.xgf, bytes, bytes, false))
         return rc;
     ScopedTimer tm(ctx, "expand");
-    const int e = csm::launch_expand_pairs_f(ctx->stream, g.levels[0].cells, g.rows, g.cols, g.pitch, g.xgf.as<float>(), prows,
-                                             g.xg_pitch, g.xg_pad);
-    if (e != 0)
-        return fail(ctx, CSM_EIO, "k_expand_pairs_f launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (int rc = launched_ok(ctx, csm_launch::expand_pairs_f(ctx->stream, g.levels[0].cells, g.rows, g.cols, g.pitch,
+                                                              g.xgf.as<float>(), prows, g.xg_pitch, g.xg_pad), "fp32 key copy"))
+        return rc;
     g.xgf_valid = true;
     return CSM_OK;
 }

@@ -21,7 +21,7 @@ bool joint_level_plan(const csm_ctx* ctx, const Plan& p, PassPlan* jp)
 {
     if (!ctx->tune.joint || !ctx->tune.two_slices || !p.fine.pairs || p.L != 1)
         return false;
-    const size_t binj_lds = csm::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, csm::binj_hash_size(p.n));
+    const size_t binj_lds = csm_launch::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, csm_launch::binj_hash_size(p.n));
     /* the exact joint kernel keeps kJRec entry words next to the window copy (not two kPbMax lists) */
     if (binj_lds > 150 * 1024 || !plan_pass_pairs(ctx->tune, p.nx, p.ny, jp, true, kJRec * 4) || jp->lists != 2)
         return false;
@@ -149,12 +149,12 @@ struct WindowRun {
         if ((rc = ensure(ctx, ctx->ntiles, (size_t)n_pairs * 8))) return rc;
         bj = bin_job(g, p, p.n_theta, p.n, max_tiles, hit_col, hit_row, ctx->sorted.as<uint32_t>(),
                      ctx->tiles.as<TileRec>(), ctx->ntiles.as<int32_t>(), flags, 2);
-        bj.hash_size = csm::binj_hash_size(p.n);
+        bj.hash_size = csm_launch::binj_hash_size(p.n);
         bj.max_mult = kMaxMult;
         bj.lstride = jp.lstride;
-        const size_t lds = csm::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, bj.hash_size);
+        const size_t lds = csm_launch::binj_lds_bytes(p.tiles_x * p.tiles_y, p.n, bj.hash_size);
         ScopedTimer tm(ctx, "bin");
-        return launched_ok(ctx, csm::launch_binj_one(ctx->stream, ctx->device, bj, n_pairs, lds), "joint binning");
+        return launched_ok(ctx, csm_launch::binj_one(ctx->stream, ctx->device, n_pairs, lds, bj), "joint binning");
     }
 
     /* The coarse level of an exhaustive window (L > 1), its sums into ctx->coarse_s / coarse_k. With
@@ -274,12 +274,10 @@ struct WindowRun {
         J.ncb = p.fine.ncb();
         J.flags = flags;
         ScopedTimer tm(ctx, "select");
-        int e = csm::launch_coarse_best(ctx->stream, J);
-        if (!e) e = csm::launch_fine_under_best(ctx->stream, J);
-        if (!e) e = csm::launch_mark_blocks(ctx->stream, J);
-        if (e)
-            return fail(ctx, CSM_EIO, "two-phase select launch failed: %s", hipGetErrorString((hipError_t)e));
-        return CSM_OK;
+        int e = csm_launch::coarse_best(ctx->stream, J);
+        if (!e) e = csm_launch::fine_under_best(ctx->stream, J);
+        if (!e) e = csm_launch::mark_blocks(ctx->stream, J);
+        return launched_ok(ctx, e, "two-phase select");
     }
 
     /* The window's record from n_records block records of the fine job; clears the next chain's flag word. */
@@ -345,9 +343,10 @@ int run_level_pass(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan&
     ScopedTimer tm(ctx, "score_coarse");
     if (!joint)
         return launch_score(ctx, fj, p.fine, p.n_theta, 1);
-    csm::JointLaunch L = joint_launch(ctx, jp, dim3(jp.ncb(), 1, 1), lane_map);
-    L.ncb = jp.ncb();
-    return launched_ok(ctx, csm::launch_joint_one(L, fj, (p.n_theta + 1) / 2), "joint level pass");
+    csm_launch::ScoreLaunch a = score_launch(ctx, jp, dim3(jp.ncb(), 1, 1), pass_lds_bytes(jp));
+    a.lane_map = lane_map;
+    a.bb = BlockBase{ 0, 0, jp.ncb() };
+    return launched_ok(ctx, csm_launch::joint_one(a, fj, (p.n_theta + 1) / 2), "joint level pass");
 }
 
 /* The fine level of a large window (L > 1) under a stored level: eligibility from the level's
@@ -373,8 +372,8 @@ int run_fine_under_level(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const
             return rc;
     }
     /* k_finalize reads kReducedBest records instead of one per block of the window */
-    if ((rc = launched_ok(ctx, csm::launch_reduce_items(ctx->stream, fj.block_best, list.items, list.count,
-                                                        list.cap, p.fine.ncb(), reduced),
+    if ((rc = launched_ok(ctx, csm_launch::reduce_items(ctx->stream, fj.block_best, list.items, list.count,
+                                                         list.cap, p.fine.ncb(), reduced),
                           "record reduction")))
         return rc;
     ctx->last_run.fine = fj;
@@ -417,10 +416,9 @@ int ensure_phase_map(csm_ctx* ctx, DeviceGrid& g, int level, int need, PhaseMap*
         return rc;
     base.cells = base.own.as<uint16_t>();
     pg.levels.push_back(std::move(base));
-    const int e = csm::launch_phase_map(ctx->stream, src, g.rows, g.cols, g.pitch, L, hp, wp, pad, pg.levels[0].cells,
-                                        pg.pitch);
-    if (e)
-        return fail(ctx, CSM_EIO, "k_phase_map launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (int rc = launched_ok(ctx, csm_launch::phase_map(ctx->stream, src, g.rows, g.cols, g.pitch, L, hp, wp, pad,
+                                                         pg.levels[0].cells, pg.pitch), "phase-major copy"))
+        return rc;
     pm.hp = hp;
     pm.wp = wp;
     pm.pad = pad;
@@ -480,11 +478,10 @@ int search_window(csm_ctx* ctx, DeviceGrid& g, const csm_window* w, const Plan& 
     int32_t* prow = pcol + hn;
     {
         ScopedTimer tm(ctx, "project");
-        const int e = csm::launch_phase_hits(ctx->stream, col_dev, row_dev, hn, p.x_lo, p.y_lo, p.L, pm->hp, pm->wp,
-                                             pm->pad, ceil_div(g.rows, p.L), ceil_div(g.cols, p.L), wc.win_x, wc.win_y,
-                                             pcol, prow);
-        if (e)
-            return fail(ctx, CSM_EIO, "k_phase_hits launch failed: %s", hipGetErrorString((hipError_t)e));
+        if ((rc = launched_ok(ctx, csm_launch::phase_hits(ctx->stream, col_dev, row_dev, hn, p.x_lo, p.y_lo, p.L, pm->hp,
+                                                          pm->wp, pm->pad, ceil_div(g.rows, p.L), ceil_div(g.cols, p.L),
+                                                          wc.win_x, wc.win_y, pcol, prow), "phase hits")))
+            return rc;
     }
     StoredLevel level;
     if ((rc = run_level_pass(ctx, *pm->grid, &wc, pc, pcol, prow, &level))) return rc;
