@@ -336,10 +336,10 @@ int csm_build_pyramid(csm_ctx* ctx, uint64_t map_id, const int32_t* win_sizes, i
         }
         g->levels.push_back(std::move(l));
     }
-    std::vector<PendingBox> pending;
+    PendingBoxes pending;
     for (int i = 1; i < n_levels; ++i)
         if (g->levels[i].owned())
-            pending.push_back({ g, i });
+            pending.jobs.push_back({ g, i });
     int rc = launch_box_jobs(ctx, pending);
     if (rc)
         return rc;
@@ -472,7 +472,7 @@ int csm_build_pyramids(csm_ctx* ctx, const uint64_t* map_ids, int32_t n_maps, co
     if (!ctx || !map_ids || n_maps < 1 || !win_sizes || n_levels < 1)
         return fail(ctx, CSM_EINVAL, "csm_build_pyramids: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<PendingBox> pending;
+    PendingBoxes pending;      /* an error return below leaves what it holds stale, not unwritten */
     for (int i = 0; i < n_maps; ++i) {
         DeviceGrid* g = find_grid(ctx, map_ids[i]);
         if (!g)

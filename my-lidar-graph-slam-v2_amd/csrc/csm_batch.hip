@@ -813,7 +813,7 @@ static int loop_batch(csm_ctx* ctx, const csm_loop_query* queries, int n_queries
     if (host_timing)
         fprintf(stderr, "[bnb batch] begin_records %8.3f ms\n", std::chrono::duration<double, std::milli>(t0 - tb0).count());
     std::vector<std::vector<int>> levels(n_queries, std::vector<int>(H + 1, 0));
-    std::vector<PendingBox> pending_levels;
+    PendingBoxes pending_levels;      /* an error return before the launch leaves what it holds stale */
     std::vector<double> max_range(n_queries, 0.0);
     {
         const int i = scans_finite_max(queries, n_queries, max_range.data());

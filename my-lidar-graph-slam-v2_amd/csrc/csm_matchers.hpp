@@ -59,6 +59,26 @@ struct PendingBox {
     int level;          /* index into grid->levels: its cells are the destination */
 };
 
+/* The levels one call collects. A collected level reads as built (a map that a call names twice is
+ * collected once) while its buffer still holds whatever hipMalloc handed out. So a list that goes
+ * away before launch_box_jobs has enqueued its kernel -- an error return in between: a later map of
+ * the call not resident, a window that does not fit it -- marks its levels stale: the next call that
+ * wants them builds them, and csm_download_level refuses them until then. */
+struct PendingBoxes {
+    std::vector<PendingBox> jobs;
+    bool launched = false;
+
+    PendingBoxes() = default;
+    PendingBoxes(const PendingBoxes&) = delete;
+    PendingBoxes& operator=(const PendingBoxes&) = delete;
+    ~PendingBoxes()
+    {
+        if (!launched)
+            for (const PendingBox& b : jobs)
+                b.grid->levels[b.level].stale = true;
+    }
+};
+
 /* Splits [0, n) over up to four host threads (the batch entries touch tens of
  * megabytes of scan data before anything can be launched); fn(lo, hi) must not
  * touch the context. */
@@ -122,10 +142,10 @@ int launch_pairs_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, const PassPlan& p
                        const JointList* list = nullptr, int which = 0);
 int launch_score_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, int n_jobs, const PassPlan& pp,
                        int n_theta_max, int n_slices, int theta_groups = 0, const JointList* list = nullptr);
-int launch_box_jobs(csm_ctx* ctx, const std::vector<PendingBox>& pending);
+int launch_box_jobs(csm_ctx* ctx, PendingBoxes& pending);
 int build_level(csm_ctx* ctx, DeviceGrid& g, int win, Level* out);
 int level_for_window(csm_ctx* ctx, DeviceGrid& g, int win, int* index,
-                     std::vector<PendingBox>* pending = nullptr);
+                     PendingBoxes* pending = nullptr);
 int ensure_xgrid(csm_ctx* ctx, DeviceGrid& g, int need_pad);
 int ensure_xgrid_f(csm_ctx* ctx, DeviceGrid& g);
 

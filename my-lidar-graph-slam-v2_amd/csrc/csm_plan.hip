@@ -794,43 +794,45 @@ int launch_score_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, int n_jobs, const
 }
 
 /* One launch for all pending levels (k_boxmax_batch). The job table is uploaded
- * from context-owned host memory. */
-int launch_box_jobs(csm_ctx* ctx, const std::vector<PendingBox>& pending)
+ * from context-owned host memory. The list counts as launched once every kernel is enqueued. */
+int launch_box_jobs(csm_ctx* ctx, PendingBoxes& pending)
 {
-    if (pending.empty())
+    const std::vector<PendingBox>& jobs = pending.jobs;
+    if (jobs.empty())
         return CSM_OK;
-    ctx->box_stage.resize(pending.size());
+    ctx->box_stage.resize(jobs.size());
     int rows_max = 0, pitch_max = 0;
-    for (size_t i = 0; i < pending.size(); ++i) {
-        const DeviceGrid& g = *pending[i].grid;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        const DeviceGrid& g = *jobs[i].grid;
         BoxJob& b = ctx->box_stage[i];
         b.src = g.levels[0].cells;
-        b.dst = g.levels[pending[i].level].cells;
+        b.dst = g.levels[jobs[i].level].cells;
         b.rows = g.rows;
         b.cols = g.cols;
         b.pitch = g.pitch;
-        b.win = g.levels[pending[i].level].win;
+        b.win = g.levels[jobs[i].level].win;
         rows_max = std::max(rows_max, g.rows);
         pitch_max = std::max(pitch_max, g.pitch);
     }
-    int rc = ensure(ctx, ctx->box_jobs, pending.size() * sizeof(BoxJob));
+    int rc = ensure(ctx, ctx->box_jobs, jobs.size() * sizeof(BoxJob));
     if (rc)
         return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->box_jobs.p, ctx->box_stage.data(), pending.size() * sizeof(BoxJob),
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->box_jobs.p, ctx->box_stage.data(), jobs.size() * sizeof(BoxJob),
                                 hipMemcpyHostToDevice, ctx->stream));
     ScopedTimer tm(ctx, "boxmax");
-    for (size_t first = 0; first < pending.size(); first += 65535) {      /* grid.z limit */
-        const unsigned nz = (unsigned)std::min<size_t>(65535, pending.size() - first);
+    for (size_t first = 0; first < jobs.size(); first += 65535) {      /* grid.z limit */
+        const unsigned nz = (unsigned)std::min<size_t>(65535, jobs.size() - first);
         const int e = csm_launch::boxmax_batch(ctx->stream, dim3(ceil_div(pitch_max, kBoxTC), ceil_div(rows_max, kBoxTR), nz),
                                                reinterpret_cast<const BoxJob*>(ctx->box_jobs.p) + first);
         if (e)
             return launched_ok(ctx, e, "box-maximum");
     }
+    pending.launched = true;
     return CSM_OK;
 }
 
 /* Prepares level `win` of g for building: into its own buffer when that is large enough, else
- * into a new one, and records it in `pending`; the caller launches. */
+ * into a new one. The caller records it in a PendingBoxes list and launches. */
 int build_level(csm_ctx* ctx, DeviceGrid& g, int win, Level* out)
 {
     if (win < 1 || win > g.rows || win > g.cols)
@@ -848,12 +850,13 @@ int build_level(csm_ctx* ctx, DeviceGrid& g, int win, Level* out)
 
 /* index of the level with this window; builds and appends it if missing. With
  * `pending` the launch is left to the caller (launch_box_jobs), so that many
- * levels of many maps share one launch. */
+ * levels of many maps share one launch; a caller that returns without launching
+ * leaves the levels it collected stale (PendingBoxes). */
 int level_for_window(csm_ctx* ctx, DeviceGrid& g, int win, int* index,
-                     std::vector<PendingBox>* pending)
+                     PendingBoxes* pending)
 {
-    std::vector<PendingBox> local;
-    std::vector<PendingBox>& todo = pending ? *pending : local;
+    PendingBoxes local;
+    std::vector<PendingBox>& todo = pending ? pending->jobs : local.jobs;
     auto finish = [&]() { return pending ? CSM_OK : launch_box_jobs(ctx, local); };
     for (size_t i = 0; i < g.levels.size(); ++i)
         if (g.levels[i].win == win) {
