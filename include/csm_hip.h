@@ -369,6 +369,53 @@ int  csm_correlative_match_batch(csm_ctx* ctx, const csm_loop_query* queries,
                                  int32_t n_queries, const csm_correlative_params* params,
                                  csm_summary* out);
 
+/* ---- the K best DISTINCT poses per window (beyond the reference, which keeps scoreMax only):
+ * a second peak almost as high as the first is how perceptual aliasing shows in the score volume.
+ *
+ * Candidates, key and eligibility are those of the single-best search: (t, x, y) over the extended
+ * domain n_theta x nx x ny (nx = ceil((2 win_x + 1) / L) L), key = 32268 K + 499 S, eligible iff the
+ * coarse node's known count >= min_known (L = 1: every candidate). Peak j is chosen among the eligible
+ * candidates that no peak p of 0..j-1 excludes (|t - p.t| <= excl_theta and |x - p.x| <= excl_x and
+ * |y - p.y| <= excl_y, in search steps, theta not wrapped): the greatest key, then the greatest f64
+ * beam-order score, then the first in the reference's sweep order. The list ends at k_max, when no
+ * candidate is left, or at the first peak whose score does not pass score_threshold (score > threshold,
+ * as `found`). Every candidate is scored exactly (the exhaustive chain, no bound pass, no coarse-first
+ * search) and the peaks are selected on the device in k_max rounds without a host round trip.
+ *
+ * Each record is a full csm_result: found = 1, offsets relative to the sensor pose, sum_values / known /
+ * key, tie_count = remaining eligible candidates sharing the key (> 1: CSM_FLAG_KEY_TIE, resolved by the
+ * f64 replay over them; CSM_FLAG_F64_TIE if several share the best f64 score too), score bit-exact.
+ * Peak 0 equals the record of csm_score_window / csm_correlative_match whenever that record carries
+ * neither CSM_FLAG_EDGE_BAND nor CSM_FLAG_LITERAL. For an edge-band window the peaks follow the closed
+ * form above (the literal pruning path is not replayed) and every record carries CSM_FLAG_EDGE_BAND.
+ * Entries past *n_peaks are zero (found / pose_found = 0).
+ * CSM_EINVAL: k_max outside 1..CSM_PEAKS_MAX, a negative radius or limit, a window of more than 1 << 26
+ * candidates, a single window whose score volume (6 bytes per candidate + 2 per coarse node) exceeds
+ * the scratch limit. Not provided: branch-and-bound peaks, the csm_group_* entries. */
+#define CSM_PEAKS_MAX 16
+typedef struct {
+    int32_t k_max;                       /* 1..CSM_PEAKS_MAX */
+    int32_t excl_x, excl_y, excl_theta;  /* >= 0, search steps; all 0: plain top-K */
+    int64_t scratch_limit_bytes;         /* 0 = default (1 GiB); batches are cut into chunks whose score
+                                            volumes fit (tests force several chunks with it) */
+} csm_peaks_params;
+
+/* hit_col / hit_row as csm_score_window takes them; out[k_max]. */
+int  csm_score_window_peaks(csm_ctx* ctx, uint64_t map_id, const csm_window* w,
+                            const int32_t* hit_col, const int32_t* hit_row,
+                            const csm_peaks_params* peaks, csm_result* out, int32_t* n_peaks);
+/* csm_correlative_match's set-up; out[k_max]: best_sensor_pose / estimated_pose per peak, computed as
+ * for the winner. */
+int  csm_correlative_peaks(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geom,
+                           const csm_scan* scan, const double initial_pose[3],
+                           const csm_correlative_params* params, const csm_peaks_params* peaks,
+                           csm_summary* out, int32_t* n_peaks);
+/* csm_correlative_match_batch's queries; out[n_queries * k_max] (query i: out[i * k_max ..]),
+ * n_peaks[n_queries]. All windows of a chunk are selected together, one launch per round. */
+int  csm_correlative_peaks_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
+                                 const csm_correlative_params* params, const csm_peaks_params* peaks,
+                                 csm_summary* out, int32_t* n_peaks);
+
 /* The raw records (csm_summary.raw) of the last csm_bnb_match_batch /
  * csm_correlative_match_batch call on this ctx, in query order, copied device
  * to device into dst_dev[n_queries] on the ctx stream (asynchronous): the
@@ -805,7 +852,8 @@ int  csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_er
  * the timed region undisturbed; 0: off. */
 int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
 /* Drains recorded events; returns total ms and launch count since the last
- * reset for kernel "score_fine" | "score_coarse" | "bin" | "finalize" | "boxmax". */
+ * reset for kernel "score_fine" | "score_coarse" | "bin" | "finalize" | "boxmax" |
+ * "peaks_coarse" | "peaks_select". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);
 int  csm_reset_kernel_timing(csm_ctx* ctx);

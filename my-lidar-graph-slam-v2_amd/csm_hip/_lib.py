@@ -195,6 +195,14 @@ class Window(C.Structure):
                 ("score_threshold", C.c_double)]
 
 
+PEAKS_MAX = 16
+
+
+class PeaksParams(C.Structure):
+    _fields_ = [("k_max", C.c_int32), ("excl_x", C.c_int32), ("excl_y", C.c_int32), ("excl_theta", C.c_int32),
+                ("scratch_limit_bytes", C.c_int64)]
+
+
 # name -> (restype, argtypes); mirrors include/csm_hip.h one to one
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -243,6 +251,12 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p]),
     "csm_correlative_match": (C.c_int, [_ctx, C.c_uint64, _P(Geometry), _P(Scan),
                                         C.c_void_p, _P(CorrelativeParams), _P(Summary)]),
+    "csm_score_window_peaks": (C.c_int, [_ctx, C.c_uint64, _P(Window), C.c_void_p, C.c_void_p, _P(PeaksParams),
+                                         _P(Result), _P(C.c_int32)]),
+    "csm_correlative_peaks": (C.c_int, [_ctx, C.c_uint64, _P(Geometry), _P(Scan), C.c_void_p,
+                                        _P(CorrelativeParams), _P(PeaksParams), _P(Summary), _P(C.c_int32)]),
+    "csm_correlative_peaks_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(CorrelativeParams),
+                                              _P(PeaksParams), _P(Summary), _P(C.c_int32)]),
     "csm_bnb_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,
                                       _P(BnbParams), _P(Summary)]),
     "csm_correlative_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,

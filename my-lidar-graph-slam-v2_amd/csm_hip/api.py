@@ -478,6 +478,67 @@ class Context:
                                                    _ptr(init), C.byref(p), C.byref(out)))
         return summary_to_dict(out)
 
+    @staticmethod
+    def peaks_params(k_max, excl=(0, 0, 0), scratch_limit_bytes=0):
+        """csm_peaks_params: excl = exclusion radii (x, y, theta) in search steps."""
+        return L.PeaksParams(k_max, excl[0], excl[1], excl[2], scratch_limit_bytes)
+
+    def score_window_peaks(self, map_id, window, hit_col, hit_row, k_max, excl=(0, 0, 0), scratch_limit_bytes=0):
+        """The K best distinct poses of one pre-projected window (csm_score_window_peaks): the list of
+        the peaks' records, best first."""
+        col = np.ascontiguousarray(hit_col, dtype=np.int32)
+        row = np.ascontiguousarray(hit_row, dtype=np.int32)
+        pk = self.peaks_params(k_max, excl, scratch_limit_bytes)
+        out = (L.Result * max(1, min(k_max, L.PEAKS_MAX)))()
+        n = C.c_int32(0)
+        self._check(self.lib.csm_score_window_peaks(self._ctx, map_id, C.byref(window), _ptr(col), _ptr(row),
+                                                    C.byref(pk), out, C.byref(n)))
+        return [result_to_dict(out[j]) for j in range(n.value)]
+
+    def correlative_peaks(self, map_id, geom, angles, ranges, rel_pose, init_pose, range_x, range_y, range_theta,
+                          low_resolution, k_max, excl=(0, 0, 0), score_threshold=0.0, known_rate_threshold=0.0,
+                          scratch_limit_bytes=0):
+        """correlative_match() returning the K best distinct poses (csm_correlative_peaks): a list of
+        summaries, best first."""
+        a, r = _f64(angles), _f64(ranges)
+        scan = L.Scan()
+        scan.angles = a.ctypes.data_as(C.POINTER(C.c_double))
+        scan.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
+        scan.n_points = a.size
+        scan.relative_sensor_pose[:] = list(rel_pose)
+        g = L.Geometry(*geom)
+        p = L.CorrelativeParams()
+        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
+        p.low_resolution = low_resolution
+        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        init = _f64(init_pose)
+        pk = self.peaks_params(k_max, excl, scratch_limit_bytes)
+        out = (L.Summary * max(1, min(k_max, L.PEAKS_MAX)))()
+        n = C.c_int32(0)
+        self._check(self.lib.csm_correlative_peaks(self._ctx, map_id, C.byref(g), C.byref(scan), _ptr(init),
+                                                   C.byref(p), C.byref(pk), out, C.byref(n)))
+        return [summary_to_dict(out[j]) for j in range(n.value)]
+
+    def correlative_peaks_batch(self, queries, range_x, range_y, range_theta, low_resolution, k_max,
+                                excl=(0, 0, 0), score_threshold=0.0, known_rate_threshold=0.0,
+                                scratch_limit_bytes=0, as_records=False):
+        """correlative_match_batch() returning the K best distinct poses of every query
+        (csm_correlative_peaks_batch): one list of summaries per query, best first. as_records: the C
+        arrays (summaries [n * k_max], peak counts [n]) instead."""
+        prep = self.prepare_queries(queries)
+        p = L.CorrelativeParams()
+        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
+        p.low_resolution = low_resolution
+        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        pk = self.peaks_params(k_max, excl, scratch_limit_bytes)
+        kk = max(1, min(k_max, L.PEAKS_MAX))
+        out = (L.Summary * (prep.n * kk))()
+        n = (C.c_int32 * prep.n)()
+        self._check(self.lib.csm_correlative_peaks_batch(self._ctx, prep.arr, prep.n, C.byref(p), C.byref(pk), out, n))
+        if as_records:
+            return out, n
+        return [[summary_to_dict(out[i * kk + j]) for j in range(n[i])] for i in range(prep.n)]
+
     def construct_map_from_scans(self, map_id, shape, map_pose, nodes, usable_range_min=0.01,
                                  usable_range_max=20.0, prob_hit=0.62, prob_miss=0.46,
                                  subpixel_scale=100):

@@ -222,6 +222,10 @@ struct csm_ctx {
     /* greedy-endpoint / hill-climbing batches (csm_greedy_api.hip): scans, job table + outputs,
      * rank scratch of scans too long for LDS, the cost tables */
     DevBuf g_scans, g_jobs, g_scratch, g_tab;
+    /* K best poses per window (csm_peaks_api.hip): score volumes of a chunk, its scans + hit indices,
+     * job table + records, pinned staging */
+    DevBuf pk_vol, pk_hits, pk_tab;
+    PinBuf pk_pin;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */

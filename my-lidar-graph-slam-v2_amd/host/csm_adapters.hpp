@@ -258,27 +258,10 @@ public:
         csm_ctx* ctx = this->mCtx.get();
         const GridMapView& g = q.mGridMap;
         const bool temporary = g.mId == GridMapView::kInvalidId;
-        if (!temporary && g.mId >= GridMapView::kReservedIds) {
-            std::fprintf(stderr, "Assertion failed: map id below 2^62 at %s:%d\n", __FILE__, __LINE__);
-            std::abort();
-        }
-        const std::uint64_t id = temporary ? GridMapView::kReservedIds : g.mId;
-        auto held = this->mRevisions.find(id);
-        /* mValues == nullptr: the map is already resident (built by a GridMapBuilderHIP on this context) */
-        if (g.mValues && (temporary || !csm_has_grid(ctx, id) || held == this->mRevisions.end() ||
-                          held->second != g.mRevision)) {
-            CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, id, g.mValues, g.mRows, g.mCols));
-            this->mRevisions[id] = g.mRevision;
-        }
+        const std::uint64_t id = this->MakeResident(g);
         csm_geometry geom { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
         const csm_scan scan = detail::ToScan(q.mScanData);
-        csm_correlative_params prm {};
-        prm.range_x = this->mRangeX;
-        prm.range_y = this->mRangeY;
-        prm.range_theta = this->mRangeTheta;
-        prm.low_resolution = this->mLowResolution;
-        prm.score_threshold = normalizedScoreThreshold;
-        prm.known_rate_threshold = knownRateThreshold;
+        const csm_correlative_params prm = this->Params(normalizedScoreThreshold, knownRateThreshold);
         const double init[3] = { q.mMapLocalInitialPose.mX, q.mMapLocalInitialPose.mY,
                                  q.mMapLocalInitialPose.mTheta };
         csm_summary s {};
@@ -308,6 +291,35 @@ public:
         return out;
     }
 
+    /* The K best DISTINCT poses of the window, best first (csm_correlative_peaks; beyond the reference,
+     * which keeps scoreMax only): a second entry scoring close to the first is a perceptually aliased
+     * match. exclX / exclY / exclTheta: half-widths, in search steps, of the box around a chosen pose
+     * in which no later one is taken. Cost and covariance are left zero. */
+    std::vector<ScanMatchingSummary> OptimizePosePeaks(const ScanMatchingQuery& q, int numOfPeaks, int exclX,
+                                                       int exclY, int exclTheta,
+                                                       const double normalizedScoreThreshold = 0.0,
+                                                       const double knownRateThreshold = 0.0)
+    {
+        csm_ctx* ctx = this->mCtx.get();
+        const GridMapView& g = q.mGridMap;
+        const std::uint64_t id = this->MakeResident(g);
+        csm_geometry geom { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
+        const csm_scan scan = detail::ToScan(q.mScanData);
+        const csm_correlative_params prm = this->Params(normalizedScoreThreshold, knownRateThreshold);
+        const double init[3] = { q.mMapLocalInitialPose.mX, q.mMapLocalInitialPose.mY,
+                                 q.mMapLocalInitialPose.mTheta };
+        const csm_peaks_params peaks { numOfPeaks, exclX, exclY, exclTheta, 0 };
+        csm_summary s[CSM_PEAKS_MAX] {};
+        std::int32_t n = 0;
+        CSM_ASSERT_OK(ctx, csm_correlative_peaks(ctx, id, &geom, &scan, init, &prm, &peaks, s, &n));
+        std::vector<ScanMatchingSummary> out(static_cast<std::size_t>(n));
+        for (std::int32_t j = 0; j < n; ++j)
+            detail::FillSummary(s[j], q.mMapLocalInitialPose, &out[j]);
+        if (g.mId == GridMapView::kInvalidId && g.mValues)
+            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
+        return out;
+    }
+
     /* Cost and covariance from the device's CostSquareError instead of a host callback
      * ("CovarianceScale", launcher_settings_default.json:11-13). */
     void UseDeviceCostFunction(double covarianceScale = 1e4) { this->mDeviceCovarianceScale = covarianceScale; }
@@ -325,6 +337,39 @@ private:
                               detail::CtxPtr ctx) :
         mName(name), mLowResolution(lowResolution), mRangeX(rangeX), mRangeY(rangeY),
         mRangeTheta(rangeTheta), mCostFunc(costFunc), mCtx(std::move(ctx)) { }
+
+    /* The query's map under its id on the device (uploaded when new or revised; a map without an id
+     * under a reserved one, released by the caller after the search). */
+    std::uint64_t MakeResident(const GridMapView& g)
+    {
+        csm_ctx* ctx = this->mCtx.get();
+        const bool temporary = g.mId == GridMapView::kInvalidId;
+        if (!temporary && g.mId >= GridMapView::kReservedIds) {
+            std::fprintf(stderr, "Assertion failed: map id below 2^62 at %s:%d\n", __FILE__, __LINE__);
+            std::abort();
+        }
+        const std::uint64_t id = temporary ? GridMapView::kReservedIds : g.mId;
+        auto held = this->mRevisions.find(id);
+        /* mValues == nullptr: the map is already resident (built by a GridMapBuilderHIP on this context) */
+        if (g.mValues && (temporary || !csm_has_grid(ctx, id) || held == this->mRevisions.end() ||
+                          held->second != g.mRevision)) {
+            CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, id, g.mValues, g.mRows, g.mCols));
+            this->mRevisions[id] = g.mRevision;
+        }
+        return id;
+    }
+
+    csm_correlative_params Params(double normalizedScoreThreshold, double knownRateThreshold) const
+    {
+        csm_correlative_params prm {};
+        prm.range_x = this->mRangeX;
+        prm.range_y = this->mRangeY;
+        prm.range_theta = this->mRangeTheta;
+        prm.low_resolution = this->mLowResolution;
+        prm.score_threshold = normalizedScoreThreshold;
+        prm.known_rate_threshold = knownRateThreshold;
+        return prm;
+    }
 
     const std::string mName;
     const int mLowResolution;
@@ -747,6 +792,49 @@ public:
         if (queries.empty())
             return results;
         csm_ctx* ctx = this->mCtx.get();
+        const std::vector<csm_loop_query> flat = this->Flatten(queries);
+        const csm_correlative_params prm = this->Params();
+        std::vector<csm_summary> out(queries.size());
+        CSM_ASSERT_OK(ctx, csm_correlative_match_batch(
+                               ctx, flat.data(), static_cast<std::int32_t>(flat.size()), &prm, out.data()));
+        for (std::size_t i = 0; i < queries.size(); ++i)
+            if (out[i].pose_found)
+                results.push_back(Result(queries[i], out[i]));
+        return results;
+    }
+
+    /* Detect() keeping up to numOfPeaks DISTINCT poses per query, best first
+     * (csm_correlative_peaks_batch): element i holds the peaks of queries[i] that pass the score
+     * threshold, none when Detect() would have skipped the query. A second entry scoring close to the
+     * first says the match is ambiguous (a corridor, repeated structure): the caller can drop the loop
+     * edge instead of adding a wrong one. exclX / exclY / exclTheta: half-widths, in search steps, of
+     * the box around a chosen pose in which no later one is taken. */
+    std::vector<LoopDetectionResultVector> DetectPeaks(const LoopDetectionQueryVector& queries, int numOfPeaks,
+                                                       int exclX, int exclY, int exclTheta)
+    {
+        std::vector<LoopDetectionResultVector> results(queries.size());
+        if (queries.empty())
+            return results;
+        csm_ctx* ctx = this->mCtx.get();
+        const std::vector<csm_loop_query> flat = this->Flatten(queries);
+        const csm_correlative_params prm = this->Params();
+        const csm_peaks_params peaks { numOfPeaks, exclX, exclY, exclTheta, 0 };
+        const std::size_t kMax = static_cast<std::size_t>(std::max(1, std::min(numOfPeaks, CSM_PEAKS_MAX)));
+        std::vector<csm_summary> out(queries.size() * kMax);
+        std::vector<std::int32_t> count(queries.size(), 0);
+        CSM_ASSERT_OK(ctx, csm_correlative_peaks_batch(ctx, flat.data(), static_cast<std::int32_t>(flat.size()), &prm,
+                                                       &peaks, out.data(), count.data()));
+        for (std::size_t i = 0; i < queries.size(); ++i)
+            for (std::int32_t j = 0; j < count[i]; ++j)
+                results[i].push_back(Result(queries[i], out[i * kMax + static_cast<std::size_t>(j)]));
+        return results;
+    }
+
+private:
+    /* the queries as the batch entries take them; maps that are not resident yet are uploaded */
+    std::vector<csm_loop_query> Flatten(const LoopDetectionQueryVector& queries)
+    {
+        csm_ctx* ctx = this->mCtx.get();
         std::vector<csm_loop_query> flat(queries.size());
         for (std::size_t i = 0; i < queries.size(); ++i) {
             const LoopDetectionQuery& q = queries[i];
@@ -764,6 +852,11 @@ public:
                                     q.mQueryScanNodeGlobalPose.mTheta };
             csm_host_inverse_compound(start, end, f.initial_pose);
         }
+        return flat;
+    }
+
+    csm_correlative_params Params() const
+    {
         csm_correlative_params prm {};
         prm.range_x = this->mRangeX;
         prm.range_y = this->mRangeY;
@@ -771,21 +864,16 @@ public:
         prm.low_resolution = this->mLowResolution;
         prm.score_threshold = this->mScoreThreshold;
         prm.known_rate_threshold = this->mKnownRateThreshold;
-        std::vector<csm_summary> out(queries.size());
-        CSM_ASSERT_OK(ctx, csm_correlative_match_batch(
-                               ctx, flat.data(), static_cast<std::int32_t>(flat.size()), &prm, out.data()));
-        for (std::size_t i = 0; i < queries.size(); ++i) {
-            if (!out[i].pose_found)
-                continue;
-            results.push_back(LoopDetectionResult {
-                { out[i].estimated_pose[0], out[i].estimated_pose[1], out[i].estimated_pose[2] },
-                queries[i].mReferenceLocalMapNodeGlobalPose, queries[i].mReferenceLocalMap.mId,
-                queries[i].mQueryScanNodeId, out[i].raw.score, out[i].raw.flags });
-        }
-        return results;
+        return prm;
     }
 
-private:
+    static LoopDetectionResult Result(const LoopDetectionQuery& q, const csm_summary& s)
+    {
+        return LoopDetectionResult { { s.estimated_pose[0], s.estimated_pose[1], s.estimated_pose[2] },
+                                     q.mReferenceLocalMapNodeGlobalPose, q.mReferenceLocalMap.mId,
+                                     q.mQueryScanNodeId, s.raw.score, s.raw.flags };
+    }
+
     LoopDetectorCorrelativeHIP(const std::string& name, int lowResolution, double rangeX,
                                double rangeY, double rangeTheta, double scoreThreshold,
                                double knownRateThreshold, detail::CtxPtr ctx) :
