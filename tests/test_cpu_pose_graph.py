@@ -11,6 +11,7 @@ import pytest
 from csm_hip import _lib as L
 from csm_hip import api, synth
 import pose_graph_literal as PL
+from pose_graph_cases import zero_rhs as _zero_rhs
 
 
 def _dup_edges(c):
@@ -21,20 +22,6 @@ def _dup_edges(c):
     if loops:
         extra.append(copy.deepcopy(loops[0]))
     c["edges"] += extra
-    return c
-
-
-def _zero_rhs(c):
-    """every measurement equal to the relative pose of the initial estimate, computed with the same
-    arithmetic: e = 0 exactly, so b = 0 and the CG returns at once"""
-    c = copy.deepcopy(c)
-    nodes = c["local"].tolist() + c["scan"].tolist()
-    nl = len(c["local"])
-    for e in c["edges"]:
-        ps, pe = nodes[e["local"]], nodes[nl + e["scan"]]
-        s, co = math.sin(ps[2]), math.cos(ps[2])
-        d = [pe[0] - ps[0], pe[1] - ps[1], pe[2] - ps[2]]
-        e["rel"] = [co * d[0] + s * d[1], -s * d[0] + co * d[1], d[2]]
     return c
 
 

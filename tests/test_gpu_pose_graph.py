@@ -73,8 +73,9 @@ def _compare(dev, host, n_vars):
         assert t["cg_iterations"] == 2 * n_vars or t["residual_norm2"] < thr or t["rhs_norm2"] == 0.0
 
 
-def _run_case(ctx, c, loss, lam=1e-4, tol=1e-4, itmax=10):
-    kw = dict(iterations_max=itmax, error_tolerance=tol, loss=loss, loss_scale=LOSS_SCALE[loss])
+def _run_case(ctx, c, loss, lam=1e-4, tol=1e-4, itmax=10, scale=None):
+    kw = dict(iterations_max=itmax, error_tolerance=tol, loss=loss,
+              loss_scale=LOSS_SCALE[loss] if scale is None else scale)
     host = api.host_pose_graph_lm(c["local"], c["scan"], c["edges"], lam, **kw)
     _check_margins(host[2], tol)
     dev = ctx.pose_graph_lm(c["local"], c["scan"], c["edges"], lam, **kw)
