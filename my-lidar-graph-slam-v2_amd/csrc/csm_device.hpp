@@ -12,8 +12,8 @@ constexpr int kMaxRegionRows = 128;        /* LDS region rows of a stride-1 job 
 constexpr int kMaxRegionRowsStrided = 128; /* ... of a strided (coarser level) job */
 constexpr int kPairMaxCby = 56;  /* candidate rows per workgroup of the pair-row fine kernel */
 constexpr int kPbMax = 1024;       /* entries per TileRec: k_bin splits fuller tiles */
-constexpr int kJRec = 256;         /* entries per TileRec of a joint list (k_binj): the record's float beam counts
-                                      (16 B per entry) live in LDS during the fp32 bound pass */
+constexpr int kJRec = 256;         /* entries per TileRec of a joint list (k_binj): one entry word per thread
+                                      of half a workgroup, 1 KB of LDS next to the window copy */
 constexpr int kMaxMult = 15;       /* beams merged into one (cell, multiplicity) entry */
 constexpr int kMaxPoints = 10240;  /* beams per scan: k_bin's hash table (16384 slots, load <= 2/3, 128 KB)
                                       and cell list must fit the CU's 160 KB of LDS */

@@ -699,6 +699,30 @@ __device__ __forceinline__ void score_body_joint(const ScoreJob& job, int cbx, i
  * instructions per (slice, parity) for 8 candidate rows instead of 8. */
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+/* Count as scalar FMA operand. A beam count n = 1 .. 15 read as an fp32 bit pattern is the denormal
+ * n * 2^-149: linear in n, no conversion. The multiply-adds of the bound pass take the count in that
+ * form straight from the scalar register the entry word's nibble was extracted to (joint_fmads), so the
+ * key copy is pre-scaled by 2^kKeyScaleLog2 to keep every product and sum a normal float, and the
+ * epilogue of score_body_jointf scales each candidate's sum back by 2^(149 - kKeyScaleLog2): everything
+ * outside the tile loop (approx_best, dump_f, key_floor, approx_slack, k_bound_select) stays in key units.
+ * What S = kKeyScaleLog2 must satisfy:
+ *   a cell's key is < 2^25, so key * 2^S < 2^128 needs S <= 102;
+ *   the smallest non-zero term, 32767 * 1 * 2^(S - 149) > 2^(S - 135), is normal (>= 2^-126) for S >= 9;
+ *   sums stay below 2^39 * 2^(S - 149) (kMaxPoints beams of keys < 2^25), far from overflow for every such S.
+ * A power-of-two scale commutes with every rounding as long as nothing leaves the normal range (the
+ * significands that are rounded are the same), so every fused multiply-add rounds to the scaled image
+ * of what the float-count form rounded to: the proven error bound (n + 3) 2^-24 and the slack
+ * 4 (n + 3) 2^-24 are unchanged, and so is every dumped key, bit for bit. Needs fp32 denormals
+ * honoured as FMA inputs: the kernels' float mode is the compiler's default "preserve" for gfx9 HIP code
+ * (tools/micro/pk_fma_bench.hip checks value and rate of this operand form). */
+constexpr int kKeyScaleLog2 = 100;
+static_assert(kKeyScaleLog2 >= 9 && kKeyScaleLog2 <= 102, "products normal, scaled keys finite");
+
+__device__ __forceinline__ float pow2f(int e)      /* 2^e, -126 <= e <= 127 */
+{
+    return __uint_as_float((uint32_t)(e + 127) << 23);
+}
+
 __global__ __launch_bounds__(256) void k_expand_pairs_f(const uint16_t* __restrict__ cells, int rows, int cols,
                                                        int pitch, float2* __restrict__ xgf, int xg_prows,
                                                        int xg_pitch, int pad)
@@ -714,76 +738,77 @@ __global__ __launch_bounds__(256) void k_expand_pairs_f(const uint16_t* __restri
             if (r0 + 1 >= 0 && r0 + 1 < rows)
                 v1 = cells[(size_t)(r0 + 1) * pitch + c];
         }
-        /* one rounding (values above 2^24): part of the bound pass's error budget */
-        xgf[i] = make_float2((float)(499u * v0 + 32268u * min(v0, 1u)), (float)(499u * v1 + 32268u * min(v1, 1u)));
+        /* one rounding (values above 2^24): part of the bound pass's error budget; the scale is exact */
+        const float ks = pow2f(kKeyScaleLog2);
+        xgf[i] = make_float2((float)(499u * v0 + 32268u * min(v0, 1u)) * ks, (float)(499u * v1 + 32268u * min(v1, 1u)) * ks);
     }
 }
 
-/* The packed multiply-adds of one entry. fa = (float beams even row, odd row) of slice 0, fb of
- * slice 1 (from the record's float table in LDS); zero counts are skipped by scalar branches on the
- * integer counts in the entry word. */
-#define CSM_JFMA_E(acc, q, f) "v_pk_fma_f32 %[" #acc "], %[" #q "], %[" #f "], %[" #acc "] op_sel_hi:[1,0,1]\n\t"
-#define CSM_JFMA_O(acc, q, f) "v_pk_fma_f32 %[" #acc "], %[" #q "], %[" #f "], %[" #acc "] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
-template <int R>
-__device__ __forceinline__ void joint_fmads(uint32_t w, const unsigned long long (&q)[R / 2 + 1], unsigned long long fa,
-                                            unsigned long long fb, f32x2 (&ea)[R / 2], f32x2 (&oa)[R / 2 + 1],
-                                            f32x2 (&eb)[R / 2], f32x2 (&ob)[R / 2 + 1])
+/* The packed multiply-adds of one entry. w2 = two entry words in an aligned scalar pair, this entry's
+ * in its low (HI = 0) or high half. Each of the entry's four (slice, row parity) counts is extracted to
+ * the low half of a scalar pair by the s_bfe_u64 whose zero test skips the branch, and IS the
+ * multiplicand of the branch's instructions (count as scalar FMA operand: src1 = the pair, op_sel /
+ * op_sel_hi take its low dword for both halves; one scalar source per instruction). E and O forms
+ * differ in their accumulators only. */
+#define CSM_JFMA(acc, q) "v_pk_fma_f32 %[" #acc "], %[" #q "], %[m], %[" #acc "] op_sel_hi:[1,0,1]\n\t"
+template <int R, int HI>
+__device__ __forceinline__ void joint_fmads(unsigned long long w2, const unsigned long long (&q)[R / 2 + 1], f32x2 (&ea)[R / 2],
+                                            f32x2 (&oa)[R / 2 + 1], f32x2 (&eb)[R / 2], f32x2 (&ob)[R / 2 + 1])
 {
     static_assert(R == 6 || R == 8, "rows per lane");
-    uint32_t m;
+    constexpr int kBfe = (4 << 16) + 32 * HI;       /* s_bfe_u64 operand: 4 bits from bit (32 HI + nibble's) */
+    unsigned long long m;
     if constexpr (R == 8) {
-        asm("s_bfe_u32 %[m], %[w], 0x40010\n\t"
+        asm("s_bfe_u64 %[m], %[w], %[k0]\n\t"
             "s_cbranch_scc0 1f\n\t"
-            CSM_JFMA_E(ea0, q0, fa) CSM_JFMA_E(ea1, q1, fa) CSM_JFMA_E(ea2, q2, fa) CSM_JFMA_E(ea3, q3, fa)
+            CSM_JFMA(ea0, q0) CSM_JFMA(ea1, q1) CSM_JFMA(ea2, q2) CSM_JFMA(ea3, q3)
             "1:\n\t"
-            "s_bfe_u32 %[m], %[w], 0x40018\n\t"
+            "s_bfe_u64 %[m], %[w], %[k1]\n\t"
             "s_cbranch_scc0 2f\n\t"
-            CSM_JFMA_E(eb0, q0, fb) CSM_JFMA_E(eb1, q1, fb) CSM_JFMA_E(eb2, q2, fb) CSM_JFMA_E(eb3, q3, fb)
+            CSM_JFMA(eb0, q0) CSM_JFMA(eb1, q1) CSM_JFMA(eb2, q2) CSM_JFMA(eb3, q3)
             "2:\n\t"
-            "s_bfe_u32 %[m], %[w], 0x40014\n\t"
+            "s_bfe_u64 %[m], %[w], %[k2]\n\t"
             "s_cbranch_scc0 3f\n\t"
-            CSM_JFMA_O(oa0, q0, fa) CSM_JFMA_O(oa1, q1, fa) CSM_JFMA_O(oa2, q2, fa) CSM_JFMA_O(oa3, q3, fa)
-            CSM_JFMA_O(oa4, q4, fa)
+            CSM_JFMA(oa0, q0) CSM_JFMA(oa1, q1) CSM_JFMA(oa2, q2) CSM_JFMA(oa3, q3) CSM_JFMA(oa4, q4)
             "3:\n\t"
-            "s_bfe_u32 %[m], %[w], 0x4001c\n\t"
+            "s_bfe_u64 %[m], %[w], %[k3]\n\t"
             "s_cbranch_scc0 4f\n\t"
-            CSM_JFMA_O(ob0, q0, fb) CSM_JFMA_O(ob1, q1, fb) CSM_JFMA_O(ob2, q2, fb) CSM_JFMA_O(ob3, q3, fb)
-            CSM_JFMA_O(ob4, q4, fb)
+            CSM_JFMA(ob0, q0) CSM_JFMA(ob1, q1) CSM_JFMA(ob2, q2) CSM_JFMA(ob3, q3) CSM_JFMA(ob4, q4)
             "4:"
             : [m] "=&s"(m), [ea0] "+v"(ea[0]), [ea1] "+v"(ea[1]), [ea2] "+v"(ea[2]), [ea3] "+v"(ea[3]),
               [oa0] "+v"(oa[0]), [oa1] "+v"(oa[1]), [oa2] "+v"(oa[2]), [oa3] "+v"(oa[3]), [oa4] "+v"(oa[4]),
               [eb0] "+v"(eb[0]), [eb1] "+v"(eb[1]), [eb2] "+v"(eb[2]), [eb3] "+v"(eb[3]),
               [ob0] "+v"(ob[0]), [ob1] "+v"(ob[1]), [ob2] "+v"(ob[2]), [ob3] "+v"(ob[3]), [ob4] "+v"(ob[4])
-            : [w] "s"(w), [q0] "v"(q[0]), [q1] "v"(q[1]), [q2] "v"(q[2]), [q3] "v"(q[3]), [q4] "v"(q[4]),
-              [fa] "v"(fa), [fb] "v"(fb)
+            : [w] "s"(w2), [q0] "v"(q[0]), [q1] "v"(q[1]), [q2] "v"(q[2]), [q3] "v"(q[3]), [q4] "v"(q[4]),
+              [k0] "n"(kBfe + 16), [k1] "n"(kBfe + 24), [k2] "n"(kBfe + 20), [k3] "n"(kBfe + 28)
             : "scc");
     } else {
-        asm("s_bfe_u32 %[m], %[w], 0x40010\n\t"
+        asm("s_bfe_u64 %[m], %[w], %[k0]\n\t"
             "s_cbranch_scc0 1f\n\t"
-            CSM_JFMA_E(ea0, q0, fa) CSM_JFMA_E(ea1, q1, fa) CSM_JFMA_E(ea2, q2, fa)
+            CSM_JFMA(ea0, q0) CSM_JFMA(ea1, q1) CSM_JFMA(ea2, q2)
             "1:\n\t"
-            "s_bfe_u32 %[m], %[w], 0x40018\n\t"
+            "s_bfe_u64 %[m], %[w], %[k1]\n\t"
             "s_cbranch_scc0 2f\n\t"
-            CSM_JFMA_E(eb0, q0, fb) CSM_JFMA_E(eb1, q1, fb) CSM_JFMA_E(eb2, q2, fb)
+            CSM_JFMA(eb0, q0) CSM_JFMA(eb1, q1) CSM_JFMA(eb2, q2)
             "2:\n\t"
-            "s_bfe_u32 %[m], %[w], 0x40014\n\t"
+            "s_bfe_u64 %[m], %[w], %[k2]\n\t"
             "s_cbranch_scc0 3f\n\t"
-            CSM_JFMA_O(oa0, q0, fa) CSM_JFMA_O(oa1, q1, fa) CSM_JFMA_O(oa2, q2, fa) CSM_JFMA_O(oa3, q3, fa)
+            CSM_JFMA(oa0, q0) CSM_JFMA(oa1, q1) CSM_JFMA(oa2, q2) CSM_JFMA(oa3, q3)
             "3:\n\t"
-            "s_bfe_u32 %[m], %[w], 0x4001c\n\t"
+            "s_bfe_u64 %[m], %[w], %[k3]\n\t"
             "s_cbranch_scc0 4f\n\t"
-            CSM_JFMA_O(ob0, q0, fb) CSM_JFMA_O(ob1, q1, fb) CSM_JFMA_O(ob2, q2, fb) CSM_JFMA_O(ob3, q3, fb)
+            CSM_JFMA(ob0, q0) CSM_JFMA(ob1, q1) CSM_JFMA(ob2, q2) CSM_JFMA(ob3, q3)
             "4:"
             : [m] "=&s"(m), [ea0] "+v"(ea[0]), [ea1] "+v"(ea[1]), [ea2] "+v"(ea[2]),
               [oa0] "+v"(oa[0]), [oa1] "+v"(oa[1]), [oa2] "+v"(oa[2]), [oa3] "+v"(oa[3]),
               [eb0] "+v"(eb[0]), [eb1] "+v"(eb[1]), [eb2] "+v"(eb[2]),
               [ob0] "+v"(ob[0]), [ob1] "+v"(ob[1]), [ob2] "+v"(ob[2]), [ob3] "+v"(ob[3])
-            : [w] "s"(w), [q0] "v"(q[0]), [q1] "v"(q[1]), [q2] "v"(q[2]), [q3] "v"(q[3]), [fa] "v"(fa), [fb] "v"(fb)
+            : [w] "s"(w2), [q0] "v"(q[0]), [q1] "v"(q[1]), [q2] "v"(q[2]), [q3] "v"(q[3]),
+              [k0] "n"(kBfe + 16), [k1] "n"(kBfe + 24), [k2] "n"(kBfe + 20), [k3] "n"(kBfe + 28)
             : "scc");
     }
 }
-#undef CSM_JFMA_E
-#undef CSM_JFMA_O
+#undef CSM_JFMA
 
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f)
@@ -794,21 +819,16 @@ __device__ __forceinline__ void static_for(F&& f)
     }
 }
 
-/* ftab_addr: LDS byte address of the record's float table (16 B per entry: beams of even / odd
- * row of slice 0, of slice 1); the two broadcast reads of an entry ride in the same lgkmcnt queue
- * as its R/2 + 1 slot reads. */
+/* The gather of one record: R/2 + 1 slot reads per entry, nothing else in the lgkmcnt queue. */
 template <int LS, int R>
-__device__ __forceinline__ void joint_gather_f(uint32_t lane_addr, uint32_t ftab_addr, const uint32_t* lpb, int lane,
-                                               int cnt, f32x2 (&ea)[R / 2], f32x2 (&oa)[R / 2 + 1],
-                                               f32x2 (&eb)[R / 2], f32x2 (&ob)[R / 2 + 1])
+__device__ __forceinline__ void joint_gather_f(uint32_t lane_addr, const uint32_t* lpb, int lane, int cnt,
+                                               f32x2 (&ea)[R / 2], f32x2 (&oa)[R / 2 + 1], f32x2 (&eb)[R / 2],
+                                               f32x2 (&ob)[R / 2 + 1])
 {
     constexpr int kRowBytes = LS * 8;
     constexpr int NQ = R / 2 + 1;
-    constexpr int NP = NQ + 2;                      /* reads per entry */
-    /* K: the entry's position in its group of four (its float-table row is an immediate offset from
-     * the group's row: one address register per group) */
-    auto issue = [&](uint32_t w, uint32_t faddr, auto kk, unsigned long long (&q)[NQ], unsigned long long (&f)[2]) {
-        constexpr int K = decltype(kk)::value;
+    constexpr int NP = NQ;                          /* reads per entry */
+    auto issue = [&](uint32_t w, unsigned long long (&q)[NQ]) {
         const uint32_t addr = lane_addr + (w & 0xffffu);
         lds_read_b64<0 * kRowBytes>(addr, q[0]);
         lds_read_b64<1 * kRowBytes>(addr, q[1]);
@@ -816,17 +836,15 @@ __device__ __forceinline__ void joint_gather_f(uint32_t lane_addr, uint32_t ftab
         lds_read_b64<3 * kRowBytes>(addr, q[3]);
         if constexpr (R >= 8)
             lds_read_b64<4 * kRowBytes>(addr, q[4]);
-        lds_read_b64<16 * K>(faddr, f[0]);
-        lds_read_b64<16 * K + 8>(faddr, f[1]);
     };
     /* waits until all but the `LATER` youngest LDS reads have landed; ties every register the
      * mads are about to read */
-    auto wait = [&](auto later, unsigned long long (&q)[NQ], unsigned long long (&f)[2]) {
+    auto wait = [&](auto later, unsigned long long (&q)[NQ]) {
         constexpr int LATER = decltype(later)::value;
         if constexpr (R >= 8)
-            asm volatile("s_waitcnt lgkmcnt(%7)" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), "+v"(q[4]), "+v"(f[0]), "+v"(f[1]) : "n"(LATER));
+            asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), "+v"(q[4]) : "n"(LATER));
         else
-            asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), "+v"(f[0]), "+v"(f[1]) : "n"(LATER));
+            asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]) : "n"(LATER));
     };
     using later_t = std::integral_constant<int, NP>;
     using now_t = std::integral_constant<int, 0>;
@@ -836,28 +854,31 @@ __device__ __forceinline__ void joint_gather_f(uint32_t lane_addr, uint32_t ftab
      * once per pass (the first wait of a pass sees the full LDS latency: 8 entries per pass instead of 4
      * took 2.2 % off the launch; 16 per pass gave half of that back, its code no longer sits well in the
      * instruction cache, and carrying two entries in flight from one pass into the next makes the register
-     * sets loop-carried: 128 VGPRs and scratch). Register sets a, b, c, d in turn; entry u's float-table row is an immediate
-     * offset from the pass's first row. */
+     * sets loop-carried: 128 VGPRs and scratch). Register sets a, b, c, d in turn. Entry words 2k and 2k + 1 of
+     * a pass share an aligned scalar pair (joint_fmads). */
     auto pass = [&](auto n_) {
         constexpr int N = decltype(n_)::value;
         uint32_t o[N];
+        unsigned long long o2[(N + 1) / 2];
 #pragma unroll
         for (int u = 0; u < N; ++u)
             o[u] = (uint32_t)__builtin_amdgcn_readlane((int)pb_cur, (j + u) & 63);
-        const uint32_t fbase = ftab_addr + (uint32_t)j * 16u;
-        unsigned long long q[4][NQ], f[4][2];
-        issue(o[0], fbase, std::integral_constant<int, 0>(), q[0], f[0]);
+#pragma unroll
+        for (int u = 0; u < N; u += 2)
+            o2[u / 2] = o[u] | (unsigned long long)(u + 1 < N ? o[u + 1] : 0u) << 32;
+        unsigned long long q[4][NQ];
+        issue(o[0], q[0]);
         if constexpr (N > 1)
-            issue(o[1], fbase, std::integral_constant<int, 1>(), q[1], f[1]);
+            issue(o[1], q[1]);
         static_for<0, N>([&](auto u_) {
             constexpr int U = decltype(u_)::value;
             if constexpr (U + 1 < N)
-                wait(later_t(), q[U % 4], f[U % 4]);
+                wait(later_t(), q[U % 4]);
             else
-                wait(now_t(), q[U % 4], f[U % 4]);
-            joint_fmads<R>(o[U], q[U % 4], f[U % 4][0], f[U % 4][1], ea, oa, eb, ob);
+                wait(now_t(), q[U % 4]);
+            joint_fmads<R, U % 2>(o2[U / 2], q[U % 4], ea, oa, eb, ob);
             if constexpr (U + 2 < N)
-                issue(o[U + 2], fbase, std::integral_constant<int, U + 2>(), q[(U + 2) % 4], f[(U + 2) % 4]);
+                issue(o[U + 2], q[(U + 2) % 4]);
         });
         j += N;
     };
@@ -913,7 +934,6 @@ __device__ __forceinline__ void score_body_jointf(const ScoreJob& job, int cbx, 
     const int max_pieces = (prows_full * kRowBytes + 1023) >> 10;
     uint32_t* sm_cells = reinterpret_cast<uint32_t*>(sm_tile);
     uint32_t* lpb = sm_cells + max_pieces * 256;                 /* [kJRec] entry words */
-    float4* ftab = reinterpret_cast<float4*>(lpb + kJRec);       /* [kJRec] float beam counts */
     const int tb = lane_on || (idle && g < groups && dxi < cbx) ? (g * (R / 2)) * kRowBytes + 8 * dxi : 0;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -961,7 +981,7 @@ __device__ __forceinline__ void score_body_jointf(const ScoreJob& job, int cbx, 
         const char* src = xg + ((size_t)((gr0 + pad) >> 1) * xg_pitch + (size_t)((c00 & ~1) + pad)) * 8;
         if (ti + 1 < ntiles)
             rec = recs[ti + 1];
-        /* this thread's entry of the record, for the float table */
+        /* this thread's entry of the record */
         uint32_t my_w = 0;
         if (tid < cnt)
             my_w = pbs[start + tid];
@@ -974,21 +994,18 @@ __device__ __forceinline__ void score_body_jointf(const ScoreJob& job, int cbx, 
                 __builtin_amdgcn_global_load_lds((glb_ptr)(src + goff[k]), (lds_ptr)(sm_cells + pc * 256), 16, 0, 0);
         }
         __builtin_amdgcn_s_setprio(0);
-        static_assert(kJRec <= kBlock, "one table entry per thread");
-        if (tid < cnt) {
+        static_assert(kJRec <= kBlock, "one entry per thread");
+        if (tid < cnt)
             lpb[tid] = my_w;
-            ftab[tid] = make_float4((float)((my_w >> 16) & 15u), (float)((my_w >> 20) & 15u),
-                                    (float)((my_w >> 24) & 15u), (float)(my_w >> 28));
-        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         const uint32_t lane_addr = lds_address(sm_cells) + (uint32_t)(tb + 8 * a);
 #ifndef CSM_ABL_NOGATHER       /* timing builds only (tools/build_variant.sh): what the tile loop costs without its gather */
         if (wave_live)
-            joint_gather_f<LS, R>(lane_addr, lds_address(ftab), lpb, lane, cnt, ea, oa, eb, ob);
+            joint_gather_f<LS, R>(lane_addr, lpb, lane, cnt, ea, oa, eb, ob);
 #else
         if (wave_live && cnt < 0)
-            joint_gather_f<LS, R>(lane_addr, lds_address(ftab), lpb, lane, cnt, ea, oa, eb, ob);
+            joint_gather_f<LS, R>(lane_addr, lpb, lane, cnt, ea, oa, eb, ob);
 #endif
     }
 
@@ -996,14 +1013,15 @@ __device__ __forceinline__ void score_body_jointf(const ScoreJob& job, int cbx, 
     const int xi = bx * cbx + dxi;
     float best0 = 0.f, best1 = 0.f;
     float* const dump_f = job.dump_f;
+    const float unscale = pow2f(149 - kKeyScaleLog2);      /* back to key units: exact */
     if (lane_on && xi < job.nx) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int yi = row0 + g * R + r;
             if (yi >= job.ny)
                 continue;
-            const float w0 = (r & 1 ? ea[r / 2].y + oa[(r + 1) / 2].x : ea[r / 2].x + oa[r / 2].y);
-            const float w1 = (r & 1 ? eb[r / 2].y + ob[(r + 1) / 2].x : eb[r / 2].x + ob[r / 2].y);
+            const float w0 = (r & 1 ? ea[r / 2].y + oa[(r + 1) / 2].x : ea[r / 2].x + oa[r / 2].y) * unscale;
+            const float w1 = (r & 1 ? eb[r / 2].y + ob[(r + 1) / 2].x : eb[r / 2].x + ob[r / 2].y) * unscale;
             best0 = fmaxf(best0, w0);
             best1 = fmaxf(best1, w1);
             if (dump_f) {

@@ -239,7 +239,8 @@ bool plan_pass_pairs(const Tuning& tune, int nx, int ny, PassPlan* out, bool two
     if (!tune.two_slices && two_slices)
         return plan_pass_pairs(tune, nx, ny, out, false);
     /* LDS of a launch: the window copy + its entry lists (kPbMax words per list of the pair kernels; list_lds
-     * bytes where the caller knows better: the joint kernels keep kJRec words) */
+     * bytes where the caller knows better: the joint kernels keep kJRec words, the exact ones and the
+     * packed-fp32 bound pass alike -- pass_lds_bytes) */
     auto lds_of = [&](int ls, int cby) {
         return list_lds >= 0 ? pair_lds_bytes(ls, cby, 0) + (size_t)list_lds : pair_lds_bytes(ls, cby, lists);
     };
@@ -351,9 +352,14 @@ int pick_buffers(const Tuning& tune, size_t lds_one, long blocks)
 
 size_t pass_lds_bytes(const PassPlan& p)
 {
-    if (p.pairs)
+    if (p.pairs) {
+        /* the packed-fp32 bound pass keeps the window copy and kJRec entry words, whatever lists the
+         * plan was made for (the counts are scalar FMA operands taken from the entry words) */
+        if (p.joint && p.fp32)
+            return pair_lds_bytes(p.lstride, p.groups * p.R, 0) + (size_t)kJRec * 4;
         return p.list_lds >= 0 ? pair_lds_bytes(p.lstride, p.groups * p.R, 0) + (size_t)p.list_lds
                                : pair_lds_bytes(p.lstride, p.groups * p.R, p.lists);
+    }
     const int cby = p.groups * p.R;
     const int rows = p.stride > 1 ? ((kTile + p.stride - 1) / p.stride + cby - 1) * p.stride
                                   : kTile + cby - 1;
