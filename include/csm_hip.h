@@ -416,6 +416,85 @@ int  csm_correlative_peaks_batch(csm_ctx* ctx, const csm_loop_query* queries, in
                                  const csm_correlative_params* params, const csm_peaks_params* peaks,
                                  csm_summary* out, int32_t* n_peaks);
 
+/* ---- pose covariance read off the whole score volume (beyond the reference, whose only covariance is
+ * the Gauss-Newton Hessian of the cost function at the winning pose): a ridge along a corridor, a plateau
+ * in front of a wall, a second lobe all show in the volume and in nothing else.
+ *
+ * Candidates, key and eligibility are those of csm_score_window_peaks. The winner b is its peak 0 (k_max
+ * = 1): the greatest key, then the greatest f64 beam-order score, then the first in sweep order; an
+ * edge-band window follows the closed form and carries CSM_FLAG_EDGE_BAND, as the peaks do. If nothing is
+ * eligible or the winner's score does not pass score_threshold, best.found = 0 and every moment is zero.
+ *
+ * Weight. With c = 0.998 / (65534 * 499) (score = key c / N, N = n_points) and tau = temperature (score
+ * units): band_keys = ceil(17 tau N / c), bin_shift = the smallest s with (band_keys >> s) <
+ * CSM_VOLUME_BINS, W[b] = floor(2^24 exp(-((b << bin_shift) c) / (N tau)) + 0.5) as uint32, computed on
+ * the host in f64 (csm_host_volume_weights); W[0] = 2^24. An eligible candidate weighs
+ * W[(key_b - key) >> bin_shift], 0 when that bin is >= CSM_VOLUME_BINS; an ineligible one weighs 0.
+ *
+ * Moments, exact in int64, over d = (x - x_b, y - y_b, t - t_b) in search steps (theta not wrapped):
+ * m0 = sum w, m1[a] = sum w d_a, m2 = sum w d_a d_b in the order xx xy xt yy yt tt, support = candidates
+ * with w > 0, border_support = those of them with x, y or t at its first or last index of the extended
+ * domain (non-zero: the window truncated the distribution). Integer sums are associative, so the device
+ * result equals the definition bit for bit whatever the order.
+ *
+ * Covariance (csm_host_volume_covariance; one fixed f64 expression, index order (x, y, theta)):
+ *   num_ab = m0 m2_ab - m1_a m1_b                      exact, __int128
+ *   cov_idx_ab = (double)num_ab / ((double)m0 * (double)m0)
+ *   sensor_covariance_ab = (cov_idx_ab * step_a) * step_b
+ *   mean_offset_a = ((double)m1_a / (double)m0) * step_a
+ *   covariance = J sensor_covariance J^T, J = d MoveBackward(sensor pose, rel_pose) / d sensor pose at the
+ *   estimated pose: the identity plus J[0][2] = sin(th) rx + cos(th) ry, J[1][2] = -cos(th) rx + sin(th) ry
+ *   (th = estimated_pose[2], libm sin / cos). T = J S with T_ij = (J_i0 S_0j + J_i1 S_1j) + J_i2 S_2j, then
+ *   covariance_ij = (T_i0 J_j0 + T_i1 J_j1) + T_i2 J_j2, every product taken (also those by 0 and 1).
+ * A covariance of zeros (a support of one candidate) is a valid answer. m0 = 0 gives all zeros.
+ *
+ * CSM_EINVAL, all checked before anything is allocated: temperature not finite or <= 0;
+ * 17 tau N / c >= 2^62; n_cand (max(n_theta, nx, ny) - 1)^2 2^24 >= 2^63; a negative scratch limit; and
+ * the peaks' own refusals (more than 1 << 26 candidates, a volume beyond the scratch limit).
+ * Not provided: branch-and-bound and grid-search volumes, the csm_group_* entries, a default temperature. */
+#define CSM_VOLUME_BINS 1024
+typedef struct {
+    double  temperature;                 /* tau, in score units; finite and > 0 */
+    int64_t scratch_limit_bytes;         /* as csm_peaks_params.scratch_limit_bytes */
+} csm_volume_params;
+
+typedef struct {
+    csm_result best;                     /* the winner: peak 0 of csm_score_window_peaks */
+    int64_t    m0, m1[3], m2[6];
+    int64_t    support, border_support;
+    int32_t    bin_shift, reserved;
+} csm_volume_moments;
+
+typedef struct {
+    csm_summary        summary;          /* as csm_correlative_match fills it, from the winner */
+    csm_volume_moments moments;
+    double             mean_offset[3];           /* of the sensor pose from the winner, metric */
+    double             sensor_covariance[9];     /* of the sensor pose, row-major (x, y, theta) */
+    double             covariance[9];            /* of the estimated (robot) pose */
+} csm_volume_summary;
+
+/* hit_col / hit_row as csm_score_window takes them. */
+int  csm_score_window_moments(csm_ctx* ctx, uint64_t map_id, const csm_window* w,
+                              const int32_t* hit_col, const int32_t* hit_row,
+                              const csm_volume_params* volume, csm_volume_moments* out);
+/* csm_correlative_match's set-up. */
+int  csm_correlative_covariance(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geom,
+                                const csm_scan* scan, const double initial_pose[3],
+                                const csm_correlative_params* params, const csm_volume_params* volume,
+                                csm_volume_summary* out);
+/* csm_correlative_match_batch's queries; out[n_queries]. All windows of a chunk share each launch. */
+int  csm_correlative_covariance_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
+                                      const csm_correlative_params* params, const csm_volume_params* volume,
+                                      csm_volume_summary* out);
+/* Host restatements (no GPU needed). The weight table of n_points beams at `temperature`:
+ * CSM_EINVAL if n_points < 1 or the temperature is refused as above. */
+int  csm_host_volume_weights(int32_t n_points, double temperature, uint32_t table[CSM_VOLUME_BINS],
+                             int32_t* bin_shift);
+/* steps = (step_x, step_y, step_theta); estimated_pose / rel_pose as in csm_summary / csm_scan. */
+int  csm_host_volume_covariance(const csm_volume_moments* moments, const double steps[3],
+                                const double estimated_pose[3], const double rel_pose[3],
+                                double mean_offset[3], double sensor_cov[9], double cov[9]);
+
 /* The raw records (csm_summary.raw) of the last csm_bnb_match_batch /
  * csm_correlative_match_batch call on this ctx, in query order, copied device
  * to device into dst_dev[n_queries] on the ctx stream (asynchronous): the
@@ -853,7 +932,7 @@ int  csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_er
 int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
 /* Drains recorded events; returns total ms and launch count since the last
  * reset for kernel "score_fine" | "score_coarse" | "bin" | "finalize" | "boxmax" |
- * "peaks_coarse" | "peaks_select". */
+ * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);
 int  csm_reset_kernel_timing(csm_ctx* ctx);

@@ -203,6 +203,24 @@ class PeaksParams(C.Structure):
                 ("scratch_limit_bytes", C.c_int64)]
 
 
+VOLUME_BINS = 1024
+
+
+class VolumeParams(C.Structure):
+    _fields_ = [("temperature", C.c_double), ("scratch_limit_bytes", C.c_int64)]
+
+
+class VolumeMoments(C.Structure):
+    _fields_ = [("best", Result), ("m0", C.c_int64), ("m1", C.c_int64 * 3), ("m2", C.c_int64 * 6),
+                ("support", C.c_int64), ("border_support", C.c_int64), ("bin_shift", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class VolumeSummary(C.Structure):
+    _fields_ = [("summary", Summary), ("moments", VolumeMoments), ("mean_offset", C.c_double * 3),
+                ("sensor_covariance", C.c_double * 9), ("covariance", C.c_double * 9)]
+
+
 # name -> (restype, argtypes); mirrors include/csm_hip.h one to one
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -257,6 +275,15 @@ SIGNATURES = {
                                         _P(CorrelativeParams), _P(PeaksParams), _P(Summary), _P(C.c_int32)]),
     "csm_correlative_peaks_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(CorrelativeParams),
                                               _P(PeaksParams), _P(Summary), _P(C.c_int32)]),
+    "csm_score_window_moments": (C.c_int, [_ctx, C.c_uint64, _P(Window), C.c_void_p, C.c_void_p, _P(VolumeParams),
+                                           _P(VolumeMoments)]),
+    "csm_correlative_covariance": (C.c_int, [_ctx, C.c_uint64, _P(Geometry), _P(Scan), C.c_void_p,
+                                             _P(CorrelativeParams), _P(VolumeParams), _P(VolumeSummary)]),
+    "csm_correlative_covariance_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(CorrelativeParams),
+                                                   _P(VolumeParams), _P(VolumeSummary)]),
+    "csm_host_volume_weights": (C.c_int, [C.c_int32, C.c_double, C.c_void_p, _P(C.c_int32)]),
+    "csm_host_volume_covariance": (C.c_int, [_P(VolumeMoments), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "csm_bnb_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,
                                       _P(BnbParams), _P(Summary)]),
     "csm_correlative_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,

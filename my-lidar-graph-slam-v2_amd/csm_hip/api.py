@@ -208,6 +208,52 @@ def host_hill_climbing(grid, geom, angles, ranges, rel_pose, init_pose, linear_s
     return Context._hill_to_dict(out)
 
 
+def host_volume_weights(n_points, temperature):
+    """(table uint32[VOLUME_BINS], bin_shift): the fixed-point weights of the volume covariance
+    (csm_host_volume_weights)."""
+    table = np.zeros(L.VOLUME_BINS, np.uint32)
+    shift = C.c_int32(0)
+    rc = L.load().csm_host_volume_weights(n_points, temperature, _ptr(table), C.byref(shift))
+    if rc != 0:
+        raise CsmError(rc, "csm_host_volume_weights")
+    return table, shift.value
+
+
+def moments_struct(m):
+    """csm_volume_moments from a dict with m0, m1[3], m2[6] (the other fields default to 0)."""
+    out = L.VolumeMoments()
+    out.m0 = m["m0"]
+    out.m1[:] = list(m["m1"])
+    out.m2[:] = list(m["m2"])
+    out.support, out.border_support = m.get("support", 0), m.get("border_support", 0)
+    out.bin_shift = m.get("bin_shift", 0)
+    return out
+
+
+def host_volume_covariance(moments, steps, estimated_pose, rel_pose):
+    """(mean_offset[3], sensor_covariance[9], covariance[9]) as lists of floats, from a moments dict
+    (csm_host_volume_covariance)."""
+    m = moments_struct(moments)
+    st, est, rel = _f64(steps), _f64(estimated_pose), _f64(rel_pose)
+    mean, scov, cov = np.zeros(3), np.zeros(9), np.zeros(9)
+    rc = L.load().csm_host_volume_covariance(C.byref(m), _ptr(st), _ptr(est), _ptr(rel), _ptr(mean), _ptr(scov),
+                                             _ptr(cov))
+    if rc != 0:
+        raise CsmError(rc, "csm_host_volume_covariance")
+    return mean.tolist(), scov.tolist(), cov.tolist()
+
+
+def moments_to_dict(m):
+    return dict(best=result_to_dict(m.best), m0=m.m0, m1=list(m.m1), m2=list(m.m2), support=m.support,
+                border_support=m.border_support, bin_shift=m.bin_shift)
+
+
+def volume_summary_to_dict(v):
+    return dict(summary=summary_to_dict(v.summary), moments=moments_to_dict(v.moments),
+                mean_offset=list(v.mean_offset), sensor_covariance=list(v.sensor_covariance),
+                covariance=list(v.covariance))
+
+
 def host_probability_lut():
     lut = np.zeros(65536)
     L.load().csm_host_probability_lut(_ptr(lut))
@@ -538,6 +584,59 @@ class Context:
         if as_records:
             return out, n
         return [[summary_to_dict(out[i * kk + j]) for j in range(n[i])] for i in range(prep.n)]
+
+    def score_window_moments(self, map_id, window, hit_col, hit_row, temperature, scratch_limit_bytes=0):
+        """The winner and the integer moments of one pre-projected window's score volume
+        (csm_score_window_moments), as a dict."""
+        col = np.ascontiguousarray(hit_col, dtype=np.int32)
+        row = np.ascontiguousarray(hit_row, dtype=np.int32)
+        vp = L.VolumeParams(temperature, scratch_limit_bytes)
+        out = L.VolumeMoments()
+        self._check(self.lib.csm_score_window_moments(self._ctx, map_id, C.byref(window), _ptr(col), _ptr(row),
+                                                      C.byref(vp), C.byref(out)))
+        return moments_to_dict(out)
+
+    def correlative_covariance(self, map_id, geom, angles, ranges, rel_pose, init_pose, range_x, range_y,
+                               range_theta, low_resolution, temperature, score_threshold=0.0,
+                               known_rate_threshold=0.0, scratch_limit_bytes=0):
+        """correlative_match() with the pose covariance read off the score volume
+        (csm_correlative_covariance): a dict of summary, moments, mean_offset, sensor_covariance,
+        covariance."""
+        a, r = _f64(angles), _f64(ranges)
+        scan = L.Scan()
+        scan.angles = a.ctypes.data_as(C.POINTER(C.c_double))
+        scan.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
+        scan.n_points = a.size
+        scan.relative_sensor_pose[:] = list(rel_pose)
+        g = L.Geometry(*geom)
+        p = L.CorrelativeParams()
+        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
+        p.low_resolution = low_resolution
+        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        init = _f64(init_pose)
+        vp = L.VolumeParams(temperature, scratch_limit_bytes)
+        out = L.VolumeSummary()
+        self._check(self.lib.csm_correlative_covariance(self._ctx, map_id, C.byref(g), C.byref(scan), _ptr(init),
+                                                        C.byref(p), C.byref(vp), C.byref(out)))
+        return volume_summary_to_dict(out)
+
+    def correlative_covariance_batch(self, queries, range_x, range_y, range_theta, low_resolution, temperature,
+                                     score_threshold=0.0, known_rate_threshold=0.0, scratch_limit_bytes=0,
+                                     as_records=False):
+        """correlative_match_batch() with the volume covariance of every query
+        (csm_correlative_covariance_batch): one dict per query. as_records: the C array instead."""
+        prep = self.prepare_queries(queries)
+        p = L.CorrelativeParams()
+        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
+        p.low_resolution = low_resolution
+        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        vp = L.VolumeParams(temperature, scratch_limit_bytes)
+        out = (L.VolumeSummary * prep.n)()
+        self._check(self.lib.csm_correlative_covariance_batch(self._ctx, prep.arr, prep.n, C.byref(p), C.byref(vp),
+                                                              out))
+        if as_records:
+            return out
+        return [volume_summary_to_dict(out[i]) for i in range(prep.n)]
 
     def construct_map_from_scans(self, map_id, shape, map_pose, nodes, usable_range_min=0.01,
                                  usable_range_max=20.0, prob_hit=0.62, prob_miss=0.46,

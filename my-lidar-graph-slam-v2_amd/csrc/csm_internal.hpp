@@ -226,6 +226,10 @@ struct csm_ctx {
      * job table + records, pinned staging */
     DevBuf pk_vol, pk_hits, pk_tab;
     PinBuf pk_pin;
+    /* volume covariance (csm_volume_api.hip) on top of the peaks' owners: job table, weight tables,
+     * workgroup records + results; pinned staging */
+    DevBuf vc_tab;
+    PinBuf vc_pin;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */

@@ -1,0 +1,91 @@
+/* csm_peaks.hpp -- what the units that read a window's whole score volume share: the peaks entries
+ * (csm_peaks_api.hip, which defines everything declared here) and the volume covariance
+ * (csm_volume_api.hip). The device-side job record of one window, and the host stages of a chunk:
+ * sizing, projection on the device, exact scores + coarse known counts + selection rounds. */
+#ifndef CSM_PEAKS_HPP
+#define CSM_PEAKS_HPP
+
+#include "csm_matchers.hpp"
+
+namespace csm {
+
+constexpr int kPeakBlock = 256;      /* threads per workgroup of the selection kernels (4 wave64) */
+constexpr int kPeakBlocksMax = 256;  /* workgroups per window and round: k_peaks_pick reduces one record per thread */
+constexpr int kPeaksMax = CSM_PEAKS_MAX;
+
+struct PeakJob {
+    const uint32_t* s;         /* [n_theta][nx][ny] */
+    const uint16_t* k;
+    uint16_t* ck;              /* [n_theta][nx / L][ny / L] known counts of the coarse nodes; null: L == 1 */
+    const uint16_t* cells;     /* level 0, pitched */
+    const uint16_t* coarse;    /* box-max(L) level, same shape */
+    int32_t rows, cols, pitch;
+    const int32_t* hit_col;    /* [n_theta][n_points] */
+    const int32_t* hit_row;
+    const double* lut;
+    const csm_result* chain;   /* the exhaustive chain's record of this window: its edge-band flag */
+    csm_result* out;           /* [k_max], zero before round 0 */
+    int32_t* state;            /* [0] peaks written, [1] list closed */
+    BlockBest* partial;        /* [blocks] */
+    int32_t n_theta, n_points, win_theta;
+    int32_t nx, ny, L, x_lo, y_lo;
+    int32_t min_known, blocks, chunk;   /* chunk: candidates per workgroup, blocks * chunk >= n_theta nx ny */
+    int32_t k_max, excl_x, excl_y, excl_theta;
+    double score_thr;
+};
+
+} /* namespace csm */
+
+namespace csm_host {
+
+constexpr int64_t kPeaksDefaultScratch = (int64_t)1 << 30;
+constexpr int64_t kPeaksMaxCandidates = (int64_t)1 << 26;
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+/* a scratch owner of the volume entries: no recorded graph points at it */
+inline int reserve(csm_ctx* ctx, DevBuf& b, size_t bytes) { return grow(ctx, b, bytes, bytes + bytes / 4 + 256, false); }
+
+/* One window of a peaks call once its arguments are checked. */
+struct PeakWindow {
+    uint64_t map_id = 0;
+    DeviceGrid* grid = nullptr;
+    csm_window w = {};
+    WindowFrame f;
+    int64_t total = 0;           /* candidates */
+    size_t vol_bytes = 0;        /* S, K and coarse K, each padded to 256 bytes */
+    size_t hit_off = 0;          /* of its hit columns in pk_hits (bytes); the rows follow */
+};
+
+/* What peaks_select_chunk leaves on the device (in ctx->pk_tab) and in pinned memory (ctx->pk_pin). */
+struct PeakChunk {
+    const csm::PeakJob* jobs_dev = nullptr;    /* [m] */
+    const csm::PeakJob* jobs_pin = nullptr;    /* the host's copy; valid until pk_pin is written again */
+    const csm_result* rec_dev = nullptr;       /* [m][k_max], followed by the states [m][2] */
+    size_t back_bytes = 0;                     /* records + states */
+    char* back_pin = nullptr;                  /* room for them in pk_pin */
+};
+
+/* The window's candidate domain and scratch need against `scratch_limit` (0: the default); nothing is
+ * allocated. */
+int peaks_size_window(csm_ctx* ctx, PeakWindow& pw, int64_t scratch_limit, int index);
+/* The search set-up of every query as csm_correlative_match makes it (head[i]: poses, steps, window),
+ * its window sized, the coarse levels built. */
+int peaks_prepare_queries(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_correlative_params* prm,
+                          int64_t scratch_limit, std::vector<PeakWindow>& wins, std::vector<csm_summary>& head);
+/* [lo, hi) of the next chunk: windows in order while their volumes fit the limit (each fits on its own). */
+int peaks_next_chunk(const std::vector<PeakWindow>& wins, int lo, int64_t scratch_limit);
+/* Scans of queries [lo, hi) projected on the device into pk_hits (a window with an entry the projection
+ * cannot certify: on the host); sets hit_off. Waits for the stream. */
+int peaks_project_chunk(csm_ctx* ctx, const csm_loop_query* queries, std::vector<PeakWindow>& wins,
+                        const std::vector<csm_summary>& head, int lo, int hi);
+/* Windows [lo, hi) with their hit indices in pk_hits: exact scores of every candidate, coarse known
+ * counts, pk->k_max selection rounds. Everything is queued on the stream; nothing is copied back and the
+ * host does not wait for the selection. */
+int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
+                       PeakChunk* out);
+/* The poses of a record: best_sensor_pose and estimated_pose of `o` from o.raw. */
+void peaks_fill_poses(csm_summary& o, const double relative_sensor_pose[3]);
+
+} /* namespace csm_host */
+#endif

@@ -9,30 +9,11 @@
  * of two launches each pick the peaks of all the chunk's windows, with no host wait between the rounds.
  * The records and the peak counts come back in one copy. The host waits for the projection's flags and
  * for that copy (and wherever the scoring chain itself waits). The scratch lives in the context's owners (pk_vol, pk_hits, pk_tab, pk_pin). */
-#include "csm_matchers.hpp"
+#include "csm_peaks.hpp"
 
 #include "csm_peaks_kernels.hip"
 
 namespace {
-
-constexpr int64_t kPeaksDefaultScratch = (int64_t)1 << 30;
-constexpr int64_t kPeaksMaxCandidates = (int64_t)1 << 26;
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-/* a scratch owner of the peaks entries: no recorded graph points at it */
-int reserve(csm_ctx* ctx, DevBuf& b, size_t bytes) { return grow(ctx, b, bytes, bytes + bytes / 4 + 256, false); }
-
-/* One window of a peaks call once its arguments are checked. */
-struct PeakWindow {
-    uint64_t map_id = 0;
-    DeviceGrid* grid = nullptr;
-    csm_window w = {};
-    WindowFrame f;
-    int64_t total = 0;           /* candidates */
-    size_t vol_bytes = 0;        /* S, K and coarse K, each padded to 256 bytes */
-    size_t hit_off = 0;          /* of its hit columns in pk_hits (bytes); the rows follow */
-};
 
 int check_params(csm_ctx* ctx, const csm_peaks_params* pk, const char* who)
 {
@@ -43,8 +24,11 @@ int check_params(csm_ctx* ctx, const csm_peaks_params* pk, const char* who)
     return CSM_OK;
 }
 
-/* The window's candidate domain and scratch need; nothing is allocated. */
-int size_window(csm_ctx* ctx, PeakWindow& pw, const csm_peaks_params* pk, int index)
+} /* namespace */
+
+namespace csm_host {
+
+int peaks_size_window(csm_ctx* ctx, PeakWindow& pw, int64_t scratch_limit, int index)
 {
     const csm_window& w = pw.w;
     if (w.n_theta < 1 || (w.n_theta & 1) == 0 || w.n_points < 1 || w.win_x < 0 || w.win_y < 0 || w.low_resolution < 1)
@@ -60,17 +44,15 @@ int size_window(csm_ctx* ctx, PeakWindow& pw, const csm_peaks_params* pk, int in
                     (long long)pw.total, (long long)kPeaksMaxCandidates);
     pw.vol_bytes = align256((size_t)pw.total * 4) + align256((size_t)pw.total * 2) +
                    (L > 1 ? align256((size_t)(pw.total / (L * L)) * 2) : 0);
-    const int64_t limit = pk->scratch_limit_bytes ? pk->scratch_limit_bytes : kPeaksDefaultScratch;
+    const int64_t limit = scratch_limit ? scratch_limit : kPeaksDefaultScratch;
     if ((int64_t)pw.vol_bytes > limit)
         return fail(ctx, CSM_EINVAL, "window %d: its score volume (%zu bytes) exceeds the scratch limit (%lld)", index,
                     pw.vol_bytes, (long long)limit);
     return CSM_OK;
 }
 
-/* Windows [lo, hi) of `wins` with their hit indices on the device (pk_hits): exact scores, coarse known
- * counts, selection rounds. rec[(i - lo) * k_max + j] and n_peaks[i - lo] receive the result. */
-int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
-              csm_result* rec, int32_t* n_peaks)
+int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
+                       PeakChunk* out)
 {
     const int m = hi - lo, k_max = pk->k_max;
     int rc;
@@ -185,7 +167,28 @@ int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const
                 return rc;
         }
     }
-    HIP_TRY(ctx, hipMemcpyAsync(back_pin, rec_dev, back_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    out->jobs_dev = jobs_dev;
+    out->jobs_pin = jobs_pin;
+    out->rec_dev = rec_dev;
+    out->back_bytes = back_bytes;
+    out->back_pin = back_pin;
+    return CSM_OK;
+}
+
+} /* namespace csm_host */
+
+namespace {
+
+/* peaks_select_chunk, then rec[(i - lo) * k_max + j] and n_peaks[i - lo] receive the result. */
+int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
+              csm_result* rec, int32_t* n_peaks)
+{
+    const int m = hi - lo, k_max = pk->k_max;
+    PeakChunk ch;
+    if (int rc = peaks_select_chunk(ctx, wins, lo, hi, pk, &ch))
+        return rc;
+    char* const back_pin = ch.back_pin;
+    HIP_TRY(ctx, hipMemcpyAsync(back_pin, ch.rec_dev, ch.back_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(rec, back_pin, (size_t)m * k_max * sizeof(csm_result));
     const int32_t* state = reinterpret_cast<const int32_t*>(back_pin + (size_t)m * k_max * sizeof(csm_result));
@@ -194,10 +197,13 @@ int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const
     return CSM_OK;
 }
 
-/* [lo, hi) of the next chunk: windows in order while their volumes fit the limit (each fits on its own). */
-int next_chunk(const std::vector<PeakWindow>& wins, int lo, const csm_peaks_params* pk)
+} /* namespace */
+
+namespace csm_host {
+
+int peaks_next_chunk(const std::vector<PeakWindow>& wins, int lo, int64_t scratch_limit)
 {
-    const int64_t limit = pk->scratch_limit_bytes ? pk->scratch_limit_bytes : kPeaksDefaultScratch;
+    const int64_t limit = scratch_limit ? scratch_limit : kPeaksDefaultScratch;
     int64_t sum = 0;
     int hi = lo;
     while (hi < (int)wins.size() && (hi == lo || sum + (int64_t)wins[hi].vol_bytes <= limit))
@@ -205,14 +211,13 @@ int next_chunk(const std::vector<PeakWindow>& wins, int lo, const csm_peaks_para
     return hi;
 }
 
-int peaks_batch(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_correlative_params* prm,
-                const csm_peaks_params* pk, csm_summary* out, int32_t* n_peaks)
+int peaks_prepare_queries(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_correlative_params* prm,
+                          int64_t scratch_limit, std::vector<PeakWindow>& wins, std::vector<csm_summary>& head)
 {
     int rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const int k_max = pk->k_max, L = prm->low_resolution;
-    std::vector<PeakWindow> wins(n);
-    std::vector<csm_summary> head(n);
+    const int L = prm->low_resolution;
+    wins.assign(n, PeakWindow());
+    head.resize(n);
     for (int i = 0; i < n; ++i) {
         const csm_loop_query& q = queries[i];
         if (!q.scan.angles || !q.scan.ranges || q.scan.n_points < 1 || !scan_is_finite(&q.scan))
@@ -234,7 +239,7 @@ int peaks_batch(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_co
         pw.w.min_known = csm_host_min_known(q.scan.n_points, prm->known_rate_threshold);
         pw.w.score_threshold = prm->score_threshold;
         pw.w.merge_mode = merging_pays(q.scan.angles, q.scan.ranges, q.scan.n_points, q.geometry.resolution) ? 0 : 1;
-        if ((rc = size_window(ctx, pw, pk, i))) return rc;
+        if ((rc = peaks_size_window(ctx, pw, scratch_limit, i))) return rc;
         o.candidates = pw.total;
     }
     {
@@ -243,71 +248,104 @@ int peaks_batch(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_co
             if ((rc = level_for_window(ctx, *wins[i].grid, L, &wins[i].w.coarse_level, &pending))) return rc;
         if ((rc = launch_box_jobs(ctx, pending))) return rc;
     }
+    return CSM_OK;
+}
+
+int peaks_project_chunk(csm_ctx* ctx, const csm_loop_query* queries, std::vector<PeakWindow>& wins,
+                        const std::vector<csm_summary>& head, int lo, int hi)
+{
+    int rc;
+    const int m = hi - lo;
+    /* pk_hits: [scans][hit indices]; pk_pin (staging): [projection jobs | flag words][scans] */
+    size_t scan_bytes = 0, hit_bytes = 0;
+    for (int i = lo; i < hi; ++i)
+        scan_bytes += (size_t)wins[i].w.n_points * 16;
+    scan_bytes = align256(scan_bytes);
+    for (int i = lo; i < hi; ++i) {
+        wins[i].hit_off = scan_bytes + hit_bytes;
+        hit_bytes += align256((size_t)wins[i].w.n_theta * wins[i].w.n_points * 8);
+    }
+    const size_t proj_bytes = align256((size_t)m * sizeof(ProjJob)), flag_bytes = align256((size_t)m * 4);
+    if ((rc = reserve(ctx, ctx->pk_hits, scan_bytes + hit_bytes + proj_bytes + flag_bytes))) return rc;
+    const size_t pin_bytes = proj_bytes + flag_bytes + scan_bytes;
+    if ((rc = grow(ctx, ctx->pk_pin, pin_bytes, pin_bytes + pin_bytes / 4, false))) return rc;
+    char* const dev = ctx->pk_hits.as<char>();
+    ProjJob* const proj_dev = reinterpret_cast<ProjJob*>(dev + scan_bytes + hit_bytes);
+    uint32_t* const flags_dev = reinterpret_cast<uint32_t*>(dev + scan_bytes + hit_bytes + proj_bytes);
+    ProjJob* const proj_pin = ctx->pk_pin.as<ProjJob>();
+    uint32_t* const flags_pin = reinterpret_cast<uint32_t*>(ctx->pk_pin.as<char>() + proj_bytes);
+    double* const scans_pin = reinterpret_cast<double*>(ctx->pk_pin.as<char>() + proj_bytes + flag_bytes);
+    size_t off = 0;
+    int n_points_max = 0, n_theta_max = 0;
+    for (int i = lo; i < hi; ++i) {
+        const csm_loop_query& q = queries[i];
+        const int np = q.scan.n_points;
+        std::memcpy(scans_pin + off, q.scan.angles, (size_t)np * 8);
+        std::memcpy(scans_pin + off + np, q.scan.ranges, (size_t)np * 8);
+        int32_t* col = reinterpret_cast<int32_t*>(dev + wins[i].hit_off);
+        ProjJob& I = proj_pin[i - lo];
+        I = proj_job(q.geometry, head[i].sensor_pose, head[i].step_theta, head[i].win_theta, np,
+                     reinterpret_cast<double*>(dev) + off, reinterpret_cast<double*>(dev) + off + np, col,
+                     col + (size_t)wins[i].w.n_theta * np);
+        I.flags = flags_dev + (i - lo);
+        I.flag_uncertain = 1;
+        off += 2 * (size_t)np;
+        n_points_max = std::max(n_points_max, np);
+        n_theta_max = std::max(n_theta_max, wins[i].w.n_theta);
+    }
+    std::memset(flags_pin, 0, flag_bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(dev, scans_pin, off * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(proj_dev, proj_pin, proj_bytes + flag_bytes, hipMemcpyHostToDevice, ctx->stream));
+    {
+        ScopedTimer tm(ctx, "project");
+        const int pb = ceil_div(n_points_max, kBlock);
+        if ((rc = launched_ok(ctx, csm_launch::project_batch(ctx->stream, dim3(pb, proj_theta_groups(n_theta_max, (long)pb * m), m),
+                                                             proj_dev), "projection")))
+            return rc;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(flags_pin, flags_dev, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = lo; i < hi; ++i) {
+        if (!(flags_pin[i - lo] & CSM_FLAG_PROJ_DELTA))
+            continue;
+        /* an entry too close to a cell edge for the device's sin / cos: this window with glibc */
+        const csm_loop_query& q = queries[i];
+        const size_t hn = (size_t)wins[i].w.n_theta * q.scan.n_points;
+        std::vector<int32_t> cr(2 * hn);
+        csm_host_project(&q.geometry, head[i].sensor_pose, head[i].step_theta, head[i].win_theta, q.scan.angles,
+                         q.scan.ranges, q.scan.n_points, cr.data(), cr.data() + hn, nullptr, nullptr);
+        HIP_TRY(ctx, hipMemcpy(dev + wins[i].hit_off, cr.data(), hn * 8, hipMemcpyHostToDevice));
+    }
+    return CSM_OK;
+}
+
+void peaks_fill_poses(csm_summary& o, const double relative_sensor_pose[3])
+{
+    o.pose_found = o.raw.found;
+    o.best_sensor_pose[0] = o.sensor_pose[0] + o.raw.best_x * o.step_x;
+    o.best_sensor_pose[1] = o.sensor_pose[1] + o.raw.best_y * o.step_y;
+    o.best_sensor_pose[2] = o.sensor_pose[2] + o.raw.best_theta * o.step_theta;
+    csm_host_move_backward(o.best_sensor_pose, relative_sensor_pose, o.estimated_pose);
+}
+
+} /* namespace csm_host */
+
+namespace {
+
+int peaks_batch(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_correlative_params* prm,
+                const csm_peaks_params* pk, csm_summary* out, int32_t* n_peaks)
+{
+    int rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int k_max = pk->k_max;
+    std::vector<PeakWindow> wins;
+    std::vector<csm_summary> head;
+    if ((rc = peaks_prepare_queries(ctx, queries, n, prm, pk->scratch_limit_bytes, wins, head))) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     std::vector<csm_result> rec((size_t)n * k_max);
     for (int lo = 0, hi; lo < n; lo = hi) {
-        hi = next_chunk(wins, lo, pk);
-        const int m = hi - lo;
-        /* pk_hits: [scans][hit indices]; pk_pin (staging): [projection jobs | flag words][scans] */
-        size_t scan_bytes = 0, hit_bytes = 0;
-        for (int i = lo; i < hi; ++i)
-            scan_bytes += (size_t)wins[i].w.n_points * 16;
-        scan_bytes = align256(scan_bytes);
-        for (int i = lo; i < hi; ++i) {
-            wins[i].hit_off = scan_bytes + hit_bytes;
-            hit_bytes += align256((size_t)wins[i].w.n_theta * wins[i].w.n_points * 8);
-        }
-        const size_t proj_bytes = align256((size_t)m * sizeof(ProjJob)), flag_bytes = align256((size_t)m * 4);
-        if ((rc = reserve(ctx, ctx->pk_hits, scan_bytes + hit_bytes + proj_bytes + flag_bytes))) return rc;
-        const size_t pin_bytes = proj_bytes + flag_bytes + scan_bytes;
-        if ((rc = grow(ctx, ctx->pk_pin, pin_bytes, pin_bytes + pin_bytes / 4, false))) return rc;
-        char* const dev = ctx->pk_hits.as<char>();
-        ProjJob* const proj_dev = reinterpret_cast<ProjJob*>(dev + scan_bytes + hit_bytes);
-        uint32_t* const flags_dev = reinterpret_cast<uint32_t*>(dev + scan_bytes + hit_bytes + proj_bytes);
-        ProjJob* const proj_pin = ctx->pk_pin.as<ProjJob>();
-        uint32_t* const flags_pin = reinterpret_cast<uint32_t*>(ctx->pk_pin.as<char>() + proj_bytes);
-        double* const scans_pin = reinterpret_cast<double*>(ctx->pk_pin.as<char>() + proj_bytes + flag_bytes);
-        size_t off = 0;
-        int n_points_max = 0, n_theta_max = 0;
-        for (int i = lo; i < hi; ++i) {
-            const csm_loop_query& q = queries[i];
-            const int np = q.scan.n_points;
-            std::memcpy(scans_pin + off, q.scan.angles, (size_t)np * 8);
-            std::memcpy(scans_pin + off + np, q.scan.ranges, (size_t)np * 8);
-            int32_t* col = reinterpret_cast<int32_t*>(dev + wins[i].hit_off);
-            ProjJob& I = proj_pin[i - lo];
-            I = proj_job(q.geometry, head[i].sensor_pose, head[i].step_theta, head[i].win_theta, np,
-                         reinterpret_cast<double*>(dev) + off, reinterpret_cast<double*>(dev) + off + np, col,
-                         col + (size_t)wins[i].w.n_theta * np);
-            I.flags = flags_dev + (i - lo);
-            I.flag_uncertain = 1;
-            off += 2 * (size_t)np;
-            n_points_max = std::max(n_points_max, np);
-            n_theta_max = std::max(n_theta_max, wins[i].w.n_theta);
-        }
-        std::memset(flags_pin, 0, flag_bytes);
-        HIP_TRY(ctx, hipMemcpyAsync(dev, scans_pin, off * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(proj_dev, proj_pin, proj_bytes + flag_bytes, hipMemcpyHostToDevice, ctx->stream));
-        {
-            ScopedTimer tm(ctx, "project");
-            const int pb = ceil_div(n_points_max, kBlock);
-            if ((rc = launched_ok(ctx, csm_launch::project_batch(ctx->stream, dim3(pb, proj_theta_groups(n_theta_max, (long)pb * m), m),
-                                                                 proj_dev), "projection")))
-                return rc;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(flags_pin, flags_dev, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = lo; i < hi; ++i) {
-            if (!(flags_pin[i - lo] & CSM_FLAG_PROJ_DELTA))
-                continue;
-            /* an entry too close to a cell edge for the device's sin / cos: this window with glibc */
-            const csm_loop_query& q = queries[i];
-            const size_t hn = (size_t)wins[i].w.n_theta * q.scan.n_points;
-            std::vector<int32_t> cr(2 * hn);
-            csm_host_project(&q.geometry, head[i].sensor_pose, head[i].step_theta, head[i].win_theta, q.scan.angles,
-                             q.scan.ranges, q.scan.n_points, cr.data(), cr.data() + hn, nullptr, nullptr);
-            HIP_TRY(ctx, hipMemcpy(dev + wins[i].hit_off, cr.data(), hn * 8, hipMemcpyHostToDevice));
-        }
+        hi = peaks_next_chunk(wins, lo, pk->scratch_limit_bytes);
+        if ((rc = peaks_project_chunk(ctx, queries, wins, head, lo, hi))) return rc;
         if ((rc = run_chunk(ctx, wins, lo, hi, pk, rec.data() + (size_t)lo * k_max, n_peaks + lo))) return rc;
     }
     const auto t2 = std::chrono::steady_clock::now();
@@ -319,11 +357,7 @@ int peaks_batch(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_co
             csm_summary& o = out[(size_t)i * k_max + j];
             o = head[i];
             o.raw = rec[(size_t)i * k_max + j];
-            o.pose_found = o.raw.found;
-            o.best_sensor_pose[0] = o.sensor_pose[0] + o.raw.best_x * o.step_x;
-            o.best_sensor_pose[1] = o.sensor_pose[1] + o.raw.best_y * o.step_y;
-            o.best_sensor_pose[2] = o.sensor_pose[2] + o.raw.best_theta * o.step_theta;
-            csm_host_move_backward(o.best_sensor_pose, queries[i].scan.relative_sensor_pose, o.estimated_pose);
+            peaks_fill_poses(o, queries[i].scan.relative_sensor_pose);
             o.input_setup_us = setup;
             o.optimization_us = opt;
         }
@@ -345,7 +379,7 @@ int csm_score_window_peaks(csm_ctx* ctx, uint64_t map_id, const csm_window* w, c
     PeakWindow& pw = wins[0];
     pw.map_id = map_id;
     pw.w = *w;
-    if ((rc = size_window(ctx, pw, pk, 0))) return rc;
+    if ((rc = peaks_size_window(ctx, pw, pk->scratch_limit_bytes, 0))) return rc;
     if (w->low_resolution > 1 &&
         (w->coarse_level < 0 || w->coarse_level >= (int)pw.grid->levels.size() || pw.grid->levels[w->coarse_level].stale ||
          pw.grid->levels[w->coarse_level].win != w->low_resolution))

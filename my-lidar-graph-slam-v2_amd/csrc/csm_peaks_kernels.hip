@@ -14,33 +14,9 @@
 #include <stdint.h>
 
 #include "csm_score_common.hpp"
+#include "csm_peaks.hpp"
 
 namespace csm {
-
-constexpr int kPeakBlock = 256;      /* threads per workgroup of the selection kernels (4 wave64) */
-constexpr int kPeakBlocksMax = 256;  /* workgroups per window and round: k_peaks_pick reduces one record per thread */
-constexpr int kPeaksMax = CSM_PEAKS_MAX;
-
-struct PeakJob {
-    const uint32_t* s;         /* [n_theta][nx][ny] */
-    const uint16_t* k;
-    uint16_t* ck;              /* [n_theta][nx / L][ny / L] known counts of the coarse nodes; null: L == 1 */
-    const uint16_t* cells;     /* level 0, pitched */
-    const uint16_t* coarse;    /* box-max(L) level, same shape */
-    int32_t rows, cols, pitch;
-    const int32_t* hit_col;    /* [n_theta][n_points] */
-    const int32_t* hit_row;
-    const double* lut;
-    const csm_result* chain;   /* the exhaustive chain's record of this window: its edge-band flag */
-    csm_result* out;           /* [k_max], zero before round 0 */
-    int32_t* state;            /* [0] peaks written, [1] list closed */
-    BlockBest* partial;        /* [blocks] */
-    int32_t n_theta, n_points, win_theta;
-    int32_t nx, ny, L, x_lo, y_lo;
-    int32_t min_known, blocks, chunk;   /* chunk: candidates per workgroup, blocks * chunk >= n_theta nx ny */
-    int32_t k_max, excl_x, excl_y, excl_theta;
-    double score_thr;
-};
 
 /* Known count of every coarse node: hit cells that are known on the box-max(L) level at the node's
  * offset (reads outside the map are unknown), as ComputeScore on the coarse map counts them. One lane

@@ -320,6 +320,39 @@ public:
         return out;
     }
 
+    /* OptimizePose with mEstimatedCovariance read off the window's whole score volume
+     * (csm_correlative_covariance; beyond the reference, whose covariance is the cost function's Hessian at
+     * the winner): every candidate weighs exp(-(best score - score) / temperature), so a ridge, a plateau
+     * or a second lobe in the window widens the matrix. temperature: in score units, the caller's choice.
+     * *borderSupport (optional): weighted candidates on a face of the window; non-zero says the window
+     * truncated the distribution. The cost stays zero. */
+    ScanMatchingSummary OptimizePoseVolumeCovariance(const ScanMatchingQuery& q, double temperature,
+                                                     long long* borderSupport = nullptr,
+                                                     const double normalizedScoreThreshold = 0.0,
+                                                     const double knownRateThreshold = 0.0)
+    {
+        csm_ctx* ctx = this->mCtx.get();
+        const GridMapView& g = q.mGridMap;
+        const std::uint64_t id = this->MakeResident(g);
+        csm_geometry geom { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
+        const csm_scan scan = detail::ToScan(q.mScanData);
+        const csm_correlative_params prm = this->Params(normalizedScoreThreshold, knownRateThreshold);
+        const double init[3] = { q.mMapLocalInitialPose.mX, q.mMapLocalInitialPose.mY,
+                                 q.mMapLocalInitialPose.mTheta };
+        const csm_volume_params volume { temperature, 0 };
+        csm_volume_summary v {};
+        CSM_ASSERT_OK(ctx, csm_correlative_covariance(ctx, id, &geom, &scan, init, &prm, &volume, &v));
+        ScanMatchingSummary out;
+        detail::FillSummary(v.summary, q.mMapLocalInitialPose, &out);
+        for (int c = 0; c < 9; ++c)
+            out.mEstimatedCovariance[c] = v.covariance[c];
+        if (borderSupport)
+            *borderSupport = v.moments.border_support;
+        if (g.mId == GridMapView::kInvalidId && g.mValues)
+            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
+        return out;
+    }
+
     /* Cost and covariance from the device's CostSquareError instead of a host callback
      * ("CovarianceScale", launcher_settings_default.json:11-13). */
     void UseDeviceCostFunction(double covarianceScale = 1e4) { this->mDeviceCovarianceScale = covarianceScale; }
@@ -827,6 +860,38 @@ public:
         for (std::size_t i = 0; i < queries.size(); ++i)
             for (std::int32_t j = 0; j < count[i]; ++j)
                 results[i].push_back(Result(queries[i], out[i * kMax + static_cast<std::size_t>(j)]));
+        return results;
+    }
+
+    /* Detect() with every result's mEstimatedCovariance read off its window's whole score volume
+     * (csm_correlative_covariance_batch; see ScanMatcherCorrelativeHIP::OptimizePoseVolumeCovariance): the
+     * information matrix of the loop edge then says how ambiguous the window was. *borderSupport
+     * (optional) receives, per result, the weighted candidates on a face of its window. */
+    LoopDetectionResultVector DetectVolumeCovariance(const LoopDetectionQueryVector& queries, double temperature,
+                                                     std::vector<long long>* borderSupport = nullptr)
+    {
+        LoopDetectionResultVector results;
+        if (borderSupport)
+            borderSupport->clear();
+        if (queries.empty())
+            return results;
+        csm_ctx* ctx = this->mCtx.get();
+        const std::vector<csm_loop_query> flat = this->Flatten(queries);
+        const csm_correlative_params prm = this->Params();
+        const csm_volume_params volume { temperature, 0 };
+        std::vector<csm_volume_summary> out(queries.size());
+        CSM_ASSERT_OK(ctx, csm_correlative_covariance_batch(ctx, flat.data(), static_cast<std::int32_t>(flat.size()),
+                                                            &prm, &volume, out.data()));
+        for (std::size_t i = 0; i < queries.size(); ++i) {
+            if (!out[i].summary.pose_found)
+                continue;
+            LoopDetectionResult r = Result(queries[i], out[i].summary);
+            for (int c = 0; c < 9; ++c)
+                r.mEstimatedCovariance[c] = out[i].covariance[c];
+            results.push_back(r);
+            if (borderSupport)
+                borderSupport->push_back(out[i].moments.border_support);
+        }
         return results;
     }
 
