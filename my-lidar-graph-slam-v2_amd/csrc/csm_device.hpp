@@ -150,9 +150,6 @@ struct ScoreJob {
                                   2: plain stores instead of atomic adds, [n_theta][nx][ny] (a launch in
                                   which one lane computes a candidate's whole sum: the coarse pass of the
                                   two-phase search) */
-    uint32_t* in_s;            /* [n_theta][ny][nx]; non-null: no gathering, the sums are read from here (the
-                                  arg-max pass after a tile-split launch) */
-    uint32_t* in_k;            /* (the pass clears what it has read) */
     BlockBest* block_best;     /* [n_theta][n_cand_blocks] */
     /* tie collection pass: append the rank of every eligible candidate whose
      * key equals *collect_key */

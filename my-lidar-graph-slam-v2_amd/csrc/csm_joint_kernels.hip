@@ -620,7 +620,7 @@ __device__ __forceinline__ void score_body_joint(const ScoreJob& job, int cbx, i
         S0[r] = K0[r] = acc0[r] = S1[r] = K1[r] = acc1[r] = 0;
     FlushState fs0 = { 0, 0 }, fs1 = { 0, 0 };
 
-    const int ntiles = __builtin_amdgcn_readfirstlane(job.in_s ? 0 : job.n_tiles[bid_y]);
+    const int ntiles = __builtin_amdgcn_readfirstlane(job.n_tiles[bid_y]);
     const TileRec* recs = job.tiles + (size_t)bid_y * job.max_tiles;
     const uint32_t* __restrict__ pbs = job.sorted_pb + (size_t)bid_y * 2 * job.n_points;
     const size_t xg_pitch = (size_t)job.xg_pitch;

@@ -4,12 +4,13 @@
  * K0 k_bin       merges the beams of one theta slice into (cell, multiplicity)
  *                entries (LDS hash table), sorts them by 64x64-cell endpoint
  *                tile, emits packed LDS offsets per entry.
- * K1 k_score     one workgroup = (theta slice, block of candidate offsets):
+ * K1 k_score_pairs (fine level), k_score (coarser levels, strided candidates)
+ *                one workgroup = (theta slice, block of candidate offsets):
  *                for every non-empty endpoint tile it stages tile + window halo
- *                of the uint16 grid into LDS with 16-byte coalesced loads, then
- *                every lane walks the tile's beams and gathers from LDS for its
- *                own R candidate offsets, accumulating exact integer (S, K).
- *                Ends in a wave64 shuffle arg-max, one record per workgroup.
+ *                of the grid into LDS, then every lane walks the tile's entries
+ *                and gathers from LDS for its own R candidate offsets, exact
+ *                integer (S, K); a wave64 shuffle arg-max, one record per workgroup
+ *                (k_argmax: that end alone, after a tile-split launch).
  *                Replaces ComputeScore inside the sweep of
  *                src/mapping/scan_matcher_correlative.cpp:161-197, 301-368 and
  *                ScorePixelAccurate::Score per branch-and-bound node
@@ -484,12 +485,12 @@ __global__ __launch_bounds__(256) void k_zero_if_band_batch(const ZeroJob* jobs)
 
 /* ------------------------------------------------------------------ K1 */
 
-/* LSTRIDE: LDS row pitch in cells. R: candidate rows per lane.
- * MODE 0: candidates one cell apart; 1: `stride` = 2^k cells apart (coarser
- * levels); 2: any stride (e.g. LowResolutionMapWinSize 5).
- * WEIGHTED: entries carry beam multiplicities (k_bin merged same-cell beams);
- * otherwise every entry is one beam and the multiply is dropped. */
-template <int LSTRIDE, int R, int MODE, bool WEIGHTED>
+/* The strided scorer of the coarser levels: candidates `stride` cells apart, entries
+ * weighted by their beam counts (k_bin's sorted_rc words, or the joint lists of k_binj).
+ * LSTRIDE: LDS row pitch in cells. R: candidate rows per lane.
+ * MODE 1: `stride` = 2^k; 2: any stride (e.g. LowResolutionMapWinSize 5).
+ * The fine level (candidates one cell apart) is always a pair-row kernel, below. */
+template <int LSTRIDE, int R, int MODE>
 __device__ __forceinline__ void score_body(const ScoreJob& job, int cbx, int groups,
                                            int slice, int n_slices, int n_buf, int t)
 {
@@ -497,9 +498,9 @@ __device__ __forceinline__ void score_body(const ScoreJob& job, int cbx, int gro
 
     if (t >= job.n_theta)
         return;
+    static_assert(MODE == 1 || MODE == 2, "a power-of-two stride, or any");
     const int tid = threadIdx.x;
-    constexpr bool STRIDED = MODE != 0;
-    const int stride = STRIDED ? job.stride : 1;
+    const int stride = job.stride;
     const int ncbx = (job.nx + cbx - 1) / cbx;
     const int bx = blockIdx.x % ncbx, by = blockIdx.x / ncbx;
     const int cby = groups * R;
@@ -516,8 +517,7 @@ __device__ __forceinline__ void score_body(const ScoreJob& job, int cbx, int gro
     const int x0 = job.x_lo + bx * cbx * stride;
     const int y0 = job.y_lo + by * cby * stride;
     /* LDS: one region of expanded cells (u32), then the beam offsets of the
-     * tile (kPbMax words). Stride-1 jobs keep the region row-major. Strided
-     * jobs (candidates 2^k cells apart) store it phase-major in both axes --
+     * tile (kPbMax words). The region is stored phase-major in both axes --
      * region cell (rho, gamma) lives at row (rho mod s) * hd + rho div s,
      * column (gamma mod s) * wd + gamma div s -- so that the candidates of one
      * beam are contiguous again: conflict-free reads, R rows per lane. */
@@ -526,7 +526,7 @@ __device__ __forceinline__ void score_body(const ScoreJob& job, int cbx, int gro
     auto smod = [&](uint32_t x) { return MODE == 1 ? x & (uint32_t)(stride - 1) : x % (uint32_t)stride; };
     const int hd = (kTile + stride - 1) / stride + cby - 1;   /* rows per row phase */
     const int wd = LSTRIDE / stride;                          /* columns per column phase */
-    const int max_rows = STRIDED ? hd * stride : kTile + (cby - 1);
+    const int max_rows = hd * stride;
     /* n_buf == 2: two (region + beam offset) buffers used alternately, one
      * barrier per tile; n_buf == 1: one buffer, two barriers per tile */
     const int buf_words = max_rows * LSTRIDE + kPbMax;
@@ -538,13 +538,7 @@ __device__ __forceinline__ void score_body(const ScoreJob& job, int cbx, int gro
 
     /* acc packs (known count << 23) + (sum of values) of at most 128 beams
      * (counted with multiplicity); S, K are the exact totals */
-    uint32_t S[R], K[R], acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        S[r] = 0;
-        K[r] = 0;
-        acc[r] = 0;
-    }
+    uint32_t S[R] = {}, K[R] = {}, acc[R] = {};
     int pending = 0;
     auto flush = [&]() {
 #pragma unroll
@@ -560,15 +554,14 @@ __device__ __forceinline__ void score_body(const ScoreJob& job, int cbx, int gro
     const uint16_t* __restrict__ cells = job.cells;
     /* joint lists (k_binj): records and entries of the PAIR of slices t belongs to; an entry
      * carries the beam counts of both slices (sorted_rc: counts << 16 | row << 7 | col) */
-    const bool joint = STRIDED && job.joint != 0;
+    const bool joint = job.joint != 0;
     const int tp = joint ? t >> 1 : t;
     const int jsh = joint ? 16 + 8 * (t & 1) : 24;          /* where this slice's (even, odd) counts sit */
-    const int ntiles = job.in_s ? 0 : job.n_tiles[tp];
+    const int ntiles = job.n_tiles[tp];
     const TileRec* recs = job.tiles + (size_t)tp * job.max_tiles;
     const uint32_t* __restrict__ pbs = job.sorted_pb + (size_t)tp * (joint ? 2 : 1) * job.n_points;
     /* chunks (8 cells, 16 B of the uint16 grid) one lane may have to fetch per tile */
-    constexpr int kMaxCh =
-        ((STRIDED ? kMaxRegionRowsStrided : kMaxRegionRows) * (LSTRIDE / 8) + kBlock - 1) / kBlock;
+    constexpr int kMaxCh = (kMaxRegionRowsStrided * (LSTRIDE / 8) + kBlock - 1) / kBlock;
     constexpr int kPbRegs = kPbMax / kBlock;
 
     /* Software pipeline: the global loads of tile i+1 (cells and beam offsets)
@@ -648,33 +641,27 @@ __device__ __forceinline__ void score_body(const ScoreJob& job, int cbx, int gro
                     hi4.y = expand(w.z >> 16);
                     hi4.z = expand(w.w & 0xffffu);
                     hi4.w = expand(w.w >> 16);
-                    if (!STRIDED) {
-                        uint4* dst = reinterpret_cast<uint4*>(sm_cells + lr * LSTRIDE + ch * 8);
-                        dst[0] = lo4;
-                        dst[1] = hi4;
+                    uint32_t* drow = sm_cells + (smod(lr) * hd + sdiv(lr)) * LSTRIDE;
+                    if (MODE == 1 && sh == 1) {
+                        /* stride 2: even cells -> phase 0, odd -> phase 1,
+                         * four consecutive dwords each */
+                        *reinterpret_cast<uint4*>(drow + ch * 4) =
+                            make_uint4(lo4.x, lo4.z, hi4.x, hi4.z);
+                        *reinterpret_cast<uint4*>(drow + wd + ch * 4) =
+                            make_uint4(lo4.y, lo4.w, hi4.y, hi4.w);
+                    } else if (MODE == 1 && sh == 2) {
+                        /* stride 4: cells j and j + 4 share phase j */
+                        *reinterpret_cast<uint2*>(drow + ch * 2) = make_uint2(lo4.x, hi4.x);
+                        *reinterpret_cast<uint2*>(drow + wd + ch * 2) = make_uint2(lo4.y, hi4.y);
+                        *reinterpret_cast<uint2*>(drow + 2 * wd + ch * 2) = make_uint2(lo4.z, hi4.z);
+                        *reinterpret_cast<uint2*>(drow + 3 * wd + ch * 2) = make_uint2(lo4.w, hi4.w);
                     } else {
-                        uint32_t* drow = sm_cells + (smod(lr) * hd + sdiv(lr)) * LSTRIDE;
-                        if (MODE == 1 && sh == 1) {
-                            /* stride 2: even cells -> phase 0, odd -> phase 1,
-                             * four consecutive dwords each */
-                            *reinterpret_cast<uint4*>(drow + ch * 4) =
-                                make_uint4(lo4.x, lo4.z, hi4.x, hi4.z);
-                            *reinterpret_cast<uint4*>(drow + wd + ch * 4) =
-                                make_uint4(lo4.y, lo4.w, hi4.y, hi4.w);
-                        } else if (MODE == 1 && sh == 2) {
-                            /* stride 4: cells j and j + 4 share phase j */
-                            *reinterpret_cast<uint2*>(drow + ch * 2) = make_uint2(lo4.x, hi4.x);
-                            *reinterpret_cast<uint2*>(drow + wd + ch * 2) = make_uint2(lo4.y, hi4.y);
-                            *reinterpret_cast<uint2*>(drow + 2 * wd + ch * 2) = make_uint2(lo4.z, hi4.z);
-                            *reinterpret_cast<uint2*>(drow + 3 * wd + ch * 2) = make_uint2(lo4.w, hi4.w);
-                        } else {
-                            const uint32_t e[8] = { lo4.x, lo4.y, lo4.z, lo4.w,
-                                                    hi4.x, hi4.y, hi4.z, hi4.w };
+                        const uint32_t e[8] = { lo4.x, lo4.y, lo4.z, lo4.w,
+                                                hi4.x, hi4.y, hi4.z, hi4.w };
 #pragma unroll
-                            for (int j = 0; j < 8; ++j) {
-                                const uint32_t gm = ch * 8 + j;
-                                drow[smod(gm) * wd + sdiv(gm)] = e[j];
-                            }
+                        for (int j = 0; j < 8; ++j) {
+                            const uint32_t gm = ch * 8 + j;
+                            drow[smod(gm) * wd + sdiv(gm)] = e[j];
                         }
                     }
                 }
@@ -697,40 +684,27 @@ __device__ __forceinline__ void score_body(const ScoreJob& job, int cbx, int gro
         }
         const int a = (cur.c0 + x0) & 7;
         const int cnt = (int)cur.count;
-        const uint32_t* base = sm_cells + tb + a;
-        /* entry = cell offset + number of beams on that cell (<= kMaxMult);
-         * strided jobs read k_bin's sorted_rc words: m_odd << 28 | m_even << 24 |
-         * row << 16 | col inside the bounding box, m_odd beams on the row below */
+        /* an entry is one of k_bin's sorted_rc words: m_odd << 28 | m_even << 24 |
+         * row << 16 | col inside the bounding box, m_even (<= kMaxMult) beams on that
+         * cell and m_odd on the row below; the cells are weighted by the beam counts */
         auto gather_at = [&](const uint32_t* p, uint32_t m) {
-            if (WEIGHTED) {                        /* weighted by the beam count */
 #pragma unroll
-                for (int r = 0; r < R; ++r)
-                    acc[r] = mad_u24(p[r * LSTRIDE], m, acc[r]);
-            } else {
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    acc[r] += p[r * LSTRIDE];
-            }
+            for (int r = 0; r < R; ++r)
+                acc[r] = mad_u24(p[r * LSTRIDE], m, acc[r]);
         };
         auto gather = [&](uint32_t pbv) {
-            if (STRIDED) {
-                const uint32_t cbm = (joint ? pbv & 127u : pbv & 0xffffu) + (uint32_t)a;
-                const uint32_t coff = smod(cbm) * wd + sdiv(cbm);
-                const uint32_t me = (pbv >> jsh) & 15u, mo = (pbv >> (jsh + 4)) & 15u;
-                uint32_t rb = joint ? (pbv >> 7) & 127u : (pbv >> 16) & 0xffu;
-                if (me)
-                    gather_at(sm_cells + tb + (smod(rb) * hd + sdiv(rb)) * LSTRIDE + coff, me);
-                if (mo) {
-                    ++rb;
-                    gather_at(sm_cells + tb + (smod(rb) * hd + sdiv(rb)) * LSTRIDE + coff, mo);
-                }
-            } else {
-                gather_at(base + (pbv & 0xffffu), pbv >> 16);
+            const uint32_t cbm = (joint ? pbv & 127u : pbv & 0xffffu) + (uint32_t)a;
+            const uint32_t coff = smod(cbm) * wd + sdiv(cbm);
+            const uint32_t me = (pbv >> jsh) & 15u, mo = (pbv >> (jsh + 4)) & 15u;
+            uint32_t rb = joint ? (pbv >> 7) & 127u : (pbv >> 16) & 0xffu;
+            if (me)
+                gather_at(sm_cells + tb + (smod(rb) * hd + sdiv(rb)) * LSTRIDE + coff, me);
+            if (mo) {
+                ++rb;
+                gather_at(sm_cells + tb + (smod(rb) * hd + sdiv(rb)) * LSTRIDE + coff, mo);
             }
         };
-        auto mult_of = [&](uint32_t pbv) {
-            return STRIDED ? ((pbv >> jsh) & 15u) + ((pbv >> (jsh + 4)) & 15u) : !WEIGHTED ? 1u : pbv >> 16;
-        };
+        auto mult_of = [&](uint32_t pbv) { return ((pbv >> jsh) & 15u) + ((pbv >> (jsh + 4)) & 15u); };
         /* entries: 64 per LDS read, broadcast with v_readlane */
         uint32_t pb_cur = lpb[lane];
         for (int b0 = 0; b0 < cnt; b0 += 64) {
@@ -768,19 +742,10 @@ __device__ __forceinline__ void score_body(const ScoreJob& job, int cbx, int gro
 }
 
 /* grid = (candidate blocks, theta slices, tile slices) */
-template <int LSTRIDE, int R, int MODE, bool WEIGHTED>
+template <int LSTRIDE, int R, int MODE>
 __global__ __launch_bounds__(kBlock) void k_score(ScoreJob job, int cbx, int groups, int n_buf)
 {
-    score_body<LSTRIDE, R, MODE, WEIGHTED>(job, cbx, groups, blockIdx.z, gridDim.z, n_buf, blockIdx.y);
-}
-
-/* The arg-max pass after a tile-split launch (job.in_s set): same lane <->
- * candidate mapping and epilogue, no gathering. A kernel of its own so that
- * profiles keep it apart from the gather launches. */
-template <int LSTRIDE, int R>
-__global__ __launch_bounds__(kBlock) void k_argmax(ScoreJob job, int cbx, int groups)
-{
-    score_body<LSTRIDE, R, 0, false>(job, cbx, groups, 0, 1, 1, blockIdx.y);
+    score_body<LSTRIDE, R, MODE>(job, cbx, groups, blockIdx.z, gridDim.z, n_buf, blockIdx.y);
 }
 
 /* grid = (candidate blocks, theta slices or fewer, jobs * n_slices). A workgroup
@@ -788,7 +753,7 @@ __global__ __launch_bounds__(kBlock) void k_argmax(ScoreJob job, int cbx, int gr
  * theta axis for levels that normally exit at once (skip_unless_band) -- 4,160
  * workgroups that each allocate a region of LDS only to read one flag and leave
  * took 47 us per 64-window launch. */
-template <int LSTRIDE, int R, int MODE, bool WEIGHTED>
+template <int LSTRIDE, int R, int MODE>
 __global__ __launch_bounds__(kBlock) void k_score_batch(const ScoreJob* jobs, int cbx, int groups,
                                                        int n_slices, int n_buf)
 {
@@ -796,7 +761,7 @@ __global__ __launch_bounds__(kBlock) void k_score_batch(const ScoreJob* jobs, in
     if (job.skip_unless_band && !(*job.flags & kFlagBandTouch))
         return;
     for (int t = blockIdx.y; t < job.n_theta; t += gridDim.y) {
-        score_body<LSTRIDE, R, MODE, WEIGHTED>(job, cbx, groups, blockIdx.z % n_slices, n_slices, n_buf, t);
+        score_body<LSTRIDE, R, MODE>(job, cbx, groups, blockIdx.z % n_slices, n_slices, n_buf, t);
         __syncthreads();
     }
 }
@@ -1085,7 +1050,7 @@ __device__ __forceinline__ void score_body_pairs(const ScoreJob& job, int cbx, i
     }
     FlushState fs = { 0, 0 };
 
-    const int ntiles = job.in_s ? 0 : job.n_tiles[t];
+    const int ntiles = job.n_tiles[t];
     const TileRec* recs = job.tiles + (size_t)t * job.max_tiles;
     const uint32_t* __restrict__ pbs = job.sorted_pb + (size_t)t * job.n_points;
     /* every job field the tile loop needs, read once: `job` lives in global memory and
@@ -1218,9 +1183,8 @@ __device__ __forceinline__ void score_body_pairs2(const ScoreJob& job, int cbx, 
         S0[r] = K0[r] = acc0[r] = S1[r] = K1[r] = acc1[r] = 0;
     FlushState fs0 = { 0, 0 }, fs1 = { 0, 0 };
 
-    const bool gather = !job.in_s;
-    const int n0 = __builtin_amdgcn_readfirstlane(gather ? job.n_tiles[t0] : 0);
-    const int n1 = __builtin_amdgcn_readfirstlane(gather && two ? job.n_tiles[t1] : 0);
+    const int n0 = __builtin_amdgcn_readfirstlane(job.n_tiles[t0]);
+    const int n1 = __builtin_amdgcn_readfirstlane(two ? job.n_tiles[t1] : 0);
     const TileRec* recs0 = job.tiles + (size_t)t0 * job.max_tiles;
     const TileRec* recs1 = job.tiles + (size_t)t1 * job.max_tiles;
     const uint32_t* __restrict__ pbs0 = job.sorted_pb + (size_t)t0 * job.n_points;
@@ -1385,6 +1349,40 @@ __global__ __launch_bounds__(kBlock, 4) void k_score_pairs2_batch(const ScoreJob
     int bx, by, bz;
     xcd_block(xcd_map, bx, by, bz);
     score_body_pairs2<LS, R, WEIGHTED>(jobs[bz], cbx, groups, lane_map, bx, by, bb);
+}
+
+/* The arg-max pass after a tile-split launch of k_score_pairs (blockIdx.z slices of the tile list
+ * added their partial sums to sum_s / sum_k, [n_theta][ny][nx]): a lane takes the complete sums of
+ * its R candidates -- the fine plan's lane <-> candidate mapping, in thread order -- and stores zero
+ * back, so that the accumulators are clean for the next query (tile_split_slices); then the
+ * workgroup ends like a scoring kernel. grid = (candidate blocks, theta slices), no dynamic LDS. */
+template <int R>
+__global__ __launch_bounds__(kBlock) void k_argmax(ScoreJob job, uint32_t* sum_s, uint32_t* sum_k, int cbx, int groups)
+{
+    const int t = blockIdx.y, tid = threadIdx.x;
+    const int ncbx = (job.nx + cbx - 1) / cbx;
+    const int bx = blockIdx.x % ncbx, by = blockIdx.x / ncbx;
+    const int cby = groups * R;
+    if (t >= job.n_theta || by * cby >= job.ny)
+        return;
+    const uint32_t qflags = (job.skip_unless_band || job.elig_only_if_band) ? *job.flags : 0u;
+    if (job.skip_unless_band && !(qflags & kFlagBandTouch))
+        return;
+    const int dxi = tid % cbx, g = tid / cbx, xi = bx * cbx + dxi;
+    const bool lane_on = g < groups;
+    uint32_t S[R] = {}, K[R] = {};
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int yi = by * cby + g * R + r;
+        if (lane_on && xi < job.nx && yi < job.ny) {
+            const size_t ai = ((size_t)t * job.ny + yi) * job.nx + xi;
+            S[r] = sum_s[ai];
+            K[r] = sum_k[ai];
+            sum_s[ai] = 0;
+            sum_k[ai] = 0;
+        }
+    }
+    score_epilogue<R>(job, S, K, t, bx, by, cbx, cby, g, dxi, lane_on, qflags, (int)blockIdx.x, (int)gridDim.x);
 }
 
 /* ------------------------------------------------------------------ K2 */

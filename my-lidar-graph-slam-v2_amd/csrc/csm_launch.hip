@@ -9,12 +9,11 @@
 namespace csm_launch {
 
 /* The strided kernels (coarser levels): kStridedLS x kStridedR, stride a power of two (MODE 1) or any
- * (MODE 2), always on weighted entries. The stride-1 level is always a pair kernel; round 1's stride-1
- * body survives only as the arg-max pass (k_argmax). */
+ * (MODE 2), always on weighted entries. The stride-1 level is always a pair kernel. */
 int score_strided(const ScoreLaunch& a, const ScoreJob& job)
 {
     return match_strided_shape(a, [&](auto ls, auto r, auto mode) {
-        return launch_lds(a.device, k_score<ls, r, mode, true>, a.grid, dim3(kBlock), a.lds, a.stream, job, a.cbx,
+        return launch_lds(a.device, k_score<ls, r, mode>, a.grid, dim3(kBlock), a.lds, a.stream, job, a.cbx,
                           a.groups, a.n_buf);
     });
 }
@@ -22,7 +21,7 @@ int score_strided(const ScoreLaunch& a, const ScoreJob& job)
 int score_strided_batch(const ScoreLaunch& a, const ScoreJob* jobs)
 {
     return match_strided_shape(a, [&](auto ls, auto r, auto mode) {
-        return launch_lds(a.device, k_score_batch<ls, r, mode, true>, a.grid, dim3(kBlock), a.lds, a.stream, jobs,
+        return launch_lds(a.device, k_score_batch<ls, r, mode>, a.grid, dim3(kBlock), a.lds, a.stream, jobs,
                           a.cbx, a.groups, a.n_slices, a.n_buf);
     });
 }
@@ -63,11 +62,11 @@ int score_pairs_list(const ScoreLaunch& a, const ScoreJob& job)
     });
 }
 
-/* only the lane <-> candidate mapping (cbx, groups, R) matters to the arg-max pass: k_argmax<128, R> */
-int argmax(const ScoreLaunch& a, const ScoreJob& job)
+/* the arg-max pass over the sums of a tile-split launch: the fine plan's lane <-> candidate mapping (cbx, groups, R) */
+int argmax(const ScoreLaunch& a, const ScoreJob& job, uint32_t* sum_s, uint32_t* sum_k)
 {
     return match<kPairR>(a.R, [&](auto r) {
-        return launch(k_argmax<128, r>, a.grid, dim3(kBlock), a.stream, job, a.cbx, a.groups);
+        return launch(k_argmax<r>, a.grid, dim3(kBlock), a.stream, job, sum_s, sum_k, a.cbx, a.groups);
     });
 }
 

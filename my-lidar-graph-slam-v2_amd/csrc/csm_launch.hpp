@@ -155,12 +155,12 @@ int launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t s, const A&.
 
 /* the scoring kernels; grid.y counts theta slices: the kernels that take two per workgroup
  * (pair batch with lists == 2, joint batch) are launched over ceil(grid.y / 2) */
-int score_strided(const ScoreLaunch& a, const ScoreJob& job);             /* k_score<LS, R, MODE, W> */
+int score_strided(const ScoreLaunch& a, const ScoreJob& job);             /* k_score<LS, R, MODE> */
 int score_strided_batch(const ScoreLaunch& a, const ScoreJob* jobs);      /* k_score_batch */
 int score_pairs(const ScoreLaunch& a, const ScoreJob& job);               /* k_score_pairs */
 int score_pairs_batch(const ScoreLaunch& a, const ScoreJob* jobs);        /* k_score_pairs_batch / pairs2_batch */
 int score_pairs_list(const ScoreLaunch& a, const ScoreJob& job);          /* k_score_pairs_list */
-int argmax(const ScoreLaunch& a, const ScoreJob& job);                    /* k_argmax<128, R> */
+int argmax(const ScoreLaunch& a, const ScoreJob& job, uint32_t* sum_s, uint32_t* sum_k);    /* k_argmax<R> */
 
 /* the other kernels: grid / block / dynamic LDS as the caller decides; those that take `device` and
  * `lds` raise the kernel's dynamic-LDS limit first (grant_lds) */

@@ -136,7 +136,8 @@ int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out);
 int launch_score(csm_ctx* ctx, const ScoreJob& job, const PassPlan& pp, int n_theta, int n_slices);
 int launch_score_list(csm_ctx* ctx, const ScoreJob& job, const PassPlan& pp, const uint32_t* items,
                       const uint32_t* count, int blocks);
-int launch_argmax(csm_ctx* ctx, const ScoreJob& job, const PassPlan& plan, int n_theta);
+int launch_argmax(csm_ctx* ctx, const ScoreJob& job, const PassPlan& plan, int n_theta, uint32_t* sum_s,
+                  uint32_t* sum_k);
 bool tail_split(const csm_ctx* ctx, const PassPlan& pp);
 int launch_pairs_batch(csm_ctx* ctx, const ScoreJob* jobs_dev, const PassPlan& pp, dim3 grid, BlockBase bb,
                        const JointList* list = nullptr, int which = 0);

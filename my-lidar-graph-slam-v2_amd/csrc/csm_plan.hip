@@ -722,12 +722,12 @@ int launch_score_list(csm_ctx* ctx, const ScoreJob& job, const PassPlan& pp, con
     return launched_ok(ctx, csm_launch::score_pairs_list(a, job), "pair-row list");
 }
 
-int launch_argmax(csm_ctx* ctx, const ScoreJob& job, const PassPlan& plan, int n_theta)
+/* the arg-max pass of `job` over the complete sums of a tile-split launch (it clears them as it reads) */
+int launch_argmax(csm_ctx* ctx, const ScoreJob& job, const PassPlan& plan, int n_theta, uint32_t* sum_s,
+                  uint32_t* sum_k)
 {
-    /* only the lane <-> candidate mapping (cbx, groups, R) matters to this pass:
-     * a pair plan borrows the R = 8 instantiation of the plain kernel */
     const csm_launch::ScoreLaunch a = score_launch(ctx, plan, dim3(plan.ncb(), n_theta, 1), 0);
-    return launched_ok(ctx, csm_launch::argmax(a, job), "arg-max");     /* k_argmax<128, 6 | 8> exist */
+    return launched_ok(ctx, csm_launch::argmax(a, job, sum_s, sum_k), "arg-max");
 }
 
 /* a window's last row block as an R = 6 launch of its own? (launch_score_batch) */

@@ -82,21 +82,6 @@ __device__ __forceinline__ void score_epilogue(const ScoreJob& job, uint32_t (&S
     __shared__ uint32_t red_cnt[kBlock / 64];
     const int tid = threadIdx.x;
     const int xi = bx * cbx + dxi;
-    if (job.in_s && lane_on && xi < job.nx) {
-        /* arg-max pass of a tile-split launch: the slices' sums are complete */
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int yi = by * cby + g * R + r;
-            if (yi < job.ny) {
-                const size_t ai = ((size_t)t * job.ny + yi) * job.nx + xi;
-                S[r] = job.in_s[ai];
-                K[r] = job.in_k[ai];
-                /* leave the accumulators clean for the next query */
-                job.in_s[ai] = 0;
-                job.in_k[ai] = 0;
-            }
-        }
-    }
     unsigned long long bkey = 0, brank = ~0ull;
     uint32_t bcnt = 0;
     bool bound_broken = false;

@@ -46,14 +46,15 @@ int tile_split_slices(csm_ctx* ctx, const Plan& p, int* fine_slices)
     if (*fine_slices <= 1)
         return CSM_OK;
     /* the accumulators are zero between queries: cleared once when
-     * (re)allocated, then by the arg-max pass as it reads them */
+     * (re)allocated, then by the arg-max pass as it reads them. A buffer that grew is told by its
+     * capacity: the allocator may hand the freed address out again, with other contents behind it */
     const size_t words = (size_t)p.n_theta * p.nx * p.ny;
-    const void *old_s = ctx->fine_s.p, *old_k = ctx->fine_k.p;
+    const size_t old_s = ctx->fine_s.cap, old_k = ctx->fine_k.cap;
     if ((rc = ensure(ctx, ctx->fine_s, words * 4))) return rc;
     if ((rc = ensure(ctx, ctx->fine_k, words * 4))) return rc;
-    if (ctx->fine_s.p != old_s || ctx->fine_acc_dirty)
+    if (ctx->fine_s.cap != old_s || ctx->fine_acc_dirty)
         HIP_TRY(ctx, hipMemsetAsync(ctx->fine_s.p, 0, ctx->fine_s.cap, ctx->stream));
-    if (ctx->fine_k.p != old_k || ctx->fine_acc_dirty)
+    if (ctx->fine_k.cap != old_k || ctx->fine_acc_dirty)
         HIP_TRY(ctx, hipMemsetAsync(ctx->fine_k.p, 0, ctx->fine_k.cap, ctx->stream));
     ctx->fine_acc_dirty = false;
     return CSM_OK;
@@ -221,11 +222,8 @@ struct WindowRun {
             if ((rc = launch_score(ctx, sj, p.fine, p.n_theta, fine_slices)))
                 return rc;
         }
-        ScoreJob aj = fj;
-        aj.in_s = sj.acc_s;
-        aj.in_k = sj.acc_k;
         ScopedTimer tm(ctx, "argmax");
-        if ((rc = launch_argmax(ctx, aj, p.fine, p.n_theta)))
+        if ((rc = launch_argmax(ctx, fj, p.fine, p.n_theta, sj.acc_s, sj.acc_k)))
             return rc;
         ctx->fine_acc_dirty = false;
         return CSM_OK;
