@@ -495,6 +495,94 @@ int  csm_host_volume_covariance(const csm_volume_moments* moments, const double 
                                 const double estimated_pose[3], const double rel_pose[3],
                                 double mean_offset[3], double sensor_cov[9], double cov[9]);
 
+/* ---- motion prior on the search window (beyond the reference, which keeps the first strict maximum in
+ * sweep order: on a score plateau -- a corridor's ridge, an all-ties map -- that is the candidate nearest
+ * the (-win_x, -win_y, -win_theta) corner, the pose farthest from the odometry guess the window was
+ * centred on). The scan likelihood is weighed against a Gaussian prior on the offset from the initial
+ * pose, as in Olson's correlative matcher.
+ *
+ * Candidates, key, eligibility and the extended domain are exactly those of csm_score_window_peaks. Every
+ * candidate is scored exactly (no bound pass, no coarse-first search).
+ *
+ * Offsets. d = (x, y, t): the candidate's offset from the window centre (the sensor pose of the initial
+ * guess) in search steps, the triple a csm_result carries in best_x / best_y / best_theta; theta is not
+ * wrapped.
+ * Prior. A symmetric 3 x 3 information matrix Lambda (row-major, index order (x, y, theta)) over the metric
+ * sensor-pose offset delta = (x step_x, y step_y, t step_theta).
+ * Penalised score. score - 1/2 delta^T Lambda delta, in score units. With c = 0.998 / (65534 * 499) and
+ * N = n_points one score unit is N / c key units (the constant of the volume covariance above).
+ * Quantisation (csm_host_motion_prior; host, f64, one fixed expression), for the six pairs in the order
+ * xx xy xt yy yt tt:
+ *   q_ab = ((((N / c) * m_ab) * Lambda_ab) * step_a) * step_b,   m_ab = 0.5 on the diagonal, 1.0 off it
+ *   Q_ab = (int64) floor(q_ab * 256 + 0.5)
+ * Penalty. pen(d) = max(0, (sum_{a<=b} Q_ab d_a d_b) >> 8): int64 arithmetic, arithmetic shift.
+ * pk(d) = (int64) key - pen(d), which may be negative. Integer sums are associative, so the device equals
+ * the definition whatever the order.
+ * Winner. The eligible candidate with the greatest pk; among equal pk the greatest key; among those the
+ * greatest f64 beam-order score (replayed over the candidates still tied, as for the peaks); among those
+ * the first in the reference's sweep order. tie_count = eligible candidates sharing the winner's
+ * (pk, key); CSM_FLAG_KEY_TIE / CSM_FLAG_F64_TIE as in the peaks. found = (the winner's f64 score >
+ * score_threshold): the raw score is tested, not the penalised one. If nothing is eligible or the winner
+ * fails the threshold, `best`, `penalty` and `penalised_key` are zeros. An edge-band window follows the
+ * closed form and both records carry CSM_FLAG_EDGE_BAND, as the peaks do.
+ * Result. `unweighted` is the record csm_score_window_peaks(k_max = 1) gives; both winners come out of the
+ * same pass over the volume, so a caller sees how far the prior moved the answer. Lambda = 0 gives
+ * best == unweighted and penalty == 0. Q is always filled.
+ *
+ * CSM_EINVAL, all checked before anything is allocated: a non-finite Lambda entry; an asymmetric Lambda
+ * (Lambda_ab != Lambda_ba as doubles); a |q_ab * 256| that does not fit int64 (>= 2^63); 6 max|Q_ab|
+ * d_max^2 >= 2^62 with d_max = max(n_theta, nx, ny) - 1; a negative scratch limit; and the peaks' own
+ * refusals. A Lambda that is not positive semi-definite is allowed: the max(0, .) clamp defines the result.
+ * Not provided: peaks or volume moments under a prior, branch-and-bound and grid-search, the csm_group_*
+ * entries, a prior mean other than the window centre. */
+typedef struct {
+    double  information[9];              /* Lambda of the sensor pose, row-major (x, y, theta) */
+    double  steps[3];                    /* (step_x, step_y, step_theta) of a raw window; the match entries
+                                            take the steps of their search set-up and ignore these */
+    int64_t scratch_limit_bytes;         /* as csm_peaks_params.scratch_limit_bytes; a batch is cut by
+                                            priors[0]'s */
+} csm_motion_prior;
+
+typedef struct {
+    csm_result best;                     /* the winner under the prior */
+    csm_result unweighted;               /* peak 0 of csm_score_window_peaks */
+    int64_t    penalty, penalised_key;   /* pen(d) and pk(d) of `best` */
+    int64_t    Q[6];                     /* xx xy xt yy yt tt */
+} csm_prior_result;
+
+typedef struct {
+    csm_summary      summary;            /* as csm_correlative_match fills it, from `best` */
+    csm_prior_result prior;
+} csm_prior_summary;
+
+/* Host only: the quantisation and its refusals. steps = (step_x, step_y, step_theta), d_max = max(n_theta,
+ * nx, ny) - 1 of the window (>= 0). */
+int  csm_host_motion_prior(const double information[9], const double steps[3], int32_t n_points,
+                           int32_t d_max, int64_t Q[6]);
+/* Host only: the information of the sensor pose from that of the robot pose, out = J^T Lambda_robot J with
+ * J = d MoveBackward(sensor pose, rel_pose) / d sensor pose at the initial pose: the identity plus
+ * J[0][2] = sin(th) rx + cos(th) ry, J[1][2] = -cos(th) rx + sin(th) ry (th = initial_pose[2], libm sin /
+ * cos), as for the volume covariance. T = J^T Lambda with T_ij = (J_0i L_0j + J_1i L_1j) + J_2i L_2j, then
+ * out_ij = (T_i0 J_0j + T_i1 J_1j) + T_i2 J_2j for i <= j, every product taken (also those by 0 and 1);
+ * out_ji = out_ij, so the result is symmetric as csm_host_motion_prior demands. rel_pose = 0 gives
+ * out == robot_information for a symmetric input. */
+int  csm_host_prior_from_robot_information(const double robot_information[9], const double initial_pose[3],
+                                           const double rel_pose[3], double out[9]);
+/* hit_col / hit_row as csm_score_window takes them. */
+int  csm_score_window_prior(csm_ctx* ctx, uint64_t map_id, const csm_window* w,
+                            const int32_t* hit_col, const int32_t* hit_row,
+                            const csm_motion_prior* prior, csm_prior_result* out);
+/* csm_correlative_match's set-up. */
+int  csm_correlative_match_prior(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geom,
+                                 const csm_scan* scan, const double initial_pose[3],
+                                 const csm_correlative_params* params, const csm_motion_prior* prior,
+                                 csm_prior_summary* out);
+/* csm_correlative_match_batch's queries; priors[n_queries], out[n_queries]. All windows of a chunk share
+ * each launch. */
+int  csm_correlative_match_prior_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
+                                       const csm_correlative_params* params, const csm_motion_prior* priors,
+                                       csm_prior_summary* out);
+
 /* The raw records (csm_summary.raw) of the last csm_bnb_match_batch /
  * csm_correlative_match_batch call on this ctx, in query order, copied device
  * to device into dst_dev[n_queries] on the ctx stream (asynchronous): the
@@ -932,7 +1020,7 @@ int  csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_er
 int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
 /* Drains recorded events; returns total ms and launch count since the last
  * reset for kernel "score_fine" | "score_coarse" | "bin" | "finalize" | "boxmax" |
- * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce". */
+ * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);
 int  csm_reset_kernel_timing(csm_ctx* ctx);

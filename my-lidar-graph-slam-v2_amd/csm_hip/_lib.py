@@ -221,6 +221,19 @@ class VolumeSummary(C.Structure):
                 ("sensor_covariance", C.c_double * 9), ("covariance", C.c_double * 9)]
 
 
+class MotionPrior(C.Structure):
+    _fields_ = [("information", C.c_double * 9), ("steps", C.c_double * 3), ("scratch_limit_bytes", C.c_int64)]
+
+
+class PriorResult(C.Structure):
+    _fields_ = [("best", Result), ("unweighted", Result), ("penalty", C.c_int64), ("penalised_key", C.c_int64),
+                ("Q", C.c_int64 * 6)]
+
+
+class PriorSummary(C.Structure):
+    _fields_ = [("summary", Summary), ("prior", PriorResult)]
+
+
 # name -> (restype, argtypes); mirrors include/csm_hip.h one to one
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -284,6 +297,14 @@ SIGNATURES = {
     "csm_host_volume_weights": (C.c_int, [C.c_int32, C.c_double, C.c_void_p, _P(C.c_int32)]),
     "csm_host_volume_covariance": (C.c_int, [_P(VolumeMoments), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    "csm_host_motion_prior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "csm_host_prior_from_robot_information": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "csm_score_window_prior": (C.c_int, [_ctx, C.c_uint64, _P(Window), C.c_void_p, C.c_void_p, _P(MotionPrior),
+                                         _P(PriorResult)]),
+    "csm_correlative_match_prior": (C.c_int, [_ctx, C.c_uint64, _P(Geometry), _P(Scan), C.c_void_p,
+                                              _P(CorrelativeParams), _P(MotionPrior), _P(PriorSummary)]),
+    "csm_correlative_match_prior_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(CorrelativeParams),
+                                                    _P(MotionPrior), _P(PriorSummary)]),
     "csm_bnb_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,
                                       _P(BnbParams), _P(Summary)]),
     "csm_correlative_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,

@@ -254,6 +254,53 @@ def volume_summary_to_dict(v):
                 covariance=list(v.covariance))
 
 
+def host_motion_prior(information, steps, n_points, d_max):
+    """Q[6] (Python ints, order xx xy xt yy yt tt): the quantised prior terms of a 3 x 3 information matrix
+    (csm_host_motion_prior). d_max = max(n_theta, nx, ny) - 1 of the window."""
+    lam, st = _f64(information).reshape(-1), _f64(steps)
+    if lam.size != 9 or st.size != 3:
+        raise CsmError(L.CSM_EINVAL, "host_motion_prior: information must be 3 x 3, steps 3")
+    q = np.zeros(6, np.int64)
+    rc = L.load().csm_host_motion_prior(_ptr(lam), _ptr(st), n_points, d_max, _ptr(q))
+    if rc != 0:
+        raise CsmError(rc, "csm_host_motion_prior")
+    return [int(v) for v in q]
+
+
+def host_prior_from_robot_information(robot_information, initial_pose, rel_pose):
+    """The 9 doubles of J^T Lambda_robot J: the information of the sensor pose from that of the robot pose
+    (csm_host_prior_from_robot_information)."""
+    lam, init, rel = _f64(robot_information).reshape(-1), _f64(initial_pose), _f64(rel_pose)
+    if lam.size != 9:
+        raise CsmError(L.CSM_EINVAL, "host_prior_from_robot_information: information must be 3 x 3")
+    out = np.zeros(9)
+    rc = L.load().csm_host_prior_from_robot_information(_ptr(lam), _ptr(init), _ptr(rel), _ptr(out))
+    if rc != 0:
+        raise CsmError(rc, "csm_host_prior_from_robot_information")
+    return out.tolist()
+
+
+def motion_prior(information, steps=(0.0, 0.0, 0.0), scratch_limit_bytes=0):
+    """csm_motion_prior from a 3 x 3 (or flat, row-major) information matrix."""
+    lam = _f64(information).reshape(-1)
+    if lam.size != 9:
+        raise CsmError(L.CSM_EINVAL, "motion_prior: information must be 3 x 3")
+    p = L.MotionPrior()
+    p.information[:] = lam.tolist()
+    p.steps[:] = list(steps)
+    p.scratch_limit_bytes = scratch_limit_bytes
+    return p
+
+
+def prior_result_to_dict(r):
+    return dict(best=result_to_dict(r.best), unweighted=result_to_dict(r.unweighted), penalty=int(r.penalty),
+                penalised_key=int(r.penalised_key), Q=[int(v) for v in r.Q])
+
+
+def prior_summary_to_dict(v):
+    return dict(summary=summary_to_dict(v.summary), prior=prior_result_to_dict(v.prior))
+
+
 def host_probability_lut():
     lut = np.zeros(65536)
     L.load().csm_host_probability_lut(_ptr(lut))
@@ -638,6 +685,60 @@ class Context:
             return out
         return [volume_summary_to_dict(out[i]) for i in range(prep.n)]
 
+    def score_window_prior(self, map_id, window, hit_col, hit_row, information, steps, scratch_limit_bytes=0):
+        """The winner of one pre-projected window under a motion prior, next to the unweighted one
+        (csm_score_window_prior), as a dict."""
+        col = np.ascontiguousarray(hit_col, dtype=np.int32)
+        row = np.ascontiguousarray(hit_row, dtype=np.int32)
+        pr = motion_prior(information, steps, scratch_limit_bytes)
+        out = L.PriorResult()
+        self._check(self.lib.csm_score_window_prior(self._ctx, map_id, C.byref(window), _ptr(col), _ptr(row),
+                                                    C.byref(pr), C.byref(out)))
+        return prior_result_to_dict(out)
+
+    def correlative_match_prior(self, map_id, geom, angles, ranges, rel_pose, init_pose, range_x, range_y,
+                                range_theta, low_resolution, information, score_threshold=0.0,
+                                known_rate_threshold=0.0, scratch_limit_bytes=0):
+        """correlative_match() under a motion prior on the offset from the initial pose
+        (csm_correlative_match_prior): a dict of summary (from the winner under the prior) and prior."""
+        a, r = _f64(angles), _f64(ranges)
+        scan = L.Scan()
+        scan.angles = a.ctypes.data_as(C.POINTER(C.c_double))
+        scan.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
+        scan.n_points = a.size
+        scan.relative_sensor_pose[:] = list(rel_pose)
+        g = L.Geometry(*geom)
+        p = L.CorrelativeParams()
+        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
+        p.low_resolution = low_resolution
+        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        init = _f64(init_pose)
+        pr = motion_prior(information, scratch_limit_bytes=scratch_limit_bytes)
+        out = L.PriorSummary()
+        self._check(self.lib.csm_correlative_match_prior(self._ctx, map_id, C.byref(g), C.byref(scan), _ptr(init),
+                                                         C.byref(p), C.byref(pr), C.byref(out)))
+        return prior_summary_to_dict(out)
+
+    def correlative_match_prior_batch(self, queries, range_x, range_y, range_theta, low_resolution, informations,
+                                      score_threshold=0.0, known_rate_threshold=0.0, scratch_limit_bytes=0,
+                                      as_records=False):
+        """correlative_match_batch() under one motion prior per query (csm_correlative_match_prior_batch):
+        one dict per query. informations: one 3 x 3 matrix per query. as_records: the C array instead."""
+        prep = self.prepare_queries(queries)
+        if len(informations) != prep.n:
+            raise CsmError(L.CSM_EINVAL, "correlative_match_prior_batch: one information matrix per query")
+        p = L.CorrelativeParams()
+        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
+        p.low_resolution = low_resolution
+        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        priors = (L.MotionPrior * prep.n)(*[motion_prior(lam, scratch_limit_bytes=scratch_limit_bytes)
+                                            for lam in informations])
+        out = (L.PriorSummary * prep.n)()
+        self._check(self.lib.csm_correlative_match_prior_batch(self._ctx, prep.arr, prep.n, C.byref(p), priors, out))
+        if as_records:
+            return out
+        return [prior_summary_to_dict(out[i]) for i in range(prep.n)]
+
     def construct_map_from_scans(self, map_id, shape, map_pose, nodes, usable_range_min=0.01,
                                  usable_range_max=20.0, prob_hit=0.62, prob_miss=0.46,
                                  subpixel_scale=100):
@@ -934,11 +1035,14 @@ class ScanMatcherCorrelativeHIP:
     """Drop-in for ScanMatcherCorrelative (constructor arguments as in
     src/my_lidar_graph_slam/scan_matcher_factory.cpp:173-177)."""
 
-    def __init__(self, name, low_resolution, range_x, range_y, range_theta, ctx=None):
+    def __init__(self, name, low_resolution, range_x, range_y, range_theta, ctx=None, prior_information=None):
+        """prior_information: a 3 x 3 information matrix of the sensor pose's offset from the initial pose
+        (beyond the reference); optimize_pose then goes through csm_correlative_match_prior."""
         self.name = name
         self.low_resolution = low_resolution
         self.range_x, self.range_y, self.range_theta = range_x, range_y, range_theta
         self.ctx = ctx or Context()
+        self.prior_information = prior_information
         self._nonce = 1 << 62
 
     def optimize_pose(self, grid, geom, angles, ranges, rel_pose, init_pose,
@@ -951,10 +1055,18 @@ class ScanMatcherCorrelativeHIP:
             mid = self._nonce
         if grid is not None and (map_id is None or not self.ctx.has_grid(mid)):
             self.ctx.upload_grid(mid, grid)
-        out = self.ctx.correlative_match(mid, geom, angles, ranges, rel_pose, init_pose,
-                                         self.range_x, self.range_y, self.range_theta,
-                                         self.low_resolution, score_threshold,
-                                         known_rate_threshold)
+        if self.prior_information is not None:
+            # the summary of the winner under the prior, with the unweighted winner and the penalty beside it
+            both = self.ctx.correlative_match_prior(mid, geom, angles, ranges, rel_pose, init_pose,
+                                                    self.range_x, self.range_y, self.range_theta,
+                                                    self.low_resolution, self.prior_information,
+                                                    score_threshold, known_rate_threshold)
+            out = dict(both["summary"], unweighted=both["prior"]["unweighted"], prior=both["prior"])
+        else:
+            out = self.ctx.correlative_match(mid, geom, angles, ranges, rel_pose, init_pose,
+                                             self.range_x, self.range_y, self.range_theta,
+                                             self.low_resolution, score_threshold,
+                                             known_rate_threshold)
         if map_id is None:
             self.ctx.release_grid(mid)
         return out

@@ -230,6 +230,10 @@ struct csm_ctx {
      * workgroup records + results; pinned staging */
     DevBuf vc_tab;
     PinBuf vc_pin;
+    /* motion prior (csm_prior_api.hip) on top of the peaks' owners: job table, workgroup records +
+     * results; pinned staging */
+    DevBuf pr_tab;
+    PinBuf pr_pin;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */

@@ -1,6 +1,6 @@
 /* csm_peaks.hpp -- what the units that read a window's whole score volume share: the peaks entries
- * (csm_peaks_api.hip, which defines everything declared here) and the volume covariance
- * (csm_volume_api.hip). The device-side job record of one window, and the host stages of a chunk:
+ * (csm_peaks_api.hip, which defines everything declared here), the volume covariance
+ * (csm_volume_api.hip) and the motion prior (csm_prior_api.hip). The device-side job record of one window, and the host stages of a chunk:
  * sizing, projection on the device, exact scores + coarse known counts + selection rounds. */
 #ifndef CSM_PEAKS_HPP
 #define CSM_PEAKS_HPP
@@ -34,6 +34,42 @@ struct PeakJob {
     double score_thr;
 };
 
+/* What the selection kernels of the units on these stages share (csm_peaks_kernels.hip,
+ * csm_prior_kernels.hip): the f64 replay of a tie set. */
+
+/* The reference's normalized score of candidate offsets (x, y) in slice t: the probabilities of the hit
+ * cells added in beam order, one rounding per add (the 0.0 of an unknown cell adds exactly). */
+__device__ __forceinline__ double replay_score(const PeakJob& job, int t, int x, int y)
+{
+    const int32_t* col = job.hit_col + (size_t)t * job.n_points;
+    const int32_t* row = job.hit_row + (size_t)t * job.n_points;
+    double sum = 0.0;
+    for (int i = 0; i < job.n_points; ++i) {
+        const int r = row[i] + y, c = col[i] + x;
+        uint32_t v = 0;
+        if (r >= 0 && r < job.rows && c >= 0 && c < job.cols)
+            v = job.cells[(size_t)r * job.pitch + c];
+        sum += job.lut[v];
+    }
+    return sum / (double)job.n_points;
+}
+
+/* (score, rank, number of candidates sharing the score): greater score first, then the smaller rank */
+__device__ __forceinline__ void tie_combine(double& s, unsigned long long& r, uint32_t& same, double s2,
+                                            unsigned long long r2, uint32_t same2)
+{
+    if (same2 == 0)
+        return;
+    if (same == 0 || s2 > s) {
+        s = s2;
+        r = r2;
+        same = same2;
+    } else if (s2 == s) {
+        r = r2 < r ? r2 : r;
+        same += same2;
+    }
+}
+
 } /* namespace csm */
 
 namespace csm_host {
@@ -64,6 +100,7 @@ struct PeakChunk {
     const csm_result* rec_dev = nullptr;       /* [m][k_max], followed by the states [m][2] */
     size_t back_bytes = 0;                     /* records + states */
     char* back_pin = nullptr;                  /* room for them in pk_pin */
+    int n_points_max = 0;                      /* the chunk's longest scan */
 };
 
 /* The window's candidate domain and scratch need against `scratch_limit` (0: the default); nothing is
@@ -79,8 +116,12 @@ int peaks_next_chunk(const std::vector<PeakWindow>& wins, int lo, int64_t scratc
  * cannot certify: on the host); sets hit_off. Waits for the stream. */
 int peaks_project_chunk(csm_ctx* ctx, const csm_loop_query* queries, std::vector<PeakWindow>& wins,
                         const std::vector<csm_summary>& head, int lo, int hi);
-/* Windows [lo, hi) with their hit indices in pk_hits: exact scores of every candidate, coarse known
- * counts, pk->k_max selection rounds. Everything is queued on the stream; nothing is copied back and the
+/* Windows [lo, hi) with their hit indices in pk_hits: the job table (room for pk->k_max records per
+ * window, zeroed), exact scores of every candidate, coarse known counts. Everything is queued on the
+ * stream. */
+int peaks_score_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
+                      PeakChunk* out);
+/* peaks_score_chunk, then pk->k_max selection rounds. Everything is queued on the stream; nothing is copied back and the
  * host does not wait for the selection. */
 int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
                        PeakChunk* out);

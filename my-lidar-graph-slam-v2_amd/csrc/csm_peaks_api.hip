@@ -51,8 +51,8 @@ int peaks_size_window(csm_ctx* ctx, PeakWindow& pw, int64_t scratch_limit, int i
     return CSM_OK;
 }
 
-int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
-                       PeakChunk* out)
+int peaks_score_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
+                      PeakChunk* out)
 {
     const int m = hi - lo, k_max = pk->k_max;
     int rc;
@@ -152,26 +152,38 @@ int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int 
                                                       (const PeakJob*)jobs_dev), "coarse known count")))
             return rc;
     }
-    int blocks_max = 1;
-    for (int k = 0; k < m; ++k)
-        blocks_max = std::max(blocks_max, jobs_pin[k].blocks);
-    {
-        ScopedTimer tm(ctx, "peaks_select");
-        for (int round = 0; round < k_max; ++round) {
-            if ((rc = launched_ok(ctx, csm_launch::launch(k_peaks_argmax, dim3(blocks_max, m), dim3(kPeakBlock), ctx->stream,
-                                                          (const PeakJob*)jobs_dev, round), "peak arg-max")))
-                return rc;
-            if ((rc = launched_ok(ctx, csm_launch::launch_lds(ctx->device, k_peaks_pick, dim3(m), dim3(kPeakBlock),
-                                                              (size_t)n_points_max * 8, ctx->stream,
-                                                              (const PeakJob*)jobs_dev, round), "peak pick")))
-                return rc;
-        }
-    }
     out->jobs_dev = jobs_dev;
     out->jobs_pin = jobs_pin;
     out->rec_dev = rec_dev;
     out->back_bytes = back_bytes;
     out->back_pin = back_pin;
+    out->n_points_max = n_points_max;
+    return CSM_OK;
+}
+
+int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
+                       PeakChunk* out)
+{
+    const int m = hi - lo, k_max = pk->k_max;
+    int rc;
+    if ((rc = peaks_score_chunk(ctx, wins, lo, hi, pk, out))) return rc;
+    const PeakJob* const jobs_dev = out->jobs_dev;
+    const int n_points_max = out->n_points_max;
+    int blocks_max = 1;
+    for (int k = 0; k < m; ++k)
+        blocks_max = std::max(blocks_max, out->jobs_pin[k].blocks);
+    {
+        ScopedTimer tm(ctx, "peaks_select");
+        for (int round = 0; round < k_max; ++round) {
+            if ((rc = launched_ok(ctx, csm_launch::launch(k_peaks_argmax, dim3(blocks_max, m), dim3(kPeakBlock), ctx->stream,
+                                                          jobs_dev, round), "peak arg-max")))
+                return rc;
+            if ((rc = launched_ok(ctx, csm_launch::launch_lds(ctx->device, k_peaks_pick, dim3(m), dim3(kPeakBlock),
+                                                              (size_t)n_points_max * 8, ctx->stream,
+                                                              jobs_dev, round), "peak pick")))
+                return rc;
+        }
+    }
     return CSM_OK;
 }
 

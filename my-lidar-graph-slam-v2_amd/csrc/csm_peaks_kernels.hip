@@ -132,39 +132,6 @@ __global__ __launch_bounds__(kPeakBlock) void k_peaks_argmax(const PeakJob* jobs
     }
 }
 
-/* The reference's normalized score of candidate offsets (x, y) in slice t: the probabilities of the hit
- * cells added in beam order, one rounding per add (the 0.0 of an unknown cell adds exactly). */
-__device__ __forceinline__ double replay_score(const PeakJob& job, int t, int x, int y)
-{
-    const int32_t* col = job.hit_col + (size_t)t * job.n_points;
-    const int32_t* row = job.hit_row + (size_t)t * job.n_points;
-    double sum = 0.0;
-    for (int i = 0; i < job.n_points; ++i) {
-        const int r = row[i] + y, c = col[i] + x;
-        uint32_t v = 0;
-        if (r >= 0 && r < job.rows && c >= 0 && c < job.cols)
-            v = job.cells[(size_t)r * job.pitch + c];
-        sum += job.lut[v];
-    }
-    return sum / (double)job.n_points;
-}
-
-/* (score, rank, number of candidates sharing the score): greater score first, then the smaller rank */
-__device__ __forceinline__ void tie_combine(double& s, unsigned long long& r, uint32_t& same, double s2,
-                                            unsigned long long r2, uint32_t same2)
-{
-    if (same2 == 0)
-        return;
-    if (same == 0 || s2 > s) {
-        s = s2;
-        r = r2;
-        same = same2;
-    } else if (s2 == s) {
-        r = r2 < r ? r2 : r;
-        same += same2;
-    }
-}
-
 __global__ __launch_bounds__(kPeakBlock) void k_peaks_pick(const PeakJob* jobs, int round)
 {
     __shared__ PeakSet ps;

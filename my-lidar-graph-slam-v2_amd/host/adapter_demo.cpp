@@ -202,9 +202,22 @@ int main(int argc, char** argv)
             return 3;
         }
         ScanMatchingQuery q { g, s, { init[0], init[1], init[2] } };
+        /* CSM_DEMO_PRIOR="xx,yy,tt": a diagonal motion prior on the offset from the initial pose */
+        if (const char* e = std::getenv("CSM_DEMO_PRIOR")) {
+            double information[9] = { 0 };
+            if (std::sscanf(e, "%lf,%lf,%lf", &information[0], &information[4], &information[8]) != 3)
+                return 2;
+            m->UseMotionPrior(information);
+        }
         const ScanMatchingSummary r = (prm[6] == 0.0 && prm[7] == 0.0)
                                           ? m->OptimizePose(q)
                                           : m->OptimizePose(q, prm[6], prm[7]);
+        if (std::getenv("CSM_DEMO_PRIOR")) {
+            const csm_prior_result& p = m->LastPriorResult();
+            std::fprintf(stderr, "prior: winner (%d, %d, %d) paid %lld key units; unweighted (%d, %d, %d)\n",
+                         p.best.best_x, p.best.best_y, p.best.best_theta, (long long)p.penalty,
+                         p.unweighted.best_x, p.unweighted.best_y, p.unweighted.best_theta);
+        }
         int metricIds = 0;
         ReportScanMatcherMetrics(m->Name(), r, s.mNumOfScans, [&](const std::string& id, double) {
             metricIds += id.rfind("demo.", 0) == 0;

@@ -265,7 +265,15 @@ public:
         const double init[3] = { q.mMapLocalInitialPose.mX, q.mMapLocalInitialPose.mY,
                                  q.mMapLocalInitialPose.mTheta };
         csm_summary s {};
-        CSM_ASSERT_OK(ctx, csm_correlative_match(ctx, id, &geom, &scan, init, &prm, &s));
+        if (this->mUsePrior) {
+            /* the winner under the motion prior; the unweighted one stays in LastPriorResult() */
+            csm_prior_summary v {};
+            CSM_ASSERT_OK(ctx, csm_correlative_match_prior(ctx, id, &geom, &scan, init, &prm, &this->mPrior, &v));
+            s = v.summary;
+            this->mLastPrior = v.prior;
+        } else {
+            CSM_ASSERT_OK(ctx, csm_correlative_match(ctx, id, &geom, &scan, init, &prm, &s));
+        }
         ScanMatchingSummary out;
         detail::FillSummary(s, q.mMapLocalInitialPose, &out);
         if (this->mCostFunc) {
@@ -363,6 +371,21 @@ public:
         this->mUseDeviceGreedy = true;
         this->mDeviceCovarianceScale = 0.0;
     }
+    /* OptimizePose under a motion prior (csm_correlative_match_prior; beyond the reference): information =
+     * the symmetric 3 x 3 information matrix, row-major (x, y, theta), of the sensor pose's offset from the
+     * initial guess, in score units per m^2 / m rad / rad^2 (csm_host_prior_from_robot_information turns
+     * one of the robot pose into it). nullptr switches the prior off. */
+    void UseMotionPrior(const double information[9])
+    {
+        this->mUsePrior = information != nullptr;
+        this->mPrior = csm_motion_prior {};
+        this->mLastPrior = csm_prior_result {};
+        for (int c = 0; information && c < 9; ++c)
+            this->mPrior.information[c] = information[c];
+    }
+    /* Both winners of the last OptimizePose under a prior: `unweighted` is what OptimizePose returns
+     * without one, `penalty` what the prior charged the winner (key units). */
+    const csm_prior_result& LastPriorResult() const { return this->mLastPrior; }
 
 private:
     ScanMatcherCorrelativeHIP(const std::string& name, int lowResolution, double rangeX,
@@ -413,6 +436,9 @@ private:
     double mDeviceCovarianceScale = 0.0;
     bool mUseDeviceGreedy = false;
     csm_greedy_params mGreedy {};
+    bool mUsePrior = false;
+    csm_motion_prior mPrior {};
+    csm_prior_result mLastPrior {};
 };
 
 /* ScanMatcherGridSearch (inc/mapping/scan_matcher_grid_search.hpp,
