@@ -583,6 +583,70 @@ int  csm_correlative_match_prior_batch(csm_ctx* ctx, const csm_loop_query* queri
                                        const csm_correlative_params* params, const csm_motion_prior* priors,
                                        csm_prior_summary* out);
 
+/* ---- likelihood-field maps (beyond the reference, which scores a scan against the raw occupancy grid):
+ * every obstacle of a resident map spread by a Gaussian of the sensor's noise into a second resident map,
+ * the lookup table Olson's correlative matcher scores against. The field is an ordinary uint16 grid under
+ * an id of its own: every entry point that takes a map_id searches it unchanged, and the exactness of the
+ * integer key and the f64 replay carries over. Cost, covariance and refinement are bilinear in occupancy
+ * and belong on the source map, not on the field.
+ *
+ * Definition (integers only). Source grid G, rows x cols; radius R in cells, 1 <= R <=
+ * CSM_LIKELIHOOD_MAX_RADIUS; threshold occupied_min >= 1; a table T[0 .. R^2] of uint32, each <= 32768,
+ * indexed by the squared cell distance. A cell o is an obstacle iff it lies inside the map and G[o] >=
+ * occupied_min.
+ *   spread(c) = max over obstacles o with d2 = (o.r - c.r)^2 + (o.c - c.c)^2 <= R^2 of
+ *                   1 + (((G[o] - 1) * T[d2]) >> 15)      (uint32: 65534 * 32768 < 2^32)
+ *               0 if there is none
+ *   out(c)    = G[c]                        if keep_unknown and G[c] == 0
+ *               max(G[c], spread(c))        otherwise
+ * With T[0] = 32768 an obstacle spreads its own value onto itself: no cell is lowered, and no value exceeds
+ * the largest obstacle's (65534 at most, as in the source); a cell with no
+ * obstacle within R is unchanged, so unknown stays unknown away from walls and known-rate thresholds keep
+ * their meaning there. With keep_unknown = 0 an unknown cell within R of an obstacle BECOMES KNOWN (a scan
+ * point that lands just behind a wall then scores the wall's likelihood instead of nothing); with
+ * keep_unknown = 1 it stays 0 and only known cells are raised. An integer maximum does not depend on the
+ * order of the obstacles, so the device equals csm_host_likelihood_map bit for bit.
+ *
+ * The table (csm_host_likelihood_kernel; host, f64, libm exp, one fixed expression; the device never
+ * evaluates exp):
+ *   T[d2] = (uint32) floor(32768 * exp(-(d2 * (res * res)) / (2 * (sigma * sigma))) + 0.5)
+ * T[0] = 32768 and T is non-increasing. The caller passes the table in, as with the volume's weights. */
+#define CSM_LIKELIHOOD_MAX_RADIUS 16
+typedef struct {
+    int32_t         radius;         /* R, cells: 1..CSM_LIKELIHOOD_MAX_RADIUS */
+    uint32_t        occupied_min;   /* >= 1; 32768: P(occupied) above one half */
+    int32_t         keep_unknown;   /* 0: unknown cells within R of an obstacle become known; else they stay 0 */
+    int32_t         reserved;
+    const uint32_t* kernel;         /* T: radius^2 + 1 entries, each <= 32768 */
+} csm_likelihood_params;
+
+/* Host only. ceil(3 * (sigma / resolution)) clamped to 1..CSM_LIKELIHOOD_MAX_RADIUS; CSM_EINVAL unless sigma
+ * and resolution are finite and > 0. */
+int  csm_host_likelihood_radius(double sigma, double resolution);
+/* Host only. table[radius^2 + 1] as defined above; CSM_EINVAL for a radius out of range or a sigma or
+ * resolution that is not finite and > 0. */
+int  csm_host_likelihood_kernel(double sigma, double resolution, int32_t radius, uint32_t* table);
+/* Host only: the definition as one plain loop over the obstacles and their taps. grid / out: dense rows x
+ * cols, row-major, distinct buffers. CSM_EINVAL: rows or cols < 1, a radius out of range, occupied_min = 0,
+ * no table, a table entry above 32768. */
+int  csm_host_likelihood_map(const uint16_t* grid, int32_t rows, int32_t cols,
+                             const csm_likelihood_params* params, uint16_t* out);
+/* The field of the resident map src_map_id, built on the device into dst_map_id. Afterwards dst is in
+ * exactly the state csm_upload_grid(dst, csm_host_likelihood_map(cells of src)) leaves it in: rows, cols
+ * and pitch of the source, first known row / column of the new cells (counted on the device), no levels
+ * above the base, the block allocation derived from the cells; an existing dst (of any shape) is replaced,
+ * its cached copies dropped. src is not touched and no cell travels to the host. Returns when the field is
+ * built.
+ * CSM_EINVAL: dst == src, the params csm_host_likelihood_map refuses. CSM_ENOENT: src is not resident.
+ * A call that is refused or fails leaves an existing dst as it was and registers nothing. */
+int  csm_build_likelihood_map(csm_ctx* ctx, uint64_t src_map_id, uint64_t dst_map_id,
+                              const csm_likelihood_params* params);
+/* The same for n maps (src_ids[i] -> dst_ids[i]) in one launch, whatever their shapes: the fields of a
+ * loop-detection batch. A source may feed several fields. CSM_EINVAL also when a dst appears twice or is
+ * one of the sources; nothing is built then. */
+int  csm_build_likelihood_maps(csm_ctx* ctx, const uint64_t* src_ids, const uint64_t* dst_ids, int32_t n,
+                               const csm_likelihood_params* params);
+
 /* The raw records (csm_summary.raw) of the last csm_bnb_match_batch /
  * csm_correlative_match_batch call on this ctx, in query order, copied device
  * to device into dst_dev[n_queries] on the ctx stream (asynchronous): the
@@ -1020,7 +1084,7 @@ int  csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_er
 int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
 /* Drains recorded events; returns total ms and launch count since the last
  * reset for kernel "score_fine" | "score_coarse" | "bin" | "finalize" | "boxmax" |
- * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select". */
+ * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select" | "likelihood". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);
 int  csm_reset_kernel_timing(csm_ctx* ctx);

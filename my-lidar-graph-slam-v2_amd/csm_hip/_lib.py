@@ -234,6 +234,14 @@ class PriorSummary(C.Structure):
     _fields_ = [("summary", Summary), ("prior", PriorResult)]
 
 
+LIKELIHOOD_MAX_RADIUS = 16
+
+
+class LikelihoodParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("occupied_min", C.c_uint32), ("keep_unknown", C.c_int32),
+                ("reserved", C.c_int32), ("kernel", C.c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/csm_hip.h one to one
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -305,6 +313,11 @@ SIGNATURES = {
                                               _P(CorrelativeParams), _P(MotionPrior), _P(PriorSummary)]),
     "csm_correlative_match_prior_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(CorrelativeParams),
                                                     _P(MotionPrior), _P(PriorSummary)]),
+    "csm_host_likelihood_radius": (C.c_int, [C.c_double, C.c_double]),
+    "csm_host_likelihood_kernel": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "csm_host_likelihood_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(LikelihoodParams), C.c_void_p]),
+    "csm_build_likelihood_map": (C.c_int, [_ctx, C.c_uint64, C.c_uint64, _P(LikelihoodParams)]),
+    "csm_build_likelihood_maps": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, _P(LikelihoodParams)]),
     "csm_bnb_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,
                                       _P(BnbParams), _P(Summary)]),
     "csm_correlative_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,

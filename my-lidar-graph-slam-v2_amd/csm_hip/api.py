@@ -301,6 +301,57 @@ def prior_summary_to_dict(v):
     return dict(summary=summary_to_dict(v.summary), prior=prior_result_to_dict(v.prior))
 
 
+def host_likelihood_radius(sigma, resolution):
+    """ceil(3 sigma / resolution) clamped to 1..LIKELIHOOD_MAX_RADIUS (csm_host_likelihood_radius)."""
+    r = L.load().csm_host_likelihood_radius(sigma, resolution)
+    if r < 0:
+        raise CsmError(r, "csm_host_likelihood_radius")
+    return r
+
+
+def host_likelihood_kernel(sigma, resolution, radius):
+    """T[0 .. radius^2] as uint32: the integer Gaussian of a likelihood field, indexed by the squared cell
+    distance (csm_host_likelihood_kernel)."""
+    if not 1 <= radius <= L.LIKELIHOOD_MAX_RADIUS:
+        raise CsmError(L.CSM_EINVAL, "host_likelihood_kernel: radius out of range")
+    table = np.zeros(radius * radius + 1, np.uint32)
+    rc = L.load().csm_host_likelihood_kernel(sigma, resolution, radius, _ptr(table))
+    if rc != 0:
+        raise CsmError(rc, "csm_host_likelihood_kernel")
+    return table
+
+
+def likelihood_params(sigma=None, resolution=None, radius=None, occupied_min=32768, keep_unknown=False,
+                      kernel=None):
+    """(csm_likelihood_params, the table it points at): the table is `kernel` if given (radius required), else
+    that of (sigma, resolution) at `radius` (default: host_likelihood_radius). Keep the table alive with the
+    struct."""
+    if kernel is None:
+        if radius is None:
+            radius = host_likelihood_radius(sigma, resolution)
+        kernel = host_likelihood_kernel(sigma, resolution, radius)
+    elif radius is None:
+        raise CsmError(L.CSM_EINVAL, "likelihood_params: a kernel table needs its radius")
+    table = np.ascontiguousarray(kernel, dtype=np.uint32)
+    if 1 <= radius <= L.LIKELIHOOD_MAX_RADIUS and table.size < radius * radius + 1:
+        raise CsmError(L.CSM_EINVAL, "likelihood_params: the table needs radius^2 + 1 entries")
+    p = L.LikelihoodParams(radius, occupied_min, 1 if keep_unknown else 0, 0, table.ctypes.data)
+    return p, table
+
+
+def host_likelihood_map(grid, sigma=None, resolution=None, radius=None, occupied_min=32768, keep_unknown=False,
+                        kernel=None):
+    """The likelihood field of a dense uint16 grid on the host (csm_host_likelihood_map): the definition
+    the device build is compared with."""
+    g = np.ascontiguousarray(grid, dtype=np.uint16)
+    p, table = likelihood_params(sigma, resolution, radius, occupied_min, keep_unknown, kernel)
+    out = np.zeros_like(g)
+    rc = L.load().csm_host_likelihood_map(_ptr(g), g.shape[0], g.shape[1], C.byref(p), _ptr(out))
+    if rc != 0:
+        raise CsmError(rc, "csm_host_likelihood_map")
+    return out
+
+
 def host_probability_lut():
     lut = np.zeros(65536)
     L.load().csm_host_probability_lut(_ptr(lut))
@@ -464,6 +515,26 @@ class Context:
         ids = np.ascontiguousarray(map_ids, dtype=np.uint64)
         w = np.ascontiguousarray(win_sizes, dtype=np.int32)
         self._check(self.lib.csm_build_pyramids(self._ctx, _ptr(ids), ids.size, _ptr(w), w.size))
+
+    def build_likelihood_map(self, src, dst, sigma=None, resolution=None, radius=None, occupied_min=32768,
+                             keep_unknown=False, kernel=None):
+        """csm_build_likelihood_map: the likelihood field of the resident map `src` built on the device under
+        `dst` (an ordinary map id from then on). Table as in likelihood_params()."""
+        p, table = likelihood_params(sigma, resolution, radius, occupied_min, keep_unknown, kernel)
+        self._check(self.lib.csm_build_likelihood_map(self._ctx, src, dst, C.byref(p)))
+        self.shapes[dst] = self.shapes[src]
+
+    def build_likelihood_maps(self, srcs, dsts, sigma=None, resolution=None, radius=None, occupied_min=32768,
+                              keep_unknown=False, kernel=None):
+        """csm_build_likelihood_maps: srcs[i] -> dsts[i], all in one launch."""
+        s = np.ascontiguousarray(srcs, dtype=np.uint64)
+        d = np.ascontiguousarray(dsts, dtype=np.uint64)
+        if s.size != d.size:
+            raise CsmError(L.CSM_EINVAL, "build_likelihood_maps: as many destinations as sources")
+        p, table = likelihood_params(sigma, resolution, radius, occupied_min, keep_unknown, kernel)
+        self._check(self.lib.csm_build_likelihood_maps(self._ctx, _ptr(s), _ptr(d), s.size, C.byref(p)))
+        for a, b in zip(srcs, dsts):
+            self.shapes[b] = self.shapes[a]
 
     def copy_last_batch_records(self, dst_ptr):
         """Device-to-device copy of the last batch's records (query order) into dst_ptr."""
@@ -1035,14 +1106,27 @@ class ScanMatcherCorrelativeHIP:
     """Drop-in for ScanMatcherCorrelative (constructor arguments as in
     src/my_lidar_graph_slam/scan_matcher_factory.cpp:173-177)."""
 
-    def __init__(self, name, low_resolution, range_x, range_y, range_theta, ctx=None, prior_information=None):
+    # the likelihood field of map id m lives under m | LIKELIHOOD_ID_BIT (callers' ids are below 2^62, the
+    # adapters' own throw-away ids start there: bit 63 is free in both)
+    LIKELIHOOD_ID_BIT = 1 << 63
+
+    def __init__(self, name, low_resolution, range_x, range_y, range_theta, ctx=None, prior_information=None,
+                 likelihood_sigma=None, covariance_scale=1e4):
         """prior_information: a 3 x 3 information matrix of the sensor pose's offset from the initial pose
-        (beyond the reference); optimize_pose then goes through csm_correlative_match_prior."""
+        (beyond the reference); optimize_pose then goes through csm_correlative_match_prior.
+        likelihood_sigma: the sensor noise in metres (beyond the reference); optimize_pose then searches on
+        the map's likelihood field (Context.build_likelihood_map at the default radius, occupied_min and
+        keep_unknown, under map id | LIKELIHOOD_ID_BIT) and adds, from the ORIGINAL occupancy map -- cost,
+        covariance and refinement are bilinear in occupancy and must not see the spread values --
+        out["cost"] (cost_covariance_batch at the best sensor pose) and out["refined"] (linear_solver_batch
+        from the estimated pose), both with covariance_scale."""
         self.name = name
         self.low_resolution = low_resolution
         self.range_x, self.range_y, self.range_theta = range_x, range_y, range_theta
         self.ctx = ctx or Context()
         self.prior_information = prior_information
+        self.likelihood_sigma = likelihood_sigma
+        self.covariance_scale = covariance_scale
         self._nonce = 1 << 62
 
     def optimize_pose(self, grid, geom, angles, ranges, rel_pose, init_pose,
@@ -1053,22 +1137,36 @@ class ScanMatcherCorrelativeHIP:
         mid = map_id
         if mid is None:
             mid = self._nonce
-        if grid is not None and (map_id is None or not self.ctx.has_grid(mid)):
+        uploaded = grid is not None and (map_id is None or not self.ctx.has_grid(mid))
+        if uploaded:
             self.ctx.upload_grid(mid, grid)
+        search_id = mid
+        if self.likelihood_sigma is not None:
+            # the field follows the map: built when the map was uploaded just now or has no field yet
+            search_id = mid | self.LIKELIHOOD_ID_BIT
+            if uploaded or not self.ctx.has_grid(search_id):
+                self.ctx.build_likelihood_map(mid, search_id, self.likelihood_sigma, geom[0])
         if self.prior_information is not None:
             # the summary of the winner under the prior, with the unweighted winner and the penalty beside it
-            both = self.ctx.correlative_match_prior(mid, geom, angles, ranges, rel_pose, init_pose,
+            both = self.ctx.correlative_match_prior(search_id, geom, angles, ranges, rel_pose, init_pose,
                                                     self.range_x, self.range_y, self.range_theta,
                                                     self.low_resolution, self.prior_information,
                                                     score_threshold, known_rate_threshold)
             out = dict(both["summary"], unweighted=both["prior"]["unweighted"], prior=both["prior"])
         else:
-            out = self.ctx.correlative_match(mid, geom, angles, ranges, rel_pose, init_pose,
+            out = self.ctx.correlative_match(search_id, geom, angles, ranges, rel_pose, init_pose,
                                              self.range_x, self.range_y, self.range_theta,
                                              self.low_resolution, score_threshold,
                                              known_rate_threshold)
+        if self.likelihood_sigma is not None:
+            q = dict(map_id=mid, geom=geom, angles=angles, ranges=ranges, rel_pose=rel_pose,
+                     init_pose=out["estimated_pose"])
+            out["cost"] = self.ctx.cost_covariance_batch([q], [out["best_sensor_pose"]], self.covariance_scale)[0]
+            out["refined"] = self.ctx.linear_solver_batch([q], covariance_scale=self.covariance_scale)[0]
         if map_id is None:
             self.ctx.release_grid(mid)
+            if search_id != mid:
+                self.ctx.release_grid(search_id)
         return out
 
 

@@ -234,6 +234,9 @@ struct csm_ctx {
      * results; pinned staging */
     DevBuf pr_tab;
     PinBuf pr_pin;
+    /* likelihood-field maps (csm_likelihood_api.hip): table, job per map, counters; pinned staging */
+    DevBuf lf_tab;
+    PinBuf lf_pin;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */

@@ -68,6 +68,9 @@ struct GridMapView {
     static constexpr std::uint64_t kInvalidId = ~0ull;
     /* ids from here on are the adapters' own (throw-away maps): a caller's id must be smaller */
     static constexpr std::uint64_t kReservedIds = 1ull << 62;
+    /* the likelihood field of map id m lives under m | kLikelihoodIdBit (ScanMatcherCorrelativeHIP::
+     * UseLikelihoodField): callers' ids and the adapters' throw-away ids both leave bit 63 clear */
+    static constexpr std::uint64_t kLikelihoodIdBit = 1ull << 63;
     const std::uint16_t* mValues = nullptr;   /* row-major rows*cols */
     int mRows = 0, mCols = 0;
     double mResolution = 0.0;
@@ -259,6 +262,9 @@ public:
         const GridMapView& g = q.mGridMap;
         const bool temporary = g.mId == GridMapView::kInvalidId;
         const std::uint64_t id = this->MakeResident(g);
+        /* the search runs on the likelihood field when one is asked for; cost, covariance and any
+         * refinement below stay on the occupancy map `id`, which they are bilinear in */
+        const std::uint64_t searchId = this->mLikelihoodSigma > 0.0 ? this->MakeField(g, id) : id;
         csm_geometry geom { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
         const csm_scan scan = detail::ToScan(q.mScanData);
         const csm_correlative_params prm = this->Params(normalizedScoreThreshold, knownRateThreshold);
@@ -268,11 +274,11 @@ public:
         if (this->mUsePrior) {
             /* the winner under the motion prior; the unweighted one stays in LastPriorResult() */
             csm_prior_summary v {};
-            CSM_ASSERT_OK(ctx, csm_correlative_match_prior(ctx, id, &geom, &scan, init, &prm, &this->mPrior, &v));
+            CSM_ASSERT_OK(ctx, csm_correlative_match_prior(ctx, searchId, &geom, &scan, init, &prm, &this->mPrior, &v));
             s = v.summary;
             this->mLastPrior = v.prior;
         } else {
-            CSM_ASSERT_OK(ctx, csm_correlative_match(ctx, id, &geom, &scan, init, &prm, &s));
+            CSM_ASSERT_OK(ctx, csm_correlative_match(ctx, searchId, &geom, &scan, init, &prm, &s));
         }
         ScanMatchingSummary out;
         detail::FillSummary(s, q.mMapLocalInitialPose, &out);
@@ -294,8 +300,11 @@ public:
         } else if (this->mUseDeviceGreedy) {
             detail::DeviceGreedyCost(ctx, id, geom, scan, s.best_sensor_pose, this->mGreedy, &out);
         }
-        if (temporary && g.mValues)
+        if (temporary && g.mValues) {
             CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
+            if (searchId != id)
+                CSM_ASSERT_OK(ctx, csm_release_grid(ctx, searchId));
+        }
         return out;
     }
 
@@ -383,6 +392,20 @@ public:
         for (int c = 0; information && c < 9; ++c)
             this->mPrior.information[c] = information[c];
     }
+    /* OptimizePose on the map's likelihood field (csm_build_likelihood_map; beyond the reference, which
+     * scores against the raw occupancy grid): every obstacle (value >= occupiedMin) spread by a Gaussian of
+     * the sensor noise sigma, in metres, over ceil(3 sigma / resolution) cells (at most
+     * CSM_LIKELIHOOD_MAX_RADIUS), so that a guess a few cells off a thin wall still scores. The field is
+     * built on the device under the map's id | GridMapView::kLikelihoodIdBit, when the map is uploaded or
+     * revised and on first use, and only the search reads it: the cost function, the covariance and the
+     * motion prior's summary poses come from the occupancy map as before. sigma <= 0 switches it off. */
+    void UseLikelihoodField(double sigma, std::uint32_t occupiedMin = 32768, bool keepUnknown = false)
+    {
+        this->mLikelihoodSigma = sigma;
+        this->mLikelihoodOccupiedMin = occupiedMin;
+        this->mLikelihoodKeepUnknown = keepUnknown;
+        this->mFieldRevisions.clear();
+    }
     /* Both winners of the last OptimizePose under a prior: `unweighted` is what OptimizePose returns
      * without one, `penalty` what the prior charged the winner (key units). */
     const csm_prior_result& LastPriorResult() const { return this->mLastPrior; }
@@ -415,6 +438,35 @@ private:
         return id;
     }
 
+    /* The likelihood field of the resident map `id` under id | kLikelihoodIdBit: built when there is none
+     * or when it was built from another revision of the map (a throw-away map: always). */
+    std::uint64_t MakeField(const GridMapView& g, std::uint64_t id)
+    {
+        csm_ctx* ctx = this->mCtx.get();
+        const std::uint64_t fieldId = id | GridMapView::kLikelihoodIdBit;
+        const bool temporary = g.mId == GridMapView::kInvalidId;
+        auto held = this->mFieldRevisions.find(id);
+        if (temporary || !csm_has_grid(ctx, fieldId) || held == this->mFieldRevisions.end() ||
+            held->second != g.mRevision) {
+            const int radius = csm_host_likelihood_radius(this->mLikelihoodSigma, g.mResolution);
+            if (radius < 1) {
+                std::fprintf(stderr, "Assertion failed: likelihood sigma and map resolution > 0 at %s:%d\n",
+                             __FILE__, __LINE__);
+                std::abort();
+            }
+            std::vector<std::uint32_t> table(static_cast<std::size_t>(radius * radius + 1));
+            CSM_ASSERT_OK(ctx, csm_host_likelihood_kernel(this->mLikelihoodSigma, g.mResolution, radius, table.data()));
+            csm_likelihood_params lp {};
+            lp.radius = radius;
+            lp.occupied_min = this->mLikelihoodOccupiedMin;
+            lp.keep_unknown = this->mLikelihoodKeepUnknown ? 1 : 0;
+            lp.kernel = table.data();
+            CSM_ASSERT_OK(ctx, csm_build_likelihood_map(ctx, id, fieldId, &lp));
+            this->mFieldRevisions[id] = g.mRevision;
+        }
+        return fieldId;
+    }
+
     csm_correlative_params Params(double normalizedScoreThreshold, double knownRateThreshold) const
     {
         csm_correlative_params prm {};
@@ -439,6 +491,10 @@ private:
     bool mUsePrior = false;
     csm_motion_prior mPrior {};
     csm_prior_result mLastPrior {};
+    double mLikelihoodSigma = 0.0;
+    std::uint32_t mLikelihoodOccupiedMin = 32768;
+    bool mLikelihoodKeepUnknown = false;
+    detail::RevisionMap mFieldRevisions;       /* the map revision each resident field was built from */
 };
 
 /* ScanMatcherGridSearch (inc/mapping/scan_matcher_grid_search.hpp,
