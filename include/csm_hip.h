@@ -1095,6 +1095,12 @@ const char* csm_version(void);
 /* Test hook: bytes of device / pinned host memory the library holds right now, over
  * every context and group of the process. */
 int  csm_debug_live_bytes(int64_t* device, int64_t* pinned);
+/* Test hook: the first row and the first column of a resident map that hold a non-zero cell, as the library
+ * keeps them on the host (rows, cols for a map with none): what csm_upload_grid counts, the block upload, the
+ * map builder and csm_build_likelihood_map(s) reduce on the device, and the edge-band test of every search
+ * reads. out = { row, column }. CSM_ENOENT: the map is not resident. Reads host state only: no
+ * synchronisation, no change to any grid. */
+int  csm_debug_grid_known(csm_ctx* ctx, uint64_t map_id, int32_t out[2]);
 
 #ifdef __cplusplus
 }

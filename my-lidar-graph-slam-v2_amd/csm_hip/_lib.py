@@ -366,6 +366,7 @@ SIGNATURES = {
     "csm_reset_kernel_timing": (C.c_int, [_ctx]),
     "csm_version": (C.c_char_p, []),
     "csm_debug_live_bytes": (C.c_int, [_P(C.c_int64), _P(C.c_int64)]),
+    "csm_debug_grid_known": (C.c_int, [_ctx, C.c_uint64, _P(C.c_int32)]),
 }
 
 _lib = None

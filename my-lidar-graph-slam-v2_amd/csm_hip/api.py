@@ -485,6 +485,15 @@ class Context:
     def has_grid(self, map_id):
         return bool(self.lib.csm_has_grid(self._ctx, map_id))
 
+    def debug_grid_known(self, map_id):
+        """csm_debug_grid_known (test hook): (first row, first column) of the resident map holding a non-zero
+        cell, (rows, cols) if it has none."""
+        out = (C.c_int32 * 2)()
+        rc = self.lib.csm_debug_grid_known(self._ctx, map_id, out)
+        if rc != 0:
+            raise CsmError(rc, "csm_debug_grid_known: map %d not resident" % map_id)
+        return out[0], out[1]
+
     def release_grid(self, map_id):
         self._check(self.lib.csm_release_grid(self._ctx, map_id))
         self.shapes.pop(map_id, None)

@@ -303,6 +303,18 @@ int csm_has_grid(csm_ctx* ctx, uint64_t map_id)
     return ctx && find_grid(ctx, map_id) ? 1 : 0;
 }
 
+int csm_debug_grid_known(csm_ctx* ctx, uint64_t map_id, int32_t out[2])
+{
+    if (!ctx || !out)
+        return CSM_EINVAL;
+    const DeviceGrid* g = find_grid(ctx, map_id);
+    if (!g)
+        return CSM_ENOENT;          /* read-only: not even the last-error text changes */
+    out[0] = g->known_r0;
+    out[1] = g->known_c0;
+    return CSM_OK;
+}
+
 int csm_release_grid(csm_ctx* ctx, uint64_t map_id)
 {
     if (!ctx)

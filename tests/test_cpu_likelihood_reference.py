@@ -67,6 +67,135 @@ def test_the_cases_cover_what_they_claim():
         assert int(LR.grid_of(name).max(initial=0)) <= 65534
 
 
+def _id(case):
+    return "%s-R%d-%s-%d" % case
+
+
+@pytest.mark.parametrize("keep_unknown", [False, True])
+@pytest.mark.parametrize("case", LR.EDGE_CASES, ids=_id)
+def test_host_map_equals_the_reference_at_the_edge_cases(case, keep_unknown):
+    name, R, kind, occ = case
+    g, t, want = LR.edge_expected(name, R, kind, occ, keep_unknown)
+    got = api.host_likelihood_map(g, radius=R, occupied_min=occ, keep_unknown=keep_unknown, kernel=t)
+    assert got.dtype == np.uint16 and got.shape == g.shape
+    assert np.array_equal(got, want), np.argwhere(got != want)[:8]
+    far = LR.far_from_obstacles(g, R, occ)
+    assert np.array_equal(got[far], g[far])                          # no obstacle within R: unchanged
+    assert (got >= g).all()
+    if keep_unknown:
+        assert not got[g == 0].any()
+    assert int(got.max(initial=0)) == int(g.max(initial=0))           # T <= 32768: nothing above the largest value
+    if name == "single_65535":
+        assert int(got.max()) == 65535 and got[LR.SINGLE_AT] == 65535   # the largest value survives unwrapped
+    else:
+        assert int(got.max(initial=0)) <= 65534
+
+
+def test_first_known_and_halo_counts_on_hand_made_grids():
+    g = np.zeros((70, 140), np.uint16)
+    assert LR.first_known(g) == (70, 140)
+    g[40, 9] = 1
+    g[13, 77] = 65535
+    assert LR.first_known(g) == (13, 9)
+    g[31, 63] = g[32, 64] = g[69, 139] = 40000
+    g[28, 60] = 32767                                                 # not an obstacle
+    # tiles: rows 0..31 / 32..63 / 64..69, columns 0..63 / 64..127 / 128..139
+    assert LR.halo_counts(g, 1).tolist() == [[2, 3, 0], [2, 2, 0], [0, 0, 1]]
+    assert LR.halo_counts(g, 16).tolist() == [[3, 3, 0], [2, 3, 1], [0, 1, 1]]
+    assert LR.halo_counts(g, 1, 1).tolist() == [[3, 3, 0], [3, 2, 0], [0, 0, 1]]
+
+
+def test_the_edge_cases_are_what_they_claim():
+    # the tables
+    for R in (1, 3, 16):
+        ramp = LR.table_of("ramp", R).tolist()
+        assert ramp[0] == 32768 and len(set(ramp)) == len(ramp) == R * R + 1 and max(ramp) <= 32768
+        assert set(LR.table_of("flat", R).tolist()) == {32768} and not LR.table_of("zero", R).any()
+    # the switch: exactly (2R + 1)^2 obstacles in the one tile's halo, and one more
+    for R, n in ((1, 9), (3, 49), (16, 1089)):
+        assert LR.switch_count(R) == n
+        assert LR.halo_counts(LR.grid_of("switch_%d" % R), R).tolist() == [[n]]
+        assert LR.halo_counts(LR.grid_of("switch_%d_plus" % R), R).tolist() == [[n + 1]]
+    assert LR.halo_counts(LR.grid_of("switch_two_tiles"), 3).tolist() == [[50, 49]]
+    # one over at R = 16 with the obstacles of the last rows each alone responsible for a cell: without any
+    # one of the last 44 the reference changes under it
+    g, t, out = LR.edge_expected("switch_16_last", 16, "ramp", 32768, True)
+    assert LR.halo_counts(g, 16).tolist() == [[1090]] and int((g[16:] >= 32768).sum()) == 110
+    under = 1 + ((65533 * int(t[1])) >> 15)
+    for r in LR.LAST_ROWS:
+        assert (g[r, ::3] == 65534).all() and (out[r + 1, ::3] == under).all()
+    for r in LR.LAST_ROWS[-2:]:
+        for c in range(0, 64, 3):
+            less = g.copy()
+            less[r, c] = 700
+            assert LR.likelihood_map(less, t, 16, 32768, True)[r + 1, c] < under
+    # dense: past the switch in all four tiles at R = 3. At R = 16 only tile (0, 0) of the 40 x 70 map can be
+    # (the three others see 40 x 22, 24 x 70 and 24 x 22 cells, of which 60 % are obstacles: fewer than 1089);
+    # the 60 x 100 map is past it in all four, partial tiles and 4 pad columns included.
+    assert LR.halo_counts(LR.grid_of("dense40x70"), 3).shape == (2, 2)
+    assert (LR.halo_counts(LR.grid_of("dense40x70"), 3) > 49).all()
+    h = LR.halo_counts(LR.grid_of("dense40x70"), 16)
+    assert h[0, 0] > 1089 and (h > 0).all() and (h.reshape(-1)[1:] <= 1089).all()
+    assert LR.halo_counts(LR.grid_of("dense60x100"), 16).shape == (2, 2)
+    assert (LR.halo_counts(LR.grid_of("dense60x100"), 16) > 1089).all()
+    # the taps path's rim: past the switch in the upper tile at every radius, and around the lone obstacle
+    # the flat output is the disc, rim cells included (an off-axis one for R = 5, 10, 13, 15)
+    g = LR.grid_of("dense_rim")
+    r0, c0 = LR.RIM_AT
+    y, x = np.ogrid[:64, :64]
+    d2 = (y - r0) ** 2 + (x - c0) ** 2
+    alone = g.copy()
+    alone[r0, c0] = 700
+    for R, off in ((5, (3, 4)), (10, (6, 8)), (13, (5, 12)), (15, (9, 12)), (16, None)):
+        assert LR.halo_counts(g, R)[0, 0] > LR.switch_count(R)
+        out = LR.edge_expected("dense_rim", R, "flat", 32768, False)[2]
+        near = (d2 <= (R + 1) ** 2) & (x < 24)
+        assert LR.far_from_obstacles(alone, R)[near].all()              # no other obstacle reaches these cells
+        assert np.array_equal(out[near] == 50000, (d2 <= R * R)[near]) and (out[near & (d2 > R * R)] < 32768).all()
+        assert out[r0 + R, c0] == 50000 and out[r0, c0 + R] == 50000    # on the rim, inside the map
+        if off:
+            assert off[0] ** 2 + off[1] ** 2 == R * R and out[r0 + off[0], c0 + off[1]] == 50000
+    h = LR.halo_counts(LR.grid_of("room200"), 16)                       # walls: long lists, never past the switch
+    assert h.shape == (7, 4) and 300 < int(h.max()) <= 1089 and int((h > 100).sum()) >= 12
+    # the flat output of one obstacle is its disc
+    r0, c0 = LR.SINGLE_AT
+    y, x = np.ogrid[:48, :80]
+    d2 = (y - r0) ** 2 + (x - c0) ** 2
+    for R in (2, 5, 10, 13, 15, 16):
+        out = LR.edge_expected("single", R, "flat", 32768, False)[2]
+        assert np.array_equal(out != 0, d2 <= R * R) and set(out[out != 0].tolist()) == {50000}
+        assert int((out != 0).sum()) == LR.disc_cells(R)
+        rim = (d2 == R * R) & (y != r0) & (x != c0)
+        assert bool(rim.any()) == (R in (5, 10, 13, 15))                # an off-axis cell exactly on the rim
+        ramp = LR.edge_expected("single", R, "ramp", 32768, False)[2]
+        t = LR.table_of("ramp", R).astype(np.int64)
+        assert np.array_equal(ramp, np.where(d2 <= R * R, 1 + ((49999 * t[np.minimum(d2, R * R)]) >> 15), 0))
+        assert not LR.edge_expected("single", R, "flat", 32768, True)[2][d2 != 0].any()
+    assert [LR.disc_cells(R) for R in (1, 2, 3, 5, 16)] == [5, 13, 29, 81, 797]
+    zero = LR.edge_expected("single", 5, "zero", 32768, False)[2]
+    assert np.array_equal(zero, np.where(d2 == 0, 50000, np.where(d2 <= 25, 1, 0)))
+    # the lines and the cell
+    assert LR.grid_of("line1xN").shape == (1, 200) and LR.grid_of("lineNx1").shape == (200, 1)
+    assert np.flatnonzero(LR.grid_of("line1xN") >= 32768).tolist() == [0, 63, 64, 65, 199]
+    assert np.flatnonzero(LR.grid_of("lineNx1") >= 32768).tolist() == [0, 31, 32, 33, 63, 64, 65, 199]
+    assert LR.grid_of("one_cell").tolist() == [[50000]]
+    # occupied_min: 40000 keeps some obstacles and drops others; from 65535 on the map is copied through
+    g = LR.grid_of("random37x53")
+    assert 0 < int((g >= 40000).sum()) < int((g >= 32768).sum())
+    a, b = LR.edge_expected("random37x53", 3, "gauss", 40000, False)[2], LR.expected("random37x53", 3, False)[2]
+    assert (a != b).any() and (a != g).any()
+    for occ in (65535, 70000):
+        assert np.array_equal(LR.edge_expected("random37x53", 3, "gauss", occ, False)[2], g)
+    # low_known: the field's first known row and column lie in the band the source has none in
+    g, _, spread = LR.edge_expected("low_known", 3, "gauss", 32768, False)
+    assert g[9].any() and g[:, 11].any() and LR.first_known(g) == (9, 11)
+    fr, fc = LR.first_known(spread)
+    assert fr < 9 and fc < 11
+    assert fr <= LR.LOW_KNOWN_OBSTACLE[0] - 3 and fc <= LR.LOW_KNOWN_OBSTACLE[1] - 3
+    assert LR.first_known(LR.edge_expected("low_known", 3, "gauss", 32768, True)[2]) == (9, 11)
+    assert LR.first_known(LR.edge_expected("all_unknown", 3, "gauss", 32768, False)[2]) == (20, 33)
+
+
 def test_default_table_and_radius_come_from_sigma():
     g = LR.grid_of("random37x53")
     got = api.host_likelihood_map(g, 0.05, 0.05)
