@@ -977,6 +977,77 @@ int  csm_update_map_with_scan(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shap
                               const double global_map_pose[3], const csm_scan_node* node,
                               const csm_map_builder_params* params, csm_map_build_info* info);
 
+/* ---- many maps per call ----
+ * What GridMapBuilder::AfterLoopClosure announces ("Re-create the local grid maps and latest map after
+ * the loop closure", grid_map_builder.cpp:134) and does not do: after an optimization every local map
+ * is re-cast from its moved scan nodes. Also AppendLocalMap's first build and offline mapping. */
+
+/* One map of csm_construct_maps_from_scans: the arguments of csm_construct_map_from_scans. */
+typedef struct {
+    uint64_t             map_id;
+    csm_map_shape        shape;              /* in: the map before the call; out: after (as the single call) */
+    double               global_map_pose[3];
+    const csm_scan_node* nodes;
+    int32_t              n_nodes;
+    int32_t              status;             /* out: CSM_OK or what the single call would have returned */
+    csm_map_build_info   info;               /* out: per map; host_us / device_us are the chunk's, divided
+                                                evenly among its maps: rough shares. The chunk's host_us
+                                                runs from its start to the first launch of the update
+                                                chain, so it holds the wait for the projection's
+                                                read-back and for the uploads of patched rays */
+} csm_map_build_job;
+
+typedef struct {
+    int64_t scratch_limit_bytes;   /* 0 = default (1 GiB), as csm_peaks_params.scratch_limit_bytes */
+} csm_map_batch_params;
+
+typedef struct {
+    int32_t chunks;                /* launch chains the call was cut into */
+    int32_t host_projection_jobs;  /* jobs whose hit points all came from the host path */
+    int64_t scan_bytes_uploaded;   /* angles + ranges actually copied (shared scans counted once) */
+    double  host_us, device_us;
+} csm_map_batch_info;
+
+/* csm_construct_map_from_scans for every job, with each step of the build launched once per chunk of
+ * jobs instead of once per job, and two read-backs per chunk (bounding boxes and uncertain-beam counts
+ * after the projection; counters at the end) instead of two per map. Afterwards the context holds what
+ * a loop of the single call over the jobs, in order and not stopping at a failing job, leaves: shapes,
+ * cells (byte-equal), first known row / column, block allocation, stale levels, dropped phase-major and
+ * pair-row copies, and each job's info counters.
+ *  - A job the single call refuses (no nodes, a node without a scan, a bad shape, an empty bounding
+ *    box, a resize out of range, more than 2^24 beams) leaves its map alone; a job whose rays leave
+ *    the resized map has its map dropped. Its status says so, the other jobs complete, and the call
+ *    returns the first status in job order that is not CSM_OK.
+ *  - CSM_EINVAL before anything changes: a null ctx / jobs / params, n_jobs < 1, bad params (as the
+ *    single call), a negative scratch_limit_bytes, or the same map_id in two jobs.
+ *  - params holds for all jobs (one pair of update tables); everything else is per job.
+ *  - Chunks: consecutive jobs, cut by csm_host_map_batch_plan. Before the projection a map's cell
+ *    count is not known; the entry plans with the bound (2 R + extent of the sensor positions + 2 res)
+ *    / res + 2 + 2 blocks per axis, R = the largest usable range of the job's nodes, capped at the
+ *    2^28 cells a map may have. The buffers themselves are sized by what the resize gives.
+ *  - Scans: each distinct (angles, ranges, n_points) of a chunk is staged and uploaded once.
+ *  - A map with more uncertain beams than the context's cap, or whose certified beams are not known to
+ *    spread, takes the host projection on its own; the rest of its chunk stays on the device.
+ * Limit: the hits of one cell are ranked by brute force (quadratic in the hits per cell), as in the
+ * single call: a global map of thousands of scans in one job is slow. `batch` and `info` may be null.
+ * A device or allocation failure (CSM_EIO, CSM_ENOMEM) ends the call: the jobs not yet finished get
+ * that status, their maps may have been dropped, and `info` holds what had run. */
+int  csm_construct_maps_from_scans(csm_ctx* ctx, csm_map_build_job* jobs, int32_t n_jobs,
+                                   const csm_map_builder_params* params, const csm_map_batch_params* batch,
+                                   csm_map_batch_info* info);
+
+/* Host only, no GPU: the cut of csm_construct_maps_from_scans. Job j has n_beams[j] beams and at most
+ * n_cells_upper[j] cells; its scratch is n (24 + 16) bytes of rays and records (n = max(n_beams, 1)),
+ * 4 * ((11 n_beams + 23) & ~3) bytes of lists, 12 bytes per cell and 8 * 135 bytes of counters. Jobs
+ * are taken in order; a chunk is closed before the job that would take it past scratch_limit_bytes
+ * (0 = 1 GiB), so a job that alone exceeds the limit gets a chunk of its own. chunk_of[n_jobs]: the
+ * chunk of each job; chunk_bytes[n_jobs]: the first *n_chunks entries hold the chunks' scratch.
+ * CSM_EINVAL: null pointers, n_jobs < 1, a negative limit, an n_beams[j] outside 0 .. 2^24 or an
+ * n_cells_upper[j] outside 0 .. 2^28 (what one map build may have). */
+int  csm_host_map_batch_plan(const int64_t* n_beams, const int64_t* n_cells_upper, int32_t n_jobs,
+                             int64_t scratch_limit_bytes, int32_t* chunk_of, int64_t* chunk_bytes,
+                             int32_t* n_chunks);
+
 /* ---- pose-graph optimization: the backend's Optimize step ---- */
 
 /* LinearSolver / SolverType of PoseGraphOptimizerLM (inc/mapping/pose_graph_optimizer_lm.hpp) */

@@ -97,6 +97,21 @@ class MapBuildInfo(C.Structure):
                 ("host_us", C.c_double), ("device_us", C.c_double)]
 
 
+class MapBuildJob(C.Structure):
+    _fields_ = [("map_id", C.c_uint64), ("shape", MapShape), ("global_map_pose", C.c_double * 3),
+                ("nodes", C.POINTER(ScanNode)), ("n_nodes", C.c_int32), ("status", C.c_int32),
+                ("info", MapBuildInfo)]
+
+
+class MapBatchParams(C.Structure):
+    _fields_ = [("scratch_limit_bytes", C.c_int64)]
+
+
+class MapBatchInfo(C.Structure):
+    _fields_ = [("chunks", C.c_int32), ("host_projection_jobs", C.c_int32), ("scan_bytes_uploaded", C.c_int64),
+                ("host_us", C.c_double), ("device_us", C.c_double)]
+
+
 class GridSearchParams(C.Structure):
     _fields_ = [("range_x", C.c_double), ("range_y", C.c_double), ("range_theta", C.c_double),
                 ("step_x", C.c_double), ("step_y", C.c_double), ("step_theta", C.c_double),
@@ -329,6 +344,9 @@ SIGNATURES = {
     "csm_host_map_resize": (C.c_int, [_P(MapShape), C.c_void_p, C.c_int32, C.c_void_p]),
     "csm_update_map_with_scan": (C.c_int, [_ctx, C.c_uint64, _P(MapShape), C.c_void_p, _P(ScanNode),
                                            _P(MapBuilderParams), _P(MapBuildInfo)]),
+    "csm_construct_maps_from_scans": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "csm_host_map_batch_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                          _P(C.c_int32)]),
     "csm_set_block_allocation": (C.c_int, [_ctx, C.c_uint64, C.c_int32, C.c_void_p]),
     "csm_cost_covariance_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, C.c_void_p, C.c_double,
                                             _P(RefineResult)]),

@@ -104,6 +104,23 @@ def host_map_resize(shape, box, expand=False):
                  log2_block=sh.log2_block_size), (int(shift[0]), int(shift[1])))
 
 
+def host_map_batch_plan(n_beams, n_cells_upper, scratch_limit_bytes=0):
+    """csm_host_map_batch_plan: how csm_construct_maps_from_scans cuts its jobs into chunks. Returns
+    (chunk of each job, scratch bytes of each chunk); 0 = the default limit of 1 GiB."""
+    nb = np.ascontiguousarray(n_beams, dtype=np.int64)
+    nc = np.ascontiguousarray(n_cells_upper, dtype=np.int64)
+    if nb.ndim != 1 or nb.shape != nc.shape:
+        raise ValueError("n_beams and n_cells_upper must be 1-D and equally long")
+    chunk_of = np.zeros(max(nb.size, 1), np.int32)
+    chunk_bytes = np.zeros(max(nb.size, 1), np.int64)
+    n_chunks = C.c_int32(0)
+    rc = L.load().csm_host_map_batch_plan(_ptr(nb), _ptr(nc), nb.size, int(scratch_limit_bytes), _ptr(chunk_of),
+                                          _ptr(chunk_bytes), C.byref(n_chunks))
+    if rc:
+        raise CsmError(rc, "csm_host_map_batch_plan")
+    return [int(c) for c in chunk_of[:nb.size]], [int(b) for b in chunk_bytes[:n_chunks.value]]
+
+
 def debug_live_bytes():
     """csm_debug_live_bytes: (device, pinned) bytes the library holds, over the whole process."""
     dev, pin = C.c_int64(0), C.c_int64(0)
@@ -838,6 +855,62 @@ class Context:
         node on top of the resident map `map_id`, which grows if it has to."""
         return self._map_build(map_id, shape, map_pose, [node], True, usable_range_min, usable_range_max,
                                prob_hit, prob_miss, subpixel_scale)
+
+    def construct_maps_from_scans(self, jobs, usable_range_min=0.01, usable_range_max=20.0, prob_hit=0.62,
+                                  prob_miss=0.46, subpixel_scale=100, scratch_limit_bytes=0):
+        """csm_construct_maps_from_scans: construct_map_from_scans for many maps in one call (what
+        GridMapBuilder::AfterLoopClosure announces and leaves undone). jobs = dicts(map_id, shape,
+        map_pose, nodes) with the single call's meanings; the builder settings hold for all of them.
+        Returns ([(new shape dict, info dict, status), ...], batch info dict). A job the single call
+        would refuse gets its status (and its shape back unchanged) while the others complete; only a
+        refusal of the whole call raises."""
+        arr = (L.MapBuildJob * max(len(jobs), 1))()
+        keep, shared = [], {}
+
+        def as_f64(a):
+            # the same array object is handed over at the same address: the library uploads it once
+            if id(a) not in shared:
+                shared[id(a)] = (a, _f64(a))
+            return shared[id(a)][1]
+
+        for j, job in enumerate(jobs):
+            shape = job["shape"]
+            arr[j].map_id = job["map_id"]
+            arr[j].shape = L.MapShape(shape["res"], shape["off_x"], shape["off_y"], shape["rows"], shape["cols"],
+                                      shape["log2_block"])
+            arr[j].global_map_pose[:] = list(job["map_pose"])
+            nodes = job["nodes"]
+            nd_arr = (L.ScanNode * max(len(nodes), 1))()
+            keep.append(nd_arr)
+            for i, nd in enumerate(nodes):
+                a_, r_ = as_f64(nd["angles"]), as_f64(nd["ranges"])
+                nd_arr[i].global_pose[:] = list(nd["pose"])
+                nd_arr[i].scan.angles = a_.ctypes.data_as(C.POINTER(C.c_double))
+                nd_arr[i].scan.ranges = r_.ctypes.data_as(C.POINTER(C.c_double))
+                nd_arr[i].scan.n_points = a_.size
+                nd_arr[i].scan.relative_sensor_pose[:] = list(nd.get("rel_pose", (0.0, 0.0, 0.0)))
+                nd_arr[i].min_range = nd.get("min_range", 0.0)
+                nd_arr[i].max_range = nd.get("max_range", 1e9)
+            arr[j].nodes = nd_arr if nodes else None
+            arr[j].n_nodes = len(nodes)
+        prm = L.MapBuilderParams(usable_range_min, usable_range_max, prob_hit, prob_miss, subpixel_scale)
+        bp = L.MapBatchParams(int(scratch_limit_bytes))
+        binfo = L.MapBatchInfo()
+        rc = self.lib.csm_construct_maps_from_scans(self._ctx, arr, len(jobs), C.byref(prm), C.byref(bp),
+                                                    C.byref(binfo))
+        if rc and (rc != L.CSM_EINVAL or not jobs or all(arr[j].status == 0 for j in range(len(jobs)))):
+            self._check(rc)                    # the whole call was refused, or failed on the device
+        out = []
+        for j, job in enumerate(jobs):
+            sh, status = arr[j].shape, int(arr[j].status)
+            if status == 0:
+                self.shapes[job["map_id"]] = (sh.rows, sh.cols)
+            elif not self.has_grid(job["map_id"]):
+                self.shapes.pop(job["map_id"], None)
+            out.append((dict(res=sh.resolution, off_x=sh.offset_x, off_y=sh.offset_y, rows=sh.rows, cols=sh.cols,
+                             log2_block=sh.log2_block_size),
+                        {name: getattr(arr[j].info, name) for name, _ in L.MapBuildInfo._fields_}, status))
+        return out, {name: getattr(binfo, name) for name, _ in L.MapBatchInfo._fields_}
 
     def _map_build(self, map_id, shape, map_pose, nodes, keep_cells, usable_range_min, usable_range_max,
                    prob_hit, prob_miss, subpixel_scale):

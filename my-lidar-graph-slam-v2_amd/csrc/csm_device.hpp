@@ -349,6 +349,7 @@ struct MapProjJob {
     uint32_t* unc_count;
     uint32_t* unc_list;
     uint32_t unc_cap;
+    const long long* node_src; /* null, or per node { angles, ranges } offsets (csm_map.hpp, map_project_beam) */
 };
 
 constexpr int kMapStripes = 64;
@@ -371,6 +372,23 @@ struct MapJob {
     const uint16_t* lut_miss;
     uint16_t* cells;           /* output grid, rows * pitch */
     int32_t keep_cells;        /* 1: the updates go on top of the cells' values (UpdateGridMap) */
+};
+
+/* Many maps per launch (csm_map_batch_kernels.hip): one MapProjJob and one MapJob per map, each
+ * pointing at its own part of the shared scratch (rays, records, lists, cell words, counter block), and
+ * per step a prefix table of the maps' workgroup counts: workgroup w of a launch belongs to the map m
+ * with pre[m] <= w < pre[m + 1] and is that map's workgroup w - pre[m]. Ray numbers, cell ids and
+ * slots stay local to the map. */
+struct MapBatchTable {
+    const MapProjJob* proj;    /* [n_maps] */
+    const MapJob* jobs;        /* [n_maps] */
+    int32_t n_maps;
+    const uint32_t* pre_beam;  /* [n_maps + 1] each: workgroups of 256 beams, of 256 rays, of 256 cells, */
+    const uint32_t* pre_ray;   /*   groups of kMapGroup rays, workgroups of 256 padded cells */
+    const uint32_t* pre_cell;
+    const uint32_t* pre_group;
+    const uint32_t* pre_apply;
+    uint32_t* hit_prefix;      /* [n_maps + 1] cells with hits before map m (k_mapb_hit_prefix) */
 };
 
 /* cost / covariance / linear-solver refinement (csm_cost_kernels.hip) */

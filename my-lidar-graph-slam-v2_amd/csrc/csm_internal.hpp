@@ -249,7 +249,9 @@ struct csm_ctx {
     DevBuf m_rays, m_recs, m_cell, m_lists, m_cnt, m_lut;
     DevBuf m_alloc;                               /* the old map's allocation bitmap during a build */
     double m_lut_hit = -1.0, m_lut_miss = -1.0;   /* probabilities the update tables were built for */
-    bool m_apply_attr = false;
+    bool m_apply_attr = false, m_batch_attr = false;
+    int m_cus = 0;                                /* compute units of the device (the batch's persistent kernel) */
+    DevBuf m_btab;                                /* csm_construct_maps_from_scans: job and prefix tables */
     hipEvent_t m_ev[2] = { nullptr, nullptr };    /* device_us of csm_map_build_info */
     std::vector<double> stage;                    /* host staging of one scan (angles, ranges) */
     /* pinned job-table blocks of csm_score_windows_dev calls (sources of asynchronous
@@ -391,6 +393,11 @@ int ensure_allocation(csm_ctx* ctx, DeviceGrid& g);
  * ctx->stream; `carried` must stay alive until the stream has drained. */
 int build_allocation(csm_ctx* ctx, DeviceGrid& g, int log2b, const uint8_t* carried, int carried_brows,
                      int carried_bcols, int carried_br0, int carried_bc0);
+
+/* defined in csm_map_api.hip */
+constexpr uint32_t kMapUncCap = 4096;    /* beams listed for exact recomputation per map build */
+/* ctx->m_lut = the value -> value tables of one hit / one miss update for prm's probabilities */
+int map_ensure_tables(csm_ctx* ctx, const csm_map_builder_params* prm);
 
 } /* namespace csm_host */
 using namespace csm_host;

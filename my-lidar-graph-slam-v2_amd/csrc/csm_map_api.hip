@@ -5,8 +5,6 @@
 
 #include "csm_map_kernels.hip"
 
-extern "C" {
-
 /* ---- map building ---- */
 
 namespace {
@@ -14,7 +12,6 @@ namespace {
 /* GridBinaryBayes's conversions (src/grid_map_new/grid_binary_bayes.cpp:345-383,
  * inc/grid_map_new/grid_values.hpp:11-46) with its constants: values 1..65535
  * stand for probabilities 0.001..0.999, 0 = unknown. */
-constexpr uint32_t kMapUncCap = 4096;    /* beams listed for exact recomputation per build */
 const double kBayesProbMin = 1e-3;
 const double kBayesProbMax = 1.0 - 1e-3;
 
@@ -58,6 +55,34 @@ int map_index_to_block(int idx, int log2_block)
 }
 
 } /* namespace */
+
+namespace csm_host {
+
+/* the two value -> value tables of the cell update, in ctx->m_lut, for prm's probabilities */
+int map_ensure_tables(csm_ctx* ctx, const csm_map_builder_params* prm)
+{
+    if (int rc = ensure(ctx, ctx->m_lut, 2 * 65536 * sizeof(uint16_t)))
+        return rc;
+    uint16_t* d_lut = reinterpret_cast<uint16_t*>(ctx->m_lut.p);
+    if (ctx->m_lut_hit != prm->prob_hit || ctx->m_lut_miss != prm->prob_miss) {
+        std::vector<uint16_t> tab(2 * 65536);
+        const double odds_hit = bayes_probability_to_odds(prm->prob_hit);     /* grid_map_builder.cpp:95-96 */
+        const double odds_miss = bayes_probability_to_odds(prm->prob_miss);
+        for (uint32_t v = 0; v < 65536; ++v) {
+            tab[v] = bayes_value_after(v, odds_hit);
+            tab[65536 + v] = bayes_value_after(v, odds_miss);
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(d_lut, tab.data(), tab.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->m_lut_hit = prm->prob_hit;
+        ctx->m_lut_miss = prm->prob_miss;
+    }
+    return CSM_OK;
+}
+
+} /* namespace csm_host */
+
+extern "C" {
 
 /* GridMap<T>::Resize(BoundingBox<int>) (src/grid_map_new/grid_map.cpp:841-889) and, with
  * expand != 0, GridMap<T>::Expand (:915-936) in front of it, on index boxes: host only. */
@@ -334,21 +359,8 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
                                          65536 * (int)sizeof(uint16_t)));
         ctx->m_apply_attr = true;
     }
-    if ((rc = ensure(ctx, ctx->m_lut, 2 * 65536 * sizeof(uint16_t)))) return rc;
+    if ((rc = map_ensure_tables(ctx, prm))) return rc;
     uint16_t* d_lut = reinterpret_cast<uint16_t*>(ctx->m_lut.p);
-    if (ctx->m_lut_hit != prm->prob_hit || ctx->m_lut_miss != prm->prob_miss) {
-        std::vector<uint16_t> tab(2 * 65536);
-        const double odds_hit = bayes_probability_to_odds(prm->prob_hit);     /* grid_map_builder.cpp:95-96 */
-        const double odds_miss = bayes_probability_to_odds(prm->prob_miss);
-        for (uint32_t v = 0; v < 65536; ++v) {
-            tab[v] = bayes_value_after(v, odds_hit);
-            tab[65536 + v] = bayes_value_after(v, odds_miss);
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(d_lut, tab.data(), tab.size() * 2, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->m_lut_hit = prm->prob_hit;
-        ctx->m_lut_miss = prm->prob_miss;
-    }
 
     /* The old map's block allocation, which Resize / Expand move and ResetValues keeps
      * (grid_map.cpp:278-287, 841-889, 915-936): the resident map_id's, if its rows and cols

@@ -1154,6 +1154,55 @@ public:
                                                            &this->mParams, &this->mInfo));
     }
 
+    /* What GridMapBuilder::AfterLoopClosure announces ("Re-create the local grid maps and latest map
+     * after the loop closure", grid_map_builder.cpp:134) and leaves undone: the listed local maps are
+     * rebuilt from their scan nodes (whose poses the optimization has moved) in one call
+     * (csm_construct_maps_from_scans), each in the frame it had. nodeSpans[i] = the scan nodes of local
+     * map localMapIds[i] in id order; a local map that does not exist yet is created first. LocalMap(id)
+     * returns the new geometry afterwards. Any job's failure is an assertion, as in the single build. */
+    void ConstructLocalMaps(const std::vector<std::uint64_t>& localMapIds,
+                            const std::vector<RobotPose2D<double>>& globalMapPoses,
+                            const std::vector<std::pair<const ScanNodeView*, std::size_t>>& nodeSpans)
+    {
+        if (localMapIds.empty() || globalMapPoses.size() != localMapIds.size() ||
+            nodeSpans.size() != localMapIds.size()) {
+            std::fprintf(stderr, "Assertion failed: one pose and one node span per local map at %s:%d\n",
+                         __FILE__, __LINE__);
+            std::abort();
+        }
+        std::vector<std::vector<csm_scan_node>> flat(localMapIds.size());
+        std::vector<csm_map_build_job> jobs(localMapIds.size());
+        for (std::size_t m = 0; m < localMapIds.size(); ++m) {
+            if (this->mLocalShapes.find(localMapIds[m]) == this->mLocalShapes.end())
+                this->CreateLocalMap(localMapIds[m]);
+            flat[m].resize(nodeSpans[m].second);
+            for (std::size_t i = 0; i < nodeSpans[m].second; ++i) {
+                const ScanNodeView& node = nodeSpans[m].first[i];
+                flat[m][i].global_pose[0] = node.mGlobalPose.mX;
+                flat[m][i].global_pose[1] = node.mGlobalPose.mY;
+                flat[m][i].global_pose[2] = node.mGlobalPose.mTheta;
+                flat[m][i].scan = detail::ToScan(node.mScanData);
+                flat[m][i].min_range = node.mMinRange;
+                flat[m][i].max_range = node.mMaxRange;
+            }
+            csm_map_build_job& job = jobs[m];
+            job = csm_map_build_job {};
+            job.map_id = localMapIds[m];
+            job.shape = this->mLocalShapes.at(localMapIds[m]);
+            job.global_map_pose[0] = globalMapPoses[m].mX;
+            job.global_map_pose[1] = globalMapPoses[m].mY;
+            job.global_map_pose[2] = globalMapPoses[m].mTheta;
+            job.nodes = flat[m].data();
+            job.n_nodes = static_cast<std::int32_t>(flat[m].size());
+        }
+        CSM_ASSERT_OK(this->mCtx, csm_construct_maps_from_scans(this->mCtx, jobs.data(),
+                                                                static_cast<std::int32_t>(jobs.size()),
+                                                                &this->mParams, nullptr, &this->mBatchInfo));
+        for (const csm_map_build_job& job : jobs)
+            this->mLocalShapes[job.map_id] = job.shape;
+    }
+    const csm_map_batch_info& LastBatchInfo() const { return this->mBatchInfo; }
+
     /* geometry + id of a local map (cells on the device), e.g. for a LoopDetectionQuery */
     GridMapView LocalMap(std::uint64_t localMapId) const
     {
@@ -1192,6 +1241,7 @@ private:
     csm_map_builder_params mParams {};
     csm_map_shape mShape {};
     csm_map_build_info mInfo {};
+    csm_map_batch_info mBatchInfo {};
     GridMapView mLatestMap;
     int mInitialCells = 0;
     std::map<std::uint64_t, csm_map_shape> mLocalShapes;
