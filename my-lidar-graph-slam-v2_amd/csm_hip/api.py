@@ -28,6 +28,25 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _scan_nodes(nodes, as_f64, keep):
+    """An array of csm_scan_node for node dicts(pose, angles, ranges, rel_pose, min_range, max_range),
+    never of length zero. as_f64 converts an angle or range array; what the array points at is
+    appended to keep."""
+    arr = (L.ScanNode * max(len(nodes), 1))()
+    for i, nd in enumerate(nodes):
+        a_, r_ = as_f64(nd["angles"]), as_f64(nd["ranges"])
+        keep += [a_, r_]
+        arr[i].global_pose[:] = list(nd["pose"])
+        arr[i].scan.angles = a_.ctypes.data_as(C.POINTER(C.c_double))
+        arr[i].scan.ranges = r_.ctypes.data_as(C.POINTER(C.c_double))
+        arr[i].scan.n_points = a_.size
+        arr[i].scan.relative_sensor_pose[:] = list(nd.get("rel_pose", (0.0, 0.0, 0.0)))
+        arr[i].min_range = nd.get("min_range", 0.0)
+        arr[i].max_range = nd.get("max_range", 1e9)
+    keep.append(arr)
+    return arr
+
+
 def result_to_dict(r):
     return dict(found=int(r.found), best_x=int(r.best_x), best_y=int(r.best_y),
                 best_theta=int(r.best_theta), key=int(r.key),
@@ -880,17 +899,7 @@ class Context:
                                       shape["log2_block"])
             arr[j].global_map_pose[:] = list(job["map_pose"])
             nodes = job["nodes"]
-            nd_arr = (L.ScanNode * max(len(nodes), 1))()
-            keep.append(nd_arr)
-            for i, nd in enumerate(nodes):
-                a_, r_ = as_f64(nd["angles"]), as_f64(nd["ranges"])
-                nd_arr[i].global_pose[:] = list(nd["pose"])
-                nd_arr[i].scan.angles = a_.ctypes.data_as(C.POINTER(C.c_double))
-                nd_arr[i].scan.ranges = r_.ctypes.data_as(C.POINTER(C.c_double))
-                nd_arr[i].scan.n_points = a_.size
-                nd_arr[i].scan.relative_sensor_pose[:] = list(nd.get("rel_pose", (0.0, 0.0, 0.0)))
-                nd_arr[i].min_range = nd.get("min_range", 0.0)
-                nd_arr[i].max_range = nd.get("max_range", 1e9)
+            nd_arr = _scan_nodes(nodes, as_f64, keep)
             arr[j].nodes = nd_arr if nodes else None
             arr[j].n_nodes = len(nodes)
         prm = L.MapBuilderParams(usable_range_min, usable_range_max, prob_hit, prob_miss, subpixel_scale)
@@ -916,18 +925,8 @@ class Context:
                    prob_hit, prob_miss, subpixel_scale):
         sh = L.MapShape(shape["res"], shape["off_x"], shape["off_y"], shape["rows"], shape["cols"],
                         shape["log2_block"])
-        arr = (L.ScanNode * len(nodes))()
         keep = []
-        for i, nd in enumerate(nodes):
-            a_, r_ = _f64(nd["angles"]), _f64(nd["ranges"])
-            keep += [a_, r_]
-            arr[i].global_pose[:] = list(nd["pose"])
-            arr[i].scan.angles = a_.ctypes.data_as(C.POINTER(C.c_double))
-            arr[i].scan.ranges = r_.ctypes.data_as(C.POINTER(C.c_double))
-            arr[i].scan.n_points = a_.size
-            arr[i].scan.relative_sensor_pose[:] = list(nd.get("rel_pose", (0.0, 0.0, 0.0)))
-            arr[i].min_range = nd.get("min_range", 0.0)
-            arr[i].max_range = nd.get("max_range", 1e9)
+        arr = _scan_nodes(nodes, _f64, keep)
         prm = L.MapBuilderParams(usable_range_min, usable_range_max, prob_hit, prob_miss, subpixel_scale)
         info = L.MapBuildInfo()
         mp = _f64(map_pose)

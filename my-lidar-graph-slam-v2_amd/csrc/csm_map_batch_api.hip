@@ -2,11 +2,12 @@
  * csm_host_map_batch_plan (include/csm_hip.h), with their kernels
  * (csm_map_batch_kernels.hip). A translation unit of libcsm_hip.so of its own.
  *
- * Per job the steps are those of map_build (csm_map_api.hip) with keep_cells = false,
- * in the same order and with the same arithmetic; what differs is that each step runs
- * for a whole chunk of jobs before the next one starts, so that the device sees one
- * launch per step and the host two read-backs per chunk. */
-#include "csm_internal.hpp"
+ * Per job the host steps are the functions map_build runs (csm_map_build.hpp, keep_cells = false);
+ * each runs for a whole chunk of jobs before the next one starts, so that the device sees one
+ * launch per step and the host two read-backs per chunk. What this file keeps: the chunk's
+ * scratch layout, prefix tables and shared scans, the launches, one synchronise per chunk where
+ * the single call has one per map, and a refused job leaving the chunk while the others go on. */
+#include "csm_map_build.hpp"
 
 #include "csm_map_batch_kernels.hip"
 
@@ -27,37 +28,18 @@ int64_t map_job_scratch(int64_t n_beams, int64_t n_cells)
            8 * (int64_t)kMapCounters;
 }
 
-/* one job on its way through a chunk */
-struct BatchJob {
+/* one job on its way through a chunk: the build's state and the job's places in the chunk's buffers */
+struct BatchJob : MapBuild {
     int index = 0;                         /* in the caller's array */
-    std::vector<MapNode> table;
-    long long usable = 0;
-    int n_beams = 0, n_nodes = 0;
     int64_t cells_upper = 0;
-    size_t ray0 = 0, node0 = 0, unc0 = 0;  /* its first ray, node and uncertain-list word in the chunk's buffers */
-    double min_x = 0, min_y = 0, max_x = 0, max_y = 0;
-    int box[4] = { 0, 0, 0, 0 };
-    bool device_projection = false, spread_known = false, live = true;
-    uint32_t n_unc = 0;
-    csm_map_shape next = {};
-    int32_t shift[2] = { 0, 0 };
-    size_t n_cells = 0, cell0 = 0, list0 = 0;
+    size_t ray0 = 0, node0 = 0, unc0 = 0;  /* its first ray, node and uncertain-list word */
+    size_t cell0 = 0, list0 = 0;
     DevBuf carried;                        /* the old map's allocation bitmap until the new one is built */
-    bool has_carried = false;
-    int carried_brows = 0, carried_bcols = 0;
-    DeviceGrid fresh;
-    DeviceGrid* dst = nullptr;
+    bool live = true;
     std::string error;
-
-    void add_point(double x, double y)
-    {
-        min_x = std::min(min_x, x);
-        min_y = std::min(min_y, y);
-        max_x = std::max(max_x, x);
-        max_y = std::max(max_y, y);
-    }
 };
 
+/* a step refused the job (its message is in ctx->err): the chunk goes on without it */
 int job_fail(csm_ctx* ctx, csm_map_build_job& job, BatchJob& b, int code)
 {
     job.status = code;
@@ -66,62 +48,30 @@ int job_fail(csm_ctx* ctx, csm_map_build_job& job, BatchJob& b, int code)
     return code;
 }
 
-/* the checks and the node table of map_build (grid_map_builder.cpp:583-612) */
+/* the checks and the node table, then the planner's bound on the cells */
 void prepare_job(csm_ctx* ctx, csm_map_build_job& job, const csm_map_builder_params* prm, BatchJob& b)
 {
-    const csm_map_shape& shape = job.shape;
-    if (!job.nodes || job.n_nodes < 1 || !(shape.resolution > 0.0) || shape.log2_block_size < 0 ||
-        shape.log2_block_size > 12) {
-        job_fail(ctx, job, b, fail(ctx, CSM_EINVAL, "map build: bad arguments"));
+    b.map_id = job.map_id;
+    b.shape = &job.shape;
+    b.map_pose = job.global_map_pose;
+    b.nodes = job.nodes;
+    b.n_nodes = job.n_nodes;
+    if (int rc = map_node_table(ctx, prm, b)) {
+        job_fail(ctx, job, b, rc);
         return;
     }
-    b.n_nodes = job.n_nodes;
-    b.table.resize((size_t)job.n_nodes);
-    long long n_beams_ll = 0;
-    double reach = 0.0;
-    for (int k = 0; k < job.n_nodes; ++k) {
-        const csm_scan_node& nd = job.nodes[k];
-        if (!nd.scan.angles || !nd.scan.ranges || nd.scan.n_points < 0) {
-            job_fail(ctx, job, b, fail(ctx, CSM_EINVAL, "scan node %d has no scan", k));
-            return;
-        }
-        double global_sensor[3], local_sensor[3];
-        csm_host_compound(nd.global_pose, nd.scan.relative_sensor_pose, global_sensor);
-        csm_host_inverse_compound(job.global_map_pose, global_sensor, local_sensor);
-        MapNode& t = b.table[k];
-        t.x = local_sensor[0];
-        t.y = local_sensor[1];
-        t.theta = local_sensor[2];
-        t.min_range = std::max(prm->usable_range_min, nd.min_range);
-        t.max_range = std::min(prm->usable_range_max, nd.max_range);
-        t.beam_base = (int32_t)n_beams_ll;
-        t.n_beams = nd.scan.n_points;
-        t.sx = t.sy = 0;
-        n_beams_ll += nd.scan.n_points;
-        for (int i = 0; i < nd.scan.n_points; ++i) {
-            const double r = nd.scan.ranges[i];
-            b.usable += !(r >= t.max_range || r <= t.min_range);
-        }
+    /* csm_hip.h: every hit point lies within `reach` of its sensor */
+    const double big = std::numeric_limits<double>::max();
+    double reach = 0.0, lo_x = big, lo_y = big, hi_x = -big, hi_y = -big;
+    for (const MapNode& t : b.table) {
         if (t.max_range > t.min_range)
             reach = std::max(reach, t.max_range);
-    }
-    if (n_beams_ll > (1ll << 24)) {
-        job_fail(ctx, job, b, fail(ctx, CSM_EINVAL, "%lld beams in one map build", n_beams_ll));
-        return;
-    }
-    b.n_beams = (int)n_beams_ll;
-    b.min_x = b.min_y = std::numeric_limits<double>::max();
-    b.max_x = b.max_y = std::numeric_limits<double>::min();   /* as the reference: smallest positive */
-    double lo_x = b.min_x, lo_y = b.min_y, hi_x = -b.min_x, hi_y = -b.min_x;
-    for (const MapNode& t : b.table) {
-        b.add_point(t.x, t.y);
         lo_x = std::min(lo_x, t.x);
         lo_y = std::min(lo_y, t.y);
         hi_x = std::max(hi_x, t.x);
         hi_y = std::max(hi_y, t.y);
     }
-    /* the planner's bound on the cells (csm_hip.h): every hit point lies within `reach` of its sensor */
-    const double block = (double)(1 << shape.log2_block_size), res = shape.resolution;
+    const double block = (double)(1 << job.shape.log2_block_size), res = job.shape.resolution;
     const double cols = std::ceil((hi_x - lo_x + 2.0 * reach + 2.0 * res) / res) + 2.0 + 2.0 * block;
     const double rows = std::ceil((hi_y - lo_y + 2.0 * reach + 2.0 * res) / res) + 2.0 + 2.0 * block;
     const double cells = rows * cols;
@@ -135,9 +85,7 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
     const auto t0 = std::chrono::steady_clock::now();
     const int scale = prm->subpixel_scale;
     int rc = 0;
-    uint32_t unc_cap = kMapUncCap;
-    if (ctx->tune.map_unc_cap > 0)          /* csm_config.map_uncertain_cap: tests of the overflow path */
-        unc_cap = (uint32_t)std::min<long>(ctx->tune.map_unc_cap, kMapUncCap);
+    const uint32_t unc_cap = map_unc_cap(ctx);
 
     /* ---- the chunk's scratch that does not depend on the cell counts ---- */
     size_t n_rays_all = 0, n_nodes_all = 0, n_unc_words = 0, list_words_all = 0;
@@ -151,9 +99,6 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
         n_nodes_all += (size_t)b.n_nodes;
         n_unc_words += std::min<size_t>(unc_cap, (size_t)std::max(b.n_beams, 1));
         list_words_all += (size_t)map_list_words(b.n_beams);
-        b.device_projection = b.n_beams > 0 && !ctx->tune.map_host_projection;
-        for (int k = 0; k < 4; ++k)
-            b.box[k] = k < 2 ? 0x7fffffff : -0x7fffffff - 1;
     }
     if ((rc = ensure(ctx, ctx->m_rays, n_rays_all * sizeof(MapRay) + n_nodes_all * (sizeof(MapNode) + 16) + 64))) return rc;
     if ((rc = ensure(ctx, ctx->m_recs, n_rays_all * sizeof(MapRayRec)))) return rc;
@@ -268,24 +213,14 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
                 binfo->scan_bytes_uploaded += (int64_t)(stage.size() * sizeof(double));
         }
     }
-    /* each map under the single call's rules: too many beams on cell edges, or a box that may be
-     * degenerate, and the map is projected on the host; the others' uncertain beams are listed */
+    /* each map under the single call's rules: projected on the host, or its uncertain beams listed */
     std::vector<std::vector<uint32_t>> unc_lists((size_t)n);
     bool any_unc = false;
     for (int j = 0; j < n; ++j) {
         BatchJob& b = *chunk[j];
         if (!b.device_projection)
             continue;
-        const int32_t* got = boxes.data() + (size_t)j * 8;
-        b.n_unc = (uint32_t)got[4];
-        b.spread_known = ((uint32_t)got[5] & 3u) == 3u;
-        if (b.n_unc > unc_cap || !b.spread_known) {
-            b.device_projection = false;
-            b.n_unc = 0;
-            continue;
-        }
-        for (int k = 0; k < 4; ++k)
-            b.box[k] = got[k];
+        map_take_projection(b, boxes.data() + (size_t)j * 8, unc_cap);
         if (b.n_unc) {
             unc_lists[j].resize(b.n_unc);
             HIP_TRY(ctx, hipMemcpyAsync(unc_lists[j].data(), d_unc_list + b.unc0, (size_t)b.n_unc * 4,
@@ -299,94 +234,18 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
     bool uploads = false;
     for (int j = 0; j < n; ++j) {
         BatchJob& b = *chunk[j];
-        const csm_scan_node* nodes = jobs[b.index].nodes;
-        if (b.device_projection && b.n_unc) {
-            /* the beams the device could not certify: exactly as the reference, and patched in */
-            std::vector<MapRay>& exact = patches[j];
-            exact.resize(b.n_unc);
-            for (uint32_t u = 0; u < b.n_unc; ++u) {
-                const uint32_t beam = unc_lists[j][u];
-                int k = 0;
-                while (k + 1 < b.n_nodes && b.table[k + 1].beam_base <= (int32_t)beam)
-                    ++k;
-                const int i = (int)beam - b.table[k].beam_base;
-                const double r = nodes[k].scan.ranges[i];
-                MapRay& ray = exact[u];
-                ray.hx = b.table[k].x + r * std::cos(b.table[k].theta + nodes[k].scan.angles[i]);
-                ray.hy = b.table[k].y + r * std::sin(b.table[k].theta + nodes[k].scan.angles[i]);
-                ray.node = k;
-                ray.usable = 1;
-                b.add_point(ray.hx, ray.hy);
-                HIP_TRY(ctx, hipMemcpyAsync(d_rays + b.ray0 + beam, &ray, sizeof(ray), hipMemcpyHostToDevice,
-                                            ctx->stream));
-            }
-            uploads = true;
-        }
-        if (!b.device_projection) {
-            /* host projection (ScanData::HitPoint, inc/sensor/sensor_data.hpp:189-203) */
-            std::vector<MapRay>& rays = patches[j];
-            rays.resize((size_t)std::max(b.n_beams, 1));
-            for (int k = 0; k < b.n_nodes; ++k) {
-                const MapNode& t = b.table[k];
-                for (int i = 0; i < t.n_beams; ++i) {
-                    MapRay& ray = rays[(size_t)t.beam_base + i];
-                    ray.hx = ray.hy = 0.0;
-                    ray.node = k;
-                    ray.usable = 0;
-                    const double r = nodes[k].scan.ranges[i];
-                    if (r >= t.max_range || r <= t.min_range)
-                        continue;
-                    ray.hx = t.x + r * std::cos(t.theta + nodes[k].scan.angles[i]);
-                    ray.hy = t.y + r * std::sin(t.theta + nodes[k].scan.angles[i]);
-                    ray.usable = 1;
-                    b.add_point(ray.hx, ray.hy);
-                }
-            }
-            for (int k = 0; k < 4; ++k)
-                b.box[k] = k < 2 ? 0x7fffffff : -0x7fffffff - 1;
-            if (b.n_beams) {
-                HIP_TRY(ctx, hipMemcpyAsync(d_rays + b.ray0, rays.data(), (size_t)b.n_beams * sizeof(MapRay),
-                                            hipMemcpyHostToDevice, ctx->stream));
-                uploads = true;
-            }
-            b.spread_known = false;
-            if (binfo)
-                ++binfo->host_projection_jobs;
-        }
+        if ((rc = map_patch_rays(ctx, b, unc_lists[j].data(), d_rays + b.ray0, patches[j], uploads))) return rc;
+        if (!b.device_projection && binfo)
+            ++binfo->host_projection_jobs;
     }
     if (uploads)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     patches.clear();
 
     /* ---- resize every map on the host; a refused job leaves the chunk here ---- */
-    for (int j = 0; j < n; ++j) {
-        BatchJob& b = *chunk[j];
-        csm_map_build_job& job = jobs[b.index];
-        const double res = job.shape.resolution, scaled_res = res / scale;
-        auto to_index = [res](double p, double off) { return static_cast<int>(std::floor((p - off) / res)); };
-        /* Assert(min < max) of Resize: the host-side points decide unless the certified
-         * beams are known to spread in both axes */
-        if (!b.spread_known && (!(b.min_x < b.max_x) || !(b.min_y < b.max_y))) {
-            job_fail(ctx, job, b, fail(ctx, CSM_EINVAL, "empty bounding box (the reference asserts)"));
-            continue;
-        }
-        if (b.min_x <= b.max_x) {               /* points the host holds as doubles (always: the sensors) */
-            b.box[0] = std::min(b.box[0], to_index(b.min_x - res, job.shape.offset_x));
-            b.box[1] = std::min(b.box[1], to_index(b.min_y - res, job.shape.offset_y));
-            b.box[2] = std::max(b.box[2], to_index(b.max_x + res, job.shape.offset_x));
-            b.box[3] = std::max(b.box[3], to_index(b.max_y + res, job.shape.offset_y));
-        }
-        b.next = job.shape;
-        if (csm_host_map_resize(&b.next, b.box, 0, b.shift) != CSM_OK) {
-            job_fail(ctx, job, b, fail(ctx, CSM_EINVAL, "resized map is out of range"));
-            continue;
-        }
-        for (MapNode& t : b.table) {
-            t.sx = static_cast<int>(std::floor((t.x - b.next.offset_x) / scaled_res));
-            t.sy = static_cast<int>(std::floor((t.y - b.next.offset_y) / scaled_res));
-        }
-        b.n_cells = (size_t)b.next.rows * b.next.cols;
-    }
+    for (int j = 0; j < n; ++j)
+        if ((rc = map_resize(ctx, *chunk[j], scale)))
+            job_fail(ctx, jobs[chunk[j]->index], *chunk[j], rc);
 
     if ((rc = map_ensure_tables(ctx, prm))) return rc;
     uint16_t* d_lut = reinterpret_cast<uint16_t*>(ctx->m_lut.p);
@@ -400,64 +259,15 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
         ctx->m_batch_attr = true;
     }
 
-    /* ---- per map: the carried allocation and the destination grid, as map_build ---- */
+    /* ---- per map: the carried allocation (it waits in the job's own buffer: many are alive at once)
+     * and the destination grid; at most one synchronise for the chunk ---- */
     size_t n_cells_all = 0;
     bool synced = false;
     for (int j = 0; j < n; ++j) {
         BatchJob& b = *chunk[j];
         if (!b.live)
             continue;
-        csm_map_build_job& job = jobs[b.index];
-        const int lb = job.shape.log2_block_size;
-        if (DeviceGrid* old = find_grid(ctx, job.map_id)) {
-            if (!old->levels.empty() && old->rows == job.shape.rows && old->cols == job.shape.cols) {
-                if (old->alloc_derived || old->alloc_log2 != lb) {
-                    old->alloc_stale |= old->alloc_log2 != lb || !old->alloc_derived;
-                    old->alloc_derived = true;
-                    old->alloc_log2 = lb;
-                }
-                if ((rc = ensure_allocation(ctx, *old))) return rc;
-                b.has_carried = true;
-                b.carried_brows = (old->rows + (1 << lb) - 1) >> lb;
-                b.carried_bcols = old->alloc_bcols;
-            }
-            std::swap(b.carried, old->alloc);   /* b.carried was empty: the grid's bitmap is built anew below */
-            old->alloc_derived = true;
-            old->alloc_stale = true;
-        }
-        const int rows = b.next.rows, cols = b.next.cols;
-        const int pitch = (cols + 7) & ~7;
-        const size_t bytes = (size_t)rows * pitch * 2;
-        b.dst = find_grid(ctx, job.map_id);
-        if (!b.dst || b.dst->levels.empty() || !b.dst->levels[0].owned() || b.dst->levels[0].own.cap < bytes) {
-            if (!synced)
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            synced = true;
-            b.fresh = take_grid(ctx, job.map_id);
-            b.dst = &b.fresh;
-            Level base;
-            if ((rc = grow(ctx, base.own, bytes + bytes / 2, bytes + bytes / 2, false))) return rc;
-            base.cells = base.own.as<uint16_t>();
-            b.fresh.levels.push_back(std::move(base));
-        }
-        DeviceGrid& g = *b.dst;
-        for (size_t i = 1; i < g.levels.size(); ++i) {
-            if (g.levels[i].owned())
-                g.levels[i].stale = true;
-            else
-                g.levels[i].cells = g.levels[0].cells;     /* an alias of the base (window 1) */
-        }
-        if (!g.phase.empty() && !synced) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            synced = true;
-        }
-        base_changed(g);
-        g.xg_stale = true;         /* the pair-row copy follows the base */
-        g.rows = rows;
-        g.cols = cols;
-        g.pitch = pitch;
-        g.known_r0 = 0;
-        g.known_c0 = 0;
+        if ((rc = map_claim_grid(ctx, b, b.carried, synced))) return rc;
         b.cell0 = n_cells_all;
         n_cells_all += b.n_cells;
     }
@@ -483,37 +293,21 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
         if (!b.live)
             continue;
         ++n_live;
-        const csm_map_build_job& job = jobs[b.index];
-        DeviceGrid& g = *b.dst;
         MapJob& mj = h_jobs[j];
         mj.rays = d_rays + b.ray0;
         mj.nodes = d_nodes + b.node0;
         mj.recs = reinterpret_cast<MapRayRec*>(ctx->m_recs.p) + b.ray0;
-        mj.n_rays = b.n_beams;                  /* a ray's number = its beam's place in ITS map's update order */
-        mj.off_x = b.next.offset_x;
-        mj.off_y = b.next.offset_y;
-        mj.res = job.shape.resolution;
-        mj.scaled_res = mj.res / scale;
-        mj.scale = scale;
-        mj.rows = g.rows;
-        mj.cols = g.cols;
-        mj.pitch = g.pitch;
         mj.n_hit = d_cell + 2 * b.cell0;        /* n_hit and n_miss of all maps first (one memset), then seg */
         mj.n_miss = mj.n_hit + b.n_cells;
         mj.seg = d_cell + 2 * n_cells_all + b.cell0;
         mj.lists = reinterpret_cast<uint32_t*>(ctx->m_lists.p) + b.list0;
-        mj.hit_cells = mj.lists + 10 * (size_t)b.n_beams + 16;
-        mj.counters = d_counters + (size_t)j * kMapCounters;
-        mj.lut_hit = d_lut;
-        mj.lut_miss = d_lut + 65536;
-        mj.cells = g.levels[0].cells;
-        mj.keep_cells = 0;
+        map_fill_job(b, scale, d_lut, mj);      /* ray numbers, cell ids and slots are local to the map */
         if (b.n_beams) {
             ray_blocks += (uint32_t)ceil_div(b.n_beams, 256);
             cell_blocks += (uint32_t)((b.n_cells + 255) / 256);
             groups += (uint32_t)ceil_div(b.n_beams, kMapGroup);
         }
-        apply_blocks += (uint32_t)(((size_t)g.rows * g.pitch + 255) / 256);
+        apply_blocks += (uint32_t)(((size_t)mj.rows * mj.pitch + 255) / 256);
         usable_all += b.usable;
     }
     {
@@ -558,16 +352,8 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
                                    tab, (const uint16_t*)d_lut);
             }
             HIP_TRY(ctx, hipGetLastError());
-            for (int j = 0; j < n; ++j) {
-                BatchJob& b = *chunk[j];
-                if (!b.live)
-                    continue;
-                const int lb = jobs[b.index].shape.log2_block_size;
-                if ((rc = build_allocation(ctx, *b.dst, lb, b.has_carried ? b.carried.as<uint8_t>() : nullptr,
-                                           b.carried_brows, b.carried_bcols, b.shift[0] / (1 << lb),
-                                           b.shift[1] / (1 << lb))))
-                    return rc;
-            }
+            for (int j = 0; j < n; ++j)
+                if (chunk[j]->live && (rc = map_carry_allocation(ctx, *chunk[j], chunk[j]->carried))) return rc;
         }
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipEventRecord(ctx->m_ev[1], ctx->stream));
@@ -588,36 +374,13 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
         if (!b.live)
             continue;
         csm_map_build_job& job = jobs[b.index];
-        const unsigned long long* c = counters.data() + (size_t)j * kMapCounters;
-        if (c[kMapError]) {
-            ctx->grids.erase(job.map_id);       /* the cells may be half updated: drop the map */
-            job_fail(ctx, job, b, fail(ctx, CSM_EINVAL, "a ray leaves the resized map (flags %llu): the reference asserts",
-                                       c[kMapError]));
-            b.fresh = DeviceGrid();
+        if ((rc = map_finish(ctx, b, counters.data() + (size_t)j * kMapCounters, &job.info))) {
+            job_fail(ctx, job, b, rc);
             continue;
         }
-        DeviceGrid& g = *b.dst;
-        g.known_r0 = c[kMapKnownRow] == ~0ull ? g.rows : (int)c[kMapKnownRow];
-        g.known_c0 = c[kMapKnownCol] == ~0ull ? g.cols : (int)c[kMapKnownCol];
-        job.shape.rows = g.rows;
-        job.shape.cols = g.cols;
-        job.shape.offset_x = b.next.offset_x;
-        job.shape.offset_y = b.next.offset_y;
-        csm_map_build_info& info = job.info;
-        info.rays = b.usable;
-        info.cell_updates = info.saturated_reads = 0;
-        for (int k = 0; k < kMapStripes; ++k) {
-            info.cell_updates += (int64_t)c[kMapStripedUpdates + k];
-            info.saturated_reads += (int64_t)c[kMapStripedSaturated + k];
-        }
-        info.first_known_row = g.known_r0;
-        info.first_known_col = g.known_c0;
-        info.device_projection = b.device_projection ? 1 : 0;
-        info.host_us = host_us / std::max(n_live, 1);
-        info.device_us = dev_ms * 1e3 / std::max(n_live, 1);
+        job.info.host_us = host_us / std::max(n_live, 1);
+        job.info.device_us = dev_ms * 1e3 / std::max(n_live, 1);
         job.status = CSM_OK;
-        if (b.dst == &b.fresh)
-            ctx->grids[job.map_id] = std::move(b.fresh);
     }
     return CSM_OK;
 }

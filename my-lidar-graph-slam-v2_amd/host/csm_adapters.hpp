@@ -124,6 +124,15 @@ struct ScanMatchingSummary {
 using CostCallback = void (*)(const ScanMatchingQuery&, const RobotPose2D<double>&, double*,
                               double*);
 
+/* What the map update reads of a ScanNode (inc/mapping/pose_graph.hpp) and its
+ * ScanData (inc/sensor/sensor_data.hpp:63-185) */
+struct ScanNodeView {
+    int mNodeId = 0;
+    RobotPose2D<double> mGlobalPose { 0.0, 0.0, 0.0 };
+    ScanDataView mScanData;
+    double mMinRange = 0.0, mMaxRange = 0.0;
+};
+
 namespace detail {
 /* which revision of which map id a context holds */
 using RevisionMap = std::map<std::uint64_t, std::uint64_t>;
@@ -152,6 +161,18 @@ inline csm_scan ToScan(const ScanDataView& s)
     out.relative_sensor_pose[0] = s.mRelativeSensorPose.mX;
     out.relative_sensor_pose[1] = s.mRelativeSensorPose.mY;
     out.relative_sensor_pose[2] = s.mRelativeSensorPose.mTheta;
+    return out;
+}
+
+inline csm_scan_node ToScanNode(const ScanNodeView& n)
+{
+    csm_scan_node out {};
+    out.global_pose[0] = n.mGlobalPose.mX;
+    out.global_pose[1] = n.mGlobalPose.mY;
+    out.global_pose[2] = n.mGlobalPose.mTheta;
+    out.scan = ToScan(n.mScanData);
+    out.min_range = n.mMinRange;
+    out.max_range = n.mMaxRange;
     return out;
 }
 
@@ -1035,15 +1056,6 @@ private:
     detail::CtxPtr mCtx;
 };
 
-/* What the map update reads of a ScanNode (inc/mapping/pose_graph.hpp) and its
- * ScanData (inc/sensor/sensor_data.hpp:63-185) */
-struct ScanNodeView {
-    int mNodeId = 0;
-    RobotPose2D<double> mGlobalPose { 0.0, 0.0, 0.0 };
-    ScanDataView mScanData;
-    double mMinRange = 0.0, mMaxRange = 0.0;
-};
-
 /* The latest-map half of GridMapBuilder (src/mapping/grid_map_builder.cpp): the
  * map the frontend matches every new scan against is rebuilt from the last
  * mNumOfScansForLatestMap scans on every call (UpdateLatestMap, :497-527).
@@ -1096,14 +1108,8 @@ public:
                                std::size_t numOfNodes)
     {
         std::vector<csm_scan_node> flat(numOfNodes);
-        for (std::size_t i = 0; i < numOfNodes; ++i) {
-            flat[i].global_pose[0] = nodes[i].mGlobalPose.mX;
-            flat[i].global_pose[1] = nodes[i].mGlobalPose.mY;
-            flat[i].global_pose[2] = nodes[i].mGlobalPose.mTheta;
-            flat[i].scan = detail::ToScan(nodes[i].mScanData);
-            flat[i].min_range = nodes[i].mMinRange;
-            flat[i].max_range = nodes[i].mMaxRange;
-        }
+        for (std::size_t i = 0; i < numOfNodes; ++i)
+            flat[i] = detail::ToScanNode(nodes[i]);
         const double pose[3] = { globalMapPose.mX, globalMapPose.mY, globalMapPose.mTheta };
         CSM_ASSERT_OK(this->mCtx, csm_construct_map_from_scans(
                                       this->mCtx, this->mLatestMap.mId, &this->mShape, pose, flat.data(),
@@ -1142,13 +1148,7 @@ public:
                          static_cast<unsigned long long>(localMapId), __FILE__, __LINE__);
             std::abort();
         }
-        csm_scan_node flat {};
-        flat.global_pose[0] = latestScanNode.mGlobalPose.mX;
-        flat.global_pose[1] = latestScanNode.mGlobalPose.mY;
-        flat.global_pose[2] = latestScanNode.mGlobalPose.mTheta;
-        flat.scan = detail::ToScan(latestScanNode.mScanData);
-        flat.min_range = latestScanNode.mMinRange;
-        flat.max_range = latestScanNode.mMaxRange;
+        const csm_scan_node flat = detail::ToScanNode(latestScanNode);
         const double pose[3] = { globalMapPose.mX, globalMapPose.mY, globalMapPose.mTheta };
         CSM_ASSERT_OK(this->mCtx, csm_update_map_with_scan(this->mCtx, localMapId, &it->second, pose, &flat,
                                                            &this->mParams, &this->mInfo));
@@ -1176,15 +1176,8 @@ public:
             if (this->mLocalShapes.find(localMapIds[m]) == this->mLocalShapes.end())
                 this->CreateLocalMap(localMapIds[m]);
             flat[m].resize(nodeSpans[m].second);
-            for (std::size_t i = 0; i < nodeSpans[m].second; ++i) {
-                const ScanNodeView& node = nodeSpans[m].first[i];
-                flat[m][i].global_pose[0] = node.mGlobalPose.mX;
-                flat[m][i].global_pose[1] = node.mGlobalPose.mY;
-                flat[m][i].global_pose[2] = node.mGlobalPose.mTheta;
-                flat[m][i].scan = detail::ToScan(node.mScanData);
-                flat[m][i].min_range = node.mMinRange;
-                flat[m][i].max_range = node.mMaxRange;
-            }
+            for (std::size_t i = 0; i < nodeSpans[m].second; ++i)
+                flat[m][i] = detail::ToScanNode(nodeSpans[m].first[i]);
             csm_map_build_job& job = jobs[m];
             job = csm_map_build_job {};
             job.map_id = localMapIds[m];

@@ -101,6 +101,17 @@ def build(names=None):
     return out
 
 
+# the cases that take two csm_update_map_with_scan calls after their build (test_updates_onto_batch_built_maps)
+UPDATED = ("tiny", "odd", "blocks_of_4")
+
+
+def update_nodes(case):
+    """The nodes of the two updates: the map's own first node (its scan is in the map, so it fits and
+    nothing is resized), then that node 3 m further along x (Expand must grow the map)."""
+    nd = case["nodes"][0]
+    return [nd, dict(nd, pose=(nd["pose"][0] + 3.0, nd["pose"][1], nd["pose"][2]))]
+
+
 def edge_beams(case, subpixel=100):
     """Usable beams of the case whose hit point, computed as the builder's host path computes it, lies
     on a cell edge of the map's frame before the call (at the cell or the sub-pixel resolution) or

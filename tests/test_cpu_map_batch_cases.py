@@ -49,6 +49,24 @@ def test_table_spans_the_sizes_the_schedule_must_balance(oracle):
     assert min(rays.values()) == 0 and sorted(rays.values())[2] == 1 and max(rays.values()) > 20000
 
 
+@pytest.mark.parametrize("name", MB.UPDATED)
+def test_update_nodes_fit_then_grow(oracle, name):
+    """The reference accepts both updates; the first leaves the frame as it is, the second grows it
+    (tiny by 16 rows at its far side, odd by 32 rows and columns and blocks_of_4 by 12 columns at the near one)."""
+    case = CASES[name]
+    shape, grid, _ = oracle.construct_map(case["shape"], case["map_pose"], case["nodes"])
+    own, moved = MB.update_nodes(case)
+    shape1, grid1, stats1 = oracle.update_map(shape, grid, case["map_pose"], own)
+    assert shape1 == shape and (stats1["row_min"], stats1["col_min"]) == (0, 0)
+    assert stats1["rays"] > 0 and stats1["end_missing"] == 0
+    shape2, grid2, stats2 = oracle.update_map(shape1, grid1, case["map_pose"], moved)
+    assert shape2["rows"] * shape2["cols"] > shape["rows"] * shape["cols"]
+    assert grid2.shape == (shape2["rows"], shape2["cols"])
+    assert stats2["rays"] > 0 and stats2["end_missing"] == 0
+    # towards negative indices, which shifts the carried block allocation, in two of the three
+    assert ((stats2["row_min"], stats2["col_min"]) != (0, 0)) == (name != "tiny")
+
+
 def test_shared_pair_holds_the_same_arrays():
     a, b = CASES["shared_a"], CASES["shared_b"]
     assert a["map_pose"] != b["map_pose"]

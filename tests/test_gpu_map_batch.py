@@ -334,3 +334,85 @@ def test_tables_follow_the_settings(gpu_ctx, oracle, cases):
         want = {n: oracle.construct_map(c["shape"], c["map_pose"], c["nodes"], **okw) for n, c in pick}
         _check_all(gpu_ctx, pick, want, results)
     _release(gpu_ctx, 2)
+
+
+def _last_error(ctx):
+    return ctx.lib.csm_last_error(ctx._ctx).decode()
+
+
+def test_refusal_messages_are_the_single_call_s(cases):
+    """A job refused in the middle of a batch leaves the message (and the status) the single call gives
+    for it, whichever step refuses it: the node table (no nodes), the resize (flat box, no box, too
+    large). With two refused jobs the message is the last one's in job order, as after the loop."""
+    good = dict(cases)
+    refused = _refused_cases() + [("no_nodes", dict(good["tiny"], nodes=[]))]
+    a, b = api.Context(0), api.Context(0)
+    try:
+        single = {}
+        for name, c in refused:
+            with pytest.raises(api.CsmError) as err:
+                a.construct_map_from_scans(BASE, c["shape"], c["map_pose"], c["nodes"])
+            single[name] = (err.value.code, str(err.value).split(": ", 1)[1])
+            assert single[name][1], name
+        assert len({text for _, text in single.values()}) >= 3      # the messages tell the steps apart
+        for name, c in refused:
+            results, _ = b.construct_maps_from_scans(_jobs([("tiny", good["tiny"]), (name, c),
+                                                            ("one_usable", good["one_usable"])]))
+            assert [r[2] for r in results] == [0, single[name][0], 0], name
+            assert _last_error(b) == single[name][1], name
+        both = dict(refused)
+        results, _ = b.construct_maps_from_scans(_jobs([("flat_box", both["flat_box"]), ("tiny", good["tiny"]),
+                                                        ("too_large", both["too_large"])]))
+        assert [r[2] for r in results] == [single["flat_box"][0], 0, single["too_large"][0]]
+        assert _last_error(b) == single["too_large"][1] != single["flat_box"][1]
+    finally:
+        a.close()
+        b.close()
+
+
+def test_updates_onto_batch_built_maps(oracle, cases):
+    """Context A builds three maps with the loop of single calls, context B with one batch call; then
+    every map takes two csm_update_map_with_scan calls, one that fits and one that makes Expand grow
+    the map (tests/map_batch_cases.py, update_nodes). After each step the two contexts hold the same
+    shape, cells, first known row / column and counters, the cells are the oracle's, and at the end
+    the cost / covariance, which reads the block allocation the updates carried, is bit-equal."""
+    picked = [(n, c) for n, c in cases if n in MB.UPDATED]
+    assert len(picked) == len(MB.UPDATED)
+    keys = ("rays", "cell_updates", "saturated_reads", "first_known_row", "first_known_col", "device_projection")
+    a, b = api.Context(0), api.Context(0)
+    try:
+        jobs = _jobs(picked)
+        singles = [a.construct_map_from_scans(j["map_id"], j["shape"], j["map_pose"], j["nodes"]) for j in jobs]
+        results, _ = b.construct_maps_from_scans(jobs)
+        shapes, grids = [], []
+        for j, (shape, _), (shape_b, _, status) in zip(jobs, singles, results):
+            assert status == 0 and shape_b == shape
+            shapes.append(shape)
+            grids.append(a.download_level(j["map_id"], 0))
+            assert np.array_equal(grids[-1], b.download_level(j["map_id"], 0))
+        for step in range(2):
+            for i, (j, (name, case)) in enumerate(zip(jobs, picked)):
+                node = MB.update_nodes(case)[step]
+                want_shape, want_grid, stats = oracle.update_map(shapes[i], grids[i], case["map_pose"], node)
+                shape_a, info_a = a.update_map_with_scan(j["map_id"], shapes[i], case["map_pose"], node)
+                shape_b, info_b = b.update_map_with_scan(j["map_id"], shapes[i], case["map_pose"], node)
+                assert shape_a == shape_b == want_shape, (name, step)
+                assert (shape_a != shapes[i]) == (step == 1), (name, step)
+                for key in keys:
+                    assert info_a[key] == info_b[key], (name, step, key)
+                assert (info_a["rays"], info_a["cell_updates"], info_a["saturated_reads"]) == \
+                    (stats["rays"], stats["updates"], stats["oob_reads"]), (name, step)
+                got_a, got_b = a.download_level(j["map_id"], 0), b.download_level(j["map_id"], 0)
+                assert np.array_equal(got_a, want_grid) and np.array_equal(got_b, want_grid), (name, step)
+                assert a.debug_grid_known(j["map_id"]) == b.debug_grid_known(j["map_id"]), (name, step)
+                shapes[i], grids[i] = want_shape, want_grid
+        queries = _queries(picked, shapes)
+        poses = [q["init_pose"] for q in queries]
+        for ca, cb in zip(a.cost_covariance_batch(queries, poses, 1e4), b.cost_covariance_batch(queries, poses, 1e4)):
+            assert np.isfinite(ca["normalized_cost"])
+            assert np.array_equal(ca["normalized_cost"], cb["normalized_cost"], equal_nan=True)
+            assert np.array_equal(ca["covariance"], cb["covariance"], equal_nan=True)
+            assert np.array_equal(ca["hessian"], cb["hessian"], equal_nan=True)
+    finally:
+        a.close()
+        b.close()
