@@ -1029,7 +1029,8 @@ typedef struct {
  *  - A map with more uncertain beams than the context's cap, or whose certified beams are not known to
  *    spread, takes the host projection on its own; the rest of its chunk stays on the device.
  * Limit: the hits of one cell are ranked by brute force (quadratic in the hits per cell), as in the
- * single call: a global map of thousands of scans in one job is slow. `batch` and `info` may be null.
+ * single call: a global map of thousands of scans in one job is slow here. That map is
+ * csm_construct_global_map's (below), which sorts long hit lists. `batch` and `info` may be null.
  * A device or allocation failure (CSM_EIO, CSM_ENOMEM) ends the call: the jobs not yet finished get
  * that status, their maps may have been dropped, and `info` holds what had run. */
 int  csm_construct_maps_from_scans(csm_ctx* ctx, csm_map_build_job* jobs, int32_t n_jobs,
@@ -1047,6 +1048,74 @@ int  csm_construct_maps_from_scans(csm_ctx* ctx, csm_map_build_job* jobs, int32_
 int  csm_host_map_batch_plan(const int64_t* n_beams, const int64_t* n_cells_upper, int32_t n_jobs,
                              int64_t scratch_limit_bytes, int32_t* chunk_of, int64_t* chunk_bytes,
                              int32_t* n_chunks);
+
+/* ---- one map of many scans: the global map ----
+ * LidarGraphSlam::GetGlobalMap -> GridMapBuilder::ConstructGlobalMap (grid_map_builder.cpp:162-184):
+ * ConstructMapFromScans over every scan node of the pose graph, in the frame of the first node. */
+
+typedef struct {
+    int64_t scratch_limit_bytes;  /* 0 = default (1 GiB), as csm_map_batch_params */
+    int32_t rank_direct_max;      /* 0 = default (32). A cell with at most this many hits is ranked as in the
+                                     single call (each hit counts the earlier arrivals); longer lists are sorted */
+    int32_t rank_tile;            /* 0 = default (4096). Entries one workgroup sorts in LDS at a time; a power of
+                                     two >= 4 and <= 16384 (64 KB of LDS). Lists longer than this are sorted tile
+                                     by tile and ranked across tiles */
+} csm_global_map_params;
+
+typedef struct {
+    int32_t parts;                /* launch chains the build was cut into */
+    int32_t max_hits_per_cell;    /* largest hit list of any part */
+    int64_t direct_cells, sorted_cells, tiled_cells;   /* hit cells by rank path, summed over parts */
+    int64_t beams;                /* all beams of all nodes: may exceed 2^24 */
+    double  host_us, device_us;
+} csm_global_map_info;
+
+/* GridMapBuilder::ConstructGlobalMap (grid_map_builder.cpp:162-184). Leaves exactly what
+ * csm_construct_map_from_scans with the same arguments leaves -- the cells of level 0 byte for byte,
+ * `shape`, first known row / column, block allocation, stale levels, dropped phase-major and pair-row
+ * copies, and info's rays, cell_updates and saturated_reads -- for any scratch_limit_bytes,
+ * rank_direct_max and rank_tile, without that call's two limits:
+ *  - The hits of a cell are ranked by a sort once there are more than rank_direct_max of them (the
+ *    single call counts, for every hit, all hits of its cell: quadratic in the revisits).
+ *  - The nodes are cut in order into parts (csm_host_global_map_parts on the beams of the nodes and the
+ *    cells of the resized map) that are cast one after the other onto the same cells: a cell's value
+ *    depends only on its own sequence of hits and misses in ray order, and the parts' sequences
+ *    concatenate. The limit of 2^24 beams holds per part, so per node here; the scratch is one part's.
+ *    The bounding box comes from a pass over all nodes before the one resize; with more than one part
+ *    the hit points are computed again when their part is cast.
+ * Refusals and the dropped map (a ray leaves the resized map) are the single call's; the cap of 2^28
+ * cells per map stays. CSM_EINVAL before anything changes: a negative scratch_limit_bytes or
+ * rank_direct_max, a rank_tile that is not a power of two in 4 .. 16384. `global`, `info` and
+ * `global_info` may be null. info->device_projection is 1 if every part was projected on the device.
+ * scratch_limit_bytes bounds what the planner counts (rays, records, lists, per-cell words, counters),
+ * not all memory of a part: the entry also stages a part's angles and ranges on the device (16 bytes per
+ * beam of the largest part) and on the host, and a part projected on the host holds its rays there once.
+ * host_us (both infos): the host steps up to the first launch of the cast phase, plus, when the parts are
+ * projected again, each part's projection with its read-back and patches; device_us: the span of the cast
+ * phase between two events, less that. */
+int  csm_construct_global_map(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
+                              const double global_map_pose[3], const csm_scan_node* nodes, int32_t n_nodes,
+                              const csm_map_builder_params* params, const csm_global_map_params* global,
+                              csm_map_build_info* info, csm_global_map_info* global_info);
+
+/* Host only, no GPU: the cut of csm_construct_global_map. Node k has n_beams[k] beams, the resized map
+ * n_cells cells. Parts are runs of consecutive nodes, in order. A part's scratch is what
+ * csm_host_map_batch_plan counts for ONE job with the part's beams and n_cells cells (the per-cell words
+ * of the whole map are cleared and used again by every part). A part is closed before the node that
+ * would take it past scratch_limit_bytes (0 = 1 GiB) or past 2^24 beams; a node that alone exceeds the
+ * limit gets a part of its own. part_of[n_nodes]: the part of each node; part_bytes[n_nodes]: the first
+ * *n_parts entries hold the parts' scratch. CSM_EINVAL: null pointers, n_nodes < 1, a negative limit,
+ * an n_beams[k] outside 0 .. 2^24 or n_cells outside 0 .. 2^28. */
+int  csm_host_global_map_parts(const int64_t* n_beams, int32_t n_nodes, int64_t n_cells,
+                               int64_t scratch_limit_bytes, int32_t* part_of, int64_t* part_bytes,
+                               int32_t* n_parts);
+
+/* Host only. The scan-node poses of GridMapBuilder::ConstructMapFromAllScans (grid_map_builder.cpp:
+ * 698-817, declared and never called): out_global_poses[i] = Compound(local_map_pose, local_poses[i])
+ * (LocalMapNode::mGlobalPose, ScanNode::mLocalPose; csm_host_compound), n triples each. A caller fills
+ * csm_scan_node.global_pose with them, nodes in ascending id, and calls csm_construct_global_map. */
+int  csm_host_global_scan_poses(const double local_map_pose[3], const double* local_poses, int32_t n,
+                                double* out_global_poses);
 
 /* ---- pose-graph optimization: the backend's Optimize step ---- */
 

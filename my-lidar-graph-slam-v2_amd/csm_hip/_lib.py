@@ -112,6 +112,16 @@ class MapBatchInfo(C.Structure):
                 ("host_us", C.c_double), ("device_us", C.c_double)]
 
 
+class GlobalMapParams(C.Structure):
+    _fields_ = [("scratch_limit_bytes", C.c_int64), ("rank_direct_max", C.c_int32), ("rank_tile", C.c_int32)]
+
+
+class GlobalMapInfo(C.Structure):
+    _fields_ = [("parts", C.c_int32), ("max_hits_per_cell", C.c_int32), ("direct_cells", C.c_int64),
+                ("sorted_cells", C.c_int64), ("tiled_cells", C.c_int64), ("beams", C.c_int64),
+                ("host_us", C.c_double), ("device_us", C.c_double)]
+
+
 class GridSearchParams(C.Structure):
     _fields_ = [("range_x", C.c_double), ("range_y", C.c_double), ("range_theta", C.c_double),
                 ("step_x", C.c_double), ("step_y", C.c_double), ("step_theta", C.c_double),
@@ -347,6 +357,12 @@ SIGNATURES = {
     "csm_construct_maps_from_scans": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "csm_host_map_batch_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                           _P(C.c_int32)]),
+    "csm_construct_global_map": (C.c_int, [_ctx, C.c_uint64, _P(MapShape), C.c_void_p, _P(ScanNode), C.c_int32,
+                                           _P(MapBuilderParams), _P(GlobalMapParams), _P(MapBuildInfo),
+                                           _P(GlobalMapInfo)]),
+    "csm_host_global_map_parts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                            _P(C.c_int32)]),
+    "csm_host_global_scan_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "csm_set_block_allocation": (C.c_int, [_ctx, C.c_uint64, C.c_int32, C.c_void_p]),
     "csm_cost_covariance_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, C.c_void_p, C.c_double,
                                             _P(RefineResult)]),

@@ -140,6 +140,34 @@ def host_map_batch_plan(n_beams, n_cells_upper, scratch_limit_bytes=0):
     return [int(c) for c in chunk_of[:nb.size]], [int(b) for b in chunk_bytes[:n_chunks.value]]
 
 
+def host_global_map_parts(n_beams, n_cells, scratch_limit_bytes=0):
+    """csm_host_global_map_parts: how csm_construct_global_map cuts its nodes into parts, given each
+    node's beams and the cells of the resized map. Returns (part of each node, scratch bytes of each
+    part); 0 = the default limit of 1 GiB."""
+    nb = np.ascontiguousarray(n_beams, dtype=np.int64)
+    if nb.ndim != 1:
+        raise ValueError("n_beams must be 1-D")
+    part_of = np.zeros(max(nb.size, 1), np.int32)
+    part_bytes = np.zeros(max(nb.size, 1), np.int64)
+    n_parts = C.c_int32(0)
+    rc = L.load().csm_host_global_map_parts(_ptr(nb), nb.size, int(n_cells), int(scratch_limit_bytes),
+                                            _ptr(part_of), _ptr(part_bytes), C.byref(n_parts))
+    if rc:
+        raise CsmError(rc, "csm_host_global_map_parts")
+    return [int(c) for c in part_of[:nb.size]], [int(b) for b in part_bytes[:n_parts.value]]
+
+
+def host_global_scan_poses(local_map_pose, local_poses):
+    """csm_host_global_scan_poses: Compound(local map pose, each scan node's local pose), as
+    GridMapBuilder::ConstructMapFromAllScans composes them. Returns an (n, 3) array."""
+    lp = np.ascontiguousarray(local_poses, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros_like(lp)
+    rc = L.load().csm_host_global_scan_poses(_ptr(_f64(local_map_pose)), _ptr(lp), lp.shape[0], _ptr(out))
+    if rc:
+        raise CsmError(rc, "csm_host_global_scan_poses")
+    return out
+
+
 def debug_live_bytes():
     """csm_debug_live_bytes: (device, pinned) bytes the library holds, over the whole process."""
     dev, pin = C.c_int64(0), C.c_int64(0)
@@ -920,6 +948,33 @@ class Context:
                              log2_block=sh.log2_block_size),
                         {name: getattr(arr[j].info, name) for name, _ in L.MapBuildInfo._fields_}, status))
         return out, {name: getattr(binfo, name) for name, _ in L.MapBatchInfo._fields_}
+
+    def construct_global_map(self, map_id, shape, map_pose, nodes, usable_range_min=0.01, usable_range_max=20.0,
+                             prob_hit=0.62, prob_miss=0.46, subpixel_scale=100, scratch_limit_bytes=0,
+                             rank_direct_max=0, rank_tile=0):
+        """csm_construct_global_map (GridMapBuilder::ConstructGlobalMap, grid_map_builder.cpp:162-184):
+        construct_map_from_scans for one map of many scans, cast in parts of at most
+        scratch_limit_bytes of scratch, long hit lists sorted (rank_direct_max, rank_tile; 0 = the
+        defaults). Returns (new shape dict, info dict, global info dict)."""
+        sh = L.MapShape(shape["res"], shape["off_x"], shape["off_y"], shape["rows"], shape["cols"],
+                        shape["log2_block"])
+        keep = []
+        arr = _scan_nodes(nodes, _f64, keep)
+        prm = L.MapBuilderParams(usable_range_min, usable_range_max, prob_hit, prob_miss, subpixel_scale)
+        gp = L.GlobalMapParams(int(scratch_limit_bytes), int(rank_direct_max), int(rank_tile))
+        info, ginfo = L.MapBuildInfo(), L.GlobalMapInfo()
+        mp = _f64(map_pose)
+        rc = self.lib.csm_construct_global_map(self._ctx, map_id, C.byref(sh), _ptr(mp), arr if nodes else None,
+                                               len(nodes), C.byref(prm), C.byref(gp), C.byref(info),
+                                               C.byref(ginfo))
+        if rc and not self.has_grid(map_id):
+            self.shapes.pop(map_id, None)       # a ray left the resized map: the map was dropped
+        self._check(rc)
+        self.shapes[map_id] = (sh.rows, sh.cols)
+        new_shape = dict(res=sh.resolution, off_x=sh.offset_x, off_y=sh.offset_y, rows=sh.rows,
+                         cols=sh.cols, log2_block=sh.log2_block_size)
+        return (new_shape, {name: getattr(info, name) for name, _ in L.MapBuildInfo._fields_},
+                {name: getattr(ginfo, name) for name, _ in L.GlobalMapInfo._fields_})
 
     def _map_build(self, map_id, shape, map_pose, nodes, keep_cells, usable_range_min, usable_range_max,
                    prob_hit, prob_miss, subpixel_scale):

@@ -249,7 +249,7 @@ struct csm_ctx {
     DevBuf m_rays, m_recs, m_cell, m_lists, m_cnt, m_lut;
     DevBuf m_alloc;                               /* the old map's allocation bitmap during a build */
     double m_lut_hit = -1.0, m_lut_miss = -1.0;   /* probabilities the update tables were built for */
-    bool m_apply_attr = false, m_batch_attr = false;
+    bool m_apply_attr = false, m_batch_attr = false, m_global_attr = false;
     int m_cus = 0;                                /* compute units of the device (the batch's persistent kernel) */
     DevBuf m_btab;                                /* csm_construct_maps_from_scans: job and prefix tables */
     hipEvent_t m_ev[2] = { nullptr, nullptr };    /* device_us of csm_map_build_info */

@@ -1196,6 +1196,36 @@ public:
     }
     const csm_map_batch_info& LastBatchInfo() const { return this->mBatchInfo; }
 
+    /* GridMapBuilder::ConstructGlobalMap (grid_map_builder.cpp:162-184): one map of all scan nodes of
+     * the pose graph (in id order), on the device under globalMapId (csm_construct_global_map: cast in
+     * parts, long hit lists sorted). The map pose is the first node's global pose (:171-172); the map
+     * is fresh, as GridMap{res, patchSize, 1.0, 1.0} at :175. globalMapPose and shape are set;
+     * LocalMap(globalMapId) and CopyLocalMapValues(globalMapId) read the result. */
+    void ConstructGlobalMap(std::uint64_t globalMapId, const ScanNodeView* nodes, std::size_t numOfNodes,
+                            RobotPose2D<double>& globalMapPose, csm_map_shape& shape)
+    {
+        if (nodes == nullptr || numOfNodes == 0) {
+            std::fprintf(stderr, "Assertion failed: !scanNodes.empty() at %s:%d\n", __FILE__, __LINE__);
+            std::abort();
+        }
+        std::vector<csm_scan_node> flat(numOfNodes);
+        for (std::size_t i = 0; i < numOfNodes; ++i)
+            flat[i] = detail::ToScanNode(nodes[i]);
+        globalMapPose = nodes[0].mGlobalPose;
+        const double pose[3] = { globalMapPose.mX, globalMapPose.mY, globalMapPose.mTheta };
+        shape = this->mShape;
+        shape.offset_x = shape.offset_y = 0.0;
+        shape.rows = shape.cols = this->mInitialCells;
+        CSM_ASSERT_OK(this->mCtx, csm_construct_global_map(
+                                      this->mCtx, globalMapId, &shape, pose, flat.data(),
+                                      static_cast<std::int32_t>(numOfNodes), &this->mParams, &this->mGlobalParams,
+                                      &this->mInfo, &this->mGlobalInfo));
+        this->mLocalShapes[globalMapId] = shape;
+    }
+    /* scratch limit and rank settings of ConstructGlobalMap (zeros: the library's defaults) */
+    void SetGlobalMapParams(const csm_global_map_params& params) { this->mGlobalParams = params; }
+    const csm_global_map_info& LastGlobalMapInfo() const { return this->mGlobalInfo; }
+
     /* geometry + id of a local map (cells on the device), e.g. for a LoopDetectionQuery */
     GridMapView LocalMap(std::uint64_t localMapId) const
     {
@@ -1235,6 +1265,8 @@ private:
     csm_map_shape mShape {};
     csm_map_build_info mInfo {};
     csm_map_batch_info mBatchInfo {};
+    csm_global_map_params mGlobalParams {};
+    csm_global_map_info mGlobalInfo {};
     GridMapView mLatestMap;
     int mInitialCells = 0;
     std::map<std::uint64_t, csm_map_shape> mLocalShapes;
