@@ -647,6 +647,99 @@ int  csm_build_likelihood_map(csm_ctx* ctx, uint64_t src_map_id, uint64_t dst_ma
 int  csm_build_likelihood_maps(csm_ctx* ctx, const uint64_t* src_ids, const uint64_t* dst_ids, int32_t n,
                                const csm_likelihood_params* params);
 
+/* ---- free-space check of loop candidates (beyond the reference, whose detectors accept a pose on the
+ * score of the scan's END POINTS alone): every beam of a scan walked from the sensor to its hit, as the map
+ * builder would walk it if it integrated the scan at this pose, and the cells it crosses classified against
+ * the resident map. A pose on the wrong side of a wall scores like the true one; only its rays run through
+ * cells the map knows to be occupied. Read-only: the map is never resized or written.
+ *
+ * Definition (integers only once the hit points are formed). A query's initial_pose is the map-local ROBOT
+ * pose to check (a summary's estimated_pose).
+ *   S = Compound(initial_pose, relative_sensor_pose)                         (csm_host_compound)
+ *   scaledRes = res / subpixel_scale                                         (ScaledGeometry, as the builder)
+ *   sX = floor((S.x - offX) / scaledRes), sY likewise
+ * Beam i is USABLE iff r > usable_range_min && r < usable_range_max (a NaN range is unusable; for finite r
+ * the builder's rule, grid_map_builder.cpp:618-619). For a usable beam
+ *   h  = (S.x + r cos(S.theta + a), S.y + r sin(S.theta + a))                (ScanData::HitPoint)
+ *   H  = (floor((h.x - offX) / res), floor((h.y - offY) / res))              the hit cell
+ *   (eX, eY) = the same expression at scaledRes                              the sub-pixel end
+ *   W  = the cells of BresenhamScaled(sX, sY, eX, eY) (src/bresenham.cpp:58-237) with its / and % read as
+ *        floored division and its remainder. Where the reference is defined (it asserts non-negative
+ *        coordinates) that is its own walk; elsewhere it is the same ray moved by whole cells: with
+ *        b = (floor_div(min(sX, eX), scale), floor_div(min(sY, eY), scale)), W = b + the reference's walk
+ *        of the ray moved by -b * scale, which is non-negative. A move by whole cells changes no
+ *        remainder, so it moves the cells and nothing else. No walk holds a cell twice.
+ *   E  = (floor_div(eX, scale), floor_div(eY, scale)); the MISSED cells M are W without E
+ *        (grid_map_builder.cpp:904-910).
+ * Only cells inside rows x cols of level 0 of the resident map are read and counted. A cell c of M inside
+ * the map, with value v and depth d = max(|c.x - H.x|, |c.y - H.y|), is
+ *   unknown   v == 0
+ *   free      0 < v <= free_max
+ *   blocking  v >= occupied_min and d >  end_tolerance
+ *   near      v >= occupied_min and d <= end_tolerance      (the wall the beam ends on is some cells thick)
+ *   other     anything else
+ * A usable beam is WALKED iff it has a missed cell inside the map or H lies inside; BLOCKED iff it has a
+ * blocking cell. If H lies inside, its value v puts the beam in end_unknown (v == 0), end_free (0 < v <=
+ * free_max), end_occupied (v >= occupied_min) or none of them. Every count is an integer and integer sums do
+ * not depend on the order, so the device equals csm_host_ray_check field for field (host_beams aside).
+ *
+ * 64 bits. CSM_EINVAL keeps |S - off| / res <= 2^20 per axis, usable_range_max / res <= 2^20 and
+ * subpixel_scale <= CSM_RAY_CHECK_MAX_SCALE = 512, so every sub-pixel coordinate lies within (2^21 + 2) * 512
+ * < 2^31 of zero. After the move by -b * scale the four coordinates lie in [0, 2^30). Then, in the closed
+ * form of csm_map.hpp (dx = eX - sX etc.): den = 2 scale dx < 2^40; y0 < 2^21, so n0 = y0 den + (2 (sY %
+ * scale) + 1) dx < 2^61 + 2^40; first + 2 scale j + last < 2^31 + 2^11 (j <= 2^21), so |dy| (..) < 2^61 +
+ * 2^41; and n0 + dy (..) + den < 2^62 + 2^42 < 2^63. */
+#define CSM_RAY_CHECK_MAX_SCALE 512
+typedef struct {
+    double   usable_range_min, usable_range_max;
+    int32_t  subpixel_scale;        /* 1..CSM_RAY_CHECK_MAX_SCALE; the builder's is 100 */
+    int32_t  end_tolerance;         /* cells, >= 0 */
+    uint32_t occupied_min, free_max;   /* raw cell values, 0 < free_max < occupied_min <= 65535 */
+    int64_t  scratch_limit_bytes;   /* 0 = default (1 GiB). A batch is cut into chunks of consecutive queries: a
+                                       query of n beams counts 36 n + 256 bytes, and a chunk is closed before
+                                       the query that would take it past the limit (a query that alone
+                                       exceeds it gets a chunk of its own) */
+} csm_ray_check_params;
+
+typedef struct {
+    int32_t beams;                  /* n_points */
+    int32_t usable, walked, blocked;
+    int32_t end_inside, end_occupied, end_free, end_unknown;
+    int64_t cells;                  /* missed cells inside the map, all classes */
+    int64_t cells_free, cells_unknown, cells_near, cells_blocking;
+    int32_t max_depth;              /* greatest depth of a blocking cell, 0 if there is none */
+    int32_t host_beams;             /* diagnostic, not part of the definition: beams whose hit point the host
+                                       recomputed with glibc (csm_host_ray_check: 0) */
+} csm_ray_check_result;
+
+/* Host only. occupied_min = the smallest value 1..65535 whose probability (csm_host_probability_lut) is >=
+ * prob_occupied; free_max = the greatest whose probability is <= prob_free. CSM_EINVAL: a null pointer, a
+ * probability that is not finite, no such value, or free_max >= occupied_min. */
+int  csm_host_ray_check_values(double prob_occupied, double prob_free, uint32_t* occupied_min, uint32_t* free_max);
+/* Host only: the definition as a sequential restatement on a dense rows x cols grid (row-major, as
+ * csm_upload_grid takes it), every ray walked step by step (not by the closed form). `pose` is the robot
+ * pose (a query's initial_pose). per_beam (may be NULL): scan->n_points words, per beam -2 unusable, -1
+ * usable but not walked, 0 walked and not blocked, otherwise that beam's greatest blocking depth.
+ * CSM_EINVAL: null pointers (per_beam aside), rows or cols < 1, n_points < 0, a resolution that is not
+ * finite and > 0, thresholds out of order (0 < free_max < occupied_min <= 65535), subpixel_scale outside
+ * 1..CSM_RAY_CHECK_MAX_SCALE, a negative end_tolerance or scratch_limit_bytes, usable ranges that are NaN, a
+ * non-finite pose, offset or angle, a sensor position more than 2^20 cells from the map's origin on an
+ * axis, usable_range_max / res > 2^20. */
+int  csm_host_ray_check(const uint16_t* grid, int32_t rows, int32_t cols, const csm_geometry* geom,
+                        const csm_scan* scan, const double pose[3], const csm_ray_check_params* params,
+                        csm_ray_check_result* result, int32_t* per_beam);
+/* The check of every query against its resident map, on the device: results[i] <-> queries[i]; per_beam
+ * (may be NULL) receives the queries' words back to back in query order (sum of n_points entries). One
+ * launch chain per chunk of queries: all beams projected in one launch under the map builder's certificate
+ * (the few uncertifiable beams recomputed with glibc on the host and patched in; more of them than the
+ * context's map_uncertain_cap, or CSM_TUNE_MAP_HOST_PROJECTION, and the hit points of that chunk and of the
+ * rest of the call all come from the host), one wavefront per ray over the closed form of its cells, one
+ * read-back of records and words. Scans that queries of a chunk share by pointer are staged once.
+ * CSM_EINVAL (before anything runs): what csm_host_ray_check refuses, for any query; n_queries < 1.
+ * CSM_ENOENT: a map that is not resident. Nothing on the context changes either way. */
+int  csm_ray_check_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
+                         const csm_ray_check_params* params, csm_ray_check_result* results, int32_t* per_beam);
+
 /* The raw records (csm_summary.raw) of the last csm_bnb_match_batch /
  * csm_correlative_match_batch call on this ctx, in query order, copied device
  * to device into dst_dev[n_queries] on the ctx stream (asynchronous): the
@@ -1224,7 +1317,8 @@ int  csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_er
 int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
 /* Drains recorded events; returns total ms and launch count since the last
  * reset for kernel "score_fine" | "score_coarse" | "bin" | "finalize" | "boxmax" |
- * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select" | "likelihood". */
+ * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select" | "likelihood" |
+ * "ray_project" | "ray_walk". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);
 int  csm_reset_kernel_timing(csm_ctx* ctx);

@@ -267,6 +267,24 @@ class LikelihoodParams(C.Structure):
                 ("reserved", C.c_int32), ("kernel", C.c_void_p)]
 
 
+RAY_CHECK_MAX_SCALE = 512
+
+
+class RayCheckParams(C.Structure):
+    _fields_ = [("usable_range_min", C.c_double), ("usable_range_max", C.c_double),
+                ("subpixel_scale", C.c_int32), ("end_tolerance", C.c_int32),
+                ("occupied_min", C.c_uint32), ("free_max", C.c_uint32), ("scratch_limit_bytes", C.c_int64)]
+
+
+class RayCheckResult(C.Structure):
+    _fields_ = [("beams", C.c_int32), ("usable", C.c_int32), ("walked", C.c_int32), ("blocked", C.c_int32),
+                ("end_inside", C.c_int32), ("end_occupied", C.c_int32), ("end_free", C.c_int32),
+                ("end_unknown", C.c_int32),
+                ("cells", C.c_int64), ("cells_free", C.c_int64), ("cells_unknown", C.c_int64),
+                ("cells_near", C.c_int64), ("cells_blocking", C.c_int64),
+                ("max_depth", C.c_int32), ("host_beams", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/csm_hip.h one to one
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -343,6 +361,11 @@ SIGNATURES = {
     "csm_host_likelihood_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(LikelihoodParams), C.c_void_p]),
     "csm_build_likelihood_map": (C.c_int, [_ctx, C.c_uint64, C.c_uint64, _P(LikelihoodParams)]),
     "csm_build_likelihood_maps": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, _P(LikelihoodParams)]),
+    "csm_host_ray_check_values": (C.c_int, [C.c_double, C.c_double, _P(C.c_uint32), _P(C.c_uint32)]),
+    "csm_host_ray_check": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(Geometry), _P(Scan), C.c_void_p,
+                                     _P(RayCheckParams), _P(RayCheckResult), C.c_void_p]),
+    "csm_ray_check_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(RayCheckParams), _P(RayCheckResult),
+                                      C.c_void_p]),
     "csm_bnb_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,
                                       _P(BnbParams), _P(Summary)]),
     "csm_correlative_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,

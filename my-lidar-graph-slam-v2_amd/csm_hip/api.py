@@ -416,6 +416,48 @@ def host_likelihood_map(grid, sigma=None, resolution=None, radius=None, occupied
     return out
 
 
+def host_ray_check_values(prob_occupied=0.65, prob_free=0.35):
+    """csm_host_ray_check_values: (occupied_min, free_max), the raw cell values at two probabilities."""
+    occ, fre = C.c_uint32(), C.c_uint32()
+    rc = L.load().csm_host_ray_check_values(prob_occupied, prob_free, C.byref(occ), C.byref(fre))
+    if rc:
+        raise CsmError(rc, "csm_host_ray_check_values")
+    return occ.value, fre.value
+
+
+def ray_check_params(usable_range_min=0.01, usable_range_max=20.0, subpixel_scale=100, occupied_min=None,
+                     free_max=None, end_tolerance=1, scratch_limit_bytes=0):
+    """A csm_ray_check_params. occupied_min / free_max default to the values of P = 0.65 / 0.35."""
+    if occupied_min is None or free_max is None:
+        occ, fre = host_ray_check_values()
+        occupied_min = occ if occupied_min is None else occupied_min
+        free_max = fre if free_max is None else free_max
+    return L.RayCheckParams(usable_range_min, usable_range_max, subpixel_scale, end_tolerance, occupied_min,
+                            free_max, scratch_limit_bytes)
+
+
+RAY_CHECK_FIELDS = tuple(name for name, _ in L.RayCheckResult._fields_)
+
+
+def ray_check_to_dict(r):
+    return {name: int(getattr(r, name)) for name in RAY_CHECK_FIELDS}
+
+
+def host_ray_check(grid, geom, angles, ranges, rel_pose, pose, per_beam=False, params=None, **kw):
+    """csm_host_ray_check: the free-space check of one scan at the robot pose `pose` on a dense grid, as a
+    dict of the record's fields; with per_beam also the int32 word of every beam."""
+    g = np.ascontiguousarray(grid, dtype=np.uint16)
+    sc, keep = _scan_struct(angles, ranges, rel_pose)
+    p = params if params is not None else ray_check_params(**kw)
+    out = L.RayCheckResult()
+    words = np.zeros(max(sc.n_points, 1), np.int32)
+    rc = L.load().csm_host_ray_check(_ptr(g), g.shape[0], g.shape[1], C.byref(L.Geometry(*geom)), C.byref(sc),
+                                     _ptr(_f64(pose)), C.byref(p), C.byref(out), _ptr(words) if per_beam else None)
+    if rc:
+        raise CsmError(rc, "csm_host_ray_check")
+    return (ray_check_to_dict(out), words[:sc.n_points]) if per_beam else ray_check_to_dict(out)
+
+
 def host_probability_lut():
     lut = np.zeros(65536)
     L.load().csm_host_probability_lut(_ptr(lut))
@@ -1051,6 +1093,32 @@ class Context:
         out = (L.Summary * prep.n)()
         self._check(self.lib.csm_correlative_match_batch(self._ctx, prep.arr, prep.n, C.byref(p), out))
         return SummaryArray(out) if as_records else [summary_to_dict(o) for o in out]
+
+    def ray_check_batch(self, queries, poses=None, per_beam=False, params=None, **kw):
+        """csm_ray_check_batch: the free-space check of every query's scan against its resident map at the
+        query's init_pose (a map-local robot pose, e.g. a summary's estimated_pose). poses: one pose per
+        query that replaces its init_pose, so the output of correlative_peaks_batch can be fed in peak by
+        peak. Returns a list of dicts; with per_beam also a list of int32 arrays, one per query."""
+        prep = self.prepare_queries(queries)
+        arr = prep.arr
+        if poses is not None:
+            if len(poses) != prep.n:
+                raise ValueError("one pose per query")
+            arr = (L.LoopQuery * prep.n)()
+            C.memmove(arr, prep.arr, C.sizeof(arr))
+            for i, pose in enumerate(poses):
+                arr[i].initial_pose[:] = list(pose)
+        p = params if params is not None else ray_check_params(**kw)
+        out = (L.RayCheckResult * prep.n)()
+        counts = [int(arr[i].scan.n_points) for i in range(prep.n)]
+        words = np.zeros(max(sum(counts), 1), np.int32)
+        self._check(self.lib.csm_ray_check_batch(self._ctx, arr, prep.n, C.byref(p), out,
+                                                 _ptr(words) if per_beam else None))
+        records = [ray_check_to_dict(o) for o in out]
+        if not per_beam:
+            return records
+        ends = np.cumsum([0] + counts)
+        return records, [words[ends[i]:ends[i + 1]].copy() for i in range(prep.n)]
 
     def bnb_match_batch(self, queries, range_x, range_y, range_theta, node_height_max,
                         score_threshold, known_rate_threshold, as_records=False):

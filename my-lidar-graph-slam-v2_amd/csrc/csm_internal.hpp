@@ -237,6 +237,10 @@ struct csm_ctx {
     /* likelihood-field maps (csm_likelihood_api.hip): table, job per map, counters; pinned staging */
     DevBuf lf_tab;
     PinBuf lf_pin;
+    /* free-space check of loop candidates (csm_ray_api.hip): a chunk's table + scans, its work block
+     * (uncertified list, records, per-beam words, ray records, patches); pinned staging up and back */
+    DevBuf rc_tab, rc_work;
+    PinBuf rc_pin, rc_back;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */

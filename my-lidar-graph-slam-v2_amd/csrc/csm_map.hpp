@@ -230,25 +230,38 @@ __device__ __forceinline__ void map_miss(const MapJob& job, const MapWindow& win
  * height N(x) counted in 1/(2 * scale * dx) cells, column j holds the rows from
  * where the ray enters it to where it leaves it; a ray that leaves through an
  * exact cell corner steps diagonally (the corner's other two cells are not
- * visited). */
-__device__ __forceinline__ void map_walk_ray(const MapJob& job, const MapWindow& win, int r, int lane)
+ * visited). The one text of the closed form: map_walk_ray (below) and the
+ * read-only ray check (csm_ray_kernels.hip) both enumerate through it.
+ *
+ * Sub-pixel coordinates are non-negative (the reference asserts it, bresenham.cpp:
+ * 73-76; the ray check moves its rays by whole cells first). visit(x, y) is called
+ * once per cell, on the lane that holds it. kClip: only cells with clip.x_lo <= x
+ * <= clip.x_hi and clip.y_lo <= y <= clip.y_hi are enumerated, and the columns and
+ * rows outside cost nothing (a column range first, then each column's row range,
+ * before the cells are spread over the lanes). */
+struct RayClip {
+    int x_lo, x_hi, y_lo, y_hi;
+};
+
+template <bool kClip, class Visit>
+__device__ __forceinline__ void ray_cells_closed_form(int sx, int sy, int ex, int ey, int scale, int lane,
+                                                      const RayClip& clip, Visit&& visit)
 {
-    const MapRayRec rec = job.recs[r];
-    if (rec.hit_cell < 0)
-        return;
-    const int scale = job.scale;
-    const MapNode& node = job.nodes[job.rays[r].node];
-    int sx = node.sx, sy = node.sy, ex = rec.ex, ey = rec.ey;
-    const int skip_x = ex / scale, skip_y = ey / scale;
     if (sx > ex) {                            /* bresenham.cpp:67-70 */
         int t = sx; sx = ex; ex = t;
         t = sy; sy = ey; ey = t;
     }
     const int x0 = sx / scale, y0 = sy / scale, x1 = ex / scale, y1 = ey / scale;
     if (x0 == x1) {                           /* bresenham.cpp:87-99 */
-        const int lo = min(y0, y1), hi = max(y0, y1);
+        int lo = min(y0, y1), hi = max(y0, y1);
+        if (kClip) {
+            if (x0 < clip.x_lo || x0 > clip.x_hi)
+                return;
+            lo = max(lo, clip.y_lo);
+            hi = min(hi, clip.y_hi);
+        }
         for (int y = lo + lane; y <= hi; y += 64)
-            map_miss(job, win, x0, y, skip_x, skip_y, (uint32_t)r);
+            visit(x0, y);
         return;
     }
     const long long dx = ex - sx, dy = ey - sy;
@@ -257,10 +270,15 @@ __device__ __forceinline__ void map_walk_ray(const MapJob& job, const MapWindow&
     const long long first = 2ll * scale - (2ll * (sx % scale) + 1);
     const long long last = 2ll * (ex % scale) + 1;
     const int m = x1 - x0;
-    for (int j0 = 0; j0 <= m; j0 += 64) {
+    int j_lo = 0, j_hi = m;
+    if (kClip) {
+        j_lo = max(0, clip.x_lo - x0);
+        j_hi = min(m, clip.x_hi - x0);
+    }
+    for (int j0 = j_lo; j0 <= j_hi; j0 += 64) {
         const int j = j0 + lane;
         int from = 0, count = 0;
-        if (j <= m) {
+        if (j <= j_hi) {
             const long long n_out = j < m ? n0 + dy * (first + 2ll * scale * j)
                                           : n0 + dy * (first + 2ll * scale * (m - 1) + last);
             const long long n_in = n0 + dy * (first + 2ll * scale * (j - 1));   /* unused for j = 0 */
@@ -272,7 +290,11 @@ __device__ __forceinline__ void map_walk_ray(const MapJob& job, const MapWindow&
                 to = j == 0 ? y0 : (int)((n_in + den - 1) / den) - 1;
                 from = (int)(n_out / den);
             }
-            count = to - from + 1;
+            if (kClip) {
+                from = max(from, clip.y_lo);
+                to = min(to, clip.y_hi);
+            }
+            count = kClip ? max(to - from + 1, 0) : to - from + 1;
         }
         /* steep rays have few columns with many rows each: spread the cells of
          * these 64 columns evenly over the lanes (prefix sum + search) */
@@ -294,9 +316,21 @@ __device__ __forceinline__ void map_walk_ray(const MapJob& job, const MapWindow&
             }
             const int y = __shfl(from, c) + (t - __shfl(excl, c));
             if (t < total)
-                map_miss(job, win, x0 + j0 + c, y, skip_x, skip_y, (uint32_t)r);
+                visit(x0 + j0 + c, y);
         }
     }
+}
+
+__device__ __forceinline__ void map_walk_ray(const MapJob& job, const MapWindow& win, int r, int lane)
+{
+    const MapRayRec rec = job.recs[r];
+    if (rec.hit_cell < 0)
+        return;
+    const int scale = job.scale;
+    const MapNode& node = job.nodes[job.rays[r].node];
+    const int skip_x = rec.ex / scale, skip_y = rec.ey / scale;
+    ray_cells_closed_form<false>(node.sx, node.sy, rec.ex, rec.ey, scale, lane, RayClip{ 0, 0, 0, 0 },
+                                 [&](int x, int y) { map_miss(job, win, x, y, skip_x, skip_y, (uint32_t)r); });
 }
 
 /* kMapGroup consecutive rays per workgroup (neighbouring beams of one scan: they

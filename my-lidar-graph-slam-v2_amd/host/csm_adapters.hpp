@@ -725,6 +725,53 @@ struct LoopDetectionResult {
 };
 using LoopDetectionResultVector = std::vector<LoopDetectionResult>;
 
+/* The free-space check of loop candidates (csm_ray_check_batch, include/csm_hip.h): every beam of the query
+ * scan walked from the sensor to its hit at the candidate pose, the cells it crosses classified against the
+ * reference local map. A correlative score only counts where the end points fall; a pose on the wrong side
+ * of a wall scores like the true one, and only its rays run through cells the map knows to be occupied.
+ * A candidate is kept iff all three hold:
+ *   walked >= mMinWalked,  blocked <= mMaxBlockedRate * walked,  end_occupied >= mMinEndOccupiedRate * end_inside */
+struct RayCheckSettings {
+    csm_ray_check_params mParams {};
+    double mMaxBlockedRate = 0.1;
+    int mMinWalked = 1;
+    double mMinEndOccupiedRate = 0.0;
+
+    /* the builder's usable range and sub-pixel scale; occupied / free at P >= probOccupied / P <= probFree */
+    static RayCheckSettings Create(double usableRangeMin = 0.01, double usableRangeMax = 20.0,
+                                   double probOccupied = 0.65, double probFree = 0.35, int endTolerance = 1,
+                                   int subpixelScale = 100)
+    {
+        RayCheckSettings s;
+        s.mParams.usable_range_min = usableRangeMin;
+        s.mParams.usable_range_max = usableRangeMax;
+        s.mParams.subpixel_scale = subpixelScale;
+        s.mParams.end_tolerance = endTolerance;
+        CSM_ASSERT_OK(nullptr, csm_host_ray_check_values(probOccupied, probFree, &s.mParams.occupied_min,
+                                                         &s.mParams.free_max));
+        return s;
+    }
+
+    bool Passes(const csm_ray_check_result& r) const
+    {
+        return r.walked >= this->mMinWalked &&
+               static_cast<double>(r.blocked) <= this->mMaxBlockedRate * static_cast<double>(r.walked) &&
+               static_cast<double>(r.end_occupied) >= this->mMinEndOccupiedRate * static_cast<double>(r.end_inside);
+    }
+};
+
+/* DetectChecked / DetectPeaksChecked: the results that pass, each with its record beside it, and every
+ * candidate that was checked (mQueryIndex: its query; mPeakIndex: its place among the query's peaks, 0 for
+ * DetectChecked; mKept) with its record, so that a caller can see why one was dropped. */
+struct CheckedLoopDetections {
+    LoopDetectionResultVector mResults;
+    std::vector<csm_ray_check_result> mRecords;              /* beside mResults */
+    LoopDetectionResultVector mCandidates;
+    std::vector<csm_ray_check_result> mCandidateRecords;     /* beside mCandidates */
+    std::vector<int> mQueryIndex, mPeakIndex;
+    std::vector<char> mKept;
+};
+
 class LoopDetectorBranchBoundHIP final {
 public:
     /* scoreThreshold / knownRateThreshold as LoopDetectorBranchBound
@@ -782,6 +829,107 @@ public:
     /* LoopDetector::Detect: results only for the queries where a pose was
      * found, in query order (loop_detector_branch_bound.cpp:107-135). */
     LoopDetectionResultVector Detect(const LoopDetectionQueryVector& queries)
+    {
+        return this->DetectFound(queries, nullptr);
+    }
+
+    /* The free-space check of queries[i]'s scan at poses[i] (map-local robot poses) against its reference
+     * local map, each member of the group on its block of the queries: one record per query. */
+    std::vector<csm_ray_check_result> CheckRays(const LoopDetectionQueryVector& queries,
+                                                const std::vector<RobotPose2D<double>>& poses,
+                                                const RayCheckSettings& settings)
+    {
+        std::vector<csm_ray_check_result> records(queries.size());
+        if (queries.empty())
+            return records;
+        if (poses.size() != queries.size()) {
+            std::fprintf(stderr, "Assertion failed: one pose per query at %s:%d\n", __FILE__, __LINE__);
+            std::abort();
+        }
+        const std::int32_t n = static_cast<std::int32_t>(queries.size());
+        const std::int32_t members = csm_group_size(this->mGroup);
+        for (std::int32_t k = 0; k < members; ++k) {
+            std::int32_t lo = 0, hi = 0;
+            csm_shard_bounds(n, k, members, &lo, &hi);
+            if (lo == hi)
+                continue;
+            csm_ctx* ctx = csm_group_member(this->mGroup, k);
+            std::vector<csm_loop_query> flat(static_cast<std::size_t>(hi - lo));
+            for (std::int32_t i = lo; i < hi; ++i) {
+                const GridMapView& g = queries[i].mReferenceLocalMap;
+                if (!csm_has_grid(ctx, g.mId))
+                    CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, g.mId, g.mValues, g.mRows, g.mCols));
+                flat[static_cast<std::size_t>(i - lo)] = CheckQuery(queries[i], poses[i]);
+            }
+            CSM_ASSERT_OK(ctx, csm_ray_check_batch(ctx, flat.data(), hi - lo, &settings.mParams, records.data() + lo,
+                                                   nullptr));
+        }
+        return records;
+    }
+
+    /* Detect(), then one free-space check per member over the found queries at their result poses: a result
+     * is kept iff settings.Passes(its record). */
+    CheckedLoopDetections DetectChecked(const LoopDetectionQueryVector& queries, const RayCheckSettings& settings)
+    {
+        CheckedLoopDetections checked;
+        std::vector<std::size_t> found;
+        checked.mCandidates = this->DetectFound(queries, &found);
+        /* the check runs where Detect() ran (each member holds the maps of its own block): the members'
+         * blocks are those of the whole query vector */
+        const std::int32_t n = static_cast<std::int32_t>(queries.size());
+        const std::int32_t members = csm_group_size(this->mGroup);
+        checked.mCandidateRecords.resize(found.size());
+        for (std::int32_t k = 0; k < members; ++k) {
+            std::int32_t lo = 0, hi = 0;
+            csm_shard_bounds(n, k, members, &lo, &hi);
+            std::vector<csm_loop_query> flat;
+            std::vector<std::size_t> at;
+            for (std::size_t j = 0; j < found.size(); ++j) {
+                const std::int32_t i = static_cast<std::int32_t>(found[j]);
+                if (i < lo || i >= hi)
+                    continue;
+                flat.push_back(CheckQuery(queries[found[j]], checked.mCandidates[j].mRelativePose));
+                at.push_back(j);
+            }
+            if (flat.empty())
+                continue;
+            csm_ctx* ctx = csm_group_member(this->mGroup, k);
+            std::vector<csm_ray_check_result> res(flat.size());
+            CSM_ASSERT_OK(ctx, csm_ray_check_batch(ctx, flat.data(), static_cast<std::int32_t>(flat.size()),
+                                                   &settings.mParams, res.data(), nullptr));
+            for (std::size_t j = 0; j < at.size(); ++j)
+                checked.mCandidateRecords[at[j]] = res[j];
+        }
+        for (std::size_t j = 0; j < found.size(); ++j) {
+            const bool keep = settings.Passes(checked.mCandidateRecords[j]);
+            checked.mQueryIndex.push_back(static_cast<int>(found[j]));
+            checked.mPeakIndex.push_back(0);
+            checked.mKept.push_back(keep ? 1 : 0);
+            if (keep) {
+                checked.mResults.push_back(checked.mCandidates[j]);
+                checked.mRecords.push_back(checked.mCandidateRecords[j]);
+            }
+        }
+        return checked;
+    }
+
+private:
+    /* query q with the map-local robot pose to check in place of its initial pose */
+    static csm_loop_query CheckQuery(const LoopDetectionQuery& q, const RobotPose2D<double>& pose)
+    {
+        const GridMapView& g = q.mReferenceLocalMap;
+        csm_loop_query f {};
+        f.map_id = g.mId;
+        f.geometry = { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
+        f.scan = detail::ToScan(q.mQueryScanData);
+        f.initial_pose[0] = pose.mX;
+        f.initial_pose[1] = pose.mY;
+        f.initial_pose[2] = pose.mTheta;
+        return f;
+    }
+
+    /* Detect(); found (may be null) receives the query index of every result */
+    LoopDetectionResultVector DetectFound(const LoopDetectionQueryVector& queries, std::vector<std::size_t>* found)
     {
         LoopDetectionResultVector results;
         if (queries.empty())
@@ -878,11 +1026,12 @@ public:
                 r.mNormalizedCost = refined[i].normalized_cost;
             }
             results.push_back(r);
+            if (found)
+                found->push_back(i);
         }
         return results;
     }
 
-private:
     LoopDetectorBranchBoundHIP(const std::string& name, int nodeHeightMax, double rangeX,
                                double rangeY, double rangeTheta, double scoreThreshold,
                                double knownRateThreshold, csm_group* group) :
@@ -924,19 +1073,81 @@ public:
 
     LoopDetectionResultVector Detect(const LoopDetectionQueryVector& queries)
     {
-        LoopDetectionResultVector results;
+        return this->DetectFound(queries, nullptr);
+    }
+
+    /* The free-space check of queries[i]'s scan at poses[i] (map-local robot poses) against its reference
+     * local map, all queries in one csm_ray_check_batch: one record per query. */
+    std::vector<csm_ray_check_result> CheckRays(const LoopDetectionQueryVector& queries,
+                                                const std::vector<RobotPose2D<double>>& poses,
+                                                const RayCheckSettings& settings)
+    {
+        std::vector<csm_ray_check_result> records(queries.size());
         if (queries.empty())
-            return results;
+            return records;
+        if (poses.size() != queries.size()) {
+            std::fprintf(stderr, "Assertion failed: one pose per query at %s:%d\n", __FILE__, __LINE__);
+            std::abort();
+        }
         csm_ctx* ctx = this->mCtx.get();
-        const std::vector<csm_loop_query> flat = this->Flatten(queries);
-        const csm_correlative_params prm = this->Params();
-        std::vector<csm_summary> out(queries.size());
-        CSM_ASSERT_OK(ctx, csm_correlative_match_batch(
-                               ctx, flat.data(), static_cast<std::int32_t>(flat.size()), &prm, out.data()));
-        for (std::size_t i = 0; i < queries.size(); ++i)
-            if (out[i].pose_found)
-                results.push_back(Result(queries[i], out[i]));
-        return results;
+        std::vector<csm_loop_query> flat = this->Flatten(queries);
+        for (std::size_t i = 0; i < flat.size(); ++i) {
+            flat[i].initial_pose[0] = poses[i].mX;
+            flat[i].initial_pose[1] = poses[i].mY;
+            flat[i].initial_pose[2] = poses[i].mTheta;
+        }
+        CSM_ASSERT_OK(ctx, csm_ray_check_batch(ctx, flat.data(), static_cast<std::int32_t>(flat.size()),
+                                               &settings.mParams, records.data(), nullptr));
+        return records;
+    }
+
+    /* Detect(), then one csm_ray_check_batch over the found queries at their estimated poses: a result is
+     * kept iff settings.Passes(its record). */
+    CheckedLoopDetections DetectChecked(const LoopDetectionQueryVector& queries, const RayCheckSettings& settings)
+    {
+        CheckedLoopDetections checked;
+        std::vector<std::size_t> found;
+        checked.mCandidates = this->DetectFound(queries, &found);
+        for (std::size_t j = 0; j < found.size(); ++j) {
+            checked.mQueryIndex.push_back(static_cast<int>(found[j]));
+            checked.mPeakIndex.push_back(0);
+        }
+        this->CheckCandidates(queries, settings, checked);
+        for (std::size_t j = 0; j < checked.mCandidates.size(); ++j)
+            if (checked.mKept[j]) {
+                checked.mResults.push_back(checked.mCandidates[j]);
+                checked.mRecords.push_back(checked.mCandidateRecords[j]);
+            }
+        return checked;
+    }
+
+    /* DetectPeaks(), then ALL peaks of ALL queries in one csm_ray_check_batch; per query the first peak
+     * (best first) that passes is kept. mKept marks that peak alone: a later peak of the same query is not
+     * kept even where its record passes. */
+    CheckedLoopDetections DetectPeaksChecked(const LoopDetectionQueryVector& queries, int numOfPeaks, int exclX,
+                                             int exclY, int exclTheta, const RayCheckSettings& settings)
+    {
+        CheckedLoopDetections checked;
+        const std::vector<LoopDetectionResultVector> peaks = this->DetectPeaks(queries, numOfPeaks, exclX, exclY,
+                                                                               exclTheta);
+        for (std::size_t i = 0; i < peaks.size(); ++i)
+            for (std::size_t j = 0; j < peaks[i].size(); ++j) {
+                checked.mCandidates.push_back(peaks[i][j]);
+                checked.mQueryIndex.push_back(static_cast<int>(i));
+                checked.mPeakIndex.push_back(static_cast<int>(j));
+            }
+        this->CheckCandidates(queries, settings, checked);
+        int taken = -1;                     /* the last query that has its peak */
+        for (std::size_t j = 0; j < checked.mCandidates.size(); ++j) {
+            if (checked.mKept[j] && checked.mQueryIndex[j] != taken) {
+                taken = checked.mQueryIndex[j];
+                checked.mResults.push_back(checked.mCandidates[j]);
+                checked.mRecords.push_back(checked.mCandidateRecords[j]);
+            } else {
+                checked.mKept[j] = 0;
+            }
+        }
+        return checked;
     }
 
     /* Detect() keeping up to numOfPeaks DISTINCT poses per query, best first
@@ -999,6 +1210,44 @@ public:
     }
 
 private:
+    /* Detect(); found (may be null) receives the query index of every result */
+    LoopDetectionResultVector DetectFound(const LoopDetectionQueryVector& queries, std::vector<std::size_t>* found)
+    {
+        LoopDetectionResultVector results;
+        if (queries.empty())
+            return results;
+        csm_ctx* ctx = this->mCtx.get();
+        const std::vector<csm_loop_query> flat = this->Flatten(queries);
+        const csm_correlative_params prm = this->Params();
+        std::vector<csm_summary> out(queries.size());
+        CSM_ASSERT_OK(ctx, csm_correlative_match_batch(
+                               ctx, flat.data(), static_cast<std::int32_t>(flat.size()), &prm, out.data()));
+        for (std::size_t i = 0; i < queries.size(); ++i)
+            if (out[i].pose_found) {
+                results.push_back(Result(queries[i], out[i]));
+                if (found)
+                    found->push_back(i);
+            }
+        return results;
+    }
+
+    /* the records of checked.mCandidates (query mQueryIndex[j] at the candidate's pose) in one call, and
+     * mKept[j] = settings.Passes(record j) */
+    void CheckCandidates(const LoopDetectionQueryVector& queries, const RayCheckSettings& settings,
+                         CheckedLoopDetections& checked)
+    {
+        LoopDetectionQueryVector sub;
+        std::vector<RobotPose2D<double>> poses;
+        for (std::size_t j = 0; j < checked.mCandidates.size(); ++j) {
+            sub.push_back(queries[static_cast<std::size_t>(checked.mQueryIndex[j])]);
+            poses.push_back(checked.mCandidates[j].mRelativePose);
+        }
+        checked.mCandidateRecords = this->CheckRays(sub, poses, settings);
+        checked.mKept.clear();
+        for (const csm_ray_check_result& r : checked.mCandidateRecords)
+            checked.mKept.push_back(settings.Passes(r) ? 1 : 0);
+    }
+
     /* the queries as the batch entries take them; maps that are not resident yet are uploaded */
     std::vector<csm_loop_query> Flatten(const LoopDetectionQueryVector& queries)
     {
