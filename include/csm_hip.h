@@ -1310,6 +1310,88 @@ int  csm_host_pose_graph_lm(double* local_poses, int32_t n_local, double* scan_p
 int  csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_error, double* loss,
                               double* weight);
 
+/* ---- pose-graph marginals: how uncertain a (local map node, scan node) pair is ----
+ *
+ * The covariance of the graph's estimate is the inverse of the information matrix H that one LM step
+ * assembles at the given poses with lambda = 0 (the robust weight on loop edges, the 1e9 anchor on the
+ * diagonal of local map node 0: every covariance is relative to the first local map, the reference's
+ * gauge). The poses are inputs only. With H = [A B^T; B D] (A: local map nodes, D: scan nodes, block
+ * diagonal), W_t,s = D_t^-1 B_t,s, S = A - B^T W and X = S^-1:
+ *   Sigma_ss = X[s, s]
+ *   Sigma_st = - sum_{s' in adj(t)} X[s, s'] W_t,s'^T                               (ascending s')
+ *   Sigma_tt = D_t^-1 + sum_{s'} sum_{s''} W_t,s' X[s', s''] W_t,s''^T              (ascending s', then s'')
+ *   relative = Js Sigma_ss Js^T + Js Sigma_st Je^T + Je Sigma_st^T Js^T + Je Sigma_tt Je^T
+ * Js, Je: the Jacobians of InverseCompound(x_s, x_t) at the two poses, as the optimizer takes them.
+ * X[r, c] is the entry in row r of column c of S^-1, solved from the LDL^T factor of S per column and
+ * independently of every other column: forward y_i = e_i - sum_{k<i} L_ik y_k (k ascending), z = y / d,
+ * backward x_i = z_i - sum_{k>i} L_ki x_k (k descending). Only the block columns of
+ * C = {s of every pair} u adj(t of every pair) are solved. Every 3-term product runs left to right,
+ * symmetric blocks are computed for i >= j and mirrored (exactly symmetric), D_t^-1 comes from the 3x3
+ * LDL^T of D_t. A pair's record is therefore bit-identical whether it is requested alone or among any
+ * other pairs, in any order (for a finite factor).
+ *
+ * CSM_EINVAL, checked on the host before any launch: the argument checks of csm_pose_graph_lm that
+ * apply; n_pairs < 1; a pair index out of range (scan_index = -1 asks for the local map node alone);
+ * n_local > CSM_PG_SCHUR_MAX_LOCAL; a local map node that is not connected to local map node 0 through
+ * edges (S would be singular); a pair that names a scan node without edges. Scan nodes without edges
+ * that no pair names take no part. An information matrix that is not positive semi-definite gives what
+ * the arithmetic gives; `finite` reports it. */
+typedef struct {
+    int32_t local_map_index;
+    int32_t scan_index;          /* -1: the local map node alone */
+} csm_pose_graph_pair;
+
+typedef struct {
+    double  local_cov[9];        /* Sigma_ss, row-major */
+    double  scan_cov[9];         /* Sigma_tt (zeros when scan_index = -1) */
+    double  cross_cov[9];        /* Sigma_st = Cov(x_s, x_t), rows of s (zeros when -1) */
+    double  relative_cov[9];     /* first-order covariance of InverseCompound(x_s, x_t) (zeros when -1) */
+    int32_t finite;              /* 1 iff every entry above is finite */
+    int32_t reserved;
+} csm_pose_graph_marginal;
+
+typedef struct {
+    int32_t n_columns;           /* |C|: distinct local map nodes whose block columns of S^-1 were solved */
+    int32_t reserved;
+} csm_pose_graph_marginals_info;
+
+/* On the device: the direct solver's kernels assemble, eliminate and factor (always the blocked path),
+ * then a multi-column substitution on the factor and a thread per pair ("marginals").
+ * Runs on the ctx stream and returns when the n_pairs records are on the host. Deterministic; differs
+ * from csm_host_pose_graph_marginals only through the device library's sin / cos. Timers:
+ * "pose_graph_marginals" (the chain), and inside it "pose_graph_marginals_factor" (the LDL^T) and
+ * "pose_graph_marginals_solve" (the columns and the pairs). info may be null. */
+int  csm_pose_graph_marginals(csm_ctx* ctx, const double* local_poses, int32_t n_local,
+                              const double* scan_poses, int32_t n_scan, const csm_pose_graph_edge* edges,
+                              int32_t n_edges, int32_t loss_type, double loss_scale,
+                              const csm_pose_graph_pair* pairs, int32_t n_pairs,
+                              csm_pose_graph_marginal* out, csm_pose_graph_marginals_info* info);
+/* Host only: the same as a sequential restatement (glibc's sin / cos). The CPU reference of the above. */
+int  csm_host_pose_graph_marginals(const double* local_poses, int32_t n_local, const double* scan_poses,
+                                   int32_t n_scan, const csm_pose_graph_edge* edges, int32_t n_edges,
+                                   int32_t loss_type, double loss_scale, const csm_pose_graph_pair* pairs,
+                                   int32_t n_pairs, csm_pose_graph_marginal* out,
+                                   csm_pose_graph_marginals_info* info);
+
+/* Host only: the loop search window from a pair's relative_cov. out_a = min(max((2 n_sigma) *
+ * sqrt(relative_cov_aa), min_range_a), max_range_a) for a = x, y, theta: the full widths range_x /
+ * range_y / range_theta of csm_correlative_params / csm_bnb_params, in the local map's frame, where
+ * mapLocalScanPose = InverseCompound(map pose, scan pose) lives. CSM_EINVAL: a negative or non-finite
+ * diagonal entry, a negative or non-finite n_sigma, a NaN bound or min_range_a > max_range_a. */
+int  csm_host_loop_search_ranges(const double relative_cov[9], double n_sigma, const double min_range[3],
+                                 const double max_range[3], double out_range[3]);
+/* Host only: the gate of a found loop against the graph's prediction. M = relative_cov + match_cov entry
+ * by entry, read from its lower triangle; d = measured - predicted with d_theta through NormalizeAngle;
+ * M = L D L^T (3x3, unpivoted, the optimizer's own), x = M^-1 d by forward, diagonal and backward
+ * substitution; *chi2 = (d_0 x_0 + d_1 x_1) + d_2 x_2. A pivot that is not positive and finite: CSM_EINVAL. */
+int  csm_host_loop_gate(const double relative_cov[9], const double match_cov[9], const double predicted[3],
+                        const double measured[3], double* chi2);
+/* Host only: out = cov^-1 through the same 3x3 LDL^T (lower triangle of cov), column j solved from the
+ * unit vector e_j, entries i >= j kept and mirrored: exactly symmetric, as
+ * csm_host_prior_from_robot_information and csm_host_motion_prior demand. A pivot that is not positive
+ * and finite: CSM_EINVAL. */
+int  csm_host_information_from_covariance(const double cov[9], double out[9]);
+
 /* ---- measurement hooks (bench.py) ---- */
 /* enable = 1: every kernel launch is bracketed by HIP events on the ctx
  * stream; enable = 2: only the dominant (fine-level) scoring kernel, to keep
@@ -1318,7 +1400,8 @@ int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
 /* Drains recorded events; returns total ms and launch count since the last
  * reset for kernel "score_fine" | "score_coarse" | "bin" | "finalize" | "boxmax" |
  * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select" | "likelihood" |
- * "ray_project" | "ray_walk". */
+ * "ray_project" | "ray_walk" | "pose_graph" | "pose_graph_marginals" |
+ * "pose_graph_marginals_factor" | "pose_graph_marginals_solve". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);
 int  csm_reset_kernel_timing(csm_ctx* ctx);

@@ -207,6 +207,19 @@ class PoseGraphLMStep(C.Structure):
                 ("cg_iterations", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PoseGraphPair(C.Structure):
+    _fields_ = [("local_map_index", C.c_int32), ("scan_index", C.c_int32)]
+
+
+class PoseGraphMarginal(C.Structure):
+    _fields_ = [("local_cov", C.c_double * 9), ("scan_cov", C.c_double * 9), ("cross_cov", C.c_double * 9),
+                ("relative_cov", C.c_double * 9), ("finite", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PoseGraphMarginalsInfo(C.Structure):
+    _fields_ = [("n_columns", C.c_int32), ("reserved", C.c_int32)]
+
+
 class LoopQuery(C.Structure):
     _fields_ = [("map_id", C.c_uint64), ("geometry", Geometry), ("scan", Scan),
                 ("initial_pose", C.c_double * 3)]
@@ -405,6 +418,15 @@ SIGNATURES = {
                                          _P(PoseGraphLMParams), _P(C.c_double), _P(PoseGraphLMInfo),
                                          _P(PoseGraphLMStep)]),
     "csm_host_pose_graph_loss": (C.c_int, [C.c_int32, C.c_double, C.c_double, _P(C.c_double), _P(C.c_double)]),
+    "csm_pose_graph_marginals": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(PoseGraphEdge),
+                                           C.c_int32, C.c_int32, C.c_double, _P(PoseGraphPair), C.c_int32,
+                                           _P(PoseGraphMarginal), _P(PoseGraphMarginalsInfo)]),
+    "csm_host_pose_graph_marginals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(PoseGraphEdge),
+                                                C.c_int32, C.c_int32, C.c_double, _P(PoseGraphPair), C.c_int32,
+                                                _P(PoseGraphMarginal), _P(PoseGraphMarginalsInfo)]),
+    "csm_host_loop_search_ranges": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "csm_host_loop_gate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_double)]),
+    "csm_host_information_from_covariance": (C.c_int, [C.c_void_p, C.c_void_p]),
     "csm_shard_bounds": (None, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "csm_group_create": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
     "csm_group_create_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, _P(C.c_void_p)]),

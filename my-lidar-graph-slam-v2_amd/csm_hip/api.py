@@ -534,6 +534,73 @@ def host_pose_graph_loss(loss, scale, squared_error):
     return lo.value, w.value
 
 
+def _pose_graph_marginals_run(fn, head, local_poses, scan_poses, edges, pairs, loss, loss_scale):
+    lp = np.array(local_poses, dtype=np.float64).reshape(-1, 3)
+    sp = np.array(scan_poses, dtype=np.float64).reshape(-1, 3)
+    ea = pose_graph_edges(edges)
+    lt = PG_LOSSES[loss] if isinstance(loss, str) else int(loss)
+    pa = (L.PoseGraphPair * max(len(pairs), 1))()
+    for d, (s, t) in zip(pa, pairs):
+        d.local_map_index = int(s)
+        d.scan_index = -1 if t is None else int(t)
+    out = (L.PoseGraphMarginal * max(len(pairs), 1))()
+    info = L.PoseGraphMarginalsInfo()
+    rc = fn(*head, _ptr(lp), lp.shape[0], _ptr(sp), sp.shape[0], ea, len(edges), lt, float(loss_scale), pa,
+            len(pairs), out, C.byref(info))
+    recs = [dict(local_cov=np.array(m.local_cov).reshape(3, 3), scan_cov=np.array(m.scan_cov).reshape(3, 3),
+                 cross_cov=np.array(m.cross_cov).reshape(3, 3), relative_cov=np.array(m.relative_cov).reshape(3, 3),
+                 finite=int(m.finite)) for m in out[:len(pairs)]] if rc == 0 else []
+    return rc, recs, dict(n_columns=info.n_columns)
+
+
+def host_pose_graph_marginals(local_poses, scan_poses, edges, pairs, loss="Huber", loss_scale=0.01):
+    """csm_host_pose_graph_marginals: the sequential restatement of Context.pose_graph_marginals.
+    pairs: (local map index, scan index or None / -1 for the local map node alone). Returns (one dict
+    per pair: local_cov, scan_cov, cross_cov, relative_cov as [3, 3] arrays and finite; info dict)."""
+    rc, recs, info = _pose_graph_marginals_run(L.load().csm_host_pose_graph_marginals, (), local_poses, scan_poses,
+                                               edges, pairs, loss, loss_scale)
+    if rc:
+        raise CsmError(rc, "csm_host_pose_graph_marginals")
+    return recs, info
+
+
+def host_loop_search_ranges(relative_cov, n_sigma, min_range, max_range):
+    """(range_x, range_y, range_theta) of a loop search from a pair's relative_cov
+    (csm_host_loop_search_ranges): 2 n_sigma standard deviations, clamped."""
+    cov, lo, hi, out = _f64(relative_cov).reshape(-1), _f64(min_range), _f64(max_range), np.zeros(3)
+    if cov.size != 9 or lo.size != 3 or hi.size != 3:
+        raise CsmError(L.CSM_EINVAL, "host_loop_search_ranges: relative_cov must be 3 x 3, the bounds 3")
+    rc = L.load().csm_host_loop_search_ranges(_ptr(cov), float(n_sigma), _ptr(lo), _ptr(hi), _ptr(out))
+    if rc:
+        raise CsmError(rc, "csm_host_loop_search_ranges")
+    return out
+
+
+def host_loop_gate(relative_cov, match_cov, predicted, measured):
+    """chi2 = d^T (relative_cov + match_cov)^-1 d of a found loop against the graph's prediction
+    (csm_host_loop_gate)."""
+    a, b, p, m = _f64(relative_cov).reshape(-1), _f64(match_cov).reshape(-1), _f64(predicted), _f64(measured)
+    if a.size != 9 or b.size != 9 or p.size != 3 or m.size != 3:
+        raise CsmError(L.CSM_EINVAL, "host_loop_gate: covariances must be 3 x 3, poses 3")
+    chi2 = C.c_double()
+    rc = L.load().csm_host_loop_gate(_ptr(a), _ptr(b), _ptr(p), _ptr(m), C.byref(chi2))
+    if rc:
+        raise CsmError(rc, "csm_host_loop_gate")
+    return chi2.value
+
+
+def host_information_from_covariance(cov):
+    """The exactly symmetric inverse of a 3 x 3 covariance (csm_host_information_from_covariance): what
+    host_prior_from_robot_information takes."""
+    a, out = _f64(cov).reshape(-1), np.zeros((3, 3))
+    if a.size != 9:
+        raise CsmError(L.CSM_EINVAL, "host_information_from_covariance: cov must be 3 x 3")
+    rc = L.load().csm_host_information_from_covariance(_ptr(a), _ptr(out))
+    if rc:
+        raise CsmError(rc, "csm_host_information_from_covariance")
+    return out
+
+
 class Context:
     """One csm_ctx: owns the device grids, workspaces and a stream."""
 
@@ -1205,6 +1272,14 @@ class Context:
         self._check(rc)
         return lp, sp, out
 
+    def pose_graph_marginals(self, local_poses, scan_poses, edges, pairs, loss="Huber", loss_scale=0.01):
+        """Marginal covariances of (local map node, scan node) pairs on the device
+        (csm_pose_graph_marginals); arguments and result as host_pose_graph_marginals."""
+        rc, recs, info = _pose_graph_marginals_run(self.lib.csm_pose_graph_marginals, (self._ctx,), local_poses,
+                                                   scan_poses, edges, pairs, loss, loss_scale)
+        self._check(rc)
+        return recs, info
+
     def enable_kernel_timing(self, on=True):
         self._check(self.lib.csm_enable_kernel_timing(self._ctx, 1 if on else 0))
 
@@ -1451,3 +1526,9 @@ class PoseGraphOptimizerLMHIP:
         self.lambda_ = info["lambda_"]
         self.last_info = info
         return lp, sp
+
+    def marginals(self, local_map_nodes, scan_nodes, edges, pairs):
+        """Marginal covariances of the pairs at the given poses, with the optimizer's loss function
+        (Context.pose_graph_marginals): one dict per pair."""
+        return self.ctx.pose_graph_marginals(local_map_nodes, scan_nodes, edges, pairs, self.params.loss_type,
+                                             self.params.loss_scale)[0]

@@ -245,6 +245,8 @@ struct csm_ctx {
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */
     std::vector<uint8_t> pg_stage;
+    DevBuf pg_cov;                /* csm_pose_graph_marginals: the columns of S^-1, the pair lists, the records */
+    std::vector<uint8_t> pg_cov_stage;
     /* the final records of the last batch call in query order (csm_copy_last_batch_records) */
     DevBuf rec_dev;
     int rec_n = 0;

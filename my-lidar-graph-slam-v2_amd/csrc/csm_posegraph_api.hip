@@ -2,7 +2,9 @@
  * ConjugateGradient solver or the direct Schur-complement Cholesky solver): validation, the block
  * structure of H with the ordered contribution list of every stored block (and of every block of the
  * Schur complement), the host restatement csm_host_pose_graph_lm (the CPU reference) and the device
- * entry csm_pose_graph_lm, whose kernels are in csm_posegraph_kernels.hip. A translation unit of
+ * entry csm_pose_graph_lm, whose kernels are in csm_posegraph_kernels.hip; the marginal covariances of
+ * node pairs from the Schur factor (csm_pose_graph_marginals, its host restatement) and the host helpers
+ * that turn them into a search window, a gate and a prior. A translation unit of
  * libcsm_hip.so of its own. DESIGN.md 4e. */
 #include "csm_internal.hpp"
 
@@ -212,17 +214,9 @@ void pg_job_structure(const PgGraph& G, const csm_pose_graph_lm_params& p, doubl
     J.lambda = lambda;
 }
 
-/* Optimize, statement by statement and in sequence: the reference the device is held to */
-void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vector<double>& pose, double& lambda,
-                 csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
+/* the host job reads the graph's own lists */
+void pg_host_lists(const PgGraph& G, PgJob& J)
 {
-    const int n = G.n_vars;
-    const bool schur = p.solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY;
-    std::vector<double> ev((size_t)kPgEdgeVals * G.n_edges), bv(9 * ((size_t)G.n_nodes + G.n_cross));
-    std::vector<double> b(n), invd(n), x(n), r(n), z(n), pv(n), ap(n);
-    PgJob J {};
-    pg_job_structure(G, p, lambda, J);
-    J.pose = pose.data();
     J.rel = G.rel.data();
     J.info = G.info.data();
     J.enode = G.enode.data();
@@ -234,6 +228,53 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
     J.row_ptr = G.row_ptr.data();
     J.row_col = G.row_col.data();
     J.row_ent = G.row_ent.data();
+}
+
+/* step 2 on the host: the stored blocks of S into the dense row-major matrix (3 n_local square) */
+void pg_host_schur_matrix(const PgGraph& G, const PgJob& J, const double* w, std::vector<double>& S)
+{
+    const int ns = 3 * G.n_local;
+    std::fill(S.begin(), S.end(), 0.0);
+    for (int q = 0; q < G.n_sblk; ++q)
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j)
+                S[(3 * (size_t)G.sb_rc[2 * q] + i) * ns + 3 * (size_t)G.sb_rc[2 * q + 1] + j] =
+                    pg_schur_entry(J, G.sb_rc.data(), G.sb_ptr.data(), G.sb_pair.data(), w, q, i, j);
+}
+
+/* step 3 on the host: the scalar LDL^T in place, L below the diagonal, d on it */
+void pg_host_ldl(std::vector<double>& S, int ns, std::vector<double>& wrow)
+{
+    for (int i = 0; i < ns; ++i) {
+        double* ri = &S[(size_t)i * ns];
+        for (int j = 0; j <= i; ++j) {
+            const double* rj = &S[(size_t)j * ns];
+            double v = ri[j];
+            for (int k = 0; k < j; ++k)
+                v -= wrow[k] * rj[k];
+            if (j < i) {
+                const double l = v / rj[j];
+                ri[j] = l;
+                wrow[j] = l * rj[j];
+            } else {
+                ri[i] = v;
+            }
+        }
+    }
+}
+
+/* Optimize, statement by statement and in sequence: the reference the device is held to */
+void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vector<double>& pose, double& lambda,
+                 csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
+{
+    const int n = G.n_vars;
+    const bool schur = p.solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY;
+    std::vector<double> ev((size_t)kPgEdgeVals * G.n_edges), bv(9 * ((size_t)G.n_nodes + G.n_cross));
+    std::vector<double> b(n), invd(n), x(n), r(n), z(n), pv(n), ap(n);
+    PgJob J {};
+    pg_job_structure(G, p, lambda, J);
+    J.pose = pose.data();
+    pg_host_lists(G, J);
     J.ev = ev.data();
     J.bv = bv.data();
     auto total_error = [&]() {
@@ -300,30 +341,10 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
     auto solve_schur = [&]() {
         for (int t = G.n_local; t < G.n_nodes; ++t)
             pg_eliminate_scan(J, g.data(), w.data(), t);
-        std::fill(S.begin(), S.end(), 0.0);
-        for (int q = 0; q < G.n_sblk; ++q)
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j)
-                    S[(3 * (size_t)G.sb_rc[2 * q] + i) * ns + 3 * (size_t)G.sb_rc[2 * q + 1] + j] =
-                        pg_schur_entry(J, G.sb_rc.data(), G.sb_ptr.data(), G.sb_pair.data(), w.data(), q, i, j);
+        pg_host_schur_matrix(G, J, w.data(), S);
         for (int a = 0; a < ns; ++a)
             x[a] = pg_schur_rhs(J, g.data(), a / 3, a % 3);
-        for (int i = 0; i < ns; ++i) {               /* L below the diagonal, d on it */
-            double* ri = &S[(size_t)i * ns];
-            for (int j = 0; j <= i; ++j) {
-                const double* rj = &S[(size_t)j * ns];
-                double v = ri[j];
-                for (int k = 0; k < j; ++k)
-                    v -= wrow[k] * rj[k];
-                if (j < i) {
-                    const double l = v / rj[j];
-                    ri[j] = l;
-                    wrow[j] = l * rj[j];
-                } else {
-                    ri[i] = v;
-                }
-            }
-        }
+        pg_host_ldl(S, ns, wrow);
         for (int i = 0; i < ns; ++i) {
             double v = x[i];
             for (int k = 0; k < i; ++k)
@@ -448,53 +469,13 @@ int pg_schur_chain(csm_ctx* ctx, const PgSchurJob& Q, bool small)
     return CSM_OK;
 }
 
-} /* namespace */
-
-extern "C" {
-
-int csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_error, double* loss, double* weight)
+/* one device call's set-up: the graph, its lists and the LM state staged and uploaded into pg_buf (on the
+ * ctx stream), the work vectors carved behind them, pg_s grown for the blocked direct solver; Q.J alone
+ * serves the conjugate-gradient kernel */
+int pg_device_job(csm_ctx* ctx, const PgGraph& G, const double* local_poses, int n_local, const double* scan_poses,
+                  int n_scan, const csm_pose_graph_lm_params* params, const double* lambda, bool schur, bool small,
+                  PgSchurJob& Q)
 {
-    if (loss_type < CSM_PG_LOSS_SQUARED || loss_type > CSM_PG_LOSS_WELSCH || !loss || !weight)
-        return CSM_EINVAL;
-    *loss = pg_loss(loss_type, scale, squared_error);
-    *weight = pg_weight(loss_type, scale, squared_error);
-    return CSM_OK;
-}
-
-int csm_host_pose_graph_lm(double* local_poses, int32_t n_local, double* scan_poses, int32_t n_scan,
-                           const csm_pose_graph_edge* edges, int32_t n_edges, const csm_pose_graph_lm_params* params,
-                           double* lambda, csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
-{
-    if (pg_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, params, lambda))
-        return CSM_EINVAL;
-    PgGraph G;
-    pg_build(n_local, n_scan, edges, n_edges, G);
-    if (params->solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY && !pg_build_schur(G))
-        return CSM_EINVAL;
-    std::vector<double> pose(G.n_vars);
-    std::memcpy(pose.data(), local_poses, 3 * (size_t)n_local * sizeof(double));
-    if (n_scan)
-        std::memcpy(pose.data() + 3 * (size_t)n_local, scan_poses, 3 * (size_t)n_scan * sizeof(double));
-    pg_host_run(G, *params, pose, *lambda, info, trace);
-    std::memcpy(local_poses, pose.data(), 3 * (size_t)n_local * sizeof(double));
-    if (n_scan)
-        std::memcpy(scan_poses, pose.data() + 3 * (size_t)n_local, 3 * (size_t)n_scan * sizeof(double));
-    return CSM_OK;
-}
-
-int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double* scan_poses, int32_t n_scan,
-                      const csm_pose_graph_edge* edges, int32_t n_edges, const csm_pose_graph_lm_params* params,
-                      double* lambda, csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
-{
-    if (!ctx)
-        return CSM_EINVAL;
-    if (const char* why = pg_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, params, lambda))
-        return fail(ctx, CSM_EINVAL, "csm_pose_graph_lm: %s", why);
-    const bool schur = params->solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY;
-    PgGraph G;
-    pg_build(n_local, n_scan, edges, n_edges, G);
-    if (schur && !pg_build_schur(G))
-        return fail(ctx, CSM_EINVAL, "csm_pose_graph_lm: the Schur complement's contribution lists are too long");
     const int n = G.n_vars, E = G.n_edges, NB = G.n_nodes + G.n_cross, R = (int)G.row_col.size();
     const int n_out = 4 + 5 * params->iterations_max;
     /* inputs (uploaded): pose, rel, info, then the int lists; work and output after them */
@@ -515,7 +496,6 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
         o = c.take(8 * (size_t)n);
     const size_t o_out = c.take(8 * (size_t)n_out);
     const int np = pg_schur_padded(n_local), nb_vars = ceil_div(n, kPgsBlock), nb_edges = ceil_div(E, kPgsBlock);
-    const bool small = 3 * n_local <= kPgsSmall;
     const size_t o_g = c.take(schur ? 24 * (size_t)n_scan : 0), o_w = c.take(schur ? 72 * (size_t)G.n_cross : 0),
                  o_y = c.take(schur ? 8 * (size_t)np : 0), o_wp = c.take(schur && !small ? 8 * (size_t)np * kPgsTile : 0),
                  o_part = c.take(schur ? 8 * (2 * (size_t)nb_vars + nb_edges) : 0);
@@ -574,18 +554,13 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
     J.out = reinterpret_cast<double*>(d + o_out);
 
     HIP_TRY(ctx, hipMemcpyAsync(d, st.data(), up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (!schur) {
-        ScopedTimer tm(ctx, "pose_graph");
-        hipLaunchKernelGGL(k_pose_graph_lm, dim3(1), dim3(kPgBlock), 0, ctx->stream, J);
-        HIP_TRY(ctx, hipGetLastError());
-    } else {
-        PgSchurJob Q {};
-        Q.J = J;
-        Q.n_s = 3 * n_local;
-        Q.np = np;
-        Q.n_sblk = G.n_sblk;
-        Q.nb_vars = nb_vars;
-        Q.nb_edges = nb_edges;
+    Q.J = J;
+    Q.n_s = 3 * n_local;
+    Q.np = np;
+    Q.n_sblk = G.n_sblk;
+    Q.nb_vars = nb_vars;
+    Q.nb_edges = nb_edges;
+    if (schur) {
         Q.sb_rc = reinterpret_cast<const int32_t*>(d + o_sbrc);
         Q.sb_ptr = reinterpret_cast<const int32_t*>(d + o_sbptr);
         Q.sb_pair = reinterpret_cast<const int32_t*>(d + o_sbpair);
@@ -596,13 +571,231 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
         Q.y = reinterpret_cast<double*>(d + o_y);
         Q.part = reinterpret_cast<double*>(d + o_part);
         Q.st = reinterpret_cast<PgState*>(d + o_state);
+    }
+    return CSM_OK;
+}
+
+/* ------------------------------------------------------------------ marginal covariances */
+
+/* the LM parameters whose checks and structure the marginals share: one step, the direct solver */
+csm_pose_graph_lm_params pg_cov_params(int32_t loss_type, double loss_scale)
+{
+    csm_pose_graph_lm_params p {};
+    p.iterations_max = 1;
+    p.solver_type = CSM_PG_SOLVER_SCHUR_CHOLESKY;
+    p.loss_type = loss_type;
+    p.loss_scale = loss_scale;
+    return p;
+}
+
+/* what the pairs ask for: C (ascending), every node's position in it, the pairs in node indices */
+struct PgCovPlan {
+    std::vector<int32_t> col_node, col_of, pairs;
+};
+
+const char* pg_cov_check(const double* local_poses, int n_local, const double* scan_poses, int n_scan,
+                         const csm_pose_graph_edge* edges, int n_edges, int32_t loss_type, double loss_scale,
+                         const csm_pose_graph_pair* pairs, int n_pairs, const csm_pose_graph_marginal* out)
+{
+    const csm_pose_graph_lm_params p = pg_cov_params(loss_type, loss_scale);
+    const double lambda = 0.0;
+    if (const char* why = pg_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, &p, &lambda))
+        return why;
+    if (n_pairs < 1 || !pairs || !out)
+        return "n_pairs < 1 or no pairs";
+    for (int q = 0; q < n_pairs; ++q)
+        if (pairs[q].local_map_index < 0 || pairs[q].local_map_index >= n_local || pairs[q].scan_index < -1 ||
+            pairs[q].scan_index >= n_scan)
+            return "pair node index out of range";
+    return nullptr;
+}
+
+/* the refusals that need the graph, then C = {s of every pair} u adj(t of every pair) */
+const char* pg_cov_plan(const PgGraph& G, const csm_pose_graph_pair* pairs, int n_pairs, PgCovPlan& P)
+{
+    const int nl = G.n_local;
+    std::vector<int32_t> root(nl);
+    for (int s = 0; s < nl; ++s)
+        root[s] = s;
+    auto find = [&](int s) {
+        while (root[s] != s)
+            s = root[s] = root[root[s]];
+        return s;
+    };
+    for (int t = nl; t < G.n_nodes; ++t) {
+        int first = -1;
+        for (int q = G.row_ptr[t]; q < G.row_ptr[t + 1]; ++q) {
+            if (G.row_col[q] == t)
+                continue;
+            if (first < 0)
+                first = find(G.row_col[q]);
+            else
+                root[find(G.row_col[q])] = first;
+        }
+    }
+    for (int s = 1; s < nl; ++s)
+        if (find(s) != find(0))
+            return "a local map node is not connected to local map node 0 (the Schur complement is singular)";
+    std::vector<uint8_t> in(nl, 0);
+    P.pairs.resize(2 * (size_t)n_pairs);
+    for (int q = 0; q < n_pairs; ++q) {
+        const int s = pairs[q].local_map_index, t = pairs[q].scan_index < 0 ? -1 : nl + pairs[q].scan_index;
+        P.pairs[2 * q] = s;
+        P.pairs[2 * q + 1] = t;
+        in[s] = 1;
+        if (t < 0)
+            continue;
+        if (G.node_ptr[t] == G.node_ptr[t + 1])
+            return "a pair names a scan node without edges";
+        for (int a = G.row_ptr[t]; a < G.row_ptr[t + 1]; ++a)
+            if (G.row_col[a] != t)
+                in[G.row_col[a]] = 1;
+    }
+    P.col_node.clear();
+    P.col_of.assign(nl, -1);
+    for (int s = 0; s < nl; ++s)
+        if (in[s]) {
+            P.col_of[s] = (int32_t)P.col_node.size();
+            P.col_node.push_back(s);
+        }
+    return nullptr;
+}
+
+void pg_cov_record(const double* v, csm_pose_graph_marginal& m)
+{
+    std::memset(&m, 0, sizeof(m));
+    std::memcpy(m.local_cov, v, 9 * sizeof(double));
+    std::memcpy(m.scan_cov, v + 9, 9 * sizeof(double));
+    std::memcpy(m.cross_cov, v + 18, 9 * sizeof(double));
+    std::memcpy(m.relative_cov, v + 27, 9 * sizeof(double));
+    m.finite = 1;
+    for (int q = 0; q < 36; ++q)
+        if (!std::isfinite(v[q]))
+            m.finite = 0;
+}
+
+/* the marginals' launches behind the upload: H at lambda = 0 eliminated and factored by the LM step's
+ * kernels (the state's done flag stays 0), then the columns of C and the pairs */
+int pg_cov_chain(csm_ctx* ctx, const PgCovJob& C, const std::vector<int32_t>& col_node)
+{
+    const PgSchurJob& Q = C.Q;
+    const PgJob& J = Q.J;
+    hipStream_t s = ctx->stream;
+    const dim3 blk(kPgsBlock);
+    const int n_scan = J.n_nodes - J.n_local, nt = Q.np / kPgsTile, ng = C.ldx / kPgsTile;
+    auto over = [](int64_t count) { return dim3((unsigned)((count + kPgsBlock - 1) / kPgsBlock)); };
+    auto strided = [](int64_t cells) {
+        return dim3((unsigned)std::min<int64_t>((cells + kPgsBlock - 1) / kPgsBlock, 16384));
+    };
+    if (J.n_edges)
+        hipLaunchKernelGGL(k_pgs_edges, over(J.n_edges), blk, 0, s, Q);
+    hipLaunchKernelGGL(k_pgs_assemble, over((int64_t)J.n_nodes + J.n_cross), blk, 0, s, Q);
+    if (n_scan)
+        hipLaunchKernelGGL(k_pgs_eliminate, over(n_scan), blk, 0, s, Q);
+    hipLaunchKernelGGL(k_pgs_clear, strided((int64_t)Q.np * Q.np), blk, 0, s, Q);
+    hipLaunchKernelGGL(k_pgs_schur, over(9 * (int64_t)Q.n_sblk + Q.np), blk, 0, s, Q);
+    {
+        ScopedTimer tm(ctx, "pose_graph_marginals_factor");
+        for (int p = 0; p < nt; ++p) {
+            hipLaunchKernelGGL(k_pgs_ldl_diag, dim3(1), blk, 0, s, Q, p);
+            const int below = nt - p - 1;
+            if (below) {
+                hipLaunchKernelGGL(k_pgs_ldl_panel, dim3(ceil_div(below * kPgsTile, 64)), dim3(64), 0, s, Q, p);
+                hipLaunchKernelGGL(k_pgs_ldl_update, dim3(below, below), blk, 0, s, Q, p);
+            }
+        }
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    ScopedTimer tm(ctx, "pose_graph_marginals_solve");
+    hipLaunchKernelGGL(k_pgc_init, strided((int64_t)Q.np * C.ldx), blk, 0, s, C);
+    /* forward: the groups whose first unit row lies in panel p or above it (C ascends, so a prefix) */
+    int live = 0;
+    for (int p = 0; p < nt; ++p) {
+        while (live < ng && 3 * col_node[(size_t)live * kPgcGroup] / kPgsTile <= p)
+            ++live;
+        if (!live)
+            continue;
+        hipLaunchKernelGGL(k_pgc_diag<true>, dim3(live), blk, 0, s, C, p);
+        if (nt - p - 1)
+            hipLaunchKernelGGL(k_pgc_update<true>, dim3(nt - p - 1, live), blk, 0, s, C, p);
+    }
+    hipLaunchKernelGGL(k_pgc_scale, strided((int64_t)Q.n_s * C.ldx), blk, 0, s, C);
+    for (int p = nt - 1; p >= 0; --p) {
+        hipLaunchKernelGGL(k_pgc_diag<false>, dim3(ng), blk, 0, s, C, p);
+        if (p)
+            hipLaunchKernelGGL(k_pgc_update<false>, dim3(p, ng), blk, 0, s, C, p);
+    }
+    hipLaunchKernelGGL(k_pgc_pairs, over(C.n_pairs), blk, 0, s, C);
+    HIP_TRY(ctx, hipGetLastError());
+    return CSM_OK;
+}
+
+} /* namespace */
+
+extern "C" {
+
+int csm_host_pose_graph_loss(int32_t loss_type, double scale, double squared_error, double* loss, double* weight)
+{
+    if (loss_type < CSM_PG_LOSS_SQUARED || loss_type > CSM_PG_LOSS_WELSCH || !loss || !weight)
+        return CSM_EINVAL;
+    *loss = pg_loss(loss_type, scale, squared_error);
+    *weight = pg_weight(loss_type, scale, squared_error);
+    return CSM_OK;
+}
+
+int csm_host_pose_graph_lm(double* local_poses, int32_t n_local, double* scan_poses, int32_t n_scan,
+                           const csm_pose_graph_edge* edges, int32_t n_edges, const csm_pose_graph_lm_params* params,
+                           double* lambda, csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
+{
+    if (pg_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, params, lambda))
+        return CSM_EINVAL;
+    PgGraph G;
+    pg_build(n_local, n_scan, edges, n_edges, G);
+    if (params->solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY && !pg_build_schur(G))
+        return CSM_EINVAL;
+    std::vector<double> pose(G.n_vars);
+    std::memcpy(pose.data(), local_poses, 3 * (size_t)n_local * sizeof(double));
+    if (n_scan)
+        std::memcpy(pose.data() + 3 * (size_t)n_local, scan_poses, 3 * (size_t)n_scan * sizeof(double));
+    pg_host_run(G, *params, pose, *lambda, info, trace);
+    std::memcpy(local_poses, pose.data(), 3 * (size_t)n_local * sizeof(double));
+    if (n_scan)
+        std::memcpy(scan_poses, pose.data() + 3 * (size_t)n_local, 3 * (size_t)n_scan * sizeof(double));
+    return CSM_OK;
+}
+
+int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double* scan_poses, int32_t n_scan,
+                      const csm_pose_graph_edge* edges, int32_t n_edges, const csm_pose_graph_lm_params* params,
+                      double* lambda, csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
+{
+    if (!ctx)
+        return CSM_EINVAL;
+    if (const char* why = pg_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, params, lambda))
+        return fail(ctx, CSM_EINVAL, "csm_pose_graph_lm: %s", why);
+    const bool schur = params->solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY;
+    PgGraph G;
+    pg_build(n_local, n_scan, edges, n_edges, G);
+    if (schur && !pg_build_schur(G))
+        return fail(ctx, CSM_EINVAL, "csm_pose_graph_lm: the Schur complement's contribution lists are too long");
+    const bool small = 3 * n_local <= kPgsSmall;
+    const int n = G.n_vars, n_out = 4 + 5 * params->iterations_max;
+    PgSchurJob Q {};
+    int rc;
+    if ((rc = pg_device_job(ctx, G, local_poses, n_local, scan_poses, n_scan, params, lambda, schur, small, Q)))
+        return rc;
+    const PgJob& J = Q.J;
+    if (!schur) {
+        ScopedTimer tm(ctx, "pose_graph");
+        hipLaunchKernelGGL(k_pose_graph_lm, dim3(1), dim3(kPgBlock), 0, ctx->stream, J);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
         ScopedTimer tm(ctx, "pose_graph");
         if ((rc = pg_schur_chain(ctx, Q, small)))
             return rc;
     }
     std::vector<double> res(n + (size_t)n_out);
-    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d + o_pose, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(res.data() + n, d + o_out, 8 * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(res.data(), J.pose, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(res.data() + n, J.out, 8 * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 
     std::memcpy(local_poses, res.data(), 24 * (size_t)n_local);
@@ -633,6 +826,212 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
         info->initial_error = o[1];
         info->final_error = o[2];
         info->final_lambda = o[3];
+    }
+    return CSM_OK;
+}
+
+int csm_host_pose_graph_marginals(const double* local_poses, int32_t n_local, const double* scan_poses, int32_t n_scan,
+                                  const csm_pose_graph_edge* edges, int32_t n_edges, int32_t loss_type,
+                                  double loss_scale, const csm_pose_graph_pair* pairs, int32_t n_pairs,
+                                  csm_pose_graph_marginal* out, csm_pose_graph_marginals_info* info)
+{
+    if (pg_cov_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, loss_type, loss_scale, pairs, n_pairs,
+                     out))
+        return CSM_EINVAL;
+    PgGraph G;
+    PgCovPlan P;
+    pg_build(n_local, n_scan, edges, n_edges, G);
+    if (!pg_build_schur(G) || pg_cov_plan(G, pairs, n_pairs, P))
+        return CSM_EINVAL;
+    const int n = G.n_vars, ns = 3 * n_local, nc = 3 * (int)P.col_node.size();
+    std::vector<double> pose(n), ev((size_t)kPgEdgeVals * G.n_edges), bv(9 * ((size_t)G.n_nodes + G.n_cross));
+    std::vector<double> b(n), invd(n), g(3 * (size_t)n_scan), w(9 * (size_t)G.n_cross), wrow(ns);
+    std::vector<double> S((size_t)ns * ns), X((size_t)ns * nc, 0.0);
+    std::memcpy(pose.data(), local_poses, 24 * (size_t)n_local);
+    if (n_scan)
+        std::memcpy(pose.data() + 3 * (size_t)n_local, scan_poses, 24 * (size_t)n_scan);
+    PgJob J {};
+    pg_job_structure(G, pg_cov_params(loss_type, loss_scale), 0.0, J);
+    J.pose = pose.data();
+    pg_host_lists(G, J);
+    J.ev = ev.data();
+    J.bv = bv.data();
+    J.b = b.data();
+    J.invd = invd.data();
+    for (int e = 0; e < G.n_edges; ++e)
+        pg_edge_values(&pose[3 * (size_t)G.enode[2 * e]], &pose[3 * (size_t)G.enode[2 * e + 1]], &G.rel[3 * (size_t)e],
+                       &G.info[9 * (size_t)e], G.is_loop[e], loss_type, loss_scale, &ev[(size_t)kPgEdgeVals * e]);
+    for (int k = 0; k < G.n_nodes; ++k)
+        pg_assemble_node(J, k, 0.0);
+    for (int u = 0; u < G.n_cross; ++u)
+        pg_assemble_cross(J, u);
+    for (int t = n_local; t < G.n_nodes; ++t)
+        if (G.node_ptr[t] != G.node_ptr[t + 1])
+            pg_eliminate_scan(J, g.data(), w.data(), t);
+    pg_host_schur_matrix(G, J, w.data(), S);
+    pg_host_ldl(S, ns, wrow);
+    /* every column by itself; row k's terms reach the columns whose unit row is k or above it (a prefix) */
+    std::vector<int32_t> reach(ns, 0);
+    for (int c = 0; c < nc; ++c) {
+        const int f = 3 * P.col_node[c / 3] + c % 3;
+        X[(size_t)f * nc + c] = 1.0;
+        ++reach[f];
+    }
+    for (int k = 1; k < ns; ++k)
+        reach[k] += reach[k - 1];
+    for (int i = 0; i < ns; ++i) {
+        double* xi = &X[(size_t)i * nc];
+        for (int k = 0; k < i; ++k) {
+            const double l = S[(size_t)i * ns + k];
+            const double* xk = &X[(size_t)k * nc];
+            for (int c = 0; c < reach[k]; ++c)
+                xi[c] -= l * xk[c];
+        }
+    }
+    for (int i = 0; i < ns; ++i)
+        for (int c = 0; c < nc; ++c)
+            X[(size_t)i * nc + c] = X[(size_t)i * nc + c] / S[(size_t)i * ns + i];
+    for (int i = ns - 1; i >= 0; --i) {
+        double* xi = &X[(size_t)i * nc];
+        for (int k = ns - 1; k > i; --k) {
+            const double l = S[(size_t)k * ns + i];
+            const double* xk = &X[(size_t)k * nc];
+            for (int c = 0; c < nc; ++c)
+                xi[c] -= l * xk[c];
+        }
+    }
+    for (int q = 0; q < n_pairs; ++q) {
+        double v[36];
+        pg_marginal_pair(J, w.data(), X.data(), (size_t)nc, P.col_of.data(), P.pairs[2 * q], P.pairs[2 * q + 1], v);
+        pg_cov_record(v, out[q]);
+    }
+    if (info) {
+        std::memset(info, 0, sizeof(*info));
+        info->n_columns = (int32_t)P.col_node.size();
+    }
+    return CSM_OK;
+}
+
+int csm_pose_graph_marginals(csm_ctx* ctx, const double* local_poses, int32_t n_local, const double* scan_poses,
+                             int32_t n_scan, const csm_pose_graph_edge* edges, int32_t n_edges, int32_t loss_type,
+                             double loss_scale, const csm_pose_graph_pair* pairs, int32_t n_pairs,
+                             csm_pose_graph_marginal* out, csm_pose_graph_marginals_info* info)
+{
+    if (!ctx)
+        return CSM_EINVAL;
+    if (const char* why = pg_cov_check(local_poses, n_local, scan_poses, n_scan, edges, n_edges, loss_type, loss_scale,
+                                       pairs, n_pairs, out))
+        return fail(ctx, CSM_EINVAL, "csm_pose_graph_marginals: %s", why);
+    PgGraph G;
+    PgCovPlan P;
+    pg_build(n_local, n_scan, edges, n_edges, G);
+    if (!pg_build_schur(G))
+        return fail(ctx, CSM_EINVAL, "csm_pose_graph_marginals: the Schur complement's contribution lists are too long");
+    if (const char* why = pg_cov_plan(G, pairs, n_pairs, P))
+        return fail(ctx, CSM_EINVAL, "csm_pose_graph_marginals: %s", why);
+    const csm_pose_graph_lm_params prm = pg_cov_params(loss_type, loss_scale);
+    const double lambda = 0.0;
+    PgCovJob C {};
+    int rc;
+    if ((rc = pg_device_job(ctx, G, local_poses, n_local, scan_poses, n_scan, &prm, &lambda, true, false, C.Q)))
+        return rc;
+    const int n_c = (int)P.col_node.size();
+    C.n_cols = 3 * n_c;
+    C.ldx = ceil_div(n_c, kPgcGroup) * kPgsTile;
+    C.n_pairs = n_pairs;
+    /* X, then the uploaded lists, then the records */
+    Carve c;
+    const size_t o_x = c.take(8 * (size_t)C.Q.np * C.ldx), o_node = c.take(4 * (size_t)n_c),
+                 o_of = c.take(4 * (size_t)n_local), o_pairs = c.take(8 * (size_t)n_pairs), o_lists = c.off,
+                 o_out = c.take(8 * 36 * (size_t)n_pairs);
+    if ((rc = grow(ctx, ctx->pg_cov, c.off, c.off, false)))
+        return rc;
+    std::vector<uint8_t>& st = ctx->pg_cov_stage;
+    st.assign(o_lists - o_node, 0);
+    std::memcpy(st.data(), P.col_node.data(), 4 * (size_t)n_c);
+    std::memcpy(st.data() + (o_of - o_node), P.col_of.data(), 4 * (size_t)n_local);
+    std::memcpy(st.data() + (o_pairs - o_node), P.pairs.data(), 8 * (size_t)n_pairs);
+    uint8_t* d = reinterpret_cast<uint8_t*>(ctx->pg_cov.p);
+    C.X = reinterpret_cast<double*>(d + o_x);
+    C.col_node = reinterpret_cast<const int32_t*>(d + o_node);
+    C.col_of = reinterpret_cast<const int32_t*>(d + o_of);
+    C.pairs = reinterpret_cast<const int32_t*>(d + o_pairs);
+    C.out = reinterpret_cast<double*>(d + o_out);
+    HIP_TRY(ctx, hipMemcpyAsync(d + o_node, st.data(), st.size(), hipMemcpyHostToDevice, ctx->stream));
+    {
+        ScopedTimer tm(ctx, "pose_graph_marginals");
+        if ((rc = pg_cov_chain(ctx, C, P.col_node)))
+            return rc;
+    }
+    std::vector<double> res(36 * (size_t)n_pairs);
+    HIP_TRY(ctx, hipMemcpyAsync(res.data(), C.out, 8 * res.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int q = 0; q < n_pairs; ++q)
+        pg_cov_record(&res[36 * (size_t)q], out[q]);
+    if (info) {
+        std::memset(info, 0, sizeof(*info));
+        info->n_columns = n_c;
+    }
+    return CSM_OK;
+}
+
+int csm_host_loop_search_ranges(const double relative_cov[9], double n_sigma, const double min_range[3],
+                                const double max_range[3], double out_range[3])
+{
+    if (!relative_cov || !min_range || !max_range || !out_range || !std::isfinite(n_sigma) || n_sigma < 0.0)
+        return CSM_EINVAL;
+    for (int a = 0; a < 3; ++a) {
+        const double d = relative_cov[4 * a];
+        if (!std::isfinite(d) || d < 0.0 || std::isnan(min_range[a]) || std::isnan(max_range[a]) ||
+            min_range[a] > max_range[a])
+            return CSM_EINVAL;
+    }
+    for (int a = 0; a < 3; ++a) {
+        double r = (2.0 * n_sigma) * sqrt(relative_cov[4 * a]);
+        if (r < min_range[a])
+            r = min_range[a];
+        if (r > max_range[a])
+            r = max_range[a];
+        out_range[a] = r;
+    }
+    return CSM_OK;
+}
+
+int csm_host_loop_gate(const double relative_cov[9], const double match_cov[9], const double predicted[3],
+                       const double measured[3], double* chi2)
+{
+    if (!relative_cov || !match_cov || !predicted || !measured || !chi2)
+        return CSM_EINVAL;
+    double M[9], f[6], x[3];
+    for (int q = 0; q < 9; ++q)
+        M[q] = relative_cov[q] + match_cov[q];
+    pg_ldl3(M, f);
+    for (int a = 0; a < 3; ++a)
+        if (!(f[a] > 0.0) || !std::isfinite(f[a]))
+            return CSM_EINVAL;
+    const double d[3] = { measured[0] - predicted[0], measured[1] - predicted[1],
+                          pg_normalize_angle(measured[2] - predicted[2]) };
+    pg_ldl3_solve(f, d[0], d[1], d[2], x);
+    *chi2 = d[0] * x[0] + d[1] * x[1] + d[2] * x[2];
+    return CSM_OK;
+}
+
+int csm_host_information_from_covariance(const double cov[9], double out[9])
+{
+    if (!cov || !out)
+        return CSM_EINVAL;
+    double f[6];
+    pg_ldl3(cov, f);
+    for (int a = 0; a < 3; ++a)
+        if (!(f[a] > 0.0) || !std::isfinite(f[a]))
+            return CSM_EINVAL;
+    for (int j = 0; j < 3; ++j) {
+        double x[3];
+        pg_ldl3_solve(f, j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0, x);
+        for (int i = j; i < 3; ++i) {
+            out[3 * i + j] = x[i];
+            out[3 * j + i] = x[i];
+        }
     }
     return CSM_OK;
 }

@@ -914,5 +914,242 @@ __global__ __launch_bounds__(kPgsBlock) void k_pgs_decide(PgSchurJob Q, int firs
     Q.J.out[3] = st.lambda;
 }
 
+/* ================================================================== marginal covariances of node pairs
+ * csm_pose_graph_marginals ("marginals"): H at lambda = 0 is eliminated and factored by
+ * the kernels above; X = S^-1 is solved for the block columns C that the pairs need, every column by
+ * itself (forward k ascending, division by d, backward k descending), and a pair's four 3x3 blocks are
+ * put together from X, W and D_t^-1. X[r, c] is always the entry in row r of the solved column c. The
+ * per-pair arithmetic is shared by the host restatement and the kernel.
+ *
+ * X is row-major [np][ldx]: column 3 m + j belongs to C[m]; sixteen nodes of C (kPgcGroup, 48 columns =
+ * one tile) are a column group. The sweep is grid-wide with launches per panel, as the factorization's:
+ * k_pgc_diag solves the panel's 48 rows of every group in LDS, k_pgc_update takes the panel out of every
+ * row tile below (forward) or above (backward), a workgroup per (row tile, group). A group starts at
+ * the panel of its first unit row; the host knows which groups are in play. */
+
+constexpr int kPgcGroup = 16;     /* nodes of C per column group: 3 * 16 = kPgsTile columns */
+static_assert(3 * kPgcGroup == kPgsTile, "a column group is one tile wide");
+
+struct PgCovJob {
+    PgSchurJob Q;
+    int n_cols, ldx;              /* 3 |C|; n_cols rounded up to whole column groups (= the row stride of X) */
+    int n_pairs;
+    const int32_t* col_node;      /* [|C|]: ascending local map nodes */
+    const int32_t* col_of;        /* [n_local]: position in C, or -1 */
+    const int32_t* pairs;         /* [2 n_pairs]: local map node, scan node as a node index or -1 */
+    double* X;                    /* [np * ldx] */
+    double* out;                  /* [36 n_pairs]: local, scan, cross, relative */
+};
+
+/* (A B)(i, j) and (A B^T)(i, j) of row-major 3x3 blocks, left to right */
+__host__ __device__ inline double pg_mul3(const double* A, const double* B, int i, int j)
+{
+    return A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
+}
+
+__host__ __device__ inline double pg_mul3t(const double* A, const double* B, int i, int j)
+{
+    return A[3 * i] * B[3 * j] + A[3 * i + 1] * B[3 * j + 1] + A[3 * i + 2] * B[3 * j + 2];
+}
+
+/* the record of pair (s, t): v = Sigma_ss, Sigma_tt, Sigma_st, relative (9 each, row-major). t is a node
+ * index, or -1 for the local map node alone. Symmetric blocks are computed for i >= j and mirrored. */
+__host__ __device__ inline void pg_marginal_pair(const PgJob& J, const double* w, const double* X, size_t ldx,
+                                                 const int32_t* col_of, int s, int t, double* v)
+{
+    for (int q = 0; q < 36; ++q)
+        v[q] = 0.0;
+    const double* Xs = X + 3 * (size_t)s * ldx;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j <= i; ++j) {
+            const double x = Xs[i * ldx + 3 * (size_t)col_of[s] + j];
+            v[3 * i + j] = x;
+            v[3 * j + i] = x;
+        }
+    if (t < 0)
+        return;
+    double *stt = v + 9, *sst = v + 18, *rel = v + 27;
+    double f[6], Dinv[9];
+    pg_ldl3(J.bv + 9 * (size_t)t, f);
+    for (int j = 0; j < 3; ++j) {
+        double x[3];
+        pg_ldl3_solve(f, j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0, x);
+        for (int i = 0; i < 3; ++i)
+            Dinv[3 * i + j] = x[i];
+    }
+    const int q0 = J.row_ptr[t], q1 = J.row_ptr[t + 1];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double acc = 0.0;
+            for (int a = q0; a < q1; ++a) {
+                if (J.row_col[a] == t)
+                    continue;
+                const double* W = w + 9 * (size_t)((J.row_ent[a] >> 2) - J.n_nodes);
+                const double* x = Xs + i * ldx + 3 * (size_t)col_of[J.row_col[a]];
+                acc -= x[0] * W[3 * j] + x[1] * W[3 * j + 1] + x[2] * W[3 * j + 2];
+            }
+            sst[3 * i + j] = acc;
+        }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double acc = Dinv[3 * i + j];
+            for (int a = q0; a < q1; ++a) {
+                if (J.row_col[a] == t)
+                    continue;
+                const double* Wa = w + 9 * (size_t)((J.row_ent[a] >> 2) - J.n_nodes);
+                const double* Xa = X + 3 * (size_t)J.row_col[a] * ldx;
+                for (int b = q0; b < q1; ++b) {
+                    if (J.row_col[b] == t)
+                        continue;
+                    const double* Wb = w + 9 * (size_t)((J.row_ent[b] >> 2) - J.n_nodes);
+                    const double* x = Xa + 3 * (size_t)col_of[J.row_col[b]];
+                    double m[3];
+                    for (int k = 0; k < 3; ++k)
+                        m[k] = Wa[3 * i] * x[k] + Wa[3 * i + 1] * x[ldx + k] + Wa[3 * i + 2] * x[2 * ldx + k];
+                    acc += m[0] * Wb[3 * j] + m[1] * Wb[3 * j + 1] + m[2] * Wb[3 * j + 2];
+                }
+            }
+            stt[3 * i + j] = acc;
+            stt[3 * j + i] = acc;
+        }
+    /* first-order covariance of InverseCompound(x_s, x_t): the Jacobians of pg_edge_values */
+    const double zero[3] = { 0.0, 0.0, 0.0 };
+    double e[3], c, sn, x, y;
+    pg_error(J.pose + 3 * (size_t)s, J.pose + 3 * (size_t)t, zero, e, c, sn, x, y);
+    const double Js[9] = { -c, -sn, y, sn, -c, -x, 0.0, 0.0, -1.0 };
+    const double Je[9] = { c, sn, 0.0, -sn, c, 0.0, 0.0, 0.0, 1.0 };
+    double sts[9], T1[9], T2[9], T3[9], T4[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            sts[3 * i + j] = sst[3 * j + i];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            T1[3 * i + j] = pg_mul3(Js, v, i, j);
+            T2[3 * i + j] = pg_mul3(Js, sst, i, j);
+            T3[3 * i + j] = pg_mul3(Je, sts, i, j);
+            T4[3 * i + j] = pg_mul3(Je, stt, i, j);
+        }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j <= i; ++j) {
+            const double r = pg_mul3t(T1, Js, i, j) + pg_mul3t(T2, Je, i, j) + pg_mul3t(T3, Js, i, j) +
+                             pg_mul3t(T4, Je, i, j);
+            rel[3 * i + j] = r;
+            rel[3 * j + i] = r;
+        }
+}
+
+/* X = the unit columns of C, zeros in the padding rows and columns */
+__global__ __launch_bounds__(kPgsBlock) void k_pgc_init(PgCovJob C)
+{
+    const size_t total = (size_t)C.Q.np * C.ldx;
+    for (size_t i = (size_t)blockIdx.x * kPgsBlock + threadIdx.x; i < total; i += (size_t)gridDim.x * kPgsBlock) {
+        const int r = (int)(i / C.ldx), c = (int)(i - (size_t)r * C.ldx);
+        C.X[i] = (c < C.n_cols && r == 3 * C.col_node[c / 3] + c % 3) ? 1.0 : 0.0;
+    }
+}
+
+/* z = y / d on the rows of S */
+__global__ __launch_bounds__(kPgsBlock) void k_pgc_scale(PgCovJob C)
+{
+    const size_t total = (size_t)C.Q.n_s * C.ldx;
+    for (size_t i = (size_t)blockIdx.x * kPgsBlock + threadIdx.x; i < total; i += (size_t)gridDim.x * kPgsBlock) {
+        const size_t r = i / C.ldx;
+        C.X[i] = C.X[i] / C.Q.S[r * C.Q.np + r];
+    }
+}
+
+/* panel p, column group blockIdx.x: the triangular solve on the panel's own rows, in LDS. Forward: row i
+ * takes rows j < i in ascending j; backward: rows j > i in descending j. Rows past n_s take no part. */
+template <bool Fwd>
+__global__ __launch_bounds__(kPgsBlock) void k_pgc_diag(PgCovJob C, int p)
+{
+    __shared__ double Lt[kPgsTile][kPgsTile + 1];
+    __shared__ double Yt[kPgsTile][kPgsTile + 1];
+    const PgSchurJob& Q = C.Q;
+    const int tid = threadIdx.x, j0 = p * kPgsTile;
+    const double* T = Q.S + (size_t)j0 * Q.np + j0;
+    double* Y = C.X + (size_t)j0 * C.ldx + (size_t)blockIdx.x * kPgsTile;
+    for (int q = tid; q < kPgsTile * kPgsTile; q += kPgsBlock) {
+        const int r = q / kPgsTile, c = q % kPgsTile;
+        Lt[r][c] = T[(size_t)r * Q.np + c];
+        Yt[r][c] = Y[(size_t)r * C.ldx + c];
+    }
+    const int kmax = (Q.n_s - j0 < kPgsTile) ? Q.n_s - j0 : kPgsTile;
+    if (Fwd) {
+        for (int j = 0; j < kmax - 1; ++j) {
+            __syncthreads();
+            for (int q = tid; q < kPgsTile * kPgsTile; q += kPgsBlock) {
+                const int i = q / kPgsTile, c = q % kPgsTile;
+                if (i > j && i < kmax)
+                    Yt[i][c] -= Lt[i][j] * Yt[j][c];
+            }
+        }
+    } else {
+        for (int j = kmax - 1; j >= 1; --j) {
+            __syncthreads();
+            for (int q = tid; q < kPgsTile * kPgsTile; q += kPgsBlock) {
+                const int i = q / kPgsTile, c = q % kPgsTile;
+                if (i < j)
+                    Yt[i][c] -= Lt[j][i] * Yt[j][c];
+            }
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < kmax * kPgsTile; q += kPgsBlock)
+        Y[(size_t)(q / kPgsTile) * C.ldx + q % kPgsTile] = Yt[q / kPgsTile][q % kPgsTile];
+}
+
+/* panel p out of row tile ti of column group blockIdx.y: X_ic -= sum_k L_(i, j0 + k) X_(j0 + k, c) with k
+ * ascending for the tiles below (forward), sum_k L_(j0 + k, i) X_(j0 + k, c) with k descending for the
+ * tiles above (backward); a 3x3 register tile per thread, both operand tiles k-major in LDS */
+template <bool Fwd>
+__global__ __launch_bounds__(kPgsBlock) void k_pgc_update(PgCovJob C, int p)
+{
+    __shared__ double Lt[kPgsTile][kPgsTile + 1];
+    __shared__ double Pt[kPgsTile][kPgsTile + 1];
+    const PgSchurJob& Q = C.Q;
+    const int ti = Fwd ? p + 1 + blockIdx.x : blockIdx.x;
+    const int i0 = ti * kPgsTile, j0 = p * kPgsTile;
+    const size_t c0 = (size_t)blockIdx.y * kPgsTile;
+    for (int q = threadIdx.x; q < kPgsTile * kPgsTile; q += kPgsBlock) {
+        const int a = q / kPgsTile, b = q % kPgsTile;
+        if (Fwd)
+            Lt[b][a] = Q.S[(size_t)(i0 + a) * Q.np + j0 + b];
+        else
+            Lt[a][b] = Q.S[(size_t)(j0 + a) * Q.np + i0 + b];
+        Pt[a][b] = C.X[(size_t)(j0 + a) * C.ldx + c0 + b];
+    }
+    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+    double acc[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            acc[a][b] = C.X[(size_t)(i0 + ty + 16 * a) * C.ldx + c0 + tx + 16 * b];
+    __syncthreads();
+    const int kmax = (Q.n_s - j0 < kPgsTile) ? Q.n_s - j0 : kPgsTile;
+    for (int kk = 0; kk < kmax; ++kk) {
+        const int k = Fwd ? kk : kmax - 1 - kk;
+        double lv[3], pv[3];
+        for (int a = 0; a < 3; ++a) {
+            lv[a] = Lt[k][ty + 16 * a];
+            pv[a] = Pt[k][tx + 16 * a];
+        }
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b)
+                acc[a][b] -= lv[a] * pv[b];
+    }
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            C.X[(size_t)(i0 + ty + 16 * a) * C.ldx + c0 + tx + 16 * b] = acc[a][b];
+}
+
+__global__ __launch_bounds__(kPgsBlock) void k_pgc_pairs(PgCovJob C)
+{
+    const int q = blockIdx.x * kPgsBlock + threadIdx.x;
+    if (q >= C.n_pairs)
+        return;
+    pg_marginal_pair(C.Q.J, C.Q.w, C.X, (size_t)C.ldx, C.col_of, C.pairs[2 * q], C.pairs[2 * q + 1],
+                     C.out + 36 * (size_t)q);
+}
+
 } /* namespace csm */
 #endif

@@ -1531,6 +1531,42 @@ struct EdgePose {
     std::array<double, 9> mInformationMat;
 };
 
+/* A (local map node, scan node) pair whose marginal covariance is asked for; mScanNodeIdx = -1: the
+ * local map node alone */
+struct NodePair {
+    int mLocalMapNodeIdx;
+    int mScanNodeIdx;
+};
+
+/* csm_pose_graph_marginal with the blocks as row-major arrays */
+struct PairMarginal {
+    std::array<double, 9> localCov;
+    std::array<double, 9> scanCov;
+    std::array<double, 9> crossCov;
+    std::array<double, 9> relativeCov;
+    bool finite;
+};
+
+/* The loop search window (range x, y, theta: full widths in the local map's frame) from a pair's
+ * relativeCov: 2 nSigma standard deviations, clamped (csm_host_loop_search_ranges). Returns false for
+ * what that function refuses. */
+inline bool LoopSearchRanges(const std::array<double, 9>& relativeCov, double nSigma,
+                             const std::array<double, 3>& minRange, const std::array<double, 3>& maxRange,
+                             std::array<double, 3>& ranges)
+{
+    return csm_host_loop_search_ranges(relativeCov.data(), nSigma, minRange.data(), maxRange.data(),
+                                       ranges.data()) == CSM_OK;
+}
+
+/* The gate of a found loop against the graph's prediction: chi2 = d^T (relativeCov + matchCov)^-1 d with
+ * d = measured - predicted (csm_host_loop_gate). Returns false when the sum is not positive definite. */
+inline bool LoopGate(const std::array<double, 9>& relativeCov, const std::array<double, 9>& matchCov,
+                     const std::array<double, 3>& predicted, const std::array<double, 3>& measured, double& chi2)
+{
+    return csm_host_loop_gate(relativeCov.data(), matchCov.data(), predicted.data(), measured.data(), &chi2) ==
+           CSM_OK;
+}
+
 /* PoseGraphOptimizerLM (inc/mapping/pose_graph_optimizer_lm.hpp:84-160) on the device. Create()
  * takes the constructor's arguments with the loss function as (CSM_PG_LOSS_*, scale); it returns null
  * for SolverType SparseCholesky (SimplicialLDLT: not provided; SchurCholesky is the direct solver that
@@ -1573,6 +1609,56 @@ public:
     void Optimize(std::vector<std::array<double, 3>>& localMapNodes, std::vector<std::array<double, 3>>& scanNodes,
                   const std::vector<EdgePose>& poseGraphEdges)
     {
+        this->FillEdges(poseGraphEdges);
+        /* std::array<double, 3> is three contiguous doubles: the vectors are the flat pose arrays */
+        static_assert(sizeof(std::array<double, 3>) == 3 * sizeof(double), "pose layout");
+        CSM_ASSERT_OK(this->mCtx.get(),
+                      csm_pose_graph_lm(this->mCtx.get(), localMapNodes.empty() ? nullptr : localMapNodes.front().data(),
+                                        static_cast<std::int32_t>(localMapNodes.size()),
+                                        scanNodes.empty() ? nullptr : scanNodes.front().data(),
+                                        static_cast<std::int32_t>(scanNodes.size()), this->mEdges.data(),
+                                        static_cast<std::int32_t>(this->mEdges.size()), &this->mParams,
+                                        &this->mLambda, &this->mLast, nullptr));
+    }
+
+    /* The marginal covariances of the pairs at the given poses, under the optimizer's loss function
+     * (csm_pose_graph_marginals): how uncertain the graph is about each pair. */
+    std::vector<PairMarginal> ComputeMarginals(const std::vector<std::array<double, 3>>& localMapNodes,
+                                               const std::vector<std::array<double, 3>>& scanNodes,
+                                               const std::vector<EdgePose>& poseGraphEdges,
+                                               const std::vector<NodePair>& pairs)
+    {
+        this->FillEdges(poseGraphEdges);
+        std::vector<csm_pose_graph_pair> cp(pairs.size());
+        for (std::size_t i = 0; i < pairs.size(); ++i)
+            cp[i] = csm_pose_graph_pair { pairs[i].mLocalMapNodeIdx, pairs[i].mScanNodeIdx };
+        std::vector<csm_pose_graph_marginal> rec(pairs.size());
+        CSM_ASSERT_OK(this->mCtx.get(),
+                      csm_pose_graph_marginals(this->mCtx.get(),
+                                               localMapNodes.empty() ? nullptr : localMapNodes.front().data(),
+                                               static_cast<std::int32_t>(localMapNodes.size()),
+                                               scanNodes.empty() ? nullptr : scanNodes.front().data(),
+                                               static_cast<std::int32_t>(scanNodes.size()), this->mEdges.data(),
+                                               static_cast<std::int32_t>(this->mEdges.size()), this->mParams.loss_type,
+                                               this->mParams.loss_scale, cp.data(),
+                                               static_cast<std::int32_t>(cp.size()), rec.data(), nullptr));
+        std::vector<PairMarginal> out(rec.size());
+        for (std::size_t i = 0; i < rec.size(); ++i) {
+            std::copy(rec[i].local_cov, rec[i].local_cov + 9, out[i].localCov.begin());
+            std::copy(rec[i].scan_cov, rec[i].scan_cov + 9, out[i].scanCov.begin());
+            std::copy(rec[i].cross_cov, rec[i].cross_cov + 9, out[i].crossCov.begin());
+            std::copy(rec[i].relative_cov, rec[i].relative_cov + 9, out[i].relativeCov.begin());
+            out[i].finite = rec[i].finite != 0;
+        }
+        return out;
+    }
+
+private:
+    PoseGraphOptimizerLMHIP(const csm_pose_graph_lm_params& prm, double lambda, detail::CtxPtr ctx) :
+        mParams(prm), mLambda(lambda), mCtx(std::move(ctx)) { }
+
+    void FillEdges(const std::vector<EdgePose>& poseGraphEdges)
+    {
         this->mEdges.resize(poseGraphEdges.size());
         for (std::size_t i = 0; i < poseGraphEdges.size(); ++i) {
             const EdgePose& e = poseGraphEdges[i];
@@ -1586,20 +1672,7 @@ public:
             for (int j = 0; j < 9; ++j)
                 d.information[j] = e.mInformationMat[j];
         }
-        /* std::array<double, 3> is three contiguous doubles: the vectors are the flat pose arrays */
-        static_assert(sizeof(std::array<double, 3>) == 3 * sizeof(double), "pose layout");
-        CSM_ASSERT_OK(this->mCtx.get(),
-                      csm_pose_graph_lm(this->mCtx.get(), localMapNodes.empty() ? nullptr : localMapNodes.front().data(),
-                                        static_cast<std::int32_t>(localMapNodes.size()),
-                                        scanNodes.empty() ? nullptr : scanNodes.front().data(),
-                                        static_cast<std::int32_t>(scanNodes.size()), this->mEdges.data(),
-                                        static_cast<std::int32_t>(this->mEdges.size()), &this->mParams,
-                                        &this->mLambda, &this->mLast, nullptr));
     }
-
-private:
-    PoseGraphOptimizerLMHIP(const csm_pose_graph_lm_params& prm, double lambda, detail::CtxPtr ctx) :
-        mParams(prm), mLambda(lambda), mCtx(std::move(ctx)) { }
 
     const csm_pose_graph_lm_params mParams;
     double mLambda;
