@@ -740,6 +740,87 @@ int  csm_host_ray_check(const uint16_t* grid, int32_t rows, int32_t cols, const 
 int  csm_ray_check_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
                          const csm_ray_check_params* params, csm_ray_check_result* results, int32_t* per_beam);
 
+/* ---- pose sets: one scan scored at many free poses (the device form of ScoreFunction::Score,
+ * ScorePixelAccurate::Score, score_function_pixel_accurate.cpp:16-58), and the measurement update of a
+ * particle set on top of it. Every other scoring entry walks a regular window of whole search steps around
+ * one pose; here every pose is an arbitrary map-local SENSOR pose (relative_sensor_pose is not applied).
+ *
+ * Record of pose p. Its hit cells are those csm_host_project returns for sensor pose p with win_theta = 0
+ * (glibc, arg = theta + a_i, floor((h - off) / res)). S = the sum of the raw values of the hit cells that lie
+ * inside the map and are known (value != 0), K = their count: what csm_score_window reads at offset (0, 0).
+ * The order key is 32268 K + 499 S, as everywhere else. flags: 0, or CSM_POSE_UNCERTAIN |
+ * CSM_POSE_HOST_PROJECTED for a pose the device could not certify (below); csm_host_score_poses writes 0.
+ *
+ * Device. The cosine and sine of every beam angle are taken once per scan and those of theta once per pose;
+ * cos / sin(theta + a_i) come from the addition theorems, and an index counts only if floor() cannot flip
+ * within the error bound of the matchers' projection (two library calls, two products, one sum: 2.4e-15 +
+ * 4e-16 (|theta| + |a_i|) on the cosine, x64 margin on the quotient). A pose with any beam inside that
+ * margin of a cell edge is marked CSM_POSE_UNCERTAIN; after one read-back of their count the host projects
+ * exactly those poses with glibc and a second kernel scores them from the host's indices
+ * (CSM_POSE_HOST_PROJECTED). All sets of a call share each launch; sets that pass the same angles / ranges
+ * pointers and n_points stage the scan once.
+ *
+ * CSM_EINVAL, checked before anything is allocated: null pointers, n_sets < 0, n_poses < 0, n_points < 1, a
+ * non-finite pose, angle, range, offset or a resolution that is not finite and > 0, an unknown map_id, a pose
+ * whose cell coordinate could reach 2^30 in magnitude ((|x - off_x| + max |r|) / res >= 2^30, y alike).
+ * n_sets = 0 and n_poses = 0 are valid and launch nothing. */
+#define CSM_POSE_UNCERTAIN       1u   /* a beam within the certificate's margin of a cell edge */
+#define CSM_POSE_HOST_PROJECTED  2u   /* scored again from indices the host computed with glibc */
+#define CSM_POSE_SET_MAX_POSES   (1 << 18)   /* csm_pose_set_update: poses and outputs per call */
+typedef struct {
+    uint64_t      map_id;        /* any resident map: occupancy, likelihood field */
+    csm_geometry  geometry;
+    csm_scan      scan;          /* relative_sensor_pose is NOT applied: poses are sensor poses */
+    const double* poses;         /* [n_poses][3], map-local sensor poses */
+    int32_t       n_poses, reserved;
+} csm_pose_set;
+typedef struct { uint32_t sum_values, known, flags, reserved; } csm_pose_record;   /* S, K */
+typedef struct {
+    int64_t poses;               /* scored in this call */
+    int32_t uncertain_poses;     /* marked CSM_POSE_UNCERTAIN by the device */
+    int32_t changed_poses;       /* of them: records whose S or K differ after the rescore */
+    double  host_us;             /* glibc projection of the uncertain poses */
+    double  device_us;           /* first launch to last, HIP events on the ctx stream */
+} csm_pose_sets_info;
+/* out: the records of all sets, concatenated in set order. info may be NULL. */
+int  csm_score_pose_sets(csm_ctx* ctx, const csm_pose_set* sets, int32_t n_sets,
+                         csm_pose_record* out, csm_pose_sets_info* info);
+/* Host restatement on a dense row-major grid (no GPU needed); the same refusals. */
+int  csm_host_score_poses(const uint16_t* grid, int32_t rows, int32_t cols, const csm_geometry* geom,
+                          const csm_scan* scan, const double* poses, int32_t n_poses, csm_pose_record* out);
+/* One fixed f64 expression: score = ((double)(32268 K + 499 S) * c) / (double)n_points with c = 0.998 /
+ * (65534 * 499) as above (volume covariance), known_rate = (double)K / (double)n_points. It is not the
+ * beam-order sum: it lies within 1e-12 of ScorePixelAccurate's normalised score for n_points <= 1080 (N
+ * additions of terms <= 1 round by at most about N^2 2^-53 on the sum, 1.2e-13 after the division).
+ * CSM_EINVAL: n_points < 1 or a null pointer. */
+int  csm_host_score_from_sums(uint32_t sum_values, uint32_t known, int32_t n_points, double* score,
+                              double* known_rate);
+
+/* Measurement update of a pose set: integer weights and systematic resampling, exact integer arithmetic
+ * after the scoring, so the device equals csm_host_pose_set_update bit for bit.
+ *   eligible_i  K_i >= csm_host_min_known(n_points, known_rate_threshold)
+ *   key_max     the greatest key over eligible poses; best_index the first pose that has it
+ *   w_i         W[(key_max - key_i) >> bin_shift], W and bin_shift from csm_host_volume_weights(n_points,
+ *               temperature); 0 when that bin is >= CSM_VOLUME_BINS and for an ineligible pose
+ *   m0          sum w_i (u64); support = poses with w_i > 0
+ *   ancestors   C_i = the inclusive prefix sum of w in pose order, u = offset mod m0,
+ *               T_j = (j m0 + u) / n_out (integer division), ancestors[j] = the smallest i with C_i > T_j
+ * No eligible pose: found = 0, best_index = -1, key_max = m0 = support = 0, every weight 0, every ancestor -1.
+ * bin_shift is always the table's. Device chain behind the scoring and its rescore, no read-back between:
+ * keys, maximum, weights and their prefix sums (one workgroup, wavefront scans), one binary search per output.
+ * CSM_EINVAL: n_poses or n_out above CSM_POSE_SET_MAX_POSES (j m0 + u stays below 2^61), n_out < 0, a
+ * temperature csm_host_volume_weights refuses, a known_rate_threshold that is NaN, and what
+ * csm_score_pose_sets refuses. records [n_poses], weights [n_poses], ancestors [n_out]; weights and
+ * ancestors may be NULL (n_poses = 0, n_out = 0). */
+typedef struct { double temperature; double known_rate_threshold; int32_t n_out, reserved; uint64_t offset; } csm_pose_update_params;
+typedef struct { uint64_t m0; uint64_t key_max; int32_t best_index, support, bin_shift, found; } csm_pose_update_info;
+int  csm_pose_set_update(csm_ctx* ctx, const csm_pose_set* set, const csm_pose_update_params* params,
+                         csm_pose_record* records, uint32_t* weights, int32_t* ancestors,
+                         csm_pose_update_info* update, csm_pose_sets_info* info);
+int  csm_host_pose_set_update(const csm_pose_record* records, int32_t n_poses, int32_t n_points,
+                              const csm_pose_update_params* params, uint32_t* weights, int32_t* ancestors,
+                              csm_pose_update_info* update);
+
 /* The raw records (csm_summary.raw) of the last csm_bnb_match_batch /
  * csm_correlative_match_batch call on this ctx, in query order, copied device
  * to device into dst_dev[n_queries] on the ctx stream (asynchronous): the
@@ -1400,7 +1481,8 @@ int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
 /* Drains recorded events; returns total ms and launch count since the last
  * reset for kernel "score_fine" | "score_coarse" | "bin" | "finalize" | "boxmax" |
  * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select" | "likelihood" |
- * "ray_project" | "ray_walk" | "pose_graph" | "pose_graph_marginals" |
+ * "ray_project" | "ray_walk" | "pose_prep" | "pose_score" | "pose_rescore" | "pose_weights" |
+ * "pose_resample" | "pose_graph" | "pose_graph_marginals" |
  * "pose_graph_marginals_factor" | "pose_graph_marginals_solve". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);

@@ -298,6 +298,34 @@ class RayCheckResult(C.Structure):
                 ("max_depth", C.c_int32), ("host_beams", C.c_int32)]
 
 
+POSE_UNCERTAIN, POSE_HOST_PROJECTED = 1, 2
+POSE_SET_MAX_POSES = 1 << 18
+
+
+class PoseSet(C.Structure):
+    _fields_ = [("map_id", C.c_uint64), ("geometry", Geometry), ("scan", Scan), ("poses", C.POINTER(C.c_double)),
+                ("n_poses", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PoseRecord(C.Structure):
+    _fields_ = [("sum_values", C.c_uint32), ("known", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PoseSetsInfo(C.Structure):
+    _fields_ = [("poses", C.c_int64), ("uncertain_poses", C.c_int32), ("changed_poses", C.c_int32),
+                ("host_us", C.c_double), ("device_us", C.c_double)]
+
+
+class PoseUpdateParams(C.Structure):
+    _fields_ = [("temperature", C.c_double), ("known_rate_threshold", C.c_double), ("n_out", C.c_int32),
+                ("reserved", C.c_int32), ("offset", C.c_uint64)]
+
+
+class PoseUpdateInfo(C.Structure):
+    _fields_ = [("m0", C.c_uint64), ("key_max", C.c_uint64), ("best_index", C.c_int32), ("support", C.c_int32),
+                ("bin_shift", C.c_int32), ("found", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/csm_hip.h one to one
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -379,6 +407,14 @@ SIGNATURES = {
                                      _P(RayCheckParams), _P(RayCheckResult), C.c_void_p]),
     "csm_ray_check_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(RayCheckParams), _P(RayCheckResult),
                                       C.c_void_p]),
+    "csm_score_pose_sets": (C.c_int, [_ctx, _P(PoseSet), C.c_int32, C.c_void_p, _P(PoseSetsInfo)]),
+    "csm_host_score_poses": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(Geometry), _P(Scan), C.c_void_p,
+                                       C.c_int32, C.c_void_p]),
+    "csm_host_score_from_sums": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int32, _P(C.c_double), _P(C.c_double)]),
+    "csm_pose_set_update": (C.c_int, [_ctx, _P(PoseSet), _P(PoseUpdateParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      _P(PoseUpdateInfo), _P(PoseSetsInfo)]),
+    "csm_host_pose_set_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(PoseUpdateParams), C.c_void_p,
+                                           C.c_void_p, _P(PoseUpdateInfo)]),
     "csm_bnb_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,
                                       _P(BnbParams), _P(Summary)]),
     "csm_correlative_match_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32,

@@ -458,6 +458,69 @@ def host_ray_check(grid, geom, angles, ranges, rel_pose, pose, per_beam=False, p
     return (ray_check_to_dict(out), words[:sc.n_points]) if per_beam else ray_check_to_dict(out)
 
 
+POSE_RECORD = np.dtype([("sum_values", "<u4"), ("known", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+
+
+def _poses(poses):
+    p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    return p
+
+
+def host_score_poses(grid, geom, angles, ranges, poses):
+    """csm_host_score_poses: the (S, K) record of the scan at every map-local sensor pose of `poses` (n, 3) on
+    a dense grid, as a POSE_RECORD array."""
+    g = np.ascontiguousarray(grid, dtype=np.uint16)
+    sc, keep = _scan_struct(angles, ranges, (0.0, 0.0, 0.0))
+    p = _poses(poses)
+    out = np.zeros(p.shape[0], POSE_RECORD)
+    rc = L.load().csm_host_score_poses(_ptr(g), g.shape[0], g.shape[1], C.byref(L.Geometry(*geom)), C.byref(sc),
+                                       _ptr(p), p.shape[0], _ptr(out))
+    if rc:
+        raise CsmError(rc, "csm_host_score_poses")
+    return out
+
+
+def host_score_from_sums(sum_values, known, n_points):
+    """csm_host_score_from_sums: (normalised score, known rate) of a record."""
+    score, rate = C.c_double(), C.c_double()
+    rc = L.load().csm_host_score_from_sums(int(sum_values), int(known), n_points, C.byref(score), C.byref(rate))
+    if rc:
+        raise CsmError(rc, "csm_host_score_from_sums")
+    return score.value, rate.value
+
+
+def pose_update_to_dict(u):
+    return dict(m0=int(u.m0), key_max=int(u.key_max), best_index=int(u.best_index), support=int(u.support),
+                bin_shift=int(u.bin_shift), found=int(u.found))
+
+
+def pose_sets_info_to_dict(i):
+    return dict(poses=int(i.poses), uncertain_poses=int(i.uncertain_poses), changed_poses=int(i.changed_poses),
+                host_us=float(i.host_us), device_us=float(i.device_us))
+
+
+def host_pose_set_update(records, n_points, temperature, known_rate_threshold=0.0, n_out=None, offset=0):
+    """csm_host_pose_set_update on a POSE_RECORD array: (weights uint32, ancestors int32, update dict)."""
+    rec = np.ascontiguousarray(records, dtype=POSE_RECORD)
+    n_out = rec.size if n_out is None else n_out
+    prm = L.PoseUpdateParams(temperature, known_rate_threshold, n_out, 0, offset & 0xFFFFFFFFFFFFFFFF)
+    weights = np.zeros(max(rec.size, 1), np.uint32)
+    ancestors = np.zeros(max(n_out, 1), np.int32)
+    upd = L.PoseUpdateInfo()
+    rc = L.load().csm_host_pose_set_update(_ptr(rec), rec.size, n_points, C.byref(prm), _ptr(weights),
+                                           _ptr(ancestors), C.byref(upd))
+    if rc:
+        raise CsmError(rc, "csm_host_pose_set_update")
+    return weights[:rec.size], ancestors[:max(n_out, 0)], pose_update_to_dict(upd)
+
+
+def effective_sample_size(weights):
+    """(sum w)^2 / sum w^2 in f64, 0.0 when every weight is 0 (not part of the C ABI)."""
+    w = np.asarray(weights, dtype=np.float64)
+    s2 = float(np.sum(w * w))
+    return float(np.sum(w)) ** 2 / s2 if s2 > 0.0 else 0.0
+
+
 def host_probability_lut():
     lut = np.zeros(65536)
     L.load().csm_host_probability_lut(_ptr(lut))
@@ -1160,6 +1223,85 @@ class Context:
         out = (L.Summary * prep.n)()
         self._check(self.lib.csm_correlative_match_batch(self._ctx, prep.arr, prep.n, C.byref(p), out))
         return SummaryArray(out) if as_records else [summary_to_dict(o) for o in out]
+
+    def _pose_sets(self, sets):
+        """A csm_pose_set array for dicts(map_id, geom, angles, ranges, poses); sets that pass the same angle
+        and range arrays share their pointers, so the library stages the scan once."""
+        arr = (L.PoseSet * max(len(sets), 1))()
+        keep, counts = [], []
+        for i, s in enumerate(sets):
+            a, r, p = _f64(s["angles"]), _f64(s["ranges"]), _poses(s["poses"])
+            keep += [a, r, p]
+            arr[i].map_id = s["map_id"]
+            arr[i].geometry = L.Geometry(*s["geom"])
+            arr[i].scan.angles = a.ctypes.data_as(C.POINTER(C.c_double))
+            arr[i].scan.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
+            arr[i].scan.n_points = a.size
+            arr[i].poses = p.ctypes.data_as(C.POINTER(C.c_double))
+            arr[i].n_poses = p.shape[0]
+            counts.append(p.shape[0])
+        return arr, keep, counts
+
+    def score_pose_sets(self, sets):
+        """csm_score_pose_sets: every set's scan at every map-local SENSOR pose of the set, all sets in one
+        launch chain. sets: dicts(map_id, geom, angles, ranges, poses (n, 3)). Returns (a POSE_RECORD array
+        per set, the call's info dict)."""
+        arr, keep, counts = self._pose_sets(sets)
+        out = np.zeros(max(sum(counts), 1), POSE_RECORD)
+        info = L.PoseSetsInfo()
+        self._check(self.lib.csm_score_pose_sets(self._ctx, arr, len(sets), _ptr(out), C.byref(info)))
+        ends = np.cumsum([0] + counts)
+        return [out[ends[i]:ends[i + 1]].copy() for i in range(len(sets))], pose_sets_info_to_dict(info)
+
+    def pose_set_update(self, map_id, geom, angles, ranges, poses, temperature, known_rate_threshold=0.0,
+                        n_out=None, offset=0):
+        """csm_pose_set_update: scores the set and turns the scores into integer weights and a systematically
+        resampled set of n_out ancestors (default: as many as poses). Returns a dict(records, weights,
+        ancestors, update, info)."""
+        arr, keep, counts = self._pose_sets([dict(map_id=map_id, geom=geom, angles=angles, ranges=ranges,
+                                                  poses=poses)])
+        n = counts[0]
+        n_out = n if n_out is None else n_out
+        prm = L.PoseUpdateParams(temperature, known_rate_threshold, n_out, 0, offset & 0xFFFFFFFFFFFFFFFF)
+        rec = np.zeros(max(n, 1), POSE_RECORD)
+        weights = np.zeros(max(n, 1), np.uint32)
+        ancestors = np.zeros(max(n_out, 1), np.int32)
+        upd, info = L.PoseUpdateInfo(), L.PoseSetsInfo()
+        self._check(self.lib.csm_pose_set_update(self._ctx, arr, C.byref(prm), _ptr(rec), _ptr(weights),
+                                                 _ptr(ancestors), C.byref(upd), C.byref(info)))
+        return dict(records=rec[:n], weights=weights[:n], ancestors=ancestors[:max(n_out, 0)],
+                    update=pose_update_to_dict(upd), info=pose_sets_info_to_dict(info))
+
+    def score_pixel_accurate_many(self, map_id, geom, angles, ranges, poses, rel_pose=None):
+        """ScorePixelAccurate::Score at many poses: a list of dict(normalized_score, score, known_rate,
+        sum_values, known, flags). poses are map-local sensor poses, or robot poses when rel_pose (the scan's
+        relative sensor pose) is given: csm_host_compound is then applied on the host."""
+        p = _poses(poses)
+        if rel_pose is not None:
+            p = np.array([host_compound(q, rel_pose) for q in p]).reshape(-1, 3)
+        recs, _ = self.score_pose_sets([dict(map_id=map_id, geom=geom, angles=angles, ranges=ranges, poses=p)])
+        n = _f64(angles).size
+        out = []
+        for r in recs[0]:
+            norm, rate = host_score_from_sums(r["sum_values"], r["known"], n)
+            out.append(dict(normalized_score=norm, score=norm * n, known_rate=rate, sum_values=int(r["sum_values"]),
+                            known=int(r["known"]), flags=int(r["flags"])))
+        return out
+
+    def score_pixel_accurate(self, map_id, geom, angles, ranges, pose, rel_pose=None):
+        """ScorePixelAccurate::Score(gridMap, scan, mapLocalSensorPose) at one pose."""
+        return self.score_pixel_accurate_many(map_id, geom, angles, ranges, [pose], rel_pose)[0]
+
+    def measurement_update(self, map_id, geom, angles, ranges, poses, temperature, known_rate_threshold=0.0,
+                           n_out=None, offset=0, rel_pose=None):
+        """ParticleSetHIP::MeasurementUpdate: pose_set_update plus the effective sample size of the weights
+        (f64, on the host). Robot poses when rel_pose is given."""
+        p = _poses(poses)
+        if rel_pose is not None:
+            p = np.array([host_compound(q, rel_pose) for q in p]).reshape(-1, 3)
+        out = self.pose_set_update(map_id, geom, angles, ranges, p, temperature, known_rate_threshold, n_out, offset)
+        out["effective_sample_size"] = effective_sample_size(out["weights"])
+        return out
 
     def ray_check_batch(self, queries, poses=None, per_beam=False, params=None, **kw):
         """csm_ray_check_batch: the free-space check of every query's scan against its resident map at the

@@ -241,6 +241,10 @@ struct csm_ctx {
      * (uncertified list, records, per-beam words, ray records, patches); pinned staging up and back */
     DevBuf rc_tab, rc_work;
     PinBuf rc_pin, rc_back;
+    /* pose sets (csm_poses_api.hip): a call's tables, scans and poses; its work block (marked poses, records,
+     * weights, ancestors, triples, prefix sums); the host's indices of the marked poses; pinned staging */
+    DevBuf ps_tab, ps_work, ps_fix;
+    PinBuf ps_pin, ps_back;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */

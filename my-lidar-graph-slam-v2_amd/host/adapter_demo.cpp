@@ -11,6 +11,8 @@
  *   double rel[3]; double init[3 * n_queries]; double angles[n]; double ranges[n]
  *   uint16 grid[rows * cols]
  * mode 5 (pose-graph optimizer) has a layout of its own: see run_pose_graph.
+ * mode 7 (pose sets) reads the common layout as: n_queries = robot poses in init, param_i = outputs of the
+ *   resampling, rangeX = temperature, rangeY / rangeT = the low / high 32 bits of the resampling offset.
  */
 #include <cinttypes>
 #include <cstdio>
@@ -227,6 +229,42 @@ int main(int argc, char** argv)
         std::printf("{\"found\": %d, \"pose\": [\"%a\", \"%a\", \"%a\"], \"score\": \"%a\", \"win\": [%d, %d, %d]}\n",
                     r.mPoseFound ? 1 : 0, r.mEstimatedPose.mX, r.mEstimatedPose.mY,
                     r.mEstimatedPose.mTheta, r.mScoreValue, r.mWinSizeX, r.mWinSizeY, r.mWinSizeTheta);
+        return 0;
+    }
+    if (mode == 7) {
+        /* ScorePixelAccurateHIP at one robot pose and at all of them, ParticleSetHIP on the same context */
+        auto scorer = ScorePixelAccurateHIP::Create();
+        if (!scorer) {
+            std::printf("{\"error\": \"no device\"}\n");
+            return 3;
+        }
+        g.mId = 42;
+        scorer->Upload(g);
+        const csm_geometry geom = { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
+        std::vector<RobotPose2D<double>> robot(nq);
+        for (int i = 0; i < nq; ++i)
+            robot[i] = { init[3 * i], init[3 * i + 1], init[3 * i + 2] };
+        const std::vector<RobotPose2D<double>> sensor = ScorePixelAccurateHIP::SensorPoses(s, robot);
+        const ScoreSummary one = scorer->Score(g.mId, geom, s, sensor.front());
+        const std::vector<ScoreSummary> all = scorer->ScoreManyRobotPoses(g.mId, geom, s, robot);
+        ParticleSetHIP particles(scorer->Context(), prm[3], prm[7]);
+        const std::uint64_t offset = ((std::uint64_t)prm[5] << 32) | (std::uint64_t)prm[4];
+        const ParticleSetHIP::Update u = particles.MeasurementUpdate(g.mId, geom, s, sensor, (size_t)pi, offset);
+        std::printf("{\"one\": [%u, %u, \"%a\", \"%a\", \"%a\"], \"all\": [", one.mSumValues, one.mKnown,
+                    one.mNormalizedScore, one.mScore, one.mKnownRate);
+        for (size_t i = 0; i < all.size(); ++i)
+            std::printf("%s[%u, %u, \"%a\", \"%a\", \"%a\"]", i ? ", " : "", all[i].mSumValues, all[i].mKnown,
+                        all[i].mNormalizedScore, all[i].mScore, all[i].mKnownRate);
+        std::printf("], \"weights\": [");
+        for (size_t i = 0; i < u.mWeights.size(); ++i)
+            std::printf("%s%u", i ? ", " : "", u.mWeights[i]);
+        std::printf("], \"ancestors\": [");
+        for (size_t i = 0; i < u.mAncestors.size(); ++i)
+            std::printf("%s%d", i ? ", " : "", u.mAncestors[i]);
+        std::printf("], \"ess\": \"%a\", \"m0\": %llu, \"key_max\": %llu, \"best_index\": %d, \"support\": %d, "
+                    "\"bin_shift\": %d, \"found\": %d, \"uncertain\": %d}\n", u.mEffectiveSampleSize,
+                    (unsigned long long)u.mUpdate.m0, (unsigned long long)u.mUpdate.key_max, u.mUpdate.best_index,
+                    u.mUpdate.support, u.mUpdate.bin_shift, u.mUpdate.found, u.mInfo.uncertain_poses);
         return 0;
     }
     /* CSM_DEMO_DEVICES="0,0": the detector over a device list (here two members on GPU 0) */

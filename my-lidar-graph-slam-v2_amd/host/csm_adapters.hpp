@@ -12,6 +12,9 @@
  *        inc/mapping/scan_matcher_grid_search.hpp, src/mapping/scan_matcher_grid_search.cpp:69-190
  *   GridMapBuilderHIP           <- GridMapBuilder (latest-map part)
  *        inc/mapping/grid_map_builder.hpp, src/mapping/grid_map_builder.cpp:497-527, 561-695
+ *   ScorePixelAccurateHIP       <- ScorePixelAccurate (ScoreFunction::Score at free poses)
+ *        inc/mapping/score_function.hpp:29-60, src/mapping/score_function_pixel_accurate.cpp:16-58
+ *   ParticleSetHIP              (beyond the reference) weights and resampling of a particle set
  *
  * The reference headers cannot be included in this image (Eigen3 / Boost are
  * absent), so the few value types the interfaces use are restated here in
@@ -1679,6 +1682,176 @@ private:
     detail::CtxPtr mCtx;
     std::vector<csm_pose_graph_edge> mEdges;
     csm_pose_graph_lm_info mLast {};
+};
+
+/* ScoreFunction::Summary (inc/mapping/score_function.hpp:29-45) plus the integers it came from */
+struct ScoreSummary {
+    double mNormalizedScore = 0.0;
+    double mScore = 0.0;
+    double mKnownRate = 0.0;
+    std::uint32_t mSumValues = 0, mKnown = 0, mFlags = 0;
+};
+
+/* ScorePixelAccurate (inc/mapping/score_function_pixel_accurate.hpp, src/mapping/
+ * score_function_pixel_accurate.cpp:16-58) on the device: Score(gridMap, scan, mapLocalSensorPose) for a
+ * resident map, at one pose or at many in one launch chain (csm_score_pose_sets). The doubles come from
+ * the integer sums through csm_host_score_from_sums: within 1e-12 of the reference's beam-order sum. A map is
+ * made resident with Upload() or by any other adapter that shares the context. */
+class ScorePixelAccurateHIP final {
+public:
+    static std::unique_ptr<ScorePixelAccurateHIP> Create(int deviceId = 0)
+    {
+        detail::CtxPtr ctx = detail::MakeContext(deviceId);
+        if (!ctx)
+            return nullptr;
+        return std::unique_ptr<ScorePixelAccurateHIP>(new ScorePixelAccurateHIP(std::move(ctx), nullptr));
+    }
+    /* on a context another adapter owns (and keeps alive) */
+    explicit ScorePixelAccurateHIP(csm_ctx* shared) : mShared(shared) { }
+
+    ScorePixelAccurateHIP(const ScorePixelAccurateHIP&) = delete;
+    ScorePixelAccurateHIP& operator=(const ScorePixelAccurateHIP&) = delete;
+
+    csm_ctx* Context() const { return this->mOwned ? this->mOwned.get() : this->mShared; }
+    const csm_pose_sets_info& LastInfo() const { return this->mLast; }
+
+    void Upload(const GridMapView& g)
+    {
+        CSM_ASSERT_OK(this->Context(), csm_upload_grid(this->Context(), g.mId, g.mValues, g.mRows, g.mCols));
+    }
+
+    ScoreSummary Score(std::uint64_t mapId, const csm_geometry& geometry, const ScanDataView& scan,
+                       const RobotPose2D<double>& mapLocalSensorPose)
+    {
+        return this->ScoreMany(mapId, geometry, scan, { mapLocalSensorPose }).front();
+    }
+
+    std::vector<ScoreSummary> ScoreMany(std::uint64_t mapId, const csm_geometry& geometry, const ScanDataView& scan,
+                                        const std::vector<RobotPose2D<double>>& mapLocalSensorPoses)
+    {
+        static_assert(sizeof(RobotPose2D<double>) == 3 * sizeof(double), "pose layout");
+        csm_pose_set set {};
+        set.map_id = mapId;
+        set.geometry = geometry;
+        set.scan = detail::ToScan(scan);
+        set.poses = mapLocalSensorPoses.empty() ? nullptr : &mapLocalSensorPoses.front().mX;
+        set.n_poses = static_cast<std::int32_t>(mapLocalSensorPoses.size());
+        std::vector<csm_pose_record> rec(mapLocalSensorPoses.size());
+        CSM_ASSERT_OK(this->Context(), csm_score_pose_sets(this->Context(), &set, 1, rec.data(), &this->mLast));
+        std::vector<ScoreSummary> out(rec.size());
+        for (std::size_t i = 0; i < rec.size(); ++i) {
+            ScoreSummary& o = out[i];
+            CSM_ASSERT_OK(this->Context(), csm_host_score_from_sums(rec[i].sum_values, rec[i].known, set.scan.n_points,
+                                                                    &o.mNormalizedScore, &o.mKnownRate));
+            o.mScore = o.mNormalizedScore * static_cast<double>(set.scan.n_points);
+            o.mSumValues = rec[i].sum_values;
+            o.mKnown = rec[i].known;
+            o.mFlags = rec[i].flags;
+        }
+        return out;
+    }
+
+    /* The same for map-local ROBOT poses: the scan's relative sensor pose is applied on the host
+     * (Compound, inc/pose.hpp:154-166), as the matchers do before they score. */
+    std::vector<ScoreSummary> ScoreManyRobotPoses(std::uint64_t mapId, const csm_geometry& geometry,
+                                                  const ScanDataView& scan,
+                                                  const std::vector<RobotPose2D<double>>& mapLocalRobotPoses)
+    {
+        return this->ScoreMany(mapId, geometry, scan, SensorPoses(scan, mapLocalRobotPoses));
+    }
+
+    static std::vector<RobotPose2D<double>> SensorPoses(const ScanDataView& scan,
+                                                        const std::vector<RobotPose2D<double>>& robotPoses)
+    {
+        const double rel[3] = { scan.mRelativeSensorPose.mX, scan.mRelativeSensorPose.mY,
+                                scan.mRelativeSensorPose.mTheta };
+        std::vector<RobotPose2D<double>> out(robotPoses.size());
+        for (std::size_t i = 0; i < robotPoses.size(); ++i) {
+            const double p[3] = { robotPoses[i].mX, robotPoses[i].mY, robotPoses[i].mTheta };
+            double s[3];
+            csm_host_compound(p, rel, s);
+            out[i] = { s[0], s[1], s[2] };
+        }
+        return out;
+    }
+
+private:
+    ScorePixelAccurateHIP(detail::CtxPtr owned, csm_ctx* shared) : mOwned(std::move(owned)), mShared(shared) { }
+
+    detail::CtxPtr mOwned;
+    csm_ctx* mShared = nullptr;
+    csm_pose_sets_info mLast {};
+};
+
+/* The measurement update of a particle filter that localises in a finished map (beyond the reference, which
+ * has no such filter): every particle's sensor pose scored against the map or its likelihood field, integer
+ * weights exp(-(score_max - score) / temperature) in 2^-24 units and a systematically resampled set, all in
+ * one launch chain (csm_pose_set_update). */
+class ParticleSetHIP final {
+public:
+    struct Update {
+        std::vector<csm_pose_record> mRecords;
+        std::vector<std::uint32_t> mWeights;
+        std::vector<std::int32_t> mAncestors;      /* index of the particle each output copies, -1: none */
+        double mEffectiveSampleSize = 0.0;         /* (sum w)^2 / sum w^2 in double, on the host */
+        csm_pose_update_info mUpdate {};
+        csm_pose_sets_info mInfo {};
+    };
+
+    static std::unique_ptr<ParticleSetHIP> Create(double temperature, double knownRateThreshold, int deviceId = 0)
+    {
+        detail::CtxPtr ctx = detail::MakeContext(deviceId);
+        if (!ctx)
+            return nullptr;
+        return std::unique_ptr<ParticleSetHIP>(new ParticleSetHIP(temperature, knownRateThreshold, std::move(ctx), nullptr));
+    }
+    ParticleSetHIP(csm_ctx* shared, double temperature, double knownRateThreshold) :
+        mTemperature(temperature), mKnownRateThreshold(knownRateThreshold), mShared(shared) { }
+
+    ParticleSetHIP(const ParticleSetHIP&) = delete;
+    ParticleSetHIP& operator=(const ParticleSetHIP&) = delete;
+
+    csm_ctx* Context() const { return this->mOwned ? this->mOwned.get() : this->mShared; }
+
+    /* `offset` places the comb of the systematic resampling: any 64-bit draw of the caller's generator */
+    Update MeasurementUpdate(std::uint64_t mapId, const csm_geometry& geometry, const ScanDataView& scan,
+                             const std::vector<RobotPose2D<double>>& mapLocalSensorPoses, std::size_t numOfOutputs,
+                             std::uint64_t offset)
+    {
+        csm_pose_set set {};
+        set.map_id = mapId;
+        set.geometry = geometry;
+        set.scan = detail::ToScan(scan);
+        set.poses = mapLocalSensorPoses.empty() ? nullptr : &mapLocalSensorPoses.front().mX;
+        set.n_poses = static_cast<std::int32_t>(mapLocalSensorPoses.size());
+        csm_pose_update_params prm {};
+        prm.temperature = this->mTemperature;
+        prm.known_rate_threshold = this->mKnownRateThreshold;
+        prm.n_out = static_cast<std::int32_t>(numOfOutputs);
+        prm.offset = offset;
+        Update out;
+        out.mRecords.resize(mapLocalSensorPoses.size());
+        out.mWeights.resize(mapLocalSensorPoses.size());
+        out.mAncestors.resize(numOfOutputs);
+        CSM_ASSERT_OK(this->Context(), csm_pose_set_update(this->Context(), &set, &prm, out.mRecords.data(),
+                                                           out.mWeights.data(), out.mAncestors.data(), &out.mUpdate,
+                                                           &out.mInfo));
+        double sum = 0.0, sumSq = 0.0;
+        for (std::uint32_t w : out.mWeights) {
+            sum += static_cast<double>(w);
+            sumSq += static_cast<double>(w) * static_cast<double>(w);
+        }
+        out.mEffectiveSampleSize = sumSq > 0.0 ? sum * sum / sumSq : 0.0;
+        return out;
+    }
+
+private:
+    ParticleSetHIP(double temperature, double knownRateThreshold, detail::CtxPtr owned, csm_ctx* shared) :
+        mTemperature(temperature), mKnownRateThreshold(knownRateThreshold), mOwned(std::move(owned)), mShared(shared) { }
+
+    const double mTemperature, mKnownRateThreshold;
+    detail::CtxPtr mOwned;
+    csm_ctx* mShared = nullptr;
 };
 
 } /* namespace CsmHip */
