@@ -3,6 +3,9 @@ in numpy over the oracle's own projection (oracle.project: HitPoint + PositionTo
 weights and ancestors in plain integer Python. Also the seeded maps, scans and poses that
 tests/test_cpu_pose_sets.py, tests/test_gpu_pose_sets.py and tests/test_gpu_pose_sets_adapter.py share, and the
 certificate's margin in numpy (how many poses of a case the device will hand to the host)."""
+import bisect
+import itertools
+
 import numpy as np
 
 from csm_hip import api
@@ -96,6 +99,37 @@ def update(S, K, n_points, temperature, threshold=0.0, n_out=None, offset=0):
         t = (j * info["m0"] + offset % info["m0"]) // n_out
         ancestors.append(next(i for i in range(n) if prefix[i] > t))
     return weights, ancestors, info
+
+
+def update_fast(S, K, n_points, temperature, threshold=0.0, n_out=None, offset=0):
+    """update() for sets too large for its quadratic searches (2^18 poses, 2^18 outputs): the same result from
+    one pass for the maximum, itertools.accumulate for the prefix and bisect_right for the ancestors (the
+    smallest i with prefix[i] > t). Python integers throughout; tests/test_cpu_pose_sets_cases.py pins it to
+    update(), which stays the definition."""
+    table, shift = api.host_volume_weights(n_points, temperature)
+    table = [int(w) for w in table]
+    n = len(S)
+    n_out = n if n_out is None else n_out
+    need = min_known(n_points, threshold)
+    keys = [32268 * int(k) + 499 * int(s) for s, k in zip(S, K)]
+    eligible = [int(k) >= need for k in K]
+    info = dict(m0=0, key_max=0, best_index=-1, support=0, bin_shift=shift, found=0)
+    for i in range(n):                                   # strict >: the first holder of the maximum stays
+        if eligible[i] and (not info["found"] or keys[i] > info["key_max"]):
+            info["key_max"], info["best_index"], info["found"] = keys[i], i, 1
+    weights = [0] * n
+    if info["found"]:
+        for i in range(n):
+            if eligible[i]:
+                b = (info["key_max"] - keys[i]) >> shift
+                weights[i] = table[b] if b < VOLUME_BINS else 0
+    prefix = list(itertools.accumulate(weights))
+    info["m0"] = prefix[-1] if n else 0
+    info["support"] = sum(1 for w in weights if w > 0)
+    if not info["found"]:
+        return weights, [-1] * n_out, info
+    m0, u = info["m0"], offset % info["m0"]
+    return weights, [bisect.bisect_right(prefix, (j * m0 + u) // n_out) for j in range(n_out)], info
 
 
 def margin_uncertain(geom, angles, ranges, poses):
