@@ -761,11 +761,12 @@ int  csm_ray_check_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_
  * pointers and n_points stage the scan once.
  *
  * CSM_EINVAL, checked before anything is allocated: null pointers, n_sets < 0, n_poses < 0, n_points < 1, a
- * non-finite pose, angle, range, offset or a resolution that is not finite and > 0, an unknown map_id, a pose
+ * non-finite pose, angle, range, offset or a resolution that is not finite and > 0, a pose
  * whose cell coordinate could reach 2^30 in magnitude ((|x - off_x| + max |r|) / res >= 2^30, y alike),
  * n_points > 65536 (65536 values of at most 65535 keep S within 32 bits, 0xFFFF0000 at the most, and the key
  * below 2^42), 2^30 or more poses in one call, 2^30 or more beams of distinct scans in one call. Ranges may be
- * zero or negative. n_sets = 0 and n_poses = 0 are valid and launch nothing. */
+ * zero or negative. n_sets = 0 and n_poses = 0 are valid and launch nothing.
+ * CSM_ENOENT, checked as early: a map_id that is not resident (as every other entry reports it). */
 #define CSM_POSE_UNCERTAIN       1u   /* a beam within the certificate's margin of a cell edge */
 #define CSM_POSE_HOST_PROJECTED  2u   /* scored again from indices the host computed with glibc */
 #define CSM_POSE_SET_MAX_POSES   (1 << 18)   /* csm_pose_set_update: poses and outputs per call */

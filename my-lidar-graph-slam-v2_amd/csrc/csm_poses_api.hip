@@ -100,7 +100,7 @@ int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record
                         "ranges and geometry, a resolution > 0, and cell coordinates below 2^30", k, kPoseMaxPoints);
         const DeviceGrid* g = find_grid(ctx, s.map_id);
         if (!g || g->levels.empty())
-            return fail(ctx, CSM_EINVAL, "pose set %d: map %llu is not resident", k, (unsigned long long)s.map_id);
+            return fail(ctx, CSM_ENOENT, "pose set %d: map %llu is not resident", k, (unsigned long long)s.map_id);
         total_ll += s.n_poses;
     }
     if (total_ll >= kPoseMaxCallPoses)

@@ -198,11 +198,18 @@ def test_refusals_run_nothing(resident):
     bad_angle[0] = np.nan
     far = poses.copy()
     far[0, 0] = 0.05 * 2.0 ** 30
-    for bad in (dict(good, poses=bad_pose), dict(good, angles=bad_angle), dict(good, map_id=MAP_ID + 77),
+    for bad in (dict(good, poses=bad_pose), dict(good, angles=bad_angle),
                 dict(good, poses=far), dict(good, angles=a[:0], ranges=r[:0])):
         with pytest.raises(api.CsmError) as e:
             ctx.score_pose_sets([good, bad])
         assert e.value.code == L.CSM_EINVAL
+    assert not ctx.has_grid(MAP_ID + 77)
+    with pytest.raises(api.CsmError) as e:                                          # a map that is not resident
+        ctx.score_pose_sets([good, dict(good, map_id=MAP_ID + 77)])
+    assert e.value.code == L.CSM_ENOENT
+    with pytest.raises(api.CsmError) as e:
+        ctx.pose_set_update(MAP_ID + 77, R.GEOM, a, r, poses, 0.05)
+    assert e.value.code == L.CSM_ENOENT
     for kw in (dict(n_out=-1), dict(n_out=(1 << 18) + 1), dict(temperature=0.0), dict(temperature=float("nan"))):
         args = dict(temperature=0.05, n_out=4)
         args.update(kw)

@@ -4,138 +4,43 @@ the coarse-first search, the pyramid of branch and bound, the block-allocation b
 recorded HIP graphs. Each cell warms a consumer on a map (three identical calls, so a graph is
 recorded), changes the map in place of the same id, calls the consumer twice more and compares
 every output with `==` against a fresh map id holding the final cells, uploaded dense, and
-against the oracle's matcher where one exists. The final cells themselves are first checked
-against the oracle's map (construct_map / update_map).
+against the oracle's matcher or the consumer's numpy reference. The final cells themselves are
+first checked against the oracle's map (construct_map / update_map) or the likelihood reference.
+
+The worlds (tests/resident_state_cases.py; tests/test_cpu_resident_state_cases.py proves that stale
+state would change every cell's answer) are twelve mutations: upload_grid over the same and over
+another shape, upload_grid_blocks then upload_grid, construct_map_from_scans into the old allocation
+and past it, update_map_with_scan in place and with a resize, construct_maps_from_scans (two maps in
+one call, both job orders: the consumers alternate), construct_global_map in parts, a likelihood
+field rebuilt from a source that changed, and release_grid followed by an upload under the same id
+(the allocator may hand the same pointers out again) or under the next one (the old id must then be
+refused). The consumers are the seven matchers and cost functions plus peaks, volume covariance,
+motion prior, pose sets and the ray check, each single and batched where both exist.
 
 The block-allocation bitmap follows the reference's GridMap: the cost cells mark every block of
 the map allocated (csm_set_block_allocation) before the change. upload_grid starts the map afresh
 (a block is allocated iff it holds a known cell); construct_map_from_scans and
 update_map_with_scan carry the old bitmap through Resize / Expand, and ResetValues keeps it, so the
 blocks of the old map that overlap the new one stay allocated. Their fresh-id reference holds the
-final cells plus the oracle's tracked bitmap (construct_map / update_map with alloc=)."""
+final cells plus the oracle's tracked bitmap (construct_map / update_map with alloc=). A rebuilt
+likelihood field starts afresh like an upload: its cell runs without a given bitmap.
+
+The second half names coarse levels by hand: score_window and its peaks / moments / prior forms, and
+windows prepared for score_windows_dev, must refuse a level that is behind level 0."""
 import itertools
-import math
 
 import numpy as np
 import pytest
 
-from csm_hip import _lib as L, api, synth
+import peaks_reference as PR
+import ray_check_reference as RC
+import resident_state_cases as RS
+from csm_hip import _lib as L, api
+from resident_state_cases import BNB, CSM, GRID, MID, MUTATIONS, world as _world
 
 pytestmark = pytest.mark.gpu
 
-MID = 5
-CSM = (1.0, 1.0, math.radians(10), 4)
-BNB = (2.5, 2.5, 0.5, 2, 0.3, 0.5)
-GRID = (0.4, 0.4, 0.2, 0.05, 0.05, 0.025)
 _ids = itertools.count(1000)
-_WORLDS = {}
-
-
-# ---------------------------------------------------------------- the map before and after
-
-
-def _room_queries(segs, geom, seed):
-    """Two 1080-beam scans over 1.5 pi (beams share cells: the batch entries take the joint fine
-    level with its bound pass, like the loop detectors' scans)."""
-    rng = np.random.RandomState(seed)
-    qs = []
-    for k in range(2):
-        truth = (0.3 * (rng.rand() - 0.5), 0.3 * (rng.rand() - 0.5), 0.2 * (rng.rand() - 0.5))
-        angles, ranges = synth.cast_scan(segs, truth, 1080, 1.5 * math.pi, 5.7296)
-        init = (truth[0] + 0.17, truth[1] - 0.12, truth[2] + 0.02)
-        qs.append(dict(geom=geom, angles=angles, ranges=ranges, rel_pose=(0.0, 0.0, 0.0), init_pose=init))
-    return qs
-
-
-def _upload(kind):
-    """upload_grid over a map of the same or of another shape; upload_grid_blocks, then upload_grid."""
-    a_shape, b_shape = ((300, 300), (300, 300)) if kind != "upload_other_shape" else ((300, 300), (340, 320))
-    if kind == "blocks_then_dense":
-        a_shape = b_shape = (320, 320)
-    seed = {"upload_same_shape": 900, "upload_other_shape": 910, "blocks_then_dense": 920}[kind]
-    ga, geom_a, _ = synth.make_room(seed, *a_shape, 0.05)
-    gb, geom_b, segs_b = synth.make_room(seed + 1, *b_shape, 0.05)
-
-    def setup(ctx):
-        if kind == "blocks_then_dense":
-            br, bc = ga.shape[0] // 16, ga.shape[1] // 16
-            blocks = [ga[r * 16:(r + 1) * 16, c * 16:(c + 1) * 16] for r in range(br) for c in range(bc)]
-            ctx.upload_grid_blocks(MID, [b if b.any() else None for b in blocks], br, bc, 4)
-        else:
-            ctx.upload_grid(MID, ga)
-
-    def mutate(ctx):
-        ctx.upload_grid(MID, gb)
-
-    queries = _room_queries(segs_b, geom_b, seed)
-    warm = [dict(q, geom=geom_a) for q in queries]
-    return dict(setup=setup, mutate=mutate, grid=gb, queries=queries, warm=warm, cost_alloc=_derived_alloc(gb))
-
-
-def _map_local(map_pose, pose, err):
-    c, s = math.cos(map_pose[2]), math.sin(map_pose[2])
-    dx, dy = pose[0] + err[0] - map_pose[0], pose[1] + err[1] - map_pose[1]
-    return (c * dx + s * dy, -s * dx + c * dy, pose[2] + err[2] - map_pose[2])
-
-
-def _pitch_bytes(shape):
-    return shape["rows"] * ((shape["cols"] + 7) & ~7) * 2
-
-
-def _built(kind, oracle):
-    """construct_map_from_scans into the old allocation and past it; update_map_with_scan in
-    place and with a resize (keep_cells)."""
-    case = synth.map_case(930, n_scans=14, n_beams=1080, max_range=5.0, step=0.3)
-    nodes, shape0 = case["nodes"], case["shape"]
-    map_pose = nodes[0]["pose"]
-    near = dict(nodes[0], ranges=np.minimum(nodes[0]["ranges"], 1.5))       # a small first map
-    first, second = {"construct_reuse": (nodes[0:8], nodes[2:9]), "construct_grow": ([near], nodes[0:14]),
-                     "update_in_place": (nodes[0:10], nodes[5]), "update_grow": (nodes[0:3], nodes[13])}[kind]
-    shape1, grid1, _ = oracle.construct_map(shape0, map_pose, first)
-    # the cost cells mark every block of the first map allocated before the change
-    ones = np.ones((shape1["rows"] >> 4, shape1["cols"] >> 4), np.uint8)
-    if kind.startswith("construct"):
-        shape2, grid2, st2 = oracle.construct_map(shape1, map_pose, second, alloc=ones)
-    else:
-        shape2, grid2, st2 = oracle.update_map(shape1, grid1, map_pose, second, alloc=ones)
-    if kind == "construct_reuse":
-        assert _pitch_bytes(shape2) <= 1.5 * _pitch_bytes(shape1), (shape1, shape2)
-    elif kind == "construct_grow":
-        assert _pitch_bytes(shape2) > 1.5 * _pitch_bytes(shape1), (shape1, shape2)
-    elif kind == "update_in_place":
-        assert shape2 == shape1
-    else:
-        assert (shape2["rows"], shape2["cols"]) != (shape1["rows"], shape1["cols"])
-
-    def setup(ctx):
-        got, _ = ctx.construct_map_from_scans(MID, shape0, map_pose, first)
-        assert got == shape1
-
-    def mutate(ctx):
-        if kind.startswith("construct"):
-            got, _ = ctx.construct_map_from_scans(MID, shape1, map_pose, second)
-        else:
-            got, _ = ctx.update_map_with_scan(MID, shape1, map_pose, second)
-        assert got == shape2
-
-    queries, warm = [], []
-    for k, err in ((6, (0.04, -0.03, 0.01)), (8, (-0.05, 0.02, -0.015))):
-        nd = nodes[k]
-        q = dict(angles=nd["angles"], ranges=nd["ranges"], rel_pose=nd["rel_pose"],
-                 init_pose=_map_local(map_pose, nd["pose"], err))
-        queries.append(dict(q, geom=(shape2["res"], shape2["off_x"], shape2["off_y"])))
-        warm.append(dict(q, geom=(shape1["res"], shape1["off_x"], shape1["off_y"])))
-    return dict(setup=setup, mutate=mutate, grid=grid2, queries=queries, warm=warm, cost_alloc=st2["alloc"])
-
-
-MUTATIONS = ["upload_same_shape", "upload_other_shape", "blocks_then_dense", "construct_reuse",
-             "construct_grow", "update_in_place", "update_grow"]
-
-
-def _world(kind, oracle):
-    if kind not in _WORLDS:
-        _WORLDS[kind] = _upload(kind) if kind.startswith(("upload", "blocks")) else _built(kind, oracle)
-    return _WORLDS[kind]
 
 
 # ---------------------------------------------------------------- consumers
@@ -214,13 +119,6 @@ def _cost(ctx, qs):
             [_plain(o) for o in ctx.linear_solver_batch(qs, 10, 1e-4, 1e-4, 1e4)])
 
 
-def _derived_alloc(grid):
-    rows, cols = -(-grid.shape[0] // 16) * 16, -(-grid.shape[1] // 16) * 16
-    g = np.zeros((rows, cols), grid.dtype)
-    g[:grid.shape[0], :grid.shape[1]] = grid
-    return (g.reshape(rows // 16, 16, cols // 16, 16).max(axis=(1, 3)) > 0).astype(np.uint8)
-
-
 def _cost_oracle(oracle, grid, qs, got, alloc):
     for q, p, o in zip(qs, _poses(qs), got[:len(qs)]):
         want = oracle.cost(grid, q["geom"], q["angles"], q["ranges"], p, alloc=alloc)
@@ -248,6 +146,112 @@ def _greedy_oracle(oracle, grid, qs, got):
             assert o[key] == want[key], (key, o[key], want[key])
 
 
+# ---- the consumers that came after the first matrix: each checked against its numpy reference
+# (RS.reference: computed once per world and consumer, shared, never changed)
+
+
+def _strip(o):
+    """A record without its timings (the *_us fields), all the way down; arrays as lists."""
+    if isinstance(o, dict):
+        return {k: _strip(v) for k, v in o.items() if not k.endswith("_us")}
+    if isinstance(o, (list, tuple)):
+        return [_strip(v) for v in o]
+    return o.tolist() if isinstance(o, np.ndarray) else o
+
+
+def _scan(q):
+    return (q["map_id"], q["geom"], q["angles"], q["ranges"], q["rel_pose"], q["init_pose"])
+
+
+def _peaks(ctx, qs):
+    single = [ctx.correlative_peaks(*_scan(q), *RS.RANGE, RS.LOW, RS.K_MAX, RS.EXCL) for q in qs]
+    return _strip(single), _strip(ctx.correlative_peaks_batch(qs, *RS.RANGE, RS.LOW, RS.K_MAX, RS.EXCL))
+
+
+def _check_poses(summary, record, win, q):
+    best, est = PR.poses_of(record, win, q["rel_pose"])
+    assert summary["pose_found"] == 1 and summary["raw"] == record
+    assert summary["best_sensor_pose"] == best and summary["estimated_pose"] == est       # bit-exact doubles
+    assert (summary["win_x"], summary["win_y"], summary["win_theta"]) == win["win"]
+    assert summary["candidates"] == int(np.prod(win["shape"]))
+
+
+def _peaks_check(ref, qs, got):
+    single, batch = got
+    assert single == batch
+    for q, r, out in zip(qs, ref, single):
+        assert r["band"] == 0 and len(r["records"]) == RS.K_MAX
+        assert [o["raw"] for o in out] == r["records"]              # field by field, score bits included
+        for o, rec in zip(out, r["records"]):
+            _check_poses(o, rec, r["win"], q)
+
+
+def _volume_cov(ctx, qs):
+    single = [ctx.correlative_covariance(*_scan(q), *RS.RANGE, RS.LOW, RS.TAU) for q in qs]
+    return _strip(single), _strip(ctx.correlative_covariance_batch(qs, *RS.RANGE, RS.LOW, RS.TAU))
+
+
+def _volume_cov_check(ref, qs, got):
+    single, batch = got
+    assert single == batch
+    for q, r, out in zip(qs, ref, single):
+        want, win = r["summary"], r["win"]
+        assert want["moments"]["best"]["found"] == 1 and want["moments"]["support"] > 1
+        assert out["moments"] == want["moments"]
+        assert out["mean_offset"] == want["mean_offset"]                   # bit-exact doubles
+        assert out["sensor_covariance"] == want["sensor_covariance"]
+        assert out["covariance"] == want["covariance"]
+        _check_poses(out["summary"], want["moments"]["best"], win, q)
+        assert out["summary"]["estimated_pose"] == want["estimated_pose"]
+
+
+def _prior(ctx, qs):
+    single = [ctx.correlative_match_prior(*_scan(q), *RS.RANGE, RS.LOW, RS.LAMBDA) for q in qs]
+    return _strip(single), _strip(ctx.correlative_match_prior_batch(qs, *RS.RANGE, RS.LOW, [RS.LAMBDA] * len(qs)))
+
+
+def _prior_check(ref, qs, got):
+    single, batch = got
+    assert single == batch
+    for q, r, out in zip(qs, ref, single):
+        want, win = r["prior"], r["win"]
+        assert r["band"] == 0 and want["best"]["found"] == 1 and want["best"] != want["unweighted"]
+        assert out["prior"] == want
+        _check_poses(out["summary"], want["best"], win, q)
+        assert (out["summary"]["step_x"], out["summary"]["step_y"], out["summary"]["step_theta"]) == tuple(win["steps"])
+
+
+def _pose_sets(ctx, qs):
+    sets = [dict(map_id=q["map_id"], geom=q["geom"], angles=q["angles"], ranges=q["ranges"], poses=RS.pose_set(q, k))
+            for k, q in enumerate(qs)]
+    recs, info = ctx.score_pose_sets(sets)
+    assert info["poses"] == RS.N_POSES * len(qs)
+    return [dict(S=r["sum_values"].astype(np.int64).tolist(), K=r["known"].astype(np.int64).tolist()) for r in recs]
+
+
+def _pose_sets_check(ref, qs, got):
+    assert got == ref
+    assert all(max(r["K"]) > 0 for r in ref)
+
+
+def _ray_check(ctx, qs):
+    records, words = ctx.ray_check_batch(qs, per_beam=True, **RS.RAY)
+    return [dict(record=RC.strip(r), words=w.tolist()) for r, w in zip(records, words)]
+
+
+def _ray_check_check(ref, qs, got):
+    assert got == ref
+    assert all(r["record"]["walked"] > 0 for r in ref)
+
+
+NEW_CONSUMERS = {
+    "peaks": (0, _peaks, _peaks_check),
+    "volume_cov": (0, _volume_cov, _volume_cov_check),
+    "prior": (0, _prior, _prior_check),
+    "pose_sets": (0, _pose_sets, _pose_sets_check),
+    "ray_check": (0, _ray_check, _ray_check_check),
+}
+
 CONSUMERS = {
     "csm_graphs": (0, _csm_single, _csm_oracle),
     "csm_two_phase": (L.TUNE_FORCE_TWO_PHASE, _csm_single, _csm_oracle),
@@ -256,6 +260,7 @@ CONSUMERS = {
     "grid_search": (0, _grid_search, _grid_search_oracle),
     "cost_linear": (0, _cost, _cost_oracle),
     "greedy_hill_climbing": (0, _greedy, _greedy_oracle),
+    **NEW_CONSUMERS,
 }
 
 
@@ -269,29 +274,45 @@ def refs():
         c.close()
 
 
+def _refused(call):
+    with pytest.raises(api.CsmError) as err:
+        call()
+    assert err.value.code == L.CSM_ENOENT, err.value
+
+
 @pytest.mark.parametrize("consumer", list(CONSUMERS))
 @pytest.mark.parametrize("mutation", MUTATIONS)
 def test_derived_state_follows_the_map(oracle, refs, mutation, consumer):
     tuning, run, check = CONSUMERS[consumer]
     world = _world(mutation, oracle)
+    new = consumer in NEW_CONSUMERS
+    queries, warm_queries = (world["queries_new"], world["warm_new"]) if new else (world["queries"], world["warm"])
+    qid = world["qid"]
+    given_bitmap = consumer == "cost_linear" and not world.get("derived_alloc_only")
     ctx = api.Context(0, tuning_off=tuning)
     try:
         world["setup"](ctx)
-        if consumer == "cost_linear":
+        if given_bitmap:
             rows, cols = ctx.shapes[MID]
             ctx.set_block_allocation(MID, 4, np.ones((-(-rows // 16), -(-cols // 16)), np.uint8))
-        warm = _with_id(world["warm"], MID)
+        warm = _with_id(warm_queries, MID)
         for _ in range(3):
             run(ctx, warm)
-        world["mutate"](ctx)
-        assert np.array_equal(ctx.download_level(MID, 0), world["grid"])
-        qs = _with_id(world["queries"], MID)
+        if mutation == "batch_build":       # both job orders, spread over the consumers
+            world["mutate"](ctx, reverse=list(CONSUMERS).index(consumer) % 2 == 1)
+        else:
+            world["mutate"](ctx)
+        assert np.array_equal(ctx.download_level(qid, 0), world["grid"])
+        qs = _with_id(queries, qid)
         ctx.bound_pass_stats()
         got = [run(ctx, qs) for _ in range(2)]
         if consumer == "csm_two_phase":
             assert ctx.last_search_info()["two_phase"] == 1
         if consumer in ("csm_batch", "bnb_batch"):
             assert sum(ctx.bound_pass_stats()) > 0
+        if world["gone"] is not None:
+            assert not ctx.has_grid(world["gone"])
+            _refused(lambda: run(ctx, _with_id(queries, world["gone"])))
     finally:
         ctx.close()
     ref = refs[tuning]
@@ -300,12 +321,116 @@ def test_derived_state_follows_the_map(oracle, refs, mutation, consumer):
     try:
         if consumer == "cost_linear":
             ref.set_block_allocation(rid, 4, world["cost_alloc"])
-        want = run(ref, _with_id(world["queries"], rid))
+        want = run(ref, _with_id(queries, rid))
     finally:
         ref.release_grid(rid)
     assert got[0] == want
     assert got[1] == want
     if consumer == "cost_linear":
         check(oracle, world["grid"], qs, want, world["cost_alloc"])
+    elif new:
+        check(RS.reference(mutation, consumer), qs, want)
     else:
         check(oracle, world["grid"], qs, want)
+
+
+# ---------------------------------------------------------------- coarse levels named by the caller
+
+
+def _window(ctx, win, n_points):
+    wx, wy, wt = win["win"]
+    return ctx.make_window(2 * wt + 1, n_points, wx, wy, RS.LOW, 1, api.host_min_known(n_points, 0.0), 0.0)
+
+
+# entry -> (the call on a window, its reference out of RS.reference(kind, ..., when)[query])
+ENTRIES = {
+    "score_window": (lambda ctx, w, win: ctx.score_window(MID, w, win["col"], win["row"]),
+                     lambda kind, when, k: RS.reference(kind, "peaks", when)[k]["records"][0]),
+    "score_window_peaks": (lambda ctx, w, win: ctx.score_window_peaks(MID, w, win["col"], win["row"], RS.K_MAX,
+                                                                      RS.EXCL),
+                           lambda kind, when, k: RS.reference(kind, "peaks", when)[k]["records"]),
+    "score_window_moments": (lambda ctx, w, win: ctx.score_window_moments(MID, w, win["col"], win["row"], RS.TAU),
+                             lambda kind, when, k: RS.reference(kind, "volume_cov", when)[k]["summary"]["moments"]),
+    "score_window_prior": (lambda ctx, w, win: ctx.score_window_prior(MID, w, win["col"], win["row"], RS.LAMBDA,
+                                                                      win["steps"]),
+                           lambda kind, when, k: RS.reference(kind, "prior", when)[k]["prior"]),
+}
+
+
+@pytest.mark.parametrize("entry", list(ENTRIES))
+@pytest.mark.parametrize("mutation", RS.LEVEL_MUTATIONS)
+def test_named_coarse_level_goes_stale(oracle, mutation, entry):
+    """Pyramid [1, L], one call, the map changes, the same window with coarse_level = 1 is refused and level 0
+    is what the change left; after build_pyramid the call equals the reference on the final map."""
+    call, want_of = ENTRIES[entry]
+    world = _world(mutation, oracle)
+    n = len(world["queries_new"][0]["angles"])
+    old, fresh = want_of(mutation, "before", 0), want_of(mutation, "after", 0)
+    old_win, fresh_win = (RS.reference(mutation, "peaks", when)[0]["win"] for when in ("before", "after"))
+    assert old != fresh and RS.reference(mutation, "peaks", "before")[0]["band"] == 0
+    ctx = api.Context(0)
+    try:
+        world["setup"](ctx)
+        ctx.build_pyramid(MID, [1, RS.LOW])
+        w = _window(ctx, old_win, n)
+        assert call(ctx, w, old_win) == old
+        world["mutate"](ctx)
+        _refused(lambda: call(ctx, w, old_win))
+        _refused(lambda: ctx.download_level(MID, 1))
+        assert np.array_equal(ctx.download_level(MID, 0), world["grid"])
+        ctx.build_pyramid(MID, [1, RS.LOW])
+        assert np.array_equal(ctx.download_level(MID, 1), oracle.boxmax(world["grid"], RS.LOW))
+        assert call(ctx, _window(ctx, fresh_win, n), fresh_win) == fresh
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("mutation", RS.LEVEL_MUTATIONS)
+def test_prepared_windows_never_score_the_old_map(oracle, mutation):
+    """Windows prepared for score_windows_dev before the change and scored after it: the refusal, or the
+    records of the same hit indices on the final cells; never the records of the old map."""
+    import torch
+    dev = torch.device("cuda", 0)
+    world = _world(mutation, oracle)
+    before = RS.reference(mutation, "peaks", "before")
+    old = [r["records"][0] for r in before]
+    # the same hit indices (the geometry of before the change) on the final cells
+    same_hits = RS.reference_of("peaks", world["grid"], world["warm_new"])
+    fresh = [r["records"][0] for r in same_hits]
+    assert all(a != b for a, b in zip(old, fresh))
+    ctx = api.Context(0)
+    try:
+        world["setup"](ctx)
+        ctx.build_pyramid(MID, [1, RS.LOW])
+        keep, cols, rows, windows = [], [], [], []
+        for r, q in zip(before, world["warm_new"]):
+            assert r["band"] == 0
+            windows.append(_window(ctx, r["win"], len(q["angles"])))
+            keep += [torch.from_numpy(np.ascontiguousarray(r["win"][key], np.int32)).to(dev) for key in ("col", "row")]
+            cols.append(keep[-2].data_ptr())
+            rows.append(keep[-1].data_ptr())
+        out = torch.zeros(len(windows) * 48, dtype=torch.uint8, device=dev)
+        prepared = ctx.prepare_windows([MID] * len(windows), windows, cols, rows)
+
+        def records():
+            ctx.score_windows_dev(prepared, out.data_ptr())
+            ctx.synchronize()
+            torch.cuda.synchronize(dev)
+            raw = out.cpu().numpy().tobytes()
+            recs = [api.result_to_dict(L.Result.from_buffer_copy(raw[48 * k:48 * (k + 1)]))
+                    for k in range(len(windows))]
+            return [dict(r, flags=r["flags"] & ~L.FLAG_PROJ_DELTA) for r in recs]
+
+        assert records() == old
+        world["mutate"](ctx)
+        try:
+            got = records()
+        except api.CsmError as err:
+            assert err.code == L.CSM_ENOENT, err
+        else:
+            assert got != old
+            assert [g for g, r in zip(got, same_hits) if r["band"] == 0] == \
+                [f for f, r in zip(fresh, same_hits) if r["band"] == 0]
+        assert np.array_equal(ctx.download_level(MID, 0), world["grid"])
+    finally:
+        ctx.close()
