@@ -242,6 +242,19 @@ def _scan_struct(angles, ranges, rel_pose):
     return sc, (a, r)
 
 
+def _correlative_params(range_x, range_y, range_theta, low_resolution, score_threshold, known_rate_threshold):
+    p = L.CorrelativeParams()
+    p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
+    p.low_resolution = low_resolution
+    p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+    return p
+
+
+def _hits(hit_col, hit_row):
+    """The hit indices of a pre-projected window as the C ABI takes them."""
+    return np.ascontiguousarray(hit_col, dtype=np.int32), np.ascontiguousarray(hit_row, dtype=np.int32)
+
+
 def host_greedy_cost(grid, geom, angles, ranges, sensor_pose, greedy=None, covariance=False):
     """csm_host_greedy_cost: Cost() (ScalingFactor applied, not normalized), and
     ComputeCovariance() if asked."""
@@ -802,8 +815,7 @@ class Context:
         return w
 
     def score_window(self, map_id, window, hit_col, hit_row, dump=False):
-        col = np.ascontiguousarray(hit_col, dtype=np.int32)
-        row = np.ascontiguousarray(hit_row, dtype=np.int32)
+        col, row = _hits(hit_col, hit_row)
         res = L.Result()
         if not dump:
             self._check(self.lib.csm_score_window(self._ctx, map_id, C.byref(window),
@@ -870,17 +882,9 @@ class Context:
     def correlative_match(self, map_id, geom, angles, ranges, rel_pose, init_pose,
                           range_x, range_y, range_theta, low_resolution,
                           score_threshold=0.0, known_rate_threshold=0.0):
-        a, r = _f64(angles), _f64(ranges)
-        scan = L.Scan()
-        scan.angles = a.ctypes.data_as(C.POINTER(C.c_double))
-        scan.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
-        scan.n_points = a.size
-        scan.relative_sensor_pose[:] = list(rel_pose)
+        scan, keep = _scan_struct(angles, ranges, rel_pose)
         g = L.Geometry(*geom)
-        p = L.CorrelativeParams()
-        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
-        p.low_resolution = low_resolution
-        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        p = _correlative_params(range_x, range_y, range_theta, low_resolution, score_threshold, known_rate_threshold)
         init = _f64(init_pose)
         out = L.Summary()
         self._check(self.lib.csm_correlative_match(self._ctx, map_id, C.byref(g), C.byref(scan),
@@ -895,8 +899,7 @@ class Context:
     def score_window_peaks(self, map_id, window, hit_col, hit_row, k_max, excl=(0, 0, 0), scratch_limit_bytes=0):
         """The K best distinct poses of one pre-projected window (csm_score_window_peaks): the list of
         the peaks' records, best first."""
-        col = np.ascontiguousarray(hit_col, dtype=np.int32)
-        row = np.ascontiguousarray(hit_row, dtype=np.int32)
+        col, row = _hits(hit_col, hit_row)
         pk = self.peaks_params(k_max, excl, scratch_limit_bytes)
         out = (L.Result * max(1, min(k_max, L.PEAKS_MAX)))()
         n = C.c_int32(0)
@@ -909,17 +912,9 @@ class Context:
                           scratch_limit_bytes=0):
         """correlative_match() returning the K best distinct poses (csm_correlative_peaks): a list of
         summaries, best first."""
-        a, r = _f64(angles), _f64(ranges)
-        scan = L.Scan()
-        scan.angles = a.ctypes.data_as(C.POINTER(C.c_double))
-        scan.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
-        scan.n_points = a.size
-        scan.relative_sensor_pose[:] = list(rel_pose)
+        scan, keep = _scan_struct(angles, ranges, rel_pose)
         g = L.Geometry(*geom)
-        p = L.CorrelativeParams()
-        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
-        p.low_resolution = low_resolution
-        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        p = _correlative_params(range_x, range_y, range_theta, low_resolution, score_threshold, known_rate_threshold)
         init = _f64(init_pose)
         pk = self.peaks_params(k_max, excl, scratch_limit_bytes)
         out = (L.Summary * max(1, min(k_max, L.PEAKS_MAX)))()
@@ -935,10 +930,7 @@ class Context:
         (csm_correlative_peaks_batch): one list of summaries per query, best first. as_records: the C
         arrays (summaries [n * k_max], peak counts [n]) instead."""
         prep = self.prepare_queries(queries)
-        p = L.CorrelativeParams()
-        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
-        p.low_resolution = low_resolution
-        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        p = _correlative_params(range_x, range_y, range_theta, low_resolution, score_threshold, known_rate_threshold)
         pk = self.peaks_params(k_max, excl, scratch_limit_bytes)
         kk = max(1, min(k_max, L.PEAKS_MAX))
         out = (L.Summary * (prep.n * kk))()
@@ -951,8 +943,7 @@ class Context:
     def score_window_moments(self, map_id, window, hit_col, hit_row, temperature, scratch_limit_bytes=0):
         """The winner and the integer moments of one pre-projected window's score volume
         (csm_score_window_moments), as a dict."""
-        col = np.ascontiguousarray(hit_col, dtype=np.int32)
-        row = np.ascontiguousarray(hit_row, dtype=np.int32)
+        col, row = _hits(hit_col, hit_row)
         vp = L.VolumeParams(temperature, scratch_limit_bytes)
         out = L.VolumeMoments()
         self._check(self.lib.csm_score_window_moments(self._ctx, map_id, C.byref(window), _ptr(col), _ptr(row),
@@ -965,17 +956,9 @@ class Context:
         """correlative_match() with the pose covariance read off the score volume
         (csm_correlative_covariance): a dict of summary, moments, mean_offset, sensor_covariance,
         covariance."""
-        a, r = _f64(angles), _f64(ranges)
-        scan = L.Scan()
-        scan.angles = a.ctypes.data_as(C.POINTER(C.c_double))
-        scan.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
-        scan.n_points = a.size
-        scan.relative_sensor_pose[:] = list(rel_pose)
+        scan, keep = _scan_struct(angles, ranges, rel_pose)
         g = L.Geometry(*geom)
-        p = L.CorrelativeParams()
-        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
-        p.low_resolution = low_resolution
-        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        p = _correlative_params(range_x, range_y, range_theta, low_resolution, score_threshold, known_rate_threshold)
         init = _f64(init_pose)
         vp = L.VolumeParams(temperature, scratch_limit_bytes)
         out = L.VolumeSummary()
@@ -989,10 +972,7 @@ class Context:
         """correlative_match_batch() with the volume covariance of every query
         (csm_correlative_covariance_batch): one dict per query. as_records: the C array instead."""
         prep = self.prepare_queries(queries)
-        p = L.CorrelativeParams()
-        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
-        p.low_resolution = low_resolution
-        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        p = _correlative_params(range_x, range_y, range_theta, low_resolution, score_threshold, known_rate_threshold)
         vp = L.VolumeParams(temperature, scratch_limit_bytes)
         out = (L.VolumeSummary * prep.n)()
         self._check(self.lib.csm_correlative_covariance_batch(self._ctx, prep.arr, prep.n, C.byref(p), C.byref(vp),
@@ -1004,8 +984,7 @@ class Context:
     def score_window_prior(self, map_id, window, hit_col, hit_row, information, steps, scratch_limit_bytes=0):
         """The winner of one pre-projected window under a motion prior, next to the unweighted one
         (csm_score_window_prior), as a dict."""
-        col = np.ascontiguousarray(hit_col, dtype=np.int32)
-        row = np.ascontiguousarray(hit_row, dtype=np.int32)
+        col, row = _hits(hit_col, hit_row)
         pr = motion_prior(information, steps, scratch_limit_bytes)
         out = L.PriorResult()
         self._check(self.lib.csm_score_window_prior(self._ctx, map_id, C.byref(window), _ptr(col), _ptr(row),
@@ -1017,17 +996,9 @@ class Context:
                                 known_rate_threshold=0.0, scratch_limit_bytes=0):
         """correlative_match() under a motion prior on the offset from the initial pose
         (csm_correlative_match_prior): a dict of summary (from the winner under the prior) and prior."""
-        a, r = _f64(angles), _f64(ranges)
-        scan = L.Scan()
-        scan.angles = a.ctypes.data_as(C.POINTER(C.c_double))
-        scan.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
-        scan.n_points = a.size
-        scan.relative_sensor_pose[:] = list(rel_pose)
+        scan, keep = _scan_struct(angles, ranges, rel_pose)
         g = L.Geometry(*geom)
-        p = L.CorrelativeParams()
-        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
-        p.low_resolution = low_resolution
-        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        p = _correlative_params(range_x, range_y, range_theta, low_resolution, score_threshold, known_rate_threshold)
         init = _f64(init_pose)
         pr = motion_prior(information, scratch_limit_bytes=scratch_limit_bytes)
         out = L.PriorSummary()
@@ -1043,10 +1014,7 @@ class Context:
         prep = self.prepare_queries(queries)
         if len(informations) != prep.n:
             raise CsmError(L.CSM_EINVAL, "correlative_match_prior_batch: one information matrix per query")
-        p = L.CorrelativeParams()
-        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
-        p.low_resolution = low_resolution
-        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        p = _correlative_params(range_x, range_y, range_theta, low_resolution, score_threshold, known_rate_threshold)
         priors = (L.MotionPrior * prep.n)(*[motion_prior(lam, scratch_limit_bytes=scratch_limit_bytes)
                                             for lam in informations])
         out = (L.PriorSummary * prep.n)()
@@ -1173,12 +1141,7 @@ class Context:
                           score_threshold=0.0, known_rate_threshold=0.0):
         """ScanMatcherGridSearch::OptimizePose
         (src/my_lidar_graph_slam/mapping/scan_matcher_grid_search.cpp:69-190)."""
-        a, r = _f64(angles), _f64(ranges)
-        scan = L.Scan()
-        scan.angles = a.ctypes.data_as(C.POINTER(C.c_double))
-        scan.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
-        scan.n_points = a.size
-        scan.relative_sensor_pose[:] = list(rel_pose)
+        scan, keep = _scan_struct(angles, ranges, rel_pose)
         g = L.Geometry(*geom)
         p = L.GridSearchParams(range_x, range_y, range_theta, step_x, step_y, step_theta,
                                score_threshold, known_rate_threshold)
@@ -1216,10 +1179,7 @@ class Context:
         or prepare_queries()'s result. as_records: return the C summaries
         (SummaryArray) instead of dicts."""
         prep = self.prepare_queries(queries)
-        p = L.CorrelativeParams()
-        p.range_x, p.range_y, p.range_theta = range_x, range_y, range_theta
-        p.low_resolution = low_resolution
-        p.score_threshold, p.known_rate_threshold = score_threshold, known_rate_threshold
+        p = _correlative_params(range_x, range_y, range_theta, low_resolution, score_threshold, known_rate_threshold)
         out = (L.Summary * prep.n)()
         self._check(self.lib.csm_correlative_match_batch(self._ctx, prep.arr, prep.n, C.byref(p), out))
         return SummaryArray(out) if as_records else [summary_to_dict(o) for o in out]

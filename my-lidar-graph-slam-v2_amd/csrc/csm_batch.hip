@@ -946,8 +946,7 @@ int csm_score_windows_dump_dev(csm_ctx* ctx, int32_t n, const uint64_t* map_ids,
                         (unsigned long long)map_ids[i]);
         const int L = w.low_resolution;
         if (L > 1) {
-            if (w.coarse_level < 0 || w.coarse_level >= (int)g->levels.size() ||
-                g->levels[w.coarse_level].stale || g->levels[w.coarse_level].win != L)
+            if (!level_holds(*g, w.coarse_level, L))
                 return fail(ctx, CSM_ENOENT, "window %d: level %d does not hold box-max(%d)", i,
                             w.coarse_level, L);
             levels[i][1] = w.coarse_level;

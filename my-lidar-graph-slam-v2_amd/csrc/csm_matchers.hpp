@@ -15,6 +15,9 @@ namespace csm_host {
 
 const int kCoarseSlices = 8;
 
+/* score = key * kKeyToScore / n_points */
+constexpr double kKeyToScore = 0.998 / (65534.0 * 499.0);
+
 /* Launch geometry of one scoring pass (one level of one window shape). */
 struct PassPlan {
     int nx = 0, ny = 0, stride = 1, log2s = 0;
@@ -147,6 +150,11 @@ int launch_box_jobs(csm_ctx* ctx, PendingBoxes& pending);
 int build_level(csm_ctx* ctx, DeviceGrid& g, int win, Level* out);
 int level_for_window(csm_ctx* ctx, DeviceGrid& g, int win, int* index,
                      PendingBoxes* pending = nullptr);
+/* What a caller that names its coarse level must name: a level that is built, not stale and box-max(L). */
+inline bool level_holds(const DeviceGrid& g, int level, int L)
+{
+    return level >= 0 && level < (int)g.levels.size() && !g.levels[level].stale && g.levels[level].win == L;
+}
 int ensure_xgrid(csm_ctx* ctx, DeviceGrid& g, int need_pad);
 int ensure_xgrid_f(csm_ctx* ctx, DeviceGrid& g);
 

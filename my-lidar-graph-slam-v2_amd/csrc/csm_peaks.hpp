@@ -1,11 +1,16 @@
 /* csm_peaks.hpp -- what the units that read a window's whole score volume share: the peaks entries
  * (csm_peaks_api.hip, which defines everything declared here), the volume covariance
- * (csm_volume_api.hip) and the motion prior (csm_prior_api.hip). The device-side job record of one window, and the host stages of a chunk:
- * sizing, projection on the device, exact scores + coarse known counts + selection rounds. */
+ * (csm_volume_api.hip) and the motion prior (csm_prior_api.hip). The device-side job record of one window,
+ * the host stages of a chunk (sizing, projection on the device, exact scores + coarse known counts +
+ * selection rounds), and the one host driver of the three entry shapes (volume_window, volume_batch,
+ * single_query): a unit hands it a VolumeUnit -- its selection rounds, its check of a sized window, its
+ * chunk body. */
 #ifndef CSM_PEAKS_HPP
 #define CSM_PEAKS_HPP
 
 #include "csm_matchers.hpp"
+
+#include <functional>
 
 namespace csm {
 
@@ -116,17 +121,62 @@ int peaks_next_chunk(const std::vector<PeakWindow>& wins, int lo, int64_t scratc
  * cannot certify: on the host); sets hit_off. Waits for the stream. */
 int peaks_project_chunk(csm_ctx* ctx, const csm_loop_query* queries, std::vector<PeakWindow>& wins,
                         const std::vector<csm_summary>& head, int lo, int hi);
-/* Windows [lo, hi) with their hit indices in pk_hits: the job table (room for pk->k_max records per
- * window, zeroed), exact scores of every candidate, coarse known counts. Everything is queued on the
- * stream. */
-int peaks_score_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
-                      PeakChunk* out);
-/* peaks_score_chunk, then pk->k_max selection rounds. Everything is queued on the stream; nothing is copied back and the
- * host does not wait for the selection. */
-int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
+/* The selection of a unit: `rounds` rounds of the peaks' two launches (0: none) with these exclusion radii. */
+struct PeakRounds {
+    int rounds = 0, excl_x = 0, excl_y = 0, excl_theta = 0;
+};
+/* Windows [lo, hi) with their hit indices in pk_hits: the job table (room for max(1, sel.rounds) records
+ * per window, zeroed), exact scores of every candidate, coarse known counts (peaks_score_chunk), then
+ * sel.rounds selection rounds. Everything is queued on the stream; nothing is copied back and the host does
+ * not wait for the selection. */
+int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const PeakRounds& sel,
                        PeakChunk* out);
-/* The poses of a record: best_sensor_pose and estimated_pose of `o` from o.raw. */
-void peaks_fill_poses(csm_summary& o, const double relative_sensor_pose[3]);
+
+/* ---- the host driver of the units on the volume ---- */
+
+/* The six entries of a symmetric 3 x 3 matrix, (kA[k], kB[k]): xx xy xt yy yt tt */
+constexpr int kA[6] = { 0, 0, 0, 1, 1, 2 }, kB[6] = { 0, 1, 2, 1, 2, 2 };
+
+/* J: MoveBackward(sensor pose, rel_pose) by the sensor pose, at a pose of heading `theta` */
+inline void move_backward_jacobian(double theta, const double rel_pose[3], double J[3][3])
+{
+    const double sn = std::sin(theta), cs = std::cos(theta);
+    const double v[3][3] = { { 1.0, 0.0, sn * rel_pose[0] + cs * rel_pose[1] },
+                             { 0.0, 1.0, -cs * rel_pose[0] + sn * rel_pose[1] },
+                             { 0.0, 0.0, 1.0 } };
+    std::memcpy(J, v, sizeof(v));
+}
+
+/* What differs between the units. The driver sizes a window, then runs `check` (if any) on it: the unit's
+ * own refusals that need the window's frame and candidate count. Per chunk it runs the stages with `sel`,
+ * then `body`: the unit's own launches on the stream, and its results of windows [lo, hi) copied back into
+ * the unit's own storage (which waits for the stream). Both are built once per call, not per chunk. */
+struct VolumeUnit {
+    PeakRounds sel;
+    int64_t scratch_limit = 0;
+    std::function<int(const PeakWindow& pw, int index)> check;
+    std::function<int(std::vector<PeakWindow>& wins, int lo, int hi, const PeakChunk& ch)> body;
+};
+
+/* Microseconds on the clock of the timing fields. */
+double clock_us();
+/* One window with the caller's hit indices and a coarse level the caller names: size, check, level, device,
+ * hits into pk_hits, stages, body. A failure past the upload waits for the stream, so that no copy from the
+ * caller's arrays stays pending. */
+int volume_window(csm_ctx* ctx, const VolumeUnit& u, uint64_t map_id, const csm_window* w, const int32_t* hit_col,
+                  const int32_t* hit_row);
+/* A batch of queries: set-up (peaks_prepare_queries), check per window, then chunk by chunk projection,
+ * stages, body. head[i]: the set-up's part of query i's summary. The per-query shares of the time from
+ * `t0_us` (the unit's clock_us() on entry) to the first chunk and of the chunks. */
+int volume_batch(csm_ctx* ctx, const VolumeUnit& u, const csm_loop_query* queries, int n,
+                 const csm_correlative_params* prm, double t0_us, std::vector<csm_summary>& head, double* setup_us,
+                 double* opt_us);
+/* The summary of a query: the set-up's part and the timing shares; with `found`, the record and its poses. */
+void fill_summary(csm_summary& o, const csm_summary& head, const csm_result& raw, bool found,
+                  const double rel_pose[3], double setup_us, double opt_us);
+/* The one query of a single-query entry. */
+csm_loop_query single_query(uint64_t map_id, const csm_geometry* geom, const csm_scan* scan,
+                            const double initial_pose[3]);
 
 } /* namespace csm_host */
 #endif

@@ -8,7 +8,14 @@
  * (csm_score_windows_dump_dev), the coarse nodes' known counts are counted, and k_max selection rounds
  * of two launches each pick the peaks of all the chunk's windows, with no host wait between the rounds.
  * The records and the peak counts come back in one copy. The host waits for the projection's flags and
- * for that copy (and wherever the scoring chain itself waits). The scratch lives in the context's owners (pk_vol, pk_hits, pk_tab, pk_pin). */
+ * for that copy (and wherever the scoring chain itself waits). The scratch lives in the context's owners
+ * (pk_vol, pk_hits, pk_tab, pk_pin).
+ *
+ * The three entry shapes -- a named window with the caller's hit indices, a batch of queries, one query --
+ * are the host driver's (volume_window, volume_batch, single_query; declared in csm_peaks.hpp, defined
+ * here), which the covariance and the prior use too. To the driver the peaks are a unit like those two:
+ * k_max selection rounds, no check of a sized window, and a chunk body that launches nothing and copies
+ * the records back (peaks_unit). */
 #include "csm_peaks.hpp"
 
 #include "csm_peaks_kernels.hip"
@@ -51,10 +58,11 @@ int peaks_size_window(csm_ctx* ctx, PeakWindow& pw, int64_t scratch_limit, int i
     return CSM_OK;
 }
 
-int peaks_score_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
-                      PeakChunk* out)
+/* The stages up to the selection: job table, exact scores, coarse known counts. */
+static int peaks_score_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const PeakRounds& sel,
+                             PeakChunk* out)
 {
-    const int m = hi - lo, k_max = pk->k_max;
+    const int m = hi - lo, k_max = std::max(1, sel.rounds);
     int rc;
     size_t vol_total = 0;
     for (int i = lo; i < hi; ++i)
@@ -131,9 +139,9 @@ int peaks_score_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int h
         J.blocks = (int)std::min<int64_t>(kPeakBlocksMax, std::max<int64_t>(1, (pw.total + 8191) / 8192));
         J.chunk = (int)((pw.total + J.blocks - 1) / J.blocks);
         J.k_max = k_max;
-        J.excl_x = pk->excl_x;
-        J.excl_y = pk->excl_y;
-        J.excl_theta = pk->excl_theta;
+        J.excl_x = sel.excl_x;
+        J.excl_y = sel.excl_y;
+        J.excl_theta = sel.excl_theta;
         J.score_thr = pw.w.score_threshold;
         n_points_max = std::max(n_points_max, pw.w.n_points);
     }
@@ -161,20 +169,20 @@ int peaks_score_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int h
     return CSM_OK;
 }
 
-int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
+int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const PeakRounds& sel,
                        PeakChunk* out)
 {
-    const int m = hi - lo, k_max = pk->k_max;
+    const int m = hi - lo;
     int rc;
-    if ((rc = peaks_score_chunk(ctx, wins, lo, hi, pk, out))) return rc;
+    if ((rc = peaks_score_chunk(ctx, wins, lo, hi, sel, out))) return rc;
     const PeakJob* const jobs_dev = out->jobs_dev;
     const int n_points_max = out->n_points_max;
     int blocks_max = 1;
     for (int k = 0; k < m; ++k)
         blocks_max = std::max(blocks_max, out->jobs_pin[k].blocks);
-    {
+    if (sel.rounds > 0) {
         ScopedTimer tm(ctx, "peaks_select");
-        for (int round = 0; round < k_max; ++round) {
+        for (int round = 0; round < sel.rounds; ++round) {
             if ((rc = launched_ok(ctx, csm_launch::launch(k_peaks_argmax, dim3(blocks_max, m), dim3(kPeakBlock), ctx->stream,
                                                           jobs_dev, round), "peak arg-max")))
                 return rc;
@@ -191,14 +199,10 @@ int peaks_select_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int 
 
 namespace {
 
-/* peaks_select_chunk, then rec[(i - lo) * k_max + j] and n_peaks[i - lo] receive the result. */
-int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_peaks_params* pk,
-              csm_result* rec, int32_t* n_peaks)
+/* The peaks' chunk body: nothing to launch. rec[k * k_max + j] and n_peaks[k] of the chunk's window k receive
+ * the result. */
+int copy_back(csm_ctx* ctx, const PeakChunk& ch, int m, int k_max, csm_result* rec, int32_t* n_peaks)
 {
-    const int m = hi - lo, k_max = pk->k_max;
-    PeakChunk ch;
-    if (int rc = peaks_select_chunk(ctx, wins, lo, hi, pk, &ch))
-        return rc;
     char* const back_pin = ch.back_pin;
     HIP_TRY(ctx, hipMemcpyAsync(back_pin, ch.rec_dev, ch.back_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -207,6 +211,20 @@ int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const
     for (int k = 0; k < m; ++k)
         n_peaks[k] = state[2 * k];
     return CSM_OK;
+}
+
+/* The peaks as a unit on the volume: k_max rounds, no check of their own; window i's records go to
+ * rec[i * k_max ...] and its count to n_peaks[i]. */
+VolumeUnit peaks_unit(csm_ctx* ctx, const csm_peaks_params* pk, csm_result* rec, int32_t* n_peaks)
+{
+    VolumeUnit u;
+    const int k_max = pk->k_max;
+    u.sel = { k_max, pk->excl_x, pk->excl_y, pk->excl_theta };
+    u.scratch_limit = pk->scratch_limit_bytes;
+    u.body = [=](std::vector<PeakWindow>&, int lo, int hi, const PeakChunk& ch) {
+        return copy_back(ctx, ch, hi - lo, k_max, rec + (size_t)lo * k_max, n_peaks + lo);
+    };
+    return u;
 }
 
 } /* namespace */
@@ -331,13 +349,86 @@ int peaks_project_chunk(csm_ctx* ctx, const csm_loop_query* queries, std::vector
     return CSM_OK;
 }
 
-void peaks_fill_poses(csm_summary& o, const double relative_sensor_pose[3])
+/* ---- the host driver of the units on the volume ---- */
+
+double clock_us()
 {
+    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+int volume_window(csm_ctx* ctx, const VolumeUnit& u, uint64_t map_id, const csm_window* w, const int32_t* hit_col,
+                  const int32_t* hit_row)
+{
+    int rc;
+    std::vector<PeakWindow> wins(1);
+    PeakWindow& pw = wins[0];
+    pw.map_id = map_id;
+    pw.w = *w;
+    if ((rc = peaks_size_window(ctx, pw, u.scratch_limit, 0))) return rc;
+    if (u.check && (rc = u.check(pw, 0))) return rc;
+    if (w->low_resolution > 1 && !level_holds(*pw.grid, w->coarse_level, w->low_resolution))
+        return fail(ctx, CSM_ENOENT, "level %d does not hold box-max(%d)", w->coarse_level, w->low_resolution);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t hn = (size_t)w->n_theta * w->n_points;
+    if ((rc = reserve(ctx, ctx->pk_hits, hn * 8))) return rc;
+    pw.hit_off = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pk_hits.p, hit_col, hn * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pk_hits.as<int32_t>() + hn, hit_row, hn * 4, hipMemcpyHostToDevice, ctx->stream));
+    PeakChunk ch;
+    if ((rc = peaks_select_chunk(ctx, wins, 0, 1, u.sel, &ch)) || (rc = u.body(wins, 0, 1, ch)))
+        (void)hipStreamSynchronize(ctx->stream);    /* no copy from the caller's arrays stays pending */
+    return rc;
+}
+
+int volume_batch(csm_ctx* ctx, const VolumeUnit& u, const csm_loop_query* queries, int n,
+                 const csm_correlative_params* prm, double t0_us, std::vector<csm_summary>& head, double* setup_us,
+                 double* opt_us)
+{
+    int rc;
+    std::vector<PeakWindow> wins;
+    if ((rc = peaks_prepare_queries(ctx, queries, n, prm, u.scratch_limit, wins, head))) return rc;
+    for (int i = 0; u.check && i < n; ++i)
+        if ((rc = u.check(wins[i], i))) return rc;
+    const double t1_us = clock_us();
+    for (int lo = 0, hi; lo < n; lo = hi) {
+        hi = peaks_next_chunk(wins, lo, u.scratch_limit);
+        PeakChunk ch;
+        if ((rc = peaks_project_chunk(ctx, queries, wins, head, lo, hi))) return rc;
+        if ((rc = peaks_select_chunk(ctx, wins, lo, hi, u.sel, &ch))) return rc;
+        if ((rc = u.body(wins, lo, hi, ch))) return rc;
+    }
+    *setup_us = (t1_us - t0_us) / n;
+    *opt_us = (clock_us() - t1_us) / n;
+    return CSM_OK;
+}
+
+void fill_summary(csm_summary& o, const csm_summary& head, const csm_result& raw, bool found,
+                  const double rel_pose[3], double setup_us, double opt_us)
+{
+    o = head;
+    o.input_setup_us = setup_us;
+    o.optimization_us = opt_us;
+    if (!found)
+        return;
+    o.raw = raw;
     o.pose_found = o.raw.found;
     o.best_sensor_pose[0] = o.sensor_pose[0] + o.raw.best_x * o.step_x;
     o.best_sensor_pose[1] = o.sensor_pose[1] + o.raw.best_y * o.step_y;
     o.best_sensor_pose[2] = o.sensor_pose[2] + o.raw.best_theta * o.step_theta;
-    csm_host_move_backward(o.best_sensor_pose, relative_sensor_pose, o.estimated_pose);
+    csm_host_move_backward(o.best_sensor_pose, rel_pose, o.estimated_pose);
+}
+
+csm_loop_query single_query(uint64_t map_id, const csm_geometry* geom, const csm_scan* scan,
+                            const double initial_pose[3])
+{
+    csm_loop_query q;
+    std::memset(&q, 0, sizeof(q));
+    q.map_id = map_id;
+    q.geometry = *geom;
+    q.scan = *scan;
+    for (int k = 0; k < 3; ++k)
+        q.initial_pose[k] = initial_pose[k];
+    return q;
 }
 
 } /* namespace csm_host */
@@ -347,32 +438,18 @@ namespace {
 int peaks_batch(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_correlative_params* prm,
                 const csm_peaks_params* pk, csm_summary* out, int32_t* n_peaks)
 {
-    int rc;
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = clock_us();
     const int k_max = pk->k_max;
-    std::vector<PeakWindow> wins;
     std::vector<csm_summary> head;
-    if ((rc = peaks_prepare_queries(ctx, queries, n, prm, pk->scratch_limit_bytes, wins, head))) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
     std::vector<csm_result> rec((size_t)n * k_max);
-    for (int lo = 0, hi; lo < n; lo = hi) {
-        hi = peaks_next_chunk(wins, lo, pk->scratch_limit_bytes);
-        if ((rc = peaks_project_chunk(ctx, queries, wins, head, lo, hi))) return rc;
-        if ((rc = run_chunk(ctx, wins, lo, hi, pk, rec.data() + (size_t)lo * k_max, n_peaks + lo))) return rc;
-    }
-    const auto t2 = std::chrono::steady_clock::now();
-    const double setup = std::chrono::duration<double, std::micro>(t1 - t0).count() / n;
-    const double opt = std::chrono::duration<double, std::micro>(t2 - t1).count() / n;
+    double setup, opt;
+    if (int rc = volume_batch(ctx, peaks_unit(ctx, pk, rec.data(), n_peaks), queries, n, prm, t0, head, &setup, &opt))
+        return rc;
     std::memset(out, 0, sizeof(csm_summary) * (size_t)n * k_max);
     for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n_peaks[i]; ++j) {
-            csm_summary& o = out[(size_t)i * k_max + j];
-            o = head[i];
-            o.raw = rec[(size_t)i * k_max + j];
-            peaks_fill_poses(o, queries[i].scan.relative_sensor_pose);
-            o.input_setup_us = setup;
-            o.optimization_us = opt;
-        }
+        for (int j = 0; j < n_peaks[i]; ++j)
+            fill_summary(out[(size_t)i * k_max + j], head[i], rec[(size_t)i * k_max + j], true,
+                         queries[i].scan.relative_sensor_pose, setup, opt);
     return CSM_OK;
 }
 
@@ -385,30 +462,9 @@ int csm_score_window_peaks(csm_ctx* ctx, uint64_t map_id, const csm_window* w, c
 {
     if (!ctx || !w || !hit_col || !hit_row || !out || !n_peaks)
         return fail(ctx, CSM_EINVAL, "csm_score_window_peaks: bad arguments");
-    int rc;
-    if ((rc = check_params(ctx, pk, "csm_score_window_peaks"))) return rc;
-    std::vector<PeakWindow> wins(1);
-    PeakWindow& pw = wins[0];
-    pw.map_id = map_id;
-    pw.w = *w;
-    if ((rc = peaks_size_window(ctx, pw, pk->scratch_limit_bytes, 0))) return rc;
-    if (w->low_resolution > 1 &&
-        (w->coarse_level < 0 || w->coarse_level >= (int)pw.grid->levels.size() || pw.grid->levels[w->coarse_level].stale ||
-         pw.grid->levels[w->coarse_level].win != w->low_resolution))
-        return fail(ctx, CSM_ENOENT, "level %d does not hold box-max(%d)", w->coarse_level, w->low_resolution);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t hn = (size_t)w->n_theta * w->n_points;
-    if ((rc = reserve(ctx, ctx->pk_hits, hn * 8))) return rc;
-    pw.hit_off = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pk_hits.p, hit_col, hn * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pk_hits.as<int32_t>() + hn, hit_row, hn * 4, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<csm_result> rec((size_t)pk->k_max);
-    if ((rc = run_chunk(ctx, wins, 0, 1, pk, rec.data(), n_peaks))) {
-        (void)hipStreamSynchronize(ctx->stream);    /* no copy from the caller's arrays stays pending */
+    if (int rc = check_params(ctx, pk, "csm_score_window_peaks"))
         return rc;
-    }
-    std::memcpy(out, rec.data(), rec.size() * sizeof(csm_result));
-    return CSM_OK;
+    return volume_window(ctx, peaks_unit(ctx, pk, out, n_peaks), map_id, w, hit_col, hit_row);
 }
 
 int csm_correlative_peaks_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
@@ -431,13 +487,7 @@ int csm_correlative_peaks(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
         return fail(ctx, CSM_EINVAL, "csm_correlative_peaks: bad arguments");
     if (int rc = check_params(ctx, pk, "csm_correlative_peaks"))
         return rc;
-    csm_loop_query q;
-    std::memset(&q, 0, sizeof(q));
-    q.map_id = map_id;
-    q.geometry = *geom;
-    q.scan = *scan;
-    for (int k = 0; k < 3; ++k)
-        q.initial_pose[k] = initial_pose[k];
+    const csm_loop_query q = single_query(map_id, geom, scan, initial_pose);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return peaks_batch(ctx, &q, 1, prm, pk, out, n_peaks);
 }

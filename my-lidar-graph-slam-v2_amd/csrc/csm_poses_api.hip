@@ -11,13 +11,12 @@
  * most kFixBatchBytes of indices. An update queues k_pose_weights and k_pose_resample behind that. One
  * read-back of [counters][records][weights][ancestors][update record] ends the call. Nothing the context
  * keeps between calls is touched but these workspaces. */
-#include "csm_internal.hpp"
+#include "csm_matchers.hpp"     /* kKeyToScore */
 
 #include "csm_poses_kernels.hip"
 
 namespace {
 
-constexpr double kKeyToScore = 0.998 / (65534.0 * 499.0);     /* score = key * kKeyToScore / n_points */
 constexpr double kPoseMaxCell = 1073741824.0;                 /* 2^30 */
 constexpr int    kPoseMaxPoints = 65536;                      /* S = sum of n_points values <= 65535 fits uint32 */
 constexpr long long kPoseMaxCallPoses = 1ll << 30;

@@ -3,23 +3,20 @@
  * csm_host_motion_prior / csm_host_prior_from_robot_information), with its kernels
  * (csm_prior_kernels.hip). A translation unit of libcsm_hip.so of its own.
  *
- * The volume comes from the peaks' stages (csm_peaks.hpp): per chunk the scans are projected, every
- * candidate is scored exactly and dumped, the coarse known counts are counted (peaks_score_chunk: no
- * selection round of the peaks runs). Two launches follow on the same stream without a host wait: one pass
- * over every window's volume that keeps the winner under the prior and the unweighted one side by side
- * (one record per workgroup), and the pick that writes both records of every window. One copy brings the
- * csm_prior_results back. Scratch beyond the peaks' owners: pr_tab (job table, workgroup records,
- * results) and pr_pin. */
+ * A unit on the volume's host driver (csm_peaks.hpp: volume_window, volume_batch), which runs the peaks'
+ * stages: per chunk the scans are projected, every candidate is scored exactly and dumped, the coarse known
+ * counts are counted (peaks_score_chunk; with 0 rounds no selection round of the peaks runs). What is this
+ * unit's own: the quantisation of the prior (the named window's check of its sized window; the batch's
+ * pre-pass ahead of the driver) and the chunk body (run_chunk) -- two launches on the same stream without a
+ * host wait: one pass over every window's volume that keeps the winner under the prior and the unweighted
+ * one side by side (one record per workgroup), and the pick that writes both records of every window. One
+ * copy brings the csm_prior_results back. Scratch beyond the peaks' owners: pr_tab (job table, workgroup
+ * records, results) and pr_pin. */
 #include "csm_peaks.hpp"
 
 #include "csm_prior_kernels.hip"
 
 namespace {
-
-/* score = key * kKeyToScore / n_points */
-constexpr double kKeyToScore = 0.998 / (65534.0 * 499.0);
-
-static const int kA[6] = { 0, 0, 0, 1, 1, 2 }, kB[6] = { 0, 1, 2, 1, 2, 2 };    /* xx xy xt yy yt tt */
 
 int check_prior(csm_ctx* ctx, const csm_motion_prior* pr, const char* who)
 {
@@ -40,17 +37,13 @@ int quantise(csm_ctx* ctx, const csm_motion_prior* pr, const double steps[3], in
     return CSM_OK;
 }
 
-/* Windows [lo, hi) with their hit indices in pk_hits: volume, both winners. res[i - lo] receives them
+/* The chunk body: windows [lo, hi) with their volume scored (ch): both winners. res[i - lo] receives them
  * (Q[i - lo] goes in and is returned in the record). */
-int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const int64_t (*Q)[6], int64_t scratch_limit,
-              csm_prior_result* res)
+int run_chunk(csm_ctx* ctx, const std::vector<PeakWindow>& wins, int lo, int hi, const PeakChunk& ch,
+              const int64_t (*Q)[6], csm_prior_result* res)
 {
     const int m = hi - lo;
     int rc;
-    const csm_peaks_params one = { 1, 0, 0, 0, scratch_limit };
-    PeakChunk ch;
-    if ((rc = peaks_score_chunk(ctx, wins, lo, hi, &one, &ch))) return rc;
-
     /* pr_tab: [jobs][workgroup records][results]; pr_pin: [jobs][results] */
     const size_t jobs_bytes = align256((size_t)m * sizeof(PriorJob));
     const size_t part_bytes = align256((size_t)m * kPeakBlocksMax * sizeof(PriorBest));
@@ -99,12 +92,23 @@ int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const
     return CSM_OK;
 }
 
+/* The prior as a unit on the volume: no selection round of the peaks; the body leaves window i's result in
+ * res[i], from Q[i]. The named-window entry adds its check, which fills Q[0]. */
+VolumeUnit prior_unit(csm_ctx* ctx, int64_t scratch_limit, const int64_t (*Q)[6], csm_prior_result* res)
+{
+    VolumeUnit u;
+    u.scratch_limit = scratch_limit;
+    u.body = [=](std::vector<PeakWindow>& wins, int lo, int hi, const PeakChunk& ch) {
+        return run_chunk(ctx, wins, lo, hi, ch, Q + lo, res + lo);
+    };
+    return u;
+}
+
 int prior_batch(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_correlative_params* prm,
                 const csm_motion_prior* priors, csm_prior_summary* out)
 {
     int rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const int64_t limit = priors[0].scratch_limit_bytes;
+    const double t0 = clock_us();
     std::vector<int64_t> Q((size_t)n * 6);
     int64_t (*const Qs)[6] = reinterpret_cast<int64_t (*)[6]>(Q.data());
     /* every refusal of the prior before anything is allocated (the set-up below may build a coarse level):
@@ -128,31 +132,16 @@ int prior_batch(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_co
         const int d_max = std::max(2 * wt + 1, std::max(f.nx, f.ny)) - 1;
         if ((rc = quantise(ctx, &priors[i], st, q.scan.n_points, d_max, Qs[i], i))) return rc;
     }
-    std::vector<PeakWindow> wins;
     std::vector<csm_summary> head;
-    if ((rc = peaks_prepare_queries(ctx, queries, n, prm, limit, wins, head))) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
     std::vector<csm_prior_result> res(n);
-    for (int lo = 0, hi; lo < n; lo = hi) {
-        hi = peaks_next_chunk(wins, lo, limit);
-        if ((rc = peaks_project_chunk(ctx, queries, wins, head, lo, hi))) return rc;
-        if ((rc = run_chunk(ctx, wins, lo, hi, Qs + lo, limit, res.data() + lo))) return rc;
-    }
-    const auto t2 = std::chrono::steady_clock::now();
-    const double setup = std::chrono::duration<double, std::micro>(t1 - t0).count() / n;
-    const double opt = std::chrono::duration<double, std::micro>(t2 - t1).count() / n;
+    double setup, opt;
+    const VolumeUnit unit = prior_unit(ctx, priors[0].scratch_limit_bytes, Qs, res.data());
+    if ((rc = volume_batch(ctx, unit, queries, n, prm, t0, head, &setup, &opt))) return rc;
     std::memset(out, 0, sizeof(csm_prior_summary) * (size_t)n);
     for (int i = 0; i < n; ++i) {
-        csm_prior_summary& v = out[i];
-        v.prior = res[i];
-        csm_summary& o = v.summary;
-        o = head[i];
-        o.input_setup_us = setup;
-        o.optimization_us = opt;
-        if (!res[i].best.found)
-            continue;
-        o.raw = res[i].best;
-        peaks_fill_poses(o, queries[i].scan.relative_sensor_pose);
+        out[i].prior = res[i];
+        fill_summary(out[i].summary, head[i], res[i].best, res[i].best.found, queries[i].scan.relative_sensor_pose,
+                     setup, opt);
     }
     return CSM_OK;
 }
@@ -201,12 +190,8 @@ int csm_host_prior_from_robot_information(const double robot_information[9], con
     if (!robot_information || !initial_pose || !rel_pose || !out)
         return CSM_EINVAL;
     const double* const R = robot_information;
-    /* J: MoveBackward(sensor pose, rel_pose) by the sensor pose, at the initial pose */
-    const double sn = std::sin(initial_pose[2]), cs = std::cos(initial_pose[2]);
-    const double J[3][3] = { { 1.0, 0.0, sn * rel_pose[0] + cs * rel_pose[1] },
-                             { 0.0, 1.0, -cs * rel_pose[0] + sn * rel_pose[1] },
-                             { 0.0, 0.0, 1.0 } };
-    double T[3][3];         /* J^T R, then (J^T R) J; each sum ((k0 + k1) + k2) */
+    double J[3][3], T[3][3];         /* J at the initial pose; J^T R, then (J^T R) J; each sum ((k0 + k1) + k2) */
+    move_backward_jacobian(initial_pose[2], rel_pose, J);
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j)
             T[i][j] = (J[0][i] * R[j] + J[1][i] * R[3 + j]) + J[2][i] * R[6 + j];
@@ -224,30 +209,14 @@ int csm_score_window_prior(csm_ctx* ctx, uint64_t map_id, const csm_window* w, c
 {
     if (!ctx || !w || !hit_col || !hit_row || !out)
         return fail(ctx, CSM_EINVAL, "csm_score_window_prior: bad arguments");
-    int rc;
-    if ((rc = check_prior(ctx, prior, "csm_score_window_prior"))) return rc;
-    std::vector<PeakWindow> wins(1);
-    PeakWindow& pw = wins[0];
-    pw.map_id = map_id;
-    pw.w = *w;
-    if ((rc = peaks_size_window(ctx, pw, prior->scratch_limit_bytes, 0))) return rc;
-    int64_t Q[1][6];
-    if ((rc = quantise(ctx, prior, prior->steps, w->n_points, d_max_of(pw), Q[0], 0))) return rc;
-    if (w->low_resolution > 1 &&
-        (w->coarse_level < 0 || w->coarse_level >= (int)pw.grid->levels.size() || pw.grid->levels[w->coarse_level].stale ||
-         pw.grid->levels[w->coarse_level].win != w->low_resolution))
-        return fail(ctx, CSM_ENOENT, "level %d does not hold box-max(%d)", w->coarse_level, w->low_resolution);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t hn = (size_t)w->n_theta * w->n_points;
-    if ((rc = reserve(ctx, ctx->pk_hits, hn * 8))) return rc;
-    pw.hit_off = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pk_hits.p, hit_col, hn * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pk_hits.as<int32_t>() + hn, hit_row, hn * 4, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_chunk(ctx, wins, 0, 1, Q, prior->scratch_limit_bytes, out))) {
-        (void)hipStreamSynchronize(ctx->stream);    /* no copy from the caller's arrays stays pending */
+    if (int rc = check_prior(ctx, prior, "csm_score_window_prior"))
         return rc;
-    }
-    return CSM_OK;
+    int64_t Q[1][6];
+    VolumeUnit unit = prior_unit(ctx, prior->scratch_limit_bytes, Q, out);
+    unit.check = [&](const PeakWindow& pw, int index) {
+        return quantise(ctx, prior, prior->steps, w->n_points, d_max_of(pw), Q[0], index);
+    };
+    return volume_window(ctx, unit, map_id, w, hit_col, hit_row);
 }
 
 int csm_correlative_match_prior_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
@@ -271,13 +240,7 @@ int csm_correlative_match_prior(csm_ctx* ctx, uint64_t map_id, const csm_geometr
         return fail(ctx, CSM_EINVAL, "csm_correlative_match_prior: bad arguments");
     if (int rc = check_prior(ctx, prior, "csm_correlative_match_prior"))
         return rc;
-    csm_loop_query q;
-    std::memset(&q, 0, sizeof(q));
-    q.map_id = map_id;
-    q.geometry = *geom;
-    q.scan = *scan;
-    for (int k = 0; k < 3; ++k)
-        q.initial_pose[k] = initial_pose[k];
+    const csm_loop_query q = single_query(map_id, geom, scan, initial_pose);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return prior_batch(ctx, &q, 1, prm, prior, out);
 }

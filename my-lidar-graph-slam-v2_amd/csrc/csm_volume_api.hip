@@ -3,20 +3,20 @@
  * csm_host_volume_weights / csm_host_volume_covariance), with its kernels (csm_volume_kernels.hip). A
  * translation unit of libcsm_hip.so of its own.
  *
- * The volume and the winner come from the peaks' stages (csm_peaks.hpp): per chunk the scans are projected,
- * every candidate is scored exactly and dumped, the coarse known counts are counted and ONE selection
- * round picks the winner. Two more launches follow on the same stream without a host wait: the moments
- * of every window of the chunk (one record per workgroup) and their sums per window. One copy brings the
- * csm_volume_moments back; the covariance is a fixed f64 expression of them on the host. Scratch beyond
- * the peaks' owners: vc_tab (job table, weight tables, workgroup records, results) and vc_pin. */
+ * A unit on the volume's host driver (csm_peaks.hpp: volume_window, volume_batch), which runs the peaks'
+ * stages: per chunk the scans are projected, every candidate is scored exactly and dumped, the coarse known
+ * counts are counted and ONE selection round picks the winner. What is this unit's own: the temperature
+ * checks ahead of the driver, the range check of a sized window, and the chunk body (run_chunk) -- two more
+ * launches on the same stream without a host wait: the moments of every window of the chunk (one record
+ * per workgroup) and their sums per window. One copy brings the csm_volume_moments back; the covariance is
+ * a fixed f64 expression of them on the host. Scratch beyond the peaks' owners: vc_tab (job table, weight
+ * tables, workgroup records, results) and vc_pin. */
 #include "csm_peaks.hpp"
 
 #include "csm_volume_kernels.hip"
 
 namespace {
 
-/* score = key * kKeyToScore / n_points */
-constexpr double kKeyToScore = 0.998 / (65534.0 * 499.0);
 constexpr double kWeightOne = 16777216.0;     /* 2^24 */
 
 bool temperature_ok(double tau, int n_points)
@@ -49,16 +49,13 @@ struct WeightTable {
     int32_t shift;
 };
 
-/* Windows [lo, hi) with their hit indices in pk_hits: volume, winner, moments. mom[i - lo] receives them. */
-int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const csm_volume_params* vp,
-              csm_volume_moments* mom)
+/* The chunk body: windows [lo, hi) with their volume scored and their winner picked (ch): moments.
+ * mom[i - lo] receives them. */
+int run_chunk(csm_ctx* ctx, const std::vector<PeakWindow>& wins, int lo, int hi, const PeakChunk& ch,
+              const csm_volume_params* vp, csm_volume_moments* mom)
 {
     const int m = hi - lo;
     int rc;
-    const csm_peaks_params one = { 1, 0, 0, 0, vp->scratch_limit_bytes };
-    PeakChunk ch;
-    if ((rc = peaks_select_chunk(ctx, wins, lo, hi, &one, &ch))) return rc;
-
     /* one weight table per beam count of the chunk */
     std::map<int, int> table_of;
     std::vector<WeightTable> tables;
@@ -118,43 +115,42 @@ int run_chunk(csm_ctx* ctx, std::vector<PeakWindow>& wins, int lo, int hi, const
     return CSM_OK;
 }
 
+/* The covariance as a unit on the volume: one selection round picks the winner, the range check runs on the
+ * sized window, the body leaves window i's moments in mom[i]. */
+VolumeUnit covariance_unit(csm_ctx* ctx, const csm_volume_params* vp, csm_volume_moments* mom)
+{
+    VolumeUnit u;
+    u.sel.rounds = 1;
+    u.scratch_limit = vp->scratch_limit_bytes;
+    u.check = [=](const PeakWindow& pw, int index) { return check_range(ctx, pw, vp, index); };
+    u.body = [=](std::vector<PeakWindow>& wins, int lo, int hi, const PeakChunk& ch) {
+        return run_chunk(ctx, wins, lo, hi, ch, vp, mom + lo);
+    };
+    return u;
+}
+
 int covariance_batch(csm_ctx* ctx, const csm_loop_query* queries, int n, const csm_correlative_params* prm,
                      const csm_volume_params* vp, csm_volume_summary* out)
 {
-    int rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<PeakWindow> wins;
-    std::vector<csm_summary> head;
+    const double t0 = clock_us();
     /* every refusal before anything is allocated: the windows' shapes need nothing but the steps */
     for (int i = 0; i < n; ++i)
         if (queries[i].scan.n_points >= 1 && !temperature_ok(vp->temperature, queries[i].scan.n_points))
             return fail(ctx, CSM_EINVAL, "query %d: temperature %g puts the weight band beyond 2^62 keys", i,
                         vp->temperature);
-    if ((rc = peaks_prepare_queries(ctx, queries, n, prm, vp->scratch_limit_bytes, wins, head))) return rc;
-    for (int i = 0; i < n; ++i)
-        if ((rc = check_range(ctx, wins[i], vp, i))) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
+    std::vector<csm_summary> head;
     std::vector<csm_volume_moments> mom(n);
-    for (int lo = 0, hi; lo < n; lo = hi) {
-        hi = peaks_next_chunk(wins, lo, vp->scratch_limit_bytes);
-        if ((rc = peaks_project_chunk(ctx, queries, wins, head, lo, hi))) return rc;
-        if ((rc = run_chunk(ctx, wins, lo, hi, vp, mom.data() + lo))) return rc;
-    }
-    const auto t2 = std::chrono::steady_clock::now();
-    const double setup = std::chrono::duration<double, std::micro>(t1 - t0).count() / n;
-    const double opt = std::chrono::duration<double, std::micro>(t2 - t1).count() / n;
+    double setup, opt;
+    if (int rc = volume_batch(ctx, covariance_unit(ctx, vp, mom.data()), queries, n, prm, t0, head, &setup, &opt))
+        return rc;
     std::memset(out, 0, sizeof(csm_volume_summary) * (size_t)n);
     for (int i = 0; i < n; ++i) {
         csm_volume_summary& v = out[i];
         v.moments = mom[i];
         csm_summary& o = v.summary;
-        o = head[i];
-        o.input_setup_us = setup;
-        o.optimization_us = opt;
+        fill_summary(o, head[i], mom[i].best, mom[i].best.found, queries[i].scan.relative_sensor_pose, setup, opt);
         if (!mom[i].best.found)
             continue;
-        o.raw = mom[i].best;
-        peaks_fill_poses(o, queries[i].scan.relative_sensor_pose);
         const double steps[3] = { o.step_x, o.step_y, o.step_theta };
         csm_host_volume_covariance(&v.moments, steps, o.estimated_pose, queries[i].scan.relative_sensor_pose,
                                    v.mean_offset, v.sensor_covariance, v.covariance);
@@ -192,7 +188,6 @@ int csm_host_volume_covariance(const csm_volume_moments* m, const double steps[3
         sensor_cov[i] = cov[i] = 0.0;
     if (m->m0 <= 0)
         return CSM_OK;
-    static const int kA[6] = { 0, 0, 0, 1, 1, 2 }, kB[6] = { 0, 1, 2, 1, 2, 2 };    /* xx xy xt yy yt tt */
     const double m0 = (double)m->m0;
     for (int k = 0; k < 6; ++k) {
         const int a = kA[k], b = kB[k];
@@ -204,12 +199,8 @@ int csm_host_volume_covariance(const csm_volume_moments* m, const double steps[3
     }
     for (int a = 0; a < 3; ++a)
         mean_offset[a] = ((double)m->m1[a] / m0) * steps[a];
-    /* J: MoveBackward(sensor pose, rel_pose) by the sensor pose, at the estimated pose */
-    const double sn = std::sin(estimated_pose[2]), cs = std::cos(estimated_pose[2]);
-    const double J[3][3] = { { 1.0, 0.0, sn * rel_pose[0] + cs * rel_pose[1] },
-                             { 0.0, 1.0, -cs * rel_pose[0] + sn * rel_pose[1] },
-                             { 0.0, 0.0, 1.0 } };
-    double T[3][3];         /* J S, then (J S) J^T; each sum ((k0 + k1) + k2) */
+    double J[3][3], T[3][3];         /* J at the estimated pose; J S, then (J S) J^T; each sum ((k0 + k1) + k2) */
+    move_backward_jacobian(estimated_pose[2], rel_pose, J);
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j)
             T[i][j] = (J[i][0] * sensor_cov[j] + J[i][1] * sensor_cov[3 + j]) + J[i][2] * sensor_cov[6 + j];
@@ -224,32 +215,12 @@ int csm_score_window_moments(csm_ctx* ctx, uint64_t map_id, const csm_window* w,
 {
     if (!ctx || !w || !hit_col || !hit_row || !out)
         return fail(ctx, CSM_EINVAL, "csm_score_window_moments: bad arguments");
-    int rc;
-    if ((rc = check_params(ctx, vp, "csm_score_window_moments"))) return rc;
-    std::vector<PeakWindow> wins(1);
-    PeakWindow& pw = wins[0];
-    pw.map_id = map_id;
-    pw.w = *w;
+    if (int rc = check_params(ctx, vp, "csm_score_window_moments"))
+        return rc;
     if (w->n_points >= 1 && !temperature_ok(vp->temperature, w->n_points))
         return fail(ctx, CSM_EINVAL, "csm_score_window_moments: temperature %g puts the weight band beyond 2^62 keys",
                     vp->temperature);
-    if ((rc = peaks_size_window(ctx, pw, vp->scratch_limit_bytes, 0))) return rc;
-    if ((rc = check_range(ctx, pw, vp, 0))) return rc;
-    if (w->low_resolution > 1 &&
-        (w->coarse_level < 0 || w->coarse_level >= (int)pw.grid->levels.size() || pw.grid->levels[w->coarse_level].stale ||
-         pw.grid->levels[w->coarse_level].win != w->low_resolution))
-        return fail(ctx, CSM_ENOENT, "level %d does not hold box-max(%d)", w->coarse_level, w->low_resolution);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t hn = (size_t)w->n_theta * w->n_points;
-    if ((rc = reserve(ctx, ctx->pk_hits, hn * 8))) return rc;
-    pw.hit_off = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pk_hits.p, hit_col, hn * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pk_hits.as<int32_t>() + hn, hit_row, hn * 4, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_chunk(ctx, wins, 0, 1, vp, out))) {
-        (void)hipStreamSynchronize(ctx->stream);    /* no copy from the caller's arrays stays pending */
-        return rc;
-    }
-    return CSM_OK;
+    return volume_window(ctx, covariance_unit(ctx, vp, out), map_id, w, hit_col, hit_row);
 }
 
 int csm_correlative_covariance_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_queries,
@@ -272,13 +243,7 @@ int csm_correlative_covariance(csm_ctx* ctx, uint64_t map_id, const csm_geometry
         return fail(ctx, CSM_EINVAL, "csm_correlative_covariance: bad arguments");
     if (int rc = check_params(ctx, vp, "csm_correlative_covariance"))
         return rc;
-    csm_loop_query q;
-    std::memset(&q, 0, sizeof(q));
-    q.map_id = map_id;
-    q.geometry = *geom;
-    q.scan = *scan;
-    for (int k = 0; k < 3; ++k)
-        q.initial_pose[k] = initial_pose[k];
+    const csm_loop_query q = single_query(map_id, geom, scan, initial_pose);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return covariance_batch(ctx, &q, 1, prm, vp, out);
 }
