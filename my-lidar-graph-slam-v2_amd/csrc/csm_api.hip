@@ -158,9 +158,6 @@ int csm_destroy(csm_ctx* ctx)
     ctx->resident_hold.clear();
     for (hipEvent_t e : ctx->event_pool)
         (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->m_ev)
-        if (e)
-            (void)hipEventDestroy(e);
     if (ctx->own_stream)
         (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;                           /* the grids and buffers free themselves */
@@ -259,7 +256,7 @@ int csm_upload_grid_blocks(csm_ctx* ctx, uint64_t map_id, const uint16_t* const*
     if (int rc = grow(ctx, g.alloc, (size_t)n_blocks + 64, (size_t)n_blocks + 64, false))
         return rc;
     /* pinned staging: [first known row, column][slot of every block][the allocated blocks]; one DMA */
-    const size_t head = (((size_t)(2 + n_blocks) * 4) + 255) & ~(size_t)255;
+    const size_t head = align256((size_t)(2 + n_blocks) * 4);
     const size_t stage_bytes = head + (size_t)n_alloc * block_cells * 2;
     if (int rc = grow(ctx, ctx->pin, stage_bytes, stage_bytes + stage_bytes / 4, false))
         return rc;

@@ -360,31 +360,23 @@ int BatchGroup::plan()
 int BatchGroup::stage_scans()
 {
     scan_off.resize(nq);
-    std::vector<int> first_use;             /* scans are laid out in first-use order */
-    std::map<std::tuple<const double*, const double*, int>, size_t> seen;
-    for (int k = 0; k < nq; ++k) {
-        const csm_scan& sc = queries[idx[k]].scan;
-        auto key = std::make_tuple(sc.angles, sc.ranges, pp[k].n);
-        auto it = resident ? seen.end() : seen.find(key);
-        if (it != seen.end()) {
-            scan_off[k] = it->second;       /* a duplicate of an earlier query's scan */
-            continue;
+    if (resident) {                         /* no scan is staged and none is shared: the offsets only count */
+        for (int k = 0; k < nq; ++k) {
+            scan_off[k] = scan_total;
+            scan_total += 2 * (size_t)pp[k].n;
         }
-        scan_off[k] = scan_total;
-        if (!resident) {
-            seen.emplace(key, scan_total);
-            first_use.push_back(k);
-        }
-        scan_total += 2 * (size_t)pp[k].n;
-    }
-    if (!resident) {
+    } else {
+        ScanTable table;                    /* scans are laid out in first-use order: [angles | ranges] each */
+        for (int k = 0; k < nq; ++k)
+            scan_off[k] = 2 * (size_t)table.slot(queries[idx[k]].scan, k);
+        scan_total = 2 * (size_t)table.beams;
         const size_t need = scan_total * 8;
         if (int rc = grow(ctx, ctx->pin_scans, need, need + need / 4 + 64, false))
             return rc;
         scans = ctx->pin_scans.as<double>();
-        host_parallel_for((int)first_use.size(), 128, [&](int lo, int hi) {
+        host_parallel_for((int)table.first_use.size(), 128, [&](int lo, int hi) {
             for (int j = lo; j < hi; ++j) {
-                const int k = first_use[j];
+                const int k = table.first_use[j];
                 const csm_loop_query& q = queries[idx[k]];
                 std::memcpy(scans + scan_off[k], q.scan.angles, (size_t)pp[k].n * 8);
                 std::memcpy(scans + scan_off[k] + pp[k].n, q.scan.ranges, (size_t)pp[k].n * 8);
@@ -595,12 +587,12 @@ int BatchGroup::upload_tables()
     if ((rc = take_pinned(ctx, tables_cap, &tables))) return rc;
     char* const jb0 = reinterpret_cast<char*>(ctx->b_jobs.p);
     char* const hb0 = tables.as<char>();
-    size_t tables_off = 0;
+    Carve c;
     auto put = [&](const void* src, size_t bytes, char** dev) -> hipError_t {
-        *dev = jb0 + tables_off;
-        std::memcpy(hb0 + tables_off, src, bytes);
-        tables_off += (bytes + 255) & ~(size_t)255;
-        return tables_off <= tables_cap ? hipSuccess : hipErrorInvalidValue;
+        const size_t at = c.take(bytes);
+        *dev = jb0 + at;
+        std::memcpy(hb0 + at, src, bytes);
+        return c.off <= tables_cap ? hipSuccess : hipErrorInvalidValue;
     };
     if (H > 0)
         HIP_TRY(ctx, put(zj.data(), zj.size() * sizeof(ZeroJob), &d_zj));
@@ -612,7 +604,7 @@ int BatchGroup::upload_tables()
     HIP_TRY(ctx, put(fj.data(), nq * sizeof(FinalJob), &d_fj));
     for (int h = 0; h <= H; ++h)
         HIP_TRY(ctx, put(sj[h].data(), nq * sizeof(ScoreJob), &d_sj[h]));
-    HIP_TRY(ctx, hipMemcpyAsync(jb0, hb0, tables_off, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(jb0, hb0, c.off, hipMemcpyHostToDevice, ctx->stream));
     tick("jobs");
     return CSM_OK;
 }
@@ -718,13 +710,9 @@ int BatchGroup::finish()
 {
     int rc;
     if (resident) {
-        hipEvent_t done = nullptr;
-        if (!ctx->event_pool.empty()) {
-            done = ctx->event_pool.back();
-            ctx->event_pool.pop_back();
-        } else {
-            HIP_TRY(ctx, hipEventCreate(&done));
-        }
+        const hipEvent_t done = take_event(ctx);
+        if (!done)
+            return fail(ctx, CSM_EIO, "resident batch: no event to hold the job tables by");
         HIP_TRY(ctx, hipEventRecord(done, ctx->stream));
         ctx->resident_hold.emplace_back(done, std::move(tables));
         return CSM_OK;

@@ -19,10 +19,11 @@ int launch_block_allocation(csm_ctx* ctx, DeviceGrid& g, int log2b, const uint8_
         return fail(ctx, CSM_EINVAL, "block allocation: %zu blocks", bytes);
     if (int rc = grow(ctx, g.alloc, bytes, bytes + 64, false))
         return rc;
-    hipLaunchKernelGGL(k_block_allocation, dim3((unsigned)bytes), dim3(256), 0, ctx->stream,
-                       g.levels[0].cells, g.rows, g.cols, g.pitch, log2b, bcols, carried, carried_brows,
-                       carried_bcols, carried_br0, carried_bc0, g.alloc.as<uint8_t>());
-    HIP_TRY(ctx, hipGetLastError());
+    const int e = launch(k_block_allocation, dim3((unsigned)bytes), dim3(256), ctx->stream, g.levels[0].cells, g.rows,
+                         g.cols, g.pitch, log2b, bcols, carried, carried_brows, carried_bcols, carried_br0, carried_bc0,
+                         g.alloc.as<uint8_t>());
+    if (int rc = launched_ok(ctx, e, "block allocation"))
+        return rc;
     g.alloc_log2 = log2b;
     g.alloc_bcols = bcols;
     g.alloc_stale = false;
@@ -120,8 +121,9 @@ int run_cost_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n, const
                                 hipMemcpyHostToDevice, ctx->stream));
     {
         ScopedTimer tm(ctx, "cost_refine");
-        hipLaunchKernelGGL(k_cost_refine, dim3(n), dim3(kCostBlock), 0, ctx->stream, d_jobs);
-        HIP_TRY(ctx, hipGetLastError());
+        const int e = launch(k_cost_refine, dim3(n), dim3(kCostBlock), ctx->stream, d_jobs);
+        if ((rc = launched_ok(ctx, e, "cost refine")))
+            return rc;
     }
     std::vector<CostOut> res((size_t)n);
     HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_out, (size_t)n * sizeof(CostOut), hipMemcpyDeviceToHost, ctx->stream));

@@ -316,9 +316,10 @@ int run_greedy_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n, con
                                 ctx->stream));
     {
         ScopedTimer tm(ctx, "greedy");
-        hipLaunchKernelGGL(k_greedy, dim3(n), dim3(kGreedyBlock), 0, ctx->stream,
-                           reinterpret_cast<const GreedyTab*>(ctx->g_tab.p), d_jobs, d_out);
-        HIP_TRY(ctx, hipGetLastError());
+        const int e = launch(k_greedy, dim3(n), dim3(kGreedyBlock), ctx->stream,
+                             reinterpret_cast<const GreedyTab*>(ctx->g_tab.p), d_jobs, d_out);
+        if ((rc = launched_ok(ctx, e, "greedy")))
+            return rc;
     }
     std::vector<GreedyOut> res((size_t)n);
     HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_out, (size_t)n * sizeof(GreedyOut), hipMemcpyDeviceToHost,

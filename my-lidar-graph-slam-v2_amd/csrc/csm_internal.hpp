@@ -1,6 +1,8 @@
 /* csm_internal.hpp -- what the translation units of libcsm_hip.so share on the host side: the
  * context (device grids, workspaces, tuning switches, graphs), error / timing helpers and the owners
- * of device and pinned memory (DevBuf, PinBuf: move-only, freed by their destructors, grown by grow()).
+ * of device and pinned memory (DevBuf, PinBuf: move-only, freed by their destructors, grown by grow()),
+ * and the plumbing every unit's host side is written in: launched_ok, align256 / Carve, reserve, ScanTable,
+ * take_event / CallSpan / ScopedTimer, clock_us.
  * csm_api.hip (matchers), csm_map_api.hip (map updates), csm_cost_api.hip (cost / covariance /
  * refinement) and csm_group.hip (several GPUs in one process) are compiled on their own. */
 #ifndef CSM_INTERNAL_HPP
@@ -29,6 +31,7 @@
 #include <vector>
 
 #include "csm_device.hpp"
+#include "csm_launch.hpp"
 #include "../../include/csm_hip.h"
 
 using namespace csm;
@@ -259,10 +262,8 @@ struct csm_ctx {
     DevBuf m_rays, m_recs, m_cell, m_lists, m_cnt, m_lut;
     DevBuf m_alloc;                               /* the old map's allocation bitmap during a build */
     double m_lut_hit = -1.0, m_lut_miss = -1.0;   /* probabilities the update tables were built for */
-    bool m_apply_attr = false, m_batch_attr = false, m_global_attr = false;
     int m_cus = 0;                                /* compute units of the device (the batch's persistent kernel) */
     DevBuf m_btab;                                /* csm_construct_maps_from_scans: job and prefix tables */
-    hipEvent_t m_ev[2] = { nullptr, nullptr };    /* device_us of csm_map_build_info */
     std::vector<double> stage;                    /* host staging of one scan (angles, ranges) */
     /* pinned job-table blocks of csm_score_windows_dev calls (sources of asynchronous
      * uploads), each kept until the event recorded behind its launch chain has fired; an entry
@@ -331,6 +332,92 @@ inline int ensure(csm_ctx* ctx, DevBuf& b, size_t bytes)
     return grow(ctx, b, bytes, bytes + bytes / 4 + 256, true);
 }
 
+/* a workspace no recorded graph points at: the same slack, pinned or device */
+template <bool Pinned>
+int reserve(csm_ctx* ctx, HipBuf<Pinned>& b, size_t n) { return grow(ctx, b, n, n + n / 4 + 256, false); }
+
+using csm_launch::keep_first;       /* what the units with kernels of their own launch through */
+using csm_launch::launch;
+using csm_launch::launch_lds;
+
+/* What every wrapper of the launch layer (csm_launch.hpp) returns: a HIP error code, or -1 for "no kernel
+ * instantiated". */
+inline int launched_ok(csm_ctx* ctx, int e, const char* what)
+{
+    if (e < 0)
+        return fail(ctx, CSM_EINVAL, "internal: no %s kernel for this launch shape", what);
+    if (e != 0)
+        return fail(ctx, CSM_EIO, "%s kernel launch failed: %s", what, hipGetErrorString((hipError_t)e));
+    return CSM_OK;
+}
+
+constexpr size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+/* one allocation carved into 256-byte aligned pieces: take() returns a piece's offset, `off` is the size so far */
+struct Carve {
+    size_t off = 0;
+    size_t take(size_t bytes)
+    {
+        const size_t o = off;
+        off += align256(bytes);
+        return o;
+    }
+};
+
+/* The distinct scans of a call in first-use order. A scan is its two arrays and its length: the same arrays
+ * at another length are another scan. */
+struct ScanTable {
+    std::map<std::tuple<const double*, const double*, int>, long long> seen;
+    std::vector<int> first_use;   /* the users that fed a scan the table did not hold: they copy it */
+    long long beams = 0;          /* of the distinct scans */
+
+    /* the slot of `user`'s scan, counted in beams */
+    long long slot(const csm_scan& sc, int user)
+    {
+        const auto ins = seen.emplace(std::make_tuple(sc.angles, sc.ranges, (int)sc.n_points), beams);
+        if (ins.second) {
+            first_use.push_back(user);
+            beams += sc.n_points;
+        }
+        return ins.first->second;
+    }
+};
+
+/* Microseconds on the clock of the timing fields. */
+inline double clock_us()
+{
+    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+/* an event of the context's pool, or a new one; null: none could be created */
+inline hipEvent_t take_event(csm_ctx* ctx)
+{
+    hipEvent_t e = nullptr;
+    if (!ctx->event_pool.empty()) {
+        e = ctx->event_pool.back();
+        ctx->event_pool.pop_back();
+    } else {
+        (void)hipEventCreate(&e);
+    }
+    return e;
+}
+
+/* The events of one call's device_us (none for a caller who does not want it): back into the context's pool
+ * however the call ends. */
+struct CallSpan {
+    csm_ctx* ctx;
+    hipEvent_t a, b;
+    explicit CallSpan(csm_ctx* c, bool wanted = true)
+        : ctx(c), a(wanted ? take_event(c) : nullptr), b(wanted ? take_event(c) : nullptr) {}
+    CallSpan(const CallSpan&) = delete;
+    CallSpan& operator=(const CallSpan&) = delete;
+    ~CallSpan()
+    {
+        if (a) ctx->event_pool.push_back(a);
+        if (b) ctx->event_pool.push_back(b);
+    }
+};
+
 struct ScopedTimer {
     csm_ctx* ctx;
     hipEvent_t a = nullptr, b = nullptr;
@@ -340,18 +427,8 @@ struct ScopedTimer {
         if (!ctx->timing || ctx->capturing ||
             (ctx->timing == 2 && std::strcmp(n, "score_fine") != 0 && std::strcmp(n, "score_bound") != 0))
             return;
-        auto get = [&]() {
-            hipEvent_t e = nullptr;
-            if (!ctx->event_pool.empty()) {
-                e = ctx->event_pool.back();
-                ctx->event_pool.pop_back();
-            } else {
-                (void)hipEventCreate(&e);
-            }
-            return e;
-        };
-        a = get();
-        b = get();
+        a = take_event(ctx);
+        b = take_event(ctx);
         (void)hipEventRecord(a, ctx->stream);
     }
     ~ScopedTimer()
@@ -375,6 +452,13 @@ inline bool scan_is_finite(const csm_scan* scan)
             return false;
     return std::isfinite(scan->relative_sensor_pose[0]) && std::isfinite(scan->relative_sensor_pose[1]) &&
            std::isfinite(scan->relative_sensor_pose[2]);
+}
+
+/* A map frame the projections can divide by: a finite resolution above zero, finite offsets. */
+inline bool geometry_is_finite(const csm_geometry* geom)
+{
+    return std::isfinite(geom->resolution) && geom->resolution > 0.0 && std::isfinite(geom->offset_x) &&
+           std::isfinite(geom->offset_y);
 }
 
 inline DeviceGrid* find_grid(csm_ctx* ctx, uint64_t id)

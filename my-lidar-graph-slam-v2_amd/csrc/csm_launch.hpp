@@ -8,7 +8,9 @@
  *
  * What the three units share is here too: THE tables of instantiated launch shapes (the planner picks
  * from them, the dispatch expands them), the one launch descriptor, and the helpers the wrappers are
- * written in (match, grant_lds, launch / launch_lds). */
+ * written in (match, grant_lds, launch / launch_lds). The units that compile their kernels with their host
+ * code (maps, cost, greedy, pose graph, peaks, volume, prior, likelihood, ray check, pose sets) launch through
+ * launch / launch_lds directly: no kernel is launched, and no dynamic-LDS limit raised, anywhere else. */
 #ifndef CSM_LAUNCH_HPP
 #define CSM_LAUNCH_HPP
 
@@ -149,6 +151,13 @@ int launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t s, const A&.
 {
     hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
     return (int)hipGetLastError();
+}
+
+/* A chain of launches that is checked once, where it ends: `e` keeps the first code that is not 0. */
+inline void keep_first(int& e, int code)
+{
+    if (!e)
+        e = code;
 }
 
 /* ---- the wrappers of csm_launch.hip ---- */

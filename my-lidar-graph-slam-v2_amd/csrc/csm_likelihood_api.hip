@@ -15,7 +15,7 @@ static_assert(kLfMaxR == CSM_LIKELIHOOD_MAX_RADIUS, "the kernel's LDS tile is si
 
 namespace {
 
-constexpr size_t kLfTableBytes = ((size_t)(kLfMaxR * kLfMaxR + 1) * 4 + 255) & ~(size_t)255;
+constexpr size_t kLfTableBytes = align256((size_t)(kLfMaxR * kLfMaxR + 1) * 4);
 
 bool likelihood_params_ok(const csm_likelihood_params* p)
 {
@@ -120,19 +120,20 @@ int csm_build_likelihood_maps(csm_ctx* ctx, const uint64_t* src_ids, const uint6
     }
 
     /* [table][jobs][counters]: one upload */
-    const size_t jobs_bytes = ((size_t)n * sizeof(LfJob) + 255) & ~(size_t)255;
-    const size_t block = kLfTableBytes + jobs_bytes + (size_t)n * 8;
-    if (int rc = grow(ctx, ctx->lf_tab, block, block + block / 4, false))
+    Carve c;
+    c.take(kLfTableBytes);
+    const size_t jobs_at = c.take((size_t)n * sizeof(LfJob)), known_at = c.off, block = known_at + (size_t)n * 8;
+    if (int rc = reserve(ctx, ctx->lf_tab, block))
         return rc;
-    if (int rc = grow(ctx, ctx->lf_pin, block, block + block / 4, false))
+    if (int rc = reserve(ctx, ctx->lf_pin, block))
         return rc;
     char* const pin = ctx->lf_pin.as<char>();
     char* const dev = ctx->lf_tab.as<char>();
     std::memset(pin, 0, kLfTableBytes);
     std::memcpy(pin, prm->kernel, (size_t)(prm->radius * prm->radius + 1) * 4);
-    LfJob* const jobs_pin = reinterpret_cast<LfJob*>(pin + kLfTableBytes);
-    int32_t* const known_pin = reinterpret_cast<int32_t*>(pin + kLfTableBytes + jobs_bytes);
-    int32_t* const known_dev = reinterpret_cast<int32_t*>(dev + kLfTableBytes + jobs_bytes);
+    LfJob* const jobs_pin = reinterpret_cast<LfJob*>(pin + jobs_at);
+    int32_t* const known_pin = reinterpret_cast<int32_t*>(pin + known_at);
+    int32_t* const known_dev = reinterpret_cast<int32_t*>(dev + known_at);
     int rows_max = 0, pitch_max = 0;
     for (int i = 0; i < n; ++i) {
         const DeviceGrid& s = *find_grid(ctx, src_ids[i]);
@@ -158,12 +159,13 @@ int csm_build_likelihood_maps(csm_ctx* ctx, const uint64_t* src_ids, const uint6
     lp.pad = 0;
     {
         ScopedTimer tm(ctx, "likelihood");
-        const LfJob* const jobs_dev = reinterpret_cast<const LfJob*>(dev + kLfTableBytes);
+        const LfJob* const jobs_dev = reinterpret_cast<const LfJob*>(dev + jobs_at);
         for (int first = 0; first < n; first += 65535) {      /* grid.z limit */
             const unsigned nz = (unsigned)std::min(65535, n - first);
-            hipLaunchKernelGGL(k_likelihood_batch, dim3(ceil_div(pitch_max, kLfTC), ceil_div(rows_max, kLfTR), nz),
-                               dim3(256), 0, ctx->stream, jobs_dev + first, lp);
-            HIP_TRY(ctx, hipGetLastError());
+            const int e = launch(k_likelihood_batch, dim3(ceil_div(pitch_max, kLfTC), ceil_div(rows_max, kLfTR), nz),
+                                 dim3(256), ctx->stream, jobs_dev + first, lp);
+            if (int rc = launched_ok(ctx, e, "likelihood field"))
+                return rc;
         }
     }
     HIP_TRY(ctx, hipMemcpyAsync(known_pin, known_dev, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));

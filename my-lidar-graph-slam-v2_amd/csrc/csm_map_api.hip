@@ -435,9 +435,9 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
     if (!ctx || !shape || !global_map_pose || !prm || prm->subpixel_scale < 1 || prm->subpixel_scale > 1024)
         return fail(ctx, CSM_EINVAL, "map build: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = clock_us();
     const int scale = prm->subpixel_scale;
-    int rc = 0;
+    int rc = 0, e = 0;
     MapBuild m;
     m.map_id = map_id;
     m.shape = shape;
@@ -498,9 +498,9 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
         pj.unc_cap = unc_cap;
         {
             ScopedTimer tm(ctx, "map_project");
-            hipLaunchKernelGGL(k_map_project, dim3((unsigned)ceil_div(n_rays, 256)), dim3(256), 0, ctx->stream, pj);
+            e = launch(k_map_project, dim3((unsigned)ceil_div(n_rays, 256)), dim3(256), ctx->stream, pj);
         }
-        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = launched_ok(ctx, e, "map project"))) return rc;
         int32_t got[8];
         HIP_TRY(ctx, hipMemcpyAsync(got, d_box, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -520,12 +520,6 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
     const size_t n_cells = m.n_cells;
 
     /* the two value -> value tables of the cell update */
-    if (!ctx->m_apply_attr) {
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_map_apply_hits),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         65536 * (int)sizeof(uint16_t)));
-        ctx->m_apply_attr = true;
-    }
     if ((rc = map_ensure_tables(ctx, prm))) return rc;
 
     /* the carried bitmap waits in ctx->m_alloc until the new one is built */
@@ -546,14 +540,13 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
     map_fill_job(m, scale, reinterpret_cast<const uint16_t*>(ctx->m_lut.p), mj);
     unsigned long long counters[kMapCounters] = { 0 };
     counters[kMapKnownRow] = counters[kMapKnownCol] = ~0ull;
-    const auto t1 = std::chrono::steady_clock::now();
-    if (info && !ctx->m_ev[0]) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->m_ev[0]));
-        HIP_TRY(ctx, hipEventCreate(&ctx->m_ev[1]));
+    const double t1 = clock_us();
+    CallSpan span(ctx, info != nullptr);    /* device_us: events only for a caller who asks */
+    if (info) {
+        if (!span.a || !span.b)
+            return fail(ctx, CSM_EIO, "map build: no event for device_us");
+        HIP_TRY(ctx, hipEventRecord(span.a, ctx->stream));
     }
-    const hipEvent_t ev_a = ctx->m_ev[0], ev_b = ctx->m_ev[1];
-    if (info)
-        HIP_TRY(ctx, hipEventRecord(ev_a, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_nodes, m.table.data(), m.table.size() * sizeof(MapNode),
                                 hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(mj.counters, counters, sizeof(counters), hipMemcpyHostToDevice, ctx->stream));
@@ -563,37 +556,37 @@ static int map_build(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape,
         const unsigned ray_blocks = (unsigned)ceil_div(std::max(n_rays, 1), 256);
         const unsigned cell_blocks = (unsigned)((n_cells + 255) / 256);
         if (n_rays) {
-            hipLaunchKernelGGL(k_map_hits, dim3(ray_blocks), dim3(256), 0, ctx->stream, mj);
-            hipLaunchKernelGGL(k_map_alloc, dim3(cell_blocks), dim3(256), 0, ctx->stream, mj);
-            hipLaunchKernelGGL(k_map_fill_hits, dim3(ray_blocks), dim3(256), 0, ctx->stream, mj);
-            hipLaunchKernelGGL(k_map_rank_hits, dim3(ray_blocks), dim3(256), 0, ctx->stream, mj);
-            hipLaunchKernelGGL(k_map_walk, dim3((unsigned)ceil_div(n_rays, kMapGroup)), dim3(512), 0, ctx->stream, mj);
+            keep_first(e, launch(k_map_hits, dim3(ray_blocks), dim3(256), ctx->stream, mj));
+            keep_first(e, launch(k_map_alloc, dim3(cell_blocks), dim3(256), ctx->stream, mj));
+            keep_first(e, launch(k_map_fill_hits, dim3(ray_blocks), dim3(256), ctx->stream, mj));
+            keep_first(e, launch(k_map_rank_hits, dim3(ray_blocks), dim3(256), ctx->stream, mj));
+            keep_first(e, launch(k_map_walk, dim3((unsigned)ceil_div(n_rays, kMapGroup)), dim3(512), ctx->stream, mj));
         }
-        hipLaunchKernelGGL(k_map_apply, dim3((unsigned)(((size_t)mj.rows * mj.pitch + 255) / 256)), dim3(256), 0,
-                           ctx->stream, mj);
+        keep_first(e, launch(k_map_apply, dim3((unsigned)(((size_t)mj.rows * mj.pitch + 255) / 256)), dim3(256),
+                             ctx->stream, mj));
         if (m.usable > 0) {
             /* one workgroup per CU at most; the kernel spreads the cells with hits over
              * their wavefronts (each has at least one usable ray) */
             const unsigned wgs = (unsigned)std::min<long long>(
                 256, ceil_div((int)std::min<long long>(m.usable, (long long)n_cells), 4));
-            hipLaunchKernelGGL(k_map_apply_hits, dim3(wgs), dim3(256), 65536 * sizeof(uint16_t), ctx->stream, mj);
+            keep_first(e, launch_lds(ctx->device, k_map_apply_hits, dim3(wgs), dim3(256), 65536 * sizeof(uint16_t),
+                                     ctx->stream, mj));
         }
-        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = launched_ok(ctx, e, "map build"))) return rc;
         /* the old allocation moved by the block shift, and every block a cell update touched
          * (each leaves a known cell) */
         if ((rc = map_carry_allocation(ctx, m, ctx->m_alloc))) return rc;
     }
-    HIP_TRY(ctx, hipGetLastError());
     if (info)
-        HIP_TRY(ctx, hipEventRecord(ev_b, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(span.b, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(counters, mj.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     float dev_ms = 0.f;
     if (info)
-        (void)hipEventElapsedTime(&dev_ms, ev_a, ev_b);
+        (void)hipEventElapsedTime(&dev_ms, span.a, span.b);
     if ((rc = map_finish(ctx, m, counters, info))) return rc;
     if (info) {
-        info->host_us = std::chrono::duration<double, std::micro>(t1 - t0).count();
+        info->host_us = t1 - t0;
         info->device_us = dev_ms * 1e3;
     }
     return CSM_OK;

@@ -82,9 +82,9 @@ void prepare_job(csm_ctx* ctx, csm_map_build_job& job, const csm_map_builder_par
 int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
               const csm_map_builder_params* prm, csm_map_batch_info* binfo)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = clock_us();
     const int scale = prm->subpixel_scale;
-    int rc = 0;
+    int rc = 0, e = 0;
     const uint32_t unc_cap = map_unc_cap(ctx);
 
     /* ---- the chunk's scratch that does not depend on the cell counts ---- */
@@ -144,8 +144,8 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
     uint32_t beam_blocks = 0;
     {
         /* every distinct scan of the chunk once: angles, then ranges */
-        std::map<std::tuple<const double*, const double*, int>, long long> seen;
-        std::vector<double> stage;
+        ScanTable scans;                                /* its users are the chunk's nodes */
+        std::vector<const csm_scan*> scan_of(n_nodes_all, nullptr);
         std::vector<long long> node_src(2 * n_nodes_all, 0);
         for (int j = 0; j < n; ++j) {
             BatchJob& b = *chunk[j];
@@ -156,16 +156,18 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
             const csm_scan_node* nodes = jobs[b.index].nodes;
             for (int k = 0; k < b.n_nodes; ++k) {
                 const csm_scan& sc = nodes[k].scan;
-                const auto key = std::make_tuple(sc.angles, sc.ranges, (int)sc.n_points);
-                auto it = seen.find(key);
-                if (it == seen.end()) {
-                    it = seen.emplace(key, (long long)stage.size()).first;
-                    stage.insert(stage.end(), sc.angles, sc.angles + sc.n_points);
-                    stage.insert(stage.end(), sc.ranges, sc.ranges + sc.n_points);
-                }
-                node_src[2 * (b.node0 + k)] = it->second;
-                node_src[2 * (b.node0 + k) + 1] = it->second + sc.n_points;
+                const long long at = 2 * scans.slot(sc, (int)(b.node0 + k));
+                scan_of[b.node0 + k] = &sc;
+                node_src[2 * (b.node0 + k)] = at;
+                node_src[2 * (b.node0 + k) + 1] = at + sc.n_points;
             }
+        }
+        std::vector<double> stage;
+        stage.reserve(2 * (size_t)scans.beams);
+        for (int node : scans.first_use) {
+            const csm_scan& sc = *scan_of[node];
+            stage.insert(stage.end(), sc.angles, sc.angles + sc.n_points);
+            stage.insert(stage.end(), sc.ranges, sc.ranges + sc.n_points);
         }
         h_pre[n] = beam_blocks;
         if (beam_blocks) {
@@ -203,9 +205,9 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
             HIP_TRY(ctx, hipMemcpyAsync(ctx->m_btab.p, tab_host.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
             {
                 ScopedTimer tm(ctx, "map_batch_project");
-                hipLaunchKernelGGL(k_mapb_project, dim3(beam_blocks), dim3(256), 0, ctx->stream, tab);
+                e = launch(k_mapb_project, dim3(beam_blocks), dim3(256), ctx->stream, tab);
             }
-            HIP_TRY(ctx, hipGetLastError());
+            if ((rc = launched_ok(ctx, e, "map batch project"))) return rc;
             /* the one read-back of the projection: every map's box, count and spread bits */
             HIP_TRY(ctx, hipMemcpyAsync(boxes.data(), d_box, boxes.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -249,14 +251,10 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
 
     if ((rc = map_ensure_tables(ctx, prm))) return rc;
     uint16_t* d_lut = reinterpret_cast<uint16_t*>(ctx->m_lut.p);
-    if (!ctx->m_batch_attr) {
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_mapb_apply_hits),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         65536 * (int)sizeof(uint16_t)));
+    if (!ctx->m_cus) {
         int cus = 0;
         HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
         ctx->m_cus = std::max(cus, 1);
-        ctx->m_batch_attr = true;
     }
 
     /* ---- per map: the carried allocation (it waits in the job's own buffer: many are alive at once)
@@ -317,15 +315,14 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
         pre[2 * tab_words + n] = groups;
         pre[3 * tab_words + n] = apply_blocks;
     }
-    const auto t1 = std::chrono::steady_clock::now();
+    const double t1 = clock_us();
     float dev_ms = 0.f;
     if (n_live) {
-        if (!ctx->m_ev[0]) {
-            HIP_TRY(ctx, hipEventCreate(&ctx->m_ev[0]));
-            HIP_TRY(ctx, hipEventCreate(&ctx->m_ev[1]));
-        }
+        CallSpan span(ctx);
+        if (!span.a || !span.b)
+            return fail(ctx, CSM_EIO, "map batch: no event for device_us");
         gather_nodes();
-        HIP_TRY(ctx, hipEventRecord(ctx->m_ev[0], ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(span.a, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(d_nodes, nodes_host.data(), nodes_host.size() * sizeof(MapNode),
                                     hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(d_counters, counters.data(), counters.size() * sizeof(unsigned long long),
@@ -335,35 +332,34 @@ int run_chunk(csm_ctx* ctx, csm_map_build_job* jobs, BatchJob** chunk, int n,
         {
             ScopedTimer tm(ctx, "map_batch_build");
             if (ray_blocks) {
-                hipLaunchKernelGGL(k_mapb_hits, dim3(ray_blocks), dim3(256), 0, ctx->stream, tab);
-                hipLaunchKernelGGL(k_mapb_alloc, dim3(cell_blocks), dim3(256), 0, ctx->stream, tab);
-                hipLaunchKernelGGL(k_mapb_fill_hits, dim3(ray_blocks), dim3(256), 0, ctx->stream, tab);
-                hipLaunchKernelGGL(k_mapb_rank_hits, dim3(ray_blocks), dim3(256), 0, ctx->stream, tab);
-                hipLaunchKernelGGL(k_mapb_walk, dim3(groups), dim3(512), 0, ctx->stream, tab);
+                keep_first(e, launch(k_mapb_hits, dim3(ray_blocks), dim3(256), ctx->stream, tab));
+                keep_first(e, launch(k_mapb_alloc, dim3(cell_blocks), dim3(256), ctx->stream, tab));
+                keep_first(e, launch(k_mapb_fill_hits, dim3(ray_blocks), dim3(256), ctx->stream, tab));
+                keep_first(e, launch(k_mapb_rank_hits, dim3(ray_blocks), dim3(256), ctx->stream, tab));
+                keep_first(e, launch(k_mapb_walk, dim3(groups), dim3(512), ctx->stream, tab));
             }
-            hipLaunchKernelGGL(k_mapb_apply, dim3(apply_blocks), dim3(256), 0, ctx->stream, tab);
+            keep_first(e, launch(k_mapb_apply, dim3(apply_blocks), dim3(256), ctx->stream, tab));
             if (usable_all > 0) {
                 /* one workgroup per CU at most, the hit table loaded once each; the kernel spreads the
                  * chunk's cells with hits over their wavefronts */
                 const unsigned wgs = (unsigned)std::min<long long>(
                     ctx->m_cus, (std::min<long long>(usable_all, (long long)n_cells_all) + 3) / 4);
-                hipLaunchKernelGGL(k_mapb_hit_prefix, dim3(1), dim3(256), 0, ctx->stream, tab);
-                hipLaunchKernelGGL(k_mapb_apply_hits, dim3(wgs), dim3(256), 65536 * sizeof(uint16_t), ctx->stream,
-                                   tab, (const uint16_t*)d_lut);
+                keep_first(e, launch(k_mapb_hit_prefix, dim3(1), dim3(256), ctx->stream, tab));
+                keep_first(e, launch_lds(ctx->device, k_mapb_apply_hits, dim3(wgs), dim3(256), 65536 * sizeof(uint16_t),
+                                         ctx->stream, tab, (const uint16_t*)d_lut));
             }
-            HIP_TRY(ctx, hipGetLastError());
+            if ((rc = launched_ok(ctx, e, "map batch build"))) return rc;
             for (int j = 0; j < n; ++j)
                 if (chunk[j]->live && (rc = map_carry_allocation(ctx, *chunk[j], chunk[j]->carried))) return rc;
         }
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipEventRecord(ctx->m_ev[1], ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(span.b, ctx->stream));
         /* the one read-back of the update: every map's counter block */
         HIP_TRY(ctx, hipMemcpyAsync(counters.data(), d_counters, counters.size() * sizeof(unsigned long long),
                                     hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipEventElapsedTime(&dev_ms, ctx->m_ev[0], ctx->m_ev[1]);
+        (void)hipEventElapsedTime(&dev_ms, span.a, span.b);
     }
-    const double host_us = std::chrono::duration<double, std::micro>(t1 - t0).count();
+    const double host_us = t1 - t0;
     if (binfo) {
         ++binfo->chunks;
         binfo->host_us += host_us;

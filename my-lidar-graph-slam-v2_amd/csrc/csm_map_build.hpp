@@ -1,8 +1,8 @@
 /* csm_map_build.hpp -- the host steps of a map build, each on ONE map, defined in csm_map_api.hip.
  * map_build (csm_map_api.hip) runs them on its one map; run_chunk (csm_map_batch_api.hip) runs each
  * in a loop over the chunk's jobs before the next one starts. What stays with the callers: the
- * launches and per-kernel attributes, the sizes and carving of the scratch buffers, where the
- * carried bitmap waits, the synchronises behind asynchronous uploads, and host_us / device_us.
+ * launches, the sizes and carving of the scratch buffers, where the carried bitmap waits, the
+ * synchronises behind asynchronous uploads, and host_us / device_us.
  *
  * Every step fails through fail(ctx, ...) and returns the code. map_node_table, map_resize and
  * map_finish refuse a MAP (CSM_EINVAL, CSM_ENOENT): a batch goes on with its other jobs.

@@ -113,11 +113,13 @@ int project_part(csm_ctx* ctx, Part& p, Scratch& s, int scale)
         pj.unc_count = reinterpret_cast<uint32_t*>(s.box + 4);
         pj.unc_list = s.unc_list;
         pj.unc_cap = s.unc_cap;
+        int e;
         {
             ScopedTimer tm(ctx, "gmap_project");
-            hipLaunchKernelGGL(k_gmap_project, dim3((unsigned)ceil_div(n_rays, 256)), dim3(256), 0, ctx->stream, pj);
+            e = launch(k_gmap_project, dim3((unsigned)ceil_div(n_rays, 256)), dim3(256), ctx->stream, pj);
         }
-        HIP_TRY(ctx, hipGetLastError());
+        if (int rc = launched_ok(ctx, e, "global map project"))
+            return rc;
         const size_t words = 8 + std::min<size_t>(s.unc_cap, (size_t)n_rays);
         HIP_TRY(ctx, hipMemcpyAsync(s.got.data(), s.box, words * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -200,7 +202,7 @@ int csm_construct_global_map(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape
     if (limit < 0 || direct_max < 1 || tile < 4 || tile > kGmapTileMax || (tile & (tile - 1)))
         return fail(ctx, CSM_EINVAL, "global map: bad scratch limit or rank settings");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = clock_us();
     const int scale = prm->subpixel_scale;
     int rc = 0;
 
@@ -292,11 +294,6 @@ int csm_construct_global_map(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape
             p.table[k].sx = whole.table[(size_t)p.first + k].sx;
             p.table[k].sy = whole.table[(size_t)p.first + k].sy;
         }
-    if (!ctx->m_global_attr) {
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_gmap_apply_hits),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * (int)sizeof(uint16_t)));
-        ctx->m_global_attr = true;
-    }
     if ((rc = map_ensure_tables(ctx, prm))) return rc;
     bool synced = false;
     if ((rc = map_claim_grid(ctx, whole, ctx->m_alloc, synced))) return rc;
@@ -314,13 +311,12 @@ int csm_construct_global_map(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape
     counters[kMapKnownRow] = counters[kMapKnownCol] = ~0ull;
     const GmapRank rk = { (uint32_t)direct_max, (uint32_t)tile };
     const uint16_t* d_lut = reinterpret_cast<const uint16_t*>(ctx->m_lut.p);
-    const auto t1 = std::chrono::steady_clock::now();
+    const double t1 = clock_us();
     double cast_host_us = 0.0;
-    if (!ctx->m_ev[0]) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->m_ev[0]));
-        HIP_TRY(ctx, hipEventCreate(&ctx->m_ev[1]));
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->m_ev[0], ctx->stream));
+    CallSpan span(ctx);
+    if (!span.a || !span.b)
+        return fail(ctx, CSM_EIO, "global map: no event for device_us");
+    HIP_TRY(ctx, hipEventRecord(span.a, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(s.counters, counters, sizeof(counters), hipMemcpyHostToDevice, ctx->stream));
     for (size_t i = 0; i < parts->size(); ++i) {
         Part& p = (*parts)[i];
@@ -328,9 +324,9 @@ int csm_construct_global_map(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape
             continue;                        /* nothing to add to the cells */
         if (reproject) {
             /* the host waits here (staging, the projection's read-back, patches): host time, not device */
-            const auto h0 = std::chrono::steady_clock::now();
+            const double h0 = clock_us();
             if ((rc = project_part(ctx, p, s, scale))) return rc;
-            cast_host_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
+            cast_host_us += clock_us() - h0;
         }
         p.keep_cells = i > 0;
         p.next = whole.next;
@@ -351,64 +347,69 @@ int csm_construct_global_map(csm_ctx* ctx, uint64_t map_id, csm_map_shape* shape
                                     ctx->stream));
         if (i > 0) {
             /* the words of a part: list cursor, hit cells, long cells. The totals go on. */
-            hipLaunchKernelGGL(k_gmap_next_part, dim3(1), dim3(64), 0, ctx->stream, s.counters);
+            if ((rc = launched_ok(ctx, launch(k_gmap_next_part, dim3(1), dim3(64), ctx->stream, s.counters),
+                                  "global map next part")))
+                return rc;
         }
         HIP_TRY(ctx, hipMemsetAsync(mj.n_hit, 0, 2 * n_cells * sizeof(uint32_t), ctx->stream));
-        const unsigned ray_blocks = (unsigned)ceil_div(std::max(n_rays, 1), 256);
-        const unsigned cell_blocks = (unsigned)((n_cells + 255) / 256);
+        const dim3 ray_blocks((unsigned)ceil_div(std::max(n_rays, 1), 256));
+        const dim3 cell_blocks((unsigned)((n_cells + 255) / 256));
+        const dim3 blk(256);
+        int e = 0;
         if (n_rays) {
             {
                 ScopedTimer tm(ctx, "gmap_hits");
-                hipLaunchKernelGGL(k_gmap_hits, dim3(ray_blocks), dim3(256), 0, ctx->stream, mj);
+                keep_first(e, launch(k_gmap_hits, ray_blocks, blk, ctx->stream, mj));
             }
             {
                 ScopedTimer tm(ctx, "gmap_alloc");
-                hipLaunchKernelGGL(k_gmap_alloc, dim3(cell_blocks), dim3(256), 0, ctx->stream, mj, rk);
+                keep_first(e, launch(k_gmap_alloc, cell_blocks, blk, ctx->stream, mj, rk));
             }
             {
                 ScopedTimer tm(ctx, "gmap_fill_hits");
-                hipLaunchKernelGGL(k_gmap_fill_hits, dim3(ray_blocks), dim3(256), 0, ctx->stream, mj);
+                keep_first(e, launch(k_gmap_fill_hits, ray_blocks, blk, ctx->stream, mj));
             }
             {
                 ScopedTimer tm(ctx, "gmap_rank_direct");
-                hipLaunchKernelGGL(k_gmap_rank_direct, dim3(ray_blocks), dim3(256), 0, ctx->stream, mj, rk);
+                keep_first(e, launch(k_gmap_rank_direct, ray_blocks, blk, ctx->stream, mj, rk));
             }
             /* a long cell has more than direct_max hits: at most this many of them */
             const unsigned long_max = (unsigned)(p.usable / ((long long)direct_max + 1));
             if (long_max) {
                 ScopedTimer tm(ctx, "gmap_rank_sort");
-                hipLaunchKernelGGL(k_gmap_rank_sort, dim3(long_max), dim3(256), (size_t)tile * sizeof(uint32_t),
-                                   ctx->stream, mj, rk);
+                keep_first(e, launch_lds(ctx->device, k_gmap_rank_sort, dim3(long_max), blk,
+                                         (size_t)tile * sizeof(uint32_t), ctx->stream, mj, rk));
             }
             {
                 ScopedTimer tm(ctx, "gmap_walk");
-                hipLaunchKernelGGL(k_gmap_walk, dim3((unsigned)ceil_div(n_rays, kMapGroup)), dim3(512), 0, ctx->stream, mj);
+                keep_first(e, launch(k_gmap_walk, dim3((unsigned)ceil_div(n_rays, kMapGroup)), dim3(512), ctx->stream,
+                                     mj));
             }
         }
         {
             ScopedTimer tm(ctx, "gmap_apply");
-            hipLaunchKernelGGL(k_gmap_apply, dim3((unsigned)(((size_t)mj.rows * mj.pitch + 255) / 256)), dim3(256), 0,
-                               ctx->stream, mj);
+            const dim3 apply_blocks((unsigned)(((size_t)mj.rows * mj.pitch + 255) / 256));
+            keep_first(e, launch(k_gmap_apply, apply_blocks, blk, ctx->stream, mj));
         }
         if (p.usable > 0) {
             const unsigned wgs = (unsigned)std::min<long long>(
                 256, ceil_div((int)std::min<long long>(p.usable, (long long)n_cells), 4));
             ScopedTimer tm(ctx, "gmap_apply_hits");
-            hipLaunchKernelGGL(k_gmap_apply_hits, dim3(wgs), dim3(256), 65536 * sizeof(uint16_t), ctx->stream, mj);
+            keep_first(e, launch_lds(ctx->device, k_gmap_apply_hits, dim3(wgs), blk, 65536 * sizeof(uint16_t),
+                                     ctx->stream, mj));
         }
-        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = launched_ok(ctx, e, "global map cast"))) return rc;
     }
     /* the old allocation moved by the block shift, and every block that holds a known cell */
     if ((rc = map_carry_allocation(ctx, whole, ctx->m_alloc))) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->m_ev[1], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(span.b, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(counters, s.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     float dev_ms = 0.f;
-    (void)hipEventElapsedTime(&dev_ms, ctx->m_ev[0], ctx->m_ev[1]);
+    (void)hipEventElapsedTime(&dev_ms, span.a, span.b);
     /* host_us: everything up to the first launch of the cast phase, plus each part's projection when the
      * parts are projected again; device_us: the event span of the cast phase less that */
-    const double host_us = std::chrono::duration<double, std::micro>(t1 - t0).count() + cast_host_us;
+    const double host_us = t1 - t0 + cast_host_us;
     const double device_us = std::max(0.0, dev_ms * 1e3 - cast_host_us);
     if (ginfo) {
         std::memset(ginfo, 0, sizeof(*ginfo));

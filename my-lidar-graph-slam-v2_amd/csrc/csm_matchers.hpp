@@ -6,8 +6,6 @@
 #define CSM_MATCHERS_HPP
 
 #include "csm_internal.hpp"
-
-#include "csm_launch.hpp"
 #include "csm_joint.hpp"
 #include "csm_phase.hpp"
 
@@ -133,7 +131,6 @@ FinalJob final_job(const ScoreJob& fine, int n_blocks, const int32_t* hit_col, c
                    double score_thr, const double* lut, void* out);
 ExactJob exact_job(const DeviceGrid& g, const uint16_t* cells, int n_theta, int n_points, int x_lo, int y_lo,
                    int nx, int ny, int stride, const double* lut, double* out_score, uint32_t* out_k);
-int launched_ok(csm_ctx* ctx, int e, const char* what);
 csm_launch::ScoreLaunch score_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, size_t lds);
 int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out);
 int launch_score(csm_ctx* ctx, const ScoreJob& job, const PassPlan& pp, int n_theta, int n_slices);

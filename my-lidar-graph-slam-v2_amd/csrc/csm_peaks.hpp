@@ -82,11 +82,6 @@ namespace csm_host {
 constexpr int64_t kPeaksDefaultScratch = (int64_t)1 << 30;
 constexpr int64_t kPeaksMaxCandidates = (int64_t)1 << 26;
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-/* a scratch owner of the volume entries: no recorded graph points at it */
-inline int reserve(csm_ctx* ctx, DevBuf& b, size_t bytes) { return grow(ctx, b, bytes, bytes + bytes / 4 + 256, false); }
-
 /* One window of a peaks call once its arguments are checked. */
 struct PeakWindow {
     uint64_t map_id = 0;
@@ -158,8 +153,6 @@ struct VolumeUnit {
     std::function<int(std::vector<PeakWindow>& wins, int lo, int hi, const PeakChunk& ch)> body;
 };
 
-/* Microseconds on the clock of the timing fields. */
-double clock_us();
 /* One window with the caller's hit indices and a coarse level the caller names: size, check, level, device,
  * hits into pk_hits, stages, body. A failure past the upload waits for the stream, so that no copy from the
  * caller's arrays stays pending. */

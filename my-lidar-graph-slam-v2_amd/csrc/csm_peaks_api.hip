@@ -351,11 +351,6 @@ int peaks_project_chunk(csm_ctx* ctx, const csm_loop_query* queries, std::vector
 
 /* ---- the host driver of the units on the volume ---- */
 
-double clock_us()
-{
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 int volume_window(csm_ctx* ctx, const VolumeUnit& u, uint64_t map_id, const csm_window* w, const int32_t* hit_col,
                   const int32_t* hit_row)
 {

@@ -552,16 +552,6 @@ ExactJob exact_job(const DeviceGrid& g, const uint16_t* cells, int n_theta, int 
     return j;
 }
 
-/* What every wrapper of the launch layer returns: a HIP error code, or -1 for "no kernel instantiated". */
-int launched_ok(csm_ctx* ctx, int e, const char* what)
-{
-    if (e < 0)
-        return fail(ctx, CSM_EINVAL, "internal: no %s kernel for this launch shape", what);
-    if (e != 0)
-        return fail(ctx, CSM_EIO, "%s kernel launch failed: %s", what, hipGetErrorString((hipError_t)e));
-    return CSM_OK;
-}
-
 /* the fields of a csm_launch::ScoreLaunch a pass plan decides */
 csm_launch::ScoreLaunch score_launch(const csm_ctx* ctx, const PassPlan& pp, dim3 grid, size_t lds)
 {

@@ -412,59 +412,65 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
     }
 }
 
-/* one device allocation carved into 256-byte aligned pieces */
-struct Carve {
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
+/* One launch of a chain on the context's stream. A chain keeps the first code that is not 0 in `e` and
+ * hands it to launched_ok where the chain, or a step of it, ends. */
+template <class... P, class... A>
+void pg_launch(csm_ctx* ctx, int& e, void (*kernel)(P...), dim3 grid, dim3 block, const A&... args)
+{
+    keep_first(e, launch(kernel, grid, block, ctx->stream, args...));
+}
+
+/* grids of kPgsBlock threads: one thread per item; a grid-stride loop over the cells of a matrix */
+dim3 pg_over(int64_t count) { return dim3((unsigned)((count + kPgsBlock - 1) / kPgsBlock)); }
+dim3 pg_strided(int64_t cells) { return dim3((unsigned)std::min<int64_t>((cells + kPgsBlock - 1) / kPgsBlock, 16384)); }
+
+/* the blocked LDL^T of S in place: per panel its diagonal tile, then the panel below it and the trailing update */
+void pg_ldl_launches(csm_ctx* ctx, int& e, const PgSchurJob& Q)
+{
+    const int nt = Q.np / kPgsTile;
+    for (int p = 0; p < nt; ++p) {
+        pg_launch(ctx, e, k_pgs_ldl_diag, dim3(1), dim3(kPgsBlock), Q, p);
+        const int below = nt - p - 1;
+        if (below) {
+            pg_launch(ctx, e, k_pgs_ldl_panel, dim3(ceil_div(below * kPgsTile, 64)), dim3(64), Q, p);
+            pg_launch(ctx, e, k_pgs_ldl_update, dim3(below, below), dim3(kPgsBlock), Q, p);
+        }
     }
-};
+}
 
 /* the direct solver's launches for one Optimize call: the initial total error, then the chain of one
  * LM step iterations_max times (a step's kernels return at once after the step that stopped) */
 int pg_schur_chain(csm_ctx* ctx, const PgSchurJob& Q, bool small)
 {
     const PgJob& J = Q.J;
-    hipStream_t s = ctx->stream;
     const dim3 blk(kPgsBlock);
-    const int n_scan = J.n_nodes - J.n_local, nt = Q.np / kPgsTile;
-    auto over = [](int64_t count) { return dim3((unsigned)((count + kPgsBlock - 1) / kPgsBlock)); };
+    const int n_scan = J.n_nodes - J.n_local;
+    int e = 0;
     if (J.n_edges)
-        hipLaunchKernelGGL(k_pgs_error, over(J.n_edges), blk, 0, s, Q);
-    hipLaunchKernelGGL(k_pgs_decide, dim3(1), blk, 0, s, Q, 1);
+        pg_launch(ctx, e, k_pgs_error, pg_over(J.n_edges), blk, Q);
+    pg_launch(ctx, e, k_pgs_decide, dim3(1), blk, Q, 1);
     for (int it = 0; it < J.iterations_max; ++it) {
         if (J.n_edges)
-            hipLaunchKernelGGL(k_pgs_edges, over(J.n_edges), blk, 0, s, Q);
-        hipLaunchKernelGGL(k_pgs_assemble, over((int64_t)J.n_nodes + J.n_cross), blk, 0, s, Q);
+            pg_launch(ctx, e, k_pgs_edges, pg_over(J.n_edges), blk, Q);
+        pg_launch(ctx, e, k_pgs_assemble, pg_over((int64_t)J.n_nodes + J.n_cross), blk, Q);
         if (n_scan)
-            hipLaunchKernelGGL(k_pgs_eliminate, over(n_scan), blk, 0, s, Q);
+            pg_launch(ctx, e, k_pgs_eliminate, pg_over(n_scan), blk, Q);
         if (small) {
-            hipLaunchKernelGGL(k_pgs_small, dim3(1), blk, 0, s, Q);
+            pg_launch(ctx, e, k_pgs_small, dim3(1), blk, Q);
         } else {
-            const int64_t cells = (int64_t)Q.np * Q.np;
-            hipLaunchKernelGGL(k_pgs_clear, dim3((unsigned)std::min<int64_t>((cells + kPgsBlock - 1) / kPgsBlock, 16384)),
-                               blk, 0, s, Q);
-            hipLaunchKernelGGL(k_pgs_schur, over(9 * (int64_t)Q.n_sblk + Q.np), blk, 0, s, Q);
-            for (int p = 0; p < nt; ++p) {
-                hipLaunchKernelGGL(k_pgs_ldl_diag, dim3(1), blk, 0, s, Q, p);
-                const int below = nt - p - 1;
-                if (below) {
-                    hipLaunchKernelGGL(k_pgs_ldl_panel, dim3(ceil_div(below * kPgsTile, 64)), dim3(64), 0, s, Q, p);
-                    hipLaunchKernelGGL(k_pgs_ldl_update, dim3(below, below), blk, 0, s, Q, p);
-                }
-            }
-            hipLaunchKernelGGL(k_pgs_solve, dim3(1), dim3(kPgsSolveBlock), 0, s, Q);
+            pg_launch(ctx, e, k_pgs_clear, pg_strided((int64_t)Q.np * Q.np), blk, Q);
+            pg_launch(ctx, e, k_pgs_schur, pg_over(9 * (int64_t)Q.n_sblk + Q.np), blk, Q);
+            pg_ldl_launches(ctx, e, Q);
+            pg_launch(ctx, e, k_pgs_solve, dim3(1), dim3(kPgsSolveBlock), Q);
         }
         if (n_scan)
-            hipLaunchKernelGGL(k_pgs_back, over(n_scan), blk, 0, s, Q);
-        hipLaunchKernelGGL(k_pgs_update, dim3(Q.nb_vars), blk, 0, s, Q);
+            pg_launch(ctx, e, k_pgs_back, pg_over(n_scan), blk, Q);
+        pg_launch(ctx, e, k_pgs_update, dim3(Q.nb_vars), blk, Q);
         if (J.n_edges)
-            hipLaunchKernelGGL(k_pgs_error, over(J.n_edges), blk, 0, s, Q);
-        hipLaunchKernelGGL(k_pgs_decide, dim3(1), blk, 0, s, Q, 0);
-        HIP_TRY(ctx, hipGetLastError());
+            pg_launch(ctx, e, k_pgs_error, pg_over(J.n_edges), blk, Q);
+        pg_launch(ctx, e, k_pgs_decide, dim3(1), blk, Q, 0);
+        if (int rc = launched_ok(ctx, e, "pose-graph LM step"))
+            return rc;
     }
     return CSM_OK;
 }
@@ -680,34 +686,24 @@ int pg_cov_chain(csm_ctx* ctx, const PgCovJob& C, const std::vector<int32_t>& co
 {
     const PgSchurJob& Q = C.Q;
     const PgJob& J = Q.J;
-    hipStream_t s = ctx->stream;
     const dim3 blk(kPgsBlock);
     const int n_scan = J.n_nodes - J.n_local, nt = Q.np / kPgsTile, ng = C.ldx / kPgsTile;
-    auto over = [](int64_t count) { return dim3((unsigned)((count + kPgsBlock - 1) / kPgsBlock)); };
-    auto strided = [](int64_t cells) {
-        return dim3((unsigned)std::min<int64_t>((cells + kPgsBlock - 1) / kPgsBlock, 16384));
-    };
+    int e = 0;
     if (J.n_edges)
-        hipLaunchKernelGGL(k_pgs_edges, over(J.n_edges), blk, 0, s, Q);
-    hipLaunchKernelGGL(k_pgs_assemble, over((int64_t)J.n_nodes + J.n_cross), blk, 0, s, Q);
+        pg_launch(ctx, e, k_pgs_edges, pg_over(J.n_edges), blk, Q);
+    pg_launch(ctx, e, k_pgs_assemble, pg_over((int64_t)J.n_nodes + J.n_cross), blk, Q);
     if (n_scan)
-        hipLaunchKernelGGL(k_pgs_eliminate, over(n_scan), blk, 0, s, Q);
-    hipLaunchKernelGGL(k_pgs_clear, strided((int64_t)Q.np * Q.np), blk, 0, s, Q);
-    hipLaunchKernelGGL(k_pgs_schur, over(9 * (int64_t)Q.n_sblk + Q.np), blk, 0, s, Q);
+        pg_launch(ctx, e, k_pgs_eliminate, pg_over(n_scan), blk, Q);
+    pg_launch(ctx, e, k_pgs_clear, pg_strided((int64_t)Q.np * Q.np), blk, Q);
+    pg_launch(ctx, e, k_pgs_schur, pg_over(9 * (int64_t)Q.n_sblk + Q.np), blk, Q);
     {
         ScopedTimer tm(ctx, "pose_graph_marginals_factor");
-        for (int p = 0; p < nt; ++p) {
-            hipLaunchKernelGGL(k_pgs_ldl_diag, dim3(1), blk, 0, s, Q, p);
-            const int below = nt - p - 1;
-            if (below) {
-                hipLaunchKernelGGL(k_pgs_ldl_panel, dim3(ceil_div(below * kPgsTile, 64)), dim3(64), 0, s, Q, p);
-                hipLaunchKernelGGL(k_pgs_ldl_update, dim3(below, below), blk, 0, s, Q, p);
-            }
-        }
+        pg_ldl_launches(ctx, e, Q);
     }
-    HIP_TRY(ctx, hipGetLastError());
+    if (int rc = launched_ok(ctx, e, "pose-graph marginals factor"))
+        return rc;
     ScopedTimer tm(ctx, "pose_graph_marginals_solve");
-    hipLaunchKernelGGL(k_pgc_init, strided((int64_t)Q.np * C.ldx), blk, 0, s, C);
+    pg_launch(ctx, e, k_pgc_init, pg_strided((int64_t)Q.np * C.ldx), blk, C);
     /* forward: the groups whose first unit row lies in panel p or above it (C ascends, so a prefix) */
     int live = 0;
     for (int p = 0; p < nt; ++p) {
@@ -715,19 +711,18 @@ int pg_cov_chain(csm_ctx* ctx, const PgCovJob& C, const std::vector<int32_t>& co
             ++live;
         if (!live)
             continue;
-        hipLaunchKernelGGL(k_pgc_diag<true>, dim3(live), blk, 0, s, C, p);
+        pg_launch(ctx, e, k_pgc_diag<true>, dim3(live), blk, C, p);
         if (nt - p - 1)
-            hipLaunchKernelGGL(k_pgc_update<true>, dim3(nt - p - 1, live), blk, 0, s, C, p);
+            pg_launch(ctx, e, k_pgc_update<true>, dim3(nt - p - 1, live), blk, C, p);
     }
-    hipLaunchKernelGGL(k_pgc_scale, strided((int64_t)Q.n_s * C.ldx), blk, 0, s, C);
+    pg_launch(ctx, e, k_pgc_scale, pg_strided((int64_t)Q.n_s * C.ldx), blk, C);
     for (int p = nt - 1; p >= 0; --p) {
-        hipLaunchKernelGGL(k_pgc_diag<false>, dim3(ng), blk, 0, s, C, p);
+        pg_launch(ctx, e, k_pgc_diag<false>, dim3(ng), blk, C, p);
         if (p)
-            hipLaunchKernelGGL(k_pgc_update<false>, dim3(p, ng), blk, 0, s, C, p);
+            pg_launch(ctx, e, k_pgc_update<false>, dim3(p, ng), blk, C, p);
     }
-    hipLaunchKernelGGL(k_pgc_pairs, over(C.n_pairs), blk, 0, s, C);
-    HIP_TRY(ctx, hipGetLastError());
-    return CSM_OK;
+    pg_launch(ctx, e, k_pgc_pairs, pg_over(C.n_pairs), blk, C);
+    return launched_ok(ctx, e, "pose-graph marginals solve");
 }
 
 } /* namespace */
@@ -786,8 +781,8 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
     const PgJob& J = Q.J;
     if (!schur) {
         ScopedTimer tm(ctx, "pose_graph");
-        hipLaunchKernelGGL(k_pose_graph_lm, dim3(1), dim3(kPgBlock), 0, ctx->stream, J);
-        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = launched_ok(ctx, launch(k_pose_graph_lm, dim3(1), dim3(kPgBlock), ctx->stream, J), "pose-graph LM")))
+            return rc;
     } else {
         ScopedTimer tm(ctx, "pose_graph");
         if ((rc = pg_schur_chain(ctx, Q, small)))

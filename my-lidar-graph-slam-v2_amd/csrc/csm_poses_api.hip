@@ -23,17 +23,15 @@ constexpr long long kPoseMaxCallPoses = 1ll << 30;
 constexpr size_t kFixBatchBytes = 64u << 20;
 constexpr int    kPoseGroupsWanted = 2048;                    /* workgroups of k_pose_score a call aims at */
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 /* What both the device entry and the host restatement refuse about a set. ang_max: max |a_i|. */
 bool pose_set_ok(const csm_geometry* geom, const csm_scan* scan, const double* poses, int n_poses, double* ang_max)
 {
     if (!geom || !scan || n_poses < 0 || (n_poses > 0 && !poses) || scan->n_points < 1 ||
         scan->n_points > kPoseMaxPoints || !scan->angles || !scan->ranges)
         return false;
-    const double res = geom->resolution;
-    if (!std::isfinite(res) || !(res > 0.0) || !std::isfinite(geom->offset_x) || !std::isfinite(geom->offset_y))
+    if (!geometry_is_finite(geom))
         return false;
+    const double res = geom->resolution;
     double r_max = 0.0, a_max = 0.0;
     for (int i = 0; i < scan->n_points; ++i) {
         if (!std::isfinite(scan->angles[i]) || !std::isfinite(scan->ranges[i]))
@@ -61,30 +59,6 @@ bool update_params_ok(const csm_pose_update_params* p, int n_poses, int n_points
         return false;
     return csm_host_volume_weights(n_points, p->temperature, table, shift) == CSM_OK;
 }
-
-hipEvent_t take_event(csm_ctx* ctx)
-{
-    hipEvent_t e = nullptr;
-    if (!ctx->event_pool.empty()) {
-        e = ctx->event_pool.back();
-        ctx->event_pool.pop_back();
-    } else {
-        (void)hipEventCreate(&e);
-    }
-    return e;
-}
-
-/* The events of one call's device_us: back into the context's pool however the call ends. */
-struct CallSpan {
-    csm_ctx* ctx;
-    hipEvent_t a, b;
-    explicit CallSpan(csm_ctx* c) : ctx(c), a(take_event(c)), b(take_event(c)) {}
-    ~CallSpan()
-    {
-        if (a) ctx->event_pool.push_back(a);
-        if (b) ctx->event_pool.push_back(b);
-    }
-};
 
 /* Scores the sets; with `prm`, sets[0] is the one set of an update. */
 int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record* out, csm_pose_sets_info* info,
@@ -128,25 +102,14 @@ int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     /* the distinct scans of the call, in first-use order */
-    std::map<std::tuple<const double*, const double*, int>, long long> seen;
-    std::vector<int> first_use;
+    ScanTable scans;
     std::vector<long long> trip_at((size_t)n_sets);
-    long long beams_ll = 0;
-    for (int k = 0; k < n_sets; ++k) {
-        const csm_scan& sc = sets[k].scan;
-        const auto key = std::make_tuple(sc.angles, sc.ranges, sc.n_points);
-        const auto it = seen.find(key);
-        if (it != seen.end()) {
-            trip_at[k] = it->second;
-            continue;
-        }
-        seen[key] = trip_at[k] = beams_ll;
-        first_use.push_back(k);
-        beams_ll += sc.n_points;
-    }
-    const int nb = (int)beams_ll;            /* <= n_sets * 65536; n_sets is an int32 of sets that each hold a pose list */
-    if (beams_ll >= (1ll << 30))
-        return fail(ctx, CSM_EINVAL, "pose sets: %lld beams of distinct scans in one call (the limit is 2^30)", beams_ll);
+    for (int k = 0; k < n_sets; ++k)
+        trip_at[k] = scans.slot(sets[k].scan, k);
+    const int nb = (int)scans.beams;     /* <= n_sets * 65536; n_sets is an int32 of sets that each hold a pose list */
+    if (scans.beams >= (1ll << 30))
+        return fail(ctx, CSM_EINVAL, "pose sets: %lld beams of distinct scans in one call (the limit is 2^30)",
+                    scans.beams);
 
     /* poses per workgroup: as many as keep about kPoseGroupsWanted workgroups in flight, a multiple of the
      * wavefronts of a workgroup, 4 .. kPoseGroupMax (more poses per staged scan gained nothing: DESIGN 4k) */
@@ -154,29 +117,28 @@ int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record
     group_poses = group_poses / 4 * 4;
 
     /* upload block: [jobs][pre_group][angles][ranges][poses][table] */
-    const size_t jobs_bytes = align256((size_t)n_sets * sizeof(PoseJob));
-    const size_t pre_bytes = align256(((size_t)n_sets + 1) * 4);
-    const size_t scan_bytes = align256((size_t)nb * 8);
-    const size_t poses_bytes = align256((size_t)total * 24);
-    const size_t table_bytes = prm ? sizeof(table) : 0;
-    const size_t up_bytes = jobs_bytes + pre_bytes + 2 * scan_bytes + poses_bytes + table_bytes;
-    /* work block: [counters + list] | [records][weights][ancestors][update record] | [triples][prefix sums] */
-    const size_t unc_bytes = align256(((size_t)total + 2) * 4);
+    Carve up;
+    up.take((size_t)n_sets * sizeof(PoseJob));
+    const size_t pre_at = up.take(((size_t)n_sets + 1) * 4);
+    const size_t angles_at = up.take((size_t)nb * 8), ranges_at = up.take((size_t)nb * 8);
+    const size_t poses_at = up.take((size_t)total * 24), table_at = up.off;
+    const size_t table_bytes = prm ? sizeof(table) : 0, up_bytes = table_at + table_bytes;
+    /* work block: [counters + list] | [records][weights][ancestors][update record] | [triples][prefix sums];
+     * a piece a plain scoring call does not have is a take(0), which advances nothing */
     const size_t rec_bytes = (size_t)total * sizeof(csm_pose_record);
-    const size_t w_bytes = prm ? (size_t)total * 4 : 0;
-    const size_t anc_bytes = prm ? align256((size_t)n_out * 4) : 0;
-    const size_t upd_bytes = prm ? sizeof(csm_pose_update_info) : 0;
-    const size_t w_at = unc_bytes + align256(rec_bytes);
-    const size_t anc_at = w_at + align256(w_bytes);
-    const size_t upd_at = anc_at + anc_bytes;
-    const size_t back_bytes = upd_at + upd_bytes;
-    const size_t trips_at = align256(back_bytes);
-    const size_t prefix_at = trips_at + align256((size_t)nb * sizeof(PoseTriple));
+    const size_t w_bytes = prm ? (size_t)total * 4 : 0, upd_bytes = prm ? sizeof(csm_pose_update_info) : 0;
+    Carve wk;
+    wk.take(((size_t)total + 2) * 4);
+    const size_t records_at = wk.take(rec_bytes);
+    const size_t w_at = wk.take(w_bytes), anc_at = wk.take(prm ? (size_t)n_out * 4 : 0);
+    const size_t upd_at = wk.take(upd_bytes), back_bytes = upd_at + upd_bytes;
+    const size_t trips_at = wk.take((size_t)nb * sizeof(PoseTriple)), prefix_at = wk.off;
     const size_t work_bytes = prefix_at + (prm ? (size_t)total * 8 : 0);
-    if (int rc = grow(ctx, ctx->ps_tab, up_bytes, up_bytes + up_bytes / 4, false)) return rc;
-    if (int rc = grow(ctx, ctx->ps_work, work_bytes, work_bytes + work_bytes / 4, false)) return rc;
-    if (int rc = grow(ctx, ctx->ps_pin, up_bytes, up_bytes + up_bytes / 4, false)) return rc;
-    if (int rc = grow(ctx, ctx->ps_back, back_bytes, back_bytes + back_bytes / 4, false)) return rc;
+    int rc, e;
+    if ((rc = reserve(ctx, ctx->ps_tab, up_bytes))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_work, work_bytes))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_pin, up_bytes))) return rc;
+    if ((rc = reserve(ctx, ctx->ps_back, back_bytes))) return rc;
     char* const pin = ctx->ps_pin.as<char>();
     char* const tab = ctx->ps_tab.as<char>();
     char* const work = ctx->ps_work.as<char>();
@@ -205,11 +167,11 @@ int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record
         pre_group[k + 1] = pre_group[k] + (uint32_t)ceil_div(s.n_poses, group_poses);
     }
     std::memcpy(pin, jobs.data(), (size_t)n_sets * sizeof(PoseJob));
-    std::memcpy(pin + jobs_bytes, pre_group.data(), ((size_t)n_sets + 1) * 4);
-    double* const angles_pin = reinterpret_cast<double*>(pin + jobs_bytes + pre_bytes);
-    double* const ranges_pin = reinterpret_cast<double*>(pin + jobs_bytes + pre_bytes + scan_bytes);
-    double* const poses_pin = reinterpret_cast<double*>(pin + jobs_bytes + pre_bytes + 2 * scan_bytes);
-    for (int k : first_use) {
+    std::memcpy(pin + pre_at, pre_group.data(), ((size_t)n_sets + 1) * 4);
+    double* const angles_pin = reinterpret_cast<double*>(pin + angles_at);
+    double* const ranges_pin = reinterpret_cast<double*>(pin + ranges_at);
+    double* const poses_pin = reinterpret_cast<double*>(pin + poses_at);
+    for (int k : scans.first_use) {
         const csm_scan& sc = sets[k].scan;
         std::memcpy(angles_pin + trip_at[k], sc.angles, (size_t)sc.n_points * 8);
         std::memcpy(ranges_pin + trip_at[k], sc.ranges, (size_t)sc.n_points * 8);
@@ -218,16 +180,16 @@ int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record
         if (sets[k].n_poses)
             std::memcpy(poses_pin + 3 * (size_t)pre_pose[k], sets[k].poses, (size_t)sets[k].n_poses * 24);
     if (prm)
-        std::memcpy(pin + up_bytes - table_bytes, table, table_bytes);
+        std::memcpy(pin + table_at, table, table_bytes);
 
     PoseChunk ch;
     ch.jobs = reinterpret_cast<const PoseJob*>(tab);
-    ch.pre_group = reinterpret_cast<const uint32_t*>(tab + jobs_bytes);
-    ch.angles = reinterpret_cast<const double*>(tab + jobs_bytes + pre_bytes);
-    ch.ranges = reinterpret_cast<const double*>(tab + jobs_bytes + pre_bytes + scan_bytes);
-    ch.poses = reinterpret_cast<const double*>(tab + jobs_bytes + pre_bytes + 2 * scan_bytes);
+    ch.pre_group = reinterpret_cast<const uint32_t*>(tab + pre_at);
+    ch.angles = reinterpret_cast<const double*>(tab + angles_at);
+    ch.ranges = reinterpret_cast<const double*>(tab + ranges_at);
+    ch.poses = reinterpret_cast<const double*>(tab + poses_at);
     ch.trips = reinterpret_cast<PoseTriple*>(work + trips_at);
-    ch.records = reinterpret_cast<csm_pose_record*>(work + unc_bytes);
+    ch.records = reinterpret_cast<csm_pose_record*>(work + records_at);
     ch.unc = reinterpret_cast<uint32_t*>(work);
     ch.n_sets = n_sets;
     ch.n_beams = nb;
@@ -242,14 +204,14 @@ int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record
     HIP_TRY(ctx, hipEventRecord(span.a, ctx->stream));
     {
         ScopedTimer tm(ctx, "pose_prep");
-        hipLaunchKernelGGL(k_pose_prep, dim3((unsigned)ceil_div(nb, kPoseBlock)), dim3(kPoseBlock), 0, ctx->stream, ch);
+        e = launch(k_pose_prep, dim3((unsigned)ceil_div(nb, kPoseBlock)), dim3(kPoseBlock), ctx->stream, ch);
     }
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = launched_ok(ctx, e, "pose prep"))) return rc;
     {
         ScopedTimer tm(ctx, "pose_score");
-        hipLaunchKernelGGL(k_pose_score, dim3(pre_group[n_sets]), dim3(kPoseBlock), 0, ctx->stream, ch);
+        e = launch(k_pose_score, dim3(pre_group[n_sets]), dim3(kPoseBlock), ctx->stream, ch);
     }
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = launched_ok(ctx, e, "pose score"))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(back, work, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t n_unc = reinterpret_cast<const uint32_t*>(back)[0];
@@ -277,30 +239,32 @@ int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record
                 ints += need;
                 ++u1;
             }
+            /* fix batch: [fixes][hit indices] */
             const size_t fix_bytes = align256(fixes.size() * sizeof(PoseFix));
             const size_t batch_bytes = fix_bytes + ints * 4;
-            if (int rc = grow(ctx, ctx->ps_pin, batch_bytes, batch_bytes + batch_bytes / 4, false)) return rc;
-            if (int rc = grow(ctx, ctx->ps_fix, batch_bytes, batch_bytes + batch_bytes / 4, false)) return rc;
+            if ((rc = reserve(ctx, ctx->ps_pin, batch_bytes))) return rc;
+            if ((rc = reserve(ctx, ctx->ps_fix, batch_bytes))) return rc;
             char* const fpin = ctx->ps_pin.as<char>();
             char* const fdev = ctx->ps_fix.as<char>();
             std::memcpy(fpin, fixes.data(), fixes.size() * sizeof(PoseFix));
             int32_t* const hits = reinterpret_cast<int32_t*>(fpin + fix_bytes);
-            const auto t0 = std::chrono::steady_clock::now();
+            const double t0 = clock_us();
             for (const PoseFix& f : fixes) {
                 const csm_pose_set& s = sets[f.set];
                 const double* const pose = s.poses + 3 * (size_t)(f.pose - pre_pose[f.set]);
                 csm_host_project(&s.geometry, pose, 0.0, 0, s.scan.angles, s.scan.ranges, s.scan.n_points,
                                  hits + f.hit_at, hits + f.hit_at + s.scan.n_points, nullptr, nullptr);
             }
-            host_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+            host_us += clock_us() - t0;
             HIP_TRY(ctx, hipMemcpyAsync(fdev, fpin, batch_bytes, hipMemcpyHostToDevice, ctx->stream));
             {
                 ScopedTimer tm(ctx, "pose_rescore");
-                hipLaunchKernelGGL(k_pose_rescore, dim3((unsigned)ceil_div((int)fixes.size(), kPoseBlock / 64)),
-                                   dim3(kPoseBlock), 0, ctx->stream, ch, reinterpret_cast<const PoseFix*>(fdev),
-                                   reinterpret_cast<const int32_t*>(fdev + fix_bytes), (int)fixes.size());
+                const dim3 fix_groups((unsigned)ceil_div((int)fixes.size(), kPoseBlock / 64));
+                e = launch(k_pose_rescore, fix_groups, dim3(kPoseBlock), ctx->stream, ch,
+                           reinterpret_cast<const PoseFix*>(fdev), reinterpret_cast<const int32_t*>(fdev + fix_bytes),
+                           (int)fixes.size());
             }
-            HIP_TRY(ctx, hipGetLastError());
+            if ((rc = launched_ok(ctx, e, "pose rescore"))) return rc;
             u0 = u1;
             if (u0 < n_unc)
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     /* the next batch is staged in the same block */
@@ -309,7 +273,7 @@ int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record
     if (prm) {
         PoseUpdate pu;
         pu.records = ch.records;
-        pu.table = reinterpret_cast<const uint32_t*>(tab + up_bytes - table_bytes);
+        pu.table = reinterpret_cast<const uint32_t*>(tab + table_at);
         pu.weights = reinterpret_cast<uint32_t*>(work + w_at);
         pu.prefix = reinterpret_cast<unsigned long long*>(work + prefix_at);
         pu.ancestors = reinterpret_cast<int32_t*>(work + anc_at);
@@ -321,22 +285,21 @@ int run_sets(csm_ctx* ctx, const csm_pose_set* sets, int n_sets, csm_pose_record
         pu.offset = prm->offset;
         {
             ScopedTimer tm(ctx, "pose_weights");
-            hipLaunchKernelGGL(k_pose_weights, dim3(1), dim3(kPoseUpdateBlock), 0, ctx->stream, pu);
+            e = launch(k_pose_weights, dim3(1), dim3(kPoseUpdateBlock), ctx->stream, pu);
         }
-        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = launched_ok(ctx, e, "pose weights"))) return rc;
         if (n_out > 0) {
             ScopedTimer tm(ctx, "pose_resample");
-            hipLaunchKernelGGL(k_pose_resample, dim3((unsigned)ceil_div(n_out, kPoseBlock)), dim3(kPoseBlock), 0,
-                               ctx->stream, pu);
-            HIP_TRY(ctx, hipGetLastError());
+            e = launch(k_pose_resample, dim3((unsigned)ceil_div(n_out, kPoseBlock)), dim3(kPoseBlock), ctx->stream, pu);
+            if ((rc = launched_ok(ctx, e, "pose resample"))) return rc;
         }
     }
     HIP_TRY(ctx, hipEventRecord(span.b, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(back, work, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(back + unc_bytes, work + unc_bytes, back_bytes - unc_bytes, hipMemcpyDeviceToHost,
+    HIP_TRY(ctx, hipMemcpyAsync(back + records_at, work + records_at, back_bytes - records_at, hipMemcpyDeviceToHost,
                                 ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, back + unc_bytes, rec_bytes);
+    std::memcpy(out, back + records_at, rec_bytes);
     if (prm) {
         std::memcpy(weights, back + w_at, w_bytes);
         if (n_out)

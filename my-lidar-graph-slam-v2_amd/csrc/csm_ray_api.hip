@@ -42,9 +42,9 @@ bool ray_frame(const csm_geometry* geom, const csm_scan* scan, const double pose
 {
     if (!geom || !scan || !pose || scan->n_points < 0 || (scan->n_points > 0 && (!scan->angles || !scan->ranges)))
         return false;
-    const double res = geom->resolution;
-    if (!std::isfinite(res) || !(res > 0.0) || !std::isfinite(geom->offset_x) || !std::isfinite(geom->offset_y))
+    if (!geometry_is_finite(geom))
         return false;
+    const double res = geom->resolution;
     for (int k = 0; k < 3; ++k)
         if (!std::isfinite(pose[k]) || !std::isfinite(scan->relative_sensor_pose[k]))
             return false;
@@ -264,7 +264,7 @@ int csm_ray_check_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_q
 
     const int64_t limit = prm->scratch_limit_bytes ? prm->scratch_limit_bytes : kRayDefaultScratch;
     const uint32_t unc_cap = ray_unc_cap(ctx);
-    const size_t unc_bytes = (((size_t)unc_cap + 1) * 4 + 255) & ~(size_t)255;
+    const size_t unc_bytes = align256(((size_t)unc_cap + 1) * 4);
     const int scale = prm->subpixel_scale;
     bool host_projection = ctx->tune.map_host_projection;
     size_t words_done = 0;
@@ -282,37 +282,28 @@ int csm_ray_check_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_q
         const int nq = q1 - q0, nb = (int)beams_ll;
 
         /* the distinct scans of the chunk, in first-use order */
-        std::map<std::tuple<const double*, const double*, int>, long long> seen;
-        std::vector<int> first_use;
-        std::vector<long long> scan_at((size_t)nq);
-        long long scan_doubles = 0;
-        for (int k = 0; k < nq; ++k) {
-            const csm_scan& sc = queries[q0 + k].scan;
-            const auto key = std::make_tuple(sc.angles, sc.ranges, sc.n_points);
-            const auto it = seen.find(key);
-            if (it != seen.end()) {
-                scan_at[k] = it->second;
-                continue;
-            }
-            seen[key] = scan_at[k] = scan_doubles;
-            first_use.push_back(k);
-            scan_doubles += 2ll * sc.n_points;
-        }
+        ScanTable table;
+        std::vector<long long> scan_at((size_t)nq);     /* of [angles | ranges], in doubles */
+        for (int k = 0; k < nq; ++k)
+            scan_at[k] = 2 * table.slot(queries[q0 + k].scan, k);
 
-        /* upload block: [queries][pre_beam][pre_group][scans] */
-        const size_t tab_bytes = ((size_t)nq * sizeof(RayQuery) + 2 * ((size_t)nq + 1) * 4 + 255) & ~(size_t)255;
-        const size_t up_bytes = tab_bytes + (size_t)scan_doubles * 8;
-        /* work block: [uncertified count + list][records][words] | [ray records][patches] */
+        /* upload block: [queries][pre_beam][pre_group][scans]; the three tables are one piece */
+        const size_t tab_bytes = align256((size_t)nq * sizeof(RayQuery) + 2 * ((size_t)nq + 1) * 4);
+        const size_t up_bytes = tab_bytes + 2 * (size_t)table.beams * 8;
+        /* work block: [uncertified count + list][records][words] | [ray records][patches]; what goes back,
+         * list, records and words, is one piece */
         const size_t rec_bytes = (size_t)nq * kRayRecordBytes, word_bytes = (size_t)nb * 4;
         const size_t back_bytes = unc_bytes + rec_bytes + word_bytes;
-        const size_t recs_at = (back_bytes + 255) & ~(size_t)255;
-        const size_t patch_at = recs_at + (((size_t)nb * sizeof(RayRec) + 255) & ~(size_t)255);
+        Carve wk;
+        wk.take(back_bytes);
+        const size_t recs_at = wk.take((size_t)nb * sizeof(RayRec)), patch_at = wk.off;
         const size_t patch_bytes = std::max((size_t)unc_cap * sizeof(RayPatch), (size_t)nb * sizeof(RayRec));
         const size_t work_bytes = patch_at + (size_t)unc_cap * sizeof(RayPatch);
-        if (int rc = grow(ctx, ctx->rc_tab, up_bytes, up_bytes + up_bytes / 4, false)) return rc;
-        if (int rc = grow(ctx, ctx->rc_work, work_bytes, work_bytes + work_bytes / 4, false)) return rc;
-        if (int rc = grow(ctx, ctx->rc_pin, up_bytes + patch_bytes, up_bytes + patch_bytes + up_bytes / 4, false)) return rc;
-        if (int rc = grow(ctx, ctx->rc_back, back_bytes, back_bytes + back_bytes / 4, false)) return rc;
+        int rc, e;
+        if ((rc = reserve(ctx, ctx->rc_tab, up_bytes))) return rc;
+        if ((rc = reserve(ctx, ctx->rc_work, work_bytes))) return rc;
+        if ((rc = reserve(ctx, ctx->rc_pin, up_bytes + patch_bytes))) return rc;
+        if ((rc = reserve(ctx, ctx->rc_back, back_bytes))) return rc;
         char* const pin = ctx->rc_pin.as<char>();
         char* const tab = ctx->rc_tab.as<char>();
         char* const work = ctx->rc_work.as<char>();
@@ -347,7 +338,7 @@ int csm_ray_check_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_q
             pre_beam[k + 1] = pre_beam[k] + (uint32_t)q.scan.n_points;
             pre_group[k + 1] = pre_group[k] + (uint32_t)ceil_div(q.scan.n_points, kRayGroup);
         }
-        for (int k : first_use) {
+        for (int k : table.first_use) {
             const csm_scan& sc = queries[q0 + k].scan;
             if (sc.n_points) {
                 std::memcpy(scans + scan_at[k], sc.angles, (size_t)sc.n_points * 8);
@@ -381,9 +372,9 @@ int csm_ray_check_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_q
         if (nb > 0 && !host_projection) {
             {
                 ScopedTimer tm(ctx, "ray_project");
-                hipLaunchKernelGGL(k_ray_project, dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, ctx->stream, ch);
+                e = launch(k_ray_project, dim3((unsigned)ceil_div(nb, 256)), dim3(256), ctx->stream, ch);
             }
-            HIP_TRY(ctx, hipGetLastError());
+            if ((rc = launched_ok(ctx, e, "ray project"))) return rc;
             HIP_TRY(ctx, hipMemcpyAsync(back, work, unc_bytes, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             n_unc = reinterpret_cast<const uint32_t*>(back)[0];
@@ -425,14 +416,14 @@ int csm_ray_check_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_q
             RayPatch* const patches_dev = reinterpret_cast<RayPatch*>(work + patch_at);
             HIP_TRY(ctx, hipMemcpyAsync(patches_dev, patches, (size_t)n_unc * sizeof(RayPatch), hipMemcpyHostToDevice,
                                         ctx->stream));
-            hipLaunchKernelGGL(k_ray_patch, dim3((unsigned)ceil_div((int)n_unc, 256)), dim3(256), 0, ctx->stream,
-                               patches_dev, (int)n_unc, ch.recs);
-            HIP_TRY(ctx, hipGetLastError());
+            e = launch(k_ray_patch, dim3((unsigned)ceil_div((int)n_unc, 256)), dim3(256), ctx->stream, patches_dev,
+                       (int)n_unc, ch.recs);
+            if ((rc = launched_ok(ctx, e, "ray patch"))) return rc;
         }
         if (pre_group[nq] > 0) {
             ScopedTimer tm(ctx, "ray_walk");
-            hipLaunchKernelGGL(k_ray_walk, dim3(pre_group[nq]), dim3(256), 0, ctx->stream, ch);
-            HIP_TRY(ctx, hipGetLastError());
+            e = launch(k_ray_walk, dim3(pre_group[nq]), dim3(256), ctx->stream, ch);
+            if ((rc = launched_ok(ctx, e, "ray walk"))) return rc;
         }
         const size_t fetch = rec_bytes + (per_beam ? word_bytes : 0);
         HIP_TRY(ctx, hipMemcpyAsync(back + unc_bytes, work + unc_bytes, fetch, hipMemcpyDeviceToHost, ctx->stream));

@@ -634,7 +634,7 @@ int query_block(csm_ctx* ctx, int n_theta, int n, QueryBlock* q)
     q->hn = (size_t)n_theta * n;
     if ((rc = ensure(ctx, ctx->hits, q->hn * 8 + 256))) return rc;
     if ((rc = ensure(ctx, ctx->unc, 16 + (size_t)kUncCap * 4))) return rc;
-    q->job_bytes = (sizeof(ProjJob) + 255) & ~(size_t)255;
+    q->job_bytes = align256(sizeof(ProjJob));
     q->up_bytes = q->job_bytes + (size_t)n * 16;
     const size_t pin_bytes = q->up_bytes + 256;
     if ((rc = grow(ctx, ctx->q_pin, pin_bytes, pin_bytes + pin_bytes / 4, true))) return rc;
