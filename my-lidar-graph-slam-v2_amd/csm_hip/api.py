@@ -7,6 +7,7 @@ Mirrors the reference's matcher interface for the hot path:
   (src/my_lidar_graph_slam/mapping/loop_detector_branch_bound.cpp:59-156)
 All arithmetic happens in libcsm_hip.so; this file only marshals numpy arrays.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -1483,6 +1484,31 @@ class Group:
         return bool(used.value), us.value
 
 
+@contextlib.contextmanager
+def _query_map(ctx, nonce, map_id, grid, likelihood_sigma=None, resolution=None):
+    """The residency rule of the three matchers below, for one optimize_pose call: the map lies under
+    map_id, or under the matcher's nonce id when it is a throw-away map (map_id None, like
+    LocalMapId::Invalid in scan_matcher_correlative_fpga.cpp:177-184); grid is uploaded when the map is
+    throw-away or not resident (grid None: it is resident already, the per-LocalMapId cache of the loop
+    detectors). With a likelihood_sigma the map's field lies under its id | LIKELIHOOD_ID_BIT: the field
+    follows the map, built when the map was uploaded just now or has no field yet. Yields (map id, id
+    to search on); a throw-away map and its field are released when the call ends."""
+    mid = nonce if map_id is None else map_id
+    uploaded = grid is not None and (map_id is None or not ctx.has_grid(mid))
+    if uploaded:
+        ctx.upload_grid(mid, grid)
+    search_id = mid
+    if likelihood_sigma is not None:
+        search_id = mid | ScanMatcherCorrelativeHIP.LIKELIHOOD_ID_BIT
+        if uploaded or not ctx.has_grid(search_id):
+            ctx.build_likelihood_map(mid, search_id, likelihood_sigma, resolution)
+    yield mid, search_id
+    if map_id is None:
+        ctx.release_grid(mid)
+        if search_id != mid:
+            ctx.release_grid(search_id)
+
+
 class ScanMatcherCorrelativeHIP:
     """Drop-in for ScanMatcherCorrelative (constructor arguments as in
     src/my_lidar_graph_slam/scan_matcher_factory.cpp:173-177)."""
@@ -1515,39 +1541,24 @@ class ScanMatcherCorrelativeHIP:
         """grid may be None when map_id is already resident (the per-LocalMapId
         cache of the loop detectors); a throw-away latest map gets a nonce id,
         like LocalMapId::Invalid in scan_matcher_correlative_fpga.cpp:177-184."""
-        mid = map_id
-        if mid is None:
-            mid = self._nonce
-        uploaded = grid is not None and (map_id is None or not self.ctx.has_grid(mid))
-        if uploaded:
-            self.ctx.upload_grid(mid, grid)
-        search_id = mid
-        if self.likelihood_sigma is not None:
-            # the field follows the map: built when the map was uploaded just now or has no field yet
-            search_id = mid | self.LIKELIHOOD_ID_BIT
-            if uploaded or not self.ctx.has_grid(search_id):
-                self.ctx.build_likelihood_map(mid, search_id, self.likelihood_sigma, geom[0])
-        if self.prior_information is not None:
-            # the summary of the winner under the prior, with the unweighted winner and the penalty beside it
-            both = self.ctx.correlative_match_prior(search_id, geom, angles, ranges, rel_pose, init_pose,
-                                                    self.range_x, self.range_y, self.range_theta,
-                                                    self.low_resolution, self.prior_information,
-                                                    score_threshold, known_rate_threshold)
-            out = dict(both["summary"], unweighted=both["prior"]["unweighted"], prior=both["prior"])
-        else:
-            out = self.ctx.correlative_match(search_id, geom, angles, ranges, rel_pose, init_pose,
-                                             self.range_x, self.range_y, self.range_theta,
-                                             self.low_resolution, score_threshold,
-                                             known_rate_threshold)
-        if self.likelihood_sigma is not None:
-            q = dict(map_id=mid, geom=geom, angles=angles, ranges=ranges, rel_pose=rel_pose,
-                     init_pose=out["estimated_pose"])
-            out["cost"] = self.ctx.cost_covariance_batch([q], [out["best_sensor_pose"]], self.covariance_scale)[0]
-            out["refined"] = self.ctx.linear_solver_batch([q], covariance_scale=self.covariance_scale)[0]
-        if map_id is None:
-            self.ctx.release_grid(mid)
-            if search_id != mid:
-                self.ctx.release_grid(search_id)
+        with _query_map(self.ctx, self._nonce, map_id, grid, self.likelihood_sigma, geom[0]) as (mid, search_id):
+            if self.prior_information is not None:
+                # the summary of the winner under the prior, with the unweighted winner and the penalty beside it
+                both = self.ctx.correlative_match_prior(search_id, geom, angles, ranges, rel_pose, init_pose,
+                                                        self.range_x, self.range_y, self.range_theta,
+                                                        self.low_resolution, self.prior_information,
+                                                        score_threshold, known_rate_threshold)
+                out = dict(both["summary"], unweighted=both["prior"]["unweighted"], prior=both["prior"])
+            else:
+                out = self.ctx.correlative_match(search_id, geom, angles, ranges, rel_pose, init_pose,
+                                                 self.range_x, self.range_y, self.range_theta,
+                                                 self.low_resolution, score_threshold,
+                                                 known_rate_threshold)
+            if self.likelihood_sigma is not None:
+                q = dict(map_id=mid, geom=geom, angles=angles, ranges=ranges, rel_pose=rel_pose,
+                         init_pose=out["estimated_pose"])
+                out["cost"] = self.ctx.cost_covariance_batch([q], [out["best_sensor_pose"]], self.covariance_scale)[0]
+                out["refined"] = self.ctx.linear_solver_batch([q], covariance_scale=self.covariance_scale)[0]
         return out
 
 
@@ -1567,15 +1578,10 @@ class ScanMatcherGridSearchHIP:
 
     def optimize_pose(self, grid, geom, angles, ranges, rel_pose, init_pose,
                       map_id=None, score_threshold=0.0, known_rate_threshold=0.0):
-        mid = self._nonce if map_id is None else map_id
-        if grid is not None and (map_id is None or not self.ctx.has_grid(mid)):
-            self.ctx.upload_grid(mid, grid)
-        out = self.ctx.grid_search_match(mid, geom, angles, ranges, rel_pose, init_pose,
-                                         *self.ranges, *self.steps, score_threshold,
-                                         known_rate_threshold)
-        if map_id is None:
-            self.ctx.release_grid(mid)
-        return out
+        with _query_map(self.ctx, self._nonce, map_id, grid) as (mid, _):
+            return self.ctx.grid_search_match(mid, geom, angles, ranges, rel_pose, init_pose,
+                                              *self.ranges, *self.steps, score_threshold,
+                                              known_rate_threshold)
 
 
 class ScanMatcherHillClimbingHIP:
@@ -1592,15 +1598,11 @@ class ScanMatcherHillClimbingHIP:
     def optimize_pose(self, grid, geom, angles, ranges, rel_pose, init_pose, map_id=None):
         """ScanMatchingSummary fields plus the matcher's metrics; grid may be None when
         map_id is resident; a throw-away latest map gets a nonce id."""
-        mid = self._nonce if map_id is None else map_id
-        if grid is not None and (map_id is None or not self.ctx.has_grid(mid)):
-            self.ctx.upload_grid(mid, grid)
-        q = dict(map_id=mid, geom=geom, angles=angles, ranges=ranges, rel_pose=rel_pose, init_pose=init_pose)
         p = self.params
-        out = self.ctx.hill_climbing_batch([q], p.linear_step, p.angular_step, p.max_iterations,
-                                           p.max_refinements, p.cost)[0]
-        if map_id is None:
-            self.ctx.release_grid(mid)
+        with _query_map(self.ctx, self._nonce, map_id, grid) as (mid, _):
+            q = dict(map_id=mid, geom=geom, angles=angles, ranges=ranges, rel_pose=rel_pose, init_pose=init_pose)
+            out = self.ctx.hill_climbing_batch([q], p.linear_step, p.angular_step, p.max_iterations,
+                                               p.max_refinements, p.cost)[0]
         out["pose_found"] = 1          # OptimizePose always finds a pose
         return out
 

@@ -38,6 +38,7 @@
 #include <cstdlib>
 #include <map>
 #include <memory>
+#include <numeric>
 #include <set>
 #include <string>
 #include <vector>
@@ -52,6 +53,17 @@ namespace CsmHip {
         if (rc_ != 0) {                                                            \
             std::fprintf(stderr, "Assertion failed: %s == 0 (rc %d: %s) at %s:%d\n", \
                          #expr, rc_, csm_last_error(ctx), __FILE__, __LINE__);     \
+            std::abort();                                                          \
+        }                                                                          \
+    } while (0)
+
+/* a condition of the adapters' own: CSM_ASSERT_THAT(cond, "text" [, printf arguments of the text]) */
+#define CSM_ASSERT_THAT(cond, ...)                                                 \
+    do {                                                                           \
+        if (!(cond)) {                                                             \
+            std::fprintf(stderr, "Assertion failed: ");                            \
+            std::fprintf(stderr, __VA_ARGS__);                                     \
+            std::fprintf(stderr, " at %s:%d\n", __FILE__, __LINE__);               \
             std::abort();                                                          \
         }                                                                          \
     } while (0)
@@ -140,6 +152,68 @@ namespace detail {
 /* which revision of which map id a context holds */
 using RevisionMap = std::map<std::uint64_t, std::uint64_t>;
 
+/* The residency rule of a matcher's query map, for all matchers: the map of a query lies on the device under
+ * its own id, uploaded when the context does not hold it or holds another revision of it; a map without an id
+ * (kInvalidId: a throw-away map) is uploaded on every call under the matcher's reserved id and released when
+ * the call ends. A view without cells (mValues == nullptr) uploads nothing: the map is already resident, e.g.
+ * built by a GridMapBuilderHIP on this context. */
+class ResidentQueryMaps final {
+public:
+    /* One call's use of a query map: Id() is where its cells lie on the device. Its end is the end of the
+     * call: a throw-away map that was uploaded is released, and after it what was derived from it. */
+    class Use final {
+    public:
+        Use(csm_ctx* ctx, std::uint64_t id, bool temporary, bool release) :
+            mCtx(ctx), mId(id), mTemporary(temporary), mRelease { id, 0 }, mNumOfReleases(release ? 1 : 0) { }
+        Use(Use&& other) : Use(static_cast<const Use&>(other)) { other.mNumOfReleases = 0; }
+        Use& operator=(const Use&) = delete;
+        ~Use()
+        {
+            for (int i = 0; i < this->mNumOfReleases; ++i)
+                CSM_ASSERT_OK(this->mCtx, csm_release_grid(this->mCtx, this->mRelease[i]));
+        }
+
+        std::uint64_t Id() const { return this->mId; }
+        bool Temporary() const { return this->mTemporary; }
+        /* derivedId holds a map made from this one (a likelihood field): it goes when this one goes */
+        void ReleaseWithIt(std::uint64_t derivedId)
+        {
+            if (this->mNumOfReleases == 1)
+                this->mRelease[this->mNumOfReleases++] = derivedId;
+        }
+
+    private:
+        Use(const Use&) = default;          /* for the move alone, which takes the releases with it */
+        csm_ctx* mCtx;
+        std::uint64_t mId;
+        bool mTemporary;
+        std::uint64_t mRelease[2];
+        int mNumOfReleases;
+    };
+
+    /* throwAwayId: GridMapView::kReservedIds + 0 / 1 / 2, one per matcher class */
+    ResidentQueryMaps(csm_ctx* ctx, std::uint64_t throwAwayId) : mCtx(ctx), mThrowAwayId(throwAwayId) { }
+
+    Use Acquire(const GridMapView& g)
+    {
+        const bool temporary = g.mId == GridMapView::kInvalidId;
+        CSM_ASSERT_THAT(temporary || g.mId < GridMapView::kReservedIds, "map id below 2^62");
+        const std::uint64_t id = temporary ? this->mThrowAwayId : g.mId;
+        auto held = this->mRevisions.find(id);
+        if (g.mValues && (temporary || !csm_has_grid(this->mCtx, id) || held == this->mRevisions.end() ||
+                          held->second != g.mRevision)) {
+            CSM_ASSERT_OK(this->mCtx, csm_upload_grid(this->mCtx, id, g.mValues, g.mRows, g.mCols));
+            this->mRevisions[id] = g.mRevision;
+        }
+        return Use(this->mCtx, id, temporary, temporary && g.mValues != nullptr);
+    }
+
+private:
+    csm_ctx* mCtx;
+    const std::uint64_t mThrowAwayId;
+    RevisionMap mRevisions;
+};
+
 struct CtxDeleter {
     void operator()(csm_ctx* c) const { if (c) csm_destroy(c); }
 };
@@ -154,6 +228,18 @@ inline CtxPtr MakeContext(int deviceId)
         return CtxPtr();
     return CtxPtr(raw);
 }
+
+/* a context of the adapter's own, or one that another adapter owns (and keeps alive) */
+class ContextRef final {
+public:
+    explicit ContextRef(CtxPtr owned) : mOwned(std::move(owned)) { }
+    explicit ContextRef(csm_ctx* shared) : mShared(shared) { }
+    csm_ctx* Get() const { return this->mOwned ? this->mOwned.get() : this->mShared; }
+
+private:
+    CtxPtr mOwned;
+    csm_ctx* mShared = nullptr;
+};
 
 inline csm_scan ToScan(const ScanDataView& s)
 {
@@ -179,6 +265,69 @@ inline csm_scan_node ToScanNode(const ScanNodeView& n)
     return out;
 }
 
+inline std::vector<csm_scan_node> ToScanNodes(const ScanNodeView* nodes, std::size_t numOfNodes)
+{
+    std::vector<csm_scan_node> flat(numOfNodes);
+    for (std::size_t i = 0; i < numOfNodes; ++i)
+        flat[i] = ToScanNode(nodes[i]);
+    return flat;
+}
+
+/* geometry + id of a map whose cells live on the device */
+inline GridMapView ToView(const csm_map_shape& shape, std::uint64_t id)
+{
+    GridMapView view;
+    view.mRows = shape.rows;
+    view.mCols = shape.cols;
+    view.mResolution = shape.resolution;
+    view.mPosOffsetX = shape.offset_x;
+    view.mPosOffsetY = shape.offset_y;
+    view.mId = id;
+    return view;
+}
+
+/* the scan of `scan` against the map that lies under `id` on the device with g's geometry, at the map-local
+ * robot pose `pose`, as the batch entries, the cost entries and the ray check take it */
+inline csm_loop_query ToLoopQuery(std::uint64_t id, const GridMapView& g, const ScanDataView& scan,
+                                  const RobotPose2D<double>& pose)
+{
+    csm_loop_query f {};
+    f.map_id = id;
+    f.geometry = { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
+    f.scan = ToScan(scan);
+    f.initial_pose[0] = pose.mX;
+    f.initial_pose[1] = pose.mY;
+    f.initial_pose[2] = pose.mTheta;
+    return f;
+}
+
+inline csm_pose_set ToPoseSet(std::uint64_t mapId, const csm_geometry& geometry, const ScanDataView& scan,
+                              const std::vector<RobotPose2D<double>>& mapLocalSensorPoses)
+{
+    /* RobotPose2D<double> is three contiguous doubles: the vector is the flat pose array */
+    static_assert(sizeof(RobotPose2D<double>) == 3 * sizeof(double), "pose layout");
+    csm_pose_set set {};
+    set.map_id = mapId;
+    set.geometry = geometry;
+    set.scan = ToScan(scan);
+    set.poses = mapLocalSensorPoses.empty() ? nullptr : &mapLocalSensorPoses.front().mX;
+    set.n_poses = static_cast<std::int32_t>(mapLocalSensorPoses.size());
+    return set;
+}
+
+inline csm_correlative_params CorrelativeParams(double rangeX, double rangeY, double rangeTheta, int lowResolution,
+                                                double normalizedScoreThreshold, double knownRateThreshold)
+{
+    csm_correlative_params prm {};
+    prm.range_x = rangeX;
+    prm.range_y = rangeY;
+    prm.range_theta = rangeTheta;
+    prm.low_resolution = lowResolution;
+    prm.score_threshold = normalizedScoreThreshold;
+    prm.known_rate_threshold = knownRateThreshold;
+    return prm;
+}
+
 inline void FillSummary(const csm_summary& s, const RobotPose2D<double>& initial,
                         ScanMatchingSummary* out)
 {
@@ -198,18 +347,24 @@ inline void FillSummary(const csm_summary& s, const RobotPose2D<double>& initial
     out->mNumOfCandidates = s.candidates;
     out->mFlags = s.raw.flags;
 }
+/* CostSquareError::Cost / n and ComputeCovariance at the best sensor pose on the device
+ * (scan_matcher_correlative.cpp:209-219) */
+inline void DeviceSquareErrorCost(csm_ctx* ctx, const csm_loop_query& query, const double bestSensorPose[3],
+                                  double covarianceScale, ScanMatchingSummary* out)
+{
+    csm_refine_result r {};
+    CSM_ASSERT_OK(ctx, csm_cost_covariance_batch(ctx, &query, 1, bestSensorPose, covarianceScale, &r));
+    out->mNormalizedCost = r.normalized_cost;
+    for (int c = 0; c < 9; ++c)
+        out->mEstimatedCovariance[c] = r.covariance[c];
+}
 /* CostGreedyEndpoint::Cost / n and ComputeCovariance at the best sensor pose on the device
  * (scan_matcher_correlative.cpp:209-219 with a "GreedyEndpoint" cost) */
-inline void DeviceGreedyCost(csm_ctx* ctx, std::uint64_t id, const csm_geometry& geom, const csm_scan& scan,
-                             const double bestSensorPose[3], const csm_greedy_params& prm,
-                             ScanMatchingSummary* out)
+inline void DeviceGreedyCost(csm_ctx* ctx, const csm_loop_query& query, const double bestSensorPose[3],
+                             const csm_greedy_params& prm, ScanMatchingSummary* out)
 {
-    csm_loop_query cq {};
-    cq.map_id = id;
-    cq.geometry = geom;
-    cq.scan = scan;
     csm_hill_climbing_result r {};
-    CSM_ASSERT_OK(ctx, csm_greedy_cost_covariance_batch(ctx, &cq, 1, bestSensorPose, &prm, &r));
+    CSM_ASSERT_OK(ctx, csm_greedy_cost_covariance_batch(ctx, &query, 1, bestSensorPose, &prm, &r));
     out->mNormalizedCost = r.normalized_cost;
     for (int c = 0; c < 9; ++c)
         out->mEstimatedCovariance[c] = r.covariance[c];
@@ -283,52 +438,31 @@ public:
                                      const double knownRateThreshold)
     {
         csm_ctx* ctx = this->mCtx.get();
-        const GridMapView& g = q.mGridMap;
-        const bool temporary = g.mId == GridMapView::kInvalidId;
-        const std::uint64_t id = this->MakeResident(g);
+        Search w = this->Prepare(q, normalizedScoreThreshold, knownRateThreshold);
+        const csm_loop_query& f = w.mQuery;
         /* the search runs on the likelihood field when one is asked for; cost, covariance and any
-         * refinement below stay on the occupancy map `id`, which they are bilinear in */
-        const std::uint64_t searchId = this->mLikelihoodSigma > 0.0 ? this->MakeField(g, id) : id;
-        csm_geometry geom { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
-        const csm_scan scan = detail::ToScan(q.mScanData);
-        const csm_correlative_params prm = this->Params(normalizedScoreThreshold, knownRateThreshold);
-        const double init[3] = { q.mMapLocalInitialPose.mX, q.mMapLocalInitialPose.mY,
-                                 q.mMapLocalInitialPose.mTheta };
+         * refinement below stay on the occupancy map f.map_id, which they are bilinear in */
+        const std::uint64_t searchId = this->mLikelihoodSigma > 0.0 ? this->MakeField(q.mGridMap, w.mMap) : f.map_id;
         csm_summary s {};
         if (this->mUsePrior) {
             /* the winner under the motion prior; the unweighted one stays in LastPriorResult() */
             csm_prior_summary v {};
-            CSM_ASSERT_OK(ctx, csm_correlative_match_prior(ctx, searchId, &geom, &scan, init, &prm, &this->mPrior, &v));
+            CSM_ASSERT_OK(ctx, csm_correlative_match_prior(ctx, searchId, &f.geometry, &f.scan, f.initial_pose,
+                                                           &w.mParams, &this->mPrior, &v));
             s = v.summary;
             this->mLastPrior = v.prior;
         } else {
-            CSM_ASSERT_OK(ctx, csm_correlative_match(ctx, searchId, &geom, &scan, init, &prm, &s));
+            CSM_ASSERT_OK(ctx, csm_correlative_match(ctx, searchId, &f.geometry, &f.scan, f.initial_pose, &w.mParams,
+                                                     &s));
         }
         ScanMatchingSummary out;
         detail::FillSummary(s, q.mMapLocalInitialPose, &out);
-        if (this->mCostFunc) {
+        if (this->mCostFunc)
             this->mCostFunc(q, out.mBestSensorPose, &out.mNormalizedCost, out.mEstimatedCovariance);
-        } else if (this->mDeviceCovarianceScale > 0.0) {
-            /* CostSquareError::Cost / ComputeCovariance at the best sensor pose on the device
-             * (scan_matcher_correlative.cpp:209-219) */
-            csm_loop_query cq {};
-            cq.map_id = id;
-            cq.geometry = geom;
-            cq.scan = scan;
-            csm_refine_result rr {};
-            CSM_ASSERT_OK(ctx, csm_cost_covariance_batch(ctx, &cq, 1, s.best_sensor_pose,
-                                                         this->mDeviceCovarianceScale, &rr));
-            out.mNormalizedCost = rr.normalized_cost;
-            for (int c = 0; c < 9; ++c)
-                out.mEstimatedCovariance[c] = rr.covariance[c];
-        } else if (this->mUseDeviceGreedy) {
-            detail::DeviceGreedyCost(ctx, id, geom, scan, s.best_sensor_pose, this->mGreedy, &out);
-        }
-        if (temporary && g.mValues) {
-            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
-            if (searchId != id)
-                CSM_ASSERT_OK(ctx, csm_release_grid(ctx, searchId));
-        }
+        else if (this->mDeviceCovarianceScale > 0.0)
+            detail::DeviceSquareErrorCost(ctx, f, s.best_sensor_pose, this->mDeviceCovarianceScale, &out);
+        else if (this->mUseDeviceGreedy)
+            detail::DeviceGreedyCost(ctx, f, s.best_sensor_pose, this->mGreedy, &out);
         return out;
     }
 
@@ -342,22 +476,16 @@ public:
                                                        const double knownRateThreshold = 0.0)
     {
         csm_ctx* ctx = this->mCtx.get();
-        const GridMapView& g = q.mGridMap;
-        const std::uint64_t id = this->MakeResident(g);
-        csm_geometry geom { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
-        const csm_scan scan = detail::ToScan(q.mScanData);
-        const csm_correlative_params prm = this->Params(normalizedScoreThreshold, knownRateThreshold);
-        const double init[3] = { q.mMapLocalInitialPose.mX, q.mMapLocalInitialPose.mY,
-                                 q.mMapLocalInitialPose.mTheta };
+        const Search w = this->Prepare(q, normalizedScoreThreshold, knownRateThreshold);
+        const csm_loop_query& f = w.mQuery;
         const csm_peaks_params peaks { numOfPeaks, exclX, exclY, exclTheta, 0 };
         csm_summary s[CSM_PEAKS_MAX] {};
         std::int32_t n = 0;
-        CSM_ASSERT_OK(ctx, csm_correlative_peaks(ctx, id, &geom, &scan, init, &prm, &peaks, s, &n));
+        CSM_ASSERT_OK(ctx, csm_correlative_peaks(ctx, f.map_id, &f.geometry, &f.scan, f.initial_pose, &w.mParams,
+                                                 &peaks, s, &n));
         std::vector<ScanMatchingSummary> out(static_cast<std::size_t>(n));
         for (std::int32_t j = 0; j < n; ++j)
             detail::FillSummary(s[j], q.mMapLocalInitialPose, &out[j]);
-        if (g.mId == GridMapView::kInvalidId && g.mValues)
-            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
         return out;
     }
 
@@ -373,24 +501,18 @@ public:
                                                      const double knownRateThreshold = 0.0)
     {
         csm_ctx* ctx = this->mCtx.get();
-        const GridMapView& g = q.mGridMap;
-        const std::uint64_t id = this->MakeResident(g);
-        csm_geometry geom { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
-        const csm_scan scan = detail::ToScan(q.mScanData);
-        const csm_correlative_params prm = this->Params(normalizedScoreThreshold, knownRateThreshold);
-        const double init[3] = { q.mMapLocalInitialPose.mX, q.mMapLocalInitialPose.mY,
-                                 q.mMapLocalInitialPose.mTheta };
+        const Search w = this->Prepare(q, normalizedScoreThreshold, knownRateThreshold);
+        const csm_loop_query& f = w.mQuery;
         const csm_volume_params volume { temperature, 0 };
         csm_volume_summary v {};
-        CSM_ASSERT_OK(ctx, csm_correlative_covariance(ctx, id, &geom, &scan, init, &prm, &volume, &v));
+        CSM_ASSERT_OK(ctx, csm_correlative_covariance(ctx, f.map_id, &f.geometry, &f.scan, f.initial_pose, &w.mParams,
+                                                      &volume, &v));
         ScanMatchingSummary out;
         detail::FillSummary(v.summary, q.mMapLocalInitialPose, &out);
         for (int c = 0; c < 9; ++c)
             out.mEstimatedCovariance[c] = v.covariance[c];
         if (borderSupport)
             *borderSupport = v.moments.border_support;
-        if (g.mId == GridMapView::kInvalidId && g.mValues)
-            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
         return out;
     }
 
@@ -439,45 +561,37 @@ private:
                               double rangeY, double rangeTheta, CostCallback costFunc,
                               detail::CtxPtr ctx) :
         mName(name), mLowResolution(lowResolution), mRangeX(rangeX), mRangeY(rangeY),
-        mRangeTheta(rangeTheta), mCostFunc(costFunc), mCtx(std::move(ctx)) { }
+        mRangeTheta(rangeTheta), mCostFunc(costFunc), mCtx(std::move(ctx)),
+        mMaps(mCtx.get(), GridMapView::kReservedIds) { }
 
-    /* The query's map under its id on the device (uploaded when new or revised; a map without an id
-     * under a reserved one, released by the caller after the search). */
-    std::uint64_t MakeResident(const GridMapView& g)
+    /* what the OptimizePose* entries share ahead of their search call: the query's map on the device for the
+     * length of the call, the query as the C entries take it (on that map) and the search settings */
+    struct Search {
+        detail::ResidentQueryMaps::Use mMap;
+        csm_loop_query mQuery;
+        csm_correlative_params mParams;
+    };
+    Search Prepare(const ScanMatchingQuery& q, double normalizedScoreThreshold, double knownRateThreshold)
     {
-        csm_ctx* ctx = this->mCtx.get();
-        const bool temporary = g.mId == GridMapView::kInvalidId;
-        if (!temporary && g.mId >= GridMapView::kReservedIds) {
-            std::fprintf(stderr, "Assertion failed: map id below 2^62 at %s:%d\n", __FILE__, __LINE__);
-            std::abort();
-        }
-        const std::uint64_t id = temporary ? GridMapView::kReservedIds : g.mId;
-        auto held = this->mRevisions.find(id);
-        /* mValues == nullptr: the map is already resident (built by a GridMapBuilderHIP on this context) */
-        if (g.mValues && (temporary || !csm_has_grid(ctx, id) || held == this->mRevisions.end() ||
-                          held->second != g.mRevision)) {
-            CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, id, g.mValues, g.mRows, g.mCols));
-            this->mRevisions[id] = g.mRevision;
-        }
-        return id;
+        detail::ResidentQueryMaps::Use map = this->mMaps.Acquire(q.mGridMap);
+        const csm_loop_query f = detail::ToLoopQuery(map.Id(), q.mGridMap, q.mScanData, q.mMapLocalInitialPose);
+        return Search { std::move(map), f,
+                        detail::CorrelativeParams(this->mRangeX, this->mRangeY, this->mRangeTheta, this->mLowResolution,
+                                                  normalizedScoreThreshold, knownRateThreshold) };
     }
 
-    /* The likelihood field of the resident map `id` under id | kLikelihoodIdBit: built when there is none
-     * or when it was built from another revision of the map (a throw-away map: always). */
-    std::uint64_t MakeField(const GridMapView& g, std::uint64_t id)
+    /* The likelihood field of the resident map under its id | kLikelihoodIdBit: built when there is none
+     * or when it was built from another revision of the map (a throw-away map: always, and released with it). */
+    std::uint64_t MakeField(const GridMapView& g, detail::ResidentQueryMaps::Use& map)
     {
         csm_ctx* ctx = this->mCtx.get();
+        const std::uint64_t id = map.Id();
         const std::uint64_t fieldId = id | GridMapView::kLikelihoodIdBit;
-        const bool temporary = g.mId == GridMapView::kInvalidId;
         auto held = this->mFieldRevisions.find(id);
-        if (temporary || !csm_has_grid(ctx, fieldId) || held == this->mFieldRevisions.end() ||
+        if (map.Temporary() || !csm_has_grid(ctx, fieldId) || held == this->mFieldRevisions.end() ||
             held->second != g.mRevision) {
             const int radius = csm_host_likelihood_radius(this->mLikelihoodSigma, g.mResolution);
-            if (radius < 1) {
-                std::fprintf(stderr, "Assertion failed: likelihood sigma and map resolution > 0 at %s:%d\n",
-                             __FILE__, __LINE__);
-                std::abort();
-            }
+            CSM_ASSERT_THAT(radius >= 1, "likelihood sigma and map resolution > 0");
             std::vector<std::uint32_t> table(static_cast<std::size_t>(radius * radius + 1));
             CSM_ASSERT_OK(ctx, csm_host_likelihood_kernel(this->mLikelihoodSigma, g.mResolution, radius, table.data()));
             csm_likelihood_params lp {};
@@ -488,19 +602,8 @@ private:
             CSM_ASSERT_OK(ctx, csm_build_likelihood_map(ctx, id, fieldId, &lp));
             this->mFieldRevisions[id] = g.mRevision;
         }
+        map.ReleaseWithIt(fieldId);
         return fieldId;
-    }
-
-    csm_correlative_params Params(double normalizedScoreThreshold, double knownRateThreshold) const
-    {
-        csm_correlative_params prm {};
-        prm.range_x = this->mRangeX;
-        prm.range_y = this->mRangeY;
-        prm.range_theta = this->mRangeTheta;
-        prm.low_resolution = this->mLowResolution;
-        prm.score_threshold = normalizedScoreThreshold;
-        prm.known_rate_threshold = knownRateThreshold;
-        return prm;
     }
 
     const std::string mName;
@@ -508,7 +611,7 @@ private:
     const double mRangeX, mRangeY, mRangeTheta;
     const CostCallback mCostFunc;
     detail::CtxPtr mCtx;
-    detail::RevisionMap mRevisions;
+    detail::ResidentQueryMaps mMaps;
     double mDeviceCovarianceScale = 0.0;
     bool mUseDeviceGreedy = false;
     csm_greedy_params mGreedy {};
@@ -556,36 +659,19 @@ public:
                                      const double knownRateThreshold)
     {
         csm_ctx* ctx = this->mCtx.get();
-        const GridMapView& g = q.mGridMap;
-        const bool temporary = g.mId == GridMapView::kInvalidId;
-        if (!temporary && g.mId >= GridMapView::kReservedIds) {
-            std::fprintf(stderr, "Assertion failed: map id below 2^62 at %s:%d\n", __FILE__, __LINE__);
-            std::abort();
-        }
-        const std::uint64_t id = temporary ? GridMapView::kReservedIds + 1 : g.mId;
-        auto held = this->mRevisions.find(id);
-        if (g.mValues && (temporary || !csm_has_grid(ctx, id) || held == this->mRevisions.end() ||
-                          held->second != g.mRevision)) {
-            CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, id, g.mValues, g.mRows, g.mCols));
-            this->mRevisions[id] = g.mRevision;
-        }
-        csm_geometry geom { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
-        const csm_scan scan = detail::ToScan(q.mScanData);
+        const detail::ResidentQueryMaps::Use map = this->mMaps.Acquire(q.mGridMap);
+        const csm_loop_query f = detail::ToLoopQuery(map.Id(), q.mGridMap, q.mScanData, q.mMapLocalInitialPose);
         const csm_grid_search_params prm { this->mRangeX, this->mRangeY, this->mRangeTheta,
                                            this->mStepX, this->mStepY, this->mStepTheta,
                                            normalizedScoreThreshold, knownRateThreshold };
-        const double init[3] = { q.mMapLocalInitialPose.mX, q.mMapLocalInitialPose.mY,
-                                 q.mMapLocalInitialPose.mTheta };
         csm_summary s {};
-        CSM_ASSERT_OK(ctx, csm_grid_search_match(ctx, id, &geom, &scan, init, &prm, &s));
+        CSM_ASSERT_OK(ctx, csm_grid_search_match(ctx, f.map_id, &f.geometry, &f.scan, f.initial_pose, &prm, &s));
         ScanMatchingSummary out;
         detail::FillSummary(s, q.mMapLocalInitialPose, &out);
-        if (!this->mCostFunc && this->mUseDeviceGreedy)
-            detail::DeviceGreedyCost(ctx, id, geom, scan, s.best_sensor_pose, this->mGreedy, &out);
-        if (temporary)
-            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
         if (this->mCostFunc)
             this->mCostFunc(q, out.mBestSensorPose, &out.mNormalizedCost, out.mEstimatedCovariance);
+        else if (this->mUseDeviceGreedy)
+            detail::DeviceGreedyCost(ctx, f, s.best_sensor_pose, this->mGreedy, &out);
         return out;
     }
 
@@ -602,14 +688,15 @@ private:
                              double rangeTheta, double stepX, double stepY, double stepTheta,
                              CostCallback costFunc, detail::CtxPtr ctx) :
         mName(name), mRangeX(rangeX), mRangeY(rangeY), mRangeTheta(rangeTheta), mStepX(stepX),
-        mStepY(stepY), mStepTheta(stepTheta), mCostFunc(costFunc), mCtx(std::move(ctx)) { }
+        mStepY(stepY), mStepTheta(stepTheta), mCostFunc(costFunc), mCtx(std::move(ctx)),
+        mMaps(mCtx.get(), GridMapView::kReservedIds + 1) { }
 
     const std::string mName;
     const double mRangeX, mRangeY, mRangeTheta;
     const double mStepX, mStepY, mStepTheta;
     const CostCallback mCostFunc;
     detail::CtxPtr mCtx;
-    detail::RevisionMap mRevisions;
+    detail::ResidentQueryMaps mMaps;
     bool mUseDeviceGreedy = false;
     csm_greedy_params mGreedy {};
 };
@@ -650,29 +737,9 @@ public:
     ScanMatchingSummary OptimizePose(const ScanMatchingQuery& q)
     {
         csm_ctx* ctx = this->mCtx.get();
-        const GridMapView& g = q.mGridMap;
-        const bool temporary = g.mId == GridMapView::kInvalidId;
-        if (!temporary && g.mId >= GridMapView::kReservedIds) {
-            std::fprintf(stderr, "Assertion failed: map id below 2^62 at %s:%d\n", __FILE__, __LINE__);
-            std::abort();
-        }
-        const std::uint64_t id = temporary ? GridMapView::kReservedIds + 2 : g.mId;
-        auto held = this->mRevisions.find(id);
-        if (g.mValues && (temporary || !csm_has_grid(ctx, id) || held == this->mRevisions.end() ||
-                          held->second != g.mRevision)) {
-            CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, id, g.mValues, g.mRows, g.mCols));
-            this->mRevisions[id] = g.mRevision;
-        }
-        csm_loop_query cq {};
-        cq.map_id = id;
-        cq.geometry = { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
-        cq.scan = detail::ToScan(q.mScanData);
-        cq.initial_pose[0] = q.mMapLocalInitialPose.mX;
-        cq.initial_pose[1] = q.mMapLocalInitialPose.mY;
-        cq.initial_pose[2] = q.mMapLocalInitialPose.mTheta;
-        CSM_ASSERT_OK(ctx, csm_hill_climbing_batch(ctx, &cq, 1, &this->mParams, &this->mLast));
-        if (temporary && g.mValues)
-            CSM_ASSERT_OK(ctx, csm_release_grid(ctx, id));
+        const detail::ResidentQueryMaps::Use map = this->mMaps.Acquire(q.mGridMap);
+        const csm_loop_query f = detail::ToLoopQuery(map.Id(), q.mGridMap, q.mScanData, q.mMapLocalInitialPose);
+        CSM_ASSERT_OK(ctx, csm_hill_climbing_batch(ctx, &f, 1, &this->mParams, &this->mLast));
         const csm_hill_climbing_result& r = this->mLast;
         ScanMatchingSummary out;
         out.mPoseFound = true;      /* scan_matcher_hill_climbing.cpp:176-179 */
@@ -689,12 +756,12 @@ public:
 private:
     ScanMatcherHillClimbingHIP(const std::string& name, const csm_hill_climbing_params& prm,
                                detail::CtxPtr ctx) :
-        mName(name), mParams(prm), mCtx(std::move(ctx)) { }
+        mName(name), mParams(prm), mCtx(std::move(ctx)), mMaps(mCtx.get(), GridMapView::kReservedIds + 2) { }
 
     const std::string mName;
     const csm_hill_climbing_params mParams;
     detail::CtxPtr mCtx;
-    detail::RevisionMap mRevisions;
+    detail::ResidentQueryMaps mMaps;
     csm_hill_climbing_result mLast {};
 };
 
@@ -775,6 +842,87 @@ struct CheckedLoopDetections {
     std::vector<char> mKept;
 };
 
+namespace detail {
+/* A reference local map is uploaded once per id and context (mPrecompMaps, loop_detector_branch_bound.hpp:98):
+ * a loop detector only sees finished local maps, which have an id and never change
+ * (Assert(localMap.mFinished), loop_detector_branch_bound.cpp:77) */
+inline void UploadOnce(csm_ctx* ctx, const GridMapView& g)
+{
+    CSM_ASSERT_THAT(g.mId != GridMapView::kInvalidId, "reference local map without an id");
+    if (!csm_has_grid(ctx, g.mId))
+        CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, g.mId, g.mValues, g.mRows, g.mCols));
+}
+
+/* query q at the map-local robot pose `pose` */
+inline csm_loop_query ToLoopQuery(const LoopDetectionQuery& q, const RobotPose2D<double>& pose)
+{
+    return ToLoopQuery(q.mReferenceLocalMap.mId, q.mReferenceLocalMap, q.mQueryScanData, pose);
+}
+
+/* query q at its initial pose, InverseCompound(localMapNode.mGlobalPose, scanNode.mGlobalPose) */
+inline csm_loop_query ToLoopQuery(const LoopDetectionQuery& q)
+{
+    csm_loop_query f = ToLoopQuery(q, RobotPose2D<double> { 0.0, 0.0, 0.0 });
+    const double start[3] = { q.mReferenceLocalMapNodeGlobalPose.mX, q.mReferenceLocalMapNodeGlobalPose.mY,
+                              q.mReferenceLocalMapNodeGlobalPose.mTheta };
+    const double end[3] = { q.mQueryScanNodeGlobalPose.mX, q.mQueryScanNodeGlobalPose.mY,
+                            q.mQueryScanNodeGlobalPose.mTheta };
+    csm_host_inverse_compound(start, end, f.initial_pose);
+    return f;
+}
+
+inline LoopDetectionResult ToResult(const LoopDetectionQuery& q, const csm_summary& s)
+{
+    return LoopDetectionResult { { s.estimated_pose[0], s.estimated_pose[1], s.estimated_pose[2] },
+                                 q.mReferenceLocalMapNodeGlobalPose, q.mReferenceLocalMap.mId,
+                                 q.mQueryScanNodeId, s.raw.score, s.raw.flags };
+}
+
+/* the candidates of a DetectFound(): candidate j belongs to query found[j] and is its only peak */
+inline void SetCandidates(LoopDetectionResultVector candidates, const std::vector<std::size_t>& found,
+                          CheckedLoopDetections& checked)
+{
+    checked.mCandidates = std::move(candidates);
+    for (std::size_t i : found) {
+        checked.mQueryIndex.push_back(static_cast<int>(i));
+        checked.mPeakIndex.push_back(0);
+    }
+}
+
+/* the map-local robot poses at which the candidates are checked */
+inline std::vector<RobotPose2D<double>> CandidatePoses(const CheckedLoopDetections& checked)
+{
+    std::vector<RobotPose2D<double>> poses;
+    for (const LoopDetectionResult& r : checked.mCandidates)
+        poses.push_back(r.mRelativePose);
+    return poses;
+}
+
+/* mKept[j] = settings.Passes(mCandidateRecords[j]) */
+inline void MarkKept(const RayCheckSettings& settings, CheckedLoopDetections& checked)
+{
+    checked.mKept.clear();
+    for (const csm_ray_check_result& r : checked.mCandidateRecords)
+        checked.mKept.push_back(settings.Passes(r) ? 1 : 0);
+}
+
+/* mResults / mRecords = the kept candidates. firstPerQuery: of a query's candidates (its peaks, best first)
+ * only the first kept one stays kept; the mark of every later one is taken back. */
+inline void CollectKept(CheckedLoopDetections& checked, bool firstPerQuery)
+{
+    int taken = -1;                     /* the last query that has its peak */
+    for (std::size_t j = 0; j < checked.mCandidates.size(); ++j) {
+        if (checked.mKept[j] && !(firstPerQuery && checked.mQueryIndex[j] == taken)) {
+            taken = checked.mQueryIndex[j];
+            checked.mResults.push_back(checked.mCandidates[j]);
+            checked.mRecords.push_back(checked.mCandidateRecords[j]);
+        } else {
+            checked.mKept[j] = 0;
+        }
+    }
+}
+} /* namespace detail */
+
 class LoopDetectorBranchBoundHIP final {
 public:
     /* scoreThreshold / knownRateThreshold as LoopDetectorBranchBound
@@ -842,32 +990,10 @@ public:
                                                 const std::vector<RobotPose2D<double>>& poses,
                                                 const RayCheckSettings& settings)
     {
-        std::vector<csm_ray_check_result> records(queries.size());
-        if (queries.empty())
-            return records;
-        if (poses.size() != queries.size()) {
-            std::fprintf(stderr, "Assertion failed: one pose per query at %s:%d\n", __FILE__, __LINE__);
-            std::abort();
-        }
-        const std::int32_t n = static_cast<std::int32_t>(queries.size());
-        const std::int32_t members = csm_group_size(this->mGroup);
-        for (std::int32_t k = 0; k < members; ++k) {
-            std::int32_t lo = 0, hi = 0;
-            csm_shard_bounds(n, k, members, &lo, &hi);
-            if (lo == hi)
-                continue;
-            csm_ctx* ctx = csm_group_member(this->mGroup, k);
-            std::vector<csm_loop_query> flat(static_cast<std::size_t>(hi - lo));
-            for (std::int32_t i = lo; i < hi; ++i) {
-                const GridMapView& g = queries[i].mReferenceLocalMap;
-                if (!csm_has_grid(ctx, g.mId))
-                    CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, g.mId, g.mValues, g.mRows, g.mCols));
-                flat[static_cast<std::size_t>(i - lo)] = CheckQuery(queries[i], poses[i]);
-            }
-            CSM_ASSERT_OK(ctx, csm_ray_check_batch(ctx, flat.data(), hi - lo, &settings.mParams, records.data() + lo,
-                                                   nullptr));
-        }
-        return records;
+        CSM_ASSERT_THAT(queries.empty() || poses.size() == queries.size(), "one pose per query");
+        std::vector<int> all(queries.size());
+        std::iota(all.begin(), all.end(), 0);
+        return this->CheckAt(queries, all, poses, settings);
     }
 
     /* Detect(), then one free-space check per member over the found queries at their result poses: a result
@@ -876,59 +1002,54 @@ public:
     {
         CheckedLoopDetections checked;
         std::vector<std::size_t> found;
-        checked.mCandidates = this->DetectFound(queries, &found);
-        /* the check runs where Detect() ran (each member holds the maps of its own block): the members'
-         * blocks are those of the whole query vector */
-        const std::int32_t n = static_cast<std::int32_t>(queries.size());
-        const std::int32_t members = csm_group_size(this->mGroup);
-        checked.mCandidateRecords.resize(found.size());
-        for (std::int32_t k = 0; k < members; ++k) {
-            std::int32_t lo = 0, hi = 0;
-            csm_shard_bounds(n, k, members, &lo, &hi);
-            std::vector<csm_loop_query> flat;
-            std::vector<std::size_t> at;
-            for (std::size_t j = 0; j < found.size(); ++j) {
-                const std::int32_t i = static_cast<std::int32_t>(found[j]);
-                if (i < lo || i >= hi)
-                    continue;
-                flat.push_back(CheckQuery(queries[found[j]], checked.mCandidates[j].mRelativePose));
-                at.push_back(j);
-            }
-            if (flat.empty())
-                continue;
-            csm_ctx* ctx = csm_group_member(this->mGroup, k);
-            std::vector<csm_ray_check_result> res(flat.size());
-            CSM_ASSERT_OK(ctx, csm_ray_check_batch(ctx, flat.data(), static_cast<std::int32_t>(flat.size()),
-                                                   &settings.mParams, res.data(), nullptr));
-            for (std::size_t j = 0; j < at.size(); ++j)
-                checked.mCandidateRecords[at[j]] = res[j];
-        }
-        for (std::size_t j = 0; j < found.size(); ++j) {
-            const bool keep = settings.Passes(checked.mCandidateRecords[j]);
-            checked.mQueryIndex.push_back(static_cast<int>(found[j]));
-            checked.mPeakIndex.push_back(0);
-            checked.mKept.push_back(keep ? 1 : 0);
-            if (keep) {
-                checked.mResults.push_back(checked.mCandidates[j]);
-                checked.mRecords.push_back(checked.mCandidateRecords[j]);
-            }
-        }
+        detail::SetCandidates(this->DetectFound(queries, &found), found, checked);
+        checked.mCandidateRecords = this->CheckAt(queries, checked.mQueryIndex, detail::CandidatePoses(checked), settings);
+        detail::MarkKept(settings, checked);
+        detail::CollectKept(checked, false);
         return checked;
     }
 
 private:
-    /* query q with the map-local robot pose to check in place of its initial pose */
-    static csm_loop_query CheckQuery(const LoopDetectionQuery& q, const RobotPose2D<double>& pose)
+    /* fn(ctx, at) for every member that has work: ctx is the member's context and `at` the places j of
+     * `index` whose query index[j] lies in the member's block. The blocks are those of the whole query vector
+     * (numOfQueries), whatever `index` selects: each member holds the maps of its own block, so that what
+     * follows a Detect() runs where Detect() ran. */
+    template <typename Fn>
+    void ForEachMember(std::size_t numOfQueries, const std::vector<int>& index, Fn&& fn) const
     {
-        const GridMapView& g = q.mReferenceLocalMap;
-        csm_loop_query f {};
-        f.map_id = g.mId;
-        f.geometry = { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
-        f.scan = detail::ToScan(q.mQueryScanData);
-        f.initial_pose[0] = pose.mX;
-        f.initial_pose[1] = pose.mY;
-        f.initial_pose[2] = pose.mTheta;
-        return f;
+        const std::int32_t members = csm_group_size(this->mGroup);
+        for (std::int32_t k = 0; k < members; ++k) {
+            std::int32_t lo = 0, hi = 0;
+            csm_shard_bounds(static_cast<std::int32_t>(numOfQueries), k, members, &lo, &hi);
+            std::vector<std::size_t> at;
+            for (std::size_t j = 0; j < index.size(); ++j)
+                if (index[j] >= lo && index[j] < hi)
+                    at.push_back(j);
+            if (!at.empty())
+                fn(csm_group_member(this->mGroup, k), at);
+        }
+    }
+
+    /* record j = the free-space check of queries[index[j]]'s scan at poses[j], each member on its block */
+    std::vector<csm_ray_check_result> CheckAt(const LoopDetectionQueryVector& queries, const std::vector<int>& index,
+                                              const std::vector<RobotPose2D<double>>& poses,
+                                              const RayCheckSettings& settings) const
+    {
+        std::vector<csm_ray_check_result> records(index.size());
+        this->ForEachMember(queries.size(), index, [&](csm_ctx* ctx, const std::vector<std::size_t>& at) {
+            std::vector<csm_loop_query> flat;
+            for (std::size_t j : at) {
+                const LoopDetectionQuery& q = queries[static_cast<std::size_t>(index[j])];
+                detail::UploadOnce(ctx, q.mReferenceLocalMap);
+                flat.push_back(detail::ToLoopQuery(q, poses[j]));
+            }
+            std::vector<csm_ray_check_result> res(flat.size());
+            CSM_ASSERT_OK(ctx, csm_ray_check_batch(ctx, flat.data(), static_cast<std::int32_t>(flat.size()),
+                                                   &settings.mParams, res.data(), nullptr));
+            for (std::size_t j = 0; j < at.size(); ++j)
+                records[at[j]] = res[j];
+        });
+        return records;
     }
 
     /* Detect(); found (may be null) receives the query index of every result */
@@ -937,38 +1058,15 @@ private:
         LoopDetectionResultVector results;
         if (queries.empty())
             return results;
-        const std::int32_t n = static_cast<std::int32_t>(queries.size());
-        const std::int32_t members = csm_group_size(this->mGroup);
         std::vector<csm_loop_query> flat(queries.size());
-        for (std::int32_t k = 0; k < members; ++k) {
-            std::int32_t lo = 0, hi = 0;
-            csm_shard_bounds(n, k, members, &lo, &hi);
-            csm_ctx* ctx = csm_group_member(this->mGroup, k);
-            for (std::int32_t i = lo; i < hi; ++i) {
-                const LoopDetectionQuery& q = queries[i];
-                const GridMapView& g = q.mReferenceLocalMap;
-                /* a loop detector only sees finished local maps, which have an id and never
-                 * change (Assert(localMap.mFinished), loop_detector_branch_bound.cpp:77) */
-                if (g.mId == GridMapView::kInvalidId) {
-                    std::fprintf(stderr, "Assertion failed: reference local map without an id at %s:%d\n",
-                                 __FILE__, __LINE__);
-                    std::abort();
-                }
-                /* upload once per id and member (mPrecompMaps, loop_detector_branch_bound.hpp:98) */
-                if (!csm_has_grid(ctx, g.mId))
-                    CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, g.mId, g.mValues, g.mRows, g.mCols));
-                csm_loop_query& f = flat[i];
-                f.map_id = g.mId;
-                f.geometry = { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
-                f.scan = detail::ToScan(q.mQueryScanData);
-                const double start[3] = { q.mReferenceLocalMapNodeGlobalPose.mX,
-                                          q.mReferenceLocalMapNodeGlobalPose.mY,
-                                          q.mReferenceLocalMapNodeGlobalPose.mTheta };
-                const double end[3] = { q.mQueryScanNodeGlobalPose.mX, q.mQueryScanNodeGlobalPose.mY,
-                                        q.mQueryScanNodeGlobalPose.mTheta };
-                csm_host_inverse_compound(start, end, f.initial_pose);
+        std::vector<int> all(queries.size());
+        std::iota(all.begin(), all.end(), 0);
+        this->ForEachMember(queries.size(), all, [&](csm_ctx* ctx, const std::vector<std::size_t>& at) {
+            for (std::size_t i : at) {
+                detail::UploadOnce(ctx, queries[i].mReferenceLocalMap);
+                flat[i] = detail::ToLoopQuery(queries[i]);
             }
-        }
+        });
         csm_bnb_params prm {};
         prm.range_x = this->mRangeX;
         prm.range_y = this->mRangeY;
@@ -977,61 +1075,41 @@ private:
         prm.score_threshold = this->mScoreThreshold;
         prm.known_rate_threshold = this->mKnownRateThreshold;
         std::vector<csm_summary> out(queries.size());
-        const int rc = csm_group_bnb_match_batch(this->mGroup, flat.data(), n, &prm, out.data());
-        if (rc != 0) {
-            std::fprintf(stderr, "Assertion failed: csm_group_bnb_match_batch == 0 (rc %d: %s) at %s:%d\n", rc,
-                         csm_group_last_error(this->mGroup), __FILE__, __LINE__);
-            std::abort();
-        }
-        /* the final matcher on every estimate that was found, member by member (each member
-         * holds the maps of its own block): loop_detector_branch_bound.cpp:119-127 */
-        std::vector<csm_refine_result> refined(queries.size());
-        if (this->mRefine) {
-            for (std::int32_t k = 0; k < members; ++k) {
-                std::int32_t lo = 0, hi = 0;
-                csm_shard_bounds(n, k, members, &lo, &hi);
-                std::vector<csm_loop_query> second;
-                std::vector<std::int32_t> index;
-                for (std::int32_t i = lo; i < hi; ++i) {
-                    if (!out[i].pose_found)
-                        continue;
-                    csm_loop_query q = flat[i];
-                    for (int c = 0; c < 3; ++c)
-                        q.initial_pose[c] = out[i].estimated_pose[c];
-                    second.push_back(q);
-                    index.push_back(i);
-                }
-                if (second.empty())
-                    continue;
-                std::vector<csm_refine_result> res(second.size());
-                csm_ctx* ctx = csm_group_member(this->mGroup, k);
-                CSM_ASSERT_OK(ctx, csm_linear_solver_batch(ctx, second.data(),
-                                                           static_cast<std::int32_t>(second.size()),
-                                                           &this->mRefineParams, res.data()));
-                for (std::size_t j = 0; j < index.size(); ++j)
-                    refined[index[j]] = res[j];
-                /* the solver object keeps its damping factor between calls */
-                this->mRefineParams.lambda = res.back().lambda;
+        const int rc = csm_group_bnb_match_batch(this->mGroup, flat.data(), static_cast<std::int32_t>(flat.size()), &prm,
+                                                 out.data());
+        CSM_ASSERT_THAT(rc == 0, "csm_group_bnb_match_batch == 0 (rc %d: %s)", rc, csm_group_last_error(this->mGroup));
+        std::vector<int> hits;              /* the queries where a pose was found */
+        for (std::size_t i = 0; i < queries.size(); ++i)
+            if (out[i].pose_found) {
+                results.push_back(detail::ToResult(queries[i], out[i]));
+                hits.push_back(static_cast<int>(i));
+                if (found)
+                    found->push_back(i);
             }
-        }
-        for (std::size_t i = 0; i < queries.size(); ++i) {
-            if (!out[i].pose_found)
-                continue;
-            LoopDetectionResult r {
-                { out[i].estimated_pose[0], out[i].estimated_pose[1], out[i].estimated_pose[2] },
-                queries[i].mReferenceLocalMapNodeGlobalPose, queries[i].mReferenceLocalMap.mId,
-                queries[i].mQueryScanNodeId, out[i].raw.score, out[i].raw.flags };
-            if (this->mRefine) {
-                r.mRelativePose = { refined[i].estimated_pose[0], refined[i].estimated_pose[1],
-                                    refined[i].estimated_pose[2] };
+        if (!this->mRefine)
+            return results;
+        /* the final matcher on every estimate that was found, member by member:
+         * loop_detector_branch_bound.cpp:119-127 */
+        this->ForEachMember(queries.size(), hits, [&](csm_ctx* ctx, const std::vector<std::size_t>& at) {
+            std::vector<csm_loop_query> second;
+            for (std::size_t j : at) {
+                second.push_back(flat[static_cast<std::size_t>(hits[j])]);
+                for (int c = 0; c < 3; ++c)
+                    second.back().initial_pose[c] = out[static_cast<std::size_t>(hits[j])].estimated_pose[c];
+            }
+            std::vector<csm_refine_result> res(second.size());
+            CSM_ASSERT_OK(ctx, csm_linear_solver_batch(ctx, second.data(), static_cast<std::int32_t>(second.size()),
+                                                       &this->mRefineParams, res.data()));
+            for (std::size_t j = 0; j < at.size(); ++j) {
+                LoopDetectionResult& r = results[at[j]];
+                r.mRelativePose = { res[j].estimated_pose[0], res[j].estimated_pose[1], res[j].estimated_pose[2] };
                 for (int c = 0; c < 9; ++c)
-                    r.mEstimatedCovariance[c] = refined[i].covariance[c];
-                r.mNormalizedCost = refined[i].normalized_cost;
+                    r.mEstimatedCovariance[c] = res[j].covariance[c];
+                r.mNormalizedCost = res[j].normalized_cost;
             }
-            results.push_back(r);
-            if (found)
-                found->push_back(i);
-        }
+            /* the solver object keeps its damping factor between calls */
+            this->mRefineParams.lambda = res.back().lambda;
+        });
         return results;
     }
 
@@ -1088,16 +1166,12 @@ public:
         std::vector<csm_ray_check_result> records(queries.size());
         if (queries.empty())
             return records;
-        if (poses.size() != queries.size()) {
-            std::fprintf(stderr, "Assertion failed: one pose per query at %s:%d\n", __FILE__, __LINE__);
-            std::abort();
-        }
+        CSM_ASSERT_THAT(poses.size() == queries.size(), "one pose per query");
         csm_ctx* ctx = this->mCtx.get();
-        std::vector<csm_loop_query> flat = this->Flatten(queries);
-        for (std::size_t i = 0; i < flat.size(); ++i) {
-            flat[i].initial_pose[0] = poses[i].mX;
-            flat[i].initial_pose[1] = poses[i].mY;
-            flat[i].initial_pose[2] = poses[i].mTheta;
+        std::vector<csm_loop_query> flat(queries.size());
+        for (std::size_t i = 0; i < queries.size(); ++i) {
+            detail::UploadOnce(ctx, queries[i].mReferenceLocalMap);
+            flat[i] = detail::ToLoopQuery(queries[i], poses[i]);
         }
         CSM_ASSERT_OK(ctx, csm_ray_check_batch(ctx, flat.data(), static_cast<std::int32_t>(flat.size()),
                                                &settings.mParams, records.data(), nullptr));
@@ -1110,17 +1184,8 @@ public:
     {
         CheckedLoopDetections checked;
         std::vector<std::size_t> found;
-        checked.mCandidates = this->DetectFound(queries, &found);
-        for (std::size_t j = 0; j < found.size(); ++j) {
-            checked.mQueryIndex.push_back(static_cast<int>(found[j]));
-            checked.mPeakIndex.push_back(0);
-        }
-        this->CheckCandidates(queries, settings, checked);
-        for (std::size_t j = 0; j < checked.mCandidates.size(); ++j)
-            if (checked.mKept[j]) {
-                checked.mResults.push_back(checked.mCandidates[j]);
-                checked.mRecords.push_back(checked.mCandidateRecords[j]);
-            }
+        detail::SetCandidates(this->DetectFound(queries, &found), found, checked);
+        this->CheckCandidates(queries, settings, checked, false);
         return checked;
     }
 
@@ -1139,17 +1204,7 @@ public:
                 checked.mQueryIndex.push_back(static_cast<int>(i));
                 checked.mPeakIndex.push_back(static_cast<int>(j));
             }
-        this->CheckCandidates(queries, settings, checked);
-        int taken = -1;                     /* the last query that has its peak */
-        for (std::size_t j = 0; j < checked.mCandidates.size(); ++j) {
-            if (checked.mKept[j] && checked.mQueryIndex[j] != taken) {
-                taken = checked.mQueryIndex[j];
-                checked.mResults.push_back(checked.mCandidates[j]);
-                checked.mRecords.push_back(checked.mCandidateRecords[j]);
-            } else {
-                checked.mKept[j] = 0;
-            }
-        }
+        this->CheckCandidates(queries, settings, checked, true);
         return checked;
     }
 
@@ -1176,7 +1231,7 @@ public:
                                                        &peaks, out.data(), count.data()));
         for (std::size_t i = 0; i < queries.size(); ++i)
             for (std::int32_t j = 0; j < count[i]; ++j)
-                results[i].push_back(Result(queries[i], out[i * kMax + static_cast<std::size_t>(j)]));
+                results[i].push_back(detail::ToResult(queries[i], out[i * kMax + static_cast<std::size_t>(j)]));
         return results;
     }
 
@@ -1202,7 +1257,7 @@ public:
         for (std::size_t i = 0; i < queries.size(); ++i) {
             if (!out[i].summary.pose_found)
                 continue;
-            LoopDetectionResult r = Result(queries[i], out[i].summary);
+            LoopDetectionResult r = detail::ToResult(queries[i], out[i].summary);
             for (int c = 0; c < 9; ++c)
                 r.mEstimatedCovariance[c] = out[i].covariance[c];
             results.push_back(r);
@@ -1227,71 +1282,41 @@ private:
                                ctx, flat.data(), static_cast<std::int32_t>(flat.size()), &prm, out.data()));
         for (std::size_t i = 0; i < queries.size(); ++i)
             if (out[i].pose_found) {
-                results.push_back(Result(queries[i], out[i]));
+                results.push_back(detail::ToResult(queries[i], out[i]));
                 if (found)
                     found->push_back(i);
             }
         return results;
     }
 
-    /* the records of checked.mCandidates (query mQueryIndex[j] at the candidate's pose) in one call, and
-     * mKept[j] = settings.Passes(record j) */
+    /* the records of checked.mCandidates (query mQueryIndex[j] at the candidate's pose) in one call, then
+     * mKept, mResults and mRecords from them */
     void CheckCandidates(const LoopDetectionQueryVector& queries, const RayCheckSettings& settings,
-                         CheckedLoopDetections& checked)
+                         CheckedLoopDetections& checked, bool firstPerQuery)
     {
         LoopDetectionQueryVector sub;
-        std::vector<RobotPose2D<double>> poses;
-        for (std::size_t j = 0; j < checked.mCandidates.size(); ++j) {
-            sub.push_back(queries[static_cast<std::size_t>(checked.mQueryIndex[j])]);
-            poses.push_back(checked.mCandidates[j].mRelativePose);
-        }
-        checked.mCandidateRecords = this->CheckRays(sub, poses, settings);
-        checked.mKept.clear();
-        for (const csm_ray_check_result& r : checked.mCandidateRecords)
-            checked.mKept.push_back(settings.Passes(r) ? 1 : 0);
+        for (int i : checked.mQueryIndex)
+            sub.push_back(queries[static_cast<std::size_t>(i)]);
+        checked.mCandidateRecords = this->CheckRays(sub, detail::CandidatePoses(checked), settings);
+        detail::MarkKept(settings, checked);
+        detail::CollectKept(checked, firstPerQuery);
     }
 
     /* the queries as the batch entries take them; maps that are not resident yet are uploaded */
     std::vector<csm_loop_query> Flatten(const LoopDetectionQueryVector& queries)
     {
-        csm_ctx* ctx = this->mCtx.get();
         std::vector<csm_loop_query> flat(queries.size());
         for (std::size_t i = 0; i < queries.size(); ++i) {
-            const LoopDetectionQuery& q = queries[i];
-            const GridMapView& g = q.mReferenceLocalMap;
-            if (!csm_has_grid(ctx, g.mId))
-                CSM_ASSERT_OK(ctx, csm_upload_grid(ctx, g.mId, g.mValues, g.mRows, g.mCols));
-            csm_loop_query& f = flat[i];
-            f.map_id = g.mId;
-            f.geometry = { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
-            f.scan = detail::ToScan(q.mQueryScanData);
-            const double start[3] = { q.mReferenceLocalMapNodeGlobalPose.mX,
-                                      q.mReferenceLocalMapNodeGlobalPose.mY,
-                                      q.mReferenceLocalMapNodeGlobalPose.mTheta };
-            const double end[3] = { q.mQueryScanNodeGlobalPose.mX, q.mQueryScanNodeGlobalPose.mY,
-                                    q.mQueryScanNodeGlobalPose.mTheta };
-            csm_host_inverse_compound(start, end, f.initial_pose);
+            detail::UploadOnce(this->mCtx.get(), queries[i].mReferenceLocalMap);
+            flat[i] = detail::ToLoopQuery(queries[i]);
         }
         return flat;
     }
 
     csm_correlative_params Params() const
     {
-        csm_correlative_params prm {};
-        prm.range_x = this->mRangeX;
-        prm.range_y = this->mRangeY;
-        prm.range_theta = this->mRangeTheta;
-        prm.low_resolution = this->mLowResolution;
-        prm.score_threshold = this->mScoreThreshold;
-        prm.known_rate_threshold = this->mKnownRateThreshold;
-        return prm;
-    }
-
-    static LoopDetectionResult Result(const LoopDetectionQuery& q, const csm_summary& s)
-    {
-        return LoopDetectionResult { { s.estimated_pose[0], s.estimated_pose[1], s.estimated_pose[2] },
-                                     q.mReferenceLocalMapNodeGlobalPose, q.mReferenceLocalMap.mId,
-                                     q.mQueryScanNodeId, s.raw.score, s.raw.flags };
+        return detail::CorrelativeParams(this->mRangeX, this->mRangeY, this->mRangeTheta, this->mLowResolution,
+                                         this->mScoreThreshold, this->mKnownRateThreshold);
     }
 
     LoopDetectorCorrelativeHIP(const std::string& name, int lowResolution, double rangeX,
@@ -1344,10 +1369,7 @@ public:
     /* GridMapBuilder::UpdateLatestMap (grid_map_builder.cpp:497-527); scanNodes in id order */
     void UpdateLatestMap(const std::vector<ScanNodeView>& scanNodes)
     {
-        if (scanNodes.empty()) {
-            std::fprintf(stderr, "Assertion failed: !scanNodes.empty() at %s:%d\n", __FILE__, __LINE__);
-            std::abort();
-        }
+        CSM_ASSERT_THAT(!scanNodes.empty(), "!scanNodes.empty()");
         const std::size_t count = std::min(scanNodes.size(),
                                            static_cast<std::size_t>(this->mNumOfScansForLatestMap));
         const ScanNodeView* first = scanNodes.data() + (scanNodes.size() - count);
@@ -1359,9 +1381,7 @@ public:
     void ConstructMapFromScans(const RobotPose2D<double>& globalMapPose, const ScanNodeView* nodes,
                                std::size_t numOfNodes)
     {
-        std::vector<csm_scan_node> flat(numOfNodes);
-        for (std::size_t i = 0; i < numOfNodes; ++i)
-            flat[i] = detail::ToScanNode(nodes[i]);
+        const std::vector<csm_scan_node> flat = detail::ToScanNodes(nodes, numOfNodes);
         const double pose[3] = { globalMapPose.mX, globalMapPose.mY, globalMapPose.mTheta };
         CSM_ASSERT_OK(this->mCtx, csm_construct_map_from_scans(
                                       this->mCtx, this->mLatestMap.mId, &this->mShape, pose, flat.data(),
@@ -1381,9 +1401,7 @@ public:
      * as UpdatePoseGraph creates it (grid_map_builder.cpp:251) */
     void CreateLocalMap(std::uint64_t localMapId)
     {
-        csm_map_shape shape = this->mShape;
-        shape.offset_x = shape.offset_y = 0.0;
-        shape.rows = shape.cols = this->mInitialCells;
+        const csm_map_shape shape = this->FreshShape();
         const std::vector<std::uint16_t> empty(static_cast<std::size_t>(shape.rows) * shape.cols, 0);
         CSM_ASSERT_OK(this->mCtx, csm_upload_grid(this->mCtx, localMapId, empty.data(), shape.rows, shape.cols));
         this->mLocalShapes[localMapId] = shape;
@@ -1395,11 +1413,8 @@ public:
                        const ScanNodeView& latestScanNode)
     {
         auto it = this->mLocalShapes.find(localMapId);
-        if (it == this->mLocalShapes.end()) {
-            std::fprintf(stderr, "Assertion failed: local map %llu exists at %s:%d\n",
-                         static_cast<unsigned long long>(localMapId), __FILE__, __LINE__);
-            std::abort();
-        }
+        CSM_ASSERT_THAT(it != this->mLocalShapes.end(), "local map %llu exists",
+                        static_cast<unsigned long long>(localMapId));
         const csm_scan_node flat = detail::ToScanNode(latestScanNode);
         const double pose[3] = { globalMapPose.mX, globalMapPose.mY, globalMapPose.mTheta };
         CSM_ASSERT_OK(this->mCtx, csm_update_map_with_scan(this->mCtx, localMapId, &it->second, pose, &flat,
@@ -1416,20 +1431,15 @@ public:
                             const std::vector<RobotPose2D<double>>& globalMapPoses,
                             const std::vector<std::pair<const ScanNodeView*, std::size_t>>& nodeSpans)
     {
-        if (localMapIds.empty() || globalMapPoses.size() != localMapIds.size() ||
-            nodeSpans.size() != localMapIds.size()) {
-            std::fprintf(stderr, "Assertion failed: one pose and one node span per local map at %s:%d\n",
-                         __FILE__, __LINE__);
-            std::abort();
-        }
+        CSM_ASSERT_THAT(!localMapIds.empty() && globalMapPoses.size() == localMapIds.size() &&
+                            nodeSpans.size() == localMapIds.size(),
+                        "one pose and one node span per local map");
         std::vector<std::vector<csm_scan_node>> flat(localMapIds.size());
         std::vector<csm_map_build_job> jobs(localMapIds.size());
         for (std::size_t m = 0; m < localMapIds.size(); ++m) {
             if (this->mLocalShapes.find(localMapIds[m]) == this->mLocalShapes.end())
                 this->CreateLocalMap(localMapIds[m]);
-            flat[m].resize(nodeSpans[m].second);
-            for (std::size_t i = 0; i < nodeSpans[m].second; ++i)
-                flat[m][i] = detail::ToScanNode(nodeSpans[m].first[i]);
+            flat[m] = detail::ToScanNodes(nodeSpans[m].first, nodeSpans[m].second);
             csm_map_build_job& job = jobs[m];
             job = csm_map_build_job {};
             job.map_id = localMapIds[m];
@@ -1456,18 +1466,11 @@ public:
     void ConstructGlobalMap(std::uint64_t globalMapId, const ScanNodeView* nodes, std::size_t numOfNodes,
                             RobotPose2D<double>& globalMapPose, csm_map_shape& shape)
     {
-        if (nodes == nullptr || numOfNodes == 0) {
-            std::fprintf(stderr, "Assertion failed: !scanNodes.empty() at %s:%d\n", __FILE__, __LINE__);
-            std::abort();
-        }
-        std::vector<csm_scan_node> flat(numOfNodes);
-        for (std::size_t i = 0; i < numOfNodes; ++i)
-            flat[i] = detail::ToScanNode(nodes[i]);
+        CSM_ASSERT_THAT(nodes != nullptr && numOfNodes != 0, "!scanNodes.empty()");
+        const std::vector<csm_scan_node> flat = detail::ToScanNodes(nodes, numOfNodes);
         globalMapPose = nodes[0].mGlobalPose;
         const double pose[3] = { globalMapPose.mX, globalMapPose.mY, globalMapPose.mTheta };
-        shape = this->mShape;
-        shape.offset_x = shape.offset_y = 0.0;
-        shape.rows = shape.cols = this->mInitialCells;
+        shape = this->FreshShape();
         CSM_ASSERT_OK(this->mCtx, csm_construct_global_map(
                                       this->mCtx, globalMapId, &shape, pose, flat.data(),
                                       static_cast<std::int32_t>(numOfNodes), &this->mParams, &this->mGlobalParams,
@@ -1481,15 +1484,7 @@ public:
     /* geometry + id of a local map (cells on the device), e.g. for a LoopDetectionQuery */
     GridMapView LocalMap(std::uint64_t localMapId) const
     {
-        const csm_map_shape& shape = this->mLocalShapes.at(localMapId);
-        GridMapView view;
-        view.mRows = shape.rows;
-        view.mCols = shape.cols;
-        view.mResolution = shape.resolution;
-        view.mPosOffsetX = shape.offset_x;
-        view.mPosOffsetY = shape.offset_y;
-        view.mId = localMapId;
-        return view;
+        return detail::ToView(this->mLocalShapes.at(localMapId), localMapId);
     }
 
     std::vector<std::uint16_t> CopyLocalMapValues(std::uint64_t localMapId) const
@@ -1501,13 +1496,15 @@ public:
     }
 
 private:
-    void SyncView()
+    void SyncView() { this->mLatestMap = detail::ToView(this->mShape, this->mLatestMap.mId); }
+
+    /* the shape of a new map: GridMap(resolution, patchSize, 1.0, 1.0), as the constructor computed it */
+    csm_map_shape FreshShape() const
     {
-        this->mLatestMap.mRows = this->mShape.rows;
-        this->mLatestMap.mCols = this->mShape.cols;
-        this->mLatestMap.mResolution = this->mShape.resolution;
-        this->mLatestMap.mPosOffsetX = this->mShape.offset_x;
-        this->mLatestMap.mPosOffsetY = this->mShape.offset_y;
+        csm_map_shape shape = this->mShape;
+        shape.offset_x = shape.offset_y = 0.0;
+        shape.rows = shape.cols = this->mInitialCells;
+        return shape;
     }
 
     csm_ctx* mCtx;
@@ -1704,15 +1701,15 @@ public:
         detail::CtxPtr ctx = detail::MakeContext(deviceId);
         if (!ctx)
             return nullptr;
-        return std::unique_ptr<ScorePixelAccurateHIP>(new ScorePixelAccurateHIP(std::move(ctx), nullptr));
+        return std::unique_ptr<ScorePixelAccurateHIP>(new ScorePixelAccurateHIP(detail::ContextRef(std::move(ctx))));
     }
     /* on a context another adapter owns (and keeps alive) */
-    explicit ScorePixelAccurateHIP(csm_ctx* shared) : mShared(shared) { }
+    explicit ScorePixelAccurateHIP(csm_ctx* shared) : mCtx(shared) { }
 
     ScorePixelAccurateHIP(const ScorePixelAccurateHIP&) = delete;
     ScorePixelAccurateHIP& operator=(const ScorePixelAccurateHIP&) = delete;
 
-    csm_ctx* Context() const { return this->mOwned ? this->mOwned.get() : this->mShared; }
+    csm_ctx* Context() const { return this->mCtx.Get(); }
     const csm_pose_sets_info& LastInfo() const { return this->mLast; }
 
     void Upload(const GridMapView& g)
@@ -1729,13 +1726,7 @@ public:
     std::vector<ScoreSummary> ScoreMany(std::uint64_t mapId, const csm_geometry& geometry, const ScanDataView& scan,
                                         const std::vector<RobotPose2D<double>>& mapLocalSensorPoses)
     {
-        static_assert(sizeof(RobotPose2D<double>) == 3 * sizeof(double), "pose layout");
-        csm_pose_set set {};
-        set.map_id = mapId;
-        set.geometry = geometry;
-        set.scan = detail::ToScan(scan);
-        set.poses = mapLocalSensorPoses.empty() ? nullptr : &mapLocalSensorPoses.front().mX;
-        set.n_poses = static_cast<std::int32_t>(mapLocalSensorPoses.size());
+        const csm_pose_set set = detail::ToPoseSet(mapId, geometry, scan, mapLocalSensorPoses);
         std::vector<csm_pose_record> rec(mapLocalSensorPoses.size());
         CSM_ASSERT_OK(this->Context(), csm_score_pose_sets(this->Context(), &set, 1, rec.data(), &this->mLast));
         std::vector<ScoreSummary> out(rec.size());
@@ -1776,10 +1767,9 @@ public:
     }
 
 private:
-    ScorePixelAccurateHIP(detail::CtxPtr owned, csm_ctx* shared) : mOwned(std::move(owned)), mShared(shared) { }
+    explicit ScorePixelAccurateHIP(detail::ContextRef ctx) : mCtx(std::move(ctx)) { }
 
-    detail::CtxPtr mOwned;
-    csm_ctx* mShared = nullptr;
+    detail::ContextRef mCtx;
     csm_pose_sets_info mLast {};
 };
 
@@ -1803,27 +1793,23 @@ public:
         detail::CtxPtr ctx = detail::MakeContext(deviceId);
         if (!ctx)
             return nullptr;
-        return std::unique_ptr<ParticleSetHIP>(new ParticleSetHIP(temperature, knownRateThreshold, std::move(ctx), nullptr));
+        return std::unique_ptr<ParticleSetHIP>(
+            new ParticleSetHIP(temperature, knownRateThreshold, detail::ContextRef(std::move(ctx))));
     }
     ParticleSetHIP(csm_ctx* shared, double temperature, double knownRateThreshold) :
-        mTemperature(temperature), mKnownRateThreshold(knownRateThreshold), mShared(shared) { }
+        ParticleSetHIP(temperature, knownRateThreshold, detail::ContextRef(shared)) { }
 
     ParticleSetHIP(const ParticleSetHIP&) = delete;
     ParticleSetHIP& operator=(const ParticleSetHIP&) = delete;
 
-    csm_ctx* Context() const { return this->mOwned ? this->mOwned.get() : this->mShared; }
+    csm_ctx* Context() const { return this->mCtx.Get(); }
 
     /* `offset` places the comb of the systematic resampling: any 64-bit draw of the caller's generator */
     Update MeasurementUpdate(std::uint64_t mapId, const csm_geometry& geometry, const ScanDataView& scan,
                              const std::vector<RobotPose2D<double>>& mapLocalSensorPoses, std::size_t numOfOutputs,
                              std::uint64_t offset)
     {
-        csm_pose_set set {};
-        set.map_id = mapId;
-        set.geometry = geometry;
-        set.scan = detail::ToScan(scan);
-        set.poses = mapLocalSensorPoses.empty() ? nullptr : &mapLocalSensorPoses.front().mX;
-        set.n_poses = static_cast<std::int32_t>(mapLocalSensorPoses.size());
+        const csm_pose_set set = detail::ToPoseSet(mapId, geometry, scan, mapLocalSensorPoses);
         csm_pose_update_params prm {};
         prm.temperature = this->mTemperature;
         prm.known_rate_threshold = this->mKnownRateThreshold;
@@ -1846,12 +1832,11 @@ public:
     }
 
 private:
-    ParticleSetHIP(double temperature, double knownRateThreshold, detail::CtxPtr owned, csm_ctx* shared) :
-        mTemperature(temperature), mKnownRateThreshold(knownRateThreshold), mOwned(std::move(owned)), mShared(shared) { }
+    ParticleSetHIP(double temperature, double knownRateThreshold, detail::ContextRef ctx) :
+        mTemperature(temperature), mKnownRateThreshold(knownRateThreshold), mCtx(std::move(ctx)) { }
 
     const double mTemperature, mKnownRateThreshold;
-    detail::CtxPtr mOwned;
-    csm_ctx* mShared = nullptr;
+    detail::ContextRef mCtx;
 };
 
 } /* namespace CsmHip */
