@@ -10,7 +10,7 @@
  * cited reference lines and are built with -ffp-contract=off.
  */
 #include "csm_matchers.hpp"
-
+#include "csm_certify.hpp"
 
 namespace csm_host {
 
@@ -447,16 +447,11 @@ int csm_host_project(const csm_geometry* geom, const double sensor_pose[3], doub
         const double theta = sensor_pose[2] + step_theta * t;
         const size_t base = (size_t)(t + win_theta) * n;
         for (int i = 0; i < n; ++i) {
-            /* ScanData::HitPoint, inc/sensor/sensor_data.hpp:189-203 */
-            const double cos_t = std::cos(theta + angles[i]);
-            const double sin_t = std::sin(theta + angles[i]);
-            const double rc = ranges[i] * cos_t;
-            const double rs = ranges[i] * sin_t;
-            const double hx = sensor_pose[0] + rc;
-            const double hy = sensor_pose[1] + rs;
-            /* PositionToIndex, src/grid_map_new/grid_map_geometry.cpp:113-122 */
-            hit_col[base + i] = static_cast<int>(std::floor((hx - geom->offset_x) / geom->resolution));
-            hit_row[base + i] = static_cast<int>(std::floor((hy - geom->offset_y) / geom->resolution));
+            /* ScanData::HitPoint and PositionToIndex (csm_certify.hpp) */
+            double rc, rs;
+            host_hit_products(theta, ranges[i], angles[i], &rc, &rs);
+            hit_col[base + i] = cell_index(sensor_pose[0] + rc, geom->offset_x, geom->resolution);
+            hit_row[base + i] = cell_index(sensor_pose[1] + rs, geom->offset_y, geom->resolution);
             if (r_cos)
                 r_cos[base + i] = rc;
             if (r_sin)

@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "csm_device.hpp"
+#include "csm_score_common.hpp"     /* wave_sum */
 
 namespace csm {
 
@@ -100,14 +100,6 @@ __device__ __forceinline__ void beam_terms(const CostJob& j, double px, double p
     t.r0 += g0 * err;
     t.r1 += g1 * err;
     t.r2 += g2 * err;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-        v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 /* sum of the beams' terms over the workgroup; every thread gets the totals */

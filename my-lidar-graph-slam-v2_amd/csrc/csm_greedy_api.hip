@@ -110,14 +110,14 @@ double host_cost(const uint16_t* grid, int rows, int cols, const csm_geometry& g
     double sum = 0.0;
     for (int i = 0; i < scan.n_points; ++i) {
         const double r = scan.ranges[i], a = scan.angles[i];
-        const double c = std::cos(pose[2] + a), s = std::sin(pose[2] + a);
-        const double hx = pose[0] + r * c, hy = pose[1] + r * s;
-        const double mx = pose[0] + (r - p.hit_and_missed_dist) * c;
-        const double my = pose[1] + (r - p.hit_and_missed_dist) * s;
-        const int hc = static_cast<int>(std::floor((hx - geom.offset_x) / geom.resolution));
-        const int hr = static_cast<int>(std::floor((hy - geom.offset_y) / geom.resolution));
-        const int mc = static_cast<int>(std::floor((mx - geom.offset_x) / geom.resolution));
-        const int mr = static_cast<int>(std::floor((my - geom.offset_y) / geom.resolution));
+        /* ScanData::HitAndMissedPoint: two hit points of one direction, at r and at r - HitAndMissedDist */
+        double hx, hy, mx, my;
+        host_hit_point(pose[0], pose[1], pose[2], r, a, &hx, &hy);
+        host_hit_point(pose[0], pose[1], pose[2], r - p.hit_and_missed_dist, a, &mx, &my);
+        const int hc = cell_index(hx, geom.offset_x, geom.resolution);
+        const int hr = cell_index(hy, geom.offset_y, geom.resolution);
+        const int mc = cell_index(mx, geom.offset_x, geom.resolution);
+        const int mr = cell_index(my, geom.offset_y, geom.resolution);
         double mn = T.def;
         for (int ky = -k; ky <= k; ++ky) {
             for (int kx = -k; kx <= k; ++kx) {

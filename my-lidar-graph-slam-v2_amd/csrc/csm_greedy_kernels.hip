@@ -1,8 +1,8 @@
 /* csm_greedy_kernels.hip -- device side of the greedy-endpoint cost and the hill-climbing matcher
  * (CostGreedyEndpoint, src/my_lidar_graph_slam/mapping/cost_function_greedy_endpoint.cpp;
  * ScanMatcherHillClimbing::OptimizePose, src/my_lidar_graph_slam/mapping/scan_matcher_hill_climbing.cpp:72-180).
- * Included by csm_greedy_api.hip (its own translation unit); cell_index and proj_err_bound come from
- * csm_score_common.hpp. gfx950 only.
+ * Included by csm_greedy_api.hip (its own translation unit); the certificate's margin comes from
+ * csm_certify.hpp, wave_sum from csm_score_common.hpp. gfx950 only.
  *
  * One workgroup per query runs the whole OptimizePose loop. An evaluation of up to six poses projects
  * every beam once per pose (lanes over beams, the six moves side by side in registers; the four x / y
@@ -56,7 +56,8 @@ struct GreedyOut {
 };
 
 /* floor((h - off) / res) as PositionToIndex computes it, and whether the host's glibc sin / cos could
- * give another integer (see map_certified in csm_map_kernels.hip: same margin) */
+ * give another integer: the margin of `certified` (csm_certify.hpp). Its own: a quotient no int holds is
+ * never certified, and the index comes back. */
 __device__ __forceinline__ bool greedy_index(double r, double h, double off, double res, int& idx)
 {
     const double q = (h - off) / res;
@@ -64,12 +65,11 @@ __device__ __forceinline__ bool greedy_index(double r, double h, double off, dou
         idx = 0;
         return false;
     }
-    const double m = 64.0 * proj_err_bound(r, h, off, res, q, 8e-16) +
-                     64.0 * 2.3e-16 * (fabs(h) + fabs(off) + 1.0e3) / res;
+    const double m = direct_margin(r, h, off, res, q);
     const double fq = floor(q);
     const double frac = q - fq;
     idx = (int)fq;
-    return frac > m && frac < 1.0 - m;
+    return off_cell_edge(frac, m);
 }
 
 __device__ __forceinline__ uint32_t greedy_cell(const GreedyJob& j, int row, int col)
@@ -96,14 +96,6 @@ __device__ __forceinline__ int greedy_beam_rank(const GreedyJob& j, int hc, int 
         }
     }
     return best;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-        v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 struct GreedyIv {

@@ -1878,10 +1878,8 @@ __global__ __launch_bounds__(256) void k_scatter_records(const csm_result* src, 
  * result is NOT the host's value bit for bit and does not have to be: an entry
  * counts only if floor() cannot flip within the error bound (the certificate),
  * everything else is recomputed on the host. Error of the cosine (sine alike):
- *   |arg_host - (sensor.theta + D + a_i)| <= 1.5 ulp of the larger angle (the host
- *   rounds theta_t and arg, the device rounds B)      -> 4e-16 * (|theta| + |D| + |a|)
- *   device libm <= 3 ulp on each of cosB, sinB, cosD, sinD, two products, one sum
- *                                                     -> 2.4e-15 */
+ * addition_trig_err(|theta| + |a| + |D|) (csm_certify.hpp): the host rounds theta_t and
+ * arg, the device rounds B, <= 1.5 ulp of the larger angle in all. */
 
 __device__ __forceinline__ void proj_body(const ProjJob& job)
 {
@@ -1919,26 +1917,23 @@ __device__ __forceinline__ void proj_body(const ProjJob& job)
     const double xr = fmax(fabs((double)x_lo), fabs((double)(x_lo + nx - 1))) * step_x;
     const double yr = fmax(fabs((double)y_lo), fabs((double)(y_lo + ny - 1))) * step_y;
     const bool unit_step = step_x == res && step_y == res;
-    /* a quotient formed as (h - off) * (1 / res): two roundings more than a division */
-    auto err_bound = [&](double hit, double off, double q, double trig_err) {
-        return (fabs(r) * trig_err + (fabs(hit) + fabs(off)) * 4e-16) * inv_res + fabs(q) * 8e-16;
-    };
+    /* the quotients are formed as (h - off) * (1 / res): the reciprocal form of the bound */
     for (int k = 0; k < n_local; ++k) {
         const int t = (int)blockIdx.y + k * (int)gridDim.y;
         const double cd = tab_c[k], sd = tab_s[k];
-        const double trig_err = 2.4e-15 + 4e-16 * (ang + fabs(step_theta * (t - win_theta)));
+        const double trig_err = addition_trig_err(ang + fabs(step_theta * (t - win_theta)));
         const double rc = r * (cb * cd - sb * sd);
         const double rs = r * (sb * cd + cb * sd);
         const double hx = sensor_x + rc, hy = sensor_y + rs;
         const double qx = (hx - off_x) * inv_res, qy = (hy - off_y) * inv_res;
         const double fx = floor(qx), fy = floor(qy);
-        const double mx = 64.0 * err_bound(hx, off_x, qx, trig_err);
-        const double my = 64.0 * err_bound(hy, off_y, qy, trig_err);
+        const double mx = kCertSafety * proj_err_bound_recip(r, hx, off_x, inv_res, qx, trig_err);
+        const double my = kCertSafety * proj_err_bound_recip(r, hy, off_y, inv_res, qy, trig_err);
         const size_t idx = (size_t)t * n_points + i;
         const int col = (int)fx, row = (int)fy;
         hit_col[idx] = col;
         hit_row[idx] = row;
-        bool uncertain = !(qx - fx > mx && qx - fx < 1.0 - mx && qy - fy > my && qy - fy < 1.0 - my);
+        bool uncertain = !(off_cell_edge(qx - fx, mx) && off_cell_edge(qy - fy, my));
         if (check_nodes && !uncertain) {
             /* appendNode's pose (scan_matcher_branch_bound.cpp:156-176):
              * floor(((sensor + x*step) + r*trig - off) / res) must equal base + x for
@@ -1947,27 +1942,27 @@ __device__ __forceinline__ void proj_body(const ProjJob& job)
              * node coordinate is q + x; every rounding on the way is bounded, hence
              * one test per beam and axis certifies all offsets at once. Only beams
              * within that (slightly wider) margin of a cell edge walk the offsets. */
-            const double wx = 64.0 * ((fabs(r) * trig_err + (fabs(hx) + xr + fabs(off_x)) * 8e-16) * inv_res +
-                                      (fabs(qx) + xr * inv_res) * 1.2e-15);
-            const double wy = 64.0 * ((fabs(r) * trig_err + (fabs(hy) + yr + fabs(off_y)) * 8e-16) * inv_res +
-                                      (fabs(qy) + yr * inv_res) * 1.2e-15);
-            const bool sure_x = unit_step && qx - fx > wx && qx - fx < 1.0 - wx;
-            const bool sure_y = unit_step && qy - fy > wy && qy - fy < 1.0 - wy;
+            const double wx = kCertSafety * ((fabs(r) * trig_err + (fabs(hx) + xr + fabs(off_x)) * kNodeRoundErr) * inv_res +
+                                             (fabs(qx) + xr * inv_res) * kNodeQuotErr);
+            const double wy = kCertSafety * ((fabs(r) * trig_err + (fabs(hy) + yr + fabs(off_y)) * kNodeRoundErr) * inv_res +
+                                             (fabs(qy) + yr * inv_res) * kNodeQuotErr);
+            const bool sure_x = unit_step && off_cell_edge(qx - fx, wx);
+            const bool sure_y = unit_step && off_cell_edge(qy - fy, wy);
             for (int xi = 0; xi < nx && !sure_x && !uncertain; ++xi) {
                 const int x = x_lo + xi;
                 const double h = (sensor_x + x * step_x) + rc;
                 const double q = (h - off_x) * inv_res;
                 const double f = floor(q);
-                const double m = 64.0 * err_bound(h, off_x, q, trig_err);
-                uncertain = !((int)f == col + x && q - f > m && q - f < 1.0 - m);
+                const double m = kCertSafety * proj_err_bound_recip(r, h, off_x, inv_res, q, trig_err);
+                uncertain = !((int)f == col + x && off_cell_edge(q - f, m));
             }
             for (int yi = 0; yi < ny && !sure_y && !uncertain; ++yi) {
                 const int y = y_lo + yi;
                 const double h = (sensor_y + y * step_y) + rs;
                 const double q = (h - off_y) * inv_res;
                 const double f = floor(q);
-                const double m = 64.0 * err_bound(h, off_y, q, trig_err);
-                uncertain = !((int)f == row + y && q - f > m && q - f < 1.0 - m);
+                const double m = kCertSafety * proj_err_bound_recip(r, h, off_y, inv_res, q, trig_err);
+                uncertain = !((int)f == row + y && off_cell_edge(q - f, m));
             }
         }
         if (uncertain) {

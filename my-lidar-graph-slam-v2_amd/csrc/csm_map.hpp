@@ -5,7 +5,7 @@
  * kernels (csm_map_kernels.hip: one launch per map, the workgroup number is the
  * place in the map) and the many-map kernels (csm_map_batch_kernels.hip: one launch
  * per chunk, each workgroup looks its map up first) run the same text. cell_index and
- * proj_err_bound come from csm_score_common.hpp. gfx950 only. */
+ * certified come from csm_certify.hpp. gfx950 only. */
 #ifndef CSM_MAP_HPP
 #define CSM_MAP_HPP
 
@@ -31,15 +31,7 @@ namespace csm {
  * where q is the same expression in the CURRENT frame. A beam whose q (cell and
  * sub-pixel scale, both axes) stays farther from the next integer than the two
  * libms can disagree plus that slack gives the host's integers; the others are
- * listed and recomputed on the host with glibc. */
-__device__ __forceinline__ bool map_certified(double r, double h, double off, double res)
-{
-    const double q = (h - off) / res;
-    const double m = 64.0 * proj_err_bound(r, h, off, res, q, 8e-16) +    /* 3 ulp between the two libms */
-                     64.0 * 2.3e-16 * (fabs(h) + fabs(off) + 1.0e3) / res;
-    const double frac = q - floor(q);
-    return frac > m && frac < 1.0 - m;
-}
+ * listed and recomputed on the host with glibc: `certified` (csm_certify.hpp). */
 
 /* beam b of a map (thread b of its launch, or of its part of a chunk's launch). node_src = null:
  * the map's scans lie concatenated at job.angles / job.ranges. Otherwise node k's angles start at
@@ -67,10 +59,10 @@ __device__ __forceinline__ void map_project_beam(const MapProjJob& job, int b)
             const uint32_t spread = (fabs(ray.hx - nd.x) > 1e-6 ? 1u : 0u) | (fabs(ray.hy - nd.y) > 1e-6 ? 2u : 0u);
             if (spread & ~job.unc_count[1])
                 atomicOr(&job.unc_count[1], spread);
-            const bool sure = map_certified(r, ray.hx, job.off_x, job.res) &&
-                              map_certified(r, ray.hy, job.off_y, job.res) &&
-                              map_certified(r, ray.hx, job.off_x, job.scaled_res) &&
-                              map_certified(r, ray.hy, job.off_y, job.scaled_res);
+            const bool sure = certified(r, ray.hx, job.off_x, job.res) &&
+                              certified(r, ray.hy, job.off_y, job.res) &&
+                              certified(r, ray.hx, job.off_x, job.scaled_res) &&
+                              certified(r, ray.hy, job.off_y, job.scaled_res);
             if (sure) {
                 /* GridMap::Resize(BoundingBox<double>) (grid_map.cpp:892-913) is monotone in h */
                 lo_x = cell_index(ray.hx - job.res, job.off_x, job.res);

@@ -160,12 +160,10 @@ void map_take_projection(MapBuild& m, const int32_t got[8], uint32_t unc_cap)
 int map_patch_rays(csm_ctx* ctx, MapBuild& m, const uint32_t* list, MapRay* d_rays, std::vector<MapRay>& src,
                    bool& uploads)
 {
-    /* ScanData::HitPoint (inc/sensor/sensor_data.hpp:189-203) */
+    /* ScanData::HitPoint with glibc (csm_certify.hpp) */
     auto hit_point = [&m](int k, int i, MapRay& ray) {
         const MapNode& t = m.table[k];
-        const double r = m.nodes[k].scan.ranges[i];
-        ray.hx = t.x + r * std::cos(t.theta + m.nodes[k].scan.angles[i]);
-        ray.hy = t.y + r * std::sin(t.theta + m.nodes[k].scan.angles[i]);
+        host_hit_point(t.x, t.y, t.theta, m.nodes[k].scan.ranges[i], m.nodes[k].scan.angles[i], &ray.hx, &ray.hy);
         ray.node = k;
         ray.usable = 1;
         m.add_point(ray.hx, ray.hy);
@@ -213,7 +211,7 @@ int map_resize(csm_ctx* ctx, MapBuild& m, int scale)
 {
     const csm_map_shape& shape = *m.shape;
     const double res = shape.resolution, scaled_res = res / scale;   /* ScaledGeometry, grid_map_geometry.cpp:46-58 */
-    auto to_index = [res](double p, double off) { return static_cast<int>(std::floor((p - off) / res)); };
+    auto to_index = [res](double p, double off) { return cell_index(p, off, res); };
     /* Assert(min < max) of Resize: the host-side points decide unless the certified
      * beams are known to spread in both axes */
     if (!m.spread_known && (!(m.min_x < m.max_x) || !(m.min_y < m.max_y)))
@@ -231,8 +229,8 @@ int map_resize(csm_ctx* ctx, MapBuild& m, int scale)
     m.resized = !m.keep_cells || m.shift[0] != 0 || m.shift[1] != 0 || m.next.rows != shape.rows ||
                 m.next.cols != shape.cols;
     for (MapNode& t : m.table) {
-        t.sx = static_cast<int>(std::floor((t.x - m.next.offset_x) / scaled_res));
-        t.sy = static_cast<int>(std::floor((t.y - m.next.offset_y) / scaled_res));
+        t.sx = cell_index(t.x, m.next.offset_x, scaled_res);
+        t.sy = cell_index(t.y, m.next.offset_y, scaled_res);
     }
     m.n_cells = (size_t)m.next.rows * m.next.cols;
     return CSM_OK;

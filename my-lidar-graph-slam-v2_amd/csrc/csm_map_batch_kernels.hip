@@ -22,61 +22,49 @@
 
 namespace csm {
 
-/* the map of workgroup (or item) w: the last m < n with pre[m] <= w; maps without work have
- * pre[m] == pre[m + 1] and are never found. pre[0] = 0, w < pre[n]. */
-__device__ __forceinline__ int map_find(const uint32_t* pre, int n, uint32_t w)
-{
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pre[mid] <= w)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
+/* the map of workgroup (or item) w is prefix_find(pre, n, w) (csm_score_common.hpp); maps without
+ * work have pre[m] == pre[m + 1] and are never found. */
 
 __global__ __launch_bounds__(256) void k_mapb_project(MapBatchTable tab)
 {
-    const int m = map_find(tab.pre_beam, tab.n_maps, blockIdx.x);
+    const int m = prefix_find(tab.pre_beam, tab.n_maps, blockIdx.x);
     map_project_beam(tab.proj[m], (int)(blockIdx.x - tab.pre_beam[m]) * 256 + (int)threadIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_mapb_hits(MapBatchTable tab)
 {
-    const int m = map_find(tab.pre_ray, tab.n_maps, blockIdx.x);
+    const int m = prefix_find(tab.pre_ray, tab.n_maps, blockIdx.x);
     map_hits_ray(tab.jobs[m], (int)(blockIdx.x - tab.pre_ray[m]) * 256 + (int)threadIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_mapb_alloc(MapBatchTable tab)
 {
-    const int m = map_find(tab.pre_cell, tab.n_maps, blockIdx.x);
+    const int m = prefix_find(tab.pre_cell, tab.n_maps, blockIdx.x);
     map_alloc_cell(tab.jobs[m], (int)(blockIdx.x - tab.pre_cell[m]) * 256 + (int)threadIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_mapb_fill_hits(MapBatchTable tab)
 {
-    const int m = map_find(tab.pre_ray, tab.n_maps, blockIdx.x);
+    const int m = prefix_find(tab.pre_ray, tab.n_maps, blockIdx.x);
     map_fill_ray(tab.jobs[m], (int)(blockIdx.x - tab.pre_ray[m]) * 256 + (int)threadIdx.x);
 }
 
 /* the rank is the hit's place among ITS map's rays: ray numbers are local to the map */
 __global__ __launch_bounds__(256) void k_mapb_rank_hits(MapBatchTable tab)
 {
-    const int m = map_find(tab.pre_ray, tab.n_maps, blockIdx.x);
+    const int m = prefix_find(tab.pre_ray, tab.n_maps, blockIdx.x);
     map_rank_ray(tab.jobs[m], (int)(blockIdx.x - tab.pre_ray[m]) * 256 + (int)threadIdx.x);
 }
 
 __global__ __launch_bounds__(512) void k_mapb_walk(MapBatchTable tab)
 {
-    const int m = map_find(tab.pre_group, tab.n_maps, blockIdx.x);
+    const int m = prefix_find(tab.pre_group, tab.n_maps, blockIdx.x);
     map_walk_group(tab.jobs[m], (int)(blockIdx.x - tab.pre_group[m]));
 }
 
 __global__ __launch_bounds__(256) void k_mapb_apply(MapBatchTable tab)
 {
-    const int m = map_find(tab.pre_apply, tab.n_maps, blockIdx.x);
+    const int m = prefix_find(tab.pre_apply, tab.n_maps, blockIdx.x);
     map_apply_cell(tab.jobs[m], blockIdx.x - tab.pre_apply[m]);
 }
 
@@ -111,7 +99,7 @@ __global__ __launch_bounds__(256) void k_mapb_hit_prefix(MapBatchTable tab)
 }
 
 /* Cells with hits of all maps of the chunk: item i is cell hit_cells[i - hit_prefix[m]] of the map m
- * that map_find gives. One workgroup per CU at most (128 KB of LDS each), the table loaded once; as in
+ * that prefix_find gives. One workgroup per CU at most (128 KB of LDS each), the table loaded once; as in
  * k_map_apply_hits, as few lanes per wavefront carry a cell as the chunk's total allows. */
 __global__ __launch_bounds__(256) void k_mapb_apply_hits(MapBatchTable tab, const uint16_t* lut_hit)
 {
@@ -130,7 +118,7 @@ __global__ __launch_bounds__(256) void k_mapb_apply_hits(MapBatchTable tab, cons
         uint32_t v = 0, sat = 0, updates = 0;
         int row = 0, col = 0, m = -1;
         if (have) {
-            m = map_find(tab.hit_prefix, tab.n_maps, idx);
+            m = prefix_find(tab.hit_prefix, tab.n_maps, idx);
             const MapJob& job = tab.jobs[m];
             map_apply_hit_cell(job, hit_table, (int)job.hit_cells[idx - tab.hit_prefix[m]], v, sat, updates, row, col);
         }

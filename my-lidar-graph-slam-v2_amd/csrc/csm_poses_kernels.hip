@@ -8,8 +8,8 @@
  *                    triples are staged in LDS kPoseTile at a time (structure of arrays: consecutive lanes
  *                    read consecutive doubles); a wavefront owns a pose at a time, its lanes the beams.
  *                    cos / sin(theta + a) come from the addition theorems, the cell index counts only under
- *                    the certificate of proj_body (csm_kernels.hip): the same two library calls, two
- *                    products and one sum, the same bound with the x64 margin. Lanes gather their cells
+ *                    the certificate proj_body uses (csm_certify.hpp, reciprocal form): the same two library
+ *                    calls, two products and one sum, the same bound and margin. Lanes gather their cells
  *                    and add integers; the wavefront reduces by shuffles (integer sums have no order). A
  *                    pose with any beam inside the margin is marked and listed once: the list has a slot
  *                    per pose and cannot overflow.
@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/csm_hip.h"
+#include "csm_score_common.hpp"     /* prefix_find; the certificate (csm_certify.hpp) */
 
 namespace csm {
 
@@ -78,28 +79,6 @@ struct PoseUpdate {
     unsigned long long offset;
 };
 
-/* last s with pre[s] <= i (pre[0] = 0, pre[n] > i) */
-__device__ __forceinline__ int pose_find(const uint32_t* pre, int n, uint32_t i)
-{
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pre[mid] <= i)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
-/* proj_body's err_bound: |q_host - q_device| in cells for q = (pose + r trig - off) * (1 / res), the
- * quotient formed with two roundings more than a division. The caller multiplies by 64. */
-__device__ __forceinline__ double pose_err_bound(double r, double hit, double off, double q, double inv_res,
-                                                 double trig_err)
-{
-    return (fabs(r) * trig_err + (fabs(hit) + fabs(off)) * 4e-16) * inv_res + fabs(q) * 8e-16;
-}
-
 __device__ __forceinline__ unsigned long long pose_key(uint32_t s, uint32_t k)
 {
     return 32268ull * k + 499ull * s;
@@ -126,7 +105,7 @@ __global__ __launch_bounds__(kPoseBlock) void k_pose_score(PoseChunk ch)
     __shared__ uint32_t acc_s[kPoseGroupMax], acc_k[kPoseGroupMax], acc_u[kPoseGroupMax];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    const int si = pose_find(ch.pre_group, ch.n_sets, blockIdx.x);        /* uniform */
+    const int si = prefix_find(ch.pre_group, ch.n_sets, blockIdx.x);        /* uniform */
     const PoseJob& job = ch.jobs[si];
     const uint16_t* const cells = job.cells;
     const int rows = job.rows, cols = job.cols, pitch = job.pitch, n_points = job.n_points;
@@ -143,7 +122,7 @@ __global__ __launch_bounds__(kPoseBlock) void k_pose_score(PoseChunk ch)
         p_y[tid] = p[1];
         p_c[tid] = cos(th);
         p_s[tid] = sin(th);
-        p_e[tid] = 2.4e-15 + 4e-16 * (fabs(th) + job.ang_max);
+        p_e[tid] = addition_trig_err(fabs(th) + job.ang_max);
         acc_s[tid] = acc_k[tid] = acc_u[tid] = 0u;
     }
     for (int tile0 = 0; tile0 < n_points; tile0 += kPoseTile) {
@@ -166,9 +145,9 @@ __global__ __launch_bounds__(kPoseBlock) void k_pose_score(PoseChunk ch)
                 const double hy = y + r * (st * ca + ct * sa);
                 const double qx = (hx - off_x) * inv_res, qy = (hy - off_y) * inv_res;
                 const double fx = floor(qx), fy = floor(qy);
-                const double mx = 64.0 * pose_err_bound(r, hx, off_x, qx, inv_res, trig_err);
-                const double my = 64.0 * pose_err_bound(r, hy, off_y, qy, inv_res, trig_err);
-                uncertain |= !(qx - fx > mx && qx - fx < 1.0 - mx && qy - fy > my && qy - fy < 1.0 - my);
+                const double mx = kCertSafety * proj_err_bound_recip(r, hx, off_x, inv_res, qx, trig_err);
+                const double my = kCertSafety * proj_err_bound_recip(r, hy, off_y, inv_res, qy, trig_err);
+                uncertain |= !(off_cell_edge(qx - fx, mx) && off_cell_edge(qy - fy, my));
                 const int col = (int)fx, row = (int)fy;          /* |q| < 2^30 + 1: the call's check */
                 if ((unsigned)col < (unsigned)cols && (unsigned)row < (unsigned)rows) {
                     const uint32_t v = cells[(size_t)row * pitch + col];

@@ -56,21 +56,21 @@ bool ray_frame(const csm_geometry* geom, const csm_scan* scan, const double pose
         !(std::fabs((S[1] - geom->offset_y) / res) <= kRayMaxCells) || !(p->usable_range_max / res <= kRayMaxCells))
         return false;
     const double scaled_res = res / p->subpixel_scale;
-    s[0] = static_cast<int>(std::floor((S[0] - geom->offset_x) / scaled_res));
-    s[1] = static_cast<int>(std::floor((S[1] - geom->offset_y) / scaled_res));
+    s[0] = cell_index(S[0], geom->offset_x, scaled_res);
+    s[1] = cell_index(S[1], geom->offset_y, scaled_res);
     return true;
 }
 
-/* ScanData::HitPoint (inc/sensor/sensor_data.hpp:189-203) with glibc, and its four integers */
+/* ScanData::HitPoint with glibc (host_hit_point, csm_certify.hpp), and its four integers */
 RayRec ray_host_rec(const double S[3], const csm_geometry* geom, double scaled_res, double r, double a)
 {
-    const double hx = S[0] + r * std::cos(S[2] + a);
-    const double hy = S[1] + r * std::sin(S[2] + a);
+    double hx, hy;
+    host_hit_point(S[0], S[1], S[2], r, a, &hx, &hy);
     RayRec rec;
-    rec.ex = static_cast<int>(std::floor((hx - geom->offset_x) / scaled_res));
-    rec.ey = static_cast<int>(std::floor((hy - geom->offset_y) / scaled_res));
-    rec.hx = static_cast<int>(std::floor((hx - geom->offset_x) / geom->resolution));
-    rec.hy = static_cast<int>(std::floor((hy - geom->offset_y) / geom->resolution));
+    rec.ex = cell_index(hx, geom->offset_x, scaled_res);
+    rec.ey = cell_index(hy, geom->offset_y, scaled_res);
+    rec.hx = cell_index(hx, geom->offset_x, geom->resolution);
+    rec.hy = cell_index(hy, geom->offset_y, geom->resolution);
     return rec;
 }
 

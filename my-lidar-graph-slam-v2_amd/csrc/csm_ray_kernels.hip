@@ -3,7 +3,7 @@
  *
  *   k_ray_project  one thread per beam of a chunk of queries: the hit point with the device's sin / cos,
  *                  its four integers (sub-pixel end, hit cell) and the map builder's certificate
- *                  (map_certified, csm_map.hpp) at both resolutions on both axes. The frame is fixed here
+ *                  (certified, csm_certify.hpp) at both resolutions on both axes. The frame is fixed here
  *                  (no resize follows), so the certificate speaks about exactly the integers stored. A
  *                  beam that is not certified is listed for the host.
  *   k_ray_patch    the listed beams' records as glibc gives them, scattered into place.
@@ -67,26 +67,12 @@ enum RayCounter {
 };
 constexpr int kRayRecordBytes = 80, kRayMaxDepthAt = 72;
 
-/* last q with pre[q] <= i (pre[0] = 0, pre[n] > i) */
-__device__ __forceinline__ int ray_find(const uint32_t* pre, int n, uint32_t i)
-{
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pre[mid] <= i)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void k_ray_project(RayChunk ch)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= ch.n_beams)
         return;
-    const int qi = ray_find(ch.pre_beam, ch.n_queries, (uint32_t)b);
+    const int qi = prefix_find(ch.pre_beam, ch.n_queries, (uint32_t)b);
     const RayQuery& q = ch.queries[qi];
     const int i = b - (int)ch.pre_beam[qi];
     const double r = ch.scans[q.ranges_at + i];
@@ -99,8 +85,8 @@ __global__ __launch_bounds__(256) void k_ray_project(RayChunk ch)
         rec.ey = cell_index(hy, q.off_y, q.scaled_res);
         rec.hx = cell_index(hx, q.off_x, q.res);
         rec.hy = cell_index(hy, q.off_y, q.res);
-        const bool sure = map_certified(r, hx, q.off_x, q.res) && map_certified(r, hy, q.off_y, q.res) &&
-                          map_certified(r, hx, q.off_x, q.scaled_res) && map_certified(r, hy, q.off_y, q.scaled_res);
+        const bool sure = certified(r, hx, q.off_x, q.res) && certified(r, hy, q.off_y, q.res) &&
+                          certified(r, hx, q.off_x, q.scaled_res) && certified(r, hy, q.off_y, q.scaled_res);
         if (!sure) {
             const uint32_t pos = atomicAdd(ch.unc, 1u);
             if (pos < ch.unc_cap)
@@ -133,7 +119,7 @@ __global__ __launch_bounds__(256) void k_ray_walk(RayChunk ch)
         depth_max = 0;
     __syncthreads();
 
-    const int qi = ray_find(ch.pre_group, ch.n_queries, blockIdx.x);     /* uniform */
+    const int qi = prefix_find(ch.pre_group, ch.n_queries, blockIdx.x);     /* uniform */
     const RayQuery& q = ch.queries[qi];
     const int first = ((int)blockIdx.x - (int)ch.pre_group[qi]) * kRayGroup;
     const int beam0 = (int)ch.pre_beam[qi];

@@ -1,7 +1,9 @@
 /* csm_score_common.hpp -- device functions shared by the scoring kernels of
  * csm_kernels.hip and csm_joint_kernels.hip (separate translation units of libcsm_hip.so):
  * the workgroup epilogue (eligibility, bound check, wave64 arg-max), the hand-issued LDS
- * reads, the flush bookkeeping of the packed accumulators and the XCD-aware block order. */
+ * reads, the flush bookkeeping of the packed accumulators and the XCD-aware block order; and what
+ * the other kernel units share with them: wave_sum, prefix_find and, through csm_certify.hpp, the
+ * projection certificate. */
 #ifndef CSM_SCORE_COMMON_HPP
 #define CSM_SCORE_COMMON_HPP
 
@@ -9,6 +11,7 @@
 #include <stdint.h>
 
 #include "csm_device.hpp"
+#include "csm_certify.hpp"
 #include "../../include/csm_hip.h"
 
 namespace csm {
@@ -66,6 +69,30 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
     const uint32_t lo = __shfl_xor((uint32_t)v, m, 64);
     const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
     return ((unsigned long long)hi << 32) | lo;
+}
+
+/* Sum over the wave's 64 lanes, every lane gets it: the xor butterfly 32 -> 1. */
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+        v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+/* last s with pre[s] <= i (pre[0] = 0, pre[n] > i): which query / map / set of a batch launch a beam or a
+ * workgroup belongs to, from the prefix table of their counts */
+__device__ __forceinline__ int prefix_find(const uint32_t* pre, int n, uint32_t i)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pre[mid] <= i)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
 }
 
 /* Shared tail of the scoring kernels: dumps, tile-split accumulation,
@@ -318,23 +345,6 @@ __device__ __forceinline__ void xcd_block(int xcd_map, int& bx, int& by, int& bz
     bx = (int)(part - (uint32_t)by * gridDim.x);
 }
 
-
-/* PositionToIndex on device, IEEE double, no contraction: bit-identical to
- * src/grid_map_new/grid_map_geometry.cpp:113-122 */
-__device__ __forceinline__ int cell_index(double pos, double off, double res)
-{
-    return (int)floor((pos - off) / res);
-}
-
-/* Bound on |q_host - q_device| for q = (sensor + r*trig - off) / res, in cells.
- * `trig_err`: absolute error of the device's cosine / sine against the host's
- * cos(arg) / sin(arg) (see proj_body); then one rounding per arithmetic step on
- * either side; the caller multiplies by a safety factor. */
-__device__ __forceinline__ double proj_err_bound(double r, double hit, double off, double res,
-                                                 double q, double trig_err)
-{
-    return (fabs(r) * trig_err + (fabs(hit) + fabs(off)) * 4e-16) / res + fabs(q) * 4e-16;
-}
 
 } /* namespace csm */
 #endif

@@ -4,6 +4,7 @@
  * only names visible outside: csm_score_window*, csm_correlative_match (query block, graph cache,
  * uncertified projection entries), csm_grid_search_match, csm_project_scan. */
 #include "csm_matchers.hpp"
+#include "csm_certify.hpp"
 
 namespace {
 
@@ -759,10 +760,10 @@ int patch_uncertified(csm_ctx* ctx, const csm_geometry* geom, const csm_scan* sc
             const int t = (int)(idx / (uint32_t)q.n) - out->win_theta;
             const int i = (int)(idx % (uint32_t)q.n);
             const double theta = out->sensor_pose[2] + out->step_theta * t;
-            const double hx = out->sensor_pose[0] + scan->ranges[i] * std::cos(theta + scan->angles[i]);
-            const double hy = out->sensor_pose[1] + scan->ranges[i] * std::sin(theta + scan->angles[i]);
-            const int32_t c = static_cast<int>(std::floor((hx - geom->offset_x) / geom->resolution));
-            const int32_t r = static_cast<int>(std::floor((hy - geom->offset_y) / geom->resolution));
+            double hx, hy;
+            host_hit_point(out->sensor_pose[0], out->sensor_pose[1], theta, scan->ranges[i], scan->angles[i], &hx, &hy);
+            const int32_t c = cell_index(hx, geom->offset_x, geom->resolution);
+            const int32_t r = cell_index(hy, geom->offset_y, geom->resolution);
             if (c != col[idx] || r != row[idx]) {
                 col[idx] = c;
                 row[idx] = r;
@@ -1006,10 +1007,8 @@ int csm_grid_search_match(csm_ctx* ctx, uint64_t map_id, const csm_geometry* geo
         double* rc = prod.data();
         double* rs = rc + (size_t)nt * n;
         for (int k = 0; k < nt; ++k)
-            for (int i = 0; i < n; ++i) {
-                rc[(size_t)k * n + i] = scan->ranges[i] * std::cos(th[k] + scan->angles[i]);
-                rs[(size_t)k * n + i] = scan->ranges[i] * std::sin(th[k] + scan->angles[i]);
-            }
+            for (int i = 0; i < n; ++i)
+                host_hit_products(th[k], scan->ranges[i], scan->angles[i], &rc[(size_t)k * n + i], &rs[(size_t)k * n + i]);
         int rc_ = 0;
         const size_t words = (size_t)nx + ny + prod.size();
         if ((rc_ = ensure(ctx, ctx->ex_coarse, words * 8 + 64))) return rc_;

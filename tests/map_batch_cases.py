@@ -116,8 +116,8 @@ def edge_beams(case, subpixel=100):
     """Usable beams of the case whose hit point, computed as the builder's host path computes it, lies
     on a cell edge of the map's frame before the call (at the cell or the sub-pixel resolution) or
     closer to one than 1.4e-11 / resolution cells. The device certifies a beam only if it stays farther
-    from the edge than its margin, which is never below 64 * 2.3e-16 * 1e3 / resolution (csm_map.hpp,
-    map_certified): these beams it can never certify. cos(pi / 2) = 6e-17 puts a beam there as surely
+    from the edge than its margin, which is never below 64 * 2.3e-16 * 1e3 / resolution (csm_certify.hpp,
+    direct_margin): these beams it can never certify. cos(pi / 2) = 6e-17 puts a beam there as surely
     as sin(0) = 0 does."""
     shape, mp = case["shape"], case["map_pose"]
     count = 0

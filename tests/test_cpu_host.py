@@ -78,6 +78,38 @@ def test_projection_matches_oracle_bit_for_bit(oracle):
     assert np.array_equal(rc[wt], case["ranges"] * np.cos(sensor[2] + case["angles"]))
 
 
+@pytest.mark.parametrize("name", ["aligned", "far"])
+def test_host_hit_point_and_index_where_the_device_hands_over(oracle, name):
+    """The frames of tests/certificate_cases.py in which the certificate lists entries (hit points on cell
+    edges) or has to scale (offsets of 1e3 m, headings of 1e2 rad): what the host recomputes there
+    (host_hit_point + cell_index, csrc/csm_certify.hpp) through its three users, against the oracle's
+    projection, the ray check's definition and the greedy literal."""
+    import certificate_cases as CC
+    import greedy_literal as GL
+    import ray_check_reference as R
+    f = CC.frame(name)
+    grid, geom, angles, ranges = f["grid"], f["geom"], f["angles"], f["ranges"]
+    sensor = tuple(api.host_compound(f["pose"], f["rel_pose"]))
+    _, _, st = api.host_search_step(geom[0], ranges)
+    wt = CC.WIN_THETA
+    col, row, rc, rs = api.host_project(geom, sensor, st, wt, angles, ranges, True)
+    for t in range(-wt, wt + 1):
+        theta = sensor[2] + st * t
+        c, r = oracle.project(geom, (sensor[0], sensor[1], theta), angles, ranges)
+        assert np.array_equal(col[t + wt], c) and np.array_equal(row[t + wt], r)
+        assert rc[t + wt].tolist() == [r_ * math.cos(theta + a) for a, r_ in zip(angles.tolist(), ranges.tolist())]
+        assert rs[t + wt].tolist() == [r_ * math.sin(theta + a) for a, r_ in zip(angles.tolist(), ranges.tolist())]
+    got, words = api.host_ray_check(grid, geom, angles, ranges, f["rel_pose"], f["pose"], per_beam=True, **R.PARAMS)
+    want, want_words = R.ray_check(grid, geom, angles, ranges, f["rel_pose"], f["pose"], R.params())
+    assert R.strip(got) == want and np.array_equal(words, want_words)
+    assert want["walked"] == angles.size              # the whole scan is on the map, far frame included
+    prm = dict(GL.DEFAULT_GREEDY)
+    cost, cov = api.host_greedy_cost(grid, geom, angles, ranges, sensor, prm, covariance=True)
+    lit = GL.Greedy(**prm)
+    assert cost == lit.cost(grid, geom, angles, ranges, sensor)
+    assert np.array_equal(cov, lit.covariance(grid, geom, angles, ranges, sensor), equal_nan=True)
+
+
 def test_host_map_resize_matches_oracle():
     """csm_host_map_resize (GridMap::Resize / Expand on index boxes) against the
     CPU restatement, over frames with negative indices and odd block sizes."""
