@@ -10,6 +10,7 @@
 
 #include "csm_posegraph_kernels.hip"
 
+#include <optional>
 #include <unordered_map>
 
 namespace {
@@ -214,20 +215,21 @@ void pg_job_structure(const PgGraph& G, const csm_pose_graph_lm_params& p, doubl
     J.lambda = lambda;
 }
 
-/* the host job reads the graph's own lists */
-void pg_host_lists(const PgGraph& G, PgJob& J)
+/* local_poses, then scan_poses: the node poses as one vector, and back into the caller's two arrays */
+std::vector<double> pg_join_poses(const double* local_poses, int n_local, const double* scan_poses, int n_scan)
 {
-    J.rel = G.rel.data();
-    J.info = G.info.data();
-    J.enode = G.enode.data();
-    J.is_loop = G.is_loop.data();
-    J.node_ptr = G.node_ptr.data();
-    J.node_edges = G.node_edges.data();
-    J.cross_ptr = G.cross_ptr.data();
-    J.cross_edges = G.cross_edges.data();
-    J.row_ptr = G.row_ptr.data();
-    J.row_col = G.row_col.data();
-    J.row_ent = G.row_ent.data();
+    std::vector<double> pose(3 * ((size_t)n_local + n_scan));
+    std::memcpy(pose.data(), local_poses, 24 * (size_t)n_local);
+    if (n_scan)
+        std::memcpy(pose.data() + 3 * (size_t)n_local, scan_poses, 24 * (size_t)n_scan);
+    return pose;
+}
+
+void pg_split_poses(const double* pose, double* local_poses, int n_local, double* scan_poses, int n_scan)
+{
+    std::memcpy(local_poses, pose, 24 * (size_t)n_local);
+    if (n_scan)
+        std::memcpy(scan_poses, pose + 3 * (size_t)n_local, 24 * (size_t)n_scan);
 }
 
 /* step 2 on the host: the stored blocks of S into the dense row-major matrix (3 n_local square) */
@@ -263,25 +265,126 @@ void pg_host_ldl(std::vector<double>& S, int ns, std::vector<double>& wrow)
     }
 }
 
-/* Optimize, statement by statement and in sequence: the reference the device is held to */
-void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vector<double>& pose, double& lambda,
-                 csm_pose_graph_lm_info* info, csm_pose_graph_lm_step* trace)
-{
-    const int n = G.n_vars;
-    const bool schur = p.solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY;
-    std::vector<double> ev((size_t)kPgEdgeVals * G.n_edges), bv(9 * ((size_t)G.n_nodes + G.n_cross));
-    std::vector<double> b(n), invd(n), x(n), r(n), z(n), pv(n), ap(n);
+/* The work set of the host restatements: the vectors of one linearization (and of the direct solver), and a job
+ * bound to them and to the graph's own lists. */
+struct PgHostWork {
+    const PgGraph& G;
     PgJob J {};
-    pg_job_structure(G, p, lambda, J);
-    J.pose = pose.data();
-    pg_host_lists(G, J);
-    J.ev = ev.data();
-    J.bv = bv.data();
+    std::vector<double> pose, ev, bv, b, invd, x;
+    std::vector<double> S, g, w, wrow;            /* the direct solver's: dense S (3 n_local square), g, W, a row of L d */
+
+    PgHostWork(const PgGraph& graph, const csm_pose_graph_lm_params& p, double lambda, std::vector<double> poses)
+        : G(graph), pose(std::move(poses)), ev((size_t)kPgEdgeVals * G.n_edges),
+          bv(9 * ((size_t)G.n_nodes + G.n_cross)), b(G.n_vars), invd(G.n_vars), x(G.n_vars)
+    {
+        if (p.solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY) {
+            const size_t ns = 3 * (size_t)G.n_local;
+            S.resize(ns * ns);
+            g.resize(3 * (size_t)(G.n_nodes - G.n_local));
+            w.resize(9 * (size_t)G.n_cross);
+            wrow.resize(ns);
+        }
+        pg_job_structure(G, p, lambda, J);
+        J.pose = pose.data();
+        J.rel = G.rel.data();
+        J.info = G.info.data();
+        J.enode = G.enode.data();
+        J.is_loop = G.is_loop.data();
+        J.node_ptr = G.node_ptr.data();
+        J.node_edges = G.node_edges.data();
+        J.cross_ptr = G.cross_ptr.data();
+        J.cross_edges = G.cross_edges.data();
+        J.row_ptr = G.row_ptr.data();
+        J.row_col = G.row_col.data();
+        J.row_ent = G.row_ent.data();
+        J.ev = ev.data();
+        J.bv = bv.data();
+        J.b = b.data();
+        J.invd = invd.data();
+        J.x = x.data();
+    }
+
+    /* H and b at the current poses: per-edge values, the nodes' blocks, the cross blocks */
+    void linearize(double lambda)
+    {
+        for (int e = 0; e < G.n_edges; ++e)
+            pg_edge_values_at(J, e);
+        for (int k = 0; k < G.n_nodes; ++k)
+            pg_assemble_node(J, k, lambda);
+        for (int u = 0; u < G.n_cross; ++u)
+            pg_assemble_cross(J, u);
+    }
+
+    /* steps 1 - 3: the scan nodes eliminated, S put together and factored in place. The LM step eliminates
+     * every scan node: with lambda on its diagonal a node without edges has D_t = lambda I, and the back
+     * substitution reads its g_t = 0. The marginals linearize at lambda = 0, where that D_t is 0 and its
+     * factor 0 / 0; nothing there reads g_t (pg_cov_plan refuses a pair that names such a node), so they
+     * pass edgeless = false and skip it. */
+    void factor_schur(bool edgeless)
+    {
+        for (int t = G.n_local; t < G.n_nodes; ++t)
+            if (edgeless || G.node_ptr[t] != G.node_ptr[t + 1])
+                pg_eliminate_scan(J, g.data(), w.data(), t);
+        pg_host_schur_matrix(G, J, w.data(), S);
+        pg_host_ldl(S, 3 * G.n_local, wrow);
+    }
+};
+
+/* info zeroed, when the caller wants one */
+template <class T>
+T* pg_cleared(T* info)
+{
+    if (info)
+        std::memset(info, 0, sizeof(*info));
+    return info;
+}
+
+/* PgJob::out, as the kernels and pg_host_run write it, into the caller's lambda, info and trace. False, and
+ * nothing written, when its step count is not in 1 .. iterations_max. */
+bool pg_report(const double* out, int iterations_max, double* lambda, csm_pose_graph_lm_info* info,
+               csm_pose_graph_lm_step* trace)
+{
+    const int steps = (int)out[0];
+    if (steps < 1 || steps > iterations_max)
+        return false;
+    *lambda = out[3];
+    int64_t cg_total = 0;
+    for (int s = 0; s < steps; ++s) {
+        const double* t = out + 4 + 5 * (size_t)s;
+        cg_total += (int64_t)t[4];                /* a count: exact in a double */
+        if (trace) {
+            std::memset(&trace[s], 0, sizeof(trace[s]));
+            trace[s].total_error = t[0];
+            trace[s].lambda = t[1];
+            trace[s].rhs_norm2 = t[2];
+            trace[s].residual_norm2 = t[3];
+            trace[s].cg_iterations = (int32_t)t[4];
+        }
+    }
+    if (pg_cleared(info)) {
+        info->steps = steps;
+        info->cg_iterations = cg_total;
+        info->initial_error = out[1];
+        info->final_error = out[2];
+        info->final_lambda = out[3];
+    }
+    return true;
+}
+
+/* Optimize, statement by statement and in sequence: the reference the device is held to. Leaves the poses in
+ * W.pose and the report in out, laid out as PgJob::out. */
+void pg_host_run(PgHostWork& W, const csm_pose_graph_lm_params& p, double lambda, double* out)
+{
+    const PgGraph& G = W.G;
+    const PgJob& J = W.J;
+    const int n = G.n_vars, ns = 3 * G.n_local;
+    const bool schur = p.solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY;
+    std::vector<double>&pose = W.pose, &b = W.b, &invd = W.invd, &x = W.x, &S = W.S;
+    std::vector<double> r(n), z(n), pv(n), ap(n);
     auto total_error = [&]() {
         double t = 0.0;
         for (int e = 0; e < G.n_edges; ++e)
-            t += pg_edge_loss(&pose[3 * (size_t)G.enode[2 * e]], &pose[3 * (size_t)G.enode[2 * e + 1]],
-                              &G.rel[3 * (size_t)e], &G.info[9 * (size_t)e], p.loss_type, p.loss_scale);
+            t += pg_edge_loss_at(J, e);
         return t;
     };
     auto dot = [n](const std::vector<double>& a, const std::vector<double>& c) {
@@ -290,8 +393,6 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
             s += a[i] * c[i];
         return s;
     };
-    J.b = b.data();
-    J.invd = invd.data();
     /* conjugate_gradient with x0 = 0: residual = b. Returns |r|^2 and the iteration count. */
     auto solve_cg = [&](double rhs2, int& cg) {
         std::fill(x.begin(), x.end(), 0.0);
@@ -330,21 +431,10 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
     };
     /* block elimination of the scan nodes, dense LDL^T of the Schur complement (steps 1 - 5 of
      * DESIGN.md 4e, "direct solver"). Returns the true |b - H x|^2. */
-    const int ns = 3 * G.n_local;
-    std::vector<double> S, g, w, wrow;
-    if (schur) {
-        S.resize((size_t)ns * ns);
-        g.resize(3 * (size_t)(G.n_nodes - G.n_local));
-        w.resize(9 * (size_t)G.n_cross);
-        wrow.resize(ns);
-    }
     auto solve_schur = [&]() {
-        for (int t = G.n_local; t < G.n_nodes; ++t)
-            pg_eliminate_scan(J, g.data(), w.data(), t);
-        pg_host_schur_matrix(G, J, w.data(), S);
+        W.factor_schur(true);
         for (int a = 0; a < ns; ++a)
-            x[a] = pg_schur_rhs(J, g.data(), a / 3, a % 3);
-        pg_host_ldl(S, ns, wrow);
+            x[a] = pg_schur_rhs(J, W.g.data(), a / 3, a % 3);
         for (int i = 0; i < ns; ++i) {
             double v = x[i];
             for (int k = 0; k < i; ++k)
@@ -360,7 +450,7 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
             x[i] = v;
         }
         for (int t = G.n_local; t < G.n_nodes; ++t)
-            pg_back_scan(J, g.data(), w.data(), x.data(), t);
+            pg_back_scan(J, W.g.data(), W.w.data(), x.data(), t);
         double r2 = 0.0;
         for (int i = 0; i < n; ++i) {
             const double ri = b[i] - pg_row_times(J, i, x.data());
@@ -369,47 +459,30 @@ void pg_host_run(const PgGraph& G, const csm_pose_graph_lm_params& p, std::vecto
         return r2;
     };
     double prev = DBL_MAX, total = DBL_MAX;
-    const double initial = total_error();
+    out[1] = total_error();
     int steps = 0;
-    int64_t cg_total = 0;
     for (;;) {
-        for (int e = 0; e < G.n_edges; ++e)
-            pg_edge_values(&pose[3 * (size_t)G.enode[2 * e]], &pose[3 * (size_t)G.enode[2 * e + 1]],
-                           &G.rel[3 * (size_t)e], &G.info[9 * (size_t)e], G.is_loop[e], p.loss_type, p.loss_scale,
-                           &ev[(size_t)kPgEdgeVals * e]);
-        for (int k = 0; k < G.n_nodes; ++k)
-            pg_assemble_node(J, k, lambda);
-        for (int u = 0; u < G.n_cross; ++u)
-            pg_assemble_cross(J, u);
+        W.linearize(lambda);
         const double rhs2 = dot(b, b);
         int cg = 0;
         const double r2 = schur ? solve_schur() : solve_cg(rhs2, cg);
         for (int i = 0; i < n; ++i)
             pose[i] += x[i];
         total = total_error();
-        if (trace) {
-            csm_pose_graph_lm_step& s = trace[steps];
-            std::memset(&s, 0, sizeof(s));
-            s.total_error = total;
-            s.lambda = lambda;
-            s.rhs_norm2 = rhs2;
-            s.residual_norm2 = r2;
-            s.cg_iterations = cg;
-        }
-        cg_total += cg;
+        double* o = out + 4 + 5 * (size_t)steps;
+        o[0] = total;
+        o[1] = lambda;
+        o[2] = rhs2;
+        o[3] = r2;
+        o[4] = (double)cg;
         if (++steps >= p.iterations_max || std::fabs(prev - total) < p.error_tolerance)
             break;
         lambda = (total < prev) ? lambda * 0.5 : lambda * 2.0;
         prev = total;
     }
-    if (info) {
-        std::memset(info, 0, sizeof(*info));
-        info->steps = steps;
-        info->cg_iterations = cg_total;
-        info->initial_error = initial;
-        info->final_error = total;
-        info->final_lambda = lambda;
-    }
+    out[0] = (double)steps;
+    out[2] = total;
+    out[3] = lambda;
 }
 
 /* One launch of a chain on the context's stream. A chain keeps the first code that is not 0 in `e` and
@@ -424,9 +497,28 @@ void pg_launch(csm_ctx* ctx, int& e, void (*kernel)(P...), dim3 grid, dim3 block
 dim3 pg_over(int64_t count) { return dim3((unsigned)((count + kPgsBlock - 1) / kPgsBlock)); }
 dim3 pg_strided(int64_t cells) { return dim3((unsigned)std::min<int64_t>((cells + kPgsBlock - 1) / kPgsBlock, 16384)); }
 
-/* the blocked LDL^T of S in place: per panel its diagonal tile, then the panel below it and the trailing update */
-void pg_ldl_launches(csm_ctx* ctx, int& e, const PgSchurJob& Q)
+/* the head of a step's chain (steps 0 and 1): the per-edge values, the blocks of H with b, the scan nodes eliminated */
+void pg_linearize_launches(csm_ctx* ctx, int& e, const PgSchurJob& Q)
 {
+    const PgJob& J = Q.J;
+    const dim3 blk(kPgsBlock);
+    if (J.n_edges)
+        pg_launch(ctx, e, k_pgs_edges, pg_over(J.n_edges), blk, Q);
+    pg_launch(ctx, e, k_pgs_assemble, pg_over((int64_t)J.n_nodes + J.n_cross), blk, Q);
+    if (J.n_nodes - J.n_local)
+        pg_launch(ctx, e, k_pgs_eliminate, pg_over(J.n_nodes - J.n_local), blk, Q);
+}
+
+/* the blocked path's steps 2 and 3: S and c from the ordered lists, then the LDL^T of S in place, per panel its
+ * diagonal tile, the panel below it and the trailing update. ldl_timer: a timer around the LDL^T alone. */
+void pg_factor_launches(csm_ctx* ctx, int& e, const PgSchurJob& Q, const char* ldl_timer = nullptr)
+{
+    const dim3 blk(kPgsBlock);
+    pg_launch(ctx, e, k_pgs_clear, pg_strided((int64_t)Q.np * Q.np), blk, Q);
+    pg_launch(ctx, e, k_pgs_schur, pg_over(9 * (int64_t)Q.n_sblk + Q.np), blk, Q);
+    std::optional<ScopedTimer> tm;
+    if (ldl_timer)
+        tm.emplace(ctx, ldl_timer);
     const int nt = Q.np / kPgsTile;
     for (int p = 0; p < nt; ++p) {
         pg_launch(ctx, e, k_pgs_ldl_diag, dim3(1), dim3(kPgsBlock), Q, p);
@@ -450,17 +542,11 @@ int pg_schur_chain(csm_ctx* ctx, const PgSchurJob& Q, bool small)
         pg_launch(ctx, e, k_pgs_error, pg_over(J.n_edges), blk, Q);
     pg_launch(ctx, e, k_pgs_decide, dim3(1), blk, Q, 1);
     for (int it = 0; it < J.iterations_max; ++it) {
-        if (J.n_edges)
-            pg_launch(ctx, e, k_pgs_edges, pg_over(J.n_edges), blk, Q);
-        pg_launch(ctx, e, k_pgs_assemble, pg_over((int64_t)J.n_nodes + J.n_cross), blk, Q);
-        if (n_scan)
-            pg_launch(ctx, e, k_pgs_eliminate, pg_over(n_scan), blk, Q);
+        pg_linearize_launches(ctx, e, Q);
         if (small) {
             pg_launch(ctx, e, k_pgs_small, dim3(1), blk, Q);
         } else {
-            pg_launch(ctx, e, k_pgs_clear, pg_strided((int64_t)Q.np * Q.np), blk, Q);
-            pg_launch(ctx, e, k_pgs_schur, pg_over(9 * (int64_t)Q.n_sblk + Q.np), blk, Q);
-            pg_ldl_launches(ctx, e, Q);
+            pg_factor_launches(ctx, e, Q);
             pg_launch(ctx, e, k_pgs_solve, dim3(1), dim3(kPgsSolveBlock), Q);
         }
         if (n_scan)
@@ -475,6 +561,42 @@ int pg_schur_chain(csm_ctx* ctx, const PgSchurJob& Q, bool small)
     return CSM_OK;
 }
 
+/* The layout table of one device buffer: add() carves the next piece (Carve's 256-byte alignment) and notes the
+ * pointer that will name it and, for an uploaded piece, its host source, so an array is stated once. `c.off`
+ * is the size so far. The noted pointers and sources must outlive upload(). */
+struct PgLayout {
+    struct Piece {
+        void* dst;
+        void (*set)(void* dst, uint8_t* at);
+        size_t off, bytes;
+        const void* src;
+    };
+    Carve c;
+    std::vector<Piece> pieces;
+
+    template <class T>
+    void add(T*& dst, size_t bytes, const void* src = nullptr)
+    {
+        pieces.push_back({ &dst, [](void* d, uint8_t* at) { *static_cast<T**>(d) = reinterpret_cast<T*>(at); },
+                           c.take(bytes), bytes, src });
+    }
+
+    /* one pass once `buf` holds c.off bytes: every pointer set, the sources within bytes [from, to) copied
+     * into the stage (zeros between them); then that range uploaded in one copy on the ctx stream */
+    int upload(csm_ctx* ctx, const DevBuf& buf, std::vector<uint8_t>& stage, size_t from, size_t to) const
+    {
+        uint8_t* d = buf.as<uint8_t>();
+        stage.assign(to - from, 0);
+        for (const Piece& p : pieces) {
+            p.set(p.dst, d + p.off);
+            if (p.src && p.bytes)
+                std::memcpy(stage.data() + (p.off - from), p.src, p.bytes);
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(d + from, stage.data(), stage.size(), hipMemcpyHostToDevice, ctx->stream));
+        return CSM_OK;
+    }
+};
+
 /* one device call's set-up: the graph, its lists and the LM state staged and uploaded into pg_buf (on the
  * ctx stream), the work vectors carved behind them, pg_s grown for the blocked direct solver; Q.J alone
  * serves the conjugate-gradient kernel */
@@ -482,103 +604,54 @@ int pg_device_job(csm_ctx* ctx, const PgGraph& G, const double* local_poses, int
                   int n_scan, const csm_pose_graph_lm_params* params, const double* lambda, bool schur, bool small,
                   PgSchurJob& Q)
 {
-    const int n = G.n_vars, E = G.n_edges, NB = G.n_nodes + G.n_cross, R = (int)G.row_col.size();
-    const int n_out = 4 + 5 * params->iterations_max;
-    /* inputs (uploaded): pose, rel, info, then the int lists; work and output after them */
-    Carve c;
-    const size_t o_pose = c.take(8 * (size_t)n), o_rel = c.take(24 * (size_t)E), o_info = c.take(72 * (size_t)E);
-    const size_t o_enode = c.take(8 * (size_t)E), o_loop = c.take(4 * (size_t)E);
-    const size_t o_nptr = c.take(4 * ((size_t)G.n_nodes + 1)), o_nedge = c.take(8 * (size_t)E);
-    const size_t o_cptr = c.take(4 * ((size_t)G.n_cross + 1)), o_cedge = c.take(4 * (size_t)E);
-    const size_t o_rptr = c.take(4 * ((size_t)G.n_nodes + 1)), o_rcol = c.take(4 * (size_t)R),
-                 o_rent = c.take(4 * (size_t)R);
-    /* the direct solver's lists and the LM state it keeps on the device */
-    const size_t o_sbrc = c.take(schur ? 8 * (size_t)G.n_sblk : 0), o_sbptr = c.take(schur ? 4 * ((size_t)G.n_sblk + 1) : 0),
-                 o_sbpair = c.take(schur ? 4 * G.sb_pair.size() : 0), o_state = c.take(schur ? sizeof(PgState) : 0);
-    const size_t up_bytes = c.off;
-    const size_t o_ev = c.take(8 * (size_t)kPgEdgeVals * E), o_bv = c.take(72 * (size_t)NB);
-    size_t o_vec[7];
-    for (size_t& o : o_vec)
-        o = c.take(8 * (size_t)n);
-    const size_t o_out = c.take(8 * (size_t)n_out);
-    const int np = pg_schur_padded(n_local), nb_vars = ceil_div(n, kPgsBlock), nb_edges = ceil_div(E, kPgsBlock);
-    const size_t o_g = c.take(schur ? 24 * (size_t)n_scan : 0), o_w = c.take(schur ? 72 * (size_t)G.n_cross : 0),
-                 o_y = c.take(schur ? 8 * (size_t)np : 0), o_wp = c.take(schur && !small ? 8 * (size_t)np * kPgsTile : 0),
-                 o_part = c.take(schur ? 8 * (2 * (size_t)nb_vars + nb_edges) : 0);
-    int rc;
-    if ((rc = ensure(ctx, ctx->pg_buf, c.off)))
-        return rc;
-    if (schur && !small && (rc = grow(ctx, ctx->pg_s, 8 * (size_t)np * np, 8 * (size_t)np * np, false)))
-        return rc;
-    std::vector<uint8_t>& st = ctx->pg_stage;
-    st.assign(up_bytes, 0);
-    auto put = [&](size_t off, const void* src, size_t bytes) {
-        if (bytes)
-            std::memcpy(st.data() + off, src, bytes);
-    };
-    put(o_pose, local_poses, 24 * (size_t)n_local);
-    put(o_pose + 24 * (size_t)n_local, scan_poses, 24 * (size_t)n_scan);
-    put(o_rel, G.rel.data(), 24 * (size_t)E);
-    put(o_info, G.info.data(), 72 * (size_t)E);
-    put(o_enode, G.enode.data(), 8 * (size_t)E);
-    put(o_loop, G.is_loop.data(), 4 * (size_t)E);
-    put(o_nptr, G.node_ptr.data(), 4 * ((size_t)G.n_nodes + 1));
-    put(o_nedge, G.node_edges.data(), 8 * (size_t)E);
-    put(o_cptr, G.cross_ptr.data(), 4 * ((size_t)G.n_cross + 1));
-    put(o_cedge, G.cross_edges.data(), 4 * (size_t)E);
-    put(o_rptr, G.row_ptr.data(), 4 * ((size_t)G.n_nodes + 1));
-    put(o_rcol, G.row_col.data(), 4 * (size_t)R);
-    put(o_rent, G.row_ent.data(), 4 * (size_t)R);
-    if (schur) {
-        const PgState st0 = { *lambda, DBL_MAX, DBL_MAX, 0.0, 0, 0 };
-        put(o_sbrc, G.sb_rc.data(), 8 * (size_t)G.n_sblk);
-        put(o_sbptr, G.sb_ptr.data(), 4 * ((size_t)G.n_sblk + 1));
-        put(o_sbpair, G.sb_pair.data(), 4 * G.sb_pair.size());
-        put(o_state, &st0, sizeof(st0));
-    }
-
-    uint8_t* d = reinterpret_cast<uint8_t*>(ctx->pg_buf.p);
-    PgJob J {};
+    const size_t n = G.n_vars, E = G.n_edges, N = G.n_nodes, U = G.n_cross, R = G.row_col.size(), B = G.n_sblk;
+    PgJob& J = Q.J;
     pg_job_structure(G, *params, *lambda, J);
-    J.pose = reinterpret_cast<double*>(d + o_pose);
-    J.rel = reinterpret_cast<const double*>(d + o_rel);
-    J.info = reinterpret_cast<const double*>(d + o_info);
-    J.enode = reinterpret_cast<const int32_t*>(d + o_enode);
-    J.is_loop = reinterpret_cast<const int32_t*>(d + o_loop);
-    J.node_ptr = reinterpret_cast<const int32_t*>(d + o_nptr);
-    J.node_edges = reinterpret_cast<const int32_t*>(d + o_nedge);
-    J.cross_ptr = reinterpret_cast<const int32_t*>(d + o_cptr);
-    J.cross_edges = reinterpret_cast<const int32_t*>(d + o_cedge);
-    J.row_ptr = reinterpret_cast<const int32_t*>(d + o_rptr);
-    J.row_col = reinterpret_cast<const int32_t*>(d + o_rcol);
-    J.row_ent = reinterpret_cast<const int32_t*>(d + o_rent);
-    J.ev = reinterpret_cast<double*>(d + o_ev);
-    J.bv = reinterpret_cast<double*>(d + o_bv);
-    double** vecs[7] = { &J.b, &J.invd, &J.x, &J.r, &J.z, &J.p, &J.ap };
-    for (int v = 0; v < 7; ++v)
-        *vecs[v] = reinterpret_cast<double*>(d + o_vec[v]);
-    J.out = reinterpret_cast<double*>(d + o_out);
-
-    HIP_TRY(ctx, hipMemcpyAsync(d, st.data(), up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    Q.J = J;
     Q.n_s = 3 * n_local;
-    Q.np = np;
+    Q.np = pg_schur_padded(n_local);
     Q.n_sblk = G.n_sblk;
-    Q.nb_vars = nb_vars;
-    Q.nb_edges = nb_edges;
-    if (schur) {
-        Q.sb_rc = reinterpret_cast<const int32_t*>(d + o_sbrc);
-        Q.sb_ptr = reinterpret_cast<const int32_t*>(d + o_sbptr);
-        Q.sb_pair = reinterpret_cast<const int32_t*>(d + o_sbpair);
-        Q.g = reinterpret_cast<double*>(d + o_g);
-        Q.w = reinterpret_cast<double*>(d + o_w);
-        Q.S = small ? nullptr : ctx->pg_s.as<double>();
-        Q.wp = reinterpret_cast<double*>(d + o_wp);
-        Q.y = reinterpret_cast<double*>(d + o_y);
-        Q.part = reinterpret_cast<double*>(d + o_part);
-        Q.st = reinterpret_cast<PgState*>(d + o_state);
-    }
-    return CSM_OK;
+    Q.nb_vars = ceil_div(G.n_vars, kPgsBlock);
+    Q.nb_edges = ceil_div(G.n_edges, kPgsBlock);
+    const size_t np = Q.np;
+    const std::vector<double> pose = pg_join_poses(local_poses, n_local, scan_poses, n_scan);
+    const PgState st0 = { *lambda, DBL_MAX, DBL_MAX, 0.0, 0, 0 };
+    PgLayout lay;
+    /* inputs (uploaded): pose, rel, info, the int lists, then the direct solver's lists and its LM state */
+    lay.add(J.pose, 8 * n, pose.data());
+    lay.add(J.rel, 24 * E, G.rel.data());
+    lay.add(J.info, 72 * E, G.info.data());
+    lay.add(J.enode, 8 * E, G.enode.data());
+    lay.add(J.is_loop, 4 * E, G.is_loop.data());
+    lay.add(J.node_ptr, 4 * (N + 1), G.node_ptr.data());
+    lay.add(J.node_edges, 8 * E, G.node_edges.data());
+    lay.add(J.cross_ptr, 4 * (U + 1), G.cross_ptr.data());
+    lay.add(J.cross_edges, 4 * E, G.cross_edges.data());
+    lay.add(J.row_ptr, 4 * (N + 1), G.row_ptr.data());
+    lay.add(J.row_col, 4 * R, G.row_col.data());
+    lay.add(J.row_ent, 4 * R, G.row_ent.data());
+    lay.add(Q.sb_rc, schur ? 8 * B : 0, G.sb_rc.data());
+    lay.add(Q.sb_ptr, schur ? 4 * (B + 1) : 0, G.sb_ptr.data());
+    lay.add(Q.sb_pair, schur ? 4 * G.sb_pair.size() : 0, G.sb_pair.data());
+    lay.add(Q.st, schur ? sizeof(PgState) : 0, &st0);
+    const size_t up_bytes = lay.c.off;
+    /* work and output */
+    lay.add(J.ev, 8 * (size_t)kPgEdgeVals * E);
+    lay.add(J.bv, 72 * (N + U));
+    for (double** v : { &J.b, &J.invd, &J.x, &J.r, &J.z, &J.p, &J.ap })
+        lay.add(*v, 8 * n);
+    lay.add(J.out, 8 * (4 + 5 * (size_t)params->iterations_max));
+    lay.add(Q.g, schur ? 24 * (size_t)n_scan : 0);
+    lay.add(Q.w, schur ? 72 * U : 0);
+    lay.add(Q.y, schur ? 8 * np : 0);
+    lay.add(Q.wp, schur && !small ? 8 * np * kPgsTile : 0);
+    lay.add(Q.part, schur ? 8 * (2 * (size_t)Q.nb_vars + Q.nb_edges) : 0);
+    int rc;
+    if ((rc = ensure(ctx, ctx->pg_buf, lay.c.off)))
+        return rc;
+    if (schur && !small && (rc = grow(ctx, ctx->pg_s, 8 * np * np, 8 * np * np, false)))
+        return rc;
+    Q.S = schur && !small ? ctx->pg_s.as<double>() : nullptr;
+    return lay.upload(ctx, ctx->pg_buf, ctx->pg_stage, 0, up_bytes);
 }
 
 /* ------------------------------------------------------------------ marginal covariances */
@@ -685,21 +758,11 @@ void pg_cov_record(const double* v, csm_pose_graph_marginal& m)
 int pg_cov_chain(csm_ctx* ctx, const PgCovJob& C, const std::vector<int32_t>& col_node)
 {
     const PgSchurJob& Q = C.Q;
-    const PgJob& J = Q.J;
     const dim3 blk(kPgsBlock);
-    const int n_scan = J.n_nodes - J.n_local, nt = Q.np / kPgsTile, ng = C.ldx / kPgsTile;
+    const int nt = Q.np / kPgsTile, ng = C.ldx / kPgsTile;
     int e = 0;
-    if (J.n_edges)
-        pg_launch(ctx, e, k_pgs_edges, pg_over(J.n_edges), blk, Q);
-    pg_launch(ctx, e, k_pgs_assemble, pg_over((int64_t)J.n_nodes + J.n_cross), blk, Q);
-    if (n_scan)
-        pg_launch(ctx, e, k_pgs_eliminate, pg_over(n_scan), blk, Q);
-    pg_launch(ctx, e, k_pgs_clear, pg_strided((int64_t)Q.np * Q.np), blk, Q);
-    pg_launch(ctx, e, k_pgs_schur, pg_over(9 * (int64_t)Q.n_sblk + Q.np), blk, Q);
-    {
-        ScopedTimer tm(ctx, "pose_graph_marginals_factor");
-        pg_ldl_launches(ctx, e, Q);
-    }
+    pg_linearize_launches(ctx, e, Q);
+    pg_factor_launches(ctx, e, Q, "pose_graph_marginals_factor");
     if (int rc = launched_ok(ctx, e, "pose-graph marginals factor"))
         return rc;
     ScopedTimer tm(ctx, "pose_graph_marginals_solve");
@@ -725,6 +788,16 @@ int pg_cov_chain(csm_ctx* ctx, const PgCovJob& C, const std::vector<int32_t>& co
     return launched_ok(ctx, e, "pose-graph marginals solve");
 }
 
+/* the LDL^T of a 3x3 (pg_ldl3) into f; false when a pivot is not positive and finite */
+bool pg_ldl3_positive(const double* M, double f[6])
+{
+    pg_ldl3(M, f);
+    for (int a = 0; a < 3; ++a)
+        if (!(f[a] > 0.0) || !std::isfinite(f[a]))
+            return false;
+    return true;
+}
+
 } /* namespace */
 
 extern "C" {
@@ -748,14 +821,11 @@ int csm_host_pose_graph_lm(double* local_poses, int32_t n_local, double* scan_po
     pg_build(n_local, n_scan, edges, n_edges, G);
     if (params->solver_type == CSM_PG_SOLVER_SCHUR_CHOLESKY && !pg_build_schur(G))
         return CSM_EINVAL;
-    std::vector<double> pose(G.n_vars);
-    std::memcpy(pose.data(), local_poses, 3 * (size_t)n_local * sizeof(double));
-    if (n_scan)
-        std::memcpy(pose.data() + 3 * (size_t)n_local, scan_poses, 3 * (size_t)n_scan * sizeof(double));
-    pg_host_run(G, *params, pose, *lambda, info, trace);
-    std::memcpy(local_poses, pose.data(), 3 * (size_t)n_local * sizeof(double));
-    if (n_scan)
-        std::memcpy(scan_poses, pose.data() + 3 * (size_t)n_local, 3 * (size_t)n_scan * sizeof(double));
+    PgHostWork W(G, *params, *lambda, pg_join_poses(local_poses, n_local, scan_poses, n_scan));
+    std::vector<double> out(4 + 5 * (size_t)params->iterations_max);
+    pg_host_run(W, *params, *lambda, out.data());
+    pg_split_poses(W.pose.data(), local_poses, n_local, scan_poses, n_scan);
+    pg_report(out.data(), params->iterations_max, lambda, info, trace);
     return CSM_OK;
 }
 
@@ -779,49 +849,20 @@ int csm_pose_graph_lm(csm_ctx* ctx, double* local_poses, int32_t n_local, double
     if ((rc = pg_device_job(ctx, G, local_poses, n_local, scan_poses, n_scan, params, lambda, schur, small, Q)))
         return rc;
     const PgJob& J = Q.J;
-    if (!schur) {
+    {
         ScopedTimer tm(ctx, "pose_graph");
-        if ((rc = launched_ok(ctx, launch(k_pose_graph_lm, dim3(1), dim3(kPgBlock), ctx->stream, J), "pose-graph LM")))
-            return rc;
-    } else {
-        ScopedTimer tm(ctx, "pose_graph");
-        if ((rc = pg_schur_chain(ctx, Q, small)))
+        rc = schur ? pg_schur_chain(ctx, Q, small)
+                   : launched_ok(ctx, launch(k_pose_graph_lm, dim3(1), dim3(kPgBlock), ctx->stream, J), "pose-graph LM");
+        if (rc)
             return rc;
     }
     std::vector<double> res(n + (size_t)n_out);
     HIP_TRY(ctx, hipMemcpyAsync(res.data(), J.pose, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(res.data() + n, J.out, 8 * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-
-    std::memcpy(local_poses, res.data(), 24 * (size_t)n_local);
-    if (n_scan)
-        std::memcpy(scan_poses, res.data() + 3 * (size_t)n_local, 24 * (size_t)n_scan);
-    const double* o = res.data() + n;
-    const int steps = (int)o[0];
-    if (steps < 1 || steps > params->iterations_max)
-        return fail(ctx, CSM_EIO, "csm_pose_graph_lm: the kernel reported %d steps", steps);
-    *lambda = o[3];
-    int64_t cg_total = 0;
-    for (int s = 0; s < steps; ++s) {
-        const double* t = o + 4 + 5 * s;
-        cg_total += (int64_t)t[4];
-        if (trace) {
-            std::memset(&trace[s], 0, sizeof(trace[s]));
-            trace[s].total_error = t[0];
-            trace[s].lambda = t[1];
-            trace[s].rhs_norm2 = t[2];
-            trace[s].residual_norm2 = t[3];
-            trace[s].cg_iterations = (int32_t)t[4];
-        }
-    }
-    if (info) {
-        std::memset(info, 0, sizeof(*info));
-        info->steps = steps;
-        info->cg_iterations = cg_total;
-        info->initial_error = o[1];
-        info->final_error = o[2];
-        info->final_lambda = o[3];
-    }
+    pg_split_poses(res.data(), local_poses, n_local, scan_poses, n_scan);
+    if (!pg_report(res.data() + n, params->iterations_max, lambda, info, trace))
+        return fail(ctx, CSM_EIO, "csm_pose_graph_lm: the kernel reported %d steps", (int)res[n]);
     return CSM_OK;
 }
 
@@ -838,33 +879,12 @@ int csm_host_pose_graph_marginals(const double* local_poses, int32_t n_local, co
     pg_build(n_local, n_scan, edges, n_edges, G);
     if (!pg_build_schur(G) || pg_cov_plan(G, pairs, n_pairs, P))
         return CSM_EINVAL;
-    const int n = G.n_vars, ns = 3 * n_local, nc = 3 * (int)P.col_node.size();
-    std::vector<double> pose(n), ev((size_t)kPgEdgeVals * G.n_edges), bv(9 * ((size_t)G.n_nodes + G.n_cross));
-    std::vector<double> b(n), invd(n), g(3 * (size_t)n_scan), w(9 * (size_t)G.n_cross), wrow(ns);
-    std::vector<double> S((size_t)ns * ns), X((size_t)ns * nc, 0.0);
-    std::memcpy(pose.data(), local_poses, 24 * (size_t)n_local);
-    if (n_scan)
-        std::memcpy(pose.data() + 3 * (size_t)n_local, scan_poses, 24 * (size_t)n_scan);
-    PgJob J {};
-    pg_job_structure(G, pg_cov_params(loss_type, loss_scale), 0.0, J);
-    J.pose = pose.data();
-    pg_host_lists(G, J);
-    J.ev = ev.data();
-    J.bv = bv.data();
-    J.b = b.data();
-    J.invd = invd.data();
-    for (int e = 0; e < G.n_edges; ++e)
-        pg_edge_values(&pose[3 * (size_t)G.enode[2 * e]], &pose[3 * (size_t)G.enode[2 * e + 1]], &G.rel[3 * (size_t)e],
-                       &G.info[9 * (size_t)e], G.is_loop[e], loss_type, loss_scale, &ev[(size_t)kPgEdgeVals * e]);
-    for (int k = 0; k < G.n_nodes; ++k)
-        pg_assemble_node(J, k, 0.0);
-    for (int u = 0; u < G.n_cross; ++u)
-        pg_assemble_cross(J, u);
-    for (int t = n_local; t < G.n_nodes; ++t)
-        if (G.node_ptr[t] != G.node_ptr[t + 1])
-            pg_eliminate_scan(J, g.data(), w.data(), t);
-    pg_host_schur_matrix(G, J, w.data(), S);
-    pg_host_ldl(S, ns, wrow);
+    const int ns = 3 * n_local, nc = 3 * (int)P.col_node.size();
+    PgHostWork W(G, pg_cov_params(loss_type, loss_scale), 0.0, pg_join_poses(local_poses, n_local, scan_poses, n_scan));
+    W.linearize(0.0);
+    W.factor_schur(false);
+    const std::vector<double>& S = W.S;
+    std::vector<double> X((size_t)ns * nc, 0.0);
     /* every column by itself; row k's terms reach the columns whose unit row is k or above it (a prefix) */
     std::vector<int32_t> reach(ns, 0);
     for (int c = 0; c < nc; ++c) {
@@ -897,13 +917,11 @@ int csm_host_pose_graph_marginals(const double* local_poses, int32_t n_local, co
     }
     for (int q = 0; q < n_pairs; ++q) {
         double v[36];
-        pg_marginal_pair(J, w.data(), X.data(), (size_t)nc, P.col_of.data(), P.pairs[2 * q], P.pairs[2 * q + 1], v);
+        pg_marginal_pair(W.J, W.w.data(), X.data(), (size_t)nc, P.col_of.data(), P.pairs[2 * q], P.pairs[2 * q + 1], v);
         pg_cov_record(v, out[q]);
     }
-    if (info) {
-        std::memset(info, 0, sizeof(*info));
+    if (pg_cleared(info))
         info->n_columns = (int32_t)P.col_node.size();
-    }
     return CSM_OK;
 }
 
@@ -935,24 +953,17 @@ int csm_pose_graph_marginals(csm_ctx* ctx, const double* local_poses, int32_t n_
     C.ldx = ceil_div(n_c, kPgcGroup) * kPgsTile;
     C.n_pairs = n_pairs;
     /* X, then the uploaded lists, then the records */
-    Carve c;
-    const size_t o_x = c.take(8 * (size_t)C.Q.np * C.ldx), o_node = c.take(4 * (size_t)n_c),
-                 o_of = c.take(4 * (size_t)n_local), o_pairs = c.take(8 * (size_t)n_pairs), o_lists = c.off,
-                 o_out = c.take(8 * 36 * (size_t)n_pairs);
-    if ((rc = grow(ctx, ctx->pg_cov, c.off, c.off, false)))
+    PgLayout lay;
+    lay.add(C.X, 8 * (size_t)C.Q.np * C.ldx);
+    const size_t o_lists = lay.c.off;
+    lay.add(C.col_node, 4 * (size_t)n_c, P.col_node.data());
+    lay.add(C.col_of, 4 * (size_t)n_local, P.col_of.data());
+    lay.add(C.pairs, 8 * (size_t)n_pairs, P.pairs.data());
+    const size_t o_out = lay.c.off;
+    lay.add(C.out, 8 * 36 * (size_t)n_pairs);
+    if ((rc = grow(ctx, ctx->pg_cov, lay.c.off, lay.c.off, false)) ||
+        (rc = lay.upload(ctx, ctx->pg_cov, ctx->pg_cov_stage, o_lists, o_out)))
         return rc;
-    std::vector<uint8_t>& st = ctx->pg_cov_stage;
-    st.assign(o_lists - o_node, 0);
-    std::memcpy(st.data(), P.col_node.data(), 4 * (size_t)n_c);
-    std::memcpy(st.data() + (o_of - o_node), P.col_of.data(), 4 * (size_t)n_local);
-    std::memcpy(st.data() + (o_pairs - o_node), P.pairs.data(), 8 * (size_t)n_pairs);
-    uint8_t* d = reinterpret_cast<uint8_t*>(ctx->pg_cov.p);
-    C.X = reinterpret_cast<double*>(d + o_x);
-    C.col_node = reinterpret_cast<const int32_t*>(d + o_node);
-    C.col_of = reinterpret_cast<const int32_t*>(d + o_of);
-    C.pairs = reinterpret_cast<const int32_t*>(d + o_pairs);
-    C.out = reinterpret_cast<double*>(d + o_out);
-    HIP_TRY(ctx, hipMemcpyAsync(d + o_node, st.data(), st.size(), hipMemcpyHostToDevice, ctx->stream));
     {
         ScopedTimer tm(ctx, "pose_graph_marginals");
         if ((rc = pg_cov_chain(ctx, C, P.col_node)))
@@ -963,10 +974,8 @@ int csm_pose_graph_marginals(csm_ctx* ctx, const double* local_poses, int32_t n_
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int q = 0; q < n_pairs; ++q)
         pg_cov_record(&res[36 * (size_t)q], out[q]);
-    if (info) {
-        std::memset(info, 0, sizeof(*info));
+    if (pg_cleared(info))
         info->n_columns = n_c;
-    }
     return CSM_OK;
 }
 
@@ -1000,10 +1009,8 @@ int csm_host_loop_gate(const double relative_cov[9], const double match_cov[9], 
     double M[9], f[6], x[3];
     for (int q = 0; q < 9; ++q)
         M[q] = relative_cov[q] + match_cov[q];
-    pg_ldl3(M, f);
-    for (int a = 0; a < 3; ++a)
-        if (!(f[a] > 0.0) || !std::isfinite(f[a]))
-            return CSM_EINVAL;
+    if (!pg_ldl3_positive(M, f))
+        return CSM_EINVAL;
     const double d[3] = { measured[0] - predicted[0], measured[1] - predicted[1],
                           pg_normalize_angle(measured[2] - predicted[2]) };
     pg_ldl3_solve(f, d[0], d[1], d[2], x);
@@ -1016,10 +1023,8 @@ int csm_host_information_from_covariance(const double cov[9], double out[9])
     if (!cov || !out)
         return CSM_EINVAL;
     double f[6];
-    pg_ldl3(cov, f);
-    for (int a = 0; a < 3; ++a)
-        if (!(f[a] > 0.0) || !std::isfinite(f[a]))
-            return CSM_EINVAL;
+    if (!pg_ldl3_positive(cov, f))
+        return CSM_EINVAL;
     for (int j = 0; j < 3; ++j) {
         double x[3];
         pg_ldl3_solve(f, j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0, x);
