@@ -1476,6 +1476,99 @@ int  csm_host_loop_gate(const double relative_cov[9], const double match_cov[9],
  * and finite: CSM_EINVAL. */
 int  csm_host_information_from_covariance(const double cov[9], double out[9]);
 
+/* ---- loop search: the candidate pairs of a pose graph (LoopSearcherNearest::Search,
+ * src/mapping/loop_searcher_nearest.cpp:59-170, per query node and for any number of query nodes) ----
+ *
+ * Inputs. scan_poses[n_scan][3]: global poses, the layout csm_pose_graph_lm takes (theta is not read).
+ * scan_map_index[n_scan]: the local map each scan node belongs to, non-decreasing, in [0, n_maps): a local
+ * map is a contiguous run of nodes. travel[n_scan]: accumulated travel distance at each node, non-decreasing
+ * (csm_host_travel_distances). Nodes [0, n_ref) may be reference nodes. query_index[n_q]: scan node indices,
+ * distinct, in any order; query_travel[n_q]: the travel distance a query's gate is measured from.
+ *
+ * A pair (query q, reference node r) is ELIGIBLE iff
+ *   r < n_ref
+ *   scan_map_index[r] != scan_map_index[q]
+ *   !(query_travel[q] - travel[r] < travel_dist_threshold)
+ *   d2 < T2, with d2 = (rx - qx) * (rx - qx) + (ry - qy) * (ry - qy)          SquaredDistance(refPose, queryPose)
+ *            and  T2 = std::pow(node_dist_threshold, 2.0), computed once on the host.
+ * d2 is f64 with every operation rounded on its own (no fused multiply-add), on the host and on the device:
+ * the subtraction comes first and is the same operation on both, so far frames lose nothing on one side
+ * that the other keeps. travel is non-decreasing and a f64 subtraction is monotone, so the third condition
+ * selects a PREFIX [0, p_q) of the reference nodes: where the reference's loop leaves through `goto Done`.
+ *
+ * Order. The candidates of one query are ordered by (d2 ascending, then r ascending); d2 >= 0, so its bit
+ * pattern orders as an unsigned 64-bit integer. The order is total: no result depends on a launch shape.
+ *
+ * Result per query. one_per_map = 0: the first n_per_query eligible pairs in that order. one_per_map = 1: of
+ * every reference map only its first eligible pair in that order, then the first n_per_query of those (the
+ * nearest reference node of each local map, the nearest maps per query node).
+ *
+ * Output. out[n_q * n_per_query]: query i's records in order in out[i * n_per_query ..], counts[i] of them
+ * used; an unused slot is { query, -1, -1, 0, 0.0 }. info (may be NULL): pairs_evaluated = the sum of the
+ * prefix lengths p_q; pairs_eligible = the sum over queries of their eligible pairs, before one_per_map and
+ * before the cut to n_per_query. Both exact.
+ *
+ * CSM_EINVAL, on the host before any launch: a null pointer (info aside); a non-finite pose coordinate (x, y),
+ * travel value, query_travel value or threshold; travel or scan_map_index decreasing; a map index outside
+ * [0, n_maps); n_scan outside 1..CSM_LOOP_SEARCH_MAX_NODES; n_maps outside 1..CSM_LOOP_SEARCH_MAX_MAPS; n_ref
+ * outside [0, n_scan]; a query index out of range or repeated; n_q < 1; n_per_query outside
+ * 1..CSM_LOOP_SEARCH_MAX_K; one_per_map other than 0 or 1. */
+#define CSM_LOOP_SEARCH_MAX_K      16
+#define CSM_LOOP_SEARCH_MAX_NODES  (1 << 20)
+#define CSM_LOOP_SEARCH_MAX_MAPS   (1 << 16)   /* one bit per map in the workgroup's LDS */
+typedef struct {
+    double  travel_dist_threshold;
+    double  node_dist_threshold;
+    int32_t n_per_query;            /* K: 1..CSM_LOOP_SEARCH_MAX_K */
+    int32_t one_per_map;            /* 0 | 1 */
+} csm_loop_search_params;
+
+typedef struct {
+    int32_t query_scan_index;
+    int32_t ref_scan_index;         /* -1: an unused slot */
+    int32_t ref_map_index;          /* -1: an unused slot */
+    int32_t reserved;               /* 0 */
+    double  dist_sq;                /* d2 */
+} csm_loop_candidate;
+
+typedef struct {
+    int64_t pairs_evaluated;
+    int64_t pairs_eligible;
+} csm_loop_search_info;
+
+/* Host only. out[0] = 0, out[i] = out[i-1] + std::hypot(x[i-1] - x[i], y[i-1] - y[i]): sequential, with
+ * glibc's hypot, as the reference accumulates Distance(prevPose, refPose). It stays on the host: it is n
+ * additions whose order is the result, and the device library's hypot is not glibc's. CSM_EINVAL: a null
+ * pointer or n < 0. */
+int  csm_host_travel_distances(const double* scan_poses, int32_t n, double* out);
+/* Host only: the rule as a sequential restatement. The CPU reference of csm_loop_search. */
+int  csm_host_loop_search(const double* scan_poses, const int32_t* scan_map_index, const double* travel,
+                          int32_t n_scan, int32_t n_maps, int32_t n_ref, const int32_t* query_index,
+                          const double* query_travel, int32_t n_q, const csm_loop_search_params* params,
+                          csm_loop_candidate* out, int32_t* counts, csm_loop_search_info* info);
+/* On the device, on the ctx stream: x, y, map index and travel uploaded as separate arrays with the query
+ * table (28 bytes per node: 280 KB at 10 000 nodes), one workgroup per query (a uniform binary search for
+ * the prefix; one pass over it that lists the eligible pairs in LDS; then one round per record: every lane
+ * keeps the least key above the last selected one -- from the list, or from another pass over the prefix
+ * when a query has more than 1 024 eligible pairs -- a wave reduction and one across the waves; with
+ * one_per_map an LDS bit per map already taken), one read-back. Returns when records and counts are on the
+ * host. Every byte of out, counts and info equals csm_host_loop_search's. Nothing of the graph stays
+ * resident between calls. Timer: "loop_search". */
+int  csm_loop_search(csm_ctx* ctx, const double* scan_poses, const int32_t* scan_map_index, const double* travel,
+                     int32_t n_scan, int32_t n_maps, int32_t n_ref, const int32_t* query_index,
+                     const double* query_travel, int32_t n_q, const csm_loop_search_params* params,
+                     csm_loop_candidate* out, int32_t* counts, csm_loop_search_info* info);
+/* Host only: the first n_total of all used records (the first counts[i] of each query's n_per_query slots),
+ * ordered by (dist_sq, ref_scan_index, query_scan_index), into out[n_total]; *n_out of them. The K globally
+ * nearest pairs are always among the K nearest of their own query, so with one_per_map = 0, n_per_query =
+ * n_total and one query_travel for all queries this is the candidate set of LoopSearcherNearest::Search.
+ * The reference cuts with std::nth_element, which leaves the choice among equal distances at the cut
+ * unspecified; this function specifies it (the order above). CSM_EINVAL: a null pointer, n_q < 1,
+ * n_per_query outside 1..CSM_LOOP_SEARCH_MAX_K, n_total < 0, a count outside [0, n_per_query]. */
+int  csm_host_loop_candidates_nearest(const csm_loop_candidate* cands, const int32_t* counts, int32_t n_q,
+                                      int32_t n_per_query, int32_t n_total, csm_loop_candidate* out,
+                                      int32_t* n_out);
+
 /* ---- measurement hooks (bench.py) ---- */
 /* enable = 1: every kernel launch is bracketed by HIP events on the ctx
  * stream; enable = 2: only the dominant (fine-level) scoring kernel, to keep
@@ -1486,7 +1579,7 @@ int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
  * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select" | "likelihood" |
  * "ray_project" | "ray_walk" | "pose_prep" | "pose_score" | "pose_rescore" | "pose_weights" |
  * "pose_resample" | "pose_graph" | "pose_graph_marginals" |
- * "pose_graph_marginals_factor" | "pose_graph_marginals_solve". */
+ * "pose_graph_marginals_factor" | "pose_graph_marginals_solve" | "loop_search". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);
 int  csm_reset_kernel_timing(csm_ctx* ctx);

@@ -298,6 +298,23 @@ class RayCheckResult(C.Structure):
                 ("max_depth", C.c_int32), ("host_beams", C.c_int32)]
 
 
+LOOP_SEARCH_MAX_K, LOOP_SEARCH_MAX_NODES, LOOP_SEARCH_MAX_MAPS = 16, 1 << 20, 1 << 16
+
+
+class LoopSearchParams(C.Structure):
+    _fields_ = [("travel_dist_threshold", C.c_double), ("node_dist_threshold", C.c_double),
+                ("n_per_query", C.c_int32), ("one_per_map", C.c_int32)]
+
+
+class LoopCandidate(C.Structure):
+    _fields_ = [("query_scan_index", C.c_int32), ("ref_scan_index", C.c_int32), ("ref_map_index", C.c_int32),
+                ("reserved", C.c_int32), ("dist_sq", C.c_double)]
+
+
+class LoopSearchInfo(C.Structure):
+    _fields_ = [("pairs_evaluated", C.c_int64), ("pairs_eligible", C.c_int64)]
+
+
 POSE_UNCERTAIN, POSE_HOST_PROJECTED = 1, 2
 POSE_SET_MAX_POSES = 1 << 18
 
@@ -463,6 +480,15 @@ SIGNATURES = {
     "csm_host_loop_search_ranges": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "csm_host_loop_gate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_double)]),
     "csm_host_information_from_covariance": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "csm_host_travel_distances": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "csm_host_loop_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_int32, _P(LoopSearchParams), C.c_void_p, C.c_void_p,
+                                       _P(LoopSearchInfo)]),
+    "csm_loop_search": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_int32, _P(LoopSearchParams), C.c_void_p, C.c_void_p,
+                                  _P(LoopSearchInfo)]),
+    "csm_host_loop_candidates_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                   _P(C.c_int32)]),
     "csm_shard_bounds": (None, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "csm_group_create": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
     "csm_group_create_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, _P(C.c_void_p)]),

@@ -678,6 +678,79 @@ def host_information_from_covariance(cov):
     return out
 
 
+# csm_loop_candidate as a numpy record: 24 bytes, the struct's layout
+LOOP_CANDIDATE_DTYPE = np.dtype([("query_scan_index", np.int32), ("ref_scan_index", np.int32),
+                                 ("ref_map_index", np.int32), ("reserved", np.int32), ("dist_sq", np.float64)])
+assert LOOP_CANDIDATE_DTYPE.itemsize == C.sizeof(L.LoopCandidate)
+
+
+def host_travel_distances(scan_poses):
+    """csm_host_travel_distances: the accumulated travel distance at each scan node, summed in order with
+    glibc's hypot as LoopSearcherNearest::Search accumulates it."""
+    sp = np.ascontiguousarray(scan_poses, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros(sp.shape[0])
+    rc = L.load().csm_host_travel_distances(_ptr(sp), sp.shape[0], _ptr(out))
+    if rc:
+        raise CsmError(rc, "csm_host_travel_distances")
+    return out
+
+
+def _loop_search_run(fn, head, scan_poses, scan_map_index, travel, query_index, query_travel, n_ref, n_maps,
+                     travel_dist_threshold, node_dist_threshold, n_per_query, one_per_map):
+    sp = np.ascontiguousarray(scan_poses, dtype=np.float64).reshape(-1, 3)
+    mi = np.ascontiguousarray(scan_map_index, dtype=np.int32).reshape(-1)
+    tr = np.ascontiguousarray(travel, dtype=np.float64).reshape(-1)
+    qi = np.ascontiguousarray(query_index, dtype=np.int32).reshape(-1)
+    if mi.size != sp.shape[0] or tr.size != sp.shape[0]:
+        raise CsmError(L.CSM_EINVAL, "loop_search: one map index and one travel value per scan node")
+    if query_travel is None:
+        if qi.size and (qi.min() < 0 or qi.max() >= tr.size):
+            raise CsmError(L.CSM_EINVAL, "loop_search: a query index out of range")
+        qt = np.ascontiguousarray(tr[qi])
+    else:
+        qt = np.ascontiguousarray(np.broadcast_to(np.asarray(query_travel, dtype=np.float64), qi.shape))
+    n_ref = sp.shape[0] if n_ref is None else int(n_ref)
+    n_maps = (int(mi.max()) + 1 if mi.size else 0) if n_maps is None else int(n_maps)
+    k = int(n_per_query)
+    p = L.LoopSearchParams(float(travel_dist_threshold), float(node_dist_threshold), k, int(one_per_map))
+    slots = max(min(k, L.LOOP_SEARCH_MAX_K), 1)
+    out = np.zeros((max(qi.size, 1), slots), LOOP_CANDIDATE_DTYPE)
+    counts = np.zeros(max(qi.size, 1), np.int32)
+    info = L.LoopSearchInfo()
+    rc = fn(*head, _ptr(sp), _ptr(mi), _ptr(tr), sp.shape[0], n_maps, n_ref, _ptr(qi), _ptr(qt), qi.size, C.byref(p),
+            _ptr(out), _ptr(counts), C.byref(info))
+    return rc, out[:qi.size], counts[:qi.size], dict(pairs_evaluated=int(info.pairs_evaluated),
+                                                     pairs_eligible=int(info.pairs_eligible))
+
+
+def host_loop_search(scan_poses, scan_map_index, travel, query_index, query_travel=None, n_ref=None,
+                     travel_dist_threshold=10.0, node_dist_threshold=2.0, n_per_query=2, one_per_map=False,
+                     n_maps=None):
+    """csm_host_loop_search: the sequential restatement of Context.loop_search, same arguments and result."""
+    rc, out, counts, info = _loop_search_run(L.load().csm_host_loop_search, (), scan_poses, scan_map_index, travel,
+                                             query_index, query_travel, n_ref, n_maps, travel_dist_threshold,
+                                             node_dist_threshold, n_per_query, one_per_map)
+    if rc:
+        raise CsmError(rc, "csm_host_loop_search")
+    return out, counts, info
+
+
+def host_loop_candidates_nearest(records, counts, n_total):
+    """csm_host_loop_candidates_nearest: the first n_total of all used records of a loop search, ordered by
+    (dist_sq, ref_scan_index, query_scan_index). records: [n_q, n_per_query] of LOOP_CANDIDATE_DTYPE."""
+    rec = np.ascontiguousarray(records, dtype=LOOP_CANDIDATE_DTYPE)
+    cnt = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if rec.ndim != 2 or rec.shape[0] != cnt.size:
+        raise CsmError(L.CSM_EINVAL, "host_loop_candidates_nearest: records must be [n_q, n_per_query], one count per row")
+    out = np.zeros(max(int(n_total), 1), LOOP_CANDIDATE_DTYPE)
+    n_out = C.c_int32(0)
+    rc = L.load().csm_host_loop_candidates_nearest(_ptr(rec), _ptr(cnt), rec.shape[0], rec.shape[1], int(n_total),
+                                                   _ptr(out), C.byref(n_out))
+    if rc:
+        raise CsmError(rc, "csm_host_loop_candidates_nearest")
+    return out[:n_out.value]
+
+
 class Context:
     """One csm_ctx: owns the device grids, workspaces and a stream."""
 
@@ -1383,6 +1456,21 @@ class Context:
         self._check(rc)
         return recs, info
 
+    def loop_search(self, scan_poses, scan_map_index, travel, query_index, query_travel=None, n_ref=None,
+                    travel_dist_threshold=10.0, node_dist_threshold=2.0, n_per_query=2, one_per_map=False,
+                    n_maps=None):
+        """csm_loop_search: the loop candidates of the query nodes on the device. scan_poses [n, 3];
+        scan_map_index [n] non-decreasing; travel [n] non-decreasing (host_travel_distances); query_index:
+        distinct scan node indices; query_travel: one value or one per query (None: each query's own travel);
+        n_ref (None: n): nodes [0, n_ref) may be reference nodes; n_maps (None: the greatest map index + 1).
+        Returns (records [n_q, n_per_query] of LOOP_CANDIDATE_DTYPE, unused slots with ref_scan_index -1;
+        counts [n_q]; info dict: pairs_evaluated, pairs_eligible)."""
+        rc, out, counts, info = _loop_search_run(self.lib.csm_loop_search, (self._ctx,), scan_poses, scan_map_index,
+                                                 travel, query_index, query_travel, n_ref, n_maps,
+                                                 travel_dist_threshold, node_dist_threshold, n_per_query, one_per_map)
+        self._check(rc)
+        return out, counts, info
+
     def enable_kernel_timing(self, on=True):
         self._check(self.lib.csm_enable_kernel_timing(self._ctx, 1 if on else 0))
 
@@ -1636,3 +1724,64 @@ class PoseGraphOptimizerLMHIP:
         (Context.pose_graph_marginals): one dict per pair."""
         return self.ctx.pose_graph_marginals(local_map_nodes, scan_nodes, edges, pairs, self.params.loss_type,
                                              self.params.loss_scale)[0]
+
+
+def loop_search_graph(scan_poses, local_maps, last_finished_map):
+    """What LoopSearchHint holds, as the arrays a loop search takes. local_maps: (scan_node_min,
+    scan_node_max) of each local map, inclusive, contiguous runs from node 0. Returns (poses of the nodes up
+    to the last finished map's last, map index of each, their travel distances, n_ref = the first node of
+    the last finished map, query_index = its nodes)."""
+    runs = [(int(a), int(b)) for a, b in local_maps][:int(last_finished_map) + 1]
+    if not runs or int(last_finished_map) < 0 or int(last_finished_map) >= len(local_maps):
+        raise CsmError(L.CSM_EINVAL, "loop search: last_finished_map names no local map")
+    if runs[0][0] != 0 or any(b < a for a, b in runs) or any(runs[i + 1][0] != runs[i][1] + 1
+                                                              for i in range(len(runs) - 1)):
+        raise CsmError(L.CSM_EINVAL, "loop search: local maps must be contiguous runs of scan nodes from node 0")
+    sp = np.ascontiguousarray(scan_poses, dtype=np.float64).reshape(-1, 3)
+    n = runs[-1][1] + 1
+    if n > sp.shape[0]:
+        raise CsmError(L.CSM_EINVAL, "loop search: a local map names a scan node that is not given")
+    sp = sp[:n]
+    map_index = np.repeat(np.arange(len(runs), dtype=np.int32), [b - a + 1 for a, b in runs])
+    return sp, map_index, host_travel_distances(sp), runs[-1][0], np.arange(runs[-1][0], n, dtype=np.int32)
+
+
+class LoopSearcherNearestHIP:
+    """Drop-in for LoopSearcherNearest (constructor arguments as its settings group: TravelDistThreshold,
+    NodeDistThreshold, NumOfCandidateNodes). search() returns the reference's candidate set, with the
+    choice among equal distances at the cut specified (host_loop_candidates_nearest). The metric inputs of
+    the last call are in last_metrics (AccumTravelDist, NodeDist per candidate, NumOfCandidateNodes)."""
+
+    def __init__(self, travel_dist_threshold, node_dist_threshold, num_of_candidate_nodes, ctx=None):
+        self.travel_dist_threshold = float(travel_dist_threshold)
+        self.node_dist_threshold = float(node_dist_threshold)
+        self.num_of_candidate_nodes = int(num_of_candidate_nodes)
+        self.ctx = ctx or Context()
+        self.last_metrics = None
+        self.last_info = None
+
+    def search(self, scan_poses, local_maps, accum_travel_dist, last_finished_map):
+        """Search(searchHint): queries are the nodes of the last finished local map, references the nodes
+        of the maps before it, every gate measured from accum_travel_dist. Returns (query scan node,
+        reference scan node, reference local map) triples, nearest first."""
+        sp, map_index, travel, n_ref, queries = loop_search_graph(scan_poses, local_maps, last_finished_map)
+        rec, counts, self.last_info = self.ctx.loop_search(
+            sp, map_index, travel, queries, float(accum_travel_dist), n_ref, self.travel_dist_threshold,
+            self.node_dist_threshold, self.num_of_candidate_nodes, False)
+        kept = host_loop_candidates_nearest(rec, counts, self.num_of_candidate_nodes)
+        self.last_metrics = dict(AccumTravelDist=float(accum_travel_dist), NodeDist=[float(d) for d in kept["dist_sq"]],
+                                 NumOfCandidateNodes=len(kept))
+        return [(int(c["query_scan_index"]), int(c["ref_scan_index"]), int(c["ref_map_index"])) for c in kept]
+
+    def search_per_map(self, scan_poses, local_maps, last_finished_map, query_nodes, n_per_query):
+        """The one_per_map form: per query node the nearest reference node of each local map, the
+        n_per_query nearest maps. Any node up to the last finished map's last may be a reference (the
+        query's own local map never is) and each query's gate is measured from its own travel distance:
+        the offline search of a finished graph. Returns the used (query, ref scan, ref map) triples, query
+        by query in the order given."""
+        sp, map_index, travel, _, _ = loop_search_graph(scan_poses, local_maps, last_finished_map)
+        rec, counts, self.last_info = self.ctx.loop_search(
+            sp, map_index, travel, query_nodes, None, None, self.travel_dist_threshold, self.node_dist_threshold,
+            n_per_query, True, len(local_maps[:int(last_finished_map) + 1]))
+        return [(int(c["query_scan_index"]), int(c["ref_scan_index"]), int(c["ref_map_index"]))
+                for row, n in zip(rec, counts) for c in row[:n]]

@@ -248,6 +248,10 @@ struct csm_ctx {
      * weights, ancestors, triples, prefix sums); the host's indices of the marked poses; pinned staging */
     DevBuf ps_tab, ps_work, ps_fix;
     PinBuf ps_pin, ps_back;
+    /* loop search (csm_loopsearch_api.hip): a call's node arrays and query table with its records and
+     * per-query counts behind them; pinned staging, up and then back */
+    DevBuf ls_dev;
+    PinBuf ls_pin;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */

@@ -15,6 +15,8 @@
  *   ScorePixelAccurateHIP       <- ScorePixelAccurate (ScoreFunction::Score at free poses)
  *        inc/mapping/score_function.hpp:29-60, src/mapping/score_function_pixel_accurate.cpp:16-58
  *   ParticleSetHIP              (beyond the reference) weights and resampling of a particle set
+ *   LoopSearcherNearestHIP      <- LoopSearcherNearest
+ *        inc/mapping/loop_searcher_nearest.hpp:33-63, src/mapping/loop_searcher_nearest.cpp:59-170
  *
  * The reference headers cannot be included in this image (Eigen3 / Boost are
  * absent), so the few value types the interfaces use are restated here in
@@ -41,6 +43,7 @@
 #include <numeric>
 #include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "csm_hip.h"
@@ -1837,6 +1840,210 @@ private:
 
     const double mTemperature, mKnownRateThreshold;
     detail::ContextRef mCtx;
+};
+
+/* What LoopSearcherNearest::Search reads of LoopSearchHint (inc/mapping/loop_searcher.hpp:25-53): the global
+ * poses of the finished scan nodes ({ x, y, theta }, node i = NodeId i), every local map's
+ * (mScanNodeIdMin, mScanNodeIdMax) -- contiguous runs from node 0 -- the accumulated travel distance and the
+ * id of the last finished local map. */
+struct LoopSearchHintView {
+    const std::array<double, 3>* mScanNodePoses = nullptr;
+    std::size_t mNumOfScanNodes = 0;
+    const std::pair<int, int>* mLocalMapNodeRanges = nullptr;
+    std::size_t mNumOfLocalMaps = 0;
+    double mAccumTravelDist = 0.0;
+    int mLastFinishedMapId = -1;
+};
+
+/* inc/mapping/loop_searcher.hpp:63-85, plus the squared node distance the searcher observes as a metric */
+struct LoopCandidate {
+    int mQueryScanNodeId;
+    int mReferenceScanNodeId;
+    int mReferenceLocalMapId;
+    double mDistSq;
+};
+using LoopCandidateVector = std::vector<LoopCandidate>;
+
+/* candidates -> the pairs PoseGraphOptimizerLMHIP::ComputeMarginals takes: (reference local map, query scan node) */
+inline std::vector<NodePair> ToNodePairs(const LoopCandidateVector& candidates)
+{
+    std::vector<NodePair> pairs(candidates.size());
+    for (std::size_t i = 0; i < candidates.size(); ++i)
+        pairs[i] = NodePair { candidates[i].mReferenceLocalMapId, candidates[i].mQueryScanNodeId };
+    return pairs;
+}
+
+/* a candidate's predicted mapLocalScanPose = InverseCompound(map pose, scan pose) (csm_host_inverse_compound):
+ * the initial pose of its loop detection query and the `predicted` of LoopGate */
+inline RobotPose2D<double> MapLocalScanPose(const std::array<double, 3>& localMapPose,
+                                            const std::array<double, 3>& scanPose)
+{
+    double out[3];
+    csm_host_inverse_compound(localMapPose.data(), scanPose.data(), out);
+    return RobotPose2D<double> { out[0], out[1], out[2] };
+}
+
+/* LoopSearcherNearest (inc/mapping/loop_searcher_nearest.hpp:33-63) on the device (csm_loop_search). Search()
+ * returns the reference's candidate set, nearest first; among equal distances at the cut, where the
+ * reference's std::nth_element keeps any, the pairs with the smaller reference and then query node
+ * (csm_host_loop_candidates_nearest). SearchPerMap() is the form the batch detectors want. */
+class LoopSearcherNearestHIP final {
+public:
+    static std::unique_ptr<LoopSearcherNearestHIP> Create(double travelDistThreshold, double nodeDistThreshold,
+                                                          int numOfCandidateNodes, int deviceId = 0)
+    {
+        if (numOfCandidateNodes < 1 || numOfCandidateNodes > CSM_LOOP_SEARCH_MAX_K)
+            return nullptr;
+        detail::CtxPtr ctx = detail::MakeContext(deviceId);
+        if (!ctx)
+            return nullptr;
+        return std::unique_ptr<LoopSearcherNearestHIP>(new LoopSearcherNearestHIP(
+            travelDistThreshold, nodeDistThreshold, numOfCandidateNodes, detail::ContextRef(std::move(ctx))));
+    }
+    /* on a context another adapter owns and keeps alive */
+    LoopSearcherNearestHIP(csm_ctx* shared, double travelDistThreshold, double nodeDistThreshold,
+                           int numOfCandidateNodes) :
+        LoopSearcherNearestHIP(travelDistThreshold, nodeDistThreshold, numOfCandidateNodes,
+                               detail::ContextRef(shared)) { }
+
+    LoopSearcherNearestHIP(const LoopSearcherNearestHIP&) = delete;
+    LoopSearcherNearestHIP& operator=(const LoopSearcherNearestHIP&) = delete;
+
+    csm_ctx* Context() const { return this->mCtx.Get(); }
+    /* pairs evaluated and eligible in the last call */
+    const csm_loop_search_info& LastInfo() const { return this->mLastInfo; }
+
+    /* LoopSearcher::Search: queries are the nodes of the last finished local map, references the nodes of
+     * the maps before it, every gate measured from mAccumTravelDist */
+    LoopCandidateVector Search(const LoopSearchHintView& searchHint)
+    {
+        const Graph g = this->ToGraph(searchHint);
+        std::vector<std::int32_t> queries(g.mNumOfNodes - g.mNumOfRefs);
+        std::iota(queries.begin(), queries.end(), g.mNumOfRefs);
+        const std::vector<double> queryTravel(queries.size(), searchHint.mAccumTravelDist);
+        std::vector<std::int32_t> counts;
+        const std::vector<csm_loop_candidate> records =
+            this->Run(searchHint, g, g.mNumOfRefs, queries, queryTravel, this->mNumOfCandidateNodes, false, counts);
+        std::vector<csm_loop_candidate> kept(static_cast<std::size_t>(this->mNumOfCandidateNodes));
+        std::int32_t numOfKept = 0;
+        CSM_ASSERT_OK(this->Context(),
+                      csm_host_loop_candidates_nearest(records.data(), counts.data(),
+                                                       static_cast<std::int32_t>(counts.size()),
+                                                       this->mNumOfCandidateNodes, this->mNumOfCandidateNodes,
+                                                       kept.data(), &numOfKept));
+        kept.resize(static_cast<std::size_t>(numOfKept));
+        this->mLastAccumTravelDist = searchHint.mAccumTravelDist;
+        this->mLast = ToCandidates(kept);
+        return this->mLast;
+    }
+
+    /* Per query node the nearest reference node of each local map, the nPerQuery nearest maps
+     * (one_per_map = 1). Any node up to the last finished map's last may be a reference (the local map of the
+     * query itself never is), and each query's gate is measured from its own travel distance: the offline
+     * search of a finished graph. Returns the used records, query by query in the order given. */
+    LoopCandidateVector SearchPerMap(const LoopSearchHintView& searchHint, const std::vector<int>& queryNodes,
+                                     int nPerQuery)
+    {
+        const Graph g = this->ToGraph(searchHint);
+        std::vector<std::int32_t> queries(queryNodes.begin(), queryNodes.end());
+        std::vector<double> queryTravel(queries.size());
+        for (std::size_t i = 0; i < queries.size(); ++i) {
+            CSM_ASSERT_THAT(queries[i] >= 0 && queries[i] < g.mNumOfNodes, "query node %d is not in the graph",
+                            queries[i]);
+            queryTravel[i] = g.mTravel[static_cast<std::size_t>(queries[i])];
+        }
+        std::vector<std::int32_t> counts;
+        const std::vector<csm_loop_candidate> records =
+            this->Run(searchHint, g, g.mNumOfNodes, queries, queryTravel, nPerQuery, true, counts);
+        std::vector<csm_loop_candidate> used;
+        for (std::size_t i = 0; i < counts.size(); ++i)
+            used.insert(used.end(), records.begin() + static_cast<std::ptrdiff_t>(i) * nPerQuery,
+                        records.begin() + static_cast<std::ptrdiff_t>(i) * nPerQuery + counts[i]);
+        return ToCandidates(used);
+    }
+
+    /* The three value sequences the reference registers (src/mapping/loop_searcher_nearest.cpp:13-28) as it
+     * observes them after a Search (:136-167), under the same ids. */
+    template <typename Observe>
+    void ReportMetrics(Observe&& observe) const
+    {
+        observe(std::string("LoopSearcherNearest.AccumTravelDist"), this->mLastAccumTravelDist);
+        observe(std::string("LoopSearcherNearest.NumOfCandidateNodes"), static_cast<double>(this->mLast.size()));
+        for (const LoopCandidate& c : this->mLast)
+            observe(std::string("LoopSearcherNearest.NodeDist"), c.mDistSq);
+    }
+
+private:
+    struct Graph {
+        std::int32_t mNumOfNodes = 0, mNumOfMaps = 0, mNumOfRefs = 0;
+        std::vector<std::int32_t> mMapIndex;
+        std::vector<double> mTravel;
+    };
+
+    LoopSearcherNearestHIP(double travelDistThreshold, double nodeDistThreshold, int numOfCandidateNodes,
+                           detail::ContextRef ctx) :
+        mTravelDistThreshold(travelDistThreshold), mNodeDistThreshold(nodeDistThreshold),
+        mNumOfCandidateNodes(numOfCandidateNodes), mCtx(std::move(ctx)) { }
+
+    Graph ToGraph(const LoopSearchHintView& h) const
+    {
+        CSM_ASSERT_THAT(h.mLastFinishedMapId >= 0 && static_cast<std::size_t>(h.mLastFinishedMapId) < h.mNumOfLocalMaps,
+                        "mLastFinishedMapId names no local map");
+        Graph g;
+        g.mNumOfMaps = h.mLastFinishedMapId + 1;
+        for (std::int32_t m = 0; m < g.mNumOfMaps; ++m) {
+            const std::pair<int, int>& run = h.mLocalMapNodeRanges[m];
+            CSM_ASSERT_THAT(run.first == g.mNumOfNodes && run.second >= run.first,
+                            "local maps must be contiguous runs of scan nodes from node 0");
+            if (m == h.mLastFinishedMapId)
+                g.mNumOfRefs = g.mNumOfNodes;
+            g.mMapIndex.insert(g.mMapIndex.end(), static_cast<std::size_t>(run.second - run.first + 1), m);
+            g.mNumOfNodes = run.second + 1;
+        }
+        CSM_ASSERT_THAT(static_cast<std::size_t>(g.mNumOfNodes) <= h.mNumOfScanNodes,
+                        "a local map names a scan node that is not given");
+        g.mTravel.resize(static_cast<std::size_t>(g.mNumOfNodes));
+        static_assert(sizeof(std::array<double, 3>) == 3 * sizeof(double), "pose layout");
+        CSM_ASSERT_OK(this->Context(),
+                      csm_host_travel_distances(h.mScanNodePoses->data(), g.mNumOfNodes, g.mTravel.data()));
+        return g;
+    }
+
+    std::vector<csm_loop_candidate> Run(const LoopSearchHintView& h, const Graph& g, std::int32_t numOfRefs,
+                                        const std::vector<std::int32_t>& queries,
+                                        const std::vector<double>& queryTravel, int nPerQuery, bool onePerMap,
+                                        std::vector<std::int32_t>& counts)
+    {
+        csm_loop_search_params prm {};
+        prm.travel_dist_threshold = this->mTravelDistThreshold;
+        prm.node_dist_threshold = this->mNodeDistThreshold;
+        prm.n_per_query = nPerQuery;
+        prm.one_per_map = onePerMap ? 1 : 0;
+        std::vector<csm_loop_candidate> records(queries.size() * static_cast<std::size_t>(std::max(nPerQuery, 1)));
+        counts.assign(queries.size(), 0);
+        CSM_ASSERT_OK(this->Context(),
+                      csm_loop_search(this->Context(), h.mScanNodePoses->data(), g.mMapIndex.data(), g.mTravel.data(),
+                                      g.mNumOfNodes, g.mNumOfMaps, numOfRefs, queries.data(), queryTravel.data(),
+                                      static_cast<std::int32_t>(queries.size()), &prm, records.data(), counts.data(),
+                                      &this->mLastInfo));
+        return records;
+    }
+
+    static LoopCandidateVector ToCandidates(const std::vector<csm_loop_candidate>& records)
+    {
+        LoopCandidateVector out(records.size());
+        for (std::size_t i = 0; i < records.size(); ++i)
+            out[i] = LoopCandidate { records[i].query_scan_index, records[i].ref_scan_index,
+                                     records[i].ref_map_index, records[i].dist_sq };
+        return out;
+    }
+
+    const double mTravelDistThreshold, mNodeDistThreshold;
+    const int mNumOfCandidateNodes;
+    detail::ContextRef mCtx;
+    csm_loop_search_info mLastInfo {};
+    double mLastAccumTravelDist = 0.0;
+    LoopCandidateVector mLast;
 };
 
 } /* namespace CsmHip */
