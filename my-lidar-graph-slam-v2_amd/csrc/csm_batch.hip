@@ -5,6 +5,8 @@
  * host finish with the exact fall-backs. */
 #include "csm_matchers.hpp"
 
+#include <optional>
+
 #ifdef CSM_BIN_TIMING
 static unsigned long long* g_bin_debug = nullptr;
 static uint32_t* bin_debug_buffer()
@@ -204,6 +206,7 @@ struct BatchGroup {
     std::vector<PassPlan> lp;                     /* [H + 1] launch geometry shared by the group */
     size_t bin_lds = 0, binj_lds = 0;
     bool joint = false, bound_pass = false, two_rounds = false;
+    bool coarse_first = false;                    /* the box-max(L) level bounds the units of the exact pass */
     size_t hit_total = 0, tile_total = 0, theta_total = 0;
     /* scans */
     std::vector<size_t> scan_off;
@@ -335,6 +338,26 @@ int BatchGroup::plan()
     two_rounds = spec.bnb;
     for (int k = 0; k < nq; ++k)
         two_rounds = two_rounds || min_known_of(k) > 1;
+    /* Coarse first: the correlative sweep has a box-max(L) level whose nodes bound their L x L candidates,
+     * at 1/L^2 of the fine level's reads. Its node keys, not an fp32 pass over every candidate, then bound
+     * the units of the exact pass (k_coarse_joint_batch, k_unit_bounds). The greatest bound is not an
+     * attained key, so the exact pass takes two rounds: the units near the greatest bound, then the units
+     * whose bound reaches the best exact key of round 1. Windows that ask for every candidate's sums or
+     * fp32 key keep the fp32 pass (for the whole group: one chain). */
+    bool dumps = false;
+    if (resident)
+        for (int k = 0; k < nq; ++k)
+            dumps = dumps || (resident->dump_s && resident->dump_s[idx[k]]) || (resident->dump_k && resident->dump_k[idx[k]]) ||
+                    (resident->dump_f && resident->dump_f[idx[k]]);
+    /* The level decides between units, a node between L x L candidates: a window of a handful of units
+     * (few slices, one candidate block) lies inside one blurred peak of the level, every unit's bound
+     * reaches the winner, and only the fp32 pass's per-candidate keys still tell units apart. */
+    constexpr int kCoarseFirstMinUnits = 16;
+    int min_units = INT_MAX;
+    for (const BatchPrep& p : pp)
+        min_units = std::min(min_units, (p.n_theta + 1) / 2 * fine.ncb());
+    coarse_first = bound_pass && !spec.bnb && H >= 1 && spec.stride[1] >= 2 && !dumps && min_units >= kCoarseFirstMinUnits;
+    two_rounds = two_rounds || coarse_first;
     for (BatchPrep& p : pp) {
         /* lists and records per slice, or per pair of slices (2 n entries each) */
         const int units = joint ? (p.n_theta + 1) / 2 : p.n_theta;
@@ -421,8 +444,9 @@ int BatchGroup::size_workspaces()
         if ((rc = ensure(ctx, ctx->b_abest, best_total * sizeof(float)))) return rc;
         /* work lists of the exact kernel: [2 counts, pad][items 0][items 1], one item per (pair, block) */
         if ((rc = ensure(ctx, ctx->b_items, 64 + 2 * blocks_total * 4))) return rc;
-        for (BatchPrep& p : pp)
-            if ((rc = ensure_xgrid_f(ctx, *p.grid))) return rc;
+        if (!coarse_first)
+            for (BatchPrep& p : pp)
+                if ((rc = ensure_xgrid_f(ctx, *p.grid))) return rc;
     }
     if ((rc = ensure(ctx, ctx->b_out, (size_t)nq * (sizeof(csm_result) + 4)))) return rc;
     jobs_bytes = (size_t)nq * (sizeof(ProjJob) + sizeof(BinJob) + sizeof(FinalJob) +
@@ -496,14 +520,16 @@ void BatchGroup::build_jobs(int k)
         /* a leaf's own known count bounds every ancestor's from below when
          * no read can fall in the edge band: the level passes are only
          * needed to detect (and then handle) that case */
-        S.skip_unless_band = spec.bnb ? 1 : (min_known <= 1);
+        S.skip_unless_band = spec.bnb ? 1 : (min_known <= 1 && !coarse_first);
         S.sorted_pb = B.sorted_rc;
         S.acc_s = lvl_s + p.lvl_off[h];
         S.acc_k = lvl_k + p.lvl_off[h];
         F.elig[h - 1] = EligLevel { S.acc_k, S.acc_s, S.stride, S.nx, S.ny };
-        /* the level's atomic accumulators: cleared only when the pass will run */
+        /* the level's atomic accumulators: cleared only when the pass will run; the coarse-first pass
+         * stores every node and needs no clear */
         ZeroJob& Z0 = zj[(size_t)k * H + (h - 1)];
-        Z0 = ZeroJob { S.acc_s, S.acc_k, (size_t)p.n_theta * S.nx * S.ny, flags, S.skip_unless_band ? 0 : 1, 0 };
+        Z0 = ZeroJob { S.acc_s, S.acc_k, coarse_first ? 0 : (size_t)p.n_theta * S.nx * S.ny, flags,
+                       S.skip_unless_band ? 0 : 1, 0 };
         zero_words_max = std::max(zero_words_max, Z0.words);
     }
     F.xg = gr.xg.as<uint32_t>();
@@ -511,7 +537,8 @@ void BatchGroup::build_jobs(int k)
     F.xg_pad = gr.xg_pad;
     F.block_best = ctx->b_best.as<BlockBest>() + p.best_off;
     if (bound_pass) {
-        F.xgf = gr.xgf.as<float>();
+        if (!coarse_first)                      /* the fp32 key copy: read by the fp32 pass only */
+            F.xgf = gr.xgf.as<float>();
         F.approx_best = ctx->b_abest.as<float>() + p.best_off;
         /* |fp32 key - key| <= (n + 2) 2^-24 * key for a sum of n non-negative terms (one rounding
          * per fused multiply-add, one for each cell's float, one for joining the two accumulator
@@ -633,13 +660,21 @@ int BatchGroup::launch_chain()
                                                          reinterpret_cast<const BinJob*>(d_bj)), "binning")))
             return rc;
     }
-    if (H > 0) {
+    if (H > 0 && zero_words_max > 0) {
         const int zb = (int)std::min<size_t>(64, (zero_words_max + 255) / 256);
         if ((rc = launched_ok(ctx, csm_launch::zero_if_band_batch(ctx->stream, std::max(1, zb), nq * H,
                                                                   reinterpret_cast<const ZeroJob*>(d_zj)), "edge-band clear")))
             return rc;
     }
     for (int h = H; h >= 1; --h) {
+        if (coarse_first) {
+            /* the level IS the bound pass of the fine level, and is timed as that */
+            ScopedTimer tm(ctx, "score_bound");
+            if ((rc = launched_ok(ctx, csm_launch::coarse_joint_batch(ctx->stream, lp[h].nx * lp[h].ny, (n_theta_max + 1) / 2, nq,
+                                                                      reinterpret_cast<const ScoreJob*>(d_sj[h])), "coarse level")))
+                return rc;
+            continue;
+        }
         /* keep >= ~2k workgroups in flight: split the tile list when the
          * level has few candidate blocks */
         const long blocks = (long)lp[h].ncb() * n_theta_max * nq;
@@ -655,7 +690,12 @@ int BatchGroup::launch_chain()
                                      n_theta_max, n_slices, all_exit && nq >= 16 ? 4 : 0)))
             return rc;
     }
-    if (bound_pass) {
+    if (coarse_first) {
+        ScopedTimer tm(ctx, "score_bound");
+        if ((rc = launched_ok(ctx, csm_launch::unit_bounds(ctx->stream, fine_jobs, nq, n_theta_max * lp[0].ncb(), lp[0].cbx,
+                                                           lp[0].groups * lp[0].R, lp[0].ncbx, lp[0].ncb()), "unit bounds")))
+            return rc;
+    } else if (bound_pass) {
         PassPlan fp = lp[0];
         fp.fp32 = true;
         ScopedTimer tm(ctx, "score_bound");
@@ -686,9 +726,15 @@ int BatchGroup::launch_chain()
     list.counts = counts;
     list.blocks = (int)std::min<size_t>(blocks_total, 2048);
     const int split_cb = tail_split(ctx, lp[0]) ? lp[0].ncbx * (lp[0].ncby - 1) : ncb;
+    /* coarse first: both rounds are one span of the exact pass (a chain counts once among the fine launches) */
+    std::optional<ScopedTimer> exact_pass;
+    if (coarse_first)
+        exact_pass.emplace(ctx, "score_fine");
     for (int round = 1; round <= (two_rounds ? 2 : 1); ++round) {
         {
-            ScopedTimer tm(ctx, "score_fine");
+            std::optional<ScopedTimer> tm;
+            if (!coarse_first)
+                tm.emplace(ctx, "score_fine");
             HIP_TRY(ctx, hipMemsetAsync(counts, 0, 8, ctx->stream));
             if ((rc = launched_ok(ctx, csm_launch::bound_select(ctx->stream, fine_jobs, nq, ncb, split_cb, items0, items1,
                                                                 counts, (uint32_t)blocks_total, round), "bound selection")))

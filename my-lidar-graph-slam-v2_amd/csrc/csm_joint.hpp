@@ -37,6 +37,15 @@ int joint_one(const ScoreLaunch& a, const ScoreJob& job, int n_pairs);
 int bound_select(hipStream_t s, const ScoreJob* jobs, int n_jobs, int ncb, int split_cb, uint32_t* items0,
                  uint32_t* items1, uint32_t* counts, uint32_t cap, int round);
 
+/* Coarse-first window batches. coarse_joint_batch: the strided level of every job (ScoreJob of the level,
+ * joint entry lists in sorted_pb) scored node by node straight from the level's cells, every node's exact
+ * (S, K) stored to acc_s / acc_k; `nodes` = nx * ny of the level. unit_bounds (fine jobs, after it): the
+ * greatest node key over each (slice, candidate block) of the fine plan, rounded up, to approx_best --
+ * what bound_select reads in place of the fp32 pass's block maxima; units_max = max slices * ncb, the
+ * blocks cbx x cby candidates, ncbx per row of blocks. */
+int coarse_joint_batch(hipStream_t s, int nodes, int n_pairs_max, int n_jobs, const ScoreJob* jobs);
+int unit_bounds(hipStream_t s, const ScoreJob* jobs, int n_jobs, int units_max, int cbx, int cby, int ncbx, int ncb);
+
 /* xgf = the level's fp32 key copy in the layout of its pair-row copy (k_expand_pairs_f) */
 int expand_pairs_f(hipStream_t s, const uint16_t* cells, int rows, int cols, int pitch, float* xgf, int xg_prows,
                    int xg_pitch, int pad);

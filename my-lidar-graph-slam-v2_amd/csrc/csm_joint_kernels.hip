@@ -1085,6 +1085,184 @@ __global__ __launch_bounds__(kBlock, 4) void k_score_joint_one(ScoreJob job, int
     score_body_joint<LS, R>(job, cbx, groups, lane_map, bx, by, bb);
 }
 
+/* ---- coarse-first window batches: the box-max(L) level as the bound (BatchGroup::coarse_first) ----
+ * The level has one node per L x L candidates, `stride` = L cells apart, and a node's key bounds every
+ * candidate under it (box maximum; the negative edge band aside, k_unit_bounds). Scoring it needs no window
+ * copy in LDS: a beam's cell under a node is read by that node alone, so a staged region (tile + 84 cells
+ * of candidate span, squared) would hold more cells than the gather ever reads. One lane per node reads
+ * its cells straight from the level: neighbouring lanes are neighbouring nodes of one row, 2 L bytes apart.
+ *
+ * grid = (ceil(nodes / 256), pairs of slices, jobs), no barrier: a wave behind the last node leaves. The
+ * entries are k_binj's sorted_rc words of the pair (counts | row << 7 | col inside the record's bounding
+ * box, row even; a count on the odd row reads row + 1), uniform per wave and therefore scalar: the entry's
+ * cell address is a scalar base plus the lane's constant offset, the four counts are scalar multiplicands.
+ * A lane holds both slices' sums: S0, S1 and the two known counts (each <= kMaxPoints < 2^16) packed into
+ * one word. Where every lane's reads of a record stay inside the level (the record's bounding box shifted by
+ * the lane's node) nothing is tested per entry; otherwise row and column are tested per read and a read
+ * outside the level counts as unknown, as in every scoring kernel. Every node of every slice is written
+ * with plain stores, [n_theta][nx][ny] -- the layout its readers assume (k_unit_bounds, the exact kernel's
+ * eligibility read): no clear, no atomics. */
+__global__ __launch_bounds__(256) void k_coarse_joint_batch(const ScoreJob* jobs)
+{
+    auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+    const ScoreJob& job = jobs[blockIdx.z];
+    const int n_theta = uni(job.n_theta);
+    const int tp = (int)blockIdx.y, t0 = 2 * tp;
+    const int nx = uni(job.nx), ny = uni(job.ny), nodes = nx * ny;
+    const int node = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (t0 >= n_theta || uni(node) >= nodes)
+        return;
+    const bool two = t0 + 1 < n_theta;
+    const bool on = node < nodes;
+    const int nd = on ? node : 0;         /* lanes behind the last node read node 0's cells and store nothing */
+    const int yi = nd / nx, xi = nd - yi * nx;
+    const int stride = uni(job.stride), pitch = uni(job.pitch), rows = uni(job.rows), cols = uni(job.cols);
+    const int dx = xi * stride, dy = yi * stride;
+    const uint32_t lane_off = (uint32_t)(dy * pitch + dx);
+    const int x_lo = uni(job.x_lo), y_lo = uni(job.y_lo);
+    const uint16_t* __restrict__ cells = job.cells;
+    const int ntiles = uni(job.n_tiles[tp]);
+    const TileRec* __restrict__ recs = job.tiles + (size_t)tp * job.max_tiles;
+    const uint32_t* __restrict__ pbs = job.sorted_pb + (size_t)tp * 2 * job.n_points;
+
+    uint32_t S0 = 0, S1 = 0, KK = 0;      /* KK: known count of slice t0 | of slice t0 + 1 << 16 */
+    auto add = [&](uint32_t v, uint32_t m0, uint32_t m1) {
+        S0 = mad_u24(v, m0, S0);
+        S1 = mad_u24(v, m1, S1);
+        KK = mad_u24(min(v, 1u), m0 | (m1 << 16), KK);
+    };
+    /* Records and entries reach the scalar registers without a wait per entry: a wave loads the words of 8
+     * records, or 64 entries, one per lane, and v_readlane hands them out (the next record's entries are
+     * loaded while this record's cells are gathered). */
+    const int lane = (int)threadIdx.x & 63;
+    auto rl = [](uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); };
+    auto rec_group = [&](int ti) {          /* the 8 words of records ti .. ti + 7, ti a multiple of 8 */
+        const int i = ti * 8 + lane;
+        return i < ntiles * 8 ? reinterpret_cast<const uint32_t*>(recs)[i] : 0u;
+    };
+    auto entries = [&](uint32_t first, int n) { return lane < n ? pbs[first + lane] : 0u; };
+    uint32_t recw = ntiles > 0 ? rec_group(0) : 0u;
+    uint32_t ent_nxt = ntiles > 0 ? entries(rl(recw, 2), (int)rl(recw, 3)) : 0u;
+    for (int ti = 0; ti < ntiles; ++ti) {
+        const int q = (ti & 7) * 8;
+        const int r0 = (int)rl(recw, q) + y_lo, c0 = (int)rl(recw, q + 1) + x_lo;
+        const uint32_t start = rl(recw, q + 2);
+        const int cnt = (int)rl(recw, q + 3), h = (int)rl(recw, q + 4), w = (int)rl(recw, q + 5);
+        uint32_t ent = ent_nxt;
+        if (ti + 1 < ntiles) {
+            if (((ti + 1) & 7) == 0)
+                recw = rec_group(ti + 1);
+            const int qn = ((ti + 1) & 7) * 8;
+            ent_nxt = entries(rl(recw, qn + 2), (int)rl(recw, qn + 3));
+        }
+        /* an entry's rows lie in [r0, r0 + h), its column in [c0, c0 + w): the box of the record's beams */
+        const bool inside = r0 + dy >= 0 && r0 + dy + h <= rows && c0 + dx >= 0 && c0 + dx + w <= cols;
+        const bool fast = __builtin_amdgcn_ballot_w64(!inside) == 0;
+        const uint16_t* base = cells + ((ptrdiff_t)r0 * pitch + c0);      /* uniform; may lie before the level */
+        for (int j0 = 0; j0 < cnt; j0 += 64) {
+            const int m = min(64, cnt - j0);
+            if (j0)
+                ent = entries(start + (uint32_t)j0, m);
+            if (fast) {
+                int j = 0;
+                for (; j + 4 <= m; j += 4) {
+                    uint32_t wd[4], ve[4], vo[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        wd[u] = rl(ent, j + u);
+                        const uint16_t* pe = base + (int)(((wd[u] >> 7) & 127u) * (uint32_t)pitch + (wd[u] & 127u));
+                        ve[u] = vo[u] = 0u;
+                        if (wd[u] & 0x0f0f0000u)
+                            ve[u] = pe[lane_off];
+                        if (wd[u] & 0xf0f00000u)
+                            vo[u] = pe[lane_off + (uint32_t)pitch];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        add(ve[u], (wd[u] >> 16) & 15u, (wd[u] >> 24) & 15u);
+                        add(vo[u], (wd[u] >> 20) & 15u, wd[u] >> 28);
+                    }
+                }
+                for (; j < m; ++j) {
+                    const uint32_t e = rl(ent, j);
+                    const uint16_t* pe = base + (int)(((e >> 7) & 127u) * (uint32_t)pitch + (e & 127u));
+                    if (e & 0x0f0f0000u)
+                        add(pe[lane_off], (e >> 16) & 15u, (e >> 24) & 15u);
+                    if (e & 0xf0f00000u)
+                        add(pe[lane_off + (uint32_t)pitch], (e >> 20) & 15u, e >> 28);
+                }
+            } else {
+                for (int j = 0; j < m; ++j) {
+                    const uint32_t e = rl(ent, j);
+                    const int r = r0 + (int)((e >> 7) & 127u) + dy, c = c0 + (int)(e & 127u) + dx;
+                    const bool c_ok = c >= 0 && c < cols;
+                    if (e & 0x0f0f0000u) {
+                        const bool ok = c_ok && r >= 0 && r < rows;
+                        const uint32_t v = cells[ok ? (size_t)r * pitch + c : 0];
+                        add(ok ? v : 0u, (e >> 16) & 15u, (e >> 24) & 15u);
+                    }
+                    if (e & 0xf0f00000u) {
+                        const bool ok = c_ok && r + 1 >= 0 && r + 1 < rows;
+                        const uint32_t v = cells[ok ? (size_t)(r + 1) * pitch + c : 0];
+                        add(ok ? v : 0u, (e >> 20) & 15u, e >> 28);
+                    }
+                }
+            }
+        }
+    }
+    if (!on)
+        return;
+    const size_t per_slice = (size_t)nodes;
+    const size_t ai = (size_t)t0 * per_slice + (size_t)xi * ny + yi;
+    job.acc_s[ai] = S0;
+    job.acc_k[ai] = KK & 0xffffu;
+    if (two) {
+        job.acc_s[ai + per_slice] = S1;
+        job.acc_k[ai + per_slice] = KK >> 16;
+    }
+}
+
+/* The bound of every unit of the exact pass from the level's sums: approx_best[t][cb] = the greatest key
+ * 32268 K + 499 S (u64, exact) among the nodes whose L x L candidates intersect candidate block cb of
+ * slice t, rounded UP to a float, so that it bounds every candidate of the block from above. The
+ * blocks are the fine launches' (csm_plan.hip: launch_score_batch): block cb = by * ncbx + bx holds the
+ * candidate columns [bx * cbx, +cbx) and rows [by * cby, +cby), cut at the window -- the same for the
+ * R = 6 launch of the last row block, which only changes the list the block goes to (k_bound_select,
+ * split_cb). The nodes are read where the fine job's eligibility level points: [n_theta][nxc][nyc].
+ * A beam in the negative edge band voids the bound (a box there may read unknown where its maximum is
+ * known): every unit gets the greatest float, k_bound_select lists them all in round 1, and the exact
+ * kernel's own check against the level raises CSM_FLAG_EDGE_BAND as without a bound.
+ * One wave per unit, grid = (ceil(units / 4), jobs). */
+__global__ __launch_bounds__(256) void k_unit_bounds(const ScoreJob* jobs, int cbx, int cby, int ncbx, int ncb)
+{
+    const ScoreJob& job = jobs[blockIdx.y];
+    const int unit = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    const int lane = (int)threadIdx.x & 63;
+    if (unit >= job.n_theta * ncb || !job.approx_best || job.n_elig < 1)
+        return;
+    const int t = unit / ncb, cb = unit - t * ncb;
+    const int by = cb / ncbx, bx = cb - by * ncbx;
+    const EligLevel& el = job.elig[0];
+    const int L = el.div;
+    const int xc0 = bx * cbx / L, xc1 = (min(job.nx, (bx + 1) * cbx) - 1) / L;
+    const int yc0 = by * cby / L, yc1 = (min(job.ny, (by + 1) * cby) - 1) / L;
+    const int nyn = yc1 - yc0 + 1, n = (xc1 - xc0 + 1) * nyn;
+    unsigned long long best = 0;
+    for (int i = lane; i < n; i += 64) {
+        const int xc = xc0 + i / nyn, yc = yc0 + i % nyn;
+        const size_t ni = ((size_t)t * el.nxc + xc) * el.nyc + yc;
+        const unsigned long long key = 32268ull * el.k[ni] + 499ull * (unsigned long long)el.s[ni];
+        best = key > best ? key : best;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned long long o = shfl_xor_u64(best, m);
+        best = o > best ? o : best;
+    }
+    if (lane == 0)
+        job.approx_best[(size_t)t * ncb + cb] = (*job.flags & kFlagBandTouch) ? 3.4028234664e38f : __ull2float_ru(best);
+}
+
 /* ---- after the bound pass: which candidate blocks the exact kernel still has to score ----
  * One workgroup per job (window). M = the window's greatest fp32 key. A block (pair of slices,
  * candidate block) whose own greatest key lies below M by more than the two passes' rounding
@@ -1262,6 +1440,16 @@ int bound_select(hipStream_t s, const ScoreJob* jobs, int n_jobs, int ncb, int s
                  uint32_t* items1, uint32_t* counts, uint32_t cap, int round)
 {
     return launch(k_bound_select, dim3(n_jobs), dim3(256), s, jobs, ncb, split_cb, items0, items1, counts, cap, round);
+}
+
+int coarse_joint_batch(hipStream_t s, int nodes, int n_pairs_max, int n_jobs, const ScoreJob* jobs)
+{
+    return launch(k_coarse_joint_batch, dim3((nodes + 255) / 256, n_pairs_max, n_jobs), dim3(256), s, jobs);
+}
+
+int unit_bounds(hipStream_t s, const ScoreJob* jobs, int n_jobs, int units_max, int cbx, int cby, int ncbx, int ncb)
+{
+    return launch(k_unit_bounds, dim3((units_max + 3) / 4, n_jobs), dim3(256), s, jobs, cbx, cby, ncbx, ncb);
 }
 
 int expand_pairs_f(hipStream_t s, const uint16_t* cells, int rows, int cols, int pitch, float* xgf, int xg_prows,
