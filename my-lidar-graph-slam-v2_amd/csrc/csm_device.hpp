@@ -28,6 +28,26 @@ constexpr int kBoxTR = 32, kBoxTC = 64, kBoxMaxWin = 64;    /* k_boxmax_batch: o
 constexpr int kProjSlices = 256;     /* k_project: theta slices per workgroup (LDS table) */
 constexpr int kBinDebugRows = 65536; /* -DCSM_BIN_TIMING builds: rows of k_bin's phase counters */
 
+/* The pair-row fine kernels copy a window of (kTile + cby) / 2 + 1 pair rows of `ls` 8-byte slots into LDS in
+ * 1-KiB pieces; the entry lists follow the last piece. The ONE statement of that size: the kernels place
+ * their lists by it (PairWindow::open, csm_score_common.hpp), the host sizes the launch by it (pair_lds_bytes). */
+constexpr __host__ __device__ int pair_window_pieces(int ls, int cby)
+{
+    return (((kTile + cby) / 2 + 1) * ls * 8 + 1023) >> 10;
+}
+
+/* One word of the lane table (lane_map_for, csm_plan.hip): which lane group g and candidate column dxi a
+ * thread of a pair kernel owns; `idle`: the thread owns no candidate, (g, dxi) is the slot it reads instead.
+ * kLaneNone: an idle thread without a slot of its own (g = 127 lies behind every launch's groups). */
+constexpr uint16_t kLaneNone = 0xffff;
+constexpr __host__ __device__ uint16_t lane_word(int g, int dxi, bool idle = false)
+{
+    return (uint16_t)((idle ? 0x8000 : 0) | g << 8 | dxi);
+}
+constexpr __host__ __device__ int lane_word_dxi(uint32_t m) { return (int)(m & 255u); }
+constexpr __host__ __device__ int lane_word_g(uint32_t m) { return (int)((m >> 8) & 127u); }
+constexpr __host__ __device__ bool lane_word_idle(uint32_t m) { return (m >> 15) != 0; }
+
 /* Where a pair-kernel launch sits among the candidate blocks of its window: a window's last
  * row block may be a launch of its own with fewer rows per lane (R = 6 for 36 rows instead of
  * R = 8 with a quarter of the lanes' rows outside the window: launch_score_batch). */

@@ -19,6 +19,10 @@
  * Replaces the sweep of src/mapping/scan_matcher_correlative.cpp:161-197, 301-368 and
  * ScorePixelAccurate::Score per leaf (src/mapping/score_function_pixel_accurate.cpp:16-58)
  * for batches; exact integer (S, K) per candidate as before.
+ *
+ * The bodies (score_body_joint, score_body_jointf) stage their windows through PairWindow and
+ * score_body_joint empties its accumulators by flush_flags / flush_packed, both shared with the
+ * per-slice bodies of csm_kernels.hip (csm_score_common.hpp).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -195,8 +199,11 @@ __device__ __forceinline__ void k_binj_body(const BinJob& job)
             const unsigned long long run = (e == 64 ? ~0ull : (1ull << e) - 1ull) & from_me;
             const uint32_t co = (uint32_t)__popcll(run & om), ce = (uint32_t)__popcll(run) - co;
             beams[u] = (unsigned long long)(ce | (co << 16)) << (32u * sl);
-            /* multiplicative hash on the full-rate 24-bit multiplier: 18 bits of key x C, scaled to the table */
-            slot[u] = __umul24(__builtin_amdgcn_ubfe(__umul24(key[u], 0x3779b1u), 9, 18), hsize) >> 18;
+            /* multiplicative hash on the full-rate 24-bit multiplier: 18 bits of key x C, scaled to the table.
+             * The product is below 2^32 (a table that fits the LDS has fewer than 2^14 slots) but HIP declares
+             * __umul24 as int: shifted as such, a product from 2^31 on -- tables above 8192 slots, scans above
+             * 3072 beams -- gave a slot far outside the table and the cell's beams were lost */
+            slot[u] = (uint32_t)__umul24(__builtin_amdgcn_ubfe(__umul24(key[u], 0x3779b1u), 9, 18), hsize) >> 18;
             pend[u] = head;
             low_edge = min(low_edge, min(r + y_lo, c + x_lo));
         }
@@ -479,14 +486,6 @@ __device__ __forceinline__ void joint_gather(uint32_t lane_addr, const uint32_t*
 {
     constexpr int kRowBytes = LS * 8;
     constexpr int NQ = R / 2 + 1;
-    auto flush = [](uint32_t (&acc)[R], uint32_t (&S)[R], uint32_t (&K)[R]) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            S[r] += acc[r];
-            K[r] += acc[r] >> 23;
-            acc[r] = 0;
-        }
-    };
     auto issue = [&](uint32_t w, unsigned long long (&q)[NQ]) {
         const uint32_t addr = lane_addr + (w & 0xffffu);
         lds_read_b64<0 * kRowBytes>(addr, q[0]);
@@ -507,24 +506,14 @@ __device__ __forceinline__ void joint_gather(uint32_t lane_addr, const uint32_t*
     };
     uint32_t pb_cur;
     unsigned long long flags0, flags1;
-    auto flags_of = [&](int b, int real, FlushState& fs) {
-        const int c1 = fs.cum + wave_prefix_sum(b), c0 = c1 - b;
-        const bool cross = ((uint32_t)c1 * 683u) >> 16 != ((uint32_t)c0 * 683u) >> 16;      /* floor(c / 96) */
-        const unsigned long long heavy = __builtin_amdgcn_ballot_w64(b > 8);
-        const unsigned long long f = __builtin_amdgcn_ballot_w64(cross) | heavy | heavy << 1 | heavy << 2 |
-                                     heavy << 3 | heavy << 4 | (fs.carry ? 0xfull : 0ull);
-        fs.carry = (heavy >> max(0, real - 4)) != 0;        /* among the last four real entries */
-        fs.cum = __builtin_amdgcn_readlane(c1, 63) % 96;
-        return f;
-    };
     auto load_chunk = [&](int j0) {
         pb_cur = lpb[j0 + lane];
         const bool real = j0 + lane < cnt;
         const int b0 = real ? (int)(((pb_cur >> 16) & 15u) + ((pb_cur >> 20) & 15u)) : 0;
         const int b1 = real ? (int)(((pb_cur >> 24) & 15u) + (pb_cur >> 28)) : 0;
         const int nreal = min(64, cnt - j0);
-        flags0 = flags_of(b0, nreal, fs0);
-        flags1 = flags_of(b1, nreal, fs1);
+        flags0 = flush_flags(b0, nreal, fs0);
+        flags1 = flush_flags(b1, nreal, fs1);
     };
     int j = 0;
     load_chunk(0);
@@ -536,9 +525,9 @@ __device__ __forceinline__ void joint_gather(uint32_t lane_addr, const uint32_t*
             const uint32_t o2 = (uint32_t)__builtin_amdgcn_readlane((int)pb_cur, (j + 2) & 63);
             const uint32_t o3 = (uint32_t)__builtin_amdgcn_readlane((int)pb_cur, (j + 3) & 63);
             if ((flags0 >> (j & 63)) & 0xfull)
-                flush(acc0, S0, K0);
+                flush_packed(acc0, S0, K0);
             if ((flags1 >> (j & 63)) & 0xfull)
-                flush(acc1, S1, K1);
+                flush_packed(acc1, S1, K1);
             unsigned long long qa[NQ], qb[NQ], qc[NQ], qd[NQ];
             issue(o0, qa);
             issue(o1, qb);
@@ -556,9 +545,9 @@ __device__ __forceinline__ void joint_gather(uint32_t lane_addr, const uint32_t*
         for (; j < stop; ++j) {
             const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)pb_cur, j & 63);
             if ((flags0 >> (j & 63)) & 1ull)
-                flush(acc0, S0, K0);
+                flush_packed(acc0, S0, K0);
             if ((flags1 >> (j & 63)) & 1ull)
-                flush(acc1, S1, K1);
+                flush_packed(acc1, S1, K1);
             unsigned long long qa[NQ];
             issue(o, qa);
             lds_wait<0, NQ>(qa);
@@ -570,49 +559,25 @@ __device__ __forceinline__ void joint_gather(uint32_t lane_addr, const uint32_t*
 }
 
 /* One workgroup = (pair of theta slices, block of cbx x groups * R candidate offsets). Lane
- * <-> candidate mapping, window staging (LDS-DMA from the pair-row copy of the level), the
- * epilogue and the row-block split (BlockBase) as in score_body_pairs2; ONE record list. */
+ * <-> candidate mapping and window staging (LDS-DMA from the pair-row copy of the level) are
+ * PairWindow's (csm_score_common.hpp), the epilogue and the row-block split (BlockBase) as in
+ * score_body_pairs2; ONE record list. */
 template <int LS, int R>
 __device__ __forceinline__ void score_body_joint(const ScoreJob& job, int cbx, int groups, const uint16_t* lane_map,
                                                  int bid_x, int bid_y, BlockBase bb)
 {
-    static_assert(R % 2 == 0 && LS % 2 == 0, "pair rows, 16-byte rows");
     extern __shared__ __attribute__((aligned(16))) uint16_t sm_tile[];
     const int t0 = 2 * bid_y, t1 = t0 + 1;
     const int n_theta = __builtin_amdgcn_readfirstlane(job.n_theta);
     if (t0 >= n_theta)
         return;
     const bool two = t1 < n_theta;
-    const int tid = threadIdx.x;
-    const int ncbx = (job.nx + cbx - 1) / cbx;
-    const int bx = bid_x % ncbx, by = bid_x / ncbx;
-    const int cby = groups * R;
-    const int row0 = bb.row_base + by * cby;
-    if (row0 >= job.ny)
+    PairWindow<LS, R> win;
+    if (!win.open(job, job.xg, sm_tile, cbx, groups, lane_map, bid_x, bb))
         return;
     const uint32_t qflags = job.elig_only_if_band ? *job.flags : 0u;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    int dxi = tid % cbx, g = tid / cbx;
-    bool idle = false;
-    if (lane_map) {
-        const uint32_t m = lane_map[tid];
-        dxi = (int)(m & 255u);
-        g = (int)((m >> 8) & 127u);
-        idle = (m >> 15) != 0;
-    }
-    const bool lane_on = !idle && g < groups;
-    const int x0 = job.x_lo + bx * cbx;
-    const int y0 = job.y_lo + row0;
-    constexpr int kRowBytes = LS * 8;
-    const int prows_full = (kTile + cby) / 2 + 1;
-    const int max_pieces = (prows_full * kRowBytes + 1023) >> 10;
-    uint32_t* sm_cells = reinterpret_cast<uint32_t*>(sm_tile);
-    uint32_t* lpb = sm_cells + max_pieces * 256;
-    const int tb = lane_on || (idle && g < groups && dxi < cbx) ? (g * (R / 2)) * kRowBytes + 8 * dxi : 0;
-    const bool wave_live = __builtin_amdgcn_ballot_w64(lane_on && bx * cbx + dxi < job.nx &&
-                                                       row0 + g * R < job.ny) != 0;
+    uint32_t* lpb = win.lists;
+    const int lane = win.lane, wave = win.wave;
 
     uint32_t S0[R], K0[R], acc0[R], S1[R], K1[R], acc1[R];
 #pragma unroll
@@ -623,44 +588,21 @@ __device__ __forceinline__ void score_body_joint(const ScoreJob& job, int cbx, i
     const int ntiles = __builtin_amdgcn_readfirstlane(job.n_tiles[bid_y]);
     const TileRec* recs = job.tiles + (size_t)bid_y * job.max_tiles;
     const uint32_t* __restrict__ pbs = job.sorted_pb + (size_t)bid_y * 2 * job.n_points;
-    const size_t xg_pitch = (size_t)job.xg_pitch;
-    const size_t xg_row_bytes = xg_pitch * 8;
-    const char* xg = reinterpret_cast<const char*>(job.xg);
-    const int pad = job.xg_pad;
-
-    constexpr int kMaxP = ((((kTile + kPairMaxCby) / 2 + 1) * kRowBytes + 1023) / 1024 + 7) / 8;
-    uint32_t goff[kMaxP];
-#pragma unroll
-    for (int k = 0; k < kMaxP; ++k) {
-        const uint32_t ob = (uint32_t)(wave + 8 * k) * 1024u + (uint32_t)lane * 16u;
-        const uint32_t prow = ob / (uint32_t)kRowBytes, cb = ob - prow * (uint32_t)kRowBytes;
-        goff[k] = prow * (uint32_t)xg_row_bytes + cb;
-    }
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    typedef const __attribute__((address_space(1))) void* glb_ptr;
 
     TileRec rec;
     if (ntiles > 0)
         rec = recs[0];
     for (int ti = 0; ti < ntiles; ++ti) {
-        const int c00 = __builtin_amdgcn_readfirstlane(rec.c0) + x0;
-        const int gr0 = __builtin_amdgcn_readfirstlane(rec.r0) + y0;          /* even */
-        const int a = c00 & 1;
+        const int c00 = __builtin_amdgcn_readfirstlane(rec.c0) + win.x0;
+        const int gr0 = __builtin_amdgcn_readfirstlane(rec.r0) + win.y0;          /* even */
         const int cnt = __builtin_amdgcn_readfirstlane((int)rec.count);
         const int start = __builtin_amdgcn_readfirstlane((int)rec.start);
-        const int nprows = (__builtin_amdgcn_readfirstlane(rec.h) + cby) >> 1;
-        const int npieces = (nprows * kRowBytes + 1023) >> 10;
-        const char* src = xg + ((size_t)((gr0 + pad) >> 1) * xg_pitch + (size_t)((c00 & ~1) + pad)) * 8;
+        const int nprows = (__builtin_amdgcn_readfirstlane(rec.h) + win.cby) >> 1;
         if (ti + 1 < ntiles)
             rec = recs[ti + 1];
         __syncthreads();                                 /* previous tile consumed */
         __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-        for (int k = 0; k < kMaxP; ++k) {
-            const int pc = wave + 8 * k;
-            if (pc < npieces)
-                __builtin_amdgcn_global_load_lds((glb_ptr)(src + goff[k]), (lds_ptr)(sm_cells + pc * 256), 16, 0, 0);
-        }
+        win.copy(c00, gr0, nprows);
         static_assert(kJRec / 64 <= 8, "one list piece per wave");
         if (wave * 64 < cnt)
             __builtin_amdgcn_global_load_lds((glb_ptr)(pbs + start + wave * 64 + lane),
@@ -668,16 +610,17 @@ __device__ __forceinline__ void score_body_joint(const ScoreJob& job, int cbx, i
         __builtin_amdgcn_s_setprio(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        const uint32_t lane_addr = lds_address(sm_cells) + (uint32_t)(tb + 8 * a);
-        if (wave_live)
-            joint_gather<LS, R>(lane_addr, lpb, lane, cnt, acc0, S0, K0, fs0, acc1, S1, K1, fs1);
+        if (win.wave_live)
+            joint_gather<LS, R>(win.lane_addr(c00), lpb, lane, cnt, acc0, S0, K0, fs0, acc1, S1, K1, fs1);
     }
     pairs_finish<R>(acc0, S0, K0);
     pairs_finish<R>(acc1, S1, K1);
-    score_epilogue<R>(job, S0, K0, t0, bx, 1, cbx, row0, g, dxi, lane_on, qflags, bid_x + bb.cb_base, bb.ncb);
+    score_epilogue<R>(job, S0, K0, t0, win.bx, 1, cbx, win.row0, win.g, win.dxi, win.lane_on, qflags,
+                      bid_x + bb.cb_base, bb.ncb);
     if (two) {
         __syncthreads();                                 /* the epilogue's reduction arrays */
-        score_epilogue<R>(job, S1, K1, t1, bx, 1, cbx, row0, g, dxi, lane_on, qflags, bid_x + bb.cb_base, bb.ncb);
+        score_epilogue<R>(job, S1, K1, t1, win.bx, 1, cbx, win.row0, win.g, win.dxi, win.lane_on, qflags,
+                          bid_x + bb.cb_base, bb.ncb);
     }
 }
 
@@ -903,7 +846,6 @@ template <int LS, int R>
 __device__ __forceinline__ void score_body_jointf(const ScoreJob& job, int cbx, int groups, const uint16_t* lane_map,
                                                   int bid_x, int bid_y, BlockBase bb)
 {
-    static_assert(R % 2 == 0 && LS % 2 == 0, "pair rows, 16-byte rows");
     extern __shared__ __attribute__((aligned(16))) uint16_t sm_tile[];
     __shared__ float red[2][kBlock / 64];
     const int t0 = 2 * bid_y, t1 = t0 + 1;
@@ -911,34 +853,12 @@ __device__ __forceinline__ void score_body_jointf(const ScoreJob& job, int cbx, 
     if (t0 >= n_theta || !job.approx_best)
         return;
     const bool two = t1 < n_theta;
-    const int tid = threadIdx.x;
-    const int ncbx = (job.nx + cbx - 1) / cbx;
-    const int bx = bid_x % ncbx, by = bid_x / ncbx;
-    const int cby = groups * R;
-    const int row0 = bb.row_base + by * cby;
-    if (row0 >= job.ny)
+    PairWindow<LS, R> win;
+    if (!win.open(job, job.xgf, sm_tile, cbx, groups, lane_map, bid_x, bb))
         return;
-    int dxi = tid % cbx, g = tid / cbx;
-    bool idle = false;
-    if (lane_map) {
-        const uint32_t m = lane_map[tid];
-        dxi = (int)(m & 255u);
-        g = (int)((m >> 8) & 127u);
-        idle = (m >> 15) != 0;
-    }
-    const bool lane_on = !idle && g < groups;
-    const int x0 = job.x_lo + bx * cbx;
-    const int y0 = job.y_lo + row0;
-    constexpr int kRowBytes = LS * 8;
-    const int prows_full = (kTile + cby) / 2 + 1;
-    const int max_pieces = (prows_full * kRowBytes + 1023) >> 10;
-    uint32_t* sm_cells = reinterpret_cast<uint32_t*>(sm_tile);
-    uint32_t* lpb = sm_cells + max_pieces * 256;                 /* [kJRec] entry words */
-    const int tb = lane_on || (idle && g < groups && dxi < cbx) ? (g * (R / 2)) * kRowBytes + 8 * dxi : 0;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool wave_live = __builtin_amdgcn_ballot_w64(lane_on && bx * cbx + dxi < job.nx &&
-                                                       row0 + g * R < job.ny) != 0;
+    uint32_t* lpb = win.lists;                                   /* [kJRec] entry words */
+    const int tid = win.tid, lane = win.lane, wave = win.wave;
+    const int bx = win.bx, row0 = win.row0, dxi = win.dxi, g = win.g;
 
     f32x2 ea[R / 2], oa[R / 2 + 1], eb[R / 2], ob[R / 2 + 1];
 #pragma unroll
@@ -951,34 +871,16 @@ __device__ __forceinline__ void score_body_jointf(const ScoreJob& job, int cbx, 
     const int ntiles = __builtin_amdgcn_readfirstlane(job.n_tiles[bid_y]);
     const TileRec* recs = job.tiles + (size_t)bid_y * job.max_tiles;
     const uint32_t* __restrict__ pbs = job.sorted_pb + (size_t)bid_y * 2 * job.n_points;
-    const size_t xg_pitch = (size_t)job.xg_pitch;
-    const size_t xg_row_bytes = xg_pitch * 8;
-    const char* xg = reinterpret_cast<const char*>(job.xgf);
-    const int pad = job.xg_pad;
-
-    constexpr int kMaxP = ((((kTile + kPairMaxCby) / 2 + 1) * kRowBytes + 1023) / 1024 + 7) / 8;
-    uint32_t goff[kMaxP];
-#pragma unroll
-    for (int k = 0; k < kMaxP; ++k) {
-        const uint32_t ob_ = (uint32_t)(wave + 8 * k) * 1024u + (uint32_t)lane * 16u;
-        const uint32_t prow = ob_ / (uint32_t)kRowBytes, cb = ob_ - prow * (uint32_t)kRowBytes;
-        goff[k] = prow * (uint32_t)xg_row_bytes + cb;
-    }
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    typedef const __attribute__((address_space(1))) void* glb_ptr;
 
     TileRec rec;
     if (ntiles > 0)
         rec = recs[0];
     for (int ti = 0; ti < ntiles; ++ti) {
-        const int c00 = __builtin_amdgcn_readfirstlane(rec.c0) + x0;
-        const int gr0 = __builtin_amdgcn_readfirstlane(rec.r0) + y0;
-        const int a = c00 & 1;
+        const int c00 = __builtin_amdgcn_readfirstlane(rec.c0) + win.x0;
+        const int gr0 = __builtin_amdgcn_readfirstlane(rec.r0) + win.y0;
         const int cnt = __builtin_amdgcn_readfirstlane((int)rec.count);
         const int start = __builtin_amdgcn_readfirstlane((int)rec.start);
-        const int nprows = (__builtin_amdgcn_readfirstlane(rec.h) + cby) >> 1;
-        const int npieces = (nprows * kRowBytes + 1023) >> 10;
-        const char* src = xg + ((size_t)((gr0 + pad) >> 1) * xg_pitch + (size_t)((c00 & ~1) + pad)) * 8;
+        const int nprows = (__builtin_amdgcn_readfirstlane(rec.h) + win.cby) >> 1;
         if (ti + 1 < ntiles)
             rec = recs[ti + 1];
         /* this thread's entry of the record */
@@ -987,25 +889,19 @@ __device__ __forceinline__ void score_body_jointf(const ScoreJob& job, int cbx, 
             my_w = pbs[start + tid];
         __syncthreads();                                 /* previous tile consumed */
         __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-        for (int k = 0; k < kMaxP; ++k) {
-            const int pc = wave + 8 * k;
-            if (pc < npieces)
-                __builtin_amdgcn_global_load_lds((glb_ptr)(src + goff[k]), (lds_ptr)(sm_cells + pc * 256), 16, 0, 0);
-        }
+        win.copy(c00, gr0, nprows);
         __builtin_amdgcn_s_setprio(0);
         static_assert(kJRec <= kBlock, "one entry per thread");
         if (tid < cnt)
             lpb[tid] = my_w;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        const uint32_t lane_addr = lds_address(sm_cells) + (uint32_t)(tb + 8 * a);
 #ifndef CSM_ABL_NOGATHER       /* timing builds only (tools/build_variant.sh): what the tile loop costs without its gather */
-        if (wave_live)
-            joint_gather_f<LS, R>(lane_addr, lpb, lane, cnt, ea, oa, eb, ob);
+        if (win.wave_live)
+            joint_gather_f<LS, R>(win.lane_addr(c00), lpb, lane, cnt, ea, oa, eb, ob);
 #else
-        if (wave_live && cnt < 0)
-            joint_gather_f<LS, R>(lane_addr, lpb, lane, cnt, ea, oa, eb, ob);
+        if (win.wave_live && cnt < 0)
+            joint_gather_f<LS, R>(win.lane_addr(c00), lpb, lane, cnt, ea, oa, eb, ob);
 #endif
     }
 
@@ -1014,7 +910,7 @@ __device__ __forceinline__ void score_body_jointf(const ScoreJob& job, int cbx, 
     float best0 = 0.f, best1 = 0.f;
     float* const dump_f = job.dump_f;
     const float unscale = pow2f(149 - kKeyScaleLog2);      /* back to key units: exact */
-    if (lane_on && xi < job.nx) {
+    if (win.lane_on && xi < job.nx) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int yi = row0 + g * R + r;

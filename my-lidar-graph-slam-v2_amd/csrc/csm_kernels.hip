@@ -11,6 +11,10 @@
  *                and gathers from LDS for its own R candidate offsets, exact
  *                integer (S, K); a wave64 shuffle arg-max, one record per workgroup
  *                (k_argmax: that end alone, after a tile-split launch).
+ *                The pair-row bodies (score_body_pairs, score_body_pairs2) share
+ *                their window stager with the joint bodies of csm_joint_kernels.hip:
+ *                PairWindow, and the flush rule of the packed accumulators,
+ *                flush_flags / flush_packed (csm_score_common.hpp).
  *                Replaces ComputeScore inside the sweep of
  *                src/mapping/scan_matcher_correlative.cpp:161-197, 301-368 and
  *                ScorePixelAccurate::Score per branch-and-bound node
@@ -849,17 +853,6 @@ __device__ __forceinline__ void pairs_gather(uint32_t lane_addr, const uint32_t*
                                              uint32_t (&S)[R], uint32_t (&K)[R], FlushState& fs)
 {
     constexpr int kRowBytes = LS * 8;
-    /* S collects the whole packed word (value sum + known count << 23, modulo 2^32), K the
-     * count; pairs_finish() takes the count back out. One instruction per row less than
-     * splitting the word here (the flushes are 6 % of the kernel). */
-    auto flush = [&]() {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            S[r] += acc[r];
-            K[r] += acc[r] >> 23;
-            acc[r] = 0;
-        }
-    };
     auto issue = [&](uint32_t pbv, auto cls, unsigned long long (&q)[R / 2 + 1]) {
         constexpr int CLS = decltype(cls)::value;
         const uint32_t addr = lane_addr + (pbv & 0x7ffffu);
@@ -921,18 +914,7 @@ __device__ __forceinline__ void pairs_gather(uint32_t lane_addr, const uint32_t*
     auto load_chunk = [&](int j0) {
         pb_cur = lpb[j0 + lane];
         const int b = j0 + lane < cnt ? (int)((pb_cur >> 19) & 31u) : 0;
-        const int c1 = fs.cum + wave_prefix_sum(b), c0 = c1 - b;        /* < 96 + 64 * 30 */
-        const bool cross = ((uint32_t)c1 * 683u) >> 16 != ((uint32_t)c0 * 683u) >> 16;   /* floor(c / 96), c < 2900 */
-        const unsigned long long heavy = __builtin_amdgcn_ballot_w64(b > 8);
-        flags = __builtin_amdgcn_ballot_w64(cross) | heavy | heavy << 1 | heavy << 2 | heavy << 3 | heavy << 4 |
-                (fs.carry ? 0xfull : 0ull);
-        /* a heavy entry among the last four REAL entries of this chunk flags the first group
-         * of the next chunk -- also when that chunk is the next tile's list (acc[] and cum
-         * live on across tiles, and a list normally ends in a partial chunk: looking at
-         * lanes 60..63 only lost the flag there and let 152 beams pile up) */
-        const int last = min(64, cnt - j0);
-        fs.carry = (heavy >> max(0, last - 4)) != 0;
-        fs.cum = __builtin_amdgcn_readlane(c1, 63) % 96;
+        flags = flush_flags(b, min(64, cnt - j0), fs);
     };
     int j = 0;
     load_chunk(0);
@@ -948,7 +930,7 @@ __device__ __forceinline__ void pairs_gather(uint32_t lane_addr, const uint32_t*
                 const uint32_t o2 = (uint32_t)__builtin_amdgcn_readlane((int)pb_cur, (j + 2) & 63);
                 const uint32_t o3 = (uint32_t)__builtin_amdgcn_readlane((int)pb_cur, (j + 3) & 63);
                 if ((flags >> (j & 63)) & 0xfull)
-                    flush();
+                    flush_packed(acc, S, K);
                 unsigned long long qa[NQ], qb[NQ], qc[NQ], qd[NQ];
                 issue(o0, cls, qa);
                 issue(o1, cls, qb);
@@ -966,7 +948,7 @@ __device__ __forceinline__ void pairs_gather(uint32_t lane_addr, const uint32_t*
             for (; j < stop; ++j) {
                 const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)pb_cur, j & 63);
                 if ((flags >> (j & 63)) & 1ull)
-                    flush();
+                    flush_packed(acc, S, K);
                 unsigned long long qa[NQ];
                 issue(o, cls, qa);
                 lds_wait<0, NQ>(qa);
@@ -1000,47 +982,11 @@ __device__ __forceinline__ void score_body_pairs(const ScoreJob& job, int cbx, i
                                                  int n_slices, int t, int cb, const uint16_t* lane_map,
                                                  BlockBase bb)
 {
-    static_assert(R % 2 == 0 && LS % 2 == 0, "pair rows, 16-byte rows");
     extern __shared__ __attribute__((aligned(16))) uint16_t sm_tile[];
     if (t >= job.n_theta)
         return;
-    const int tid = threadIdx.x;
-    const int ncbx = (job.nx + cbx - 1) / cbx;
-    const int bx = cb % ncbx, by = cb / ncbx;
-    const int cby = groups * R;
-    const int row0 = bb.row_base + by * cby;         /* first candidate row of this workgroup */
-    if (row0 >= job.ny)
-        return;
-    const uint32_t qflags = job.elig_only_if_band ? *job.flags : 0u;
-
-    /* which candidate column and lane group this thread owns: in thread order, or by the
-     * host's table that keeps half-waves free of bank conflicts (lane_map_for, csm_api.hip) */
-    int dxi = tid % cbx, g = tid / cbx;
-    bool idle = false;
-    if (lane_map) {
-        const uint32_t m = lane_map[tid];
-        dxi = (int)(m & 255u);
-        g = (int)((m >> 8) & 127u);
-        idle = (m >> 15) != 0;
-    }
-    const bool lane_on = !idle && g < groups;
-    const int x0 = job.x_lo + bx * cbx;
-    const int y0 = job.y_lo + row0;
-    constexpr int kRowBytes = LS * 8;                   /* one pair row of the region */
-    const int prows_full = (kTile + cby) / 2 + 1;
-    const int max_pieces = (prows_full * kRowBytes + 1023) >> 10;
-    uint32_t* sm_cells = reinterpret_cast<uint32_t*>(sm_tile);
-    uint32_t* lpb = sm_cells + max_pieces * 256;
-    /* idle lanes of the table read the slot it gives them (a bank pair of their own) */
-    const int tb = lane_on || (idle && g < groups && dxi < cbx) ? (g * (R / 2)) * kRowBytes + 8 * dxi : 0;      /* bytes */
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    /* a wave none of whose lanes owns a candidate inside the window (the last row block
-     * of 84 rows in blocks of 48: rows 88..95) copies windows and keeps the barriers,
-     * but gathers nothing */
-    const bool wave_live = __builtin_amdgcn_ballot_w64(lane_on && bx * cbx + dxi < job.nx &&
-                                                       row0 + g * R < job.ny) != 0;
-
+    /* (accumulators and the slice's lists before the stager opens: with that order k_score_pairs, which
+     * holds this body twice, keeps its registers -- <86, 8, true> stays at 80 VGPRs, six waves per SIMD) */
     uint32_t S[R], K[R], acc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -1053,25 +999,13 @@ __device__ __forceinline__ void score_body_pairs(const ScoreJob& job, int cbx, i
     const int ntiles = job.n_tiles[t];
     const TileRec* recs = job.tiles + (size_t)t * job.max_tiles;
     const uint32_t* __restrict__ pbs = job.sorted_pb + (size_t)t * job.n_points;
-    /* every job field the tile loop needs, read once: `job` lives in global memory and
-     * a read inside the loop is a load per tile (a stray one cost 7 % of the kernel) */
-    const size_t xg_pitch = (size_t)job.xg_pitch;
-    const size_t xg_row_bytes = xg_pitch * 8;
-    const char* xg = reinterpret_cast<const char*>(job.xg);
-    const int pad = job.xg_pad;
 
-    /* piece pc = wave + 8 k of the region (LDS bytes [1024 pc, 1024 pc + 1024)): this
-     * lane's 16 bytes sit in pair row prow at byte cb of it */
-    constexpr int kMaxP = ((((kTile + kPairMaxCby) / 2 + 1) * kRowBytes + 1023) / 1024 + 7) / 8;
-    uint32_t goff[kMaxP];
-#pragma unroll
-    for (int k = 0; k < kMaxP; ++k) {
-        const uint32_t ob = (uint32_t)(wave + 8 * k) * 1024u + (uint32_t)lane * 16u;
-        const uint32_t prow = ob / (uint32_t)kRowBytes, cb = ob - prow * (uint32_t)kRowBytes;
-        goff[k] = prow * (uint32_t)xg_row_bytes + cb;
-    }
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    typedef const __attribute__((address_space(1))) void* glb_ptr;
+    PairWindow<LS, R> win;
+    if (!win.open(job, job.xg, sm_tile, cbx, groups, lane_map, cb, bb))
+        return;
+    const uint32_t qflags = job.elig_only_if_band ? *job.flags : 0u;
+    uint32_t* lpb = win.lists;
+    const int lane = win.lane, wave = win.wave;
 
     TileRec rec;
     int ti = slice;
@@ -1080,26 +1014,18 @@ __device__ __forceinline__ void score_body_pairs(const ScoreJob& job, int cbx, i
     for (; ti < ntiles; ti += n_slices) {
         /* wave-uniform values, told to the compiler as such: the entry loops then run
          * on scalar registers and scalar branches */
-        const int c00 = __builtin_amdgcn_readfirstlane(rec.c0) + x0;
-        const int gr0 = __builtin_amdgcn_readfirstlane(rec.r0) + y0;          /* even */
-        const int a = c00 & 1;
+        const int c00 = __builtin_amdgcn_readfirstlane(rec.c0) + win.x0;
+        const int gr0 = __builtin_amdgcn_readfirstlane(rec.r0) + win.y0;          /* even */
         const int cnt = __builtin_amdgcn_readfirstlane((int)rec.count);
         const int start = __builtin_amdgcn_readfirstlane((int)rec.start);
-        const int nprows = (__builtin_amdgcn_readfirstlane(rec.h) + cby) >> 1;
+        const int nprows = (__builtin_amdgcn_readfirstlane(rec.h) + win.cby) >> 1;
         const int classes = __builtin_amdgcn_readfirstlane(rec.pad[0]);
         const int end_both = classes & 0xffff;
         const int end_even = end_both + (classes >> 16);
-        const int npieces = (nprows * kRowBytes + 1023) >> 10;
-        const char* src = xg + ((size_t)((gr0 + pad) >> 1) * xg_pitch + (size_t)((c00 & ~1) + pad)) * 8;
         if (ti + n_slices < ntiles)
             rec = recs[ti + n_slices];
         __syncthreads();                                 /* previous tile consumed */
-#pragma unroll
-        for (int k = 0; k < kMaxP; ++k) {
-            const int pc = wave + 8 * k;
-            if (pc < npieces)
-                __builtin_amdgcn_global_load_lds((glb_ptr)(src + goff[k]), (lds_ptr)(sm_cells + pc * 256), 16, 0, 0);
-        }
+        win.copy(c00, gr0, nprows);
 #pragma unroll
         for (int e = 0; e < kPbMax / 64 / 8; ++e) {
             const int pe = wave + 8 * e;
@@ -1110,13 +1036,13 @@ __device__ __forceinline__ void score_body_pairs(const ScoreJob& job, int cbx, i
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
 
-        const uint32_t lane_addr = lds_address(sm_cells) + (uint32_t)(tb + 8 * a);
-        if (wave_live)
-            pairs_gather<LS, R, WEIGHTED>(lane_addr, lpb, lane, cnt, end_both, end_even, acc, S, K, fs);
+        if (win.wave_live)
+            pairs_gather<LS, R, WEIGHTED>(win.lane_addr(c00), lpb, lane, cnt, end_both, end_even, acc, S, K, fs);
     }
     pairs_finish<R>(acc, S, K);
     /* the epilogue wants the row block as (by, cby) and uses only their product */
-    score_epilogue<R>(job, S, K, t, bx, 1, cbx, row0, g, dxi, lane_on, qflags, cb + bb.cb_base, bb.ncb);
+    score_epilogue<R>(job, S, K, t, win.bx, 1, cbx, win.row0, win.g, win.dxi, win.lane_on, qflags, cb + bb.cb_base,
+                      bb.ncb);
 }
 
 /* ---- two theta slices per workgroup ---------------------------------------
@@ -1132,7 +1058,6 @@ template <int LS, int R, bool WEIGHTED>
 __device__ __forceinline__ void score_body_pairs2(const ScoreJob& job, int cbx, int groups, const uint16_t* lane_map,
                                                   int bid_x, int bid_y, BlockBase bb)
 {   /* bid_x: candidate block, bid_y: pair of theta slices (the kernel's, after its XCD mapping) */
-    static_assert(R % 2 == 0 && LS % 2 == 0, "pair rows, 16-byte rows");
     extern __shared__ __attribute__((aligned(16))) uint16_t sm_tile[];
     const int t0 = 2 * bid_y, t1 = t0 + 1;
     /* values loaded from the job are uniform, but only readfirstlane tells the compiler:
@@ -1141,41 +1066,14 @@ __device__ __forceinline__ void score_body_pairs2(const ScoreJob& job, int cbx, 
     if (t0 >= n_theta)
         return;
     const bool two = t1 < n_theta;
-    const int tid = threadIdx.x;
-    const int ncbx = (job.nx + cbx - 1) / cbx;
-    const int bx = bid_x % ncbx, by = bid_x / ncbx;
-    const int cby = groups * R;
-    const int row0 = bb.row_base + by * cby;         /* first candidate row of this workgroup */
-    if (row0 >= job.ny)
+    PairWindow<LS, R> win;
+    if (!win.open(job, job.xg, sm_tile, cbx, groups, lane_map, bid_x, bb))
         return;
     const uint32_t qflags = job.elig_only_if_band ? *job.flags : 0u;
-
-    /* which candidate column and lane group this thread owns: in thread order, or by the
-     * host's table that keeps half-waves free of bank conflicts (lane_map_for, csm_api.hip) */
-    int dxi = tid % cbx, g = tid / cbx;
-    bool idle = false;
-    if (lane_map) {
-        const uint32_t m = lane_map[tid];
-        dxi = (int)(m & 255u);
-        g = (int)((m >> 8) & 127u);
-        idle = (m >> 15) != 0;
-    }
-    const bool lane_on = !idle && g < groups;
-    const int x0 = job.x_lo + bx * cbx;
-    const int y0 = job.y_lo + row0;
     constexpr int kRowBytes = LS * 8;
-    const int prows_full = (kTile + cby) / 2 + 1;
-    const int max_pieces = (prows_full * kRowBytes + 1023) >> 10;
-    uint32_t* sm_cells = reinterpret_cast<uint32_t*>(sm_tile);
-    uint32_t* lpb0 = sm_cells + max_pieces * 256;
+    uint32_t* lpb0 = win.lists;
     uint32_t* lpb1 = lpb0 + kPbMax;
-    /* idle lanes of the table read the slot it gives them (a bank pair of their own) */
-    const int tb = lane_on || (idle && g < groups && dxi < cbx) ? (g * (R / 2)) * kRowBytes + 8 * dxi : 0;      /* bytes */
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    /* see score_body_pairs: waves without a candidate inside the window do not gather */
-    const bool wave_live = __builtin_amdgcn_ballot_w64(lane_on && bx * cbx + dxi < job.nx &&
-                                                       row0 + g * R < job.ny) != 0;
+    const int lane = win.lane, wave = win.wave;
 
     uint32_t S0[R], K0[R], acc0[R], S1[R], K1[R], acc1[R];
 #pragma unroll
@@ -1189,21 +1087,6 @@ __device__ __forceinline__ void score_body_pairs2(const ScoreJob& job, int cbx, 
     const TileRec* recs1 = job.tiles + (size_t)t1 * job.max_tiles;
     const uint32_t* __restrict__ pbs0 = job.sorted_pb + (size_t)t0 * job.n_points;
     const uint32_t* __restrict__ pbs1 = job.sorted_pb + (size_t)t1 * job.n_points;
-    const size_t xg_pitch = (size_t)job.xg_pitch;
-    const size_t xg_row_bytes = xg_pitch * 8;
-    const char* xg = reinterpret_cast<const char*>(job.xg);
-    const int pad = job.xg_pad;
-
-    constexpr int kMaxP = ((((kTile + kPairMaxCby) / 2 + 1) * kRowBytes + 1023) / 1024 + 7) / 8;
-    uint32_t goff[kMaxP];
-#pragma unroll
-    for (int k = 0; k < kMaxP; ++k) {
-        const uint32_t ob = (uint32_t)(wave + 8 * k) * 1024u + (uint32_t)lane * 16u;
-        const uint32_t prow = ob / (uint32_t)kRowBytes, cb = ob - prow * (uint32_t)kRowBytes;
-        goff[k] = prow * (uint32_t)xg_row_bytes + cb;
-    }
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    typedef const __attribute__((address_space(1))) void* glb_ptr;
 
     TileRec ra, rb;
     int i0 = 0, i1 = 0;
@@ -1232,15 +1115,12 @@ __device__ __forceinline__ void score_body_pairs2(const ScoreJob& job, int cbx, 
         const int ru = use0 && use1 ? min(r00, r01) : use0 ? r00 : r01;
         const int cu = use0 && use1 ? min(c00_, c01_) : use0 ? c00_ : c01_;
         const int re = use0 && use1 ? max(r00 + h0, r01 + h1) : use0 ? r00 + h0 : r01 + h1;
-        const int c00 = cu + x0;
-        const int gr0 = ru + y0;
-        const int a = c00 & 1;
-        const int nprows = (re - ru + cby) >> 1;
-        const int npieces = (nprows * kRowBytes + 1023) >> 10;
+        const int c00 = cu + win.x0;
+        const int gr0 = ru + win.y0;
+        const int nprows = (re - ru + win.cby) >> 1;
         /* where each slice's box starts inside the staged window, bytes */
         const int shift0 = ((r00 - ru) >> 1) * kRowBytes + (c00_ - cu) * 8;
         const int shift1 = ((r01 - ru) >> 1) * kRowBytes + (c01_ - cu) * 8;
-        const char* src = xg + ((size_t)((gr0 + pad) >> 1) * xg_pitch + (size_t)((c00 & ~1) + pad)) * 8;
         if (use0 && ++i0 < n0)
             ra = recs0[i0];
         if (use1 && ++i1 < n1)
@@ -1248,12 +1128,7 @@ __device__ __forceinline__ void score_body_pairs2(const ScoreJob& job, int cbx, 
         __syncthreads();                                 /* previous tile consumed */
         __builtin_amdgcn_s_setprio(3);                   /* the copy's requests go out ahead of the other
                                                             workgroup's gather instructions (-0.35 %) */
-#pragma unroll
-        for (int k = 0; k < kMaxP; ++k) {
-            const int pc = wave + 8 * k;
-            if (pc < npieces)
-                __builtin_amdgcn_global_load_lds((glb_ptr)(src + goff[k]), (lds_ptr)(sm_cells + pc * 256), 16, 0, 0);
-        }
+        win.copy(c00, gr0, nprows);
 #pragma unroll
         for (int e = 0; e < kPbMax / 64 / 8; ++e) {
             const int pe = wave + 8 * e;
@@ -1267,20 +1142,22 @@ __device__ __forceinline__ void score_body_pairs2(const ScoreJob& job, int cbx, 
         __builtin_amdgcn_s_setprio(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        const uint32_t lane_addr = lds_address(sm_cells) + (uint32_t)(tb + 8 * a);
-        if (wave_live && cnt0 > 0)
+        const uint32_t lane_addr = win.lane_addr(c00);
+        if (win.wave_live && cnt0 > 0)
             pairs_gather<LS, R, WEIGHTED>(lane_addr + (uint32_t)shift0, lpb0, lane, cnt0, cls0 & 0xffff,
                                           (cls0 & 0xffff) + (cls0 >> 16), acc0, S0, K0, fs0);
-        if (wave_live && cnt1 > 0)
+        if (win.wave_live && cnt1 > 0)
             pairs_gather<LS, R, WEIGHTED>(lane_addr + (uint32_t)shift1, lpb1, lane, cnt1, cls1 & 0xffff,
                                           (cls1 & 0xffff) + (cls1 >> 16), acc1, S1, K1, fs1);
     }
     pairs_finish<R>(acc0, S0, K0);
     pairs_finish<R>(acc1, S1, K1);
-    score_epilogue<R>(job, S0, K0, t0, bx, 1, cbx, row0, g, dxi, lane_on, qflags, bid_x + bb.cb_base, bb.ncb);
+    score_epilogue<R>(job, S0, K0, t0, win.bx, 1, cbx, win.row0, win.g, win.dxi, win.lane_on, qflags,
+                      bid_x + bb.cb_base, bb.ncb);
     if (two) {
         __syncthreads();                                 /* the epilogue's reduction arrays */
-        score_epilogue<R>(job, S1, K1, t1, bx, 1, cbx, row0, g, dxi, lane_on, qflags, bid_x + bb.cb_base, bb.ncb);
+        score_epilogue<R>(job, S1, K1, t1, win.bx, 1, cbx, win.row0, win.g, win.dxi, win.lane_on, qflags,
+                          bid_x + bb.cb_base, bb.ncb);
     }
 }
 

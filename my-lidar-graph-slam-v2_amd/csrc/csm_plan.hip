@@ -227,8 +227,7 @@ using csm_launch::kPairR;
 
 size_t pair_lds_bytes(int ls, int cby, int lists)
 {
-    const size_t region = (size_t)((kTile + cby) / 2 + 1) * ls * 8;
-    return ((region + 1023) / 1024) * 1024 + (size_t)lists * kPbMax * 4;
+    return (size_t)pair_window_pieces(ls, cby) * 1024 + (size_t)lists * kPbMax * 4;
 }
 
 /* two_slices: plan for the batch kernel that takes two theta slices per workgroup
@@ -581,8 +580,8 @@ csm_launch::ScoreLaunch score_launch(const csm_ctx* ctx, const PassPlan& pp, dim
  * first 32 * floor(cbx / 32) columns and deals the remaining columns of all groups to the
  * remaining half-waves so that a half-wave holds each bank pair once; what cannot be placed
  * that way is collected in the last half-waves (cbx = 84, 6 groups, LS = 150: 17 passes per
- * wave-round of reads instead of 21). Entry = idle << 15 | g << 8 | dxi; 0xffff = idle lane without
- * a slot of its own. Returns null
+ * wave-round of reads instead of 21). Entry = lane_word(g, dxi, idle), kLaneNone = idle lane without
+ * a slot of its own (csm_device.hpp). Returns null
  * (threads in order) where the table would not save a pass. */
 int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out)
 {
@@ -603,23 +602,23 @@ int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out)
         for (int h = 0; h < nhw; ++h) {
             int cnt[32] = { 0 }, worst = 0;
             for (int l = 0; l < 32; ++l)
-                if (t[h * 32 + l] != 0xffff)
-                    worst = std::max(worst, ++cnt[pos((t[h * 32 + l] >> 8) & 127, t[h * 32 + l] & 255)]);
+                if (t[h * 32 + l] != kLaneNone)
+                    worst = std::max(worst, ++cnt[pos(lane_word_g(t[h * 32 + l]), lane_word_dxi(t[h * 32 + l]))]);
             total += worst;
         }
         return total;
     };
-    std::vector<uint16_t> linear(kBlock, 0xffff), table(kBlock, 0xffff);
+    std::vector<uint16_t> linear(kBlock, kLaneNone), table(kBlock, kLaneNone);
     for (int tid = 0; tid < kBlock; ++tid)
         if (tid / pp.cbx < pp.groups)
-            linear[tid] = (uint16_t)((tid / pp.cbx) << 8 | (tid % pp.cbx));
+            linear[tid] = lane_word(tid / pp.cbx, tid % pp.cbx);
     if (pp.cbx > 255 || pp.groups > 127 || pp.groups * nfull >= nhw)
         return CSM_OK;
     int hw = 0;
     for (int g = 0; g < pp.groups; ++g)
         for (int k = 0; k < nfull; ++k, ++hw)
             for (int l = 0; l < 32; ++l)
-                table[hw * 32 + l] = (uint16_t)(g << 8 | (32 * k + l));
+                table[hw * 32 + l] = lane_word(g, 32 * k + l);
     const int nrem = nhw - hw;
     std::vector<std::vector<uint16_t>> lists(nrem);
     std::vector<uint16_t> extra;
@@ -627,7 +626,7 @@ int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out)
     for (int g = 0; g < pp.groups; ++g)
         for (int c = 32 * nfull; c < pp.cbx; ++c) {
             const int i = seen[pos(g, c)]++;
-            const uint16_t v = (uint16_t)(g << 8 | c);
+            const uint16_t v = lane_word(g, c);
             if (i < nrem && lists[i].size() < 32)
                 lists[i].push_back(v);
             else
@@ -645,7 +644,7 @@ int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out)
         bool used[32] = { false };
         for (size_t l = 0; l < lists[h].size(); ++l) {
             table[(hw + h) * 32 + l] = lists[h][l];
-            used[pos(lists[h][l] >> 8, lists[h][l] & 255)] = true;
+            used[pos(lane_word_g(lists[h][l]), lane_word_dxi(lists[h][l]))] = true;
         }
         /* idle lanes read too (the instruction is the wave's): each gets a slot of its own on a
          * bank pair the half-wave does not use (group 0, column q), marked idle by bit 15 */
@@ -654,7 +653,7 @@ int lane_map_for(csm_ctx* ctx, const PassPlan& pp, const uint16_t** out)
             while (q < 32 && (used[q] || q >= pp.cbx))
                 ++q;
             if (q < 32) {
-                table[(hw + h) * 32 + l] = (uint16_t)(0x8000 | q);
+                table[(hw + h) * 32 + l] = lane_word(0, q, true);
                 used[q] = true;
             }
         }

@@ -1,7 +1,8 @@
 /* csm_score_common.hpp -- device functions shared by the scoring kernels of
  * csm_kernels.hip and csm_joint_kernels.hip (separate translation units of libcsm_hip.so):
  * the workgroup epilogue (eligibility, bound check, wave64 arg-max), the hand-issued LDS
- * reads, the flush bookkeeping of the packed accumulators and the XCD-aware block order; and what
+ * reads, the window stager of the pair-row kernels (PairWindow), the flush rule of the packed
+ * accumulators (flush_flags, flush_packed) and the XCD-aware block order; and what
  * the other kernel units share with them: wave_sum, prefix_find and, through csm_certify.hpp, the
  * projection certificate. */
 #ifndef CSM_SCORE_COMMON_HPP
@@ -276,7 +277,109 @@ __device__ __forceinline__ void lds_wait(unsigned long long (&q)[N])
         asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(q[0]), "+v"(q[1]) : "n"(LATER));
 }
 
+/* operands of global_load_lds (LDS-DMA): a per-lane global source, a wave-uniform LDS destination */
+typedef __attribute__((address_space(3))) void* lds_ptr;
+typedef const __attribute__((address_space(1))) void* glb_ptr;
 
+/* The window stager of the pair-row fine kernels (score_body_pairs / _pairs2 in csm_kernels.hip,
+ * score_body_joint / _jointf in csm_joint_kernels.hip). A workgroup scores a block of cbx x cby candidate
+ * offsets, cby = groups * R; a lane owns candidate column dxi of the block and the R rows of lane group g.
+ * Per record the workgroup copies a window of the level's pair-row copy (k_expand_pairs: 8-byte slots,
+ * LS slots per pair row of the window) into LDS by DMA in 1-KiB pieces, piece pc by wave pc mod 8, and the
+ * lanes gather from it with hand-issued ds_read_b64. The struct is what the four bodies share: the
+ * candidate-block and lane-table decode, the LDS layout (window, then the entry lists), the per-lane piece
+ * offsets, the source address of a window and the lane's read address in it. The record walk, the list
+ * staging, the barriers and waits around the copy, the gather and the epilogue stay in the bodies. */
+template <int LS, int R>
+struct PairWindow {
+    static_assert(R % 2 == 0 && LS % 2 == 0, "pair rows, 16-byte rows");
+    static constexpr int kRowBytes = LS * 8;            /* one pair row of the window */
+    static constexpr int kMaxP = (pair_window_pieces(LS, kPairMaxCby) + 7) / 8;      /* pieces per wave */
+    int tid, lane, wave;
+    int bx, cby, row0;          /* candidate block column; rows per block; first candidate row of this workgroup */
+    int dxi, g;
+    int x0, y0;                 /* cell offset of the block's first candidate */
+    int tb;                     /* byte offset of the lane's first slot in a window whose first column is even */
+    bool lane_on, wave_live;
+    uint32_t* sm_cells;         /* the window copy */
+    uint32_t* lists;            /* the entry lists behind it */
+    const char* xg;
+    int xg_pitch;
+    int pad;
+    uint32_t goff[kMaxP];
+
+    /* copy: the level's pair-row copy the windows come from (job.xg, or job.xgf for the fp32 pass); sm: the
+     * kernel's dynamic LDS; bid_x: candidate block of the launch. False: the block lies behind the window's
+     * last row (the tail launch of a row-block split, BlockBase), the workgroup has nothing to do. The test
+     * is the last statement on purpose: a return from the middle, with half the members unset on one path,
+     * cost the callers one or two VGPRs, and some shapes an occupancy step with them. */
+    __device__ __forceinline__ bool open(const ScoreJob& job, const void* copy, void* sm, int cbx, int groups,
+                                         const uint16_t* lane_map, int bid_x, const BlockBase& bb)
+    {
+        tid = threadIdx.x;
+        const int ncbx = (job.nx + cbx - 1) / cbx;
+        bx = bid_x % ncbx;
+        cby = groups * R;
+        row0 = bb.row_base + (bid_x / ncbx) * cby;
+        /* which candidate column and lane group this thread owns: in thread order, or by the host's
+         * table that keeps half-waves free of bank conflicts (lane_map_for, csm_plan.hip) */
+        dxi = tid % cbx;
+        g = tid / cbx;
+        bool idle = false;
+        if (lane_map) {
+            const uint32_t m = lane_map[tid];
+            dxi = lane_word_dxi(m);
+            g = lane_word_g(m);
+            idle = lane_word_idle(m);
+        }
+        lane_on = !idle && g < groups;
+        x0 = job.x_lo + bx * cbx;
+        y0 = job.y_lo + row0;
+        sm_cells = reinterpret_cast<uint32_t*>(sm);
+        lists = sm_cells + pair_window_pieces(LS, cby) * 256;
+        /* idle lanes of the table read the slot it gives them (a bank pair of their own) */
+        tb = lane_on || (idle && g < groups && dxi < cbx) ? (g * (R / 2)) * kRowBytes + 8 * dxi : 0;
+        lane = tid & 63;
+        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        /* a wave none of whose lanes owns a candidate inside the window (the last row block of 84 rows
+         * in blocks of 48: rows 88..95) copies windows and keeps the barriers, but gathers nothing */
+        wave_live = __builtin_amdgcn_ballot_w64(lane_on && bx * cbx + dxi < job.nx && row0 + g * R < job.ny) != 0;
+        /* every job field the record loop needs, read once: `job` lives in global memory and a read
+         * inside the loop is a load per record (a stray one cost 7 % of the kernel) */
+        xg_pitch = job.xg_pitch;
+        xg = reinterpret_cast<const char*>(copy);
+        pad = job.xg_pad;
+        /* piece pc = wave + 8 k of the window (LDS bytes [1024 pc, 1024 pc + 1024)): this lane's 16 bytes
+         * sit in pair row prow at byte cb of it */
+#pragma unroll
+        for (int k = 0; k < kMaxP; ++k) {
+            const uint32_t ob = (uint32_t)(wave + 8 * k) * 1024u + (uint32_t)lane * 16u;
+            const uint32_t prow = ob / (uint32_t)kRowBytes, cb = ob - prow * (uint32_t)kRowBytes;
+            goff[k] = prow * (uint32_t)((size_t)xg_pitch * 8) + cb;
+        }
+        return row0 < job.ny;
+    }
+
+    /* The DMA of one window: nprows pair rows from cell row gr0 (even) and column c00 of the level, the
+     * column rounded down to an even one (16-byte pieces). Wave-uniform arguments. */
+    __device__ __forceinline__ void copy(int c00, int gr0, int nprows) const
+    {
+        const int npieces = (nprows * kRowBytes + 1023) >> 10;
+        const char* src = xg + ((size_t)((gr0 + pad) >> 1) * (size_t)xg_pitch + (size_t)((c00 & ~1) + pad)) * 8;
+#pragma unroll
+        for (int k = 0; k < kMaxP; ++k) {
+            const int pc = wave + 8 * k;
+            if (pc < npieces)
+                __builtin_amdgcn_global_load_lds((glb_ptr)(src + goff[k]), (lds_ptr)(sm_cells + pc * 256), 16, 0, 0);
+        }
+    }
+
+    /* LDS address of the lane's first slot in the window copied for column c00 (its parity is the shift) */
+    __device__ __forceinline__ uint32_t lane_addr(int c00) const
+    {
+        return lds_address(sm_cells) + (uint32_t)(tb + 8 * (c00 & 1));
+    }
+};
 
 /* Inclusive prefix sum over the wave's 64 lanes, data-parallel primitives only (no LDS
  * traffic: the gather counts its own LDS reads in lgkmcnt). */
@@ -305,6 +408,37 @@ struct FlushState {
     int cum;        /* beams gathered so far, modulo 96 */
     int carry;      /* a heavy entry among the last four of the previous chunk */
 };
+
+/* The flags of one chunk, one bit per entry: `beams` = the beams of this lane's entry (0 behind the last
+ * real one), n_real = real entries of the chunk (1 .. 64). A heavy entry among the last four REAL entries
+ * flags the first group of the next chunk -- also when that chunk is the next record's list (the
+ * accumulators and `cum` live on across records, and a list normally ends in a partial chunk: looking at
+ * lanes 60..63 only lost the flag there and let 152 beams pile up). */
+__device__ __forceinline__ unsigned long long flush_flags(int beams, int n_real, FlushState& fs)
+{
+    const int c1 = fs.cum + wave_prefix_sum(beams), c0 = c1 - beams;        /* < 96 + 64 * 30 */
+    const bool cross = ((uint32_t)c1 * 683u) >> 16 != ((uint32_t)c0 * 683u) >> 16;   /* floor(c / 96), c < 2900 */
+    const unsigned long long heavy = __builtin_amdgcn_ballot_w64(beams > 8);
+    const unsigned long long f = __builtin_amdgcn_ballot_w64(cross) | heavy | heavy << 1 | heavy << 2 |
+                                 heavy << 3 | heavy << 4 | (fs.carry ? 0xfull : 0ull);
+    fs.carry = (heavy >> max(0, n_real - 4)) != 0;
+    fs.cum = __builtin_amdgcn_readlane(c1, 63) % 96;
+    return f;
+}
+
+/* One flush. S collects the whole packed word (value sum + known count << 23, modulo 2^32), K the
+ * count; pairs_finish() takes the count back out. One instruction per row less than splitting the
+ * word here (the flushes are 6 % of the kernel). */
+template <int R>
+__device__ __forceinline__ void flush_packed(uint32_t (&acc)[R], uint32_t (&S)[R], uint32_t (&K)[R])
+{
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        S[r] += acc[r];
+        K[r] += acc[r] >> 23;
+        acc[r] = 0;
+    }
+}
 
 /* After the last record: the accumulators' rest, then the value sum alone
  * (S held sum + count << 23 modulo 2^32; the sum itself is below 2^27). */

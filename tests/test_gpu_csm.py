@@ -114,7 +114,7 @@ def test_saturated_grid_never_overflows_the_packed_accumulators(gpu_ctx, oracle,
 
 def test_lane_table_on_and_off_give_identical_sums(gpu_ctx, oracle):
     """The pair kernels take the thread -> (lane group, column) assignment from a host
-    table that keeps half-waves free of LDS bank conflicts (lane_map_for, csm_api.hip);
+    table that keeps half-waves free of LDS bank conflicts (lane_map_for, csm_plan.hip);
     CSM_TUNE_NO_LANE_MAP numbers the threads through the groups in order. Both must give
     every candidate's sums (84 x 84 window: 6 groups of 84 columns, the shape the table is for)."""
     case = synth.csm_case(21, n_beams=1080, fov=1.5 * math.pi)
