@@ -321,7 +321,9 @@ int BatchGroup::plan()
     joint = ctx->tune.joint && fine.pairs && fine.lists == 2 && fine.weighted &&
               binj_lds <= 150 * 1024;     /* up to ~1,100 beams four binning workgroups share a CU, two up
                                                to ~2,200; one (the fine level's gain outweighs the slower
-                                               binning) up to ~4,200 beams per scan */
+                                               binning) up to 4,248 beams per scan on maps of at most 32
+                                               endpoint tiles (153,264 B with 16 tiles; 4,249 beams take
+                                               154,036 B), 4,224 with 64 tiles: tests/beam_ladder_cases.py */
     fine.joint = joint;
     /* The packed-fp32 bound pass in front of the exact kernel: only where the arg-max is over ALL
      * candidates of the window -- the correlative sweep with a known-rate threshold that the coarse
