@@ -1569,6 +1569,115 @@ int  csm_host_loop_candidates_nearest(const csm_loop_candidate* cands, const int
                                       int32_t n_per_query, int32_t n_total, csm_loop_candidate* out,
                                       int32_t* n_out);
 
+/* ---- loop search by appearance: polar scan descriptors matched on the device (the 2D form of ring-and-sector
+ * "scan context" place recognition; the complement of csm_loop_search, which proposes by estimated pose) ----
+ *
+ * THE DESCRIPTOR of a scan is n_rings x n_sectors bytes, layout [ring][sector]: how many beams end in each
+ * cell of a polar grid around the sensor, saturated at 255. csm_descriptor_params: n_rings in 1..32,
+ * n_sectors a multiple of 4 in 4..128, range_min < range_max, both finite. Two edge tables, computed once on
+ * the host in f64 with exactly these expressions (the device receives the tables and never recomputes them):
+ *   ring_edge[k]   = range_min + ((range_max - range_min) * k) / n_rings,  k = 0..n_rings,   ring_edge[n_rings] = range_max
+ *   sector_edge[k] = -M_PI + (2.0 * M_PI * k) / n_sectors,                 k = 0..n_sectors, sector_edge[n_sectors] = M_PI
+ * A beam (a, r) is USED iff a and r are finite, ring_edge[0] <= r < ring_edge[n_rings] and sector_edge[0] <= a
+ * < sector_edge[n_sectors]. Its ring is the greatest k with ring_edge[k] <= r, its sector the greatest k with
+ * sector_edge[k] <= a: comparisons only, no division and no floor, so the bin is the same everywhere. A cell
+ * holds min(count, 255). Counts are integers: no result depends on the order of the beams.
+ * Scans are ragged: scan i is beams offsets[i] .. offsets[i + 1] of angles / ranges. out[n_scans * n_rings *
+ * n_sectors]; beams_used[i] = the used beams of scan i (the others, offsets[i + 1] - offsets[i] - beams_used[i],
+ * were not counted into any cell).
+ * CSM_EINVAL, on the host before any launch: a null pointer; n_scans outside 1..CSM_LOOP_SEARCH_MAX_NODES;
+ * offsets[0] != 0, offsets decreasing, or a scan of more than CSM_DESCRIPTOR_MAX_BEAMS beams; a parameter
+ * outside the ranges above.
+ *
+ * THE DISTANCE of descriptors Q (query) and R (reference), with S = n_sectors and a shift s in [0, S):
+ *   L1(s)         = sum over ring, sec of |Q[ring][(sec + s) mod S] - R[ring][sec]|
+ *   distance      = min over s of L1(s);  shift = the smallest s that attains it
+ *   ring_distance = sum over ring of |sum_sec Q[ring][sec] - sum_sec R[ring][sec]|
+ * ring_distance depends on no shift and never exceeds distance (a sum of absolute values is at least the
+ * absolute value of the sum). All integers: L1 <= 32 * 128 * 255 < 2^20.
+ * csm_host_descriptor_shift_angle: the heading difference theta_query - theta_ref a shift implies (a feature
+ * the reference sees at bearing b the query sees at b + shift * 2 pi / S), through NormalizeAngle:
+ *   t = std::fmod((-(double)shift * (2.0 * M_PI)) / (double)n_sectors, 2.0 * M_PI);
+ *   if (t > M_PI) t -= 2.0 * M_PI; else if (t < -M_PI) t += 2.0 * M_PI;
+ * CSM_EINVAL: a null pointer, n_sectors outside the range above, shift outside [0, n_sectors).
+ *
+ * THE SEARCH. descriptors[n_scan][n_rings * n_sectors]; scan_map_index, travel, n_ref, query_index and
+ * query_travel as csm_loop_search takes them (poses are not read). A pair (query q, reference node r) is
+ * ELIGIBLE iff
+ *   r < n_ref
+ *   scan_map_index[r] != scan_map_index[q]
+ *   !(query_travel[q] - travel[r] < travel_dist_threshold)        the prefix [0, p_q) of csm_loop_search
+ *   the byte sums of both descriptors are >= min_cell_sum          (a scan that saw almost nothing matches anything)
+ *   distance <= max_distance
+ * Order: (distance ascending, then r ascending), total. one_per_map and the cut to n_per_query exactly as in
+ * csm_loop_search. out[n_q * n_per_query], counts[n_q]; an unused slot is { query, -1, -1, 0, 0, 0 }. info (may
+ * be NULL): pairs_evaluated = the sum of the prefix lengths p_q, pairs_eligible = the eligible pairs before
+ * one_per_map and the cut; both exact. A pair with ring_distance > max_distance is not eligible whatever its
+ * shifts say, so both implementations skip its shift search; no output can tell.
+ * CSM_EINVAL, on the host before any launch: the list of csm_loop_search without the poses and the node
+ * threshold (a null pointer, info aside; a non-finite travel, query_travel or travel_dist_threshold; travel or
+ * scan_map_index decreasing; a map index outside [0, n_maps); n_scan, n_maps, n_ref, n_q, n_per_query,
+ * one_per_map outside their ranges; a query index out of range or repeated); a descriptor parameter outside
+ * its range; n_scan * n_rings * n_sectors > 2^30. */
+#define CSM_DESCRIPTOR_MAX_RINGS    32
+#define CSM_DESCRIPTOR_MAX_SECTORS  128
+#define CSM_DESCRIPTOR_MAX_BEAMS    65536
+#define CSM_APPEARANCE_REF_CHUNK    128           /* reference nodes of a query that one workgroup scores */
+#define CSM_APPEARANCE_TABLE_BYTES  (64u << 20)   /* the pair table of one chunk of queries: 4 bytes per pair */
+typedef struct {
+    int32_t n_rings;                /* 1..CSM_DESCRIPTOR_MAX_RINGS */
+    int32_t n_sectors;              /* 4..CSM_DESCRIPTOR_MAX_SECTORS, a multiple of 4 */
+    double  range_min, range_max;
+} csm_descriptor_params;
+
+typedef struct {
+    csm_descriptor_params descriptor;
+    double   travel_dist_threshold;
+    uint32_t max_distance;
+    uint32_t min_cell_sum;
+    int32_t  n_per_query;           /* K: 1..CSM_LOOP_SEARCH_MAX_K */
+    int32_t  one_per_map;           /* 0 | 1 */
+} csm_appearance_params;
+
+typedef struct {
+    int32_t  query_scan_index;
+    int32_t  ref_scan_index;        /* -1: an unused slot */
+    int32_t  ref_map_index;         /* -1: an unused slot */
+    int32_t  shift;
+    uint32_t distance;
+    uint32_t ring_distance;
+} csm_appearance_candidate;
+
+/* Host only: the descriptors of n_scans ragged scans. The CPU reference of csm_scan_descriptors. */
+int  csm_host_scan_descriptors(const double* angles, const double* ranges, const int32_t* offsets, int32_t n_scans,
+                               const csm_descriptor_params* params, uint8_t* out, int32_t* beams_used);
+/* On the device, on the ctx stream: one upload ([edge tables | offsets | angles | ranges]), one workgroup per
+ * scan (the edge tables and a histogram of the cells in LDS; per beam two binary searches on the tables and one
+ * integer LDS atomic), one read-back. Every byte of out and beams_used equals the host function's. Timer:
+ * "scan_descriptors". */
+int  csm_scan_descriptors(csm_ctx* ctx, const double* angles, const double* ranges, const int32_t* offsets,
+                          int32_t n_scans, const csm_descriptor_params* params, uint8_t* out, int32_t* beams_used);
+int  csm_host_descriptor_shift_angle(int32_t shift, int32_t n_sectors, double* out);
+/* Host only: the rule as a sequential restatement. The CPU reference of csm_appearance_search. */
+int  csm_host_appearance_search(const uint8_t* descriptors, const int32_t* scan_map_index, const double* travel,
+                                int32_t n_scan, int32_t n_maps, int32_t n_ref, const int32_t* query_index,
+                                const double* query_travel, int32_t n_q, const csm_appearance_params* params,
+                                csm_appearance_candidate* out, int32_t* counts, csm_loop_search_info* info);
+/* On the device, on the ctx stream: the descriptors, map indices, travel values and the query table uploaded
+ * once (n_rings * n_sectors + 12 bytes per node: 12.9 MB at 10 000 nodes of 20 x 64; nothing stays resident
+ * between calls); the ring sums of every node; then, per chunk of queries whose pair table (4 bytes per pair of
+ * a query and a node below n_ref) stays within CSM_APPEARANCE_TABLE_BYTES, the scoring kernel (a workgroup per
+ * query and CSM_APPEARANCE_REF_CHUNK reference nodes: the query's descriptor in LDS with its sector axis
+ * doubled, in four byte phases; a wavefront per reference node, a shift per lane, v_sad_u8 on aligned dwords;
+ * the minimum of L1 << 8 | s across the wave) and the selection kernel (a workgroup per query: one round per
+ * record over the key distance << 32 | r, an LDS bit per map already taken); one read-back. Every byte of out,
+ * counts and info equals csm_host_appearance_search's, for every launch shape. Timer: "appearance_search". */
+int  csm_appearance_search(csm_ctx* ctx, const uint8_t* descriptors, const int32_t* scan_map_index,
+                           const double* travel, int32_t n_scan, int32_t n_maps, int32_t n_ref,
+                           const int32_t* query_index, const double* query_travel, int32_t n_q,
+                           const csm_appearance_params* params, csm_appearance_candidate* out, int32_t* counts,
+                           csm_loop_search_info* info);
+
 /* ---- measurement hooks (bench.py) ---- */
 /* enable = 1: every kernel launch is bracketed by HIP events on the ctx
  * stream; enable = 2: only the dominant (fine-level) scoring kernel, to keep
@@ -1579,7 +1688,8 @@ int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
  * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select" | "likelihood" |
  * "ray_project" | "ray_walk" | "pose_prep" | "pose_score" | "pose_rescore" | "pose_weights" |
  * "pose_resample" | "pose_graph" | "pose_graph_marginals" |
- * "pose_graph_marginals_factor" | "pose_graph_marginals_solve" | "loop_search". */
+ * "pose_graph_marginals_factor" | "pose_graph_marginals_solve" | "loop_search" | "scan_descriptors" |
+ * "appearance_search". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);
 int  csm_reset_kernel_timing(csm_ctx* ctx);

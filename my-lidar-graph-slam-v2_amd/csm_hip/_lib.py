@@ -315,6 +315,26 @@ class LoopSearchInfo(C.Structure):
     _fields_ = [("pairs_evaluated", C.c_int64), ("pairs_eligible", C.c_int64)]
 
 
+DESCRIPTOR_MAX_RINGS, DESCRIPTOR_MAX_SECTORS, DESCRIPTOR_MAX_BEAMS = 32, 128, 65536
+APPEARANCE_REF_CHUNK, APPEARANCE_TABLE_BYTES = 128, 64 << 20
+
+
+class DescriptorParams(C.Structure):
+    _fields_ = [("n_rings", C.c_int32), ("n_sectors", C.c_int32), ("range_min", C.c_double),
+                ("range_max", C.c_double)]
+
+
+class AppearanceParams(C.Structure):
+    _fields_ = [("descriptor", DescriptorParams), ("travel_dist_threshold", C.c_double),
+                ("max_distance", C.c_uint32), ("min_cell_sum", C.c_uint32), ("n_per_query", C.c_int32),
+                ("one_per_map", C.c_int32)]
+
+
+class AppearanceCandidate(C.Structure):
+    _fields_ = [("query_scan_index", C.c_int32), ("ref_scan_index", C.c_int32), ("ref_map_index", C.c_int32),
+                ("shift", C.c_int32), ("distance", C.c_uint32), ("ring_distance", C.c_uint32)]
+
+
 POSE_UNCERTAIN, POSE_HOST_PROJECTED = 1, 2
 POSE_SET_MAX_POSES = 1 << 18
 
@@ -487,6 +507,17 @@ SIGNATURES = {
     "csm_loop_search": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_int32, _P(LoopSearchParams), C.c_void_p, C.c_void_p,
                                   _P(LoopSearchInfo)]),
+    "csm_host_scan_descriptors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(DescriptorParams),
+                                            C.c_void_p, C.c_void_p]),
+    "csm_scan_descriptors": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(DescriptorParams),
+                                       C.c_void_p, C.c_void_p]),
+    "csm_host_descriptor_shift_angle": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_double)]),
+    "csm_host_appearance_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_int32, _P(AppearanceParams), C.c_void_p,
+                                             C.c_void_p, _P(LoopSearchInfo)]),
+    "csm_appearance_search": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_int32, _P(AppearanceParams), C.c_void_p,
+                                        C.c_void_p, _P(LoopSearchInfo)]),
     "csm_host_loop_candidates_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                                    _P(C.c_int32)]),
     "csm_shard_bounds": (None, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),

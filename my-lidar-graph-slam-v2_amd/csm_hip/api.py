@@ -751,6 +751,108 @@ def host_loop_candidates_nearest(records, counts, n_total):
     return out[:n_out.value]
 
 
+# csm_appearance_candidate as a numpy record: 24 bytes, the struct's layout
+APPEARANCE_CANDIDATE_DTYPE = np.dtype([("query_scan_index", np.int32), ("ref_scan_index", np.int32),
+                                       ("ref_map_index", np.int32), ("shift", np.int32), ("distance", np.uint32),
+                                       ("ring_distance", np.uint32)])
+assert APPEARANCE_CANDIDATE_DTYPE.itemsize == C.sizeof(L.AppearanceCandidate)
+
+
+def _scan_descriptors_run(fn, head, angles, ranges, offsets, n_rings, n_sectors, range_min, range_max):
+    an = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+    rg = np.ascontiguousarray(ranges, dtype=np.float64).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+    if an.size != rg.size or off.size < 1 or (off.size > 1 and int(off.max()) > an.size):
+        raise CsmError(L.CSM_EINVAL, "scan_descriptors: one range per angle, offsets within them")
+    if an.size == 0:                    # never a pointer to nothing
+        an, rg = np.zeros(1), np.zeros(1)
+    p = L.DescriptorParams(int(n_rings), int(n_sectors), float(range_min), float(range_max))
+    n = off.size - 1
+    cells = max(min(int(n_rings), L.DESCRIPTOR_MAX_RINGS), 1) * max(min(int(n_sectors), L.DESCRIPTOR_MAX_SECTORS), 1)
+    out = np.zeros((max(n, 1), cells), np.uint8)
+    used = np.zeros(max(n, 1), np.int32)
+    rc = fn(*head, _ptr(an), _ptr(rg), _ptr(off), n, C.byref(p), _ptr(out), _ptr(used))
+    if rc:
+        return rc, None, None
+    return rc, out[:n].reshape(n, int(n_rings), int(n_sectors)), used[:n]
+
+
+def ragged_scans(scans):
+    """(angles, ranges) pairs -> the three arrays a descriptor build takes: angles, ranges, offsets."""
+    sizes = [len(a) for a, _ in scans]
+    cat = lambda i: (np.concatenate([np.asarray(s[i], np.float64).reshape(-1) for s in scans])
+                     if scans else np.zeros(0))
+    return cat(0), cat(1), np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
+def host_scan_descriptors(angles, ranges, offsets, n_rings=20, n_sectors=64, range_min=0.5, range_max=20.0):
+    """csm_host_scan_descriptors: the polar descriptors of ragged scans (scan i is beams offsets[i] ..
+    offsets[i + 1]). Returns (descriptors [n_scans, n_rings, n_sectors] uint8, beams_used [n_scans])."""
+    rc, out, used = _scan_descriptors_run(L.load().csm_host_scan_descriptors, (), angles, ranges, offsets, n_rings,
+                                          n_sectors, range_min, range_max)
+    if rc:
+        raise CsmError(rc, "csm_host_scan_descriptors")
+    return out, used
+
+
+def host_descriptor_shift_angle(shift, n_sectors):
+    """csm_host_descriptor_shift_angle: theta_query - theta_ref that a candidate's shift implies."""
+    out = C.c_double()
+    rc = L.load().csm_host_descriptor_shift_angle(int(shift), int(n_sectors), C.byref(out))
+    if rc:
+        raise CsmError(rc, "csm_host_descriptor_shift_angle")
+    return out.value
+
+
+def _appearance_run(fn, head, descriptors, scan_map_index, travel, query_index, query_travel, n_ref, n_maps,
+                    travel_dist_threshold, max_distance, min_cell_sum, n_per_query, one_per_map, n_rings, n_sectors,
+                    range_min, range_max):
+    d = np.ascontiguousarray(descriptors, dtype=np.uint8)
+    if d.ndim != 3:
+        raise CsmError(L.CSM_EINVAL, "appearance_search: descriptors must be [n_scan, n_rings, n_sectors]")
+    n_rings = d.shape[1] if n_rings is None else int(n_rings)
+    n_sectors = d.shape[2] if n_sectors is None else int(n_sectors)
+    mi = np.ascontiguousarray(scan_map_index, dtype=np.int32).reshape(-1)
+    tr = np.ascontiguousarray(travel, dtype=np.float64).reshape(-1)
+    qi = np.ascontiguousarray(query_index, dtype=np.int32).reshape(-1)
+    if mi.size != d.shape[0] or tr.size != d.shape[0]:
+        raise CsmError(L.CSM_EINVAL, "appearance_search: one map index and one travel value per scan node")
+    if query_travel is None:
+        if qi.size and (qi.min() < 0 or qi.max() >= tr.size):
+            raise CsmError(L.CSM_EINVAL, "appearance_search: a query index out of range")
+        qt = np.ascontiguousarray(tr[qi])
+    else:
+        qt = np.ascontiguousarray(np.broadcast_to(np.asarray(query_travel, dtype=np.float64), qi.shape))
+    n_ref = d.shape[0] if n_ref is None else int(n_ref)
+    n_maps = (int(mi.max()) + 1 if mi.size else 0) if n_maps is None else int(n_maps)
+    k = int(n_per_query)
+    p = L.AppearanceParams(L.DescriptorParams(n_rings, n_sectors, float(range_min), float(range_max)),
+                           float(travel_dist_threshold), int(max_distance), int(min_cell_sum), k, int(one_per_map))
+    slots = max(min(k, L.LOOP_SEARCH_MAX_K), 1)
+    out = np.zeros((max(qi.size, 1), slots), APPEARANCE_CANDIDATE_DTYPE)
+    counts = np.zeros(max(qi.size, 1), np.int32)
+    info = L.LoopSearchInfo()
+    rc = fn(*head, _ptr(d), _ptr(mi), _ptr(tr), d.shape[0], n_maps, n_ref, _ptr(qi), _ptr(qt), qi.size, C.byref(p),
+            _ptr(out), _ptr(counts), C.byref(info))
+    return rc, out[:qi.size], counts[:qi.size], dict(pairs_evaluated=int(info.pairs_evaluated),
+                                                     pairs_eligible=int(info.pairs_eligible))
+
+
+def host_appearance_search(descriptors, scan_map_index, travel, query_index, query_travel=None, n_ref=None,
+                           travel_dist_threshold=10.0, max_distance=0xffffffff, min_cell_sum=0, n_per_query=2,
+                           one_per_map=False, n_maps=None, n_rings=None, n_sectors=None, range_min=0.5,
+                           range_max=20.0):
+    """csm_host_appearance_search: the sequential restatement of Context.appearance_search, same arguments and
+    result."""
+    rc, out, counts, info = _appearance_run(L.load().csm_host_appearance_search, (), descriptors, scan_map_index,
+                                            travel, query_index, query_travel, n_ref, n_maps, travel_dist_threshold,
+                                            max_distance, min_cell_sum, n_per_query, one_per_map, n_rings, n_sectors,
+                                            range_min, range_max)
+    if rc:
+        raise CsmError(rc, "csm_host_appearance_search")
+    return out, counts, info
+
+
 class Context:
     """One csm_ctx: owns the device grids, workspaces and a stream."""
 
@@ -1471,6 +1573,31 @@ class Context:
         self._check(rc)
         return out, counts, info
 
+    def scan_descriptors(self, angles, ranges, offsets, n_rings=20, n_sectors=64, range_min=0.5, range_max=20.0):
+        """csm_scan_descriptors: the polar descriptors of ragged scans on the device; arguments and result as
+        host_scan_descriptors, byte for byte."""
+        rc, out, used = _scan_descriptors_run(self.lib.csm_scan_descriptors, (self._ctx,), angles, ranges, offsets,
+                                              n_rings, n_sectors, range_min, range_max)
+        self._check(rc)
+        return out, used
+
+    def appearance_search(self, descriptors, scan_map_index, travel, query_index, query_travel=None, n_ref=None,
+                          travel_dist_threshold=10.0, max_distance=0xffffffff, min_cell_sum=0, n_per_query=2,
+                          one_per_map=False, n_maps=None, n_rings=None, n_sectors=None, range_min=0.5,
+                          range_max=20.0):
+        """csm_appearance_search: loop candidates by what the scans look like. descriptors [n, n_rings,
+        n_sectors] uint8 (scan_descriptors); scan_map_index, travel, query_index, query_travel, n_ref and n_maps
+        as loop_search takes them. A pair is a candidate when the least L1 distance over all sector shifts is at
+        most max_distance and both descriptors sum to min_cell_sum or more. Returns (records [n_q, n_per_query]
+        of APPEARANCE_CANDIDATE_DTYPE ordered by (distance, reference node), unused slots with ref_scan_index
+        -1; counts [n_q]; info dict: pairs_evaluated, pairs_eligible)."""
+        rc, out, counts, info = _appearance_run(self.lib.csm_appearance_search, (self._ctx,), descriptors,
+                                                scan_map_index, travel, query_index, query_travel, n_ref, n_maps,
+                                                travel_dist_threshold, max_distance, min_cell_sum, n_per_query,
+                                                one_per_map, n_rings, n_sectors, range_min, range_max)
+        self._check(rc)
+        return out, counts, info
+
     def enable_kernel_timing(self, on=True):
         self._check(self.lib.csm_enable_kernel_timing(self._ctx, 1 if on else 0))
 
@@ -1785,3 +1912,70 @@ class LoopSearcherNearestHIP:
             n_per_query, True, len(local_maps[:int(last_finished_map) + 1]))
         return [(int(c["query_scan_index"]), int(c["ref_scan_index"]), int(c["ref_map_index"]))
                 for row, n in zip(rec, counts) for c in row[:n]]
+
+
+class LoopSearcherAppearanceHIP:
+    """The loop searcher by appearance, beside LoopSearcherNearestHIP and on the same loop_search_graph inputs
+    plus the scans: scans[i] = (angles, ranges) of scan node i. A node's descriptor is built once, when a
+    search first sees the node, and kept; a later search builds only those of new nodes (reset() forgets them).
+    search() and search_per_map() return (query scan node, reference scan node, reference local map) triples
+    as LoopSearcherNearestHIP does; last_records holds the records behind them (shift, distance,
+    ring_distance) and last_headings the heading difference theta_query - theta_ref each shift implies: the
+    centre of the theta window of the matcher that follows."""
+
+    def __init__(self, travel_dist_threshold, max_distance, num_of_candidate_nodes, n_rings=20, n_sectors=64,
+                 range_min=0.5, range_max=20.0, min_cell_sum=0, ctx=None):
+        self.travel_dist_threshold = float(travel_dist_threshold)
+        self.max_distance = int(max_distance)
+        self.num_of_candidate_nodes = int(num_of_candidate_nodes)
+        self.shape = (int(n_rings), int(n_sectors))
+        self.range_min, self.range_max = float(range_min), float(range_max)
+        self.min_cell_sum = int(min_cell_sum)
+        self.ctx = ctx or Context()
+        self.last_info = self.last_records = self.last_headings = None
+        self.reset()
+
+    def reset(self):
+        self.descriptors = np.zeros((0,) + self.shape, np.uint8)
+        self.beams_used = np.zeros(0, np.int32)
+
+    def _descriptors(self, scans, n):
+        """The descriptors of nodes [0, n): those kept, and the new nodes' in one device call."""
+        have = self.descriptors.shape[0]
+        if n > len(scans):
+            raise CsmError(L.CSM_EINVAL, "loop search: a local map names a scan node whose scan is not given")
+        if n > have:
+            d, used = self.ctx.scan_descriptors(*ragged_scans(scans[have:n]), self.shape[0], self.shape[1],
+                                                self.range_min, self.range_max)
+            self.descriptors = np.concatenate([self.descriptors, d])
+            self.beams_used = np.concatenate([self.beams_used, used])
+        return self.descriptors[:n]
+
+    def _run(self, desc, map_index, travel, queries, query_travel, n_ref, k, one_per_map, n_maps=None):
+        rec, counts, self.last_info = self.ctx.appearance_search(
+            desc, map_index, travel, queries, query_travel, n_ref, self.travel_dist_threshold, self.max_distance,
+            self.min_cell_sum, k, one_per_map, n_maps, range_min=self.range_min, range_max=self.range_max)
+        return np.concatenate([row[:n] for row, n in zip(rec, counts)]) if len(rec) else rec.reshape(-1)
+
+    def _finish(self, used):
+        self.last_records = used
+        self.last_headings = [host_descriptor_shift_angle(c["shift"], self.shape[1]) for c in used]
+        return [(int(c["query_scan_index"]), int(c["ref_scan_index"]), int(c["ref_map_index"])) for c in used]
+
+    def search(self, scan_poses, local_maps, accum_travel_dist, last_finished_map, scans):
+        """Queries are the nodes of the last finished local map, references the nodes of the maps before it,
+        every gate measured from accum_travel_dist: the num_of_candidate_nodes pairs of least (distance,
+        reference node, query node), nearest first."""
+        sp, map_index, travel, n_ref, queries = loop_search_graph(scan_poses, local_maps, last_finished_map)
+        used = self._run(self._descriptors(scans, len(sp)), map_index, travel, queries, float(accum_travel_dist),
+                         n_ref, self.num_of_candidate_nodes, False)
+        order = np.lexsort((used["query_scan_index"], used["ref_scan_index"], used["distance"]))
+        return self._finish(used[order][:self.num_of_candidate_nodes])
+
+    def search_per_map(self, scan_poses, local_maps, last_finished_map, query_nodes, n_per_query, scans):
+        """Per query node the most similar reference node of each local map, the n_per_query most similar
+        maps; any node up to the last finished map's last may be a reference and each query's gate is measured
+        from its own travel distance. Returns the used triples, query by query in the order given."""
+        sp, map_index, travel, _, _ = loop_search_graph(scan_poses, local_maps, last_finished_map)
+        return self._finish(self._run(self._descriptors(scans, len(sp)), map_index, travel, query_nodes, None, None,
+                                      n_per_query, True, len(local_maps[:int(last_finished_map) + 1])))

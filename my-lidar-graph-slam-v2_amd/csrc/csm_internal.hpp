@@ -252,6 +252,10 @@ struct csm_ctx {
      * per-query counts behind them; pinned staging, up and then back */
     DevBuf ls_dev;
     PinBuf ls_pin;
+    /* appearance search (csm_appearance_api.hip): a call's upload with its ring sums and read-back block
+     * behind it, the pair table of one chunk of queries; pinned staging, up and then back */
+    DevBuf ap_dev, ap_table;
+    PinBuf ap_pin;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */

@@ -17,6 +17,7 @@
  *   ParticleSetHIP              (beyond the reference) weights and resampling of a particle set
  *   LoopSearcherNearestHIP      <- LoopSearcherNearest
  *        inc/mapping/loop_searcher_nearest.hpp:33-63, src/mapping/loop_searcher_nearest.cpp:59-170
+ *   LoopSearcherAppearanceHIP   (no counterpart: candidates by scan descriptors, csm_appearance_search)
  *
  * The reference headers cannot be included in this image (Eigen3 / Boost are
  * absent), so the few value types the interfaces use are restated here in
@@ -43,6 +44,7 @@
 #include <numeric>
 #include <set>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -1855,6 +1857,41 @@ struct LoopSearchHintView {
     int mLastFinishedMapId = -1;
 };
 
+namespace detail {
+
+/* a hint as the arrays a loop search takes: the nodes up to the last finished map's last, the map of each,
+ * their travel distances; mNumOfRefs = the first node of the last finished map */
+struct LoopGraph {
+    std::int32_t mNumOfNodes = 0, mNumOfMaps = 0, mNumOfRefs = 0;
+    std::vector<std::int32_t> mMapIndex;
+    std::vector<double> mTravel;
+};
+
+inline LoopGraph ToLoopGraph(const LoopSearchHintView& h, csm_ctx* ctx)
+{
+    CSM_ASSERT_THAT(h.mLastFinishedMapId >= 0 && static_cast<std::size_t>(h.mLastFinishedMapId) < h.mNumOfLocalMaps,
+                    "mLastFinishedMapId names no local map");
+    LoopGraph g;
+    g.mNumOfMaps = h.mLastFinishedMapId + 1;
+    for (std::int32_t m = 0; m < g.mNumOfMaps; ++m) {
+        const std::pair<int, int>& run = h.mLocalMapNodeRanges[m];
+        CSM_ASSERT_THAT(run.first == g.mNumOfNodes && run.second >= run.first,
+                        "local maps must be contiguous runs of scan nodes from node 0");
+        if (m == h.mLastFinishedMapId)
+            g.mNumOfRefs = g.mNumOfNodes;
+        g.mMapIndex.insert(g.mMapIndex.end(), static_cast<std::size_t>(run.second - run.first + 1), m);
+        g.mNumOfNodes = run.second + 1;
+    }
+    CSM_ASSERT_THAT(static_cast<std::size_t>(g.mNumOfNodes) <= h.mNumOfScanNodes,
+                    "a local map names a scan node that is not given");
+    g.mTravel.resize(static_cast<std::size_t>(g.mNumOfNodes));
+    static_assert(sizeof(std::array<double, 3>) == 3 * sizeof(double), "pose layout");
+    CSM_ASSERT_OK(ctx, csm_host_travel_distances(h.mScanNodePoses->data(), g.mNumOfNodes, g.mTravel.data()));
+    return g;
+}
+
+} /* namespace detail */
+
 /* inc/mapping/loop_searcher.hpp:63-85, plus the squared node distance the searcher observes as a metric */
 struct LoopCandidate {
     int mQueryScanNodeId;
@@ -1974,40 +2011,14 @@ public:
     }
 
 private:
-    struct Graph {
-        std::int32_t mNumOfNodes = 0, mNumOfMaps = 0, mNumOfRefs = 0;
-        std::vector<std::int32_t> mMapIndex;
-        std::vector<double> mTravel;
-    };
+    using Graph = detail::LoopGraph;
 
     LoopSearcherNearestHIP(double travelDistThreshold, double nodeDistThreshold, int numOfCandidateNodes,
                            detail::ContextRef ctx) :
         mTravelDistThreshold(travelDistThreshold), mNodeDistThreshold(nodeDistThreshold),
         mNumOfCandidateNodes(numOfCandidateNodes), mCtx(std::move(ctx)) { }
 
-    Graph ToGraph(const LoopSearchHintView& h) const
-    {
-        CSM_ASSERT_THAT(h.mLastFinishedMapId >= 0 && static_cast<std::size_t>(h.mLastFinishedMapId) < h.mNumOfLocalMaps,
-                        "mLastFinishedMapId names no local map");
-        Graph g;
-        g.mNumOfMaps = h.mLastFinishedMapId + 1;
-        for (std::int32_t m = 0; m < g.mNumOfMaps; ++m) {
-            const std::pair<int, int>& run = h.mLocalMapNodeRanges[m];
-            CSM_ASSERT_THAT(run.first == g.mNumOfNodes && run.second >= run.first,
-                            "local maps must be contiguous runs of scan nodes from node 0");
-            if (m == h.mLastFinishedMapId)
-                g.mNumOfRefs = g.mNumOfNodes;
-            g.mMapIndex.insert(g.mMapIndex.end(), static_cast<std::size_t>(run.second - run.first + 1), m);
-            g.mNumOfNodes = run.second + 1;
-        }
-        CSM_ASSERT_THAT(static_cast<std::size_t>(g.mNumOfNodes) <= h.mNumOfScanNodes,
-                        "a local map names a scan node that is not given");
-        g.mTravel.resize(static_cast<std::size_t>(g.mNumOfNodes));
-        static_assert(sizeof(std::array<double, 3>) == 3 * sizeof(double), "pose layout");
-        CSM_ASSERT_OK(this->Context(),
-                      csm_host_travel_distances(h.mScanNodePoses->data(), g.mNumOfNodes, g.mTravel.data()));
-        return g;
-    }
+    Graph ToGraph(const LoopSearchHintView& h) const { return detail::ToLoopGraph(h, this->Context()); }
 
     std::vector<csm_loop_candidate> Run(const LoopSearchHintView& h, const Graph& g, std::int32_t numOfRefs,
                                         const std::vector<std::int32_t>& queries,
@@ -2044,6 +2055,202 @@ private:
     csm_loop_search_info mLastInfo {};
     double mLastAccumTravelDist = 0.0;
     LoopCandidateVector mLast;
+};
+
+/* One scan as the descriptor build reads it: mNumOfBeams angles and ranges in the sensor's frame. */
+struct ScanView {
+    const double* mAngles = nullptr;
+    const double* mRanges = nullptr;
+    std::size_t mNumOfBeams = 0;
+};
+
+/* a LoopCandidate found by appearance, with what the descriptor comparison knows of it: the sector shift,
+ * the L1 distance at that shift, the shift-free lower bound, and the heading difference theta_query -
+ * theta_ref the shift implies (csm_host_descriptor_shift_angle): the centre of the matcher's theta window */
+struct AppearanceCandidate {
+    int mQueryScanNodeId;
+    int mReferenceScanNodeId;
+    int mReferenceLocalMapId;
+    int mShift;
+    std::uint32_t mDistance;
+    std::uint32_t mRingDistance;
+    double mHeadingDiff;
+};
+using AppearanceCandidateVector = std::vector<AppearanceCandidate>;
+
+/* same shape as what LoopSearcherNearestHIP returns; mDistSq carries the descriptor distance */
+inline LoopCandidateVector ToLoopCandidates(const AppearanceCandidateVector& candidates)
+{
+    LoopCandidateVector out(candidates.size());
+    for (std::size_t i = 0; i < candidates.size(); ++i)
+        out[i] = LoopCandidate { candidates[i].mQueryScanNodeId, candidates[i].mReferenceScanNodeId,
+                                 candidates[i].mReferenceLocalMapId, static_cast<double>(candidates[i].mDistance) };
+    return out;
+}
+
+/* The loop searcher by appearance (csm_scan_descriptors, csm_appearance_search), beside LoopSearcherNearestHIP
+ * and on the same hint plus the scans: scans[i] is scan node i. A node's descriptor is built once, when a
+ * search first sees the node, and kept; a later search builds only those of new nodes. Search() and
+ * SearchPerMap() return candidates in LoopSearcherNearestHIP's shape; LastCandidates() holds the same
+ * candidates with shift, distances and implied heading difference. */
+class LoopSearcherAppearanceHIP final {
+public:
+    static std::unique_ptr<LoopSearcherAppearanceHIP> Create(double travelDistThreshold, std::uint32_t maxDistance,
+                                                             int numOfCandidateNodes,
+                                                             const csm_descriptor_params& descriptor,
+                                                             std::uint32_t minCellSum = 0, int deviceId = 0)
+    {
+        if (numOfCandidateNodes < 1 || numOfCandidateNodes > CSM_LOOP_SEARCH_MAX_K)
+            return nullptr;
+        detail::CtxPtr ctx = detail::MakeContext(deviceId);
+        if (!ctx)
+            return nullptr;
+        return std::unique_ptr<LoopSearcherAppearanceHIP>(new LoopSearcherAppearanceHIP(
+            travelDistThreshold, maxDistance, numOfCandidateNodes, descriptor, minCellSum,
+            detail::ContextRef(std::move(ctx))));
+    }
+    /* on a context another adapter owns and keeps alive */
+    LoopSearcherAppearanceHIP(csm_ctx* shared, double travelDistThreshold, std::uint32_t maxDistance,
+                              int numOfCandidateNodes, const csm_descriptor_params& descriptor,
+                              std::uint32_t minCellSum = 0) :
+        LoopSearcherAppearanceHIP(travelDistThreshold, maxDistance, numOfCandidateNodes, descriptor, minCellSum,
+                                  detail::ContextRef(shared)) { }
+
+    LoopSearcherAppearanceHIP(const LoopSearcherAppearanceHIP&) = delete;
+    LoopSearcherAppearanceHIP& operator=(const LoopSearcherAppearanceHIP&) = delete;
+
+    csm_ctx* Context() const { return this->mCtx.Get(); }
+    const csm_loop_search_info& LastInfo() const { return this->mLastInfo; }
+    const AppearanceCandidateVector& LastCandidates() const { return this->mLast; }
+    /* nodes whose descriptors are kept */
+    std::size_t NumOfDescriptors() const { return this->mBeamsUsed.size(); }
+    void Reset()
+    {
+        this->mDescriptors.clear();
+        this->mBeamsUsed.clear();
+    }
+
+    /* queries are the nodes of the last finished local map, references the nodes of the maps before it, every
+     * gate measured from mAccumTravelDist: the numOfCandidateNodes pairs of least (distance, reference node,
+     * query node) */
+    LoopCandidateVector Search(const LoopSearchHintView& searchHint, const std::vector<ScanView>& scans)
+    {
+        const detail::LoopGraph g = detail::ToLoopGraph(searchHint, this->Context());
+        std::vector<std::int32_t> queries(g.mNumOfNodes - g.mNumOfRefs);
+        std::iota(queries.begin(), queries.end(), g.mNumOfRefs);
+        const std::vector<double> queryTravel(queries.size(), searchHint.mAccumTravelDist);
+        std::vector<csm_appearance_candidate> used =
+            this->Run(g, scans, g.mNumOfRefs, queries, queryTravel, this->mNumOfCandidateNodes, false);
+        std::sort(used.begin(), used.end(), [](const csm_appearance_candidate& a, const csm_appearance_candidate& b) {
+            return std::tie(a.distance, a.ref_scan_index, a.query_scan_index) <
+                   std::tie(b.distance, b.ref_scan_index, b.query_scan_index);
+        });
+        used.resize(std::min(used.size(), static_cast<std::size_t>(this->mNumOfCandidateNodes)));
+        return this->Finish(used);
+    }
+
+    /* per query node the most similar reference node of each local map, the nPerQuery most similar maps
+     * (one_per_map = 1); references and gates as LoopSearcherNearestHIP::SearchPerMap */
+    LoopCandidateVector SearchPerMap(const LoopSearchHintView& searchHint, const std::vector<ScanView>& scans,
+                                     const std::vector<int>& queryNodes, int nPerQuery)
+    {
+        const detail::LoopGraph g = detail::ToLoopGraph(searchHint, this->Context());
+        std::vector<std::int32_t> queries(queryNodes.begin(), queryNodes.end());
+        std::vector<double> queryTravel(queries.size());
+        for (std::size_t i = 0; i < queries.size(); ++i) {
+            CSM_ASSERT_THAT(queries[i] >= 0 && queries[i] < g.mNumOfNodes, "query node %d is not in the graph",
+                            queries[i]);
+            queryTravel[i] = g.mTravel[static_cast<std::size_t>(queries[i])];
+        }
+        return this->Finish(this->Run(g, scans, g.mNumOfNodes, queries, queryTravel, nPerQuery, true));
+    }
+
+private:
+    LoopSearcherAppearanceHIP(double travelDistThreshold, std::uint32_t maxDistance, int numOfCandidateNodes,
+                              const csm_descriptor_params& descriptor, std::uint32_t minCellSum,
+                              detail::ContextRef ctx) :
+        mTravelDistThreshold(travelDistThreshold), mMaxDistance(maxDistance), mMinCellSum(minCellSum),
+        mNumOfCandidateNodes(numOfCandidateNodes), mDescriptor(descriptor), mCtx(std::move(ctx)) { }
+
+    /* the descriptors of nodes [0, numOfNodes): those kept, and the new nodes' in one device call */
+    void BuildDescriptors(const std::vector<ScanView>& scans, std::size_t numOfNodes)
+    {
+        const std::size_t have = this->mBeamsUsed.size();
+        CSM_ASSERT_THAT(numOfNodes <= scans.size(), "a local map names a scan node whose scan is not given");
+        if (numOfNodes <= have)
+            return;
+        std::vector<double> angles, ranges;
+        std::vector<std::int32_t> offsets(1, 0);
+        for (std::size_t i = have; i < numOfNodes; ++i) {
+            angles.insert(angles.end(), scans[i].mAngles, scans[i].mAngles + scans[i].mNumOfBeams);
+            ranges.insert(ranges.end(), scans[i].mRanges, scans[i].mRanges + scans[i].mNumOfBeams);
+            offsets.push_back(static_cast<std::int32_t>(angles.size()));
+        }
+        if (angles.empty()) {           /* never a pointer to nothing */
+            angles.push_back(0.0);
+            ranges.push_back(0.0);
+        }
+        const std::size_t cells = static_cast<std::size_t>(this->mDescriptor.n_rings) *
+                                  static_cast<std::size_t>(this->mDescriptor.n_sectors);
+        this->mDescriptors.resize(numOfNodes * cells);
+        this->mBeamsUsed.resize(numOfNodes);
+        CSM_ASSERT_OK(this->Context(),
+                      csm_scan_descriptors(this->Context(), angles.data(), ranges.data(), offsets.data(),
+                                           static_cast<std::int32_t>(numOfNodes - have), &this->mDescriptor,
+                                           this->mDescriptors.data() + have * cells, this->mBeamsUsed.data() + have));
+    }
+
+    /* the used records, query by query */
+    std::vector<csm_appearance_candidate> Run(const detail::LoopGraph& g, const std::vector<ScanView>& scans,
+                                              std::int32_t numOfRefs, const std::vector<std::int32_t>& queries,
+                                              const std::vector<double>& queryTravel, int nPerQuery, bool onePerMap)
+    {
+        this->BuildDescriptors(scans, static_cast<std::size_t>(g.mNumOfNodes));
+        csm_appearance_params prm {};
+        prm.descriptor = this->mDescriptor;
+        prm.travel_dist_threshold = this->mTravelDistThreshold;
+        prm.max_distance = this->mMaxDistance;
+        prm.min_cell_sum = this->mMinCellSum;
+        prm.n_per_query = nPerQuery;
+        prm.one_per_map = onePerMap ? 1 : 0;
+        const std::size_t slots = static_cast<std::size_t>(std::max(nPerQuery, 1));
+        std::vector<csm_appearance_candidate> records(queries.size() * slots);
+        std::vector<std::int32_t> counts(queries.size(), 0);
+        CSM_ASSERT_OK(this->Context(),
+                      csm_appearance_search(this->Context(), this->mDescriptors.data(), g.mMapIndex.data(),
+                                            g.mTravel.data(), g.mNumOfNodes, g.mNumOfMaps, numOfRefs, queries.data(),
+                                            queryTravel.data(), static_cast<std::int32_t>(queries.size()), &prm,
+                                            records.data(), counts.data(), &this->mLastInfo));
+        std::vector<csm_appearance_candidate> used;
+        for (std::size_t i = 0; i < counts.size(); ++i)
+            used.insert(used.end(), records.begin() + static_cast<std::ptrdiff_t>(i * slots),
+                        records.begin() + static_cast<std::ptrdiff_t>(i * slots) + counts[i]);
+        return used;
+    }
+
+    LoopCandidateVector Finish(const std::vector<csm_appearance_candidate>& used)
+    {
+        this->mLast.resize(used.size());
+        for (std::size_t i = 0; i < used.size(); ++i) {
+            double heading = 0.0;
+            CSM_ASSERT_OK(this->Context(),
+                          csm_host_descriptor_shift_angle(used[i].shift, this->mDescriptor.n_sectors, &heading));
+            this->mLast[i] = AppearanceCandidate { used[i].query_scan_index, used[i].ref_scan_index,
+                                                   used[i].ref_map_index, used[i].shift, used[i].distance,
+                                                   used[i].ring_distance, heading };
+        }
+        return ToLoopCandidates(this->mLast);
+    }
+
+    const double mTravelDistThreshold;
+    const std::uint32_t mMaxDistance, mMinCellSum;
+    const int mNumOfCandidateNodes;
+    const csm_descriptor_params mDescriptor;
+    detail::ContextRef mCtx;
+    csm_loop_search_info mLastInfo {};
+    std::vector<std::uint8_t> mDescriptors;
+    std::vector<std::int32_t> mBeamsUsed;
+    AppearanceCandidateVector mLast;
 };
 
 } /* namespace CsmHip */
