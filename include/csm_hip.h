@@ -824,6 +824,103 @@ int  csm_host_pose_set_update(const csm_pose_record* records, int32_t n_poses, i
                               const csm_pose_update_params* params, uint32_t* weights, int32_t* ancestors,
                               csm_pose_update_info* update);
 
+/* ---- virtual scans: beams cast through a resident map (beyond the reference, which only ever walks a
+ * MEASURED beam). From a sensor pose, in a direction: which is the first cell of the map that stops the beam,
+ * and how far is it? Read-only. The sets are csm_pose_set, read as follows: `poses` are map-local SENSOR poses
+ * (relative_sensor_pose is not applied), scan.angles[n_points] are the beam angles, scan.ranges is NULL or
+ * holds a limit per beam.
+ *
+ * Definition (integers only once the end points are formed), for pose p and beam i:
+ *   limit  range_max if scan.ranges == NULL. Otherwise the beam is CAST iff r_i > 0 (a NaN is not cast), with
+ *          limit = r_i < range_max ? r_i : range_max.
+ *   s, e, W  exactly the ray check's objects (above) for a beam of range `limit` from sensor pose p:
+ *          s = floor((p.xy - off) / scaledRes), e = ScanData::HitPoint's double expression at scaledRes, W the
+ *          cells of BresenhamScaled(s, e) under the floored reading, after the whole-cell move.
+ *   order  The sensor's cell floor_div(s, scale) is one end of W (no walk holds a cell twice). W is read from
+ *          that end: the reference's order when it did not swap its end points, the reverse when it did. (A
+ *          walk is a sequence of columns with a run of rows each, both monotone; the reference starts at the
+ *          cell of the end point with the smaller x, or for one column at the smaller row; the other end point
+ *          lies in the last cell.)
+ *   dist   For a cell c, D = 2 c scale + scale - 2 s - 1 per axis (twice the distance, in sub-pixels, from the
+ *          centre of the sensor's sub-pixel to the centre of the cell), dist2 = Dx^2 + Dy^2 as int64.
+ *   stop   min_dist2 = m^2, m = csm_host_ray_cast_min_dist2's (below). Walk W in order. Cells outside rows x
+ *          cols of level 0 and cells with dist2 < min_dist2 are passed over. The first remaining cell with
+ *          value v >= occupied_min stops the ray, kind CSM_CAST_OCCUPIED; with unknown_stops so does the first
+ *          with v == 0, kind CSM_CAST_UNKNOWN. E = floor_div(e, scale) is part of W and can be the stop.
+ *   record cell, value, kind, dist2 of the stop; all zero (CSM_CAST_NONE) for a beam that is not cast or does
+ *          not stop. Records are pose-major per set ([n_poses][n_points]), sets concatenated.
+ * The device writes no floating-point result: it equals csm_host_ray_cast record for record.
+ *
+ * 64 bits. The ray check's limits hold here (|p - off| / res <= 2^20 per axis, range_max / res <= 2^20,
+ * subpixel_scale <= CSM_RAY_CHECK_MAX_SCALE), so the closed form stays within 2^63 as shown there. A cell of W
+ * lies between s and e per axis, up to one cell: |D| <= 2 |e - s| + 2 scale <= 2 (2^20 + 1) 512 + 2^10 < 2^30.1,
+ * and dist2 < 2^61.2 < 2^62. m is capped at 2^31, so min_dist2 <= 2^62 fits and then no cell stops a ray. */
+#define CSM_CAST_NONE      0
+#define CSM_CAST_OCCUPIED  1
+#define CSM_CAST_UNKNOWN   2
+typedef struct {
+    double   range_max, range_min;  /* range_max finite and > 0; range_min >= 0 (may be +inf: nothing stops) */
+    int32_t  subpixel_scale;        /* 1..CSM_RAY_CHECK_MAX_SCALE; the builder's is 100 */
+    uint32_t occupied_min;          /* raw cell value, 1..65535 */
+    int32_t  unknown_stops;         /* 0 | 1 */
+    int32_t  reserved;              /* 0 */
+    int64_t  scratch_limit_bytes;   /* 0 = default (1 GiB). A call is cut into chunks of consecutive poses (a
+                                       chunk may end inside a set): a pose of n beams counts 48 n + 64 bytes (ray
+                                       record, result record, workgroup counters, its share of the scan, pose
+                                       entry), and a chunk is closed before the pose that would take it past the
+                                       limit (a pose that alone exceeds it gets a chunk of its own) */
+} csm_ray_cast_params;
+typedef struct {
+    int32_t  cell_x, cell_y;        /* the stopping cell (column, row) */
+    uint32_t value;                 /* its raw value */
+    int32_t  kind;                  /* CSM_CAST_* */
+    int64_t  dist2;
+} csm_ray_cast_record;
+typedef struct {
+    int64_t rays;                   /* records written */
+    int64_t host_rays;              /* diagnostic, not part of the records: rays whose end point the host
+                                       recomputed with glibc */
+    int64_t cells_read;             /* cells of level 0 the walk loaded: whole groups of up to 64 per ray */
+    int64_t cells_to_stop;          /* cells inside the map up to and including each ray's stop (all of them
+                                       for a ray that does not stop); cells_read / cells_to_stop is the price of
+                                       one ray per wavefront */
+    double  host_us;                /* glibc end points */
+    double  device_us;              /* first launch to last, HIP events on the ctx stream */
+} csm_ray_cast_info;
+
+/* Host only: m = (int64)ceil(2 range_min / (resolution / subpixel_scale)), at most 2^31; *min_dist2 = m^2.
+ * CSM_EINVAL: a null pointer, range_min NaN or negative, a resolution that is not finite and > 0,
+ * subpixel_scale outside 1..CSM_RAY_CHECK_MAX_SCALE. */
+int  csm_host_ray_cast_min_dist2(double range_min, double resolution, int32_t subpixel_scale, int64_t* min_dist2);
+/* Host only: ranges[k] = (0.5 * (resolution / subpixel_scale)) * sqrt((double)records[k].dist2) for a record
+ * that stopped, none_value otherwise. One fixed f64 expression. CSM_EINVAL: null pointers (n > 0), n < 0, a
+ * resolution that is not finite and > 0, subpixel_scale outside 1..CSM_RAY_CHECK_MAX_SCALE. */
+int  csm_host_ray_cast_ranges(const csm_ray_cast_record* records, int64_t n, double resolution,
+                              int32_t subpixel_scale, double none_value, double* ranges);
+/* Host only: the definition as a sequential restatement on a dense rows x cols grid (row-major), every ray
+ * walked step by step (not by the closed form). records [n_poses][scan->n_points].
+ * CSM_EINVAL: null pointers (scan->ranges aside; angles, poses and records only where there is something to
+ * read or write), rows or cols < 1, n_points < 0, n_poses < 0, a resolution that is not finite and > 0,
+ * subpixel_scale outside 1..CSM_RAY_CHECK_MAX_SCALE, occupied_min outside 1..65535, unknown_stops other than
+ * 0 | 1, a negative scratch_limit_bytes, range_max not finite or <= 0, range_min NaN or negative, a non-finite
+ * pose, offset or angle, a sensor position more than 2^20 cells from the map's origin on an axis,
+ * range_max / res > 2^20. */
+int  csm_host_ray_cast(const uint16_t* grid, int32_t rows, int32_t cols, const csm_geometry* geom,
+                       const csm_scan* scan, const double* poses, int32_t n_poses,
+                       const csm_ray_cast_params* params, csm_ray_cast_record* records);
+/* The cast of every set against its resident map, on the device. One launch chain per chunk of poses: all end
+ * points in one launch under the map builder's certificate at the sub-pixel resolution (the few uncertifiable
+ * rays recomputed with glibc on the host and patched in; more of them than the context's map_uncertain_cap, or
+ * CSM_TUNE_MAP_HOST_PROJECTION, and the end points of that chunk and of the rest of the call all come from the
+ * host), one wavefront per ray over the closed form of its cells from the sensor's end, which stops reading at
+ * the ray's stop; one read-back of the records. Scans that sets of a chunk share by pointer are staged once.
+ * info may be NULL. n_sets = 0, n_poses = 0 and n_points = 0 are valid and launch nothing.
+ * CSM_EINVAL (before anything runs): what csm_host_ray_cast refuses, for any set; n_sets < 0; 2^30 or more
+ * poses in one set. CSM_ENOENT: a map that is not resident. The call reads the map only and keeps nothing on
+ * the context but workspaces. */
+int  csm_ray_cast(csm_ctx* ctx, const csm_pose_set* sets, int32_t n_sets, const csm_ray_cast_params* params,
+                  csm_ray_cast_record* records, csm_ray_cast_info* info);
+
 /* The raw records (csm_summary.raw) of the last csm_bnb_match_batch /
  * csm_correlative_match_batch call on this ctx, in query order, copied device
  * to device into dst_dev[n_queries] on the ctx stream (asynchronous): the

@@ -363,6 +363,25 @@ class PoseUpdateInfo(C.Structure):
                 ("bin_shift", C.c_int32), ("found", C.c_int32)]
 
 
+CAST_NONE, CAST_OCCUPIED, CAST_UNKNOWN = 0, 1, 2
+
+
+class RayCastParams(C.Structure):
+    _fields_ = [("range_max", C.c_double), ("range_min", C.c_double), ("subpixel_scale", C.c_int32),
+                ("occupied_min", C.c_uint32), ("unknown_stops", C.c_int32), ("reserved", C.c_int32),
+                ("scratch_limit_bytes", C.c_int64)]
+
+
+class RayCastRecord(C.Structure):
+    _fields_ = [("cell_x", C.c_int32), ("cell_y", C.c_int32), ("value", C.c_uint32), ("kind", C.c_int32),
+                ("dist2", C.c_int64)]
+
+
+class RayCastInfo(C.Structure):
+    _fields_ = [("rays", C.c_int64), ("host_rays", C.c_int64), ("cells_read", C.c_int64),
+                ("cells_to_stop", C.c_int64), ("host_us", C.c_double), ("device_us", C.c_double)]
+
+
 # name -> (restype, argtypes); mirrors include/csm_hip.h one to one
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -444,6 +463,11 @@ SIGNATURES = {
                                      _P(RayCheckParams), _P(RayCheckResult), C.c_void_p]),
     "csm_ray_check_batch": (C.c_int, [_ctx, _P(LoopQuery), C.c_int32, _P(RayCheckParams), _P(RayCheckResult),
                                       C.c_void_p]),
+    "csm_host_ray_cast_min_dist2": (C.c_int, [C.c_double, C.c_double, C.c_int32, _P(C.c_int64)]),
+    "csm_host_ray_cast_ranges": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_void_p]),
+    "csm_host_ray_cast": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(Geometry), _P(Scan), C.c_void_p, C.c_int32,
+                                    _P(RayCastParams), C.c_void_p]),
+    "csm_ray_cast": (C.c_int, [_ctx, _P(PoseSet), C.c_int32, _P(RayCastParams), C.c_void_p, _P(RayCastInfo)]),
     "csm_score_pose_sets": (C.c_int, [_ctx, _P(PoseSet), C.c_int32, C.c_void_p, _P(PoseSetsInfo)]),
     "csm_host_score_poses": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(Geometry), _P(Scan), C.c_void_p,
                                        C.c_int32, C.c_void_p]),

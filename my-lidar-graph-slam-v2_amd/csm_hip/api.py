@@ -472,6 +472,75 @@ def host_ray_check(grid, geom, angles, ranges, rel_pose, pose, per_beam=False, p
     return (ray_check_to_dict(out), words[:sc.n_points]) if per_beam else ray_check_to_dict(out)
 
 
+CAST_RECORD = np.dtype([("cell_x", "<i4"), ("cell_y", "<i4"), ("value", "<u4"), ("kind", "<i4"), ("dist2", "<i8")])
+CAST_NONE, CAST_OCCUPIED, CAST_UNKNOWN = L.CAST_NONE, L.CAST_OCCUPIED, L.CAST_UNKNOWN
+
+
+def ray_cast_params(range_max=20.0, range_min=0.0, subpixel_scale=100, occupied_min=None, unknown_stops=0,
+                    scratch_limit_bytes=0):
+    """A csm_ray_cast_params. occupied_min defaults to the value of P = 0.65 (host_ray_check_values)."""
+    if occupied_min is None:
+        occupied_min = host_ray_check_values()[0]
+    return L.RayCastParams(range_max, range_min, subpixel_scale, occupied_min, int(unknown_stops), 0,
+                           scratch_limit_bytes)
+
+
+def ray_cast_info_to_dict(i):
+    return dict(rays=int(i.rays), host_rays=int(i.host_rays), cells_read=int(i.cells_read),
+                cells_to_stop=int(i.cells_to_stop), host_us=float(i.host_us), device_us=float(i.device_us))
+
+
+def _cast_scan(angles, ranges):
+    """A csm_scan as the cast reads it: beam angles, and limits or None (a null pointer)."""
+    a = _f64(angles).reshape(-1)
+    r = None if ranges is None else _f64(ranges).reshape(-1)
+    if r is not None and r.size != a.size:
+        raise CsmError(L.CSM_EINVAL, "ray cast: one limit per angle")
+    sc = L.Scan()
+    sc.n_points = a.size
+    if a.size:                           # never a pointer to nothing
+        sc.angles = a.ctypes.data_as(C.POINTER(C.c_double))
+        if r is not None:
+            sc.ranges = r.ctypes.data_as(C.POINTER(C.c_double))
+    return sc, (a, r)
+
+
+def host_ray_cast_min_dist2(range_min, resolution, subpixel_scale):
+    """csm_host_ray_cast_min_dist2: the least dist2 a stopping cell may have."""
+    out = C.c_int64()
+    rc = L.load().csm_host_ray_cast_min_dist2(range_min, resolution, subpixel_scale, C.byref(out))
+    if rc:
+        raise CsmError(rc, "csm_host_ray_cast_min_dist2")
+    return out.value
+
+
+def host_ray_cast_ranges(records, resolution, subpixel_scale, none_value=0.0):
+    """csm_host_ray_cast_ranges: the f64 range of every record (any shape), none_value where it did not stop."""
+    rec = np.ascontiguousarray(records, dtype=CAST_RECORD)
+    out = np.zeros(rec.shape, np.float64)
+    rc = L.load().csm_host_ray_cast_ranges(_ptr(rec) if rec.size else None, rec.size, resolution, subpixel_scale,
+                                           none_value, _ptr(out) if rec.size else None)
+    if rc:
+        raise CsmError(rc, "csm_host_ray_cast_ranges")
+    return out
+
+
+def host_ray_cast(grid, geom, angles, poses, ranges=None, params=None, **kw):
+    """csm_host_ray_cast: beams at `angles` cast from every map-local sensor pose of `poses` (n, 3) through a
+    dense grid, step by step: a CAST_RECORD array (n, len(angles)). ranges: a limit per beam, or None."""
+    g = np.ascontiguousarray(grid, dtype=np.uint16)
+    sc, keep = _cast_scan(angles, ranges)
+    p = _poses(poses)
+    prm = params if params is not None else ray_cast_params(**kw)
+    out = np.zeros((p.shape[0], sc.n_points), CAST_RECORD)
+    rc = L.load().csm_host_ray_cast(_ptr(g), g.shape[0], g.shape[1], C.byref(L.Geometry(*geom)), C.byref(sc),
+                                    _ptr(p) if p.size else None, p.shape[0], C.byref(prm),
+                                    _ptr(out) if out.size else None)
+    if rc:
+        raise CsmError(rc, "csm_host_ray_cast")
+    return out
+
+
 POSE_RECORD = np.dtype([("sum_values", "<u4"), ("known", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 
 
@@ -1438,6 +1507,45 @@ class Context:
         out = self.pose_set_update(map_id, geom, angles, ranges, p, temperature, known_rate_threshold, n_out, offset)
         out["effective_sample_size"] = effective_sample_size(out["weights"])
         return out
+
+    def ray_cast(self, sets, params=None, **kw):
+        """csm_ray_cast: every set's beams cast from every map-local SENSOR pose of the set through its resident
+        map. sets: dicts(map_id, geom, angles, poses (n, 3)[, ranges: a limit per beam]); sets that pass the
+        same arrays share their pointers, so the library stages them once. Returns (a CAST_RECORD array
+        (n_poses, n_points) per set, the call's info dict)."""
+        arr = (L.PoseSet * max(len(sets), 1))()
+        keep, shapes = [], []
+        for i, s in enumerate(sets):
+            sc, held = _cast_scan(s["angles"], s.get("ranges"))
+            p = _poses(s["poses"])
+            keep += [held, p]
+            arr[i].map_id = s["map_id"]
+            arr[i].geometry = L.Geometry(*s["geom"])
+            arr[i].scan = sc
+            if p.size:
+                arr[i].poses = p.ctypes.data_as(C.POINTER(C.c_double))
+            arr[i].n_poses = p.shape[0]
+            shapes.append((p.shape[0], int(sc.n_points)))
+        prm = params if params is not None else ray_cast_params(**kw)
+        ends = np.cumsum([0] + [a * b for a, b in shapes])
+        out = np.zeros(max(int(ends[-1]), 1), CAST_RECORD)
+        info = L.RayCastInfo()
+        self._check(self.lib.csm_ray_cast(self._ctx, arr, len(sets), C.byref(prm), _ptr(out), C.byref(info)))
+        return ([out[ends[i]:ends[i + 1]].reshape(shapes[i]).copy() for i in range(len(sets))],
+                ray_cast_info_to_dict(info))
+
+    def virtual_scan(self, map_id, geom, pose, angles, ranges=None, params=None, **kw):
+        """A scan of the resident map from the map-local sensor pose `pose`: (angles, ranges) of the beams that
+        stopped, in beam order, ready for scan_descriptors, correlative_match (with a zero relative sensor
+        pose) and ray_check_batch. The ranges are csm_host_ray_cast_ranges' (centre of the sensor's sub-pixel
+        to the centre of the stopping cell)."""
+        prm = params if params is not None else ray_cast_params(**kw)
+        a = _f64(angles).reshape(-1)
+        recs, _ = self.ray_cast([dict(map_id=map_id, geom=geom, angles=a, ranges=ranges, poses=[pose])], params=prm)
+        rec = recs[0][0]
+        hit = rec["kind"] != CAST_NONE
+        rng = host_ray_cast_ranges(rec, geom[0], prm.subpixel_scale)
+        return a[hit].copy(), rng[hit].copy()
 
     def ray_check_batch(self, queries, poses=None, per_beam=False, params=None, **kw):
         """csm_ray_check_batch: the free-space check of every query's scan against its resident map at the

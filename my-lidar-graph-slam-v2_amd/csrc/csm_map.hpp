@@ -235,6 +235,28 @@ struct RayClip {
     int x_lo, x_hi, y_lo, y_hi;
 };
 
+/* The rows from..to of column x0 + j, 0 <= j <= m = x1 - x0, of a ray with x0 < x1 in the closed form's terms
+ * (below): from where the ray enters the column to where it leaves it. The ray cast (csm_cast_kernels.hip)
+ * enumerates the cells of ray_cells_closed_form from the sensor's end through this function. The template
+ * below keeps its own lines of the same expressions: calling this function from it moved the scalar register
+ * counts of k_map_walk (78 -> 80) and k_ray_walk (74 -> 75), and those kernels are to stay as they are. The
+ * ray cast's tests compare the two texts cell for cell (the cast against the step-by-step walk, which the
+ * ray check's tests compare the template with). */
+__device__ __forceinline__ void ray_column_rows(int j, int m, int y0, int scale, long long n0, long long dy,
+                                                long long den, long long first, long long last, int& from, int& to)
+{
+    const long long n_out = j < m ? n0 + dy * (first + 2ll * scale * j)
+                                  : n0 + dy * (first + 2ll * scale * (m - 1) + last);
+    const long long n_in = n0 + dy * (first + 2ll * scale * (j - 1));   /* unused for j = 0 */
+    if (dy > 0) {
+        from = j == 0 ? y0 : (int)(n_in / den);
+        to = (int)((n_out + den - 1) / den) - 1;
+    } else {
+        to = j == 0 ? y0 : (int)((n_in + den - 1) / den) - 1;
+        from = (int)(n_out / den);
+    }
+}
+
 template <bool kClip, class Visit>
 __device__ __forceinline__ void ray_cells_closed_form(int sx, int sy, int ex, int ey, int scale, int lane,
                                                       const RayClip& clip, Visit&& visit)

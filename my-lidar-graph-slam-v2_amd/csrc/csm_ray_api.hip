@@ -1,6 +1,7 @@
 /* csm_ray_api.hip -- the free-space check of loop candidates: csm_ray_check_batch and the host
  * restatements csm_host_ray_check / csm_host_ray_check_values (include/csm_hip.h), with their kernels
- * (csm_ray_kernels.hip). A translation unit of libcsm_hip.so of its own.
+ * (csm_ray_kernels.hip). A translation unit of libcsm_hip.so of its own; what it shares with the ray cast
+ * (csm_cast_api.hip) is csm_ray.hpp.
  *
  * A batch is checked first (every query, every map: a refused call has run nothing) and then cut into chunks
  * of consecutive queries. Per chunk: one upload ([queries][prefixes][the distinct scans], from rc_pin into
@@ -21,14 +22,6 @@ static_assert(sizeof(csm_ray_check_result) == kRayRecordBytes &&
 
 namespace {
 
-constexpr double kRayMaxCells = 1048576.0;           /* 2^20: the 64-bit bound of the closed form */
-constexpr int64_t kRayDefaultScratch = 1ll << 30;
-
-uint32_t ray_unc_cap(const csm_ctx* ctx)             /* csm_config.map_uncertain_cap, as the map builder */
-{
-    return ctx->tune.map_unc_cap > 0 ? (uint32_t)std::min<long>(ctx->tune.map_unc_cap, kMapUncCap) : kMapUncCap;
-}
-
 bool ray_params_ok(const csm_ray_check_params* p)
 {
     return p && p->subpixel_scale >= 1 && p->subpixel_scale <= CSM_RAY_CHECK_MAX_SCALE && p->end_tolerance >= 0 &&
@@ -36,15 +29,14 @@ bool ray_params_ok(const csm_ray_check_params* p)
            p->scratch_limit_bytes >= 0 && !std::isnan(p->usable_range_min) && !std::isnan(p->usable_range_max);
 }
 
-/* the sensor pose S and its sub-pixel index; false: the query is refused */
-bool ray_frame(const csm_geometry* geom, const csm_scan* scan, const double pose[3], const csm_ray_check_params* p,
-               double S[3], int32_t s[2])
+/* the sensor pose S and its sub-pixel index (ray_frame, csm_ray.hpp); false: the query is refused */
+bool ray_query_frame(const csm_geometry* geom, const csm_scan* scan, const double pose[3],
+                     const csm_ray_check_params* p, double S[3], int32_t s[2])
 {
     if (!geom || !scan || !pose || scan->n_points < 0 || (scan->n_points > 0 && (!scan->angles || !scan->ranges)))
         return false;
     if (!geometry_is_finite(geom))
         return false;
-    const double res = geom->resolution;
     for (int k = 0; k < 3; ++k)
         if (!std::isfinite(pose[k]) || !std::isfinite(scan->relative_sensor_pose[k]))
             return false;
@@ -52,88 +44,7 @@ bool ray_frame(const csm_geometry* geom, const csm_scan* scan, const double pose
         if (!std::isfinite(scan->angles[i]))
             return false;
     csm_host_compound(pose, scan->relative_sensor_pose, S);
-    if (!(std::fabs((S[0] - geom->offset_x) / res) <= kRayMaxCells) ||
-        !(std::fabs((S[1] - geom->offset_y) / res) <= kRayMaxCells) || !(p->usable_range_max / res <= kRayMaxCells))
-        return false;
-    const double scaled_res = res / p->subpixel_scale;
-    s[0] = cell_index(S[0], geom->offset_x, scaled_res);
-    s[1] = cell_index(S[1], geom->offset_y, scaled_res);
-    return true;
-}
-
-/* ScanData::HitPoint with glibc (host_hit_point, csm_certify.hpp), and its four integers */
-RayRec ray_host_rec(const double S[3], const csm_geometry* geom, double scaled_res, double r, double a)
-{
-    double hx, hy;
-    host_hit_point(S[0], S[1], S[2], r, a, &hx, &hy);
-    RayRec rec;
-    rec.ex = cell_index(hx, geom->offset_x, scaled_res);
-    rec.ey = cell_index(hy, geom->offset_y, scaled_res);
-    rec.hx = cell_index(hx, geom->offset_x, geom->resolution);
-    rec.hy = cell_index(hy, geom->offset_y, geom->resolution);
-    return rec;
-}
-
-int host_floor_div(int a, int b)
-{
-    const int q = a / b;
-    return q * b > a ? q - 1 : q;
-}
-
-typedef std::pair<int, int> Cell;   /* (x = column, y = row) */
-
-/* BresenhamScaled (src/bresenham.cpp:58-237) step by step, on non-negative coordinates: the error term is
- * carried from column to column as the reference carries it. The falling case runs the rising loop on the
- * mirrored sub-row position (subY < 0 <-> subY > denominator, subY == 0 <-> subY == denominator). */
-void ray_step_cells(int sx, int sy, int ex, int ey, int scale, std::vector<Cell>& out)
-{
-    out.clear();
-    if (sx > ex) {
-        std::swap(sx, ex);
-        std::swap(sy, ey);
-    }
-    const int start_x = sx / scale, start_y = sy / scale, end_x = ex / scale, end_y = ey / scale;
-    auto visit = [&out](int x, int y) {
-        if (out.empty() || out.back() != Cell(x, y))
-            out.emplace_back(x, y);
-    };
-    if (start_x == end_x) {
-        for (int y = std::min(start_y, end_y); y <= std::max(start_y, end_y); ++y)
-            visit(start_x, y);
-        return;
-    }
-    const int64_t dx = ex - sx, dy = ey - sy;
-    const int64_t denom = 2 * static_cast<int64_t>(scale) * dx;
-    const int up = dy > 0 ? 1 : -1;
-    const int64_t rise = dy > 0 ? dy : -dy;
-    int64_t sub = (2 * (sy % scale) + 1) * dx;
-    if (up < 0)
-        sub = denom - sub;
-    int x = start_x, y = start_y;
-    visit(x, y);
-    sub += rise * (2 * scale - (2 * (sx % scale) + 1));
-    for (;;) {
-        visit(x, y);
-        while (sub > denom) {
-            sub -= denom;
-            y += up;
-            visit(x, y);
-        }
-        if (sub == denom) {                 /* exactly through a corner: a diagonal step */
-            sub -= denom;
-            y += up;
-        }
-        if (++x == end_x)
-            break;
-        sub += 2 * rise * scale;
-    }
-    sub += rise * (2 * (ex % scale) + 1);
-    visit(x, y);
-    while (sub > denom) {
-        sub -= denom;
-        y += up;
-        visit(x, y);
-    }
+    return ray_frame(geom, S, p->usable_range_max, p->subpixel_scale, s);
 }
 
 /* Chunks of consecutive queries: a query of n beams counts 36 n + 256 bytes (record, word, scan, table
@@ -170,7 +81,8 @@ int csm_host_ray_check(const uint16_t* grid, int32_t rows, int32_t cols, const c
 {
     double S[3];
     int32_t s[2];
-    if (!grid || rows < 1 || cols < 1 || !result || !ray_params_ok(prm) || !ray_frame(geom, scan, pose, prm, S, s))
+    if (!grid || rows < 1 || cols < 1 || !result || !ray_params_ok(prm) ||
+        !ray_query_frame(geom, scan, pose, prm, S, s))
         return CSM_EINVAL;
     const int scale = prm->subpixel_scale;
     const double scaled_res = geom->resolution / scale;
@@ -253,7 +165,7 @@ int csm_ray_check_batch(csm_ctx* ctx, const csm_loop_query* queries, int32_t n_q
     std::vector<Frame> frames((size_t)n_queries);
     for (int i = 0; i < n_queries; ++i) {
         const csm_loop_query& q = queries[i];
-        if (!ray_frame(&q.geometry, &q.scan, q.initial_pose, prm, frames[i].S, frames[i].s))
+        if (!ray_query_frame(&q.geometry, &q.scan, q.initial_pose, prm, frames[i].S, frames[i].s))
             return fail(ctx, CSM_EINVAL, "ray check: query %d has a bad scan, geometry or pose, a sensor more than "
                         "2^20 cells from the map's origin, or usable_range_max / resolution > 2^20", i);
         const DeviceGrid* g = find_grid(ctx, q.map_id);

@@ -1,6 +1,8 @@
 /* csm_ray_kernels.hip -- the free-space check of loop candidates (included by csm_ray_api.hip; the
  * definition is in include/csm_hip.h, csm_ray_check_batch). gfx950 only.
  *
+ * RayRec, the projection body and the patch body are csm_ray.hpp's, shared with the ray cast.
+ *
  *   k_ray_project  one thread per beam of a chunk of queries: the hit point with the device's sin / cos,
  *                  its four integers (sub-pixel end, hit cell) and the map builder's certificate
  *                  (certified, csm_certify.hpp) at both resolutions on both axes. The frame is fixed here
@@ -20,18 +22,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "csm_map.hpp"
+#include "csm_ray.hpp"
 
 namespace csm {
 
 constexpr int kRayGroup = 16;                /* rays per workgroup of k_ray_walk: 4 per wavefront */
-constexpr int32_t kRayUnusable = (int32_t)0x80000000;   /* RayRec.ex of an unusable beam (no index reaches it) */
-
-struct RayRec {
-    int32_t ex, ey;            /* sub-pixel index of the hit point; ex = kRayUnusable: the beam is not usable */
-    int32_t hx, hy;            /* the hit cell H */
-};
-
 /* one query of a chunk */
 struct RayQuery {
     const uint16_t* cells;     /* level 0 of its map */
@@ -78,34 +73,18 @@ __global__ __launch_bounds__(256) void k_ray_project(RayChunk ch)
     const double r = ch.scans[q.ranges_at + i];
     RayRec rec = { kRayUnusable, 0, 0, 0 };
     if (r > ch.min_range && r < ch.max_range) {
-        const double arg = q.theta + ch.scans[q.angles_at + i];
-        const double hx = q.x + r * cos(arg);
-        const double hy = q.y + r * sin(arg);
-        rec.ex = cell_index(hx, q.off_x, q.scaled_res);
-        rec.ey = cell_index(hy, q.off_y, q.scaled_res);
-        rec.hx = cell_index(hx, q.off_x, q.res);
-        rec.hy = cell_index(hy, q.off_y, q.res);
-        const bool sure = certified(r, hx, q.off_x, q.res) && certified(r, hy, q.off_y, q.res) &&
-                          certified(r, hx, q.off_x, q.scaled_res) && certified(r, hy, q.off_y, q.scaled_res);
-        if (!sure) {
-            const uint32_t pos = atomicAdd(ch.unc, 1u);
-            if (pos < ch.unc_cap)
-                ch.unc[1 + pos] = (uint32_t)b;
-        }
+        bool sure;
+        rec = ray_project<true>(q.x, q.y, q.theta, r, ch.scans[q.angles_at + i], q.off_x, q.off_y, q.res, q.scaled_res,
+                                sure);
+        if (!sure)
+            ray_list(ch.unc, ch.unc_cap, (uint32_t)b);
     }
     ch.recs[b] = rec;
 }
 
-struct RayPatch {
-    uint32_t beam;
-    RayRec   rec;
-};
-
 __global__ __launch_bounds__(256) void k_ray_patch(const RayPatch* patches, int n, RayRec* recs)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n)
-        recs[patches[i].beam] = patches[i].rec;
+    ray_patch_one(patches, n, recs, blockIdx.x * 256 + threadIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_ray_walk(RayChunk ch)

@@ -13,6 +13,8 @@
  * mode 5 (pose-graph optimizer) has a layout of its own: see run_pose_graph.
  * mode 7 (pose sets) reads the common layout as: n_queries = robot poses in init, param_i = outputs of the
  *   resampling, rangeX = temperature, rangeY / rangeT = the low / high 32 bits of the resampling offset.
+ * mode 8 (virtual scans) reads it as: n_queries = sensor poses in init, param_i = unknown_stops, rangeX =
+ *   range_max, rangeY = range_min, rangeT = the sub-pixel scale, scoreThr = occupied_min; ranges is not used.
  */
 #include <cinttypes>
 #include <cstdio>
@@ -265,6 +267,40 @@ int main(int argc, char** argv)
                     "\"bin_shift\": %d, \"found\": %d, \"uncertain\": %d}\n", u.mEffectiveSampleSize,
                     (unsigned long long)u.mUpdate.m0, (unsigned long long)u.mUpdate.key_max, u.mUpdate.best_index,
                     u.mUpdate.support, u.mUpdate.bin_shift, u.mUpdate.found, u.mInfo.uncertain_poses);
+        return 0;
+    }
+    if (mode == 8) {
+        /* VirtualScanHIP: the records and ranges of every pose's beams, and the scan of the first pose */
+        auto caster = VirtualScanHIP::Create();
+        if (!caster) {
+            std::printf("{\"error\": \"no device\"}\n");
+            return 3;
+        }
+        g.mId = 42;
+        caster->Upload(g);
+        const csm_geometry geom = { g.mResolution, g.mPosOffsetX, g.mPosOffsetY };
+        std::vector<RobotPose2D<double>> sensor(nq);
+        for (int i = 0; i < nq; ++i)
+            sensor[i] = { init[3 * i], init[3 * i + 1], init[3 * i + 2] };
+        RayCastSettings settings;
+        settings.mRangeMax = prm[3];
+        settings.mRangeMin = prm[4];
+        settings.mSubpixelScale = (int)prm[5];
+        settings.mOccupiedMin = (std::uint32_t)prm[6];
+        settings.mUnknownStops = pi != 0;
+        settings.mNoneValue = -1.0;
+        const VirtualScanHIP::Casts casts = caster->Cast(g.mId, geom, sensor, angles, settings);
+        const VirtualScan scan = caster->ScanFromMap(g.mId, geom, sensor.front(), angles, settings);
+        std::printf("{\"records\": [");
+        for (size_t i = 0; i < casts.mRecords.size(); ++i) {
+            const csm_ray_cast_record& r = casts.mRecords[i];
+            std::printf("%s[%d, %d, %u, %d, %lld, \"%a\"]", i ? ", " : "", r.cell_x, r.cell_y, r.value, r.kind,
+                        (long long)r.dist2, casts.mRanges[i]);
+        }
+        std::printf("], \"scan\": [");
+        for (size_t i = 0; i < scan.mAngles.size(); ++i)
+            std::printf("%s[\"%a\", \"%a\"]", i ? ", " : "", scan.mAngles[i], scan.mRanges[i]);
+        std::printf("], \"rays\": %lld, \"beams\": %zu}\n", (long long)casts.mInfo.rays, scan.View().mNumOfScans);
         return 0;
     }
     /* CSM_DEMO_DEVICES="0,0": the detector over a device list (here two members on GPU 0) */

@@ -15,6 +15,7 @@
  *   ScorePixelAccurateHIP       <- ScorePixelAccurate (ScoreFunction::Score at free poses)
  *        inc/mapping/score_function.hpp:29-60, src/mapping/score_function_pixel_accurate.cpp:16-58
  *   ParticleSetHIP              (beyond the reference) weights and resampling of a particle set
+ *   VirtualScanHIP              (beyond the reference) beams cast through a resident map: records, ranges, a scan
  *   LoopSearcherNearestHIP      <- LoopSearcherNearest
  *        inc/mapping/loop_searcher_nearest.hpp:33-63, src/mapping/loop_searcher_nearest.cpp:59-170
  *   LoopSearcherAppearanceHIP   (no counterpart: candidates by scan descriptors, csm_appearance_search)
@@ -1841,6 +1842,127 @@ private:
         mTemperature(temperature), mKnownRateThreshold(knownRateThreshold), mCtx(std::move(ctx)) { }
 
     const double mTemperature, mKnownRateThreshold;
+    detail::ContextRef mCtx;
+};
+
+/* The settings of a cast (csm_ray_cast_params). Create: occupied at P >= probOccupied (above 0.5), the raw
+ * value the ray check would use (csm_host_ray_check_values). */
+struct RayCastSettings {
+    double mRangeMax = 20.0, mRangeMin = 0.0;
+    int mSubpixelScale = 100;
+    std::uint32_t mOccupiedMin = 0;
+    bool mUnknownStops = false;
+    double mNoneValue = 0.0;             /* the range reported for a beam that did not stop */
+
+    static RayCastSettings Create(double rangeMax = 20.0, double rangeMin = 0.0, double probOccupied = 0.65,
+                                  bool unknownStops = false, int subpixelScale = 100)
+    {
+        RayCastSettings s;
+        s.mRangeMax = rangeMax;
+        s.mRangeMin = rangeMin;
+        s.mSubpixelScale = subpixelScale;
+        s.mUnknownStops = unknownStops;
+        std::uint32_t freeMax = 0;
+        CSM_ASSERT_OK(nullptr, csm_host_ray_check_values(probOccupied, 1.0 - probOccupied, &s.mOccupiedMin, &freeMax));
+        return s;
+    }
+    csm_ray_cast_params Params() const
+    {
+        csm_ray_cast_params p {};
+        p.range_max = this->mRangeMax;
+        p.range_min = this->mRangeMin;
+        p.subpixel_scale = this->mSubpixelScale;
+        p.occupied_min = this->mOccupiedMin;
+        p.unknown_stops = this->mUnknownStops ? 1 : 0;
+        return p;
+    }
+};
+
+/* A scan that owns its beams (ScanDataView points into it). */
+struct VirtualScan {
+    std::vector<double> mAngles, mRanges;
+    ScanDataView View() const
+    {
+        ScanDataView v;
+        v.mAngles = this->mAngles.data();
+        v.mRanges = this->mRanges.data();
+        v.mNumOfScans = this->mAngles.size();
+        return v;
+    }
+};
+
+/* Virtual scans (beyond the reference, which only ever walks a measured beam): from map-local sensor poses,
+ * in the directions of `angles`, the first cell of a resident map that stops each beam and its distance
+ * (csm_ray_cast; the ranges from csm_host_ray_cast_ranges). ScanFromMap gives the stopped beams of one pose as
+ * a scan with a zero relative sensor pose: a finished local map seen from its centre can then go through the
+ * descriptors, the matchers and the ray check like any scan node. A map is made resident with Upload() or by
+ * any other adapter that shares the context. */
+class VirtualScanHIP final {
+public:
+    struct Casts {
+        std::vector<csm_ray_cast_record> mRecords;     /* [poses][angles] */
+        std::vector<double> mRanges;                   /* likewise; mNoneValue where a beam did not stop */
+        csm_ray_cast_info mInfo {};
+    };
+
+    static std::unique_ptr<VirtualScanHIP> Create(int deviceId = 0)
+    {
+        detail::CtxPtr ctx = detail::MakeContext(deviceId);
+        if (!ctx)
+            return nullptr;
+        return std::unique_ptr<VirtualScanHIP>(new VirtualScanHIP(detail::ContextRef(std::move(ctx))));
+    }
+    /* on a context another adapter owns (and keeps alive) */
+    explicit VirtualScanHIP(csm_ctx* shared) : mCtx(shared) { }
+
+    VirtualScanHIP(const VirtualScanHIP&) = delete;
+    VirtualScanHIP& operator=(const VirtualScanHIP&) = delete;
+
+    csm_ctx* Context() const { return this->mCtx.Get(); }
+
+    void Upload(const GridMapView& g)
+    {
+        CSM_ASSERT_OK(this->Context(), csm_upload_grid(this->Context(), g.mId, g.mValues, g.mRows, g.mCols));
+    }
+
+    Casts Cast(std::uint64_t mapId, const csm_geometry& geometry,
+               const std::vector<RobotPose2D<double>>& mapLocalSensorPoses, const std::vector<double>& angles,
+               const RayCastSettings& settings)
+    {
+        ScanDataView beams;
+        beams.mAngles = angles.data();
+        beams.mNumOfScans = angles.size();
+        const csm_pose_set set = detail::ToPoseSet(mapId, geometry, beams, mapLocalSensorPoses);
+        const csm_ray_cast_params prm = settings.Params();
+        Casts out;
+        out.mRecords.resize(mapLocalSensorPoses.size() * angles.size());
+        out.mRanges.resize(out.mRecords.size());
+        CSM_ASSERT_OK(this->Context(), csm_ray_cast(this->Context(), &set, 1, &prm, out.mRecords.data(), &out.mInfo));
+        CSM_ASSERT_OK(this->Context(), csm_host_ray_cast_ranges(out.mRecords.data(),
+                                                                static_cast<std::int64_t>(out.mRecords.size()),
+                                                                geometry.resolution, prm.subpixel_scale,
+                                                                settings.mNoneValue, out.mRanges.data()));
+        return out;
+    }
+
+    /* the beams of one pose that stopped, in beam order */
+    VirtualScan ScanFromMap(std::uint64_t mapId, const csm_geometry& geometry,
+                            const RobotPose2D<double>& mapLocalSensorPose, const std::vector<double>& angles,
+                            const RayCastSettings& settings)
+    {
+        const Casts casts = this->Cast(mapId, geometry, { mapLocalSensorPose }, angles, settings);
+        VirtualScan scan;
+        for (std::size_t i = 0; i < angles.size(); ++i)
+            if (casts.mRecords[i].kind != CSM_CAST_NONE) {
+                scan.mAngles.push_back(angles[i]);
+                scan.mRanges.push_back(casts.mRanges[i]);
+            }
+        return scan;
+    }
+
+private:
+    explicit VirtualScanHIP(detail::ContextRef ctx) : mCtx(std::move(ctx)) { }
+
     detail::ContextRef mCtx;
 };
 
