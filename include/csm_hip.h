@@ -1775,6 +1775,89 @@ int  csm_appearance_search(csm_ctx* ctx, const uint8_t* descriptors, const int32
                            const csm_appearance_params* params, csm_appearance_candidate* out, int32_t* counts,
                            csm_loop_search_info* info);
 
+/* ---- loop edges: pairwise consistency and the largest consistent set ----
+ *
+ * Do the loop edges agree with each other? Two correct closures predict the same drift; a closure onto an
+ * aliased place agrees with nobody. Every pair of edges closes a cycle: its two measurements forward, the
+ * current estimates backward; the cycle's error is tested against its first-order covariance.
+ *
+ * Inputs. local_poses[n_local][3], scan_poses[n_scan][3]: the current estimates, as csm_pose_graph_lm takes
+ * them. edges[n_edges]: start = local map node s, end = scan node t, z = relative_pose = the measured
+ * InverseCompound(x_s, x_t), Lambda = information; is_loop is not read. gate: the chi-square bound. The drift
+ * model (all three or none): drift_var_per_metre[3], local_travel[n_local], scan_travel[n_scan] (accumulated
+ * travel: csm_host_travel_distances for scan nodes; a local map takes the value of its first scan node).
+ *
+ * Tables, on the host (glibc; the device does no trigonometry): per edge (cos z.theta, sin z.theta) and Sigma =
+ * Lambda^-1 through csm_host_information_from_covariance (exactly symmetric; a pivot that is not positive and
+ * finite: CSM_EINVAL); per node that an edge names (cos theta, sin theta), once.
+ *
+ * The pair i < j. R(c, s) is the rotation of a table entry, J = [[0, -1], [1, 0]], p a pose's translation;
+ * rotations are composed as products of table entries, never from summed angles:
+ *   t_B = R_ti^T (p_tj - p_ti)      R_B = R_ti^T R_tj          scan node t_i -> t_j, estimates
+ *   t_C = -R_zj^T t_zj              R_C = R_zj^T               z_j inverted
+ *   t_D = R_sj^T (p_si - p_sj)                                 local map s_j -> s_i, estimates
+ *   u   = t_B + R_B (t_C + R_C t_D)
+ *   e_xy = t_zi + R_zi u
+ *   e_th = NormalizeAngle(((z_i.th + (th_tj - th_ti)) - z_j.th) + (th_si - th_sj))
+ *   J_i  = [[I, R_zi J u], [0, 1]]
+ *   R_Q  = (R_zi R_B) R_C
+ *   J_j  = [[-R_Q, R_Q J (t_zj - t_D)], [0, -1]]
+ *   l_ij = |scan_travel[t_i] - scan_travel[t_j]| + |local_travel[s_i] - local_travel[s_j]|    (0 without a model)
+ *   M    = (J_i Sigma_i J_i^T + J_j Sigma_j J_j^T) + l_ij diag(drift_var_per_metre)
+ *   chi2 = e^T M^-1 e      through the optimizer's 3x3 LDL^T and substitution, as csm_host_loop_gate forms it:
+ *                          (e_0 x_0 + e_1 x_1) + e_2 x_2
+ * J_i, J_j: the first-order Jacobians of e in z_i and z_j. The drift term is added unrotated, which is exact
+ * when its x and y entries are equal. Every operation is +, -, *, / or fmod in f64 in one fixed order (DESIGN.md
+ * 4o), the same text on the host and on the device.
+ *
+ * Consistency. The pair (i, j), i < j, is consistent iff every pivot of M is positive and finite and chi2 <=
+ * gate; a bad pivot makes it inconsistent and is counted. The relation is defined for i < j and mirrored (the
+ * cycle taken from j's side is another first-order expression); the diagonal is 0. Two peaks of the same (map,
+ * scan) pair are inconsistent unless they agree within their covariances; identical edges have chi2 = 0.
+ *
+ * Selection, integers only. Seeds: the n_seeds vertices of highest degree, ties to the lower index (n_seeds = 0
+ * or >= n_edges: all). Per seed v0: K = {v0}, C = N(v0); while C is not empty take the u in C with the largest
+ * |N(u) & C|, ties to the lower index, K += u, C &= N(u). The result is the largest K, ties to the seed of
+ * better rank.
+ *
+ * Outputs. selected[n_edges] (0 | 1), degree[n_edges], info; optionally adjacency[n_edges][ceil(n_edges / 64)]
+ * (bit j & 63 of word j >> 6 of row i) and chi2[n_edges][n_edges] (mirrored, zero diagonal, +inf where a pivot
+ * was bad), the latter for at most CSM_LOOP_CONSISTENCY_MAX_CHI2_EDGES edges (32 MB).
+ *
+ * CSM_EINVAL, on the host before any launch: a null pointer (the optional ones aside); n_local or n_scan < 1;
+ * n_edges outside 1..CSM_LOOP_CONSISTENCY_MAX_EDGES; an edge's node index out of range; a non-finite pose,
+ * relative pose, information entry, travel value or drift variance; a negative drift variance; a negative or
+ * NaN gate (+inf is allowed: every pair with good pivots is consistent); travel arrays without the variances or
+ * the reverse; n_seeds < 0; chi2 asked for above its cap; an information matrix that cannot be inverted. */
+#define CSM_LOOP_CONSISTENCY_MAX_EDGES       8192   /* 8 MB of adjacency */
+#define CSM_LOOP_CONSISTENCY_MAX_CHI2_EDGES  2048   /* 32 MB of chi-square values */
+typedef struct {
+    int64_t consistent_pairs;       /* pairs i < j that are consistent */
+    int64_t bad_pivots;             /* pairs i < j whose M had a pivot that is not positive and finite */
+    int32_t clique_size;            /* edges selected */
+    int32_t winning_seed;           /* the edge the winning search started from */
+    int32_t seeds_run;
+    int32_t reserved;               /* 0 */
+} csm_loop_consistency_info;
+
+/* Host only: the rule as a sequential restatement. The CPU reference of csm_loop_consistency. */
+int  csm_host_loop_consistency(const double* local_poses, int32_t n_local, const double* scan_poses, int32_t n_scan,
+                               const csm_pose_graph_edge* edges, int32_t n_edges, double gate,
+                               const double* drift_var_per_metre, const double* local_travel,
+                               const double* scan_travel, int32_t n_seeds, int32_t* selected, int32_t* degree,
+                               csm_loop_consistency_info* info, uint64_t* adjacency, double* chi2);
+/* On the device, on the ctx stream: one upload of the edge records (192 bytes per edge), the pair kernel (a
+ * wavefront per row edge and 64 column edges, a pair per lane, the ballot is the adjacency word), degrees by
+ * popcount, the seed ranking by counting, a workgroup per seed for the greedy searches, one workgroup that
+ * picks the winner; one read-back. No host round trip inside the chain. Returns when the results are on the
+ * host. Every byte of every output equals csm_host_loop_consistency's. Timers: "loop_consistency" (the chain),
+ * and inside it "loop_consistency_pairs" and "loop_consistency_select". */
+int  csm_loop_consistency(csm_ctx* ctx, const double* local_poses, int32_t n_local, const double* scan_poses,
+                          int32_t n_scan, const csm_pose_graph_edge* edges, int32_t n_edges, double gate,
+                          const double* drift_var_per_metre, const double* local_travel, const double* scan_travel,
+                          int32_t n_seeds, int32_t* selected, int32_t* degree, csm_loop_consistency_info* info,
+                          uint64_t* adjacency, double* chi2);
+
 /* ---- measurement hooks (bench.py) ---- */
 /* enable = 1: every kernel launch is bracketed by HIP events on the ctx
  * stream; enable = 2: only the dominant (fine-level) scoring kernel, to keep
@@ -1786,7 +1869,7 @@ int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
  * "ray_project" | "ray_walk" | "pose_prep" | "pose_score" | "pose_rescore" | "pose_weights" |
  * "pose_resample" | "pose_graph" | "pose_graph_marginals" |
  * "pose_graph_marginals_factor" | "pose_graph_marginals_solve" | "loop_search" | "scan_descriptors" |
- * "appearance_search". */
+ * "appearance_search" | "loop_consistency" | "loop_consistency_pairs" | "loop_consistency_select". */
 int  csm_kernel_time(csm_ctx* ctx, const char* name, double* total_ms,
                      int64_t* launches);
 int  csm_reset_kernel_timing(csm_ctx* ctx);

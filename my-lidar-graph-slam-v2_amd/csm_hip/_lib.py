@@ -315,6 +315,14 @@ class LoopSearchInfo(C.Structure):
     _fields_ = [("pairs_evaluated", C.c_int64), ("pairs_eligible", C.c_int64)]
 
 
+LOOP_CONSISTENCY_MAX_EDGES, LOOP_CONSISTENCY_MAX_CHI2_EDGES = 8192, 2048
+
+
+class LoopConsistencyInfo(C.Structure):
+    _fields_ = [("consistent_pairs", C.c_int64), ("bad_pivots", C.c_int64), ("clique_size", C.c_int32),
+                ("winning_seed", C.c_int32), ("seeds_run", C.c_int32), ("reserved", C.c_int32)]
+
+
 DESCRIPTOR_MAX_RINGS, DESCRIPTOR_MAX_SECTORS, DESCRIPTOR_MAX_BEAMS = 32, 128, 65536
 APPEARANCE_REF_CHUNK, APPEARANCE_TABLE_BYTES = 128, 64 << 20
 
@@ -544,6 +552,12 @@ SIGNATURES = {
                                         C.c_void_p, _P(LoopSearchInfo)]),
     "csm_host_loop_candidates_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                                    _P(C.c_int32)]),
+    "csm_host_loop_consistency": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(PoseGraphEdge), C.c_int32,
+                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, _P(LoopConsistencyInfo), C.c_void_p, C.c_void_p]),
+    "csm_loop_consistency": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(PoseGraphEdge), C.c_int32,
+                                       C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, _P(LoopConsistencyInfo), C.c_void_p, C.c_void_p]),
     "csm_shard_bounds": (None, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "csm_group_create": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
     "csm_group_create_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, _P(C.c_void_p)]),

@@ -747,6 +747,59 @@ def host_information_from_covariance(cov):
     return out
 
 
+def _loop_consistency_run(fn, head, local_poses, scan_poses, edges, gate, drift_var_per_metre, local_travel,
+                          scan_travel, n_seeds, want_adjacency, want_chi2):
+    lp = np.ascontiguousarray(local_poses, dtype=np.float64).reshape(-1, 3)
+    sp = np.ascontiguousarray(scan_poses, dtype=np.float64).reshape(-1, 3)
+    ea = pose_graph_edges(edges)
+    m = len(edges)
+    words = (max(m, 1) + 63) // 64
+    dv = None if drift_var_per_metre is None else _f64(drift_var_per_metre).reshape(-1)
+    lt = None if local_travel is None else _f64(local_travel).reshape(-1)
+    st = None if scan_travel is None else _f64(scan_travel).reshape(-1)
+    if (dv is not None and dv.size != 3) or (lt is not None and lt.size != lp.shape[0]) or \
+            (st is not None and st.size != sp.shape[0]):
+        raise CsmError(L.CSM_EINVAL, "loop_consistency: three drift variances, one travel value per node")
+    selected = np.zeros(max(m, 1), np.int32)
+    degree = np.zeros(max(m, 1), np.int32)
+    info = L.LoopConsistencyInfo()
+    adj = np.zeros((max(m, 1), words), np.uint64) if want_adjacency else None
+    chi = np.zeros((max(m, 1), max(m, 1))) if want_chi2 else None
+    opt = lambda a: None if a is None else _ptr(a)
+    rc = fn(*head, _ptr(lp), lp.shape[0], _ptr(sp), sp.shape[0], ea, m, float(gate), opt(dv), opt(lt), opt(st),
+            int(n_seeds), _ptr(selected), _ptr(degree), C.byref(info), opt(adj), opt(chi))
+    out = dict(selected=selected[:m], degree=degree[:m],
+               info=dict(consistent_pairs=int(info.consistent_pairs), bad_pivots=int(info.bad_pivots),
+                         clique_size=int(info.clique_size), winning_seed=int(info.winning_seed),
+                         seeds_run=int(info.seeds_run)))
+    if want_adjacency:
+        out["adjacency"] = adj[:m]
+    if want_chi2:
+        out["chi2"] = chi[:m, :m]
+    return rc, out
+
+
+def host_loop_consistency(local_poses, scan_poses, edges, gate, drift_var_per_metre=None, local_travel=None,
+                          scan_travel=None, n_seeds=0, want_adjacency=False, want_chi2=False):
+    """csm_host_loop_consistency: the sequential restatement of Context.loop_consistency, same arguments and
+    result."""
+    rc, out = _loop_consistency_run(L.load().csm_host_loop_consistency, (), local_poses, scan_poses, edges, gate,
+                                    drift_var_per_metre, local_travel, scan_travel, n_seeds, want_adjacency,
+                                    want_chi2)
+    if rc:
+        raise CsmError(rc, "csm_host_loop_consistency")
+    return out
+
+
+def loop_edges_from_matches(matches):
+    """Edge dicts (pose_graph_edges) from detector output. matches: dicts with local (local map node index),
+    scan (scan node index), pose (the estimated map-local scan pose = the measured InverseCompound(x_s, x_t))
+    and covariance (3 x 3, the match's pose covariance). The information matrix is the covariance's exactly
+    symmetric inverse (host_information_from_covariance); every edge is a loop edge."""
+    return [dict(local=int(m["local"]), scan=int(m["scan"]), rel=[float(v) for v in m["pose"]],
+                 info=host_information_from_covariance(m["covariance"]), loop=True) for m in matches]
+
+
 # csm_loop_candidate as a numpy record: 24 bytes, the struct's layout
 LOOP_CANDIDATE_DTYPE = np.dtype([("query_scan_index", np.int32), ("ref_scan_index", np.int32),
                                  ("ref_map_index", np.int32), ("reserved", np.int32), ("dist_sq", np.float64)])
@@ -1680,6 +1733,22 @@ class Context:
                                                  travel_dist_threshold, node_dist_threshold, n_per_query, one_per_map)
         self._check(rc)
         return out, counts, info
+
+    def loop_consistency(self, local_poses, scan_poses, edges, gate, drift_var_per_metre=None, local_travel=None,
+                         scan_travel=None, n_seeds=0, want_adjacency=False, want_chi2=False):
+        """csm_loop_consistency: which loop edges agree with each other, on the device. local_poses [n, 3],
+        scan_poses [m, 3]: the current estimates; edges: as pose_graph_lm takes them (is_loop is not read); gate:
+        the chi-square bound of a pair's cycle; the drift model (all three or none): drift_var_per_metre (3),
+        local_travel [n], scan_travel [m]; n_seeds: greedy searches from the vertices of highest degree (0: all).
+        Returns a dict: selected int32 [M] (the largest consistent set found), degree int32 [M], info
+        (consistent_pairs, bad_pivots, clique_size, winning_seed, seeds_run), and on request adjacency uint64
+        [M, ceil(M / 64)] and chi2 float64 [M, M] (M <= LOOP_CONSISTENCY_MAX_CHI2_EDGES). Every byte equals
+        host_loop_consistency's."""
+        rc, out = _loop_consistency_run(self.lib.csm_loop_consistency, (self._ctx,), local_poses, scan_poses, edges,
+                                        gate, drift_var_per_metre, local_travel, scan_travel, n_seeds,
+                                        want_adjacency, want_chi2)
+        self._check(rc)
+        return out
 
     def scan_descriptors(self, angles, ranges, offsets, n_rings=20, n_sectors=64, range_min=0.5, range_max=20.0):
         """csm_scan_descriptors: the polar descriptors of ragged scans on the device; arguments and result as

@@ -256,6 +256,10 @@ struct csm_ctx {
      * behind it, the pair table of one chunk of queries; pinned staging, up and then back */
     DevBuf ap_dev, ap_table;
     PinBuf ap_pin;
+    /* loop-edge consistency (csm_consistency_api.hip): a call's edge records, adjacency, per-seed cliques and
+     * results; pinned staging, up and then back */
+    DevBuf lc_dev;
+    PinBuf lc_pin;
     /* pose-graph optimization (csm_posegraph_api.hip): graph, structure, work vectors; host staging */
     DevBuf pg_buf;
     DevBuf pg_s;                  /* the dense Schur complement of the direct solver (blocked path) */

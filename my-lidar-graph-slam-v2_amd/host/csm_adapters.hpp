@@ -1687,6 +1687,131 @@ private:
     csm_pose_graph_lm_info mLast {};
 };
 
+/* The drift model of LoopConsistencyHIP: variances per metre travelled and the accumulated travel distance at
+ * every node (a local map takes the value of its first scan node). */
+struct LoopDriftModel {
+    std::array<double, 3> mVariancePerMetre;
+    std::vector<double> mLocalMapTravel;
+    std::vector<double> mScanTravel;
+};
+
+/* Do the loop edges agree with each other (csm_loop_consistency)? Sits in RunStep between Detect and
+ * AppendLoopClosingEdges: Check() tests every pair of candidate edges at the graph's current poses and finds the
+ * largest set that is pairwise consistent; SelectConsistent() keeps that subset of the detector's results. Nodes
+ * and edges are taken as PoseGraphOptimizerLMHIP takes them. The library has no such class in the reference. */
+class LoopConsistencyHIP final {
+public:
+    /* gate: the chi-square bound of a pair's cycle (11.34 = 99 % of three degrees of freedom); numOfSeeds: greedy
+     * searches from the vertices of highest degree, 0 = from every vertex */
+    static std::unique_ptr<LoopConsistencyHIP> Create(double gate, int numOfSeeds = 0, int deviceId = 0)
+    {
+        if (!(gate >= 0.0) || numOfSeeds < 0)
+            return nullptr;
+        detail::CtxPtr ctx = detail::MakeContext(deviceId);
+        if (!ctx)
+            return nullptr;
+        return std::unique_ptr<LoopConsistencyHIP>(
+            new LoopConsistencyHIP(gate, numOfSeeds, detail::ContextRef(std::move(ctx))));
+    }
+    /* on a context another adapter owns and keeps alive */
+    LoopConsistencyHIP(csm_ctx* shared, double gate, int numOfSeeds = 0) :
+        LoopConsistencyHIP(gate, numOfSeeds, detail::ContextRef(shared)) { }
+
+    LoopConsistencyHIP(const LoopConsistencyHIP&) = delete;
+    LoopConsistencyHIP& operator=(const LoopConsistencyHIP&) = delete;
+
+    csm_ctx* Context() const { return this->mCtx.Get(); }
+    /* the records of the last Check: one flag and one degree per edge, and the totals */
+    const std::vector<std::int32_t>& Selected() const { return this->mSelected; }
+    const std::vector<std::int32_t>& Degree() const { return this->mDegree; }
+    const csm_loop_consistency_info& LastInfo() const { return this->mLastInfo; }
+
+    void Check(const std::vector<std::array<double, 3>>& localMapNodes,
+               const std::vector<std::array<double, 3>>& scanNodes, const std::vector<EdgePose>& loopEdges,
+               const LoopDriftModel* drift = nullptr)
+    {
+        std::vector<csm_pose_graph_edge> edges(loopEdges.size());
+        for (std::size_t i = 0; i < loopEdges.size(); ++i) {
+            const EdgePose& e = loopEdges[i];
+            csm_pose_graph_edge& d = edges[i];
+            d = csm_pose_graph_edge {};
+            d.local_map_index = e.mLocalMapNodeIdx;
+            d.scan_index = e.mScanNodeIdx;
+            d.is_loop = e.mIsLoopConstraint ? 1 : 0;
+            std::copy(e.mRelativePose.begin(), e.mRelativePose.end(), d.relative_pose);
+            std::copy(e.mInformationMat.begin(), e.mInformationMat.end(), d.information);
+        }
+        this->Run(localMapNodes, scanNodes, edges, drift);
+    }
+
+    /* the same on a detector's results: z = the estimated map-local pose, Lambda = the inverse of the estimated
+     * covariance (csm_host_information_from_covariance), the local map node and scan node by their ids */
+    void Check(const std::vector<std::array<double, 3>>& localMapNodes,
+               const std::vector<std::array<double, 3>>& scanNodes, const LoopDetectionResultVector& results,
+               const LoopDriftModel* drift = nullptr)
+    {
+        std::vector<csm_pose_graph_edge> edges(results.size());
+        for (std::size_t i = 0; i < results.size(); ++i) {
+            const LoopDetectionResult& r = results[i];
+            csm_pose_graph_edge& d = edges[i];
+            d = csm_pose_graph_edge {};
+            d.local_map_index = static_cast<std::int32_t>(r.mLocalMapNodeId);
+            d.scan_index = r.mScanNodeId;
+            d.is_loop = 1;
+            d.relative_pose[0] = r.mRelativePose.mX;
+            d.relative_pose[1] = r.mRelativePose.mY;
+            d.relative_pose[2] = r.mRelativePose.mTheta;
+            CSM_ASSERT_OK(this->Context(), csm_host_information_from_covariance(r.mEstimatedCovariance, d.information));
+        }
+        this->Run(localMapNodes, scanNodes, edges, drift);
+    }
+
+    /* the results the last Check selected, in their original order; `results` is what that Check was given */
+    LoopDetectionResultVector SelectConsistent(const LoopDetectionResultVector& results) const
+    {
+        CSM_ASSERT_THAT(results.size() == this->mSelected.size(), "%zu results, but the last Check saw %zu edges",
+                        results.size(), this->mSelected.size());
+        LoopDetectionResultVector kept;
+        for (std::size_t i = 0; i < results.size(); ++i)
+            if (this->mSelected[i])
+                kept.push_back(results[i]);
+        return kept;
+    }
+
+private:
+    LoopConsistencyHIP(double gate, int numOfSeeds, detail::ContextRef ctx) :
+        mGate(gate), mNumOfSeeds(numOfSeeds), mCtx(std::move(ctx)) { }
+
+    void Run(const std::vector<std::array<double, 3>>& localMapNodes,
+             const std::vector<std::array<double, 3>>& scanNodes, const std::vector<csm_pose_graph_edge>& edges,
+             const LoopDriftModel* drift)
+    {
+        static_assert(sizeof(std::array<double, 3>) == 3 * sizeof(double), "pose layout");
+        if (drift)
+            CSM_ASSERT_THAT(drift->mLocalMapTravel.size() == localMapNodes.size() &&
+                            drift->mScanTravel.size() == scanNodes.size(), "%s", "one travel distance per node");
+        this->mSelected.assign(edges.size(), 0);
+        this->mDegree.assign(edges.size(), 0);
+        CSM_ASSERT_OK(this->Context(),
+                      csm_loop_consistency(this->Context(), localMapNodes.empty() ? nullptr : localMapNodes.front().data(),
+                                           static_cast<std::int32_t>(localMapNodes.size()),
+                                           scanNodes.empty() ? nullptr : scanNodes.front().data(),
+                                           static_cast<std::int32_t>(scanNodes.size()), edges.data(),
+                                           static_cast<std::int32_t>(edges.size()), this->mGate,
+                                           drift ? drift->mVariancePerMetre.data() : nullptr,
+                                           drift ? drift->mLocalMapTravel.data() : nullptr,
+                                           drift ? drift->mScanTravel.data() : nullptr, this->mNumOfSeeds,
+                                           this->mSelected.data(), this->mDegree.data(), &this->mLastInfo, nullptr,
+                                           nullptr));
+    }
+
+    const double mGate;
+    const int mNumOfSeeds;
+    detail::ContextRef mCtx;
+    std::vector<std::int32_t> mSelected, mDegree;
+    csm_loop_consistency_info mLastInfo {};
+};
+
 /* ScoreFunction::Summary (inc/mapping/score_function.hpp:29-45) plus the integers it came from */
 struct ScoreSummary {
     double mNormalizedScore = 0.0;
