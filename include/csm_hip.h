@@ -647,6 +647,80 @@ int  csm_build_likelihood_map(csm_ctx* ctx, uint64_t src_map_id, uint64_t dst_ma
 int  csm_build_likelihood_maps(csm_ctx* ctx, const uint64_t* src_ids, const uint64_t* dst_ids, int32_t n,
                                const csm_likelihood_params* params);
 
+/* ---- distance fields (beyond the reference): every cell's squared distance to its NEAREST obstacle, exact
+ * over the whole map, and a second resident map read off it through a caller's table. Where the likelihood
+ * field above visits every obstacle within R of a cell (so R <= 16), a distance transform costs the same at
+ * any radius: a field that decays over metres for global searches, the distance sensor model (the probability
+ * of a beam as a function of the distance from its end point to the nearest obstacle), clearance masks,
+ * chamfer scores, nearest-obstacle correspondences. The field is an ordinary uint16 grid under an id of its
+ * own, as the likelihood field is.
+ *
+ * Definition (integers only). Source grid G, rows x cols (pad columns are not cells), both at most 32767;
+ * threshold occupied_min >= 1. A cell o is an obstacle iff it lies inside the map and G[o] >= occupied_min.
+ *   d2(c)      = min over obstacles o of (o.r - c.r)^2 + (o.c - c.c)^2      (uint32)
+ *                CSM_DISTANCE_NONE if the map has no obstacle
+ *   nearest(c) = o.r * cols + o.c of the obstacle that attains d2(c); among several the smallest such index
+ *                (smallest row, then smallest column); CSM_DISTANCE_NONE if there is none
+ *   out(c)     = 0                        if keep_unknown and G[c] == 0
+ *                T[min(d2(c), R^2)]       otherwise
+ * T[0 .. R^2]: the caller's table of uint16, each <= 65534, R in 1..CSM_DISTANCE_MAX_RADIUS. T[R^2] is what
+ * every cell farther than R from all obstacles gets: 0 leaves them unknown, a positive floor makes the whole
+ * map known. d2 and nearest are NOT capped by R. Squared distances are integers and a minimum does not depend
+ * on the order it is taken in, so device, host function and definition agree in every bit. A ramp, a
+ * truncated quadratic (1 + min(d2, cap), whose sum over a scan's end points is the chamfer score) or a hard
+ * clearance mask are tables like any other.
+ *
+ * The usual table (csm_host_distance_kernel; host, f64, libm exp, one fixed expression; the device never
+ * evaluates exp):
+ *   T[d2] = floor_value + (uint16) floor((peak - floor_value) * exp(-(d2 * (res * res)) / (2 * (sigma * sigma))) + 0.5) */
+#define CSM_DISTANCE_MAX_RADIUS 255
+#define CSM_DISTANCE_NONE       0xFFFFFFFFu
+/* device scratch of one launch chain of csm_build_distance_maps (2 bytes per cell): a batch beyond it is cut
+ * into chunks of maps, a single map beyond it runs alone (the convention of csm_host_map_batch_plan) */
+#define CSM_DISTANCE_SCRATCH_LIMIT (1ll << 30)
+typedef struct {
+    int32_t         radius;         /* R, cells: 1..CSM_DISTANCE_MAX_RADIUS */
+    uint32_t        occupied_min;   /* >= 1; 32768: P(occupied) above one half */
+    int32_t         keep_unknown;   /* 0: every cell gets its table entry; else unknown cells of the source stay 0 */
+    int32_t         reserved;
+    const uint16_t* table;          /* T: radius^2 + 1 entries, each <= 65534 */
+} csm_distance_params;
+
+/* Host only. table[radius^2 + 1] as defined above; CSM_EINVAL for a radius out of range, a sigma or resolution
+ * that is not finite and > 0, or unless floor_value <= peak <= 65534. */
+int  csm_host_distance_kernel(double sigma, double resolution, int32_t radius, uint32_t peak,
+                              uint32_t floor_value, uint16_t* table);
+/* Host only: d2 and nearest of a dense rows x cols grid, row-major; either output may be null. A plain
+ * sequential restatement of the device's two passes (column offsets, then per cell a walk over the columns
+ * that hold an obstacle). CSM_EINVAL: rows or cols < 1 or > 32767, occupied_min = 0, both outputs null. */
+int  csm_host_distance_transform(const uint16_t* grid, int32_t rows, int32_t cols, uint32_t occupied_min,
+                                 uint32_t* d2, uint32_t* nearest);
+/* Host only: out(c) of the definition. grid / out: dense rows x cols, distinct buffers. CSM_EINVAL: what
+ * csm_host_distance_transform refuses, a radius out of range, no table, a table entry above 65534. */
+int  csm_host_distance_map(const uint16_t* grid, int32_t rows, int32_t cols,
+                           const csm_distance_params* params, uint16_t* out);
+/* d2 and nearest of the resident map map_id, computed on the device and copied to the host buffers (dense
+ * rows x cols each; either may be null, not both). The map, its levels and its derived copies are not
+ * touched. Runs on the ctx stream and returns when the outputs are written. CSM_EINVAL: occupied_min = 0,
+ * both outputs null, a map with more than 32767 rows or columns. CSM_ENOENT: the map is not resident. */
+int  csm_distance_transform(csm_ctx* ctx, uint64_t map_id, uint32_t occupied_min, uint32_t* d2,
+                            uint32_t* nearest);
+/* The field of the resident map src_map_id, built on the device into dst_map_id. Afterwards dst is in
+ * exactly the state csm_upload_grid(dst, csm_host_distance_map(cells of src)) leaves it in, on the terms of
+ * csm_build_likelihood_map: shape of the source, first known row / column counted on the device, no levels
+ * above the base, derived copies stale, block allocation derived from the cells, base_epoch bumped when the
+ * id existed. src is not touched and no cell travels to the host. Returns when the field is built.
+ * CSM_EINVAL: dst == src, the params csm_host_distance_map refuses, a source with more than 32767 rows or
+ * columns. CSM_ENOENT: src is not resident. A call that is refused or fails leaves an existing dst as it was
+ * and registers nothing. */
+int  csm_build_distance_map(csm_ctx* ctx, uint64_t src_map_id, uint64_t dst_map_id,
+                            const csm_distance_params* params);
+/* The same for n maps (src_ids[i] -> dst_ids[i]) of any shapes on one launch chain (two kernels; chunks of
+ * maps beyond CSM_DISTANCE_SCRATCH_LIMIT). A source may feed several fields. CSM_EINVAL also when a dst
+ * appears twice or is one of the sources; nothing is built then. */
+int  csm_build_distance_maps(csm_ctx* ctx, const uint64_t* src_ids, const uint64_t* dst_ids, int32_t n,
+                             const csm_distance_params* params);
+
 /* ---- free-space check of loop candidates (beyond the reference, whose detectors accept a pose on the
  * score of the scan's END POINTS alone): every beam of a scan walked from the sensor to its hit, as the map
  * builder would walk it if it integrated the scan at this pose, and the cells it crosses classified against
@@ -1866,7 +1940,7 @@ int  csm_enable_kernel_timing(csm_ctx* ctx, int32_t enable);
 /* Drains recorded events; returns total ms and launch count since the last
  * reset for kernel "score_fine" | "score_coarse" | "bin" | "finalize" | "boxmax" |
  * "peaks_coarse" | "peaks_select" | "volume_moments" | "volume_reduce" | "prior_select" | "likelihood" |
- * "ray_project" | "ray_walk" | "pose_prep" | "pose_score" | "pose_rescore" | "pose_weights" |
+ * "distance_columns" | "distance_rows" | "ray_project" | "ray_walk" | "pose_prep" | "pose_score" | "pose_rescore" | "pose_weights" |
  * "pose_resample" | "pose_graph" | "pose_graph_marginals" |
  * "pose_graph_marginals_factor" | "pose_graph_marginals_solve" | "loop_search" | "scan_descriptors" |
  * "appearance_search" | "loop_consistency" | "loop_consistency_pairs" | "loop_consistency_select". */
@@ -1882,7 +1956,7 @@ const char* csm_version(void);
 int  csm_debug_live_bytes(int64_t* device, int64_t* pinned);
 /* Test hook: the first row and the first column of a resident map that hold a non-zero cell, as the library
  * keeps them on the host (rows, cols for a map with none): what csm_upload_grid counts, the block upload, the
- * map builder and csm_build_likelihood_map(s) reduce on the device, and the edge-band test of every search
+ * map builder, csm_build_likelihood_map(s) and csm_build_distance_map(s) reduce on the device, and the edge-band test of every search
  * reads. out = { row, column }. CSM_ENOENT: the map is not resident. Reads host state only: no
  * synchronisation, no change to any grid. */
 int  csm_debug_grid_known(csm_ctx* ctx, uint64_t map_id, int32_t out[2]);

@@ -280,6 +280,14 @@ class LikelihoodParams(C.Structure):
                 ("reserved", C.c_int32), ("kernel", C.c_void_p)]
 
 
+DISTANCE_MAX_RADIUS, DISTANCE_NONE = 255, 0xFFFFFFFF
+
+
+class DistanceParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("occupied_min", C.c_uint32), ("keep_unknown", C.c_int32),
+                ("reserved", C.c_int32), ("table", C.c_void_p)]
+
+
 RAY_CHECK_MAX_SCALE = 512
 
 
@@ -466,6 +474,12 @@ SIGNATURES = {
     "csm_host_likelihood_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(LikelihoodParams), C.c_void_p]),
     "csm_build_likelihood_map": (C.c_int, [_ctx, C.c_uint64, C.c_uint64, _P(LikelihoodParams)]),
     "csm_build_likelihood_maps": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, _P(LikelihoodParams)]),
+    "csm_host_distance_kernel": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "csm_host_distance_transform": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "csm_host_distance_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(DistanceParams), C.c_void_p]),
+    "csm_distance_transform": (C.c_int, [_ctx, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "csm_build_distance_map": (C.c_int, [_ctx, C.c_uint64, C.c_uint64, _P(DistanceParams)]),
+    "csm_build_distance_maps": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, _P(DistanceParams)]),
     "csm_host_ray_check_values": (C.c_int, [C.c_double, C.c_double, _P(C.c_uint32), _P(C.c_uint32)]),
     "csm_host_ray_check": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(Geometry), _P(Scan), C.c_void_p,
                                      _P(RayCheckParams), _P(RayCheckResult), C.c_void_p]),

@@ -9,6 +9,7 @@ All arithmetic happens in libcsm_hip.so; this file only marshals numpy arrays.
 """
 import contextlib
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -427,6 +428,65 @@ def host_likelihood_map(grid, sigma=None, resolution=None, radius=None, occupied
     rc = L.load().csm_host_likelihood_map(_ptr(g), g.shape[0], g.shape[1], C.byref(p), _ptr(out))
     if rc != 0:
         raise CsmError(rc, "csm_host_likelihood_map")
+    return out
+
+
+def host_distance_kernel(sigma, resolution, radius, peak=65534, floor_value=1):
+    """T[0 .. radius^2] as uint16: floor_value + the integer Gaussian of height peak - floor_value, indexed by
+    the squared cell distance (csm_host_distance_kernel)."""
+    if not 1 <= radius <= L.DISTANCE_MAX_RADIUS:
+        raise CsmError(L.CSM_EINVAL, "host_distance_kernel: radius out of range")
+    table = np.zeros(radius * radius + 1, np.uint16)
+    rc = L.load().csm_host_distance_kernel(sigma, resolution, radius, peak, floor_value, _ptr(table))
+    if rc != 0:
+        raise CsmError(rc, "csm_host_distance_kernel")
+    return table
+
+
+def distance_params(sigma=None, resolution=None, radius=None, occupied_min=32768, keep_unknown=False, table=None,
+                    peak=65534, floor_value=1):
+    """(csm_distance_params, the table it points at): the table is `table` if given (radius required), else
+    that of (sigma, resolution, peak, floor_value) at `radius` (default: ceil(3 sigma / resolution) clamped to
+    1..DISTANCE_MAX_RADIUS). Keep the table alive with the struct."""
+    if table is None:
+        if radius is None:
+            if not (sigma is not None and resolution is not None and sigma > 0 and resolution > 0):
+                raise CsmError(L.CSM_EINVAL, "distance_params: sigma and resolution > 0, or a table")
+            radius = int(min(float(L.DISTANCE_MAX_RADIUS), max(1.0, math.ceil(3.0 * (sigma / resolution)))))
+        table = host_distance_kernel(sigma, resolution, radius, peak, floor_value)
+    elif radius is None:
+        raise CsmError(L.CSM_EINVAL, "distance_params: a table needs its radius")
+    t = np.asarray(table)
+    if t.size and (t.min() < 0 or t.max() > 65535):
+        raise CsmError(L.CSM_EINVAL, "distance_params: table entries are uint16")
+    t = np.ascontiguousarray(t, dtype=np.uint16)
+    if 1 <= radius <= L.DISTANCE_MAX_RADIUS and t.size < radius * radius + 1:
+        raise CsmError(L.CSM_EINVAL, "distance_params: the table needs radius^2 + 1 entries")
+    p = L.DistanceParams(radius, occupied_min, 1 if keep_unknown else 0, 0, t.ctypes.data)
+    return p, t
+
+
+def host_distance_transform(grid, occupied_min=32768):
+    """(d2, nearest) of a dense uint16 grid on the host, uint32 each (csm_host_distance_transform):
+    DISTANCE_NONE everywhere when the grid has no obstacle."""
+    g = np.ascontiguousarray(grid, dtype=np.uint16)
+    d2, nearest = np.zeros(g.shape, np.uint32), np.zeros(g.shape, np.uint32)
+    rc = L.load().csm_host_distance_transform(_ptr(g), g.shape[0], g.shape[1], occupied_min, _ptr(d2), _ptr(nearest))
+    if rc != 0:
+        raise CsmError(rc, "csm_host_distance_transform")
+    return d2, nearest
+
+
+def host_distance_map(grid, sigma=None, resolution=None, radius=None, occupied_min=32768, keep_unknown=False,
+                      table=None, peak=65534, floor_value=1):
+    """The distance field of a dense uint16 grid on the host (csm_host_distance_map): what the device build
+    is compared with."""
+    g = np.ascontiguousarray(grid, dtype=np.uint16)
+    p, t = distance_params(sigma, resolution, radius, occupied_min, keep_unknown, table, peak, floor_value)
+    out = np.zeros_like(g)
+    rc = L.load().csm_host_distance_map(_ptr(g), g.shape[0], g.shape[1], C.byref(p), _ptr(out))
+    if rc != 0:
+        raise CsmError(rc, "csm_host_distance_map")
     return out
 
 
@@ -1089,6 +1149,40 @@ class Context:
             raise CsmError(L.CSM_EINVAL, "build_likelihood_maps: as many destinations as sources")
         p, table = likelihood_params(sigma, resolution, radius, occupied_min, keep_unknown, kernel)
         self._check(self.lib.csm_build_likelihood_maps(self._ctx, _ptr(s), _ptr(d), s.size, C.byref(p)))
+        for a, b in zip(srcs, dsts):
+            self.shapes[b] = self.shapes[a]
+
+    def distance_transform(self, map_id, occupied_min=32768, want_d2=True, want_nearest=True):
+        """csm_distance_transform: (d2, nearest) of the resident map, uint32 [rows, cols] each, computed on
+        the device; an output that is not wanted is None."""
+        if map_id in self.shapes or self.has_grid(map_id):
+            rows, cols = self.shapes[map_id]        # resident but of unknown shape: KeyError, as download_level
+        else:
+            rows, cols = 1, 1                       # not resident: nothing is written, the call says CSM_ENOENT
+        d2 = np.zeros((rows, cols), np.uint32) if want_d2 else None
+        nearest = np.zeros((rows, cols), np.uint32) if want_nearest else None
+        self._check(self.lib.csm_distance_transform(self._ctx, map_id, occupied_min,
+                                                    _ptr(d2) if want_d2 else None,
+                                                    _ptr(nearest) if want_nearest else None))
+        return d2, nearest
+
+    def build_distance_map(self, src, dst, sigma=None, resolution=None, radius=None, occupied_min=32768,
+                           keep_unknown=False, table=None, peak=65534, floor_value=1):
+        """csm_build_distance_map: the distance field of the resident map `src` built on the device under
+        `dst` (an ordinary map id from then on). Table as in distance_params()."""
+        p, t = distance_params(sigma, resolution, radius, occupied_min, keep_unknown, table, peak, floor_value)
+        self._check(self.lib.csm_build_distance_map(self._ctx, src, dst, C.byref(p)))
+        self.shapes[dst] = self.shapes[src]
+
+    def build_distance_maps(self, srcs, dsts, sigma=None, resolution=None, radius=None, occupied_min=32768,
+                            keep_unknown=False, table=None, peak=65534, floor_value=1):
+        """csm_build_distance_maps: srcs[i] -> dsts[i], all on one launch chain."""
+        s = np.ascontiguousarray(srcs, dtype=np.uint64)
+        d = np.ascontiguousarray(dsts, dtype=np.uint64)
+        if s.size != d.size:
+            raise CsmError(L.CSM_EINVAL, "build_distance_maps: as many destinations as sources")
+        p, t = distance_params(sigma, resolution, radius, occupied_min, keep_unknown, table, peak, floor_value)
+        self._check(self.lib.csm_build_distance_maps(self._ctx, _ptr(s), _ptr(d), s.size, C.byref(p)))
         for a, b in zip(srcs, dsts):
             self.shapes[b] = self.shapes[a]
 
@@ -1877,14 +1971,16 @@ class Group:
 
 
 @contextlib.contextmanager
-def _query_map(ctx, nonce, map_id, grid, likelihood_sigma=None, resolution=None):
+def _query_map(ctx, nonce, map_id, grid, likelihood_sigma=None, resolution=None, distance_sigma=None,
+               distance_radius=None):
     """The residency rule of the three matchers below, for one optimize_pose call: the map lies under
     map_id, or under the matcher's nonce id when it is a throw-away map (map_id None, like
     LocalMapId::Invalid in scan_matcher_correlative_fpga.cpp:177-184); grid is uploaded when the map is
     throw-away or not resident (grid None: it is resident already, the per-LocalMapId cache of the loop
     detectors). With a likelihood_sigma the map's field lies under its id | LIKELIHOOD_ID_BIT: the field
-    follows the map, built when the map was uploaded just now or has no field yet. Yields (map id, id
-    to search on); a throw-away map and its field are released when the call ends."""
+    follows the map, built when the map was uploaded just now or has no field yet. With a distance_sigma
+    it is the distance field instead (Context.build_distance_map), under ScanMatcherCorrelativeHIP.field_id.
+    Yields (map id, id to search on); a throw-away map and its field are released when the call ends."""
     mid = nonce if map_id is None else map_id
     uploaded = grid is not None and (map_id is None or not ctx.has_grid(mid))
     if uploaded:
@@ -1894,6 +1990,10 @@ def _query_map(ctx, nonce, map_id, grid, likelihood_sigma=None, resolution=None)
         search_id = mid | ScanMatcherCorrelativeHIP.LIKELIHOOD_ID_BIT
         if uploaded or not ctx.has_grid(search_id):
             ctx.build_likelihood_map(mid, search_id, likelihood_sigma, resolution)
+    elif distance_sigma is not None:
+        search_id = ScanMatcherCorrelativeHIP.field_id(mid, ScanMatcherCorrelativeHIP.DISTANCE_ID_BIT)
+        if uploaded or not ctx.has_grid(search_id):
+            ctx.build_distance_map(mid, search_id, distance_sigma, resolution, distance_radius)
     yield mid, search_id
     if map_id is None:
         ctx.release_grid(mid)
@@ -1908,9 +2008,18 @@ class ScanMatcherCorrelativeHIP:
     # the likelihood field of map id m lives under m | LIKELIHOOD_ID_BIT (callers' ids are below 2^62, the
     # adapters' own throw-away ids start there: bit 63 is free in both)
     LIKELIHOOD_ID_BIT = 1 << 63
+    # ... and its distance field under m | DISTANCE_ID_BIT, for a caller's id m (below 2^62)
+    DISTANCE_ID_BIT = 1 << 62
+
+    @classmethod
+    def field_id(cls, map_id, bit):
+        """Where the field of map_id lies. A caller's id: map_id | bit. The adapters' own throw-away ids
+        carry bit 62 already, so a throw-away map's field, of either kind, lies under bit 63: a matcher
+        has one kind of field, and the field goes with the map when the call ends."""
+        return map_id | (cls.LIKELIHOOD_ID_BIT if map_id & bit else bit)
 
     def __init__(self, name, low_resolution, range_x, range_y, range_theta, ctx=None, prior_information=None,
-                 likelihood_sigma=None, covariance_scale=1e4):
+                 likelihood_sigma=None, covariance_scale=1e4, distance_sigma=None, distance_radius=None):
         """prior_information: a 3 x 3 information matrix of the sensor pose's offset from the initial pose
         (beyond the reference); optimize_pose then goes through csm_correlative_match_prior.
         likelihood_sigma: the sensor noise in metres (beyond the reference); optimize_pose then searches on
@@ -1918,7 +2027,14 @@ class ScanMatcherCorrelativeHIP:
         keep_unknown, under map id | LIKELIHOOD_ID_BIT) and adds, from the ORIGINAL occupancy map -- cost,
         covariance and refinement are bilinear in occupancy and must not see the spread values --
         out["cost"] (cost_covariance_batch at the best sensor pose) and out["refined"] (linear_solver_batch
-        from the estimated pose), both with covariance_scale."""
+        from the estimated pose), both with covariance_scale.
+        distance_sigma (metres), distance_radius (cells; default ceil(3 sigma / resolution), at most
+        DISTANCE_MAX_RADIUS): the same on the map's distance field (Context.build_distance_map at the default
+        peak, floor, occupied_min and keep_unknown, under field_id(map id, DISTANCE_ID_BIT)), whose radius is
+        not limited to 16 cells. Giving both sigmas is CSM_EINVAL."""
+        if likelihood_sigma is not None and distance_sigma is not None:
+            raise CsmError(L.CSM_EINVAL, "ScanMatcherCorrelativeHIP: likelihood_sigma or distance_sigma, not both")
+        self.distance_sigma, self.distance_radius = distance_sigma, distance_radius
         self.name = name
         self.low_resolution = low_resolution
         self.range_x, self.range_y, self.range_theta = range_x, range_y, range_theta
@@ -1933,7 +2049,8 @@ class ScanMatcherCorrelativeHIP:
         """grid may be None when map_id is already resident (the per-LocalMapId
         cache of the loop detectors); a throw-away latest map gets a nonce id,
         like LocalMapId::Invalid in scan_matcher_correlative_fpga.cpp:177-184."""
-        with _query_map(self.ctx, self._nonce, map_id, grid, self.likelihood_sigma, geom[0]) as (mid, search_id):
+        with _query_map(self.ctx, self._nonce, map_id, grid, self.likelihood_sigma, geom[0], self.distance_sigma,
+                        self.distance_radius) as (mid, search_id):
             if self.prior_information is not None:
                 # the summary of the winner under the prior, with the unweighted winner and the penalty beside it
                 both = self.ctx.correlative_match_prior(search_id, geom, angles, ranges, rel_pose, init_pose,
@@ -1946,7 +2063,7 @@ class ScanMatcherCorrelativeHIP:
                                                  self.range_x, self.range_y, self.range_theta,
                                                  self.low_resolution, score_threshold,
                                                  known_rate_threshold)
-            if self.likelihood_sigma is not None:
+            if search_id != mid:
                 q = dict(map_id=mid, geom=geom, angles=angles, ranges=ranges, rel_pose=rel_pose,
                          init_pose=out["estimated_pose"])
                 out["cost"] = self.ctx.cost_covariance_batch([q], [out["best_sensor_pose"]], self.covariance_scale)[0]

@@ -48,6 +48,55 @@ DeviceGrid take_grid(csm_ctx* ctx, uint64_t map_id)
     return g;
 }
 
+int field_ids_ok(csm_ctx* ctx, const char* what, const uint64_t* src_ids, const uint64_t* dst_ids, int n)
+{
+    for (int i = 0; i < n; ++i) {
+        const DeviceGrid* s = find_grid(ctx, src_ids[i]);
+        if (!s || s->levels.empty())
+            return fail(ctx, CSM_ENOENT, "map %llu not resident", (unsigned long long)src_ids[i]);
+    }
+    std::vector<uint64_t> dsts(dst_ids, dst_ids + n);
+    std::sort(dsts.begin(), dsts.end());
+    if (std::adjacent_find(dsts.begin(), dsts.end()) != dsts.end())
+        return fail(ctx, CSM_EINVAL, "%s: a destination map appears twice", what);
+    for (int i = 0; i < n; ++i)
+        if (std::binary_search(dsts.begin(), dsts.end(), src_ids[i]))
+            return fail(ctx, CSM_EINVAL, "%s: map %llu is both a source and a destination", what,
+                        (unsigned long long)src_ids[i]);
+    return CSM_OK;
+}
+
+int alloc_field_bases(csm_ctx* ctx, const uint64_t* src_ids, int n, std::vector<Level>& bases)
+{
+    bases.clear();
+    bases.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const DeviceGrid& s = *find_grid(ctx, src_ids[i]);
+        const size_t bytes = (size_t)s.rows * s.pitch * 2;
+        if (int rc = grow(ctx, bases[i].own, bytes, bytes, false))
+            return rc;
+        bases[i].cells = bases[i].own.as<uint16_t>();
+    }
+    return CSM_OK;
+}
+
+void register_fields(csm_ctx* ctx, const uint64_t* src_ids, const uint64_t* dst_ids, int n, std::vector<Level>& bases,
+                     const int32_t* known)
+{
+    for (int i = 0; i < n; ++i) {
+        const DeviceGrid& s = *find_grid(ctx, src_ids[i]);
+        const int rows = s.rows, cols = s.cols, pitch = s.pitch;
+        DeviceGrid g = take_grid(ctx, dst_ids[i]);      /* an old field: memory released, copies dropped */
+        g.rows = rows;
+        g.cols = cols;
+        g.pitch = pitch;
+        g.known_r0 = known[2 * i];
+        g.known_c0 = known[2 * i + 1];
+        g.levels.push_back(std::move(bases[i]));
+        ctx->grids[dst_ids[i]] = std::move(g);
+    }
+}
+
 } /* namespace csm_host */
 
 /* ------------------------------------------------------------------ C ABI */

@@ -240,6 +240,10 @@ struct csm_ctx {
     /* likelihood-field maps (csm_likelihood_api.hip): table, job per map, counters; pinned staging */
     DevBuf lf_tab;
     PinBuf lf_pin;
+    /* distance fields (csm_distance_api.hip): table, job per map, counters; the column pass's offsets of a
+     * chunk of maps (and the transform's two outputs); pinned staging */
+    DevBuf dt_tab, dt_work;
+    PinBuf dt_pin;
     /* free-space check of loop candidates (csm_ray_api.hip): a chunk's table + scans, its work block
      * (uncertified list, records, per-beam words, ray records, patches); pinned staging up and back */
     DevBuf rc_tab, rc_work;
@@ -489,6 +493,18 @@ DeviceGrid take_grid(csm_ctx* ctx, uint64_t map_id);
 /* level 0's cells changed: drop the phase-major copies and bump base_epoch (the caller has
  * synchronised the stream that may still read them) */
 void base_changed(DeviceGrid& g);
+/* What the builders of fields from resident maps share (likelihood fields, distance fields): src_ids[i] ->
+ * dst_ids[i], every field with the rows, cols and pitch of its source.
+ * field_ids_ok: CSM_ENOENT for a source that is not resident, CSM_EINVAL for a destination that appears
+ * twice or is one of the sources (`what` names the field in the message).
+ * alloc_field_bases: the new base levels, owned by the caller until every one of them is built.
+ * register_fields: the caller has built bases[i] and synchronised the stream; known[2 i], known[2 i + 1] are
+ * the first known row / column of its cells. dst_ids[i] is left in the state csm_upload_grid of those cells
+ * leaves it in: an old map under the id has its memory released and its copies dropped, base_epoch bumped. */
+int field_ids_ok(csm_ctx* ctx, const char* what, const uint64_t* src_ids, const uint64_t* dst_ids, int n);
+int alloc_field_bases(csm_ctx* ctx, const uint64_t* src_ids, int n, std::vector<Level>& bases);
+void register_fields(csm_ctx* ctx, const uint64_t* src_ids, const uint64_t* dst_ids, int n, std::vector<Level>& bases,
+                     const int32_t* known);
 
 /* defined in csm_cost_api.hip */
 /* g.alloc made current: a derived bitmap that is stale is rebuilt from the cells */

@@ -5,8 +5,9 @@
  *
  * A build call checks everything and allocates every new base level first, uploads one block ([table][one
  * job per map][two counters per map], from lf_pin into lf_tab), launches k_likelihood_batch over all maps,
- * reads the counters back and only then replaces the destination grids (take_grid): a call that is refused
- * or fails has changed nothing. */
+ * reads the counters back and only then replaces the destination grids (register_fields): a call that is
+ * refused or fails has changed nothing. The id checks, the new base levels and the registration are the
+ * field helpers of csm_internal.hpp, shared with csm_distance_api.hip. */
 #include "csm_internal.hpp"
 
 #include "csm_likelihood_kernels.hip"
@@ -92,32 +93,14 @@ int csm_build_likelihood_maps(csm_ctx* ctx, const uint64_t* src_ids, const uint6
         return fail(ctx, CSM_EINVAL,
                     "likelihood field: radius must be 1..%d, occupied_min >= 1 and every table entry <= 32768",
                     CSM_LIKELIHOOD_MAX_RADIUS);
-    for (int i = 0; i < n; ++i) {
-        const DeviceGrid* s = find_grid(ctx, src_ids[i]);
-        if (!s || s->levels.empty())
-            return fail(ctx, CSM_ENOENT, "map %llu not resident", (unsigned long long)src_ids[i]);
-    }
-    {
-        std::vector<uint64_t> dsts(dst_ids, dst_ids + n);
-        std::sort(dsts.begin(), dsts.end());
-        if (std::adjacent_find(dsts.begin(), dsts.end()) != dsts.end())
-            return fail(ctx, CSM_EINVAL, "likelihood field: a destination map appears twice");
-        for (int i = 0; i < n; ++i)
-            if (std::binary_search(dsts.begin(), dsts.end(), src_ids[i]))
-                return fail(ctx, CSM_EINVAL, "likelihood field: map %llu is both a source and a destination",
-                            (unsigned long long)src_ids[i]);
-    }
+    if (int rc = field_ids_ok(ctx, "likelihood field", src_ids, dst_ids, n))
+        return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     /* the new base levels, owned here until every one of them is built */
-    std::vector<Level> bases((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const DeviceGrid& s = *find_grid(ctx, src_ids[i]);
-        const size_t bytes = (size_t)s.rows * s.pitch * 2;
-        if (int rc = grow(ctx, bases[i].own, bytes, bytes, false))
-            return rc;
-        bases[i].cells = bases[i].own.as<uint16_t>();
-    }
+    std::vector<Level> bases;
+    if (int rc = alloc_field_bases(ctx, src_ids, n, bases))
+        return rc;
 
     /* [table][jobs][counters]: one upload */
     Carve c;
@@ -172,18 +155,7 @@ int csm_build_likelihood_maps(csm_ctx* ctx, const uint64_t* src_ids, const uint6
     /* also: nothing queued reads an old destination any more */
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 
-    for (int i = 0; i < n; ++i) {
-        const DeviceGrid& s = *find_grid(ctx, src_ids[i]);
-        const int rows = s.rows, cols = s.cols, pitch = s.pitch;
-        DeviceGrid g = take_grid(ctx, dst_ids[i]);      /* an old field: memory released, copies dropped */
-        g.rows = rows;
-        g.cols = cols;
-        g.pitch = pitch;
-        g.known_r0 = known_pin[2 * i];
-        g.known_c0 = known_pin[2 * i + 1];
-        g.levels.push_back(std::move(bases[i]));
-        ctx->grids[dst_ids[i]] = std::move(g);
-    }
+    register_fields(ctx, src_ids, dst_ids, n, bases, known_pin);
     return CSM_OK;
 }
 

@@ -92,6 +92,15 @@ struct GridMapView {
     /* the likelihood field of map id m lives under m | kLikelihoodIdBit (ScanMatcherCorrelativeHIP::
      * UseLikelihoodField): callers' ids and the adapters' throw-away ids both leave bit 63 clear */
     static constexpr std::uint64_t kLikelihoodIdBit = 1ull << 63;
+    /* ... and its distance field under m | kDistanceIdBit (UseDistanceField), for a caller's id m. The
+     * adapters' throw-away ids carry this bit already: FieldId */
+    static constexpr std::uint64_t kDistanceIdBit = 1ull << 62;
+    /* Where the field of map id `id` lies: id | bit; a throw-away map's field, of either kind, under bit 63
+     * (a matcher has one kind of field, and a throw-away map's field goes with it when the call ends). */
+    static constexpr std::uint64_t FieldId(std::uint64_t id, std::uint64_t bit)
+    {
+        return id | ((id & bit) ? kLikelihoodIdBit : bit);
+    }
     const std::uint16_t* mValues = nullptr;   /* row-major rows*cols */
     int mRows = 0, mCols = 0;
     double mResolution = 0.0;
@@ -448,7 +457,8 @@ public:
         const csm_loop_query& f = w.mQuery;
         /* the search runs on the likelihood field when one is asked for; cost, covariance and any
          * refinement below stay on the occupancy map f.map_id, which they are bilinear in */
-        const std::uint64_t searchId = this->mLikelihoodSigma > 0.0 ? this->MakeField(q.mGridMap, w.mMap) : f.map_id;
+        const std::uint64_t searchId =
+            this->mLikelihoodSigma > 0.0 || this->mDistanceSigma > 0.0 ? this->MakeField(q.mGridMap, w.mMap) : f.map_id;
         csm_summary s {};
         if (this->mUsePrior) {
             /* the winner under the motion prior; the unweighted one stays in LastPriorResult() */
@@ -553,9 +563,25 @@ public:
      * motion prior's summary poses come from the occupancy map as before. sigma <= 0 switches it off. */
     void UseLikelihoodField(double sigma, std::uint32_t occupiedMin = 32768, bool keepUnknown = false)
     {
+        CSM_ASSERT_THAT(!(sigma > 0.0 && this->mDistanceSigma > 0.0), "a likelihood field or a distance field, not both");
         this->mLikelihoodSigma = sigma;
-        this->mLikelihoodOccupiedMin = occupiedMin;
-        this->mLikelihoodKeepUnknown = keepUnknown;
+        this->mFieldOccupiedMin = occupiedMin;
+        this->mFieldKeepUnknown = keepUnknown;
+        this->mFieldRevisions.clear();
+    }
+    /* OptimizePose on the map's distance field (csm_build_distance_map; beyond the reference): every cell
+     * scores a Gaussian, of the sensor noise sigma in metres, of its distance to the NEAREST obstacle (value
+     * >= occupiedMin) out to `radius` cells, 1..CSM_DISTANCE_MAX_RADIUS (0: ceil(3 sigma / resolution),
+     * clamped), and 1 beyond: a slope over metres where the likelihood field ends at 16 cells. Built under
+     * GridMapView::FieldId(map id, kDistanceIdBit) and kept on the terms of UseLikelihoodField; the two
+     * exclude each other. sigma <= 0 switches it off. */
+    void UseDistanceField(double sigma, int radius = 0, std::uint32_t occupiedMin = 32768, bool keepUnknown = false)
+    {
+        CSM_ASSERT_THAT(!(sigma > 0.0 && this->mLikelihoodSigma > 0.0), "a likelihood field or a distance field, not both");
+        this->mDistanceSigma = sigma;
+        this->mDistanceRadius = radius;
+        this->mFieldOccupiedMin = occupiedMin;
+        this->mFieldKeepUnknown = keepUnknown;
         this->mFieldRevisions.clear();
     }
     /* Both winners of the last OptimizePose under a prior: `unweighted` is what OptimizePose returns
@@ -586,30 +612,62 @@ private:
                                                   normalizedScoreThreshold, knownRateThreshold) };
     }
 
-    /* The likelihood field of the resident map under its id | kLikelihoodIdBit: built when there is none
-     * or when it was built from another revision of the map (a throw-away map: always, and released with it). */
+    /* The field of the resident map (the likelihood field under its id | kLikelihoodIdBit, or the distance
+     * field under FieldId(id, kDistanceIdBit)): built when there is none or when it was built from another
+     * revision of the map (a throw-away map: always, and released with it). */
     std::uint64_t MakeField(const GridMapView& g, detail::ResidentQueryMaps::Use& map)
     {
         csm_ctx* ctx = this->mCtx.get();
         const std::uint64_t id = map.Id();
-        const std::uint64_t fieldId = id | GridMapView::kLikelihoodIdBit;
+        const bool distance = this->mDistanceSigma > 0.0;
+        const std::uint64_t fieldId =
+            distance ? GridMapView::FieldId(id, GridMapView::kDistanceIdBit) : id | GridMapView::kLikelihoodIdBit;
         auto held = this->mFieldRevisions.find(id);
         if (map.Temporary() || !csm_has_grid(ctx, fieldId) || held == this->mFieldRevisions.end() ||
             held->second != g.mRevision) {
-            const int radius = csm_host_likelihood_radius(this->mLikelihoodSigma, g.mResolution);
-            CSM_ASSERT_THAT(radius >= 1, "likelihood sigma and map resolution > 0");
-            std::vector<std::uint32_t> table(static_cast<std::size_t>(radius * radius + 1));
-            CSM_ASSERT_OK(ctx, csm_host_likelihood_kernel(this->mLikelihoodSigma, g.mResolution, radius, table.data()));
-            csm_likelihood_params lp {};
-            lp.radius = radius;
-            lp.occupied_min = this->mLikelihoodOccupiedMin;
-            lp.keep_unknown = this->mLikelihoodKeepUnknown ? 1 : 0;
-            lp.kernel = table.data();
-            CSM_ASSERT_OK(ctx, csm_build_likelihood_map(ctx, id, fieldId, &lp));
+            if (distance)
+                this->BuildDistanceField(g, id, fieldId);
+            else
+                this->BuildLikelihoodField(g, id, fieldId);
             this->mFieldRevisions[id] = g.mRevision;
         }
         map.ReleaseWithIt(fieldId);
         return fieldId;
+    }
+
+    void BuildLikelihoodField(const GridMapView& g, std::uint64_t id, std::uint64_t fieldId)
+    {
+        csm_ctx* ctx = this->mCtx.get();
+        const int radius = csm_host_likelihood_radius(this->mLikelihoodSigma, g.mResolution);
+        CSM_ASSERT_THAT(radius >= 1, "likelihood sigma and map resolution > 0");
+        std::vector<std::uint32_t> table(static_cast<std::size_t>(radius * radius + 1));
+        CSM_ASSERT_OK(ctx, csm_host_likelihood_kernel(this->mLikelihoodSigma, g.mResolution, radius, table.data()));
+        csm_likelihood_params lp {};
+        lp.radius = radius;
+        lp.occupied_min = this->mFieldOccupiedMin;
+        lp.keep_unknown = this->mFieldKeepUnknown ? 1 : 0;
+        lp.kernel = table.data();
+        CSM_ASSERT_OK(ctx, csm_build_likelihood_map(ctx, id, fieldId, &lp));
+    }
+
+    void BuildDistanceField(const GridMapView& g, std::uint64_t id, std::uint64_t fieldId)
+    {
+        csm_ctx* ctx = this->mCtx.get();
+        CSM_ASSERT_THAT(g.mResolution > 0.0, "map resolution > 0");
+        int radius = this->mDistanceRadius;
+        if (radius <= 0) {
+            const double r = std::ceil(3.0 * (this->mDistanceSigma / g.mResolution));
+            radius = r < 1.0 ? 1 : r > CSM_DISTANCE_MAX_RADIUS ? CSM_DISTANCE_MAX_RADIUS : static_cast<int>(r);
+        }
+        CSM_ASSERT_THAT(radius <= CSM_DISTANCE_MAX_RADIUS, "distance field radius at most %d", CSM_DISTANCE_MAX_RADIUS);
+        std::vector<std::uint16_t> table(static_cast<std::size_t>(radius * radius + 1));
+        CSM_ASSERT_OK(ctx, csm_host_distance_kernel(this->mDistanceSigma, g.mResolution, radius, 65534, 1, table.data()));
+        csm_distance_params dp {};
+        dp.radius = radius;
+        dp.occupied_min = this->mFieldOccupiedMin;
+        dp.keep_unknown = this->mFieldKeepUnknown ? 1 : 0;
+        dp.table = table.data();
+        CSM_ASSERT_OK(ctx, csm_build_distance_map(ctx, id, fieldId, &dp));
     }
 
     const std::string mName;
@@ -625,8 +683,10 @@ private:
     csm_motion_prior mPrior {};
     csm_prior_result mLastPrior {};
     double mLikelihoodSigma = 0.0;
-    std::uint32_t mLikelihoodOccupiedMin = 32768;
-    bool mLikelihoodKeepUnknown = false;
+    double mDistanceSigma = 0.0;
+    int mDistanceRadius = 0;
+    std::uint32_t mFieldOccupiedMin = 32768;       /* of the field in use, of either kind */
+    bool mFieldKeepUnknown = false;
     detail::RevisionMap mFieldRevisions;       /* the map revision each resident field was built from */
 };
 
